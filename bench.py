@@ -4,7 +4,7 @@
 Metric (BASELINE.json): Mrays/s (+ achieved GB/s against the memory roofline),
 cornell_dragon 1920x1080, depth 4, reference sphere room, 1/2/4/8 GPUs.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -83,6 +83,9 @@ def parse():
                     help="do not collect HBM traffic live (child runs of this script under rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)   # the run rocprofv3 wraps: timed steps only
     ap.add_argument("--big-parity-spp", type=int, default=2, help="samples of the big scene's in-run parity frame against the oracle (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float32, at most 64 MB in all; same arguments = same inputs, for output-for-output comparison of two builds)")
     ap.add_argument("--rehearse", action="store_true",
                     help="N>1 dry run on a ONE-GPU box: every rank uses cuda:0, gloo backend, stripes gathered "
                          "through host memory (validates the multi-rank code path, not its speed)")
@@ -210,6 +213,30 @@ def pmc_live(kernel_family, extra_args, timeout=240):
     fs, ws = out["FETCH_SIZE"][0], out["WRITE_SIZE"][0]
     return {"fetch_bytes_raw": int(fs), "fetch_bytes_x2": int(2 * fs), "write_bytes": int(ws), "hbm_bytes_per_launch": int(fs + ws),
             "launches_profiled": out["FETCH_SIZE"][1], "source": "live: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE child runs of this bench, same sources"}
+
+
+DUMP_BUDGET = 64 * 2 ** 20
+
+
+def dump_outputs(directory, accum, rgba):
+    """The frame of the last timed step as a caller of pt_render receives it: `accum` [H][W][3] float32 (the running
+    mean) and the display words uint32 [H][W] (0x00BBGGRR), unpacked into their R, G, B bytes as float32.  When both
+    together exceed DUMP_BUDGET, a fixed sample of pixels (seed 0, sorted) is kept, and its flat pixel indices are
+    written beside as `pixel_index` (float64, exact).  Returns {name: shape}."""
+    os.makedirs(directory, exist_ok=True)
+    H, W = rgba.shape
+    words = np.ascontiguousarray(rgba).view(np.uint32)
+    rgb8 = np.stack([(words >> (8 * c)) & 0xFF for c in range(3)], axis=-1).astype(np.float32)
+    arrays = {"accum": np.ascontiguousarray(accum, dtype=np.float32), "rgba8": rgb8}
+    per_pixel = sum(v[0, 0].nbytes for v in arrays.values())
+    if per_pixel * H * W > DUMP_BUDGET:
+        n = (DUMP_BUDGET - 4096) // (per_pixel + 8)
+        idx = np.sort(np.random.default_rng(0).choice(H * W, size=n, replace=False))
+        arrays = {k: v.reshape(H * W, -1)[idx] for k, v in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    for name, v in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), v)
+    return {name: list(v.shape) for name, v in arrays.items()}
 
 
 def spawn_ranks(a):
@@ -417,6 +444,13 @@ def main():
         step(k)
     step_ms = []
     dt = timed(a.steps, a.warmup, per_step=step_ms)
+    dumped = None
+    if a.dump_outputs:   # before anything below renders into the same buffers again
+        acc_full = accum.cpu() if a.rehearse else accum.clone()
+        if use_dist:   # every rank holds its own stripes of the accumulator; the display words are on rank 0 already
+            tile_split.gather_stripes(acc_full, layout, dst=0, force=a.force_dist)
+        if rank == 0:
+            dumped = dump_outputs(a.dump_outputs, acc_full[:H].cpu().numpy(), last_frame()[:H].cpu().numpy())
     if a.pmc_child:   # the run rocprofv3 wraps (pmc_live): nothing but the timed steps
         if rank == 0:
             os.write(json_fd, (json.dumps({"pmc_child": True, "ms_per_step": round(dt / a.steps * 1e3, 4)}) + "\n").encode())
@@ -552,6 +586,8 @@ def main():
             "stage_ms": {k: round(v, 4) for k, v in stage.items() if v > 0},
         }
         out.update(extra)
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         # ---------------------------------------------------------------- roofline of the dominant kernel
         # units: one launch of the dominant kernel.  PT_KERNEL_WAVEFRONT launches k_wf_extend once per bounce
         # (`depth` launches per step); the other frame kernels are one launch per step.

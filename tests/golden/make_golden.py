@@ -10,6 +10,8 @@
                         cornell + sphere room): regression vectors for oracle AND HIP.
   oracle_kat.npz        RNG / sincos / pow / camera-ray known answers of the oracle.
   cornell_compact.npz   our flatten of cornell.obj in the reference's Compact layout.
+  ref_config1_cornell.npz  BASELINE.json configs[0] (cornell 256x256 1 spp) rendered by
+                        oracle/_ref: its path / segment counts, image mean and 16x16 block means.
 The oracle has no reference-provided vectors to pin its radiance against (the reference has
 no tests and its RNG is cuRAND): see the PARITY STATUS note in oracle/pt_oracle.c.
 """
@@ -164,8 +166,21 @@ def make_ref_render():
     print("reference room radiance:", r.stdout.strip().splitlines()[-1], "block means", blocks.mean(axis=-1).round(3).tolist())
 
 
+def make_ref_config1():
+    if not os.path.exists(orc.REF_BIN):
+        print("skip ref_config1_cornell (needs oracle/_ref)")
+        return
+    with tempfile.TemporaryDirectory() as td:
+        j, img = orc.run_ref_config1(td)
+    np.savez_compressed(os.path.join(HERE, "ref_config1_cornell.npz"), blocks=orc.config1_blocks(img),
+                        mean=np.float64(img.mean(dtype=np.float64)), json_mean=np.float64(j["mean"]),
+                        paths=np.int64(j["paths"]), segments=np.int64(j["segments"]), finite=np.bool_(np.isfinite(img).all()))
+    print("reference config 1:", j)
+
+
 if __name__ == "__main__":
     make_ref_render()
+    make_ref_config1()
     make_ref_hits()
     make_oracle_images()
     make_kat()

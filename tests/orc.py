@@ -180,3 +180,41 @@ def random_rays(n, lo, hi, seed=1234):
     rays[:, 0:3] = o
     rays[:, 4:7] = d
     return rays
+
+
+# ---- BASELINE.json configs[0] through oracle/_ref (the reference's CpuRayTracer classes) -----------------------------
+CONFIG1_W = CONFIG1_H = 256
+CONFIG1_BLOCK = 16
+
+
+def config1_mesh():
+    """cornell.obj scaled into main.cpp's room: 3 units, z-up, standing on the z = 0 floor (float64, as written to .obj)."""
+    mesh = g.scene_mesh("cornell")
+    v, f = mesh.verts.astype(np.float64), mesh.tris
+    lo, hi = v.min(0), v.max(0)
+    v = (v - 0.5 * (lo + hi)) * (3.0 / float(np.max(hi - lo)))
+    v = np.stack([v[:, 0], -v[:, 2], v[:, 1]], -1)
+    v[:, 2] -= v[:, 2].min()
+    return v, f
+
+
+def run_ref_config1(tmp_dir):
+    """cornell 256x256 1 spp through oracle/_ref; returns (its JSON line as a dict, the float32 image).  Deterministic:
+    the image does not depend on the thread count."""
+    import json
+    v, f = config1_mesh()
+    obj, out = os.path.join(tmp_dir, "cornell.obj"), os.path.join(tmp_dir, "img.f32")
+    with open(obj, "w") as fh:
+        fh.write("o cornell\n")
+        np.savetxt(fh, v, fmt="v %.6f %.6f %.6f")
+        np.savetxt(fh, f + 1, fmt="f %d %d %d")
+    r = subprocess.run([REF_BIN, "render", obj, str(CONFIG1_W), str(CONFIG1_H), "1", "0", "0", "0", out],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-300:]
+    j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    return j, np.fromfile(out, np.float32).reshape(CONFIG1_H, CONFIG1_W, 3)
+
+
+def config1_blocks(img):
+    B = CONFIG1_BLOCK
+    return img.reshape(CONFIG1_H // B, B, CONFIG1_W // B, B, 3).mean(axis=(1, 3), dtype=np.float64).astype(np.float32)

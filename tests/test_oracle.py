@@ -258,30 +258,38 @@ def test_partition_is_bit_identical():
 
 def test_config1_cornell_256_through_the_reference_cpu_tracer(tmp_path):
     """BASELINE.json configs[0], literally: cornell.obj 256x256 1 spp through the reference's own CpuRayTracer classes on
-    the host CPU (oracle/_ref = Scene / Mesh / KDNode / Material compiled from /root/reference; plumbing, no GPU).  The
-    render loop is renderer.cpp:197-222's, the room main.cpp:26-35's; every camera ray is one path, the segment counter
-    sits in front of the mesh (a forwarding Object), and the image is finite and lit."""
-    import json
-    import subprocess
-    if not os.path.exists(orc.REF_BIN):
-        pytest.skip("oracle/_ref not built (needs /root/reference at build time)")
-    mesh = g.scene_mesh("cornell")
-    v, f = mesh.verts.astype(np.float64), mesh.tris
-    lo, hi = v.min(0), v.max(0)
-    v = (v - 0.5 * (lo + hi)) * (3.0 / float(np.max(hi - lo)))     # into the room: 3 units, z-up, on the floor
-    v = np.stack([v[:, 0], -v[:, 2], v[:, 1]], -1)
-    v[:, 2] -= v[:, 2].min()
-    obj, out = tmp_path / "cornell.obj", tmp_path / "img.f32"
-    with open(obj, "w") as fh:
-        fh.write("o cornell\n")
-        np.savetxt(fh, v, fmt="v %.6f %.6f %.6f")
-        np.savetxt(fh, f + 1, fmt="f %d %d %d")
-    r = subprocess.run([orc.REF_BIN, "render", str(obj), "256", "256", "1", "0", "0", "0", str(out)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-300:]
-    j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
-    img = np.fromfile(out, np.float32).reshape(256, 256, 3)
-    assert j["paths"] == 256 * 256 and j["segments"] >= j["paths"]
-    assert np.isfinite(img).all() and 0.05 < img.mean() < 2.2 and abs(img.mean() - j["mean"]) < 1e-4
+    the host CPU (oracle/_ref = Scene / Mesh / KDNode / Material compiled from the reference's sources; plumbing, no GPU).
+    The render loop is renderer.cpp:197-222's, the room main.cpp:26-35's; every camera ray is one path, the segment
+    counter sits in front of the mesh (a forwarding Object), and the image is finite and lit.  That run is stored in
+    tests/golden/ref_config1_cornell.npz (tests/golden/make_golden.py); where oracle/_ref is built, a fresh run must
+    reproduce it exactly.  The oracle, switched to that renderer's estimator (PT_FLAGS_CPU_TRACER), is held to its
+    global mean: loosely, since the reference's skewed lobe (see test_reference_radiance.py) darkens the box's walls."""
+    z = np.load(os.path.join(GOLD, "ref_config1_cornell.npz"))
+    if os.path.exists(orc.REF_BIN):
+        j, img = orc.run_ref_config1(str(tmp_path))
+        assert j["paths"] == int(z["paths"]) and j["segments"] == int(z["segments"])
+        assert abs(j["mean"] - float(z["json_mean"])) < 1e-6
+        assert bool(np.isfinite(img).all()) == bool(z["finite"])
+        assert img.mean(dtype=np.float64) == float(z["mean"])
+        assert np.array_equal(orc.config1_blocks(img), z["blocks"])
+    W, H = orc.CONFIG1_W, orc.CONFIG1_H
+    assert int(z["paths"]) == W * H and int(z["segments"]) >= int(z["paths"])
+    assert bool(z["finite"]) and 0.05 < float(z["mean"]) < 2.2 and abs(float(z["mean"]) - float(z["json_mean"])) < 1e-4
+    assert z["blocks"].shape == (H // orc.CONFIG1_BLOCK, W // orc.CONFIG1_BLOCK, 3)
+    assert abs(float(z["blocks"].mean(dtype=np.float64)) - float(z["mean"])) < 1e-5
+
+    import test_reference_radiance as rr
+    _, _, spheres, cam, q = rr.room()                       # main.cpp's room and camera, emission x EMISSION_SCALE
+    v, f = orc.config1_mesh()
+    v = np.loadtxt([f"{x:.6f} {y:.6f} {w:.6f}" for x, y, w in v])   # the vertices exactly as the .obj holds them
+    cam.aspect = W / H
+    p = g.default_params(W, H, depth=64)
+    p.flags, p.cull_backfaces, p.tri_mat = q.flags, q.cull_backfaces, q.tri_mat
+    p.bk_color[:], p.tri_col[:], p.tri_emi[:] = q.bk_color, q.tri_col, q.tri_emi
+    acc, _, _ = orc.render(g.Bvh(g.Mesh.from_arrays(v.astype(np.float32), f)), spheres, cam, p, spp=16, want_rgba=False)
+    r = float(acc.mean(dtype=np.float64)) / rr.EMISSION_SCALE / float(z["mean"])
+    print(f"oracle / reference global mean, config 1: {r:.4f}")
+    assert 0.98 < r < 1.10
 
 
 def test_arbiter_sample_pixels_matches_render_and_brute_force():
