@@ -226,6 +226,7 @@ int build_bvh_impl(pt_ctx* c, const float* verts, size_t n_verts, const int32_t*
     HIP_TRY(c, hipEventElapsedTime(&c->build_ms, e0, e1));
     if (stats[3] > 64) return fail(c, PT_ERR_UNSUPPORTED, "pt_build_bvh: tree deeper than 64 levels (degenerate input); use the host builder");
 
+    refit_release(c);
     (void)hipFree(c->d_nodes);
     c->d_nodes = items;
     guard.p = nullptr;

@@ -30,6 +30,7 @@ struct pt_ctx {
     int32_t* d_light_slot = nullptr;
     float4* d_tri_lights = nullptr;
     uint64_t mat_gen = 0, lights_key = ~0ull;
+    uint64_t lights_geom = 0;          // the refit generation (geom_gen) the light list was collected at
     // the light list is (re)written on the caller's stream; a side stream (PT_OPT_OVERLAP) waits for lights_ev before its
     // first kernel that may read that generation of the list
     hipEvent_t lights_ev = nullptr;
@@ -96,6 +97,23 @@ struct pt_ctx {
     int pick_last = -1;          // entry of the last PT_KERNEL_AUTO call (pt_auto_choice), -1 = none
     uint64_t pick_tick = 0;
     uint64_t scene_gen = 0;      // bumped by every upload / build
+    // pt_refit_bvh: the boxes and records of the tree are rewritten on the caller's stream; geom_gen counts the refits and a side
+    // stream (PT_OPT_OVERLAP) waits for geom_ev before its first path kernel after one (the light list is re-collected too)
+    uint64_t geom_gen = 0;
+    hipEvent_t geom_ev = nullptr;
+    // what the refit of one tree needs on the device, made by its first refit (pt_refit.hip) and released with the tree
+    struct Refit {
+        uint64_t scene_gen = 0;
+        const float4* items = nullptr;           // the tree it was made for: (scene_gen, item buffer)
+        void* d_mem = nullptr;                   // one allocation: the lists and scratch below
+        int4* bin_list = nullptr;                // binary nodes by height: {node, records of leaf child 0 (0: inner), of child 1, 0}
+        int4* wide_list = nullptr;               // wide nodes by height: {slot, children, records of 0 | 1 << 16, of 2 | 3 << 16}
+        float* bin_box = nullptr;                // [n_inner][6] exact union of a binary node's triangles (lo > hi: all dropped)
+        float* wide_box = nullptr;               // [n_wide][6] the same per wide node
+        float* rec_box = nullptr;                // [n_refs][6] triangle box of every record
+        uint32_t* first_use = nullptr;           // bit per record: the first record of its triangle (counts a dropped triangle once)
+        std::vector<uint32_t> bin_off, wide_off; // list offsets per height (size heights + 1)
+    } refit;
     // Overlap of consecutive calls (PT_OPT_OVERLAP, persistent / mega kernels): the path kernel of call k + 1 runs on
     // a side stream into its own sample buffer while call k's last paths drain; only the folds (which touch the
     // accumulator, in order) stay on the caller's stream.  side[x]: stream, sample buffer, queue counters of slot x.
@@ -108,6 +126,7 @@ struct pt_ctx {
         size_t samples_bytes = 0;
         unsigned int* queue = nullptr;
         uint64_t lights_seen = 0;   // the light list generation this stream has been ordered behind (lights_gen)
+        uint64_t geom_seen = 0;     // the refit generation this stream has been ordered behind (geom_gen)
     } side[2];
     int side_next = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -183,6 +202,8 @@ int stage_mark(pt_ctx* c, int kind_of_work_since_last_mark);
 // device BVH builder (pt_build.hip)
 int build_bvh_impl(pt_ctx* c, const float* verts, size_t n_verts, const int32_t* tris, size_t n_tris, int algo, bool* too_deep,
                    const int32_t* id_map = nullptr);
+// pt_refit_bvh's per-tree state (pt_refit.hip): released wherever the tree is replaced or the context destroyed
+void refit_release(pt_ctx* c);
 
 }  // namespace ptmi
 

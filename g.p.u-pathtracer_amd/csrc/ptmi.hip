@@ -109,6 +109,7 @@ static int install_tree(pt_ctx* c, ptscene::Tree& X, int32_t max_id) {
     if ((nb + tb + wb) / 16 >= (size_t)PT_SENTINEL) return fail(c, PT_ERR_INVALID, "pt_upload_bvh: scene too large for 32-bit links");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    refit_release(c);
     (void)hipFree(c->d_nodes); c->d_nodes = nullptr;
     c->d_tris = nullptr;
     c->has_bvh = false;
@@ -206,6 +207,7 @@ int pt_destroy(pt_ctx* c) {
     (void)hipFree(c->d_queue);
     (void)hipFree(c->d_samples);
     (void)hipFree(c->d_wave);
+    refit_release(c);
     for (pt_ctx::Side& s : c->side) {
         if (s.stream) (void)hipStreamSynchronize(s.stream);
         (void)hipFree(s.samples);
@@ -218,6 +220,7 @@ int pt_destroy(pt_ctx* c) {
     for (pt_ctx::AutoPick& a : c->picks)
         for (hipEvent_t e : a.e) if (e) (void)hipEventDestroy(e);
     if (c->lights_ev) (void)hipEventDestroy(c->lights_ev);
+    if (c->geom_ev) (void)hipEventDestroy(c->geom_ev);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -439,6 +442,7 @@ int pt_upload_bvh(pt_ctx* c, const float* nodes, size_t n_node_vec4, const float
             c->opt_cost[0] = mine_opt[0]; c->opt_cost[1] = mine_opt[1];
             c->err.clear();
         }
+        refit_release(c);   // made for neither tree (pt_refit_bvh makes it again for the one kept)
         c->scene_gen++;
     }
     return PT_OK;
@@ -616,13 +620,14 @@ int pt_render(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, const pt_camera* 
     if ((p->flags & PT_FLAG_NEE) && c->has_bvh && !c->emissive_ids.empty()) {
         if (c->records_woop) return fail(c, PT_ERR_UNSUPPORTED, "pt_render: PT_FLAG_NEE over emissive triangles needs the exact (Moller-Trumbore) records");
         const uint64_t key = (c->scene_gen << 32) ^ c->mat_gen;
-        if (c->lights_key != key) {   // the scene or the materials changed: copy the lights' vertices out of the records again
+        if (c->lights_key != key || c->lights_geom != c->geom_gen) {   // the scene, its geometry (pt_refit_bvh) or the materials changed: copy the lights' vertices out of the records again
             const uint32_t n_rec = (uint32_t)c->n_refs;
             HIP_TRY(c, hipMemsetAsync(c->d_tri_lights, 0, c->emissive_ids.size() * 3 * sizeof(float4), c->stream));
             hipLaunchKernelGGL(k_collect_tri_lights, dim3((n_rec + 255) / 256), dim3(256), 0, c->stream, c->d_nodes + 4 * (size_t)c->n_inner, n_rec,
                                c->d_light_slot, (uint32_t)c->n_tri_matid, c->d_tri_matid, c->d_mat_table, c->d_tri_lights);
             HIP_TRY(c, hipGetLastError());
             c->lights_key = key;
+            c->lights_geom = c->geom_gen;
             // a path kernel on a side stream (PT_OPT_OVERLAP) must not read the list before it is written
             if (!c->lights_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->lights_ev, hipEventDisableTiming));
             HIP_TRY(c, hipEventRecord(c->lights_ev, c->stream));
@@ -774,6 +779,10 @@ int pt_render(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, const pt_camera* 
         if (P.tri_lights && sd->lights_seen != c->lights_gen) {   // the light list was (re)written on the caller's stream
             HIP_TRY(c, hipStreamWaitEvent(sd->stream, c->lights_ev, 0));
             sd->lights_seen = c->lights_gen;
+        }
+        if (sd->geom_seen != c->geom_gen) {   // the tree was refit on the caller's stream (pt_refit_bvh)
+            HIP_TRY(c, hipStreamWaitEvent(sd->stream, c->geom_ev, 0));
+            sd->geom_seen = c->geom_gen;
         }
     }
 

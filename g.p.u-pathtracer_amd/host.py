@@ -69,6 +69,10 @@ class Mesh:
         p = _abi.pthost().pth_mesh_tris(self._h)
         return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int32)), (self.n_tris, 3)).copy()
 
+    def triangle_soup(self):
+        """float32 [n_tris, 9]: v0, v1, v2 of every triangle, row = triangle id (what PathTracer.refit_bvh takes)."""
+        return np.ascontiguousarray(self.verts[self.tris.astype(np.int64)].reshape(self.n_tris, 9))
+
     # per-triangle materials (extension; OBJ `usemtl` + .mtl, or PTMESH2 fixtures)
     @property
     def materials(self):

@@ -68,6 +68,9 @@ class PathTracer:
 
     def close(self):
         if getattr(self, "_ctx", None):
+            if getattr(self, "_refit_buf", None) is not None:
+                self._refit_buf.free()
+                self._refit_buf = None
             self._lib.pt_destroy(self._ctx)
             self._ctx = None
 
@@ -112,6 +115,31 @@ class PathTracer:
         ms = C.c_float()
         self._check(self._lib.pt_last_build_ms(self._ctx, C.byref(ms)))
         return ms.value
+
+    def refit_bvh(self, tri_verts, n_tris=None, n_dropped=None):
+        """Move the triangles of the tree on the context (pt_refit_bvh; extension): the hierarchy keeps its topology, every
+        box is refit on the device.  tri_verts: float32 rows v0, v1, v2 by original triangle id, as a DeviceBuffer or a raw
+        device pointer (n_tris rows; a DeviceBuffer's size gives it when omitted), or a host numpy array of shape (n, 9) or
+        (n, 3, 3), staged through a device buffer the tracer owns.  n_dropped: a DeviceBuffer or device pointer that
+        receives the uint32 count of dropped (non-finite) triangles.  Asynchronous like launch_kernel."""
+        if isinstance(tri_verts, np.ndarray):
+            a = np.ascontiguousarray(tri_verts)
+            if a.dtype != np.float32 or a.ndim not in (2, 3) or a.shape[1:] not in ((9,), (3, 3)):
+                raise ValueError("refit_bvh: a float32 array of shape (n, 9) or (n, 3, 3) expected")
+            if getattr(self, "_refit_buf", None) is None or self._refit_buf.nbytes < a.nbytes:
+                if getattr(self, "_refit_buf", None) is not None:
+                    self._refit_buf.free()
+                self._refit_buf = DeviceBuffer(self, max(a.nbytes, 36))
+            self._refit_buf.upload(a)
+            ptr, n = self._refit_buf.ptr, len(a)
+        elif isinstance(tri_verts, DeviceBuffer):
+            ptr, n = tri_verts.ptr, tri_verts.nbytes // 36 if n_tris is None else n_tris
+        else:
+            if n_tris is None:
+                raise ValueError("refit_bvh: a raw device pointer needs n_tris")
+            ptr, n = tri_verts, n_tris
+        nd = n_dropped.ptr if isinstance(n_dropped, DeviceBuffer) else n_dropped
+        self._check(self._lib.pt_refit_bvh(self._ctx, ptr, int(n), nd))
 
     def upload_tri_materials(self, table, tri_material):
         """Per-triangle materials (extension): `table` = sequence of Material, `tri_material` =

@@ -309,6 +309,26 @@ int pt_build_bvh(pt_ctx* ctx, const float* verts, size_t n_verts, const int32_t*
 int pt_last_build_ms(pt_ctx* ctx, float* ms_out);   /* device time of the build behind the tree on the context (pt_build_bvh or a
                                                        kept PT_OPT_REBUILD tree); PT_ERR_INVALID for an uploaded hierarchy */
 
+/* Move the triangles of the scene on the context — an EXTENSION (an update / refit operation): the hierarchy keeps its
+ * topology and every box is refit on the device, so an optimised tree (PT_OPT_OPTIMIZE, PT_OPT_REBUILD) survives animation.
+ * tri_verts_dev: float[n_tris][9] = v0, v1, v2 of the triangle whose ORIGINAL id is the row (the ids of the Compact index
+ * array, or the rows of pt_build_bvh's `tris`); device memory (pt_malloc, hipMalloc, a torch tensor).  n_tris must cover
+ * every id of the tree; rows the tree does not reference are ignored.
+ * A triangle with a coordinate that is not finite or has |x| > 3.0e38 (pt_build_bvh's rule) is dropped: it is never hit and
+ * adds nothing to any box.  When n_dropped_dev != NULL, the number of dropped triangles is written there (uint32, device).
+ * Boxes are the min / max of the three vertices, as pt_build_bvh computes them: a refit to the vertices a device tree was
+ * built from reproduces that tree bit for bit.  A spatial-split reference (host SBVH, PT_OPT_PRESPLIT) gets its whole
+ * triangle's box: correct, but looser.  Woop records (PT_OPT_TRI_TEST 1): PT_ERR_UNSUPPORTED.
+ * Asynchronous on the context's stream.  It is ordered after earlier pt_render / pt_trace_rays calls and before later ones,
+ * side streams (PT_OPT_OVERLAP) included.  The first refit of a tree synchronises once: it reads the tree's shape back (links,
+ * ids and leaf flags: 8 bytes per binary node and per record, 16 per wide node) and allocates and uploads the per-height
+ * schedule and scratch boxes, about 24 bytes per record + 40 per binary and per wide node of device memory, held until the
+ * tree is replaced or the context destroyed and not counted in pt_scene_info.  Later refits neither allocate nor synchronise.
+ * With PT_OPT_TIMING=1, pt_last_kernel_ms reports the refit's device time.  pt_scene_info, pt_last_build_ms and the tree's
+ * generation are unchanged.  Every tree this library installs has an inner root (pt_build_bvh doubles a lone triangle); a
+ * tree without the [binary nodes][records][wide nodes] layout would give PT_ERR_UNSUPPORTED. */
+int pt_refit_bvh(pt_ctx* ctx, const float* tri_verts_dev, size_t n_tris, uint32_t* n_dropped_dev);
+
 /* Per-triangle materials — an EXTENSION.  The reference parses the .mtl into
  * `materials` but never reads it (utilfun.cpp:458-462) and shades every triangle with the ONE
  * material of kernelInfo (tracer.cu:131-135 = pt_params.tri_mat/tri_col/tri_emi/phong_expo).

@@ -9,8 +9,8 @@ make -j8 csrc/libptmi.so >/dev/null
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-function -include "$ROOT/tools/pt_exp_hooks.h" "$@" -c -o /tmp/${FAM%.hip}_$TAG.o csrc/$FAM
 OBJS=""
-for o in ptmi pt_build pt_k_mega pt_k_persist pt_k_wave; do
-  if [ "$o.hip" = "$FAM" ]; then OBJS="$OBJS /tmp/${FAM%.hip}_$TAG.o"; else OBJS="$OBJS csrc/$o.o"; fi
+for o in $(make -s objs); do   # the Makefile's list: a new translation unit cannot be left out
+  if [ "$o" = "csrc/${FAM%.hip}.o" ]; then OBJS="$OBJS /tmp/${FAM%.hip}_$TAG.o"; else OBJS="$OBJS $o"; fi
 done
 $HIPCC --offload-arch=gfx950 -fPIC -shared -o csrc/libptmi_$TAG.so $OBJS
 echo csrc/libptmi_$TAG.so
