@@ -35,6 +35,12 @@ class Material(C.Structure):
     _fields_ = [("col", C.c_float * 3), ("emi", C.c_float * 3), ("mat", C.c_int32), ("phong_expo", C.c_float)]
 
 
+class DenoiseParams(C.Structure):
+    """pt_denoise_params — the a-trous filter of pt_denoise (extension, include/ptmi.h; 24 bytes)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32),
+                ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float)]
+
+
 class CheckpointInfo(C.Structure):
     """pth_checkpoint_info (host/pthost.h)."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("next_frame", C.c_uint64),
@@ -101,6 +107,8 @@ PTMI_SYMBOLS = [
     ("pt_upload_spheres", _i, [_vp, C.POINTER(Sphere), _sz]),
     ("pt_render", _i, [_vp, _vp, _vp, C.POINTER(Camera), C.POINTER(Params), _u32]),
     ("pt_trace_rays", _i, [_vp, _vp, _sz, _i, _vp, _vp, _vp]),
+    ("pt_render_aux", _i, [_vp, C.POINTER(Camera), C.POINTER(Params), _vp, _vp, _vp, _vp]),
+    ("pt_denoise", _i, [_vp, C.POINTER(DenoiseParams), _vp, _vp, _vp, _vp, _vp, _vp]),
     ("pt_build_bvh", _i, [_vp, _vp, C.c_size_t, _vp, C.c_size_t]),
     ("pt_last_build_ms", _i, [_vp, C.POINTER(C.c_float)]),
     ("pt_refit_bvh", _i, [_vp, _vp, _sz, _vp]),

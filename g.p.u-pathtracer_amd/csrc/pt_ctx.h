@@ -114,6 +114,9 @@ struct pt_ctx {
         uint32_t* first_use = nullptr;           // bit per record: the first record of its triangle (counts a dropped triangle once)
         std::vector<uint32_t> bin_off, wide_off; // list offsets per height (size heights + 1)
     } refit;
+    // pt_denoise's ping-pong colour frames (pt_denoise.hip): grown on demand, released by pt_destroy
+    void* d_denoise = nullptr;
+    size_t denoise_bytes = 0;
     // Overlap of consecutive calls (PT_OPT_OVERLAP, persistent / mega kernels): the path kernel of call k + 1 runs on
     // a side stream into its own sample buffer while call k's last paths drain; only the folds (which touch the
     // accumulator, in order) stay on the caller's stream.  side[x]: stream, sample buffer, queue counters of slot x.
@@ -204,6 +207,8 @@ int build_bvh_impl(pt_ctx* c, const float* verts, size_t n_verts, const int32_t*
                    const int32_t* id_map = nullptr);
 // pt_refit_bvh's per-tree state (pt_refit.hip): released wherever the tree is replaced or the context destroyed
 void refit_release(pt_ctx* c);
+// pt_denoise's scratch (pt_denoise.hip)
+void denoise_release(pt_ctx* c);
 
 }  // namespace ptmi
 

@@ -1,0 +1,291 @@
+// pt_denoise.hip — pt_render_aux (first-hit guide buffers) and pt_denoise (edge-avoiding a-trous wavelet filter, Dammertz et
+// al. 2010).  One translation unit of libptmi.so (pt_ctx.h).
+//   k_render_aux     one lane per pixel, a 256-thread block per 16x16 tile (one wave per 8x8 quadrant): the pixel-centre camera
+//                    ray, the binary closest-hit walk of pt_trace_rays, the spheres by pt_closest_sphere; albedo, normal,
+//                    position (+ t) as float4 rows, the hit id
+//   k_dn_demod       colour / albedo into ping-pong buffer A as float4 (i, hit) — the hit flag rides in .w, so a tap learns
+//                    whether q is a miss from the colour load it makes anyway
+//   k_dn_iter<LAST>  one launch per iteration, 16x16 tiles: 25 taps, each one dwordx4 load per buffer (colour; normal and
+//                    position only where both ends are hits) and ONE v_exp_f32 (the three terms folded into exp2 with log2(e)
+//                    in the per-launch constants); the last iteration remodulates, clamps, writes out (+ display words)
+//   k_dn_copy        iterations = 0: out = color bit for bit (+ display words)
+// No LDS tile: at step 16 the taps are 64 rows apart, an apron would re-read more than it saves; the packed buffers of a 1080p
+// frame (~100 MB) stay in the 256 MB Infinity Cache.
+#include <cmath>
+#include <cstring>
+
+#include "pt_ctx.h"
+
+#define PTD_TILE 16
+#define PTD_BLOCK (PTD_TILE * PTD_TILE)
+
+namespace {
+
+struct AuxOut {
+    float4* __restrict__ albedo;
+    float4* __restrict__ normal;
+    float4* __restrict__ position;
+    int32_t* __restrict__ id;   // may be null
+};
+
+// KParams first: pt_closest_sphere reads the spheres through the kernel-argument pointer at offset 0 (PT_KARGS)
+__global__ void __launch_bounds__(PT_BLOCK_RAYS) k_render_aux(const KParams P, const AuxOut A) {
+    float4* s_top = s_dyn;
+    lds_load_top<PT_BLOCK_RAYS>(P.sc, s_top);
+    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+    const int px = blockIdx.x * 16 + (wv & 1) * 8 + (lane & 7);
+    const int py = blockIdx.y * 16 + (wv >> 1) * 8 + (lane >> 3);
+    if (px >= P.W || py >= P.H) return;
+    const size_t pix = (size_t)py * (size_t)P.W + (size_t)px;
+    v3 o, d;
+    pt_camera_ray(P.cam, P.W, P.H, px, py, 0.0f, 0.0f, o, d);   // u0 = u1 = 0.5: the pixel centre
+    TravCount tc;
+    tc.inner = tc.tris = tc.leaves = 0;
+    TravOverflow<PT_STACK_CAP> stk_ovf;
+    TravStack<PT_STACK_CAP, PT_BLOCK_RAYS> stk(__builtin_amdgcn_readfirstlane(16 * P.sc.n_top + (tid & ~63)), stk_ovf);
+    const Hit h = trav_bvh2<false, true>(P.sc, o, d, P.cull != 0, stk, tc, s_top);
+    const SceneHit sh = pt_closest_sphere(P, o, d, h);
+    float4 alb = make_float4(0.f, 0.f, 0.f, 0.f), nrm = alb, pos = alb;
+    int32_t id = -1;
+    if (sh.geom != 3) {
+        const v3 hitpos = vmadd(d, sh.t, o);
+        v3 n, col;
+        if (sh.geom == 1) {
+            const pt_sphere_d& s = P.sc.spheres[sh.sph_id];
+            n = vnormalize(vsub(hitpos, V3(s.px, s.py, s.pz)));
+            col = V3(s.col[0], s.col[1], s.col[2]);
+            id = -2 - sh.sph_id;
+        } else {
+            n = vnormalize(pt_hit_normal(P.sc, h));
+            if (P.tri_matid) {
+                const float4 m0 = P.mat_table[2 * P.tri_matid[h.tri]];
+                col = V3(m0.x, m0.y, m0.z);
+            } else {
+                col = V3(P.tri_col[0], P.tri_col[1], P.tri_col[2]);
+            }
+            id = h.tri;
+        }
+        if (!(vdot(n, d) < 0)) n = vscale(n, -1.0f);
+        alb = make_float4(col.x, col.y, col.z, 0.f);
+        nrm = make_float4(n.x, n.y, n.z, 0.f);
+        pos = make_float4(hitpos.x, hitpos.y, hitpos.z, sh.t);
+    }
+    A.albedo[pix] = alb;
+    A.normal[pix] = nrm;
+    A.position[pix] = pos;
+    if (A.id) A.id[pix] = id;
+}
+
+struct DnArgs {
+    const float* color;                   // [H][W][3] (out may alias it)
+    const float4* __restrict__ albedo;
+    const float4* __restrict__ normal;
+    const float4* __restrict__ position;
+    const float4* __restrict__ src;       // ping-pong (i, hit)
+    float4* __restrict__ dst;
+    float* out;                           // [H][W][3], may alias color
+    uint32_t* rgba;                       // may be null
+    int W, H;
+    int step;                             // 2^l
+    float kc, kn, kx;                     // log2(e) / sigma^2 of the three terms (colour: of this iteration), 0 = off
+};
+
+__device__ __forceinline__ float ptd_demod_div(float a) { return a > 1e-3f ? a : 1.0f; }
+__device__ __forceinline__ bool ptd_pixel(const DnArgs& A, int& x, int& y) {
+    x = blockIdx.x * PTD_TILE + (threadIdx.x & (PTD_TILE - 1));
+    y = blockIdx.y * PTD_TILE + (threadIdx.x / PTD_TILE);
+    return x < A.W && y < A.H;
+}
+
+__global__ void __launch_bounds__(PTD_BLOCK) k_dn_demod(const DnArgs A) {
+    int x, y;
+    if (!ptd_pixel(A, x, y)) return;
+    const size_t p = (size_t)y * (size_t)A.W + (size_t)x;
+    const float4 a = A.albedo[p], n = A.normal[p];
+    const float* c = A.color + 3 * p;
+    const bool hit = n.x != 0.f || n.y != 0.f || n.z != 0.f;
+    A.dst[p] = make_float4(c[0] / ptd_demod_div(a.x), c[1] / ptd_demod_div(a.y), c[2] / ptd_demod_div(a.z), hit ? 1.f : 0.f);
+}
+
+__global__ void __launch_bounds__(PTD_BLOCK) k_dn_copy(const DnArgs A) {
+    int x, y;
+    if (!ptd_pixel(A, x, y)) return;
+    const size_t p = (size_t)y * (size_t)A.W + (size_t)x;
+    const float r = A.color[3 * p], g = A.color[3 * p + 1], b = A.color[3 * p + 2];
+    A.out[3 * p] = r; A.out[3 * p + 1] = g; A.out[3 * p + 2] = b;
+    if (A.rgba) A.rgba[p] = pt_pack_rgba(r, g, b);
+}
+
+template <bool LAST>
+__global__ void __launch_bounds__(PTD_BLOCK) k_dn_iter(const DnArgs A) {
+    int x, y;
+    if (!ptd_pixel(A, x, y)) return;
+    const size_t p = (size_t)y * (size_t)A.W + (size_t)x;
+    const float4 cp = A.src[p];
+    const bool hp = cp.w != 0.f;
+    float4 np = make_float4(0.f, 0.f, 0.f, 0.f), xp = np;
+    float kxp = 0.f;
+    if (hp) {
+        np = A.normal[p];
+        xp = A.position[p];
+        kxp = fminf(A.kx / (xp.w * xp.w), 1e30f);   // 1 / (sigma_x t_p)^2, finite
+    }
+    const float hk[5] = {1.f / 16.f, 4.f / 16.f, 6.f / 16.f, 4.f / 16.f, 1.f / 16.f};
+    float sr = 0.f, sg = 0.f, sb = 0.f, sw = 0.f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+        const int yq = y + dy * A.step;
+        if (yq < 0 || yq >= A.H) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const int xq = x + dx * A.step;
+            if (xq < 0 || xq >= A.W) continue;
+            const float hh = hk[dy + 2] * hk[dx + 2];
+            if (dx == 0 && dy == 0) {   // the centre: e = 0
+                sr = fmaf(hh, cp.x, sr); sg = fmaf(hh, cp.y, sg); sb = fmaf(hh, cp.z, sb); sw += hh;
+                continue;
+            }
+            const size_t q = (size_t)yq * (size_t)A.W + (size_t)xq;
+            const float4 cq = A.src[q];
+            if ((cq.w != 0.f) != hp) continue;   // exactly one of p, q is a miss
+            const float dr = cp.x - cq.x, dg = cp.y - cq.y, db = cp.z - cq.z;
+            float e = A.kc * fmaf(db, db, fmaf(dg, dg, dr * dr));
+            if (hp) {
+                const float4 nq = A.normal[q], xq4 = A.position[q];
+                const float ax = np.x - nq.x, ay = np.y - nq.y, az = np.z - nq.z;
+                const float bx = xp.x - xq4.x, by = xp.y - xq4.y, bz = xp.z - xq4.z;
+                e = fmaf(A.kn, fmaf(az, az, fmaf(ay, ay, ax * ax)), e);
+                e = fmaf(kxp, fmaf(bz, bz, fmaf(by, by, bx * bx)), e);
+            }
+            const float w = hh * __builtin_amdgcn_exp2f(-e);   // one v_exp_f32
+            sr = fmaf(w, cq.x, sr); sg = fmaf(w, cq.y, sg); sb = fmaf(w, cq.z, sb); sw += w;
+        }
+    }
+    const float inv = 1.0f / sw;
+    const float r = sr * inv, g = sg * inv, b = sb * inv;
+    if (!LAST) {
+        A.dst[p] = make_float4(r, g, b, cp.w);
+    } else {
+        const float4 a = A.albedo[p];
+        const float o0 = pt_clamp01(r * ptd_demod_div(a.x)), o1 = pt_clamp01(g * ptd_demod_div(a.y)), o2 = pt_clamp01(b * ptd_demod_div(a.z));
+        A.out[3 * p] = o0; A.out[3 * p + 1] = o1; A.out[3 * p + 2] = o2;
+        if (A.rgba) A.rgba[p] = pt_pack_rgba(o0, o1, o2);
+    }
+}
+
+}  // namespace
+
+namespace ptmi {
+
+void denoise_release(pt_ctx* c) {
+    (void)hipFree(c->d_denoise);
+    c->d_denoise = nullptr;
+    c->denoise_bytes = 0;
+}
+
+}  // namespace ptmi
+
+using namespace ptmi;
+
+extern "C" int pt_render_aux(pt_ctx* c, const pt_camera* cam, const pt_params* p, float* albedo_dev, float* normal_dev,
+                             float* position_dev, int32_t* id_dev) {
+    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
+    if (!cam || !p || !albedo_dev || !normal_dev || !position_dev) return fail(c, PT_ERR_INVALID, "pt_render_aux: null argument");
+    if (p->width < 1 || p->height < 1) return fail(c, PT_ERR_INVALID, "pt_render_aux: width and height must be >= 1");
+    if (!c->has_bvh) return fail(c, PT_ERR_NO_SCENE, "pt_render_aux: no BVH uploaded");
+    if (c->records_woop) return fail(c, PT_ERR_UNSUPPORTED, "pt_render_aux: the binary walk reads Moller-Trumbore records (upload with PT_OPT_TRI_TEST 0)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    KParams P;
+    std::memset(&P, 0, sizeof P);
+    P.sc.nodes = c->d_nodes;
+    P.sc.tris = c->d_tris;
+    P.sc.spheres = c->d_spheres;
+    P.sc.n_spheres = c->n_spheres;
+    std::memcpy(P.ksph, c->h_spheres, sizeof P.ksph);
+    P.sc.has_bvh = 1;
+    P.sc.stack_n = PT_STACK_CAP;
+    P.sc.top_base = 0;
+    P.sc.wide_root = (int)c->wide_root;
+    P.sc.n_top = (int)std::min<uint32_t>((uint32_t)c->opt_top, c->n_top_layout);
+    size_t lds = lds_bytes(P.sc.n_top, P.sc.stack_n, PT_BLOCK_RAYS);
+    while (lds > 160 * 1024 && P.sc.n_top > 0) { P.sc.n_top /= 2; lds = lds_bytes(P.sc.n_top, P.sc.stack_n, PT_BLOCK_RAYS); }
+    P.cam = *cam;
+    P.W = p->width; P.H = p->height;
+    P.cull = p->cull_backfaces;
+    for (int i = 0; i < 3; i++) P.tri_col[i] = p->tri_col[i];
+    P.tri_matid = c->d_tri_matid;
+    P.mat_table = c->d_mat_table;
+    AuxOut A;
+    A.albedo = (float4*)albedo_dev;
+    A.normal = (float4*)normal_dev;
+    A.position = (float4*)position_dev;
+    A.id = id_dev;
+    HIP_TRY(c, allow_lds(k_render_aux, lds));
+    if (c->opt_timing) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    const dim3 grid((unsigned)((p->width + 15) / 16), (unsigned)((p->height + 15) / 16));
+    hipLaunchKernelGGL(k_render_aux, grid, dim3(PT_BLOCK_RAYS), lds, c->stream, P, A);
+    HIP_TRY(c, hipGetLastError());
+    if (c->opt_timing) { HIP_TRY(c, hipEventRecord(c->ev1, c->stream)); c->timed = true; }
+    return PT_OK;
+}
+
+extern "C" int pt_denoise(pt_ctx* c, const pt_denoise_params* dp, const float* color_dev, const float* albedo_dev,
+                          const float* normal_dev, const float* position_dev, float* out_dev, uint32_t* rgba_dev) {
+    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
+    if (!dp || !color_dev || !albedo_dev || !normal_dev || !position_dev || !out_dev) return fail(c, PT_ERR_INVALID, "pt_denoise: null argument");
+    if (dp->width < 1 || dp->height < 1) return fail(c, PT_ERR_INVALID, "pt_denoise: width and height must be >= 1");
+    if (dp->iterations < 0 || dp->iterations > 10) return fail(c, PT_ERR_INVALID, "pt_denoise: iterations must be 0..10");
+    if (!std::isfinite(dp->sigma_color) || !std::isfinite(dp->sigma_normal) || !std::isfinite(dp->sigma_position))
+        return fail(c, PT_ERR_INVALID, "pt_denoise: a sigma is not finite");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n_pix = (size_t)dp->width * (size_t)dp->height;
+    DnArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.color = color_dev;
+    A.albedo = (const float4*)albedo_dev;
+    A.normal = (const float4*)normal_dev;
+    A.position = (const float4*)position_dev;
+    A.out = out_dev;
+    A.rgba = rgba_dev;
+    A.W = dp->width; A.H = dp->height;
+    const dim3 grid((unsigned)((dp->width + PTD_TILE - 1) / PTD_TILE), (unsigned)((dp->height + PTD_TILE - 1) / PTD_TILE));
+    const int L = dp->iterations;
+    float4* ping[2] = {nullptr, nullptr};
+    if (L > 0) {
+        const size_t need = 2 * n_pix * sizeof(float4);
+        if (need > c->denoise_bytes) {   // the old buffers may still be read by an earlier call's launches
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            denoise_release(c);
+            HIP_TRY(c, hipMalloc(&c->d_denoise, need));
+            c->denoise_bytes = need;
+        }
+        ping[0] = (float4*)c->d_denoise;
+        ping[1] = ping[0] + n_pix;
+    }
+    // log2(e) / sigma^2, in double; a term with sigma <= 0 is off (0); capped so that 0 x constant stays 0
+    auto k_of = [](double sigma, double scale) -> float {
+        if (!(sigma > 0.0)) return 0.f;
+        return (float)std::min(1.4426950408889634 * scale / (sigma * sigma), 1e30);
+    };
+    hipStream_t st = c->stream;
+    if (c->opt_timing) HIP_TRY(c, hipEventRecord(c->ev0, st));
+    if (L == 0) {
+        hipLaunchKernelGGL(k_dn_copy, grid, dim3(PTD_BLOCK), 0, st, A);
+    } else {
+        A.dst = ping[0];
+        hipLaunchKernelGGL(k_dn_demod, grid, dim3(PTD_BLOCK), 0, st, A);
+        A.kn = k_of(dp->sigma_normal, 1.0);
+        A.kx = k_of(dp->sigma_position, 1.0);
+        for (int l = 0; l < L; l++) {
+            A.step = 1 << l;
+            A.kc = k_of(dp->sigma_color, std::ldexp(1.0, 2 * l));   // (sigma_c 2^-l)^2 = sigma_c^2 / 4^l
+            A.src = ping[l & 1];
+            A.dst = ping[(l + 1) & 1];
+            if (l + 1 < L) hipLaunchKernelGGL(k_dn_iter<false>, grid, dim3(PTD_BLOCK), 0, st, A);
+            else hipLaunchKernelGGL(k_dn_iter<true>, grid, dim3(PTD_BLOCK), 0, st, A);
+        }
+    }
+    HIP_TRY(c, hipGetLastError());
+    if (c->opt_timing) { HIP_TRY(c, hipEventRecord(c->ev1, st)); c->timed = true; }
+    return PT_OK;
+}

@@ -50,6 +50,19 @@ __device__ __forceinline__ void path_begin_hashed(const KParams& P, int px, int 
     ps.depth = 0;
     ps.nee_mask = 0;
 }
+// The same camera ray for an explicit camera and sub-pixel offset (jx, jy in -0.5 .. 0.5; 0 = the pixel centre), same
+// arithmetic in the same order.  path_begin_hashed keeps its own copy: it reads the camera through the kernel-argument
+// pointer where it is used, which the persistent loop's register budget depends on.
+__device__ __forceinline__ void pt_camera_ray(const pt_camera& cam, int W, int H, int px, int py, float jx, float jy, v3& o, v3& d) {
+    const float xs = ((((float)px - (float)W / 2.0f) + 0.5f) + jx) * cam.dist * cam.aspect * cam.fov / (float)(W - 1);
+    const float ys = ((((float)py - (float)H / 2.0f) + 0.5f) + jy) * cam.dist * cam.fov / (float)(H - 1);
+    const v3 front = V3(cam.front[0], cam.front[1], cam.front[2]);
+    const v3 right = V3(cam.right[0], cam.right[1], cam.right[2]);
+    const v3 up = V3(cam.up[0], cam.up[1], cam.up[2]);
+    const v3 dir0 = vmadd(up, ys, vmadd(right, xs, vscale(front, cam.dist)));
+    o = vadd(V3(cam.pos[0], cam.pos[1], cam.pos[2]), dir0);
+    d = vnormalize(dir0);
+}
 __device__ __forceinline__ void path_begin(const KParams& P, int px, int py, uint64_t pix, uint64_t frame, PathState& ps) {
     path_begin_hashed(P, px, py, pix, pt_wang64(frame), ps);
 }

@@ -208,6 +208,7 @@ int pt_destroy(pt_ctx* c) {
     (void)hipFree(c->d_samples);
     (void)hipFree(c->d_wave);
     refit_release(c);
+    denoise_release(c);
     for (pt_ctx::Side& s : c->side) {
         if (s.stream) (void)hipStreamSynchronize(s.stream);
         (void)hipFree(s.samples);

@@ -7,7 +7,8 @@
 // Usage: pt_app --mesh assets/cornell.ptmesh [--width 1280 --height 720 --frames 16 --spp 1
 //               --depth 4 --mat 0..3 --no-spheres --no-materials --bk r g b --device 0
 //               --out image.ppm|.png|.pfm  --checkpoint state.ckpt [--checkpoint-every N]
-//               --resume state.ckpt --device-build --fix-estimators --nee --gpus N --tile ROWS]
+//               --resume state.ckpt --device-build --fix-estimators --nee --gpus N --tile ROWS
+//               --denoise-out image.ppm|.png|.pfm]
 // --gpus N splits the framebuffer over N contexts, one per GPU (devices device, device+1, ... modulo the number
 // present, so N > 1 also runs on a one-GPU box): stripes of --tile rows (default 8) are dealt round-robin
 // (pt_params.part_*), every context holds the whole scene and renders only its stripes of every frame — the random
@@ -20,6 +21,9 @@
 // A mesh that carries materials (OBJ usemtl + .mtl, PTMESH2) is shaded with them
 // (pt_upload_tri_materials) unless --no-materials.  --resume continues a checkpointed
 // progressive render: the result is bit-identical to one uninterrupted run.
+// --denoise-out also writes the final accumulator through pt_denoise (guides from pt_render_aux, the library's default
+// filter settings), format by extension as --out; with --gpus N the gathered frame is denoised on the first context.
+// --out is written first and is the same image with or without it.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -37,7 +41,7 @@ static int die(const char* what, const char* msg) {
 }
 
 int main(int argc, char** argv) {
-    std::string mesh_path, out_path, ckpt_path, resume_path;
+    std::string mesh_path, out_path, ckpt_path, resume_path, denoise_path;
     int W = 1280, H = 720, frames = 16, depth = 4, mat = PT_MAT_DIFF, device = 0, spp = 1, ckpt_every = 0, gpus = 1, tile = 8;
     bool spheres = true, use_materials = true, device_build = false, fix_estimators = false, nee = false;
     float bk[3] = {1.f, 1.f, 1.f};
@@ -49,6 +53,7 @@ int main(int argc, char** argv) {
         };
         if (a == "--mesh") mesh_path = next("--mesh");
         else if (a == "--out") out_path = next("--out");
+        else if (a == "--denoise-out") denoise_path = next("--denoise-out");
         else if (a == "--width") W = std::atoi(next("--width"));
         else if (a == "--height") H = std::atoi(next("--height"));
         else if (a == "--frames") frames = std::atoi(next("--frames"));
@@ -254,6 +259,37 @@ int main(int argc, char** argv) {
             rc = ext == ".png" ? pth_write_png(out_path.c_str(), img.data(), W, H) : pth_write_ppm(out_path.c_str(), img.data(), W, H);
         }
         if (rc != 0) return die("write", pth_last_error());
+    }
+    if (!denoise_path.empty()) {   // guides of the pixel centres + the a-trous filter of the final accumulator, on the first context
+        const size_t n_pix = (size_t)W * H;
+        void *color = accum, *alb = nullptr, *nrm = nullptr, *pos = nullptr, *dout = nullptr, *drgba = nullptr;
+        if (pt_malloc(ctx, n_pix * 16, &alb) != PT_OK || pt_malloc(ctx, n_pix * 16, &nrm) != PT_OK || pt_malloc(ctx, n_pix * 16, &pos) != PT_OK ||
+            pt_malloc(ctx, n_pix * 12, &dout) != PT_OK || pt_malloc(ctx, n_pix * 4, &drgba) != PT_OK)
+            return die("pt_malloc", pt_last_error(ctx));
+        if (gpus > 1) {   // the stripes of the other contexts: the gathered frame, uploaded to a buffer of the first
+            host_acc.resize(n_pix * 3);
+            if (int grc = gather(accums, host_acc.data(), 12)) return grc;
+            if (pt_malloc(ctx, n_pix * 12, &color) != PT_OK || pt_upload(ctx, color, host_acc.data(), n_pix * 12) != PT_OK)
+                return die("pt_upload", pt_last_error(ctx));
+        }
+        const pt_denoise_params dn = {W, H, 4, 0.0f, 1.0f, 0.03f};   // = gpu_pathtracer_amd.DENOISE_DEFAULTS
+        if (pt_render_aux(ctx, &cam, &p, (float*)alb, (float*)nrm, (float*)pos, nullptr) != PT_OK) return die("pt_render_aux", pt_last_error(ctx));
+        if (pt_denoise(ctx, &dn, (const float*)color, (const float*)alb, (const float*)nrm, (const float*)pos, (float*)dout, (uint32_t*)drgba) != PT_OK)
+            return die("pt_denoise", pt_last_error(ctx));
+        const std::string ext = denoise_path.size() > 4 ? denoise_path.substr(denoise_path.size() - 4) : std::string();
+        int rc;
+        if (ext == ".pfm") {
+            std::vector<float> img(n_pix * 3);
+            if (pt_download(ctx, img.data(), dout, img.size() * 4) != PT_OK) return die("pt_download", pt_last_error(ctx));
+            rc = pth_write_pfm(denoise_path.c_str(), img.data(), W, H);
+        } else {
+            std::vector<uint32_t> img(n_pix);
+            if (pt_download(ctx, img.data(), drgba, img.size() * 4) != PT_OK) return die("pt_download", pt_last_error(ctx));
+            rc = ext == ".png" ? pth_write_png(denoise_path.c_str(), img.data(), W, H) : pth_write_ppm(denoise_path.c_str(), img.data(), W, H);
+        }
+        if (rc != 0) return die("write", pth_last_error());
+        for (void* b : {alb, nrm, pos, dout, drgba}) pt_free(ctx, b);
+        if (color != accum) pt_free(ctx, color);
     }
     (void)accum; (void)rgba;
     for (int g = 0; g < gpus; g++) {

@@ -13,7 +13,11 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import Camera, Counters, Material, Params, Sphere
+from ._abi import Camera, Counters, DenoiseParams, Material, Params, Sphere
+
+# pt_denoise defaults (iterations, sigma_color, sigma_normal, sigma_position): chosen by the CPU sweep of DESIGN.md §10 f6;
+# host/pt_app.cpp uses the same values
+DENOISE_DEFAULTS = dict(iterations=4, sigma_color=0.0, sigma_normal=1.0, sigma_position=0.03)
 
 
 class PtError(RuntimeError):
@@ -173,6 +177,19 @@ class PathTracer:
 
     def trace_rays(self, rays_ptr, n, cull, t_ptr, tri_ptr, normal_ptr=None):
         self._check(self._lib.pt_trace_rays(self._ctx, rays_ptr, n, int(cull), t_ptr, tri_ptr, normal_ptr))
+
+    def render_aux(self, cam, params, albedo_ptr, normal_ptr, position_ptr, id_ptr=None):
+        """First-hit guide buffers of the pixel-centre rays (pt_render_aux): albedo, normal, position as float[H][W][4], the hit
+        id as int32[H][W] (optional).  Asynchronous until sync()."""
+        self._check(self._lib.pt_render_aux(self._ctx, C.byref(cam), C.byref(params), albedo_ptr, normal_ptr, position_ptr, id_ptr))
+
+    def denoise(self, color_ptr, albedo_ptr, normal_ptr, position_ptr, width, height, out_ptr, rgba_ptr=None,
+                iterations=DENOISE_DEFAULTS["iterations"], sigma_color=DENOISE_DEFAULTS["sigma_color"],
+                sigma_normal=DENOISE_DEFAULTS["sigma_normal"], sigma_position=DENOISE_DEFAULTS["sigma_position"]):
+        """Edge-avoiding a-trous filter of an accumulator (pt_denoise): color / out float[H][W][3] (out may be color), the
+        guides of render_aux, the display words into rgba (optional).  A sigma <= 0 switches its term off."""
+        dp = DenoiseParams(int(width), int(height), int(iterations), float(sigma_color), float(sigma_normal), float(sigma_position))
+        self._check(self._lib.pt_denoise(self._ctx, C.byref(dp), color_ptr, albedo_ptr, normal_ptr, position_ptr, out_ptr, rgba_ptr))
 
     # ------------------------------------------------------------------ measurement
     def counters(self):

@@ -362,6 +362,48 @@ int pt_render(pt_ctx* ctx, float* accum_dev, uint32_t* rgba_dev,
 int pt_trace_rays(pt_ctx* ctx, const float* rays_dev, size_t n_rays, int cull_backfaces,
                   float* t_dev, int32_t* tri_dev, float* normal_dev);
 
+/* ---- guide buffers and denoiser — an EXTENSION --------------------------
+ * pt_render_aux: the first hit of ONE ray through every pixel centre (the camera ray of pt_render with zero jitter), for a
+ * denoiser or for picking.  Triangles by the binary closest-hit walk of pt_trace_rays, then the spheres with the path kernels'
+ * rule (t > 0.01 and closer than the triangle).  Device outputs, row-major [height][width]:
+ *   albedo_dev   float[4]  (r, g, b, 0): the `col` of what was hit — the sphere's, the triangle's material row
+ *                          (pt_upload_tri_materials) or params->tri_col; emission is ignored
+ *   normal_dev   float[4]  (x, y, z, 0): unit geometric normal facing the ray (dot(n, d) < 0), triangles and spheres alike
+ *   position_dev float[4]  (x, y, z, t): the hit point o + t d and the ray distance t
+ *   id_dev       int32     original triangle id (>= 0), -2 - i for sphere i, -1 on a miss; may be NULL
+ * A miss writes 0 to every component of the three float buffers: a pixel is a miss exactly when its normal is (0, 0, 0).
+ * Reads width, height, cull_backfaces and tri_col of params only (always the full frame; partition fields and flags are
+ * ignored).  PT_ERR_NO_SCENE without a BVH, PT_ERR_UNSUPPORTED over Woop records (PT_OPT_TRI_TEST 1), PT_ERR_INVALID for a
+ * NULL required pointer or width / height < 1.  Asynchronous on the context's stream (ordered after pt_refit_bvh); with
+ * PT_OPT_TIMING=1, pt_last_kernel_ms reports its device time. */
+int pt_render_aux(pt_ctx* ctx, const pt_camera* cam, const pt_params* params,
+                  float* albedo_dev, float* normal_dev, float* position_dev, int32_t* id_dev);
+
+/* pt_denoise: edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) of an accumulator, guided by pt_render_aux's
+ * buffers.  With a'_p = albedo_p where albedo_p > 1e-3 per channel, else 1 (misses: 1), the colour is demodulated,
+ * i0 = c / a', then iteration l = 0 .. iterations-1 (step s = 2^l) computes
+ *     i(l+1)_p = sum_q w_pq i(l)_q / sum_q w_pq,   q = p + s (dx, dy), dx, dy in -2..2, inside the image,
+ *     w_pq = h(dx) h(dy) exp(-|i_p - i_q|^2 / (sigma_color 2^-l)^2 - |n_p - n_q|^2 / sigma_normal^2
+ *                             - |x_p - x_q|^2 / (sigma_position t_p)^2),   h = (1, 4, 6, 4, 1) / 16,
+ * the normal and position terms only where both p and q are hits, w = 0 where exactly one of them is a miss, a term with
+ * sigma <= 0 left out (t_p = position.w of p: sigma_position is a fraction of the distance).  out = clamp01(i(L) a').
+ * iterations = 0 copies color to out bit for bit.
+ *   color_dev float[h][w][3] (pt_render's accumulator layout, never written); out_dev the same layout and may alias color_dev;
+ *   rgba_dev (may be NULL) receives the 0x00BBGGRR display word of out, as pt_render packs it.
+ * PT_ERR_INVALID: NULL color / guide / out pointer, width or height < 1, iterations outside 0..10, a non-finite sigma.  No
+ * scene needed.  Asynchronous on the context's stream, hence ordered after the fold of an earlier pt_render (which stays on
+ * that stream under PT_OPT_OVERLAP).  Scratch (two float[4] frames) belongs to the context: allocated on first use or when the
+ * frame grows (that call synchronises once), freed by pt_destroy, not counted in pt_scene_info; a later call at the same or a
+ * smaller size neither allocates nor synchronises.  With PT_OPT_TIMING=1, pt_last_kernel_ms covers all of its launches. */
+typedef struct pt_denoise_params {
+    int32_t width, height;
+    int32_t iterations;                               /* 0..10                           */
+    float sigma_color, sigma_normal, sigma_position;  /* <= 0 switches that term off     */
+} pt_denoise_params;                                  /* 24 bytes                        */
+int pt_denoise(pt_ctx* ctx, const pt_denoise_params* dp, const float* color_dev,
+               const float* albedo_dev, const float* normal_dev, const float* position_dev,
+               float* out_dev, uint32_t* rgba_dev);
+
 /* ---- measurement --------------------------------------------------------------- */
 int pt_get_counters(pt_ctx* ctx, pt_counters* out);
 /* Schedule statistics of the last instrumented launch of the persistent wide walk
