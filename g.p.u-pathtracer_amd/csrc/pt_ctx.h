@@ -12,6 +12,11 @@
 #include "../../include/ptmi.h"
 #include "pt_kernels.h"
 
+// the bounce-0 walk of a new context (PT_OPT_FIRST_WALK); -DPT_FIRST_WALK_DEFAULT=0 builds the per-lane one for A/B timing
+#ifndef PT_FIRST_WALK_DEFAULT
+#define PT_FIRST_WALK_DEFAULT 1
+#endif
+
 struct pt_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -78,6 +83,8 @@ struct pt_ctx {
     int opt_wave_batch = 16;     // extend kernel: finished lanes that make a wave leave the walk to write hits / refill
     int opt_wave_samples = 16;   // bounce 0 of the stage-split pipeline: samples of one pixel per wave (PT_OPT_WAVE_SAMPLES)
     int opt_wave_blocks = 8;     // extend kernel: resident 256-thread blocks per CU the grid is sized for (PT_OPT_WAVE_BLOCKS)
+    int opt_first_walk = PT_FIRST_WALK_DEFAULT;   // extend kernel of bounce 0: 0 per-lane walk, 1 wave-wide packets (PT_OPT_FIRST_WALK)
+    int opt_packet_stack = PT_PACKET_STACK_MAX;   // (link, mask) entries the packet walk may use per wave (PT_OPT_PACKET_STACK)
     // PT_KERNEL_AUTO: which stage layout is faster depends on the workload (long paths and many samples per call:
     // the stage-split pipeline; short paths or few samples: the persistent kernel), so the first FOUR calls of a
     // configuration are timed trials, two per layout, alternating (HIP events on the stream, buffers allocated before the

@@ -200,6 +200,54 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_wf_extend(const KParams P) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// extend of bounce 0 as wave-wide packets (PT_OPT_FIRST_WALK 1; trav_packet_wide): a wave walks 64-slot groups g, g + stride, ...
+// (lane i = slot 64 g + i, the camera ray of path_begin_hashed), no queue and no refill.  The product launch is a plain grid of
+// one wave per group (the loop runs once); the instrumented one (COUNT) runs a resident grid, so that each wave books its
+// counters once for all of its groups instead of 518 400 waves adding to the same nine words.  The hits of a group are one
+// coalesced 512-byte row.
+template <bool COUNT>
+__global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet(const KParams P) {
+    const uint32_t n_groups = P.wf.n_slots / 64u;   // (n_slots is a multiple of 64)
+    const uint32_t stride = gridDim.x * (uint32_t)(PT_BLOCK / 64);
+    TravCount tc;
+    tc.inner = tc.tris = tc.leaves = 0;
+    tc.it_node = tc.act_node = tc.it_rec = tc.act_rec = 0;
+    uint32_t n_rays = 0, n_walked = 0;
+    for (uint32_t group = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (PT_BLOCK / 64) + (threadIdx.x >> 6)));
+         group < n_groups; group += stride) {   // (wave-uniform)
+        const uint32_t slot = group * 64u + (threadIdx.x & 63u);
+        uint32_t s_idx = 0;
+        int px = 0, py = 0;
+        v3 o = V3(0.f, 0.f, 0.f), d = V3(0.f, 0.f, 0.f);
+        const bool in = wf_slot_pixel(P, slot, s_idx, px, py);
+        if (in) {
+            PathState ps;
+            path_begin_hashed(P, px, py, (uint64_t)((uint32_t)py * (uint32_t)P.W + (uint32_t)px), P.wf.hashes[s_idx], ps);
+            o = ps.o;
+            d = ps.d;
+        }
+        const Hit h = trav_packet_wide<COUNT>(P.sc, o, d, P.cull != 0, in, tc);
+        if (in) pt_sst2(P.wf.hit + slot, make_float2(h.t, __int_as_float(h.rec)));
+        if (COUNT) { n_rays += in ? 1u : 0u; n_walked++; }
+    }
+    if (COUNT && n_walked) {   // 0-3 per lane of the masks; 6-9 wave node / record steps and the lanes in their masks (lane 0 books
+                               // them); 10 (wave stat 4) groups walked
+        const uint32_t a = wave_sum_u32(n_rays), b = wave_sum_u32(tc.inner), c = wave_sum_u32(tc.tris), dd = wave_sum_u32(tc.leaves);
+        if ((threadIdx.x & 63) == 0) {
+            atomicAdd(&P.counters[0], (unsigned long long)a);
+            atomicAdd(&P.counters[1], (unsigned long long)b);
+            atomicAdd(&P.counters[2], (unsigned long long)c);
+            atomicAdd(&P.counters[3], (unsigned long long)dd);
+            atomicAdd(&P.counters[6], (unsigned long long)tc.it_node);
+            atomicAdd(&P.counters[7], (unsigned long long)tc.act_node);
+            atomicAdd(&P.counters[8], (unsigned long long)tc.it_rec);
+            atomicAdd(&P.counters[9], (unsigned long long)tc.act_rec);
+            atomicAdd(&P.counters[10], (unsigned long long)n_walked);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // shade: one bounce of tracer.cu:98-296 for every live record of a region; see the file header.
 // FIRST: bounce 0 — lane = slot; the path starts here (camera ray, RNG) and the sample colour is written, not added to.
 // LAST: the path's final bounce (without PT_FLAG_NEE): only the hit's emission is still wanted (path_last_emission).
@@ -457,8 +505,18 @@ int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles) 
             hipLaunchKernelGGL((k_wf_extend<COUNT, OCC, LSTK, FIRST>), dim3((unsigned)std::min<size_t>((size_t)per_cu * L.n_cu, (size_t)Q.wf.n_regions)), \
                                dim3(PT_BLOCK), lds_ext, s, Q);                                                    \
         } while (0)
+    // bounce 0 as wave-wide packets (PT_OPT_FIRST_WALK 1) when the tree fits the packet stack budget (PT_OPT_PACKET_STACK)
+    const bool packet = c->opt_first_walk == 1 && 3 * c->wide_depth + 2 <= (uint32_t)c->opt_packet_stack;
     auto launch_extend = [&](const KParams& Q, bool first, hipStream_t s, int blocks_per_cu) -> hipError_t {
-        if (first) {
+        if (first && packet) {   // one block per region (4 groups); instrumented: the resident grid, 8 blocks per CU
+#ifdef PT_PACKET_RESIDENT_GRID   // experiment (tools/build_variant.sh): the product launch on the resident grid too
+            const size_t n_blk = std::min<size_t>((size_t)Q.wf.n_regions, (size_t)8 * L.n_cu);
+#else
+            const size_t n_blk = L.count ? std::min<size_t>((size_t)Q.wf.n_regions, (size_t)8 * L.n_cu) : (size_t)Q.wf.n_regions;
+#endif
+            if (L.count) hipLaunchKernelGGL(k_wf_extend_packet<true>, dim3((unsigned)n_blk), dim3(PT_BLOCK), 0, s, Q);
+            else hipLaunchKernelGGL(k_wf_extend_packet<false>, dim3((unsigned)n_blk), dim3(PT_BLOCK), 0, s, Q);
+        } else if (first) {
             if (L.count) { if (L.lstk == 24) PT_EXT(true, 6, 24, true); else PT_EXT(true, 8, 16, true); }
             else { if (L.lstk == 24) PT_EXT(false, 6, 24, true); else PT_EXT(false, 8, 16, true); }
         } else {

@@ -96,13 +96,18 @@ struct TravStack {
     }
 };
 
-template <class STK>
-__device__ __forceinline__ void trav_begin(TravState& s, v3 o, v3 d, STK& stk, int root = 0) {
+// the ray's inverse direction and origin / direction, as the slab tests use them
+__device__ __forceinline__ void trav_ray(TravState& s, v3 o, v3 d) {
     const float ooeps = 8.271806125530277e-25f;  // exp2f(-80), cudaUtils.h:283
     s.idx = 1.0f / (fabsf(d.x) > ooeps ? d.x : copysignf(ooeps, d.x));
     s.idy = 1.0f / (fabsf(d.y) > ooeps ? d.y : copysignf(ooeps, d.y));
     s.idz = 1.0f / (fabsf(d.z) > ooeps ? d.z : copysignf(ooeps, d.z));
     s.oodx = o.x * s.idx; s.oody = o.y * s.idy; s.oodz = o.z * s.idz;
+}
+
+template <class STK>
+__device__ __forceinline__ void trav_begin(TravState& s, v3 o, v3 d, STK& stk, int root = 0) {
+    trav_ray(s, o, d);
     s.sp = 0;
     stk.put(0, PT_SENTINEL);
     s.leaf = 0; s.node = root;
@@ -333,9 +338,9 @@ __device__ __forceinline__ int wide_link(const WideNode& w, uint32_t kk) {
     return k == 0u ? w.l0 : (k == 1u ? w.l1 : (k == 2u ? w.l2 : w.l3));
 }
 
-// the four child-box tests of a node: keys = (entry distance bits | child number), 0xffffffff = missed; sorted ascending
-__device__ __forceinline__ void wide_node_keys(const WideNode& w, float idx, float idy, float idz, float oodx, float oody, float oodz,
-                                               float t_max, uint32_t key[4]) {
+// the four child-box tests of a node: key[k] = (entry distance bits | k) for child k, 0xffffffff = missed; in child order
+__device__ __forceinline__ void wide_node_keys_raw(const WideNode& w, float idx, float idy, float idz, float oodx, float oody, float oodz,
+                                                   float t_max, uint32_t key[4]) {
     const float sx = w.sx * idx, sy = w.sy * idy, sz = w.sz * idz;  // per-axis grid step / direction
     const float bx = fmaf(w.ox, idx, -oodx), by = fmaf(w.oy, idy, -oody), bz = fmaf(w.oz, idz, -oodz);
     // entry/exit planes per axis follow the sign of the ray direction, so pick the packed
@@ -356,10 +361,20 @@ __device__ __forceinline__ void wide_node_keys(const WideNode& w, float idx, flo
         const bool hit = tmin <= tmax;  // unused slots hold inverted boxes
         key[k] = hit ? ((__float_as_uint(tmin) & 0x7ffffffcu) | (uint32_t)k) : 0xffffffffu;
     }
-    // sorting network for 4 keys: (0,1)(2,3)(0,2)(1,3)(1,2)
+}
+
+// sorting network for 4 keys, ascending: (0,1)(2,3)(0,2)(1,3)(1,2)
+__device__ __forceinline__ void wide_sort4(uint32_t key[4]) {
 #define PT_CE(i, j) { const uint32_t lo_ = min(key[i], key[j]), hi_ = max(key[i], key[j]); key[i] = lo_; key[j] = hi_; }
     PT_CE(0, 1) PT_CE(2, 3) PT_CE(0, 2) PT_CE(1, 3) PT_CE(1, 2)
 #undef PT_CE
+}
+
+// the four child-box tests of a node, sorted ascending (the hit children nearest first)
+__device__ __forceinline__ void wide_node_keys(const WideNode& w, float idx, float idy, float idz, float oodx, float oody, float oodz,
+                                               float t_max, uint32_t key[4]) {
+    wide_node_keys_raw(w, idx, idy, idz, oodx, oody, oodz, t_max, key);
+    wide_sort4(key);
 }
 
 // AHEAD: request a leaf's second record together with its first (see the record step); costs 12 VGPRs while the
@@ -569,6 +584,139 @@ __device__ __forceinline__ bool trav_run_wide_pend(TravState& s, const KScene& s
     }
     s.node = cur; s.sp = sp; s.h = h; s.leaf = pend;
     return cur == PT_SENTINEL && pend == 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// Packet walk over the wide tree (bounce 0 of the stage-split pipeline, PT_OPT_FIRST_WALK 1): the 64 lanes of a wave hold
+// rays that start at neighbouring pixels (pt_slot_pixel), so they walk almost the same nodes.  The wave walks ONE node or
+// leaf at a time; the walk's position is wave-uniform (SGPRs) and the item is fetched once per wave with scalar loads
+// instead of once per lane through the vector-memory pipe (TA/TD: ~1 cycle per lane-level access).
+//   - state: the current item `cur` and the mask `m` of the lanes that go there; a stack of (link, mask) per wave in LDS
+//     (16-byte entries written by lane 0, read back by every lane and made uniform with readfirstlane).  A node step
+//     pushes up to three entries and descends one level, so 3 * wide_depth + 2 entries suffice, as for the per-lane stack.
+//   - node step: every lane runs the per-lane walk's box tests (wide_node_keys_raw) with its own ray and h.t; lanes
+//     outside `m` are masked out of the ballots.  A child is visited by exactly the lanes whose own test passed.
+//   - leaf step: every record of the leaf is tested by the lanes of `m`, with the per-lane walk's closest-hit rule.
+// So each lane tests the same kind of candidates as in trav_run_wide, in another order; the closest hit (t, id) does not
+// depend on the order (valid upper bounds, equal-t ties to the smaller id).
+// PT_PACKET_ORDER: which child the wave descends into first — 0: in the entry order of the first lane of `m` (children it
+// missed after those it hit), 1: the child the most lanes go to.
+#ifndef PT_PACKET_ORDER
+#define PT_PACKET_ORDER 0
+#endif
+#define PT_PACKET_STACK_MAX 72   // (link, mask) entries per wave; PT_OPT_PACKET_STACK chooses the budget below it
+
+typedef const __attribute__((address_space(4))) float pt_cfloat;   // read through the scalar data cache
+
+// the float4 at a wave-uniform index of the item buffer, by scalar loads (hipcc merges neighbouring ones into one s_load_dwordx*)
+// (the float4 pointer is indexed BEFORE the cast: its offset is formed in 64 bits, as `sc.nodes + a` of the per-lane walks; an
+// int `4 * a` would wrap past 2^29 float4s = 8 GiB of items)
+__device__ __forceinline__ float4 pt_uld4(const float4* items, int a) {
+    pt_cfloat* p = (pt_cfloat*)(items + a);
+    return make_float4(p[0], p[1], p[2], p[3]);
+}
+
+// one 64-byte wide node at a wave-uniform float4 index: s_load, no vector-memory access
+__device__ __forceinline__ WideNode wide_node_load_uniform(const KScene& sc, int a) {
+    const float4 q0 = pt_uld4(sc.nodes, a), q1 = pt_uld4(sc.nodes, a + 1), q2 = pt_uld4(sc.nodes, a + 2), q3 = pt_uld4(sc.nodes, a + 3);
+    WideNode w;
+    w.ox = q0.x; w.oy = q0.y; w.oz = q0.z;
+    w.sx = q0.w; w.sy = q3.z; w.sz = q3.w;
+    w.qlx = __float_as_uint(q1.x); w.qly = __float_as_uint(q1.y); w.qlz = __float_as_uint(q1.z);
+    w.qhx = __float_as_uint(q1.w); w.qhy = __float_as_uint(q2.x); w.qhz = __float_as_uint(q2.y);
+    w.l0 = __float_as_int(q2.z); w.l1 = __float_as_int(q2.w);
+    w.l2 = __float_as_int(q3.x); w.l3 = __float_as_int(q3.y);
+    return w;
+}
+
+__device__ __forceinline__ uint64_t pt_pick4(uint32_t k, uint64_t a, uint64_t b, uint64_t c, uint64_t d) {
+    return k == 0u ? a : (k == 1u ? b : (k == 2u ? c : d));
+}
+
+// the closest hit of every lane with `in` set; the whole wave must call it with every lane active (EXEC = all 64)
+template <bool COUNT>
+__device__ __forceinline__ Hit trav_packet_wide(const KScene& sc, v3 o, v3 d, bool cull, bool in, TravCount& tc) {
+    __shared__ int4 s_pkt[PT_BLOCK / 64][PT_PACKET_STACK_MAX];
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = (int)(threadIdx.x & 63);
+    TravState s;
+    trav_ray(s, o, d);
+    const float idx = s.idx, idy = s.idy, idz = s.idz, oodx = s.oodx, oody = s.oody, oodz = s.oodz;
+    Hit h;
+    h.t = PT_F32_MAX; h.tri = -1; h.rec = 0;
+    uint64_t m = __ballot(in);
+    int cur = m ? sc.wide_root : PT_SENTINEL;
+    int sp = 0;
+    while (cur != PT_SENTINEL) {
+        const bool act = ((m >> lane) & 1ull) != 0;
+        if (cur >= 0) {
+            const WideNode w = wide_node_load_uniform(sc, cur);
+            if (COUNT) {
+                if (act) tc.inner++;
+                if (lane == 0) { tc.it_node++; tc.act_node += (uint32_t)__popcll(m); }
+            }
+            uint32_t key[4];
+            wide_node_keys_raw(w, idx, idy, idz, oodx, oody, oodz, h.t, key);
+            uint64_t mk[4];
+            uint32_t sk[4];
+#if PT_PACKET_ORDER == 0
+            const int lead = __ffsll((long long)m) - 1;
+#endif
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                mk[k] = __ballot(act && key[k] != 0xffffffffu);
+#if PT_PACKET_ORDER == 0
+                const uint32_t lk = (uint32_t)__builtin_amdgcn_readlane((int)key[k], lead);
+                sk[k] = mk[k] == 0 ? 0xffffffffu : (lk != 0xffffffffu ? lk : (0x7ffffffcu | (uint32_t)k));
+#else
+                sk[k] = mk[k] == 0 ? 0xffffffffu : (((uint32_t)(64 - __popcll(mk[k])) << 2) | (uint32_t)k);
+#endif
+            }
+            wide_sort4(sk);
+            // far to near onto the stack, the nearest is visited now
+#pragma unroll
+            for (int j = 3; j >= 1; j--) {
+                if (sk[j] != 0xffffffffu) {
+                    const uint64_t mm = pt_pick4(sk[j] & 3u, mk[0], mk[1], mk[2], mk[3]);
+                    if (lane == 0) s_pkt[wv][sp] = make_int4(wide_link(w, sk[j]), (int)(uint32_t)mm, (int)(uint32_t)(mm >> 32), 0);
+                    sp++;
+                }
+            }
+            if (sk[0] != 0xffffffffu) {
+                cur = wide_link(w, sk[0]);
+                m = pt_pick4(sk[0] & 3u, mk[0], mk[1], mk[2], mk[3]);
+                continue;
+            }
+        } else {
+            int a = ~cur & ~3;
+            if (COUNT && act) tc.leaves++;
+            for (;;) {
+                const float4 q0 = pt_uld4(sc.nodes, a), q1 = pt_uld4(sc.nodes, a + 1), q2 = pt_uld4(sc.nodes, a + 2);
+                if (COUNT) {
+                    if (act) tc.tris++;
+                    if (lane == 0) { tc.it_rec++; tc.act_rec += (uint32_t)__popcll(m); }
+                }
+                const float t = pt_mt_intersect(V3(q0.x, q0.y, q0.z), V3(q1.x, q1.y, q1.z), V3(q2.x, q2.y, q2.z), o, d, cull);
+                const int id = __float_as_int(q0.w);
+                if (act && t > 0.0f && (t < h.t || (t == h.t && h.tri != -1 && id < h.tri))) {
+                    h.t = t;
+                    h.tri = id;
+                    h.rec = a;
+                }
+                if (__float_as_int(q1.w) != 0) break;  // last record of the leaf
+                a += 4;
+            }
+        }
+        if (sp == 0) {
+            cur = PT_SENTINEL;
+        } else {
+            sp--;
+            const int4 e = s_pkt[wv][sp];
+            cur = __builtin_amdgcn_readfirstlane(e.x);
+            m = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(e.y) | ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(e.z) << 32);
+        }
+    }
+    return h;
 }
 
 template <bool COUNT, bool TOP, class STK>

@@ -312,6 +312,14 @@ int pt_set_option(pt_ctx* c, int option, int value) {
             if (value < 1 || value > 64) return fail(c, PT_ERR_INVALID, "pt_set_option: batch must be 1..64");
             c->opt_batch = value;
             return PT_OK;
+        case PT_OPT_FIRST_WALK:
+            if (value != 0 && value != 1) return fail(c, PT_ERR_INVALID, "pt_set_option: first walk must be 0 (per lane) or 1 (wave-wide packets)");
+            c->opt_first_walk = value;
+            return PT_OK;
+        case PT_OPT_PACKET_STACK:
+            if (value < 2 || value > PT_PACKET_STACK_MAX) return fail(c, PT_ERR_INVALID, "pt_set_option: packet stack must be 2..72 entries");
+            c->opt_packet_stack = value;
+            return PT_OK;
         default: return fail(c, PT_ERR_INVALID, "pt_set_option: unknown option");
     }
 }

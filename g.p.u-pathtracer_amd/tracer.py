@@ -216,6 +216,8 @@ class PathTracer:
         return a.value, b.value
 
     def wave_stats(self):
+        """pt_get_wave_stats of the last instrumented launch.  Under PT_KERNEL_WAVEFRONT "it_shade" holds the 64-ray groups walked by
+        the bounce-0 packet walk (PT_OPT_FIRST_WALK 1; include/ptmi.h), not shading passes."""
         out = (C.c_uint64 * 10)()
         self._check(self._lib.pt_get_wave_stats(self._ctx, out, 10))
         names = ("it_node", "act_node", "it_rec", "act_rec", "it_shade", "act_shade", "it_begin", "act_begin", "it_loop", "stack_overflows")

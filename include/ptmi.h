@@ -160,6 +160,14 @@ enum {
                                  pixel block: the samples of a pixel are the same ray but for the sub-pixel jitter, so they walk the
                                  same nodes and records in step), 1 = one sample of a whole 8x8 tile per wave as in the other
                                  kernels.  A speed knob: which lane traces which (pixel, sample) changes no result       */
+    PT_OPT_FIRST_WALK = 26,   /* PT_KERNEL_WAVEFRONT, extend of bounce 0: 1 (default) = wave-wide packets — a wave walks ONE node or
+                                 leaf at a time for the lanes whose own box tests lead there, fetching it once with scalar loads;
+                                 0 = every lane walks on its own, as at the later bounces.  Same closest hits, hence the same
+                                 images.  The packet walk keeps a stack of (link, lane mask) per wave in LDS; a tree that needs more
+                                 than PT_OPT_PACKET_STACK entries (3 x wide depth + 2) runs the per-lane walk.  Woop records
+                                 (PT_OPT_TRI_TEST 1) never reach this stage: they run PT_KERNEL_PERSISTENT              */
+    PT_OPT_PACKET_STACK = 27, /* PT_OPT_FIRST_WALK 1: the packet stack's budget in entries per wave, 2..72 (default 72); a smaller
+                                 value only sends deeper trees to the per-lane walk                                      */
     PT_OPT_OVERLAP = 21,      /* 1 (default): the path kernel of a pt_render call (persistent / mega kernels) runs on a
                                  stream of the context's own, so that it can start while the PREVIOUS call's last paths
                                  drain; the fold into the accumulator stays on the caller's stream, in call order.  When
@@ -413,7 +421,9 @@ int pt_get_counters(pt_ctx* ctx, pt_counters* out);
  * [8] outer-loop iterations  [9] traversal-stack pushes that overflowed the LDS window into
  * private memory (PT_OPT_LDS_STACK).  A wave-iteration with all 64 lanes active is 100 % use.
  * PT_KERNEL_WAVEFRONT: [0]-[3] and [6]-[9] are the extend stage's ([6]/[7] = refill passes), its
- * shade stage runs one lane per live path ([4], [5] stay 0). */
+ * shade stage runs one lane per live path ([5] stays 0); [4] counts the 64-ray groups the bounce-0
+ * packet walk (PT_OPT_FIRST_WALK 1) walked — 0 when bounce 0 ran the per-lane walk — and that
+ * launch books its wave node / record steps and the lanes of their masks in [0]-[3]. */
 #define PT_WAVE_STATS 10
 int pt_get_wave_stats(pt_ctx* ctx, uint64_t* out, int n);
 int pt_last_kernel_ms(pt_ctx* ctx, float* ms_out);   /* needs PT_OPT_TIMING=1 */
