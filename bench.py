@@ -20,9 +20,13 @@ gathered on rank 0 with RCCL each step (the reference copies the frame to the di
 every frame too, BasicScene.cpp:424-432) and the float accumulator stripes once at the end.  Total work is fixed => "scaling": "strong".
 `--gpus N` without a torchrun environment starts the N ranks itself, as child processes.
 
-Rank 0 prints ONE JSON line.  Everything under oracle/ is used here only AFTER the timed region:
-for the `cpu_baseline` leg, for the parity check of the timed configuration against it, and for
-the algorithmic-byte counters of the roofline (checker, never the thing measured).
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set-up, the library's
+warm start, the W warm-up and K timed steps, `--dump-outputs`, and two instrumented replays that count the
+ray segments `value` is made of.  `--full` adds every side measurement and check after the timed region:
+`stage_ms`, the other materials, 1 spp per call, both stage layouts, the other trees, the big scene, the
+roofline (live PMC child runs, gather ceiling), the CPU baselines and parity against the oracle, and with
+N > 1 the gather of the accumulator stripes and the single-GPU re-check of the gathered frame.  Everything under oracle/ is used only there (checker,
+never the thing measured).
 """
 import argparse
 import glob
@@ -67,9 +71,12 @@ def parse():
     ap.add_argument("--batch", type=int, default=0, help="PT_OPT_BATCH / PT_OPT_WAVE_BATCH (0 = library default)")
     ap.add_argument("--no-overlap", action="store_true", help="PT_OPT_OVERLAP 0: every launch on the caller's stream")
     ap.add_argument("--stripe-rows", type=int, default=8)
-    ap.add_argument("--cpu-frames", type=int, default=1, help="steps of the workload run on the CPU oracle: baseline + parity (0 = skip)")
-    ap.add_argument("--no-cpu-reference", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the side measurements (materials, 1 spp, device tree, big scene, gather bound)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every side measurement and check: stage times, other materials / spp / "
+                         "layouts / trees, big scene, roofline, CPU baselines and oracle parity, the multi-GPU re-check")
+    ap.add_argument("--cpu-frames", type=int, default=1, help="with --full: steps of the workload run on the CPU oracle: baseline + parity (0 = skip)")
+    ap.add_argument("--no-cpu-reference", action="store_true", help="with --full: skip the reference's CPU tracer")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the side measurements (materials, 1 spp, device tree, big scene, gather bound)")
     ap.add_argument("--device-build", action="store_true", help="build the BVH on the device (pt_build_bvh) instead of the host SBVH builder")
     ap.add_argument("--device-optimize", type=int, default=0, help="with --device-build: PT_OPT_OPTIMIZE passes over the device-built tree")
     ap.add_argument("--host-splits", action="store_true", help="host tree with the builder's spatial splits (the reference's splitAlpha = 1e-5)")
@@ -80,7 +87,7 @@ def parse():
                     help="with --gpus 1: still initialise torch.distributed over RCCL (backend nccl, world 1) and send every step's "
                          "display words through the same gather-to-root / side-stream path the N > 1 runs use")
     ap.add_argument("--no-pmc", action="store_true",
-                    help="do not collect HBM traffic live (child runs of this script under rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE)")
+                    help="with --full: do not collect HBM traffic live (child runs of this script under rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)   # the run rocprofv3 wraps: timed steps only
     ap.add_argument("--big-parity-spp", type=int, default=2, help="samples of the big scene's in-run parity frame against the oracle (0 = skip)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -459,17 +466,18 @@ def main():
 
     # ---- everything below is outside the timed region ------------------------------------------
     # device time by stage (HIP events recorded by the library on the launch stream, PT_OPT_TIMING)
-    pt.set_option(g.OPT_TIMING, 1)
     stage = {}
-    n_tm = min(a.steps, 8)
-    for k in range(n_tm):
-        step(a.warmup + k)
-        torch.cuda.synchronize()
-        for name, ms in pt.stage_ms().items():
-            stage[name] = stage.get(name, 0.0) + ms / n_tm
-    pt.set_option(g.OPT_TIMING, 0)
+    if a.full:
+        pt.set_option(g.OPT_TIMING, 1)
+        n_tm = min(a.steps, 8)
+        for k in range(n_tm):
+            step(a.warmup + k)
+            torch.cuda.synchronize()
+            for name, ms in pt.stage_ms().items():
+                stage[name] = stage.get(name, 0.0) + ms / n_tm
+        pt.set_option(g.OPT_TIMING, 0)
 
-    # exact segment / item counts of the timed frames: replay them instrumented — with the kernel that was TIMED (under
+    # exact segment / item counts of the timed frames (what `value` is made of): replay them instrumented — with the kernel that was TIMED (under
     # PT_KERNEL_AUTO an instrumented call would otherwise run the persistent kernel whatever the decision was)
     timed_kernel = a.kernel
     if a.kernel == g.KERNEL_AUTO:
@@ -506,7 +514,7 @@ def main():
         torch.cuda.synchronize()
 
     extra = {}
-    if not a.no_extra:
+    if a.full and not a.no_extra:
         n_x = max(5, a.steps // 5)
         for name, m in (("metal", g.MAT_METAL), ("spec", g.MAT_SPEC)):
             if m == mat:
@@ -535,7 +543,7 @@ def main():
 
     merged_ok = None
     accum_gather_ms = None
-    if use_dist:
+    if a.full and use_dist:
         # the last step once more, fresh (sample_index 1: the frame does not depend on accumulated history), then what north_star
         # names: the gather of the ACCUMULATED tiles (float accumulator stripes, 24.9 MB in all at 1080p) to rank 0, beside the
         # per-step gather of the display words; rank 0 re-renders the frame alone and compares both buffers
@@ -579,15 +587,19 @@ def main():
                                "area_cost_node_visits": None if tree_cost is None else round(tree_cost[0], 3)},
                        "parallelism": (f"tile-split x{world} ({rows}-row stripes, "
                                        f"{'REHEARSAL: all ranks on one GPU, gloo gather through host memory' if a.rehearse else 'RCCL gather to rank 0 (ncclSend/ncclRecv group)'}"
-                                       f" of RGBA8 every step{', overlapped with the next render' if overlap else ''}; float accumulator stripes gathered at the end)") if use_dist else "1 GPU",
+                                       f" of RGBA8 every step{', overlapped with the next render' if overlap else ''}"
+                                       f"{'; float accumulator stripes gathered at the end' if a.full or a.dump_outputs else ''})") if use_dist else "1 GPU",
                        "closed_scene": bool(closed), "rays_per_step": rays_per_step,
                        "tile_split_equals_single_gpu": merged_ok,
                        "accumulator_gather_ms": None if accum_gather_ms is None else round(accum_gather_ms, 3)},
-            "stage_ms": {k: round(v, 4) for k, v in stage.items() if v > 0},
         }
+        if a.full:
+            out["stage_ms"] = {k: round(v, 4) for k, v in stage.items() if v > 0}
         out.update(extra)
         if dumped is not None:
             out["dumped_outputs"] = dumped
+
+    if rank == 0 and a.full:
         # ---------------------------------------------------------------- roofline of the dominant kernel
         # units: one launch of the dominant kernel.  PT_KERNEL_WAVEFRONT launches k_wf_extend once per bounce
         # (`depth` launches per step); the other frame kernels are one launch per step.
@@ -722,7 +734,7 @@ def main():
             except Exception as e:  # a baseline, never a reason to lose the GPU number
                 out["cpu_reference_tracer"] = {"error": str(e)[:200]}
 
-    if not a.no_extra and world == 1:
+    if a.full and not a.no_extra and world == 1:
         # side measurement: the same workload over a tree built ON the device
         # (pt_build_bvh); done last, it replaces the scene of this context
         n_x = max(5, a.steps // 5)
