@@ -85,6 +85,7 @@ struct pt_ctx {
     int opt_wave_blocks = 8;     // extend kernel: resident 256-thread blocks per CU the grid is sized for (PT_OPT_WAVE_BLOCKS)
     int opt_first_walk = PT_FIRST_WALK_DEFAULT;   // extend kernel of bounce 0: 0 per-lane walk, 1 wave-wide packets (PT_OPT_FIRST_WALK)
     int opt_packet_stack = PT_PACKET_STACK_MAX;   // (link, mask) entries the packet walk may use per wave (PT_OPT_PACKET_STACK)
+    int opt_fuse_stages = 1;     // bounce 0's shade in the packet walk's launch, the fold in the last shade launch (PT_OPT_FUSE_STAGES)
     // PT_KERNEL_AUTO: which stage layout is faster depends on the workload (long paths and many samples per call:
     // the stage-split pipeline; short paths or few samples: the persistent kernel), so the first FOUR calls of a
     // configuration are timed trials, two per layout, alternating (HIP events on the stream, buffers allocated before the
@@ -197,8 +198,9 @@ hipError_t launch_rays(const KScene& sc, size_t lds, const float4* rays, size_t 
                        float* n_out, hipStream_t st);                                 // pt_k_mega.hip
 hipError_t launch_persist(const LaunchCfg& L, const KParams& P, hipStream_t st);     // pt_k_persist.hip
 hipError_t launch_fold(const KParams& P, hipStream_t st);                            // pt_k_persist.hip
-// stage-split pipeline (pt_k_wave.hip): generate -> depth x (extend, shade) ; returns PT_* status
-int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles);
+// stage-split pipeline (pt_k_wave.hip): generate -> depth x (extend, shade) ; returns PT_* status; folded = the samples are
+// already folded into the accumulator (PT_OPT_FUSE_STAGES), no launch_fold after it
+int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles, bool& folded);
 // samples of one pixel that share a wave at bounce 0 of the stage-split pipeline, as a power of two (wf_slot_pixel): the largest
 // 2^k <= PT_OPT_WAVE_SAMPLES, k >= 2, that divides spp; else 0 (one sample of a whole tile per wave, the other kernels' order)
 inline uint32_t wave_sample_group_log2(uint32_t spp, int cap) {

@@ -243,37 +243,7 @@ __global__ void __launch_bounds__(256) k_fold_samples_grouped(const KParams P) {
     const bool have_tile = pt_tile_coords(P, tile, tx, ty);   // the LP lanes of a pixel agree; nobody leaves before the last hand-over
     const int px = tx * PT_TILE + (k & 7), py = ty * PT_TILE + ((k >> 3) & 7);
     const bool in = have_tile && px < P.W && py < P.H;
-    const size_t pix = in ? (size_t)py * (size_t)P.W + (size_t)px : 0;
-    float* acc = P.accum + 3 * pix;
-    float ax = 0.f, ay = 0.f, az = 0.f;
-    if (in && P.sample_index != 1) { ax = acc[0]; ay = acc[1]; az = acc[2]; }
-    const uint32_t per = P.spp / (uint32_t)LP, s0 = (uint32_t)part * per;   // a multiple of 4 samples
-    const float4* c4 = (const float4*)pt_sample_ptr(P, s0, pix);
-    // one group of four (the 16-, 8- and 4-sample calls): requested before the hand-over chain starts; longer shares stream theirs
-    // inside their turn
-    const bool pre = per == 4u;
-    float4 qa = make_float4(0.f, 0.f, 0.f, 0.f), qb = qa, qd = qa;
-    if (in && pre) { qa = pt_sld4(c4); qb = pt_sld4(c4 + 1); qd = pt_sld4(c4 + 2); }
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int turn = 0; turn < LP; turn++) {
-        if (in && part == turn) {
-            for (uint32_t s = 0; s < per; s += 4, c4 += 3) {
-                if (!pre) { qa = pt_sld4(c4); qb = pt_sld4(c4 + 1); qd = pt_sld4(c4 + 2); }
-                pt_accumulate(ax, ay, az, V3(qa.x, qa.y, qa.z), P.sample_index + s0 + s);
-                pt_accumulate(ax, ay, az, V3(qa.w, qb.x, qb.y), P.sample_index + s0 + s + 1);
-                pt_accumulate(ax, ay, az, V3(qb.z, qb.w, qd.x), P.sample_index + s0 + s + 2);
-                pt_accumulate(ax, ay, az, V3(qd.y, qd.z, qd.w), P.sample_index + s0 + s + 3);
-            }
-        }
-        if (LP > 1) {   // the share that just ran hands the mean on
-            const int src = (lane & ~(LP - 1)) | turn;
-            ax = __shfl(ax, src); ay = __shfl(ay, src); az = __shfl(az, src);
-        }
-    }
-    if (!in || part != 0) return;
-    acc[0] = ax; acc[1] = ay; acc[2] = az;
-    if ((P.flags & PT_FLAG_WRITE_RGBA) && P.rgba) P.rgba[pix] = pt_pack_rgba(ax, ay, az);
+    pt_fold_pixel_grouped<LP>(P, in, in ? (size_t)py * (size_t)P.W + (size_t)px : 0, part);   // (pt_shade.h)
 }
 
 namespace ptmi {

@@ -257,7 +257,55 @@ __global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet(const KParams 
 #define PT_SURVIVOR_RANK(P, alive, ps, total, s_cnt) wf_block_rank(alive, total, s_cnt)
 #endif
 
-template <bool COUNT, bool NEE, bool FIRST, bool LAST = false>
+// one path's segment after the walk: h = its closest triangle hit (h.tri 0, or the triangle's id with P.tri_matid; -1 on a
+// miss); the spheres, then the background, the emission alone (LAST) or shading + the BRDF sample, the emission going to the
+// sample colour smp (FIRST: written, not added to).  True when the path goes on.
+template <bool NEE, bool FIRST, bool LAST>
+__device__ __forceinline__ bool wf_shade_segment(const KParams& P, PathState& ps, const Hit& h, bool tri_hit, float* smp, NeeReq* req) {
+    v3 tri_n = V3(0.f, 0.f, 0.f);
+    if (!LAST && tri_hit) {   // the triangle's un-normalised normal (4th piece)
+        const float4 q3 = P.sc.nodes[h.rec + 3];
+        tri_n = V3(q3.x, q3.y, q3.z);
+    }
+    const SceneHit sh = pt_closest_sphere(P, ps.o, ps.d, h, 0);
+    if (sh.geom == 3) {   // tracer.cu:140-142: the sample IS the background colour, whatever was gathered before
+        PT_KARGS(K);
+        if (FIRST && (K.flags & PT_FLAG_MISS_KEEPS_PATH)) {
+            smp[0] = 0.f + ps.mask.x * K.bk[0]; smp[1] = 0.f + ps.mask.y * K.bk[1]; smp[2] = 0.f + ps.mask.z * K.bk[2];
+        } else if (K.flags & PT_FLAG_MISS_KEEPS_PATH) {   // extension: accu (= the sample buffer) + mask * bk
+            smp[0] += ps.mask.x * K.bk[0]; smp[1] += ps.mask.y * K.bk[1]; smp[2] += ps.mask.z * K.bk[2];
+        } else {
+            smp[0] = K.bk[0]; smp[1] = K.bk[1]; smp[2] = K.bk[2];
+        }
+        return false;
+    }
+    v3 col;
+    const bool done = LAST ? true : path_shade_hit(P, ps, h, sh, tri_n, col, 0, NEE ? req : nullptr);
+    if (LAST) col = path_last_emission(P, ps, h, sh, 0);
+    const v3 e = done ? col : ps.accu;   // mask * emission of this hit (accu entered as 0)
+    if (FIRST) {   // accu = 0 (tracer.cu:48) + this hit's emission
+        pt_sst3(smp, V3(0.f + e.x, 0.f + e.y, 0.f + e.z));
+    } else if (!(e.x == 0.f) || !(e.y == 0.f) || !(e.z == 0.f)) {
+        smp[0] += e.x; smp[1] += e.y; smp[2] += e.z;   // (as ONE dwordx3 each way: the last bounce's launch +6 %)
+    }
+    return !done;
+}
+
+// PT_OPT_FUSE_STAGES: the fold of one region inside the last shade launch, when the region's slots hold ALL samples of their
+// pixels (sample groups of G = 4 LP = spp samples: 256 / G pixels x G samples).  Wave 0 folds them, LP lanes per pixel, through
+// the code k_fold_samples_grouped<LP> runs, so the accumulator and the display words are the same bit for bit.
+template <int LP>
+__device__ __forceinline__ void wf_fold_region(const KParams& P, uint32_t region) {
+    if (threadIdx.x >= 64) return;
+    uint32_t s_idx = 0;
+    int px = 0, py = 0;
+    // sample 0 of the region's pixel threadIdx.x / LP (pt_slot_pixel: the G samples of a pixel are G consecutive slots)
+    const bool in = wf_slot_pixel(P, region * PT_REGION + (threadIdx.x / LP) * (4u * LP), s_idx, px, py);
+    pt_fold_pixel_grouped<LP>(P, in, in ? (size_t)py * (size_t)P.W + (size_t)px : 0, (int)(threadIdx.x % LP));
+}
+
+// FOLD (PT_OPT_FUSE_STAGES, LAST only): LP of wf_fold_region — this launch also folds the samples, no k_fold_samples follows
+template <bool COUNT, bool NEE, bool FIRST, bool LAST = false, int FOLD = 0>
 __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
     __shared__ int s_cnt[PT_BLOCK / 64];
     __shared__ int s_cnt2[PT_BLOCK / 64];
@@ -267,6 +315,7 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
     if (n_in == 0) {   // (the whole block: before anything is set up — in an open scene most regions are empty after the first bounce)
         if (!last && threadIdx.x == 0) P.wf.cnt_out[region] = 0;
         if (NEE && threadIdx.x == 0) P.wf.s_cnt[region] = 0;
+        if constexpr (FOLD > 0) wf_fold_region<FOLD>(P, region);   // every path of the region ended earlier: its samples are final
         return;
     }
     wf_sphere_table();
@@ -307,39 +356,12 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
         h.t = hh.x;
         h.rec = __float_as_int(hh.y);
         h.tri = -1;
-        v3 tri_n = V3(0.f, 0.f, 0.f);
         tri_hit = h.t < PT_F32_MAX;
-        if (tri_hit) {   // a triangle was hit: its id (v0.w) and un-normalised normal (4th piece)
-            if (!LAST) {
-                const float4 q3 = P.sc.nodes[h.rec + 3];
-                tri_n = V3(q3.x, q3.y, q3.z);
-            }
+        if (tri_hit) {   // a triangle was hit: its id (v0.w)
             h.tri = 0;
             if (P.tri_matid) h.tri = __float_as_int(P.sc.nodes[h.rec].w);
         }
-        float* smp = pt_sample_ptr(P, s_idx, (size_t)pix);
-        const SceneHit sh = pt_closest_sphere(P, ps.o, ps.d, h, 0);
-        if (sh.geom == 3) {   // tracer.cu:140-142: the sample IS the background colour, whatever was gathered before
-            PT_KARGS(K);
-            if (FIRST && (K.flags & PT_FLAG_MISS_KEEPS_PATH)) {
-                smp[0] = 0.f + ps.mask.x * K.bk[0]; smp[1] = 0.f + ps.mask.y * K.bk[1]; smp[2] = 0.f + ps.mask.z * K.bk[2];
-            } else if (K.flags & PT_FLAG_MISS_KEEPS_PATH) {   // extension: accu (= the sample buffer) + mask * bk
-                smp[0] += ps.mask.x * K.bk[0]; smp[1] += ps.mask.y * K.bk[1]; smp[2] += ps.mask.z * K.bk[2];
-            } else {
-                smp[0] = K.bk[0]; smp[1] = K.bk[1]; smp[2] = K.bk[2];
-            }
-        } else {
-            v3 col;
-            const bool done = LAST ? true : path_shade_hit(P, ps, h, sh, tri_n, col, 0, NEE ? &req : nullptr);
-            if (LAST) col = path_last_emission(P, ps, h, sh, 0);
-            const v3 e = done ? col : ps.accu;   // mask * emission of this hit (accu entered as 0)
-            if (FIRST) {   // accu = 0 (tracer.cu:48) + this hit's emission
-                pt_sst3(smp, V3(0.f + e.x, 0.f + e.y, 0.f + e.z));
-            } else if (!(e.x == 0.f) || !(e.y == 0.f) || !(e.z == 0.f)) {
-                smp[0] += e.x; smp[1] += e.y; smp[2] += e.z;   // (as ONE dwordx3 each way: the last bounce's launch +6 %)
-            }
-            alive = !done;
-        }
+        alive = wf_shade_segment<NEE, FIRST, LAST>(P, ps, h, tri_hit, pt_sample_ptr(P, s_idx, (size_t)pix), &req);
     }
     if (COUNT) {   // all 64 lanes of every wave are here
         const uint32_t nh = wave_sum_u32(tri_hit ? 1u : 0u), np = wave_sum_u32(have && !alive ? 1u : 0u);
@@ -359,7 +381,15 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
         }
         if (threadIdx.x == 0) P.wf.s_cnt[region] = n_sh;
     }
-    if (last) return;   // every path ends with this bounce (tracer.cu:305)
+    if (last) {   // every path ends with this bounce (tracer.cu:305)
+        if constexpr (FOLD > 0) {
+            // workgroup-scope release / acquire (vmcnt(0) + s_barrier): the emission adds above reach the folding wave; the
+            // block is on one CU, and no other block writes these samples in this launch
+            __syncthreads();
+            wf_fold_region<FOLD>(P, region);
+        }
+        return;
+    }
     int total;
     const int r = PT_SURVIVOR_RANK(P, alive, ps, total, s_cnt);
     if (alive) {
@@ -367,6 +397,46 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
         pt_sst4(P.wf.ray0_out + j, make_float4(ps.o.x, ps.o.y, ps.o.z, ps.d.x));
         pt_sst4(P.wf.ray1_out + j, make_float4(ps.d.y, ps.d.z, __uint_as_float(NEE ? (pix | ((ps.nee_mask & 0xffu) << 24)) : pix),
                                               __uint_as_float((s_idx << 12) | ps.rng.n | (NEE ? (ps.nee_mask >> 8) << 31 : 0u))));
+        pt_sst1(P.wf.mask_out + j, ps.mask.x);
+        pt_sst1(P.wf.mask_out + (size_t)P.wf.cap + j, ps.mask.y);
+        pt_sst1(P.wf.mask_out + 2 * (size_t)P.wf.cap + j, ps.mask.z);
+    }
+    if (threadIdx.x == 0) P.wf.cnt_out[region] = total;
+}
+
+// bounce 0's packet walk and its shade in ONE launch (PT_OPT_FUSE_STAGES 1: the product launch without PT_FLAG_NEE).  One block
+// per region, as both launches it replaces run, so lane = slot of k_wf_shade<FIRST>: after trav_packet_wide the lane shades its
+// own hit with the camera ray and RNG state it started the walk with — no hit record written and read back, no camera ray
+// computed twice — and the survivors are packed as k_wf_shade<FIRST> packs them (same records, same order).
+__global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet_shade(const KParams P) {
+    __shared__ int s_cnt[PT_BLOCK / 64];
+    wf_sphere_table();
+    const uint32_t region = blockIdx.x;
+    const size_t i = (size_t)region * PT_REGION + threadIdx.x;
+    uint32_t s_idx = 0;
+    int px = 0, py = 0;
+    const bool have = wf_slot_pixel(P, (uint32_t)i, s_idx, px, py);
+    const uint32_t pix = (uint32_t)py * (uint32_t)P.W + (uint32_t)px;
+    PathState ps;
+    ps.o = ps.d = V3(0.f, 0.f, 0.f);
+    if (have) path_begin_hashed(P, px, py, (uint64_t)pix, P.wf.hashes[s_idx], ps);
+    TravCount tc;
+    tc.inner = tc.tris = tc.leaves = 0;
+    tc.it_node = tc.act_node = tc.it_rec = tc.act_rec = 0;
+    Hit h = trav_packet_wide<false>(P.sc, ps.o, ps.d, P.cull != 0, have, tc);   // (every lane of the wave: EXEC = all 64)
+    bool alive = false;
+    if (have) {
+        const bool tri_hit = h.t < PT_F32_MAX;
+        if (tri_hit && !P.tri_matid) h.tri = 0;   // (else the walk's id: the record's v0.w, what k_wf_shade reads back)
+        alive = wf_shade_segment<false, true, false>(P, ps, h, tri_hit, pt_sample_ptr(P, s_idx, (size_t)pix), nullptr);
+    }
+    if (P.wf.bounce + 1 >= P.depth) return;   // depth 1
+    int total;
+    const int r = PT_SURVIVOR_RANK(P, alive, ps, total, s_cnt);
+    if (alive) {
+        const size_t j = (size_t)region * PT_REGION + (size_t)r;
+        pt_sst4(P.wf.ray0_out + j, make_float4(ps.o.x, ps.o.y, ps.o.z, ps.d.x));
+        pt_sst4(P.wf.ray1_out + j, make_float4(ps.d.y, ps.d.z, __uint_as_float(pix), __uint_as_float((s_idx << 12) | ps.rng.n)));
         pt_sst1(P.wf.mask_out + j, ps.mask.x);
         pt_sst1(P.wf.mask_out + (size_t)P.wf.cap + j, ps.mask.y);
         pt_sst1(P.wf.mask_out + 2 * (size_t)P.wf.cap + j, ps.mask.z);
@@ -441,7 +511,8 @@ int wave_reserve(pt_ctx* c, const KParams& P, int work_tiles) {
     return PT_OK;
 }
 
-int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles) {
+int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles, bool& folded) {
+    folded = false;
     WaveLayout w;
     {
         const int rc = wave_layout(c, P, work_tiles, w);
@@ -528,9 +599,19 @@ int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles) 
 #undef PT_EXT
 #define PT_SHADE(COUNT, NEE, FIRST) \
         hipLaunchKernelGGL((k_wf_shade<COUNT, NEE, FIRST>), dim3((unsigned)Q.wf.n_regions), dim3(PT_BLOCK), lds_shade, s, Q)
+    // PT_OPT_FUSE_STAGES 1, the product launch without PT_FLAG_NEE: bounce 0's shade runs in the packet walk's launch, and the last
+    // shade launch folds the samples when every region holds all samples of its pixels (sample groups of spp = 16, 8 or 4)
+    const bool fuse = c->opt_fuse_stages != 0 && !nee && !L.count;
+    const bool fuse_first = fuse && packet;
+    const int fold_lp = fuse && P.depth >= 2 && P.sgroup_log2 >= 2 && P.sgroup_log2 <= 4 && P.spp == (1u << P.sgroup_log2) ? (int)P.spp / 4 : 0;
+    folded = fold_lp != 0;
     auto launch_shade = [&](const KParams& Q, bool first, hipStream_t s) -> hipError_t {
         if (!first && !nee && !L.count && Q.wf.bounce + 1 >= Q.depth) {   // the final bounce: emission only
-            hipLaunchKernelGGL((k_wf_shade<false, false, false, true>), dim3((unsigned)Q.wf.n_regions), dim3(PT_BLOCK), lds_shade, s, Q);
+            const dim3 grid((unsigned)Q.wf.n_regions);
+            if (fold_lp == 4) hipLaunchKernelGGL((k_wf_shade<false, false, false, true, 4>), grid, dim3(PT_BLOCK), lds_shade, s, Q);
+            else if (fold_lp == 2) hipLaunchKernelGGL((k_wf_shade<false, false, false, true, 2>), grid, dim3(PT_BLOCK), lds_shade, s, Q);
+            else if (fold_lp == 1) hipLaunchKernelGGL((k_wf_shade<false, false, false, true, 1>), grid, dim3(PT_BLOCK), lds_shade, s, Q);
+            else hipLaunchKernelGGL((k_wf_shade<false, false, false, true>), grid, dim3(PT_BLOCK), lds_shade, s, Q);
             return hipGetLastError();
         }
         if (first) {
@@ -553,6 +634,12 @@ int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles) 
     for (uint32_t b = 0; b < P.depth; b++) {
         set_bounce(P, b);
         P.wf.queue = queues + (size_t)b * PT_SHARDS * PT_SHARD_STRIDE;
+        if (b == 0 && fuse_first) {   // walk + shade of bounce 0, booked as the extend stage
+            hipLaunchKernelGGL(k_wf_extend_packet_shade, dim3((unsigned)n_regions), dim3(PT_BLOCK), lds_shade, st, P);
+            HIP_TRY(c, hipGetLastError());
+            if (stage_mark(c, PT_STAGE_EXTEND) != PT_OK) return PT_ERR_DEVICE;
+            continue;
+        }
         HIP_TRY(c, launch_extend(P, b == 0, st, c->opt_wave_blocks));
         if (stage_mark(c, PT_STAGE_EXTEND) != PT_OK) return PT_ERR_DEVICE;
         HIP_TRY(c, launch_shade(P, b == 0, st));

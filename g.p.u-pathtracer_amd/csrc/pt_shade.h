@@ -433,3 +433,42 @@ __device__ __forceinline__ uint32_t pt_pack_rgba(float ax, float ay, float az) {
     return (b << 16) | (g << 8) | r;
 }
 
+// One pixel's share of the fold over the [pixel][sample][3] sample buffer of the sample groups (spp a multiple of 4): LP
+// adjacent lanes of a wave per pixel (part = lane % LP), each reading spp / LP consecutive samples in 16-byte pieces, the
+// running mean handed from lane to lane so that the samples enter it in order 0 .. spp-1; part 0 writes the accumulator and
+// the display word.  All 64 lanes of the wave call it (the hand-over is a shuffle); `in` is false for pixels that do not exist.
+// k_fold_samples_grouped and the last shade launch of the stage-split pipeline (k_wf_shade, FOLD) both fold through it.
+template <int LP>
+__device__ __forceinline__ void pt_fold_pixel_grouped(const KParams& P, bool in, size_t pix, int part) {
+    float* acc = P.accum + 3 * pix;
+    float ax = 0.f, ay = 0.f, az = 0.f;
+    if (in && P.sample_index != 1) { ax = acc[0]; ay = acc[1]; az = acc[2]; }
+    const uint32_t per = P.spp / (uint32_t)LP, s0 = (uint32_t)part * per;   // a multiple of 4 samples
+    const float4* c4 = (const float4*)pt_sample_ptr(P, s0, pix);
+    // one group of four (the 16-, 8- and 4-sample calls): requested before the hand-over chain starts; longer shares stream theirs
+    // inside their turn
+    const bool pre = per == 4u;
+    float4 qa = make_float4(0.f, 0.f, 0.f, 0.f), qb = qa, qd = qa;
+    if (in && pre) { qa = pt_sld4(c4); qb = pt_sld4(c4 + 1); qd = pt_sld4(c4 + 2); }
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int turn = 0; turn < LP; turn++) {
+        if (in && part == turn) {
+            for (uint32_t s = 0; s < per; s += 4, c4 += 3) {
+                if (!pre) { qa = pt_sld4(c4); qb = pt_sld4(c4 + 1); qd = pt_sld4(c4 + 2); }
+                pt_accumulate(ax, ay, az, V3(qa.x, qa.y, qa.z), P.sample_index + s0 + s);
+                pt_accumulate(ax, ay, az, V3(qa.w, qb.x, qb.y), P.sample_index + s0 + s + 1);
+                pt_accumulate(ax, ay, az, V3(qb.z, qb.w, qd.x), P.sample_index + s0 + s + 2);
+                pt_accumulate(ax, ay, az, V3(qd.y, qd.z, qd.w), P.sample_index + s0 + s + 3);
+            }
+        }
+        if (LP > 1) {   // the share that just ran hands the mean on
+            const int src = (lane & ~(LP - 1)) | turn;
+            ax = __shfl(ax, src); ay = __shfl(ay, src); az = __shfl(az, src);
+        }
+    }
+    if (!in || part != 0) return;
+    acc[0] = ax; acc[1] = ay; acc[2] = az;
+    if ((P.flags & PT_FLAG_WRITE_RGBA) && P.rgba) P.rgba[pix] = pt_pack_rgba(ax, ay, az);
+}
+

@@ -320,6 +320,10 @@ int pt_set_option(pt_ctx* c, int option, int value) {
             if (value < 2 || value > PT_PACKET_STACK_MAX) return fail(c, PT_ERR_INVALID, "pt_set_option: packet stack must be 2..72 entries");
             c->opt_packet_stack = value;
             return PT_OK;
+        case PT_OPT_FUSE_STAGES:
+            if (value != 0 && value != 1) return fail(c, PT_ERR_INVALID, "pt_set_option: fuse stages must be 0 (separate launches) or 1");
+            c->opt_fuse_stages = value;
+            return PT_OK;
         default: return fail(c, PT_ERR_INVALID, "pt_set_option: unknown option");
     }
 }
@@ -848,8 +852,9 @@ int pt_render(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, const pt_camera* 
     L.blocks = (work_tiles + waves_per_block - 1) / waves_per_block;
     L.work_blocks = (int)(((long)work_tiles * 64 + P.chunk * (PT_BLOCK / 64) - 1) / (P.chunk * (PT_BLOCK / 64)));
     L.n_cu = c->n_cu;
+    bool folded = false;
     if (wavefront) {
-        const int rc = render_wavefront(c, P, L, work_tiles);
+        const int rc = render_wavefront(c, P, L, work_tiles, folded);
         if (rc != PT_OK) return rc;
     } else if (persistent) {
         HIP_TRY(c, launch_persist(L, P, trace_stream));
@@ -862,7 +867,7 @@ int pt_render(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, const pt_camera* 
         HIP_TRY(c, hipEventRecord(sd->traced, sd->stream));
         HIP_TRY(c, hipStreamWaitEvent(c->stream, sd->traced, 0));
     }
-    if (P.samples) {
+    if (P.samples && !folded) {
         HIP_TRY(c, launch_fold(P, c->stream));
         if (stage_mark(c, PT_STAGE_FOLD) != PT_OK) return PT_ERR_DEVICE;
     }

@@ -207,9 +207,14 @@ enum {
                                  (cudaUtils.h:135-172; default, bit-exact vs the oracle);
                                  1 = Woop affine rows (north_star; CudaBVH.cpp:274-305 done
                                  right), tolerance-class parity, wide walk only               */
-    PT_OPT_LEAF_MAX = 9       /* leaves holding more triangle references than this are split
+    PT_OPT_LEAF_MAX = 9,      /* leaves holding more triangle references than this are split
                                  at the next pt_upload_bvh (0 = keep the producer's leaves;
                                  default 2)                                                   */
+    PT_OPT_FUSE_STAGES = 28   /* PT_KERNEL_WAVEFRONT without PT_FLAG_NEE or PT_OPT_COUNTERS: 1 (default) = bounce 0 is shaded in
+                                 the launch of its packet walk (no hit records of bounce 0), and when every region of the call holds
+                                 all samples of its pixels (PT_OPT_WAVE_SAMPLES groups of spp = 16, 8 or 4, depth >= 2) the last
+                                 shade launch folds them into the accumulator (no separate fold launch); 0 = one launch per
+                                 stage.  Same images, same counters                                                     */
 };
 
 /* CamInfo, GpuPathTracer/CpuStructs.hpp:19-28 (pitch/yaw/dirty/bias/enabled are host-only
