@@ -714,11 +714,22 @@ int orc_render_mat(float* accum, uint32_t* rgba,
 /* Selected pixels, sample by sample (the tests' arbiter for pixels where two renders differ): out_col[n][spp][3] = the
  * sample colours BEFORE the fold, out_seg[n][spp][depth][2] (may be NULL) = every segment's (t, triangle id bits; F32_MAX /
  * -1 where the path had ended).  Closest hits come from the BVH arrays, or — when nodes is NULL and a raw mesh is given —
- * from the brute-force loop over all its triangles (no tree: nothing can be culled by a box).  Global material only. */
+ * from the brute-force loop over all its triangles (no tree: nothing can be culled by a box).  Global material only;
+ * orc_sample_pixels_mat takes the per-triangle material table of orc_render_mat. */
 int orc_sample_pixels(const float* nodes, const float* tris, const int32_t* tidx,
                       const float* verts, const int32_t* tri_vidx, size_t n_tris,
                       const pt_sphere* sph, size_t n_sph, const pt_camera* cam, const pt_params* P, uint32_t spp,
                       const int32_t* pixels_xy, size_t n, float* out_col, float* out_seg) {
+    return orc_sample_pixels_mat(nodes, tris, tidx, verts, tri_vidx, n_tris, sph, n_sph, NULL, NULL, cam, P, spp, pixels_xy, n,
+                                 out_col, out_seg);
+}
+
+int orc_sample_pixels_mat(const float* nodes, const float* tris, const int32_t* tidx,
+                          const float* verts, const int32_t* tri_vidx, size_t n_tris,
+                          const pt_sphere* sph, size_t n_sph, const pt_material* mtab, const int32_t* tri_mat,
+                          const pt_camera* cam, const pt_params* P, uint32_t spp,
+                          const int32_t* pixels_xy, size_t n, float* out_col, float* out_seg) {
+    if (mtab && !tri_mat) return -1;
     if (!cam || !P || !pixels_xy || !out_col || (!nodes && !(verts && tri_vidx && n_tris))) return -1;
     const long total = (long)n * (long)spp;
 #pragma omp parallel for schedule(dynamic, 1)
@@ -732,7 +743,7 @@ int orc_sample_pixels(const float* nodes, const float* tris, const int32_t* tidx
         if (!nodes) { tl_brute_verts = verts; tl_brute_vidx = tri_vidx; tl_brute_n = n_tris; }
         tl_seg_log = seg; tl_seg_cap = P->depth;
         rng_t rng = rng_init(P->frame + s, pix);
-        const v3 col = get_sample(nodes, tris, tidx, sph, n_sph, cam, P, NULL, NULL, x, y, &rng, NULL);
+        const v3 col = get_sample(nodes, tris, tidx, sph, n_sph, cam, P, mtab, tri_mat, x, y, &rng, NULL);
         tl_brute_n = 0; tl_seg_log = 0; tl_seg_cap = 0;
         out_col[3 * k] = col.x; out_col[3 * k + 1] = col.y; out_col[3 * k + 2] = col.z;
     }

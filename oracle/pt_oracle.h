@@ -43,6 +43,11 @@ int orc_sample_pixels(const float* nodes, const float* tris, const int32_t* tidx
                       const float* verts, const int32_t* tri_vidx, size_t n_tris,
                       const pt_sphere* sph, size_t n_sph, const pt_camera* cam, const pt_params* P, uint32_t spp,
                       const int32_t* pixels_xy, size_t n, float* out_col, float* out_seg);
+int orc_sample_pixels_mat(const float* nodes, const float* tris, const int32_t* tidx,
+                          const float* verts, const int32_t* tri_vidx, size_t n_tris,
+                          const pt_sphere* sph, size_t n_sph, const pt_material* mtab, const int32_t* tri_mat,
+                          const pt_camera* cam, const pt_params* P, uint32_t spp,
+                          const int32_t* pixels_xy, size_t n, float* out_col, float* out_seg);
 void orc_primary_rays(const pt_camera* cam, int W, int H, uint64_t frame, int jitter, float* rays8);
 
 #ifdef __cplusplus

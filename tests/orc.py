@@ -53,6 +53,9 @@ def lib():
         L.orc_sample_pixels.restype = i32
         L.orc_sample_pixels.argtypes = [vp, vp, vp, vp, vp, sz, C.POINTER(g.Sphere), sz, C.POINTER(g.Camera), C.POINTER(g.Params),
                                         C.c_uint32, vp, sz, vp, vp]
+        L.orc_sample_pixels_mat.restype = i32
+        L.orc_sample_pixels_mat.argtypes = [vp, vp, vp, vp, vp, sz, C.POINTER(g.Sphere), sz, vp, vp, C.POINTER(g.Camera),
+                                            C.POINTER(g.Params), C.c_uint32, vp, sz, vp, vp]
         L.orc_primary_rays.restype = None
         L.orc_primary_rays.argtypes = [C.POINTER(g.Camera), i32, i32, C.c_uint64, i32, vp]
         _lib = L
@@ -106,23 +109,29 @@ def render(bvh, spheres, cam, params, spp=1, accum=None, want_rgba=True, materia
     return accum, rgba, counters_dict(cnt)
 
 
-def sample_pixels(pixels_xy, spheres, cam, params, spp, bvh=None, mesh=None):
+def sample_pixels(pixels_xy, spheres, cam, params, spp, bvh=None, mesh=None, materials=None, tri_material=None):
     """Selected pixels sample by sample: the colours before the fold [n][spp][3] and every segment's (t, triangle id)
     [n][spp][depth].  bvh: hits from the oracle's walk over the Compact arrays; mesh (bvh None): hits from the
-    BRUTE-FORCE loop over the raw triangles — the arbiter for pixels where two renders differ."""
+    BRUTE-FORCE loop over the raw triangles — the arbiter for pixels where two renders differ.  materials / tri_material:
+    the per-triangle material table, as in render()."""
     px = np.ascontiguousarray(pixels_xy, np.int32).reshape(-1, 2)
     n, depth = len(px), params.depth
     col = np.zeros((n, spp, 3), np.float32)
     seg = np.zeros((n, spp, depth, 2), np.float32)
     n_s = len(spheres) if spheres is not None else 0
+    mtab = ids = None
+    if materials is not None and len(materials):
+        mtab = (g.Material * len(materials))(*materials)
+        ids = np.ascontiguousarray(tri_material, np.int32)
+    tab = (C.cast(mtab, C.c_void_p), ids.ctypes.data) if mtab is not None else (None, None)
     if bvh is not None:
-        rc = lib().orc_sample_pixels(bvh.nodes.ctypes.data, bvh.tris.ctypes.data, bvh.index.ctypes.data, None, None, 0,
-                                     spheres if n_s else None, n_s, C.byref(cam), C.byref(params), spp, px.ctypes.data, n,
-                                     col.ctypes.data, seg.ctypes.data)
+        rc = lib().orc_sample_pixels_mat(bvh.nodes.ctypes.data, bvh.tris.ctypes.data, bvh.index.ctypes.data, None, None, 0,
+                                         spheres if n_s else None, n_s, *tab, C.byref(cam), C.byref(params), spp, px.ctypes.data,
+                                         n, col.ctypes.data, seg.ctypes.data)
     else:
         v, f = np.ascontiguousarray(mesh.verts), np.ascontiguousarray(mesh.tris)
-        rc = lib().orc_sample_pixels(None, None, None, v.ctypes.data, f.ctypes.data, len(f), spheres if n_s else None, n_s,
-                                     C.byref(cam), C.byref(params), spp, px.ctypes.data, n, col.ctypes.data, seg.ctypes.data)
+        rc = lib().orc_sample_pixels_mat(None, None, None, v.ctypes.data, f.ctypes.data, len(f), spheres if n_s else None, n_s, *tab,
+                                         C.byref(cam), C.byref(params), spp, px.ctypes.data, n, col.ctypes.data, seg.ctypes.data)
     assert rc == 0
     return col, seg[..., 0], seg[..., 1].view(np.int32)
 

@@ -213,10 +213,12 @@ def test_auto_times_both_layouts_and_keeps_one():
         t.close()
 
 
-def arbitrate(pt, mesh, bvh, sph, cam, p, frames, what, max_diff, oracle_key=None):
+def arbitrate(pt, mesh, bvh, sph, cam, p, frames, what, max_diff, oracle_key=None, materials=None, tri_material=None):
     """Sample by sample (one pt_render per frame, N = 1) against the oracle's walk over `bvh`; every (frame, pixel) where the
     two differ is replayed with the BRUTE-FORCE closest hit (orc.sample_pixels over the raw triangles: no tree, so no box
-    can cull anything) and the GPU must hold brute force's colour.  Returns (differing, of which the oracle's walk was off)."""
+    can cull anything) and the GPU must hold brute force's colour.  Returns (differing, of which the oracle's walk was off).
+    materials / tri_material: the per-triangle material table on the context, handed to both oracle renderers."""
+    mk = dict(materials=materials, tri_material=tri_material)
     W, H = p.width, p.height
     acc, rgba = pt.alloc_frame(W, H)
     diffs = []
@@ -226,8 +228,8 @@ def arbitrate(pt, mesh, bvh, sph, cam, p, frames, what, max_diff, oracle_key=Non
         pt.launch_kernel(acc.ptr, rgba.ptr, cam, q, 1)
         pt.sync()
         got = acc.download(np.float32, (H, W, 3))
-        ref = oracle((oracle_key, f), lambda: orc.render(bvh, sph, cam, q, 1, want_rgba=False)[0]) if oracle_key else \
-            orc.render(bvh, sph, cam, q, 1, want_rgba=False)[0]
+        ref = oracle((oracle_key, f), lambda: orc.render(bvh, sph, cam, q, 1, want_rgba=False, **mk)[0]) if oracle_key else \
+            orc.render(bvh, sph, cam, q, 1, want_rgba=False, **mk)[0]
         ys, xs = np.nonzero(np.any(got != ref, axis=-1))
         diffs += [(f, int(x), int(y), got[y, x].copy(), ref[y, x].copy()) for x, y in zip(xs, ys)]
     acc.free()
@@ -236,8 +238,8 @@ def arbitrate(pt, mesh, bvh, sph, cam, p, frames, what, max_diff, oracle_key=Non
     for f, x, y, got, ref in diffs:
         q = g.Params.from_buffer_copy(p)
         q.frame, q.sample_index = f, 1
-        col, t_b, id_b = orc.sample_pixels([(x, y)], sph, cam, q, 1, mesh=mesh)
-        _, t_o, id_o = orc.sample_pixels([(x, y)], sph, cam, q, 1, bvh=bvh)
+        col, t_b, id_b = orc.sample_pixels([(x, y)], sph, cam, q, 1, mesh=mesh, **mk)
+        _, t_o, id_o = orc.sample_pixels([(x, y)], sph, cam, q, 1, bvh=bvh, **mk)
         brute = orc.fold_samples(col, 1)[0]
         seg = int(np.argmax((t_b[0, 0] != t_o[0, 0]) | (id_b[0, 0] != id_o[0, 0]))) if (np.any(t_b != t_o) or np.any(id_b != id_o)) else -1
         print(f"  {what}: frame {f} pixel ({x},{y}) gpu {got} oracle {ref} brute {brute}; oracle's walk leaves brute force at segment {seg}: "
