@@ -77,7 +77,11 @@ __device__ __forceinline__ bool wf_slot_pixel(const KParams& P, uint32_t slot, u
 // ------------------------------------------------------------------------------------------------
 // extend: the closest-hit walk (rows a5-a7) over the ray queue; see the file header.
 // FIRST: bounce 0 — a region is 256 consecutive slots and the ray is the slot's camera ray.
-template <bool COUNT, int OCC, int LSTK, bool FIRST>
+// ANY (PT_OPT_LAST_ANYHIT): the path's last segment when no triangle emits — the shade launch before left (ts, sphere) of the
+// ray's nearest sphere in the ray's hit slot, and all the picture still needs is whether a triangle is hit at t <= ts.  The
+// lane starts the walk bounded by the next float above ts and leaves at the first record it accepts (trav_run_wide<.., ANY>);
+// it writes t = 0 over ts when there is one and leaves the slot alone otherwise.
+template <bool COUNT, int OCC, int LSTK, bool FIRST, bool ANY = false>
 __global__ void __launch_bounds__(PT_BLOCK, OCC) k_wf_extend(const KParams P) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -137,6 +141,7 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_wf_extend(const KParams P) {
                 const uint32_t take = min((uint32_t)n_idle - served, end - next);
                 if (!live && rank >= served && rank < served + take) {
                     idx = next + (rank - served);
+                    float bound = PT_F32_MAX;
                     if (FIRST) {
                         uint32_t s_idx = 0;
                         int px = 0, py = 0;
@@ -149,11 +154,14 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_wf_extend(const KParams P) {
                         }
                     } else {
                         const float4 a = pt_sld4(P.wf.ray0_in + idx), b = pt_sld4(P.wf.ray1_in + idx);
+                        if (ANY) bound = pt_sld1((const float*)(P.wf.hit + idx));
                         o = V3(a.x, a.y, a.z);
                         d = V3(a.w, b.x, b.y);
                         live = true;
                     }
                     if (live) trav_begin(ts, o, d, stk, P.sc.wide_root);
+                    // t <= ts as the walk's t < h.t: one bit up (ts > 0.01; PT_F32_MAX = no sphere stays)
+                    if (ANY) ts.h.t = bound < PT_F32_MAX ? __uint_as_float(__float_as_uint(bound) + 1u) : bound;
                 }
                 next += take;
                 served += take;
@@ -168,9 +176,10 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_wf_extend(const KParams P) {
         // ---- walk until `batch` lanes have finished (lanes that can get no more work do not count)
         const int n_dead = empty ? 64 - __popcll(busy) : 0;
         if (live) {
-            const bool fin = trav_run_wide<COUNT, true, false, true>(ts, P.sc, o, d, cull, stk, tc, n_dead, batch);
+            const bool fin = trav_run_wide<COUNT, true, false, true, ANY>(ts, P.sc, o, d, cull, stk, tc, n_dead, batch);
             if (fin) {
-                pt_sst2(P.wf.hit + idx, make_float2(ts.h.t, __int_as_float(ts.h.rec)));
+                if (ANY) { if (ts.h.t == 0.0f) pt_sst1((float*)(P.wf.hit + idx), 0.0f); }
+                else pt_sst2(P.wf.hit + idx, make_float2(ts.h.t, __int_as_float(ts.h.rec)));
                 live = false;
                 if (COUNT) n_rays++;
             }
@@ -191,6 +200,7 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_wf_extend(const KParams P) {
             atomicAdd(&P.counters[7], (unsigned long long)w_act_node);
             atomicAdd(&P.counters[8], (unsigned long long)w_it_rec);
             atomicAdd(&P.counters[9], (unsigned long long)w_act_rec);
+            if (ANY) atomicAdd(&P.counters[11], (unsigned long long)a);   // wave stat 5: the rays of the any-hit launch
             atomicAdd(&P.counters[12], (unsigned long long)it_begin);
             atomicAdd(&P.counters[13], (unsigned long long)act_begin);
             atomicAdd(&P.counters[14], (unsigned long long)it_loop);
@@ -304,8 +314,20 @@ __device__ __forceinline__ void wf_fold_region(const KParams& P, uint32_t region
     pt_fold_pixel_grouped<LP>(P, in, in ? (size_t)py * (size_t)P.W + (size_t)px : 0, (int)(threadIdx.x % LP));
 }
 
+// PT_OPT_LAST_ANYHIT: the nearest sphere along a survivor's NEW ray, (ts, sphere) — pt_closest_sphere's loop over an empty
+// triangle hit, so (PT_F32_MAX, -1) when no sphere qualifies.  With the strict running minimum this is the sphere the loop after
+// the walk picks whenever a sphere wins, so the pair is final: the last segment only asks the triangles for a hit at t <= ts.
+__device__ __forceinline__ float2 wf_sphere_bound(const KParams& P, const PathState& ps) {
+    Hit none;
+    none.t = PT_F32_MAX; none.tri = -1; none.rec = 0;
+    const SceneHit sh = pt_closest_sphere(P, ps.o, ps.d, none, 0);
+    return make_float2(sh.t, __int_as_float(sh.sph_id));
+}
+
 // FOLD (PT_OPT_FUSE_STAGES, LAST only): LP of wf_fold_region — this launch also folds the samples, no k_fold_samples follows
-template <bool COUNT, bool NEE, bool FIRST, bool LAST = false, int FOLD = 0>
+// BOUND (PT_OPT_LAST_ANYHIT, the shade launch of bounce depth - 2): the survivors' rays are the paths' last segments; their
+// sphere bound goes to the survivor's hit slot for k_wf_extend<.., ANY> and k_wf_shade_last_any
+template <bool COUNT, bool NEE, bool FIRST, bool LAST = false, int FOLD = 0, bool BOUND = false>
 __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
     __shared__ int s_cnt[PT_BLOCK / 64];
     __shared__ int s_cnt2[PT_BLOCK / 64];
@@ -363,6 +385,8 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
         }
         alive = wf_shade_segment<NEE, FIRST, LAST>(P, ps, h, tri_hit, pt_sample_ptr(P, s_idx, (size_t)pix), &req);
     }
+    float2 bound = make_float2(PT_F32_MAX, __int_as_float(-1));
+    if (BOUND && alive) bound = wf_sphere_bound(P, ps);
     if (COUNT) {   // all 64 lanes of every wave are here
         const uint32_t nh = wave_sum_u32(tri_hit ? 1u : 0u), np = wave_sum_u32(have && !alive ? 1u : 0u);
         if ((threadIdx.x & 63) == 0) {
@@ -400,14 +424,67 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
         pt_sst1(P.wf.mask_out + j, ps.mask.x);
         pt_sst1(P.wf.mask_out + (size_t)P.wf.cap + j, ps.mask.y);
         pt_sst1(P.wf.mask_out + 2 * (size_t)P.wf.cap + j, ps.mask.z);
+        // (slot j held another lane's hit of THIS bounce: every lane of the region has read its own before the rank's barrier)
+        if (BOUND) pt_sst2(P.wf.hit + j, bound);
     }
     if (threadIdx.x == 0) P.wf.cnt_out[region] = total;
+}
+
+// PT_OPT_LAST_ANYHIT: the last shade launch behind k_wf_extend<.., ANY>.  The hit slot holds (ts, sphere) of the segment's nearest
+// sphere, t = 0 when a triangle lies at or before it: a triangle emits nothing (the launch is only chosen when none can), a sphere
+// adds path_last_emission's 0 + mask * emission, neither is the background rule of wf_shade_segment.  No ray, no sphere tests.
+template <bool COUNT, int FOLD>
+__global__ void __launch_bounds__(PT_BLOCK) k_wf_shade_last_any(const KParams P) {
+    const uint32_t region = blockIdx.x;
+    const int n_in = P.wf.cnt_in[region];
+    if (n_in == 0) {
+        if constexpr (FOLD > 0) wf_fold_region<FOLD>(P, region);
+        return;
+    }
+    wf_sphere_table();
+    const size_t i = (size_t)region * PT_REGION + threadIdx.x;
+    const bool have = (int)threadIdx.x < n_in;
+    bool tri_hit = false;
+    if (have) {
+        const float4 b = pt_sld4(P.wf.ray1_in + i);
+        const float2 hh = pt_sld2(P.wf.hit + i);
+        const v3 mask = V3(pt_sld1(P.wf.mask_in + i), pt_sld1(P.wf.mask_in + (size_t)P.wf.cap + i), pt_sld1(P.wf.mask_in + 2 * (size_t)P.wf.cap + i));
+        const uint32_t pix = __float_as_uint(b.z), s_idx = __float_as_uint(b.w) >> 12;
+        float* smp = pt_sample_ptr(P, s_idx, (size_t)pix);
+        const int sph = __float_as_int(hh.y);
+        tri_hit = hh.x == 0.0f;
+        if (!tri_hit && sph >= 0) {
+            const float* t = (const float*)s_dyn + 11 * sph;
+            const v3 e = vadd(V3(0.f, 0.f, 0.f), vmul(mask, V3(t[4], t[5], t[6])));
+            if (!(e.x == 0.f) || !(e.y == 0.f) || !(e.z == 0.f)) { smp[0] += e.x; smp[1] += e.y; smp[2] += e.z; }
+        } else if (!tri_hit) {   // tracer.cu:140-142
+            PT_KARGS(K);
+            if (K.flags & PT_FLAG_MISS_KEEPS_PATH) {
+                smp[0] += mask.x * K.bk[0]; smp[1] += mask.y * K.bk[1]; smp[2] += mask.z * K.bk[2];
+            } else {
+                smp[0] = K.bk[0]; smp[1] = K.bk[1]; smp[2] = K.bk[2];
+            }
+        }
+    }
+    if (COUNT) {   // all 64 lanes of every wave are here
+        const uint32_t nh = wave_sum_u32(tri_hit ? 1u : 0u), np = wave_sum_u32(have ? 1u : 0u);
+        if ((threadIdx.x & 63) == 0) {
+            atomicAdd(&P.counters[4], (unsigned long long)nh);
+            atomicAdd(&P.counters[5], (unsigned long long)np);
+        }
+    }
+    if constexpr (FOLD > 0) {
+        __syncthreads();   // (as in k_wf_shade: the emission adds above reach the folding wave)
+        wf_fold_region<FOLD>(P, region);
+    }
 }
 
 // bounce 0's packet walk and its shade in ONE launch (PT_OPT_FUSE_STAGES 1: the product launch without PT_FLAG_NEE).  One block
 // per region, as both launches it replaces run, so lane = slot of k_wf_shade<FIRST>: after trav_packet_wide the lane shades its
 // own hit with the camera ray and RNG state it started the walk with — no hit record written and read back, no camera ray
 // computed twice — and the survivors are packed as k_wf_shade<FIRST> packs them (same records, same order).
+// BOUND: as k_wf_shade's (depth 2: bounce 0's survivors are the last segments).
+template <bool BOUND>
 __global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet_shade(const KParams P) {
     __shared__ int s_cnt[PT_BLOCK / 64];
     wf_sphere_table();
@@ -431,6 +508,8 @@ __global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet_shade(const KP
         alive = wf_shade_segment<false, true, false>(P, ps, h, tri_hit, pt_sample_ptr(P, s_idx, (size_t)pix), nullptr);
     }
     if (P.wf.bounce + 1 >= P.depth) return;   // depth 1
+    float2 bound = make_float2(PT_F32_MAX, __int_as_float(-1));
+    if (BOUND && alive) bound = wf_sphere_bound(P, ps);
     int total;
     const int r = PT_SURVIVOR_RANK(P, alive, ps, total, s_cnt);
     if (alive) {
@@ -440,6 +519,7 @@ __global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet_shade(const KP
         pt_sst1(P.wf.mask_out + j, ps.mask.x);
         pt_sst1(P.wf.mask_out + (size_t)P.wf.cap + j, ps.mask.y);
         pt_sst1(P.wf.mask_out + 2 * (size_t)P.wf.cap + j, ps.mask.z);
+        if (BOUND) pt_sst2(P.wf.hit + j, bound);
     }
     if (threadIdx.x == 0) P.wf.cnt_out[region] = total;
 }
@@ -566,19 +646,19 @@ int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles, 
     const size_t lds_shade = 15 * PT_KSPHERES * 4;
     // launchers: the extend stage's persistent grid (resident blocks, at most `blocks_per_cu` per CU) and the shade stage's one
     // block per region, for the launch parameters Q on stream s
-#define PT_EXT(COUNT, OCC, LSTK, FIRST)                                                                           \
+#define PT_EXT(COUNT, OCC, LSTK, FIRST, ANY)                                                                         \
         do {                                                                                                      \
             int per_cu = 0;                                                                                       \
-            if (allow_lds(k_wf_extend<COUNT, OCC, LSTK, FIRST>, lds_ext) != hipSuccess) return hipErrorInvalidValue; \
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_wf_extend<COUNT, OCC, LSTK, FIRST>, PT_BLOCK, lds_ext) != hipSuccess || per_cu < 1) \
+            if (allow_lds(k_wf_extend<COUNT, OCC, LSTK, FIRST, ANY>, lds_ext) != hipSuccess) return hipErrorInvalidValue; \
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_wf_extend<COUNT, OCC, LSTK, FIRST, ANY>, PT_BLOCK, lds_ext) != hipSuccess || per_cu < 1) \
                 per_cu = 1;                                                                                       \
             per_cu = std::min(per_cu, blocks_per_cu);                                                             \
-            hipLaunchKernelGGL((k_wf_extend<COUNT, OCC, LSTK, FIRST>), dim3((unsigned)std::min<size_t>((size_t)per_cu * L.n_cu, (size_t)Q.wf.n_regions)), \
+            hipLaunchKernelGGL((k_wf_extend<COUNT, OCC, LSTK, FIRST, ANY>), dim3((unsigned)std::min<size_t>((size_t)per_cu * L.n_cu, (size_t)Q.wf.n_regions)), \
                                dim3(PT_BLOCK), lds_ext, s, Q);                                                    \
         } while (0)
     // bounce 0 as wave-wide packets (PT_OPT_FIRST_WALK 1) when the tree fits the packet stack budget (PT_OPT_PACKET_STACK)
     const bool packet = c->opt_first_walk == 1 && 3 * c->wide_depth + 2 <= (uint32_t)c->opt_packet_stack;
-    auto launch_extend = [&](const KParams& Q, bool first, hipStream_t s, int blocks_per_cu) -> hipError_t {
+    auto launch_extend = [&](const KParams& Q, bool first, hipStream_t s, int blocks_per_cu, bool any = false) -> hipError_t {
         if (first && packet) {   // one block per region (4 groups); instrumented: the resident grid, 8 blocks per CU
 #ifdef PT_PACKET_RESIDENT_GRID   // experiment (tools/build_variant.sh): the product launch on the resident grid too
             const size_t n_blk = std::min<size_t>((size_t)Q.wf.n_regions, (size_t)8 * L.n_cu);
@@ -588,24 +668,51 @@ int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles, 
             if (L.count) hipLaunchKernelGGL(k_wf_extend_packet<true>, dim3((unsigned)n_blk), dim3(PT_BLOCK), 0, s, Q);
             else hipLaunchKernelGGL(k_wf_extend_packet<false>, dim3((unsigned)n_blk), dim3(PT_BLOCK), 0, s, Q);
         } else if (first) {
-            if (L.count) { if (L.lstk == 24) PT_EXT(true, 6, 24, true); else PT_EXT(true, 8, 16, true); }
-            else { if (L.lstk == 24) PT_EXT(false, 6, 24, true); else PT_EXT(false, 8, 16, true); }
+            if (L.count) { if (L.lstk == 24) PT_EXT(true, 6, 24, true, false); else PT_EXT(true, 8, 16, true, false); }
+            else { if (L.lstk == 24) PT_EXT(false, 6, 24, true, false); else PT_EXT(false, 8, 16, true, false); }
+        } else if (any) {   // the last segment as an any-hit query (PT_OPT_LAST_ANYHIT)
+            if (L.count) { if (L.lstk == 24) PT_EXT(true, 6, 24, false, true); else PT_EXT(true, 8, 16, false, true); }
+            else { if (L.lstk == 24) PT_EXT(false, 6, 24, false, true); else PT_EXT(false, 8, 16, false, true); }
         } else {
-            if (L.count) { if (L.lstk == 24) PT_EXT(true, 6, 24, false); else PT_EXT(true, 8, 16, false); }
-            else { if (L.lstk == 24) PT_EXT(false, 6, 24, false); else PT_EXT(false, 8, 16, false); }
+            if (L.count) { if (L.lstk == 24) PT_EXT(true, 6, 24, false, false); else PT_EXT(true, 8, 16, false, false); }
+            else { if (L.lstk == 24) PT_EXT(false, 6, 24, false, false); else PT_EXT(false, 8, 16, false, false); }
         }
         return hipGetLastError();
     };
 #undef PT_EXT
 #define PT_SHADE(COUNT, NEE, FIRST) \
         hipLaunchKernelGGL((k_wf_shade<COUNT, NEE, FIRST>), dim3((unsigned)Q.wf.n_regions), dim3(PT_BLOCK), lds_shade, s, Q)
+#define PT_SHADE_BOUND(COUNT, FIRST) \
+        hipLaunchKernelGGL((k_wf_shade<COUNT, false, FIRST, false, 0, true>), dim3((unsigned)Q.wf.n_regions), dim3(PT_BLOCK), lds_shade, s, Q)
+#define PT_SHADE_ANY(COUNT, FOLD) \
+        hipLaunchKernelGGL((k_wf_shade_last_any<COUNT, FOLD>), dim3((unsigned)Q.wf.n_regions), dim3(PT_BLOCK), lds_shade, s, Q)
     // PT_OPT_FUSE_STAGES 1, the product launch without PT_FLAG_NEE: bounce 0's shade runs in the packet walk's launch, and the last
     // shade launch folds the samples when every region holds all samples of its pixels (sample groups of spp = 16, 8 or 4)
     const bool fuse = c->opt_fuse_stages != 0 && !nee && !L.count;
     const bool fuse_first = fuse && packet;
     const int fold_lp = fuse && P.depth >= 2 && P.sgroup_log2 >= 2 && P.sgroup_log2 <= 4 && P.spp == (1u << P.sgroup_log2) ? (int)P.spp / 4 : 0;
     folded = fold_lp != 0;
+    // PT_OPT_LAST_ANYHIT: when no triangle can emit, the last segment of a path reaches the picture only through the sphere or the
+    // background it ends on.  The shade launch of bounce depth - 2 leaves the nearest sphere of every survivor's new ray in its hit
+    // slot, the walk of bounce depth - 1 is an any-hit query bounded by it, and the last shade launch reads the verdict.
+    // Instrumented launches take part with the value 2 only: their counters stay those of the closest-hit walk otherwise.
+    const bool tri_dark = P.tri_emi[0] == 0.f && P.tri_emi[1] == 0.f && P.tri_emi[2] == 0.f;
+    const bool anyhit = (L.count ? c->opt_last_anyhit == 2 : c->opt_last_anyhit >= 1) && P.depth >= 2 && !nee && !P.tri_matid && tri_dark &&
+                        P.sc.n_spheres <= PT_KSPHERES && !c->records_woop;
     auto launch_shade = [&](const KParams& Q, bool first, hipStream_t s) -> hipError_t {
+        if (anyhit && Q.wf.bounce + 1 >= Q.depth) {   // behind the any-hit walk: the verdict's emission only
+            if (L.count) PT_SHADE_ANY(true, 0);
+            else if (fold_lp == 4) PT_SHADE_ANY(false, 4);
+            else if (fold_lp == 2) PT_SHADE_ANY(false, 2);
+            else if (fold_lp == 1) PT_SHADE_ANY(false, 1);
+            else PT_SHADE_ANY(false, 0);
+            return hipGetLastError();
+        }
+        if (anyhit && Q.wf.bounce + 2 == Q.depth) {   // its survivors' rays are the last segments: their sphere bound
+            if (first) { if (L.count) PT_SHADE_BOUND(true, true); else PT_SHADE_BOUND(false, true); }
+            else { if (L.count) PT_SHADE_BOUND(true, false); else PT_SHADE_BOUND(false, false); }
+            return hipGetLastError();
+        }
         if (!first && !nee && !L.count && Q.wf.bounce + 1 >= Q.depth) {   // the final bounce: emission only
             const dim3 grid((unsigned)Q.wf.n_regions);
             if (fold_lp == 4) hipLaunchKernelGGL((k_wf_shade<false, false, false, true, 4>), grid, dim3(PT_BLOCK), lds_shade, s, Q);
@@ -624,6 +731,8 @@ int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles, 
         return hipGetLastError();
     };
 #undef PT_SHADE
+#undef PT_SHADE_BOUND
+#undef PT_SHADE_ANY
     auto set_bounce = [&](KParams& Q, uint32_t b) {
         const int g = (int)(b & 1u);
         Q.wf.bounce = b;
@@ -635,12 +744,13 @@ int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles, 
         set_bounce(P, b);
         P.wf.queue = queues + (size_t)b * PT_SHARDS * PT_SHARD_STRIDE;
         if (b == 0 && fuse_first) {   // walk + shade of bounce 0, booked as the extend stage
-            hipLaunchKernelGGL(k_wf_extend_packet_shade, dim3((unsigned)n_regions), dim3(PT_BLOCK), lds_shade, st, P);
+            if (anyhit && P.depth == 2) hipLaunchKernelGGL(k_wf_extend_packet_shade<true>, dim3((unsigned)n_regions), dim3(PT_BLOCK), lds_shade, st, P);
+            else hipLaunchKernelGGL(k_wf_extend_packet_shade<false>, dim3((unsigned)n_regions), dim3(PT_BLOCK), lds_shade, st, P);
             HIP_TRY(c, hipGetLastError());
             if (stage_mark(c, PT_STAGE_EXTEND) != PT_OK) return PT_ERR_DEVICE;
             continue;
         }
-        HIP_TRY(c, launch_extend(P, b == 0, st, c->opt_wave_blocks));
+        HIP_TRY(c, launch_extend(P, b == 0, st, c->opt_wave_blocks, anyhit && b + 1 == P.depth));
         if (stage_mark(c, PT_STAGE_EXTEND) != PT_OK) return PT_ERR_DEVICE;
         HIP_TRY(c, launch_shade(P, b == 0, st));
         if (stage_mark(c, PT_STAGE_SHADE) != PT_OK) return PT_ERR_DEVICE;

@@ -379,7 +379,10 @@ __device__ __forceinline__ void wide_node_keys(const WideNode& w, float idx, flo
 
 // AHEAD: request a leaf's second record together with its first (see the record step); costs 12 VGPRs while the
 // records are in flight, so only the kernel whose lanes carry nothing but the walk (k_wf_extend) asks for it.
-template <bool COUNT, bool DYN, bool WOOP, bool AHEAD = false, class STK>
+// ANY (exact records only): an any-hit query — is there a record with 0 < t < s.h.t, the bound the caller starts the lane with?
+// The lane leaves at the first such record (no further record of the leaf, nothing popped) with s.h.t = 0; a lane that found
+// none keeps its bound.  h.tri / h.rec are not written.
+template <bool COUNT, bool DYN, bool WOOP, bool AHEAD = false, bool ANY = false, class STK>
 __device__ __forceinline__ bool trav_run_wide(TravState& s, const KScene& sc, v3 o, v3 d, bool cull, STK& stk,
                                               TravCount& tc, int n_dead, int batch) {
     int cur = s.node, sp = s.sp;
@@ -457,6 +460,35 @@ __device__ __forceinline__ bool trav_run_wide(TravState& s, const KScene& sc, v3
                 t = pt_mt_intersect(v0, e1, e2, o, d, cull);
                 id = __float_as_int(q0.w);
                 last = __float_as_int(q1.w) != 0;
+            }
+            if constexpr (ANY) {
+                bool occ = t > 0.0f && t < h.t;
+                int aa = a;
+                if (AHEAD && !last && !occ) {   // the record requested ahead
+                    aa += 4;
+                    if (COUNT) tc.tris++;
+                    const float t2 = pt_mt_intersect(V3(x0.x, x0.y, x0.z), V3(x1.x, x1.y, x1.z), V3(x2.x, x2.y, x2.z), o, d, cull);
+                    last = __float_as_int(x1.w) != 0;
+                    occ = t2 > 0.0f && t2 < h.t;
+                }
+                while (!last && !occ) {
+                    aa += 4;
+                    float4 r0, r1, r2;
+                    pt_ld4x3(sc.nodes + aa, r0, r1, r2);
+                    if (COUNT) tc.tris++;
+                    const float t2 = pt_mt_intersect(V3(r0.x, r0.y, r0.z), V3(r1.x, r1.y, r1.z), V3(r2.x, r2.y, r2.z), o, d, cull);
+                    last = __float_as_int(r1.w) != 0;
+                    occ = t2 > 0.0f && t2 < h.t;
+                }
+                if (occ) {   // the query is answered: the lane is done
+                    h.t = 0.0f;
+                    cur = PT_SENTINEL;
+                } else {
+                    cur = stk.get(sp);
+                    sp--;
+                    if (COUNT && cur < 0 && cur != PT_SENTINEL) tc.leaves++;
+                }
+                continue;
             }
             if (t > 0.0f && (t < h.t || (t == h.t && h.tri != -1 && id < h.tri))) {
                 h.t = t;

@@ -324,6 +324,10 @@ int pt_set_option(pt_ctx* c, int option, int value) {
             if (value != 0 && value != 1) return fail(c, PT_ERR_INVALID, "pt_set_option: fuse stages must be 0 (separate launches) or 1");
             c->opt_fuse_stages = value;
             return PT_OK;
+        case PT_OPT_LAST_ANYHIT:
+            if (value < 0 || value > 2) return fail(c, PT_ERR_INVALID, "pt_set_option: last any-hit must be 0 (off), 1 (product launches) or 2 (instrumented launches too)");
+            c->opt_last_anyhit = value;
+            return PT_OK;
         default: return fail(c, PT_ERR_INVALID, "pt_set_option: unknown option");
     }
 }

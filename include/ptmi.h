@@ -210,11 +210,20 @@ enum {
     PT_OPT_LEAF_MAX = 9,      /* leaves holding more triangle references than this are split
                                  at the next pt_upload_bvh (0 = keep the producer's leaves;
                                  default 2)                                                   */
-    PT_OPT_FUSE_STAGES = 28   /* PT_KERNEL_WAVEFRONT without PT_FLAG_NEE or PT_OPT_COUNTERS: 1 (default) = bounce 0 is shaded in
+    PT_OPT_FUSE_STAGES = 28,  /* PT_KERNEL_WAVEFRONT without PT_FLAG_NEE or PT_OPT_COUNTERS: 1 (default) = bounce 0 is shaded in
                                  the launch of its packet walk (no hit records of bounce 0), and when every region of the call holds
                                  all samples of its pixels (PT_OPT_WAVE_SAMPLES groups of spp = 16, 8 or 4, depth >= 2) the last
                                  shade launch folds them into the accumulator (no separate fold launch); 0 = one launch per
                                  stage.  Same images, same counters                                                     */
+    PT_OPT_LAST_ANYHIT = 29   /* PT_KERNEL_WAVEFRONT: after `depth` segments only the gathered light is returned, so a path's last
+                                 segment matters only through the emission of what it ends on.  When no triangle can emit (tri_emi
+                                 all zero, no pt_upload_tri_materials table; also depth >= 2, no PT_FLAG_NEE, at most 8 spheres,
+                                 PT_OPT_TRI_TEST 0) the shade launch before it records the nearest sphere hit ts of the new ray, and
+                                 the last walk only answers "is a triangle hit at t <= ts?", leaving at the first such record
+                                 instead of finding the closest one.  1 (default) = product launches do so; 2 = instrumented
+                                 (PT_OPT_COUNTERS) launches too: pt_get_counters then counts the shorter walk and
+                                 pt_get_wave_stats [5] the rays of that launch (0 = it did not run); 0 = closest hit on every
+                                 segment.  With 0 or 1 the counters are those of the closest-hit walk.  Same images            */
 };
 
 /* CamInfo, GpuPathTracer/CpuStructs.hpp:19-28 (pitch/yaw/dirty/bias/enabled are host-only
@@ -426,7 +435,7 @@ int pt_get_counters(pt_ctx* ctx, pt_counters* out);
  * [8] outer-loop iterations  [9] traversal-stack pushes that overflowed the LDS window into
  * private memory (PT_OPT_LDS_STACK).  A wave-iteration with all 64 lanes active is 100 % use.
  * PT_KERNEL_WAVEFRONT: [0]-[3] and [6]-[9] are the extend stage's ([6]/[7] = refill passes), its
- * shade stage runs one lane per live path ([5] stays 0); [4] counts the 64-ray groups the bounce-0
+ * shade stage runs one lane per live path ([5] = the rays of the any-hit launch, PT_OPT_LAST_ANYHIT 2, else 0); [4] counts the 64-ray groups the bounce-0
  * packet walk (PT_OPT_FIRST_WALK 1) walked — 0 when bounce 0 ran the per-lane walk — and that
  * launch books its wave node / record steps and the lanes of their masks in [0]-[3]. */
 #define PT_WAVE_STATS 10
