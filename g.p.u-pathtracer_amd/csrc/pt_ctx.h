@@ -5,8 +5,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ptmi.h"
@@ -181,6 +183,30 @@ inline size_t lds_bytes(int n_top, int stack_n, int block) { return (size_t)n_to
 template <typename K>
 hipError_t allow_lds(K kernel, size_t bytes) {
     return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+
+// ---- compile-time dispatch: generic lambdas take template arguments as std::integral_constant values; only the combinations a
+// lambda is CALLED with are instantiated
+template <int V> constexpr std::integral_constant<int, V> int_c{};
+template <class F>   // f(true_type) or f(false_type), by v
+auto with_bool(bool v, F&& f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+template <int V0, int... Vs, class F>   // f(int_c<V>) for the listed V that equals v, the LAST listed one when none does
+auto with_int(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) return f(int_c<V0>);
+    else return v == V0 ? f(int_c<V0>) : with_int<Vs...>(v, f);
+}
+
+// A grid of resident blocks for a kernel whose waves draw work from a queue: what the device holds at once (at most `max_per_cu` per
+// CU), never more than `work_cap`.  No grid-wide wait anywhere: an over-estimate only means a few late blocks find the queue empty.
+template <class K>
+hipError_t launch_resident(K kernel, size_t lds, int max_per_cu, int n_cu, size_t work_cap, hipStream_t st, const KParams& P) {
+    int per_cu = 0;
+    const hipError_t e = allow_lds(kernel, lds);
+    if (e != hipSuccess) return e;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, PT_BLOCK, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    per_cu = std::min(per_cu, max_per_cu);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<size_t>((size_t)per_cu * n_cu, work_cap)), dim3(PT_BLOCK), lds, st, P);
+    return hipGetLastError();
 }
 
 // ---- launchers of the kernel families (one translation unit each) -------------------------------

@@ -40,7 +40,6 @@ __global__ void __launch_bounds__(PT_BLOCK_RAYS) k_render_aux(const KParams P, c
     v3 o, d;
     pt_camera_ray(P.cam, P.W, P.H, px, py, 0.0f, 0.0f, o, d);   // u0 = u1 = 0.5: the pixel centre
     TravCount tc;
-    tc.inner = tc.tris = tc.leaves = 0;
     TravOverflow<PT_STACK_CAP> stk_ovf;
     TravStack<PT_STACK_CAP, PT_BLOCK_RAYS> stk(__builtin_amdgcn_readfirstlane(16 * P.sc.n_top + (tid & ~63)), stk_ovf);
     const Hit h = trav_bvh2<false, true>(P.sc, o, d, P.cull != 0, stk, tc, s_top);

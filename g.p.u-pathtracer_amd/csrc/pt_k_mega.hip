@@ -29,7 +29,6 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_trace_mega_bvh2(const KParams
     TravStack<LSTK, PT_BLOCK> stk(__builtin_amdgcn_readfirstlane(16 * P.sc.n_top + (tid & ~63)), stk_ovf);
 
     TravCount tc;
-    tc.inner = tc.tris = tc.leaves = 0;
     uint32_t n_rays = 0, n_hits = 0;
 
     uint32_t n_done = P.spp;
@@ -50,15 +49,12 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_trace_mega_bvh2(const KParams
         if ((P.flags & PT_FLAG_WRITE_RGBA) && P.rgba) P.rgba[pix] = pt_pack_rgba(ax, ay, az);
     }
     if (COUNT) {
-        const uint32_t a = wave_sum_u32(n_rays), b = wave_sum_u32(tc.inner), c = wave_sum_u32(tc.tris);
-        const uint32_t dd = wave_sum_u32(tc.leaves), e = wave_sum_u32(n_hits), f = wave_sum_u32(n_done);
-        if (__ffsll((long long)__ballot(1)) - 1 == lane) {
-            atomicAdd(&P.counters[0], (unsigned long long)a);
-            atomicAdd(&P.counters[1], (unsigned long long)b);
-            atomicAdd(&P.counters[2], (unsigned long long)c);
-            atomicAdd(&P.counters[3], (unsigned long long)dd);
-            atomicAdd(&P.counters[4], (unsigned long long)e);
-            atomicAdd(&P.counters[5], (unsigned long long)f);
+        const bool booker = __ffsll((long long)__ballot(1)) - 1 == lane;
+        const uint32_t e = wave_sum_u32(n_hits), f = wave_sum_u32(n_done);
+        pt_book_walk<false>(P, booker, n_rays, tc);   // (no wave statistics: they are the persistent walks')
+        if (booker) {
+            atomicAdd(&P.counters[PT_CNT_HITS], (unsigned long long)e);
+            atomicAdd(&P.counters[PT_CNT_PATHS], (unsigned long long)f);
         }
     }
 }
@@ -73,7 +69,6 @@ __global__ void __launch_bounds__(PT_BLOCK_RAYS) k_trace_rays_bvh2(const KScene 
     if (i >= n) return;
     const float4 ro = rays[2 * i], rd = rays[2 * i + 1];
     TravCount tc;
-    tc.inner = tc.tris = tc.leaves = 0;
     TravOverflow<PT_STACK_CAP> stk_ovf;
     TravStack<PT_STACK_CAP, PT_BLOCK_RAYS> stk(__builtin_amdgcn_readfirstlane(16 * sc.n_top + ((int)threadIdx.x & ~63)), stk_ovf);
     const Hit h = trav_bvh2<false, true>(sc, V3(ro.x, ro.y, ro.z), V3(rd.x, rd.y, rd.z), cull != 0, stk, tc, s_top);
@@ -90,30 +85,19 @@ namespace ptmi {
 // Instantiated register / stack budgets: (8 waves/SIMD, 16-entry LDS window), (4, 16), (4, all 72 in LDS);
 // other requests run the nearest one (they are speed knobs, never results).
 hipError_t launch_mega(const LaunchCfg& L, const KParams& P, hipStream_t st) {
-#define PT_GO(COUNT, OCC, LSTK, ALG)                                                                             \
-    do {                                                                                                         \
-        hipError_t e_ = allow_lds(k_trace_mega_bvh2<COUNT, OCC, LSTK, ALG>, L.lds);                              \
-        if (e_ != hipSuccess) return e_;                                                                         \
-        hipLaunchKernelGGL((k_trace_mega_bvh2<COUNT, OCC, LSTK, ALG>), dim3(L.blocks), dim3(PT_BLOCK), L.lds, st, P); \
-        return hipGetLastError();                                                                                \
-    } while (0)
-#define PT_GO_ALG(COUNT, OCC, LSTK)                        \
-    do {                                                   \
-        if (L.walk >= 2) PT_GO(COUNT, OCC, LSTK, 2);       \
-        else if (L.walk == 1) PT_GO(COUNT, OCC, LSTK, 1);  \
-        else PT_GO(COUNT, OCC, LSTK, 0);                   \
-    } while (0)
-#define PT_GO_CFG(COUNT)                                                   \
-    do {                                                                   \
-        if (L.lstk >= PT_STACK_CAP) PT_GO_ALG(COUNT, 4, PT_STACK_CAP);     \
-        else if (L.occ >= 5) PT_GO_ALG(COUNT, 8, 16);                      \
-        else PT_GO_ALG(COUNT, 4, 16);                                      \
-    } while (0)
-    if (L.count) PT_GO_CFG(true);
-    else PT_GO_CFG(false);
-#undef PT_GO_CFG
-#undef PT_GO_ALG
-#undef PT_GO
+    auto go = [&](auto count, auto occ, auto lstk) {
+        return with_int<2, 1, 0>(std::min(L.walk, 2), [&](auto alg) {
+            const auto kernel = k_trace_mega_bvh2<count(), occ(), lstk(), alg()>;
+            const hipError_t e = allow_lds(kernel, L.lds);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(kernel, dim3(L.blocks), dim3(PT_BLOCK), L.lds, st, P);
+            return hipGetLastError();
+        });
+    };
+    return with_bool(L.count, [&](auto count) {
+        if (L.lstk >= PT_STACK_CAP) return go(count, int_c<4>, int_c<PT_STACK_CAP>);
+        return L.occ >= 5 ? go(count, int_c<8>, int_c<16>) : go(count, int_c<4>, int_c<16>);
+    });
 }
 
 hipError_t launch_rays(const KScene& sc, size_t lds, const float4* rays, size_t n, int cull, float* t_out, int* tri_out,

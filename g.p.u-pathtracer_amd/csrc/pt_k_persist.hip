@@ -50,11 +50,9 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_trace_persist_bvh2(const KPar
     ps.depth = 0; ps.rng.s0 = ps.rng.s1 = ps.rng.n = 0;
     ts.idx = ts.idy = ts.idz = ts.oodx = ts.oody = ts.oodz = 0.f;
     ts.node = PT_SENTINEL; ts.leaf = 0; ts.sp = 0;
-    ts.h.t = PT_F32_MAX; ts.h.tri = -1; ts.h.rec = 0;
+    ts.h = pt_no_hit();
 
     TravCount tc;
-    tc.inner = tc.tris = tc.leaves = 0;
-    tc.it_node = tc.act_node = tc.it_rec = tc.act_rec = 0;
     uint32_t n_rays = 0, n_hits = 0, n_paths = 0;
     uint32_t it_begin = 0, act_begin = 0, it_shade = 0, act_shade = 0, it_loop = 0;  // COUNT only
 
@@ -106,12 +104,14 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_trace_persist_bvh2(const KPar
                             path_begin(P, px, py, (uint64_t)pix, P.frame + s_idx, ps);
                             if (P.depth == 0) {
                                 phase = PH_SHADE;
+                                // (not pt_no_hit(): nothing reads the hit at depth 0, and with h.rec written here too, or with
+                                // nothing written, every product instantiation of this kernel allocates its registers anew)
                                 ts.h.t = PT_F32_MAX; ts.h.tri = -1;
                             } else if (P.sc.has_bvh) {
                                 trav_begin(ts, ps.o, ps.d, stk, ALG >= 2 ? P.sc.wide_root : 0);
                                 phase = PH_TRAV;
                             } else {
-                                ts.h.t = PT_F32_MAX; ts.h.tri = -1; ts.h.rec = 0;
+                                ts.h = pt_no_hit();
                                 phase = PH_SHADE;
                             }
                             started = true;
@@ -180,30 +180,18 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_trace_persist_bvh2(const KPar
     }
 
     if (COUNT) {
-        const uint32_t a = wave_sum_u32(n_rays), b = wave_sum_u32(tc.inner), c = wave_sum_u32(tc.tris);
-        const uint32_t dd = wave_sum_u32(tc.leaves), e = wave_sum_u32(n_hits), f = wave_sum_u32(n_paths);
-        // the walk books its iterations in whichever lane is first among those inside it: sum the lanes
-        const uint32_t w_it_node = wave_sum_u32(tc.it_node), w_act_node = wave_sum_u32(tc.act_node);
-        const uint32_t w_it_rec = wave_sum_u32(tc.it_rec), w_act_rec = wave_sum_u32(tc.act_rec);
-        const uint32_t w_ovf = wave_sum_u32(stk.n_ovf);
+        const uint32_t e = wave_sum_u32(n_hits), f = wave_sum_u32(n_paths), w_ovf = wave_sum_u32(stk.n_ovf);
+        pt_book_walk<true>(P, lane == 0, n_rays, tc);
         if (lane == 0) {
-            atomicAdd(&P.counters[0], (unsigned long long)a);
-            atomicAdd(&P.counters[1], (unsigned long long)b);
-            atomicAdd(&P.counters[2], (unsigned long long)c);
-            atomicAdd(&P.counters[3], (unsigned long long)dd);
-            atomicAdd(&P.counters[4], (unsigned long long)e);
-            atomicAdd(&P.counters[5], (unsigned long long)f);
+            atomicAdd(&P.counters[PT_CNT_HITS], (unsigned long long)e);
+            atomicAdd(&P.counters[PT_CNT_PATHS], (unsigned long long)f);
             // schedule statistics, one contribution per wave (pt_get_wave_stats)
-            atomicAdd(&P.counters[6], (unsigned long long)w_it_node);
-            atomicAdd(&P.counters[7], (unsigned long long)w_act_node);
-            atomicAdd(&P.counters[8], (unsigned long long)w_it_rec);
-            atomicAdd(&P.counters[9], (unsigned long long)w_act_rec);
-            atomicAdd(&P.counters[10], (unsigned long long)it_shade);
-            atomicAdd(&P.counters[11], (unsigned long long)act_shade);
-            atomicAdd(&P.counters[12], (unsigned long long)it_begin);
-            atomicAdd(&P.counters[13], (unsigned long long)act_begin);
-            atomicAdd(&P.counters[14], (unsigned long long)it_loop);
-            atomicAdd(&P.counters[15], (unsigned long long)w_ovf);
+            atomicAdd(&P.counters[PT_CNT_IT_SHADE], (unsigned long long)it_shade);
+            atomicAdd(&P.counters[PT_CNT_ACT_SHADE], (unsigned long long)act_shade);
+            atomicAdd(&P.counters[PT_CNT_IT_BEGIN], (unsigned long long)it_begin);
+            atomicAdd(&P.counters[PT_CNT_ACT_BEGIN], (unsigned long long)act_begin);
+            atomicAdd(&P.counters[PT_CNT_IT_LOOP], (unsigned long long)it_loop);
+            atomicAdd(&P.counters[PT_CNT_STACK_OVF], (unsigned long long)w_ovf);
         }
     }
 }
@@ -252,42 +240,18 @@ namespace ptmi {
 // leaf) get (4,16) (6,16) (6,24) (8,16) (4,72); the two exact binary walks (parity variants) (8,16) and
 // (4,72).  Other requests run the nearest one: they are speed knobs, never results.
 hipError_t launch_persist(const LaunchCfg& L, const KParams& P, hipStream_t st) {
-#define PT_GO(COUNT, OCC, LSTK, ALG)                                                                               \
-    do {                                                                                                           \
-        int per_cu = 0;                                                                                            \
-        hipError_t e_ = allow_lds(k_trace_persist_bvh2<COUNT, OCC, LSTK, ALG>, L.lds);                             \
-        if (e_ != hipSuccess) return e_;                                                                           \
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_trace_persist_bvh2<COUNT, OCC, LSTK, ALG>,    \
-                                                         PT_BLOCK, L.lds) != hipSuccess || per_cu < 1)            \
-            per_cu = 1;                                                                                            \
-        /* grid = resident blocks only (no grid-wide wait anywhere, so an over-estimate only means a few late */  \
-        /* blocks find the queue empty and exit) */                                                                \
-        hipLaunchKernelGGL((k_trace_persist_bvh2<COUNT, OCC, LSTK, ALG>),                                          \
-                           dim3(std::min(per_cu * L.n_cu, std::max(1, L.work_blocks))), dim3(PT_BLOCK), L.lds, st, P); \
-        return hipGetLastError();                                                                                  \
-    } while (0)
-#define PT_GO_WIDE(COUNT, OCC, LSTK)                       \
-    do {                                                   \
-        if (L.walk == 4) PT_GO(COUNT, OCC, LSTK, 4);       \
-        else if (L.walk == 3) PT_GO(COUNT, OCC, LSTK, 3);  \
-        else PT_GO(COUNT, OCC, LSTK, 2);                   \
-    } while (0)
-#define PT_GO_CFG(COUNT)                                                               \
-    do {                                                                               \
-        if (L.walk <= 1) {                                                             \
-            if (L.lstk >= PT_STACK_CAP) { if (L.walk == 1) PT_GO(COUNT, 4, PT_STACK_CAP, 1); else PT_GO(COUNT, 4, PT_STACK_CAP, 0); } \
-            else { if (L.walk == 1) PT_GO(COUNT, 8, 16, 1); else PT_GO(COUNT, 8, 16, 0); } \
-        } else if (L.lstk >= PT_STACK_CAP) PT_GO_WIDE(COUNT, 4, PT_STACK_CAP);         \
-        else if (L.lstk == 24) PT_GO_WIDE(COUNT, 6, 24);                               \
-        else if (L.occ >= 8) PT_GO_WIDE(COUNT, 8, 16);                                 \
-        else if (L.occ >= 5) PT_GO_WIDE(COUNT, 6, 16);                                 \
-        else PT_GO_WIDE(COUNT, 4, 16);                                                 \
-    } while (0)
-    if (L.count) PT_GO_CFG(true);
-    else PT_GO_CFG(false);
-#undef PT_GO_CFG
-#undef PT_GO_WIDE
-#undef PT_GO
+    return with_bool(L.count, [&](auto count) {
+        auto go = [&](auto occ, auto lstk, auto alg) {
+            return launch_resident(k_trace_persist_bvh2<count(), occ(), lstk(), alg()>, L.lds, INT_MAX, L.n_cu,
+                                   (size_t)std::max(1, L.work_blocks), st, P);
+        };
+        auto binary = [&](auto occ, auto lstk) { return L.walk == 1 ? go(occ, lstk, int_c<1>) : go(occ, lstk, int_c<0>); };
+        auto wide = [&](auto occ, auto lstk) { return with_int<4, 3, 2>(L.walk, [&](auto alg) { return go(occ, lstk, alg); }); };
+        if (L.walk <= 1) return L.lstk >= PT_STACK_CAP ? binary(int_c<4>, int_c<PT_STACK_CAP>) : binary(int_c<8>, int_c<16>);
+        if (L.lstk >= PT_STACK_CAP) return wide(int_c<4>, int_c<PT_STACK_CAP>);
+        if (L.lstk == 24) return wide(int_c<6>, int_c<24>);
+        return L.occ >= 8 ? wide(int_c<8>, int_c<16>) : L.occ >= 5 ? wide(int_c<6>, int_c<16>) : wide(int_c<4>, int_c<16>);
+    });
 }
 
 hipError_t launch_fold(const KParams& P, hipStream_t st) {

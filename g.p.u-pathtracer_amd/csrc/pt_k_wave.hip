@@ -20,12 +20,7 @@
 //              (tracer.cu:140-142), survivors are packed to the front of their region's next generation with
 //              a ballot + prefix count (v_mbcnt) — dead paths cost nothing in the next stage
 //   k_fold_samples folds the sample colours into the running mean (tracer.cu:386-391), as for every kernel.
-//
-// The path records stream through HBM (read once, written once per stage, 16-byte pieces, coalesced): this
-// is the part of the path loop that is bandwidth work, and the only per-ray state the latency-bound BVH walk
-// still carries is the ray itself.  Why it pays: in the persistent kernel a finished lane idles through other
-// lanes' node steps until 36 of 64 lanes want shading (node steps ran at 55 % lane use, shading passes of
-// ~700 instructions at 56 %, path starts at 20 %); here every stage runs one kind of work.
+// Which of the kernels below a bounce runs: WavePlan, at the end of the file.  Why the split pays: DESIGN.md §5.2.
 #include "pt_ctx.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -102,10 +97,8 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_wf_extend(const KParams P) {
     TravState ts;
     ts.idx = ts.idy = ts.idz = ts.oodx = ts.oody = ts.oodz = 0.f;
     ts.node = PT_SENTINEL; ts.leaf = 0; ts.sp = 0;
-    ts.h.t = PT_F32_MAX; ts.h.tri = -1; ts.h.rec = 0;
+    ts.h = pt_no_hit();
     TravCount tc;
-    tc.inner = tc.tris = tc.leaves = 0;
-    tc.it_node = tc.act_node = tc.it_rec = tc.act_rec = 0;
     uint32_t n_rays = 0, it_begin = 0, act_begin = 0, it_loop = 0;
 
     for (;;) {
@@ -187,24 +180,14 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_wf_extend(const KParams P) {
     }
 
     if (COUNT) {
-        const uint32_t a = wave_sum_u32(n_rays), b = wave_sum_u32(tc.inner), c = wave_sum_u32(tc.tris), dd = wave_sum_u32(tc.leaves);
-        const uint32_t w_it_node = wave_sum_u32(tc.it_node), w_act_node = wave_sum_u32(tc.act_node);
-        const uint32_t w_it_rec = wave_sum_u32(tc.it_rec), w_act_rec = wave_sum_u32(tc.act_rec);
-        const uint32_t w_ovf = wave_sum_u32(stk.n_ovf);
+        const uint32_t w_ovf = wave_sum_u32(stk.n_ovf), w_rays = ANY ? wave_sum_u32(n_rays) : 0u;
+        pt_book_walk<true>(P, lane == 0, n_rays, tc);
         if (lane == 0) {
-            atomicAdd(&P.counters[0], (unsigned long long)a);
-            atomicAdd(&P.counters[1], (unsigned long long)b);
-            atomicAdd(&P.counters[2], (unsigned long long)c);
-            atomicAdd(&P.counters[3], (unsigned long long)dd);
-            atomicAdd(&P.counters[6], (unsigned long long)w_it_node);
-            atomicAdd(&P.counters[7], (unsigned long long)w_act_node);
-            atomicAdd(&P.counters[8], (unsigned long long)w_it_rec);
-            atomicAdd(&P.counters[9], (unsigned long long)w_act_rec);
-            if (ANY) atomicAdd(&P.counters[11], (unsigned long long)a);   // wave stat 5: the rays of the any-hit launch
-            atomicAdd(&P.counters[12], (unsigned long long)it_begin);
-            atomicAdd(&P.counters[13], (unsigned long long)act_begin);
-            atomicAdd(&P.counters[14], (unsigned long long)it_loop);
-            atomicAdd(&P.counters[15], (unsigned long long)w_ovf);
+            if (ANY) atomicAdd(&P.counters[PT_CNT_ANY_RAYS], (unsigned long long)w_rays);
+            atomicAdd(&P.counters[PT_CNT_IT_BEGIN], (unsigned long long)it_begin);
+            atomicAdd(&P.counters[PT_CNT_ACT_BEGIN], (unsigned long long)act_begin);
+            atomicAdd(&P.counters[PT_CNT_IT_LOOP], (unsigned long long)it_loop);
+            atomicAdd(&P.counters[PT_CNT_STACK_OVF], (unsigned long long)w_ovf);
         }
     }
 }
@@ -220,8 +203,6 @@ __global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet(const KParams 
     const uint32_t n_groups = P.wf.n_slots / 64u;   // (n_slots is a multiple of 64)
     const uint32_t stride = gridDim.x * (uint32_t)(PT_BLOCK / 64);
     TravCount tc;
-    tc.inner = tc.tris = tc.leaves = 0;
-    tc.it_node = tc.act_node = tc.it_rec = tc.act_rec = 0;
     uint32_t n_rays = 0, n_walked = 0;
     for (uint32_t group = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (PT_BLOCK / 64) + (threadIdx.x >> 6)));
          group < n_groups; group += stride) {   // (wave-uniform)
@@ -240,20 +221,10 @@ __global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet(const KParams 
         if (in) pt_sst2(P.wf.hit + slot, make_float2(h.t, __int_as_float(h.rec)));
         if (COUNT) { n_rays += in ? 1u : 0u; n_walked++; }
     }
-    if (COUNT && n_walked) {   // 0-3 per lane of the masks; 6-9 wave node / record steps and the lanes in their masks (lane 0 books
-                               // them); 10 (wave stat 4) groups walked
-        const uint32_t a = wave_sum_u32(n_rays), b = wave_sum_u32(tc.inner), c = wave_sum_u32(tc.tris), dd = wave_sum_u32(tc.leaves);
-        if ((threadIdx.x & 63) == 0) {
-            atomicAdd(&P.counters[0], (unsigned long long)a);
-            atomicAdd(&P.counters[1], (unsigned long long)b);
-            atomicAdd(&P.counters[2], (unsigned long long)c);
-            atomicAdd(&P.counters[3], (unsigned long long)dd);
-            atomicAdd(&P.counters[6], (unsigned long long)tc.it_node);
-            atomicAdd(&P.counters[7], (unsigned long long)tc.act_node);
-            atomicAdd(&P.counters[8], (unsigned long long)tc.it_rec);
-            atomicAdd(&P.counters[9], (unsigned long long)tc.act_rec);
-            atomicAdd(&P.counters[10], (unsigned long long)n_walked);
-        }
+    if (COUNT && n_walked) {   // (wave-uniform) rays .. leaves per lane of the masks; the wave's node / record steps and the lanes
+                               // in their masks are lane 0's
+        pt_book_walk<true>(P, (threadIdx.x & 63) == 0, n_rays, tc);
+        if ((threadIdx.x & 63) == 0) atomicAdd(&P.counters[PT_CNT_PACKET_GROUPS], (unsigned long long)n_walked);
     }
 }
 
@@ -267,6 +238,25 @@ __global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet(const KParams 
 #define PT_SURVIVOR_RANK(P, alive, ps, total, s_cnt) wf_block_rank(alive, total, s_cnt)
 #endif
 
+// tracer.cu:140-142: a miss makes the sample the background colour; PT_FLAG_MISS_KEEPS_PATH (extension) adds mask * background (FIRST: to 0)
+template <bool FIRST>
+__device__ __forceinline__ void wf_shade_miss(float* smp, v3 mask) {
+    PT_KARGS(K);
+    if (FIRST && (K.flags & PT_FLAG_MISS_KEEPS_PATH)) {
+        smp[0] = 0.f + mask.x * K.bk[0]; smp[1] = 0.f + mask.y * K.bk[1]; smp[2] = 0.f + mask.z * K.bk[2];
+    } else if (K.flags & PT_FLAG_MISS_KEEPS_PATH) {
+        smp[0] += mask.x * K.bk[0]; smp[1] += mask.y * K.bk[1]; smp[2] += mask.z * K.bk[2];
+    } else {
+        smp[0] = K.bk[0]; smp[1] = K.bk[1]; smp[2] = K.bk[2];
+    }
+}
+// mask * emission of a later bounce's hit, added to the sample colour in place; nothing is touched when it is all zero
+__device__ __forceinline__ void wf_add_emission(float* smp, v3 e) {
+    if (!(e.x == 0.f) || !(e.y == 0.f) || !(e.z == 0.f)) {
+        smp[0] += e.x; smp[1] += e.y; smp[2] += e.z;   // (as ONE dwordx3 each way: the last bounce's launch +6 %)
+    }
+}
+
 // one path's segment after the walk: h = its closest triangle hit (h.tri 0, or the triangle's id with P.tri_matid; -1 on a
 // miss); the spheres, then the background, the emission alone (LAST) or shading + the BRDF sample, the emission going to the
 // sample colour smp (FIRST: written, not added to).  True when the path goes on.
@@ -278,15 +268,8 @@ __device__ __forceinline__ bool wf_shade_segment(const KParams& P, PathState& ps
         tri_n = V3(q3.x, q3.y, q3.z);
     }
     const SceneHit sh = pt_closest_sphere(P, ps.o, ps.d, h, 0);
-    if (sh.geom == 3) {   // tracer.cu:140-142: the sample IS the background colour, whatever was gathered before
-        PT_KARGS(K);
-        if (FIRST && (K.flags & PT_FLAG_MISS_KEEPS_PATH)) {
-            smp[0] = 0.f + ps.mask.x * K.bk[0]; smp[1] = 0.f + ps.mask.y * K.bk[1]; smp[2] = 0.f + ps.mask.z * K.bk[2];
-        } else if (K.flags & PT_FLAG_MISS_KEEPS_PATH) {   // extension: accu (= the sample buffer) + mask * bk
-            smp[0] += ps.mask.x * K.bk[0]; smp[1] += ps.mask.y * K.bk[1]; smp[2] += ps.mask.z * K.bk[2];
-        } else {
-            smp[0] = K.bk[0]; smp[1] = K.bk[1]; smp[2] = K.bk[2];
-        }
+    if (sh.geom == 3) {
+        wf_shade_miss<FIRST>(smp, ps.mask);
         return false;
     }
     v3 col;
@@ -295,9 +278,7 @@ __device__ __forceinline__ bool wf_shade_segment(const KParams& P, PathState& ps
     const v3 e = done ? col : ps.accu;   // mask * emission of this hit (accu entered as 0)
     if (FIRST) {   // accu = 0 (tracer.cu:48) + this hit's emission
         pt_sst3(smp, V3(0.f + e.x, 0.f + e.y, 0.f + e.z));
-    } else if (!(e.x == 0.f) || !(e.y == 0.f) || !(e.z == 0.f)) {
-        smp[0] += e.x; smp[1] += e.y; smp[2] += e.z;   // (as ONE dwordx3 each way: the last bounce's launch +6 %)
-    }
+    } else wf_add_emission(smp, e);
     return !done;
 }
 
@@ -318,9 +299,7 @@ __device__ __forceinline__ void wf_fold_region(const KParams& P, uint32_t region
 // triangle hit, so (PT_F32_MAX, -1) when no sphere qualifies.  With the strict running minimum this is the sphere the loop after
 // the walk picks whenever a sphere wins, so the pair is final: the last segment only asks the triangles for a hit at t <= ts.
 __device__ __forceinline__ float2 wf_sphere_bound(const KParams& P, const PathState& ps) {
-    Hit none;
-    none.t = PT_F32_MAX; none.tri = -1; none.rec = 0;
-    const SceneHit sh = pt_closest_sphere(P, ps.o, ps.d, none, 0);
+    const SceneHit sh = pt_closest_sphere(P, ps.o, ps.d, pt_no_hit(), 0);
     return make_float2(sh.t, __int_as_float(sh.sph_id));
 }
 
@@ -362,16 +341,16 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
             ps.nee_mask = 0;
             uint32_t sn = __float_as_uint(b.w);
             if (NEE) {   // the sphere bits ride above the pixel, the triangle-light bit above the sample number
-                ps.nee_mask = (pix >> 24) | ((sn >> 31) << 8);
-                pix &= 0xffffffu;
-                sn &= 0x7fffffffu;
+                ps.nee_mask = (pix >> PT_REC_PIXEL_BITS) | ((sn >> PT_REC_LIGHT_BIT) << 8);
+                pix &= (1u << PT_REC_PIXEL_BITS) - 1u;
+                sn &= (1u << PT_REC_LIGHT_BIT) - 1u;
             }
-            s_idx = sn >> 12;
+            s_idx = sn >> PT_REC_DRAW_BITS;
             ps.mask = V3(pt_sld1(P.wf.mask_in + i), pt_sld1(P.wf.mask_in + (size_t)P.wf.cap + i), pt_sld1(P.wf.mask_in + 2 * (size_t)P.wf.cap + i));
             ps.accu = V3(0.f, 0.f, 0.f);   // this segment's emission only: the running sum lives in the sample buffer
             ps.depth = P.wf.bounce;
             ps.rng = pt_rng_init(P.wf.hashes[s_idx], (uint64_t)pix);
-            ps.rng.n = sn & 0xfffu;
+            ps.rng.n = sn & (PT_REC_MAX_DRAWS - 1u);
         }
         const float2 hh = pt_sld2(P.wf.hit + i);
         Hit h;
@@ -390,8 +369,8 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
     if (COUNT) {   // all 64 lanes of every wave are here
         const uint32_t nh = wave_sum_u32(tri_hit ? 1u : 0u), np = wave_sum_u32(have && !alive ? 1u : 0u);
         if ((threadIdx.x & 63) == 0) {
-            atomicAdd(&P.counters[4], (unsigned long long)nh);
-            atomicAdd(&P.counters[5], (unsigned long long)np);
+            atomicAdd(&P.counters[PT_CNT_HITS], (unsigned long long)nh);
+            atomicAdd(&P.counters[PT_CNT_PATHS], (unsigned long long)np);
         }
     }
     if (NEE) {   // PT_FLAG_NEE: the shadow rays of this bounce's DIFF hits, packed like the survivors
@@ -419,8 +398,8 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
     if (alive) {
         const size_t j = (size_t)region * PT_REGION + (size_t)r;
         pt_sst4(P.wf.ray0_out + j, make_float4(ps.o.x, ps.o.y, ps.o.z, ps.d.x));
-        pt_sst4(P.wf.ray1_out + j, make_float4(ps.d.y, ps.d.z, __uint_as_float(NEE ? (pix | ((ps.nee_mask & 0xffu) << 24)) : pix),
-                                              __uint_as_float((s_idx << 12) | ps.rng.n | (NEE ? (ps.nee_mask >> 8) << 31 : 0u))));
+        pt_sst4(P.wf.ray1_out + j, make_float4(ps.d.y, ps.d.z, __uint_as_float(NEE ? (pix | ((ps.nee_mask & 0xffu) << PT_REC_PIXEL_BITS)) : pix),
+                                              __uint_as_float((s_idx << PT_REC_DRAW_BITS) | ps.rng.n | (NEE ? (ps.nee_mask >> 8) << PT_REC_LIGHT_BIT : 0u))));
         pt_sst1(P.wf.mask_out + j, ps.mask.x);
         pt_sst1(P.wf.mask_out + (size_t)P.wf.cap + j, ps.mask.y);
         pt_sst1(P.wf.mask_out + 2 * (size_t)P.wf.cap + j, ps.mask.z);
@@ -449,28 +428,22 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade_last_any(const KParams P)
         const float4 b = pt_sld4(P.wf.ray1_in + i);
         const float2 hh = pt_sld2(P.wf.hit + i);
         const v3 mask = V3(pt_sld1(P.wf.mask_in + i), pt_sld1(P.wf.mask_in + (size_t)P.wf.cap + i), pt_sld1(P.wf.mask_in + 2 * (size_t)P.wf.cap + i));
-        const uint32_t pix = __float_as_uint(b.z), s_idx = __float_as_uint(b.w) >> 12;
+        const uint32_t pix = __float_as_uint(b.z), s_idx = __float_as_uint(b.w) >> PT_REC_DRAW_BITS;
         float* smp = pt_sample_ptr(P, s_idx, (size_t)pix);
         const int sph = __float_as_int(hh.y);
         tri_hit = hh.x == 0.0f;
         if (!tri_hit && sph >= 0) {
             const float* t = (const float*)s_dyn + 11 * sph;
-            const v3 e = vadd(V3(0.f, 0.f, 0.f), vmul(mask, V3(t[4], t[5], t[6])));
-            if (!(e.x == 0.f) || !(e.y == 0.f) || !(e.z == 0.f)) { smp[0] += e.x; smp[1] += e.y; smp[2] += e.z; }
-        } else if (!tri_hit) {   // tracer.cu:140-142
-            PT_KARGS(K);
-            if (K.flags & PT_FLAG_MISS_KEEPS_PATH) {
-                smp[0] += mask.x * K.bk[0]; smp[1] += mask.y * K.bk[1]; smp[2] += mask.z * K.bk[2];
-            } else {
-                smp[0] = K.bk[0]; smp[1] = K.bk[1]; smp[2] = K.bk[2];
-            }
+            wf_add_emission(smp, vadd(V3(0.f, 0.f, 0.f), vmul(mask, V3(t[4], t[5], t[6]))));
+        } else if (!tri_hit) {
+            wf_shade_miss<false>(smp, mask);
         }
     }
     if (COUNT) {   // all 64 lanes of every wave are here
         const uint32_t nh = wave_sum_u32(tri_hit ? 1u : 0u), np = wave_sum_u32(have ? 1u : 0u);
         if ((threadIdx.x & 63) == 0) {
-            atomicAdd(&P.counters[4], (unsigned long long)nh);
-            atomicAdd(&P.counters[5], (unsigned long long)np);
+            atomicAdd(&P.counters[PT_CNT_HITS], (unsigned long long)nh);
+            atomicAdd(&P.counters[PT_CNT_PATHS], (unsigned long long)np);
         }
     }
     if constexpr (FOLD > 0) {
@@ -498,8 +471,6 @@ __global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet_shade(const KP
     ps.o = ps.d = V3(0.f, 0.f, 0.f);
     if (have) path_begin_hashed(P, px, py, (uint64_t)pix, P.wf.hashes[s_idx], ps);
     TravCount tc;
-    tc.inner = tc.tris = tc.leaves = 0;
-    tc.it_node = tc.act_node = tc.it_rec = tc.act_rec = 0;
     Hit h = trav_packet_wide<false>(P.sc, ps.o, ps.d, P.cull != 0, have, tc);   // (every lane of the wave: EXEC = all 64)
     bool alive = false;
     if (have) {
@@ -515,7 +486,7 @@ __global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet_shade(const KP
     if (alive) {
         const size_t j = (size_t)region * PT_REGION + (size_t)r;
         pt_sst4(P.wf.ray0_out + j, make_float4(ps.o.x, ps.o.y, ps.o.z, ps.d.x));
-        pt_sst4(P.wf.ray1_out + j, make_float4(ps.d.y, ps.d.z, __uint_as_float(pix), __uint_as_float((s_idx << 12) | ps.rng.n)));
+        pt_sst4(P.wf.ray1_out + j, make_float4(ps.d.y, ps.d.z, __uint_as_float(pix), __uint_as_float((s_idx << PT_REC_DRAW_BITS) | ps.rng.n)));
         pt_sst1(P.wf.mask_out + j, ps.mask.x);
         pt_sst1(P.wf.mask_out + (size_t)P.wf.cap + j, ps.mask.y);
         pt_sst1(P.wf.mask_out + 2 * (size_t)P.wf.cap + j, ps.mask.z);
@@ -558,16 +529,17 @@ static uint32_t draws_per_bounce(uint32_t flags) {
 }
 
 static int wave_layout(pt_ctx* c, const KParams& P, int work_tiles, WaveLayout& w) {
-    // limits of the record's packed fields: 12 bits of RNG draw count (2 camera draws + draws_per_bounce per bounce), 20 bits of sample
-    if ((uint64_t)P.depth * draws_per_bounce(P.flags) + 2u >= 4096u || P.spp >= (1u << 20))
-        return fail(c, PT_ERR_UNSUPPORTED, "pt_render: PT_KERNEL_WAVEFRONT packs < 4096 RNG draws per path (2 + depth x 4..9, by flags) and < 2^20 samples per call into a path record");
+    // limits of the record's packed fields (pt_kernels.h): the RNG draw count (2 camera draws + draws_per_bounce per bounce), the sample
+    if ((uint64_t)P.depth * draws_per_bounce(P.flags) + 2u >= PT_REC_MAX_DRAWS || P.spp >= PT_REC_MAX_SAMPLES)
+        return fail(c, PT_ERR_UNSUPPORTED, "pt_render: PT_KERNEL_WAVEFRONT packs < " + std::to_string(PT_REC_MAX_DRAWS) + " RNG draws per path (2 + depth x 4..9, by flags) and < " +
+                                           std::to_string(PT_REC_MAX_SAMPLES) + " samples per call into a path record");
     w.n_regions = ((size_t)work_tiles + PT_REGION / 64 - 1) / (PT_REGION / 64);
     w.cap = w.n_regions * PT_REGION;
     if (w.cap >= (1ull << 31)) return fail(c, PT_ERR_INVALID, "pt_render: too many path records for one call");
     w.b_ray = w.cap * 16; w.b_mask = w.cap * 12; w.b_hit = w.cap * 8; w.b_cnt = ((w.n_regions * 4 + 255) / 256) * 256;
     w.b_hash = (((size_t)P.spp * 8 + 255) / 256) * 256;
     w.nee = (P.flags & PT_FLAG_NEE) != 0;
-    if (w.nee && P.spp >= (1u << 19)) return fail(c, PT_ERR_UNSUPPORTED, "pt_render: PT_FLAG_NEE in the stage-split pipeline packs < 2^19 samples per call into a path record");
+    if (w.nee && P.spp >= PT_REC_MAX_SAMPLES_NEE) return fail(c, PT_ERR_UNSUPPORTED, "pt_render: PT_FLAG_NEE in the stage-split pipeline packs < " + std::to_string(PT_REC_MAX_SAMPLES_NEE) + " samples per call into a path record");
     w.q_words = (size_t)P.depth * (w.nee ? 2 : 1) * PT_SHARDS * PT_SHARD_STRIDE;   // one set of queue counters per extend launch
     w.b_q = w.q_words * 4;
     w.b_nee = w.nee ? 3 * w.b_ray + w.b_hit + w.b_cnt : 0;   // shadow records: s_ray0, s_ray1, s_con, s_hit, s_cnt
@@ -575,11 +547,8 @@ static int wave_layout(pt_ctx* c, const KParams& P, int work_tiles, WaveLayout& 
     return PT_OK;
 }
 
-// makes sure the context holds path records for this call (PT_KERNEL_AUTO calls it ahead of the timed span of its trial)
-int wave_reserve(pt_ctx* c, const KParams& P, int work_tiles) {
-    WaveLayout w;
-    const int rc = wave_layout(c, P, work_tiles, w);
-    if (rc != PT_OK) return rc;
+// makes sure the context holds the path records of layout w
+static int wave_reserve(pt_ctx* c, const WaveLayout& w) {
     if (w.need > c->wave_bytes) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         (void)hipFree(c->d_wave);
@@ -591,176 +560,188 @@ int wave_reserve(pt_ctx* c, const KParams& P, int work_tiles) {
     return PT_OK;
 }
 
+// the same for this call (PT_KERNEL_AUTO calls it ahead of the timed span of its trial)
+int wave_reserve(pt_ctx* c, const KParams& P, int work_tiles) {
+    WaveLayout w;
+    const int rc = wave_layout(c, P, work_tiles, w);
+    return rc != PT_OK ? rc : wave_reserve(c, w);
+}
+
+// c->d_wave carved by layout w: the two generations of every piece (bounce b reads [b & 1] and writes the other)
+struct WaveBuffers {
+    float4 *ray0[2], *ray1[2];
+    float* mask[2];
+    float2* hit;
+    int* cnt[2];
+    unsigned long long* hashes;   // then the queue counters of every extend launch
+    unsigned int* queues;
+    char* nee;   // the shadow records (PT_FLAG_NEE): s_ray0, s_ray1, s_con, s_hit, s_cnt
+};
+static WaveBuffers wave_carve(char* base, const WaveLayout& w) {
+    WaveBuffers b;
+    for (int g = 0; g < 2; g++) {
+        b.ray0[g] = (float4*)(base + g * w.b_ray);
+        b.ray1[g] = (float4*)(base + (2 + g) * w.b_ray);
+        b.mask[g] = (float*)(base + 4 * w.b_ray + g * w.b_mask);
+    }
+    base += 4 * w.b_ray + 2 * w.b_mask;
+    b.hit = (float2*)base;
+    base += w.b_hit;
+    b.cnt[0] = (int*)base;
+    b.cnt[1] = (int*)(base + w.b_cnt);
+    base += 2 * w.b_cnt;
+    b.hashes = (unsigned long long*)base;
+    base += w.b_hash;
+    b.queues = (unsigned int*)base;
+    b.nee = base + w.b_q;
+    return b;
+}
+
+// What one call launches, decided once: which extend and which shade kernel every bounce runs.
+enum WaveExtend { EXT_CLOSEST, EXT_ANY, EXT_FIRST, EXT_PACKET, EXT_FUSED };   // k_wf_extend<.., FIRST, ANY>, .._packet, .._packet_shade
+enum WaveShade { SHADE_PLAIN, SHADE_BOUND, SHADE_LAST, SHADE_LAST_ANY, SHADE_NONE };   // k_wf_shade<..>, k_wf_shade_last_any, in EXT_FUSED
+struct WavePlan {
+    bool count, nee, deep_stack;   // instrumented kernels; PT_FLAG_NEE; the (6 waves, 24 entries) budget instead of (8, 16)
+    bool packet;       // bounce 0 as wave-wide packets (PT_OPT_FIRST_WALK 1): the tree fits the packet stack budget (PT_OPT_PACKET_STACK)
+    // PT_OPT_FUSE_STAGES 1, the product launch without PT_FLAG_NEE: bounce 0's shade runs in the packet walk's launch, and the last shade
+    // launch folds the samples (fold_lp lanes per pixel) when every region holds all samples of its pixels (groups of spp = 16, 8 or 4)
+    bool fuse_first;
+    int fold_lp;
+    // PT_OPT_LAST_ANYHIT: when no triangle can emit, a path's last segment reaches the picture only through the sphere or the background it
+    // ends on.  The shade launch of bounce depth - 2 leaves the nearest sphere of every survivor's new ray in its hit slot, the walk of bounce
+    // depth - 1 is an any-hit query bounded by it, the last shade launch reads the verdict.  Instrumented launches: with the value 2 only.
+    bool anyhit;
+    WaveExtend extend(uint32_t b, uint32_t depth) const {
+        if (b == 0) return fuse_first ? EXT_FUSED : packet ? EXT_PACKET : EXT_FIRST;
+        return anyhit && b + 1 == depth ? EXT_ANY : EXT_CLOSEST;
+    }
+    WaveShade shade(uint32_t b, uint32_t depth) const {
+        if (b == 0 && fuse_first) return SHADE_NONE;
+        if (anyhit && b + 1 >= depth) return SHADE_LAST_ANY;   // behind the any-hit walk: the verdict's emission only
+        if (anyhit && b + 2 == depth) return SHADE_BOUND;      // its survivors' rays are the last segments: their sphere bound
+        if (b != 0 && !nee && !count && b + 1 >= depth) return SHADE_LAST;   // the final bounce: emission only
+        return SHADE_PLAIN;
+    }
+};
+static WavePlan wave_plan(const pt_ctx* c, const KParams& P, const LaunchCfg& L, bool nee) {
+    WavePlan p;
+    p.count = L.count; p.nee = nee; p.deep_stack = L.lstk == 24;
+    p.packet = c->opt_first_walk == 1 && 3 * c->wide_depth + 2 <= (uint32_t)c->opt_packet_stack;
+    const bool fuse = c->opt_fuse_stages != 0 && !nee && !L.count, tri_dark = P.tri_emi[0] == 0.f && P.tri_emi[1] == 0.f && P.tri_emi[2] == 0.f;
+    p.fuse_first = fuse && p.packet;
+    p.fold_lp = fuse && P.depth >= 2 && P.sgroup_log2 >= 2 && P.sgroup_log2 <= 4 && P.spp == (1u << P.sgroup_log2) ? (int)P.spp / 4 : 0;
+    p.anyhit = (L.count ? c->opt_last_anyhit == 2 : c->opt_last_anyhit >= 1) && P.depth >= 2 && !nee && !P.tri_matid && tri_dark &&
+               P.sc.n_spheres <= PT_KSPHERES && !c->records_woop;
+    return p;
+}
+
+constexpr size_t WF_LDS_SHADE = 15 * PT_KSPHERES * 4;   // wf_sphere_table
+// the extend stage's persistent grid (resident blocks, at most `blocks_per_cu` per CU) over the records of Q
+static hipError_t launch_extend(const WavePlan& p, WaveExtend kind, const KParams& Q, const LaunchCfg& L, int blocks_per_cu, hipStream_t s) {
+    auto plain = [&](auto kernel, size_t n_blk, size_t lds) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)n_blk), dim3(PT_BLOCK), lds, s, Q);
+        return hipGetLastError();
+    };
+    const size_t n_reg = (size_t)Q.wf.n_regions;
+    if (kind == EXT_FUSED)   // (BOUND at depth 2: bounce 0's survivors are the last segments)
+        return p.anyhit && Q.depth == 2 ? plain(k_wf_extend_packet_shade<true>, n_reg, WF_LDS_SHADE) : plain(k_wf_extend_packet_shade<false>, n_reg, WF_LDS_SHADE);
+    if (kind == EXT_PACKET) {   // one block per region (4 groups); instrumented: the resident grid, 8 blocks per CU
+#ifdef PT_PACKET_RESIDENT_GRID   // experiment (tools/build_variant.sh): the product launch on the resident grid too
+        const bool resident = true;
+#else
+        const bool resident = p.count;
+#endif
+        const size_t n_blk = resident ? std::min<size_t>(n_reg, (size_t)8 * L.n_cu) : n_reg;
+        return p.count ? plain(k_wf_extend_packet<true>, n_blk, 0) : plain(k_wf_extend_packet<false>, n_blk, 0);
+    }
+    return with_bool(p.count, [&](auto count) {
+        return with_bool(p.deep_stack, [&](auto deep) {
+            constexpr int OCC = deep() ? 6 : 8, LSTK = deep() ? 24 : 16;
+            auto go = [&](auto first, auto any) {
+                return launch_resident(k_wf_extend<count(), OCC, LSTK, first(), any()>, (size_t)LSTK * PT_BLOCK * 4, blocks_per_cu, L.n_cu,
+                                       (size_t)Q.wf.n_regions, s, Q);
+            };
+            if (kind == EXT_FIRST) return go(std::true_type{}, std::false_type{});
+            if (kind == EXT_ANY) return go(std::false_type{}, std::true_type{});
+            return go(std::false_type{}, std::false_type{});
+        });
+    });
+}
+
+// the shade stage: one block per region of Q
+static hipError_t launch_shade(const WavePlan& p, WaveShade kind, bool first, const KParams& Q, hipStream_t s) {
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)Q.wf.n_regions), dim3(PT_BLOCK), WF_LDS_SHADE, s, Q);
+        return hipGetLastError();
+    };
+    if (p.count) {   // (never SHADE_LAST, never a fold)
+        if (kind == SHADE_LAST_ANY) return go(k_wf_shade_last_any<true, 0>);
+        return with_bool(first, [&](auto f) {
+            if (kind == SHADE_BOUND) return go(k_wf_shade<true, false, f(), false, 0, true>);
+            return p.nee ? go(k_wf_shade<true, true, f()>) : go(k_wf_shade<true, false, f()>);
+        });
+    }
+    if (kind == SHADE_LAST_ANY) return with_int<4, 2, 1, 0>(p.fold_lp, [&](auto lp) { return go(k_wf_shade_last_any<false, lp()>); });
+    if (kind == SHADE_LAST) return with_int<4, 2, 1, 0>(p.fold_lp, [&](auto lp) { return go(k_wf_shade<false, false, false, true, lp()>); });
+    return with_bool(first, [&](auto f) {
+        if (kind == SHADE_BOUND) return go(k_wf_shade<false, false, f(), false, 0, true>);
+        return p.nee ? go(k_wf_shade<false, true, f()>) : go(k_wf_shade<false, false, f()>);
+    });
+}
+
 int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles, bool& folded) {
     folded = false;
     WaveLayout w;
-    {
-        const int rc = wave_layout(c, P, work_tiles, w);
-        if (rc != PT_OK) return rc;
-        const int rc2 = wave_reserve(c, P, work_tiles);
-        if (rc2 != PT_OK) return rc2;
-    }
-    const size_t n_regions = w.n_regions, cap = w.cap, b_ray = w.b_ray, b_mask = w.b_mask, b_hit = w.b_hit, b_cnt = w.b_cnt, b_hash = w.b_hash;
-    const size_t q_words = w.q_words, b_q = w.b_q;
-    const bool nee = w.nee;
-    char* base = (char*)c->d_wave;
-    float4* ray0[2] = {(float4*)base, (float4*)(base + b_ray)};
-    float4* ray1[2] = {(float4*)(base + 2 * b_ray), (float4*)(base + 3 * b_ray)};
-    base += 4 * b_ray;
-    float* mask[2] = {(float*)base, (float*)(base + b_mask)};
-    base += 2 * b_mask;
-    float2* hit = (float2*)base;
-    base += b_hit;
-    int* cnt[2] = {(int*)base, (int*)(base + b_cnt)};
-    base += 2 * b_cnt;
-    unsigned long long* hashes = (unsigned long long*)base;
-    base += b_hash;
-    unsigned int* queues = (unsigned int*)base;
-    base += b_q;
-    P.wf.nee = nee ? 1 : 0;
-    if (nee) {
-        P.wf.s_ray0 = (float4*)base;
-        P.wf.s_ray1 = (float4*)(base + b_ray);
-        P.wf.s_con = (float4*)(base + 2 * b_ray);
-        P.wf.s_hit = (float2*)(base + 3 * b_ray);
-        P.wf.s_cnt = (int*)(base + 3 * b_ray + b_hit);
+    int rc = wave_layout(c, P, work_tiles, w);
+    if (rc == PT_OK) rc = wave_reserve(c, w);
+    if (rc != PT_OK) return rc;
+    const WaveBuffers buf = wave_carve((char*)c->d_wave, w);
+    const WavePlan plan = wave_plan(c, P, L, w.nee);
+    folded = plan.fold_lp != 0;
+    P.wf.nee = w.nee ? 1 : 0;
+    if (w.nee) {
+        P.wf.s_ray0 = (float4*)buf.nee;
+        P.wf.s_ray1 = (float4*)(buf.nee + w.b_ray);
+        P.wf.s_con = (float4*)(buf.nee + 2 * w.b_ray);
+        P.wf.s_hit = (float2*)(buf.nee + 3 * w.b_ray);
+        P.wf.s_cnt = (int*)(buf.nee + 3 * w.b_ray + w.b_hit);
     }
 
     hipStream_t st = c->stream;
     P.sc.n_top = 0;
     P.sph_tab = 0;
     P.batch = c->opt_wave_batch;
-    P.wf.hit = hit;
-    P.wf.hashes = hashes;
-    P.wf.queues_all = queues;
-    P.wf.queues_words = (uint32_t)q_words;
-    P.wf.cap = (uint32_t)cap;
-    P.wf.n_regions = (int)n_regions;
+    P.wf.hit = buf.hit;
+    P.wf.hashes = buf.hashes;
+    P.wf.queues_all = buf.queues;
+    P.wf.queues_words = (uint32_t)w.q_words;
+    P.wf.cap = (uint32_t)w.cap;
+    P.wf.n_regions = (int)w.n_regions;
     P.wf.n_slots = (uint32_t)((size_t)work_tiles * 64);
     P.wf.bounce = 0;
     hipLaunchKernelGGL(k_wf_prepare, dim3(1), dim3(256), 0, st, P);
     HIP_TRY(c, hipGetLastError());
     if (stage_mark(c, PT_STAGE_GENERATE) != PT_OK) return PT_ERR_DEVICE;
 
-    const size_t lds_ext = (size_t)(L.lstk == 24 ? 24 : 16) * PT_BLOCK * 4;
-    const size_t lds_shade = 15 * PT_KSPHERES * 4;
-    // launchers: the extend stage's persistent grid (resident blocks, at most `blocks_per_cu` per CU) and the shade stage's one
-    // block per region, for the launch parameters Q on stream s
-#define PT_EXT(COUNT, OCC, LSTK, FIRST, ANY)                                                                         \
-        do {                                                                                                      \
-            int per_cu = 0;                                                                                       \
-            if (allow_lds(k_wf_extend<COUNT, OCC, LSTK, FIRST, ANY>, lds_ext) != hipSuccess) return hipErrorInvalidValue; \
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_wf_extend<COUNT, OCC, LSTK, FIRST, ANY>, PT_BLOCK, lds_ext) != hipSuccess || per_cu < 1) \
-                per_cu = 1;                                                                                       \
-            per_cu = std::min(per_cu, blocks_per_cu);                                                             \
-            hipLaunchKernelGGL((k_wf_extend<COUNT, OCC, LSTK, FIRST, ANY>), dim3((unsigned)std::min<size_t>((size_t)per_cu * L.n_cu, (size_t)Q.wf.n_regions)), \
-                               dim3(PT_BLOCK), lds_ext, s, Q);                                                    \
-        } while (0)
-    // bounce 0 as wave-wide packets (PT_OPT_FIRST_WALK 1) when the tree fits the packet stack budget (PT_OPT_PACKET_STACK)
-    const bool packet = c->opt_first_walk == 1 && 3 * c->wide_depth + 2 <= (uint32_t)c->opt_packet_stack;
-    auto launch_extend = [&](const KParams& Q, bool first, hipStream_t s, int blocks_per_cu, bool any = false) -> hipError_t {
-        if (first && packet) {   // one block per region (4 groups); instrumented: the resident grid, 8 blocks per CU
-#ifdef PT_PACKET_RESIDENT_GRID   // experiment (tools/build_variant.sh): the product launch on the resident grid too
-            const size_t n_blk = std::min<size_t>((size_t)Q.wf.n_regions, (size_t)8 * L.n_cu);
-#else
-            const size_t n_blk = L.count ? std::min<size_t>((size_t)Q.wf.n_regions, (size_t)8 * L.n_cu) : (size_t)Q.wf.n_regions;
-#endif
-            if (L.count) hipLaunchKernelGGL(k_wf_extend_packet<true>, dim3((unsigned)n_blk), dim3(PT_BLOCK), 0, s, Q);
-            else hipLaunchKernelGGL(k_wf_extend_packet<false>, dim3((unsigned)n_blk), dim3(PT_BLOCK), 0, s, Q);
-        } else if (first) {
-            if (L.count) { if (L.lstk == 24) PT_EXT(true, 6, 24, true, false); else PT_EXT(true, 8, 16, true, false); }
-            else { if (L.lstk == 24) PT_EXT(false, 6, 24, true, false); else PT_EXT(false, 8, 16, true, false); }
-        } else if (any) {   // the last segment as an any-hit query (PT_OPT_LAST_ANYHIT)
-            if (L.count) { if (L.lstk == 24) PT_EXT(true, 6, 24, false, true); else PT_EXT(true, 8, 16, false, true); }
-            else { if (L.lstk == 24) PT_EXT(false, 6, 24, false, true); else PT_EXT(false, 8, 16, false, true); }
-        } else {
-            if (L.count) { if (L.lstk == 24) PT_EXT(true, 6, 24, false, false); else PT_EXT(true, 8, 16, false, false); }
-            else { if (L.lstk == 24) PT_EXT(false, 6, 24, false, false); else PT_EXT(false, 8, 16, false, false); }
-        }
-        return hipGetLastError();
-    };
-#undef PT_EXT
-#define PT_SHADE(COUNT, NEE, FIRST) \
-        hipLaunchKernelGGL((k_wf_shade<COUNT, NEE, FIRST>), dim3((unsigned)Q.wf.n_regions), dim3(PT_BLOCK), lds_shade, s, Q)
-#define PT_SHADE_BOUND(COUNT, FIRST) \
-        hipLaunchKernelGGL((k_wf_shade<COUNT, false, FIRST, false, 0, true>), dim3((unsigned)Q.wf.n_regions), dim3(PT_BLOCK), lds_shade, s, Q)
-#define PT_SHADE_ANY(COUNT, FOLD) \
-        hipLaunchKernelGGL((k_wf_shade_last_any<COUNT, FOLD>), dim3((unsigned)Q.wf.n_regions), dim3(PT_BLOCK), lds_shade, s, Q)
-    // PT_OPT_FUSE_STAGES 1, the product launch without PT_FLAG_NEE: bounce 0's shade runs in the packet walk's launch, and the last
-    // shade launch folds the samples when every region holds all samples of its pixels (sample groups of spp = 16, 8 or 4)
-    const bool fuse = c->opt_fuse_stages != 0 && !nee && !L.count;
-    const bool fuse_first = fuse && packet;
-    const int fold_lp = fuse && P.depth >= 2 && P.sgroup_log2 >= 2 && P.sgroup_log2 <= 4 && P.spp == (1u << P.sgroup_log2) ? (int)P.spp / 4 : 0;
-    folded = fold_lp != 0;
-    // PT_OPT_LAST_ANYHIT: when no triangle can emit, the last segment of a path reaches the picture only through the sphere or the
-    // background it ends on.  The shade launch of bounce depth - 2 leaves the nearest sphere of every survivor's new ray in its hit
-    // slot, the walk of bounce depth - 1 is an any-hit query bounded by it, and the last shade launch reads the verdict.
-    // Instrumented launches take part with the value 2 only: their counters stay those of the closest-hit walk otherwise.
-    const bool tri_dark = P.tri_emi[0] == 0.f && P.tri_emi[1] == 0.f && P.tri_emi[2] == 0.f;
-    const bool anyhit = (L.count ? c->opt_last_anyhit == 2 : c->opt_last_anyhit >= 1) && P.depth >= 2 && !nee && !P.tri_matid && tri_dark &&
-                        P.sc.n_spheres <= PT_KSPHERES && !c->records_woop;
-    auto launch_shade = [&](const KParams& Q, bool first, hipStream_t s) -> hipError_t {
-        if (anyhit && Q.wf.bounce + 1 >= Q.depth) {   // behind the any-hit walk: the verdict's emission only
-            if (L.count) PT_SHADE_ANY(true, 0);
-            else if (fold_lp == 4) PT_SHADE_ANY(false, 4);
-            else if (fold_lp == 2) PT_SHADE_ANY(false, 2);
-            else if (fold_lp == 1) PT_SHADE_ANY(false, 1);
-            else PT_SHADE_ANY(false, 0);
-            return hipGetLastError();
-        }
-        if (anyhit && Q.wf.bounce + 2 == Q.depth) {   // its survivors' rays are the last segments: their sphere bound
-            if (first) { if (L.count) PT_SHADE_BOUND(true, true); else PT_SHADE_BOUND(false, true); }
-            else { if (L.count) PT_SHADE_BOUND(true, false); else PT_SHADE_BOUND(false, false); }
-            return hipGetLastError();
-        }
-        if (!first && !nee && !L.count && Q.wf.bounce + 1 >= Q.depth) {   // the final bounce: emission only
-            const dim3 grid((unsigned)Q.wf.n_regions);
-            if (fold_lp == 4) hipLaunchKernelGGL((k_wf_shade<false, false, false, true, 4>), grid, dim3(PT_BLOCK), lds_shade, s, Q);
-            else if (fold_lp == 2) hipLaunchKernelGGL((k_wf_shade<false, false, false, true, 2>), grid, dim3(PT_BLOCK), lds_shade, s, Q);
-            else if (fold_lp == 1) hipLaunchKernelGGL((k_wf_shade<false, false, false, true, 1>), grid, dim3(PT_BLOCK), lds_shade, s, Q);
-            else hipLaunchKernelGGL((k_wf_shade<false, false, false, true>), grid, dim3(PT_BLOCK), lds_shade, s, Q);
-            return hipGetLastError();
-        }
-        if (first) {
-            if (nee) { if (L.count) PT_SHADE(true, true, true); else PT_SHADE(false, true, true); }
-            else { if (L.count) PT_SHADE(true, false, true); else PT_SHADE(false, false, true); }
-        } else {
-            if (nee) { if (L.count) PT_SHADE(true, true, false); else PT_SHADE(false, true, false); }
-            else { if (L.count) PT_SHADE(true, false, false); else PT_SHADE(false, false, false); }
-        }
-        return hipGetLastError();
-    };
-#undef PT_SHADE
-#undef PT_SHADE_BOUND
-#undef PT_SHADE_ANY
-    auto set_bounce = [&](KParams& Q, uint32_t b) {
-        const int g = (int)(b & 1u);
-        Q.wf.bounce = b;
-        Q.wf.ray0_in = ray0[g]; Q.wf.ray1_in = ray1[g]; Q.wf.mask_in = mask[g]; Q.wf.cnt_in = cnt[g];
-        Q.wf.ray0_out = ray0[g ^ 1]; Q.wf.ray1_out = ray1[g ^ 1]; Q.wf.mask_out = mask[g ^ 1]; Q.wf.cnt_out = cnt[g ^ 1];
-    };
-
     for (uint32_t b = 0; b < P.depth; b++) {
-        set_bounce(P, b);
-        P.wf.queue = queues + (size_t)b * PT_SHARDS * PT_SHARD_STRIDE;
-        if (b == 0 && fuse_first) {   // walk + shade of bounce 0, booked as the extend stage
-            if (anyhit && P.depth == 2) hipLaunchKernelGGL(k_wf_extend_packet_shade<true>, dim3((unsigned)n_regions), dim3(PT_BLOCK), lds_shade, st, P);
-            else hipLaunchKernelGGL(k_wf_extend_packet_shade<false>, dim3((unsigned)n_regions), dim3(PT_BLOCK), lds_shade, st, P);
-            HIP_TRY(c, hipGetLastError());
-            if (stage_mark(c, PT_STAGE_EXTEND) != PT_OK) return PT_ERR_DEVICE;
-            continue;
-        }
-        HIP_TRY(c, launch_extend(P, b == 0, st, c->opt_wave_blocks, anyhit && b + 1 == P.depth));
+        const int g = (int)(b & 1u);
+        P.wf.bounce = b;
+        P.wf.ray0_in = buf.ray0[g]; P.wf.ray1_in = buf.ray1[g]; P.wf.mask_in = buf.mask[g]; P.wf.cnt_in = buf.cnt[g];
+        P.wf.ray0_out = buf.ray0[g ^ 1]; P.wf.ray1_out = buf.ray1[g ^ 1]; P.wf.mask_out = buf.mask[g ^ 1]; P.wf.cnt_out = buf.cnt[g ^ 1];
+        P.wf.queue = buf.queues + (size_t)b * PT_SHARDS * PT_SHARD_STRIDE;
+        HIP_TRY(c, launch_extend(plan, plan.extend(b, P.depth), P, L, c->opt_wave_blocks, st));   // (EXT_FUSED: walk + shade, booked as extend)
         if (stage_mark(c, PT_STAGE_EXTEND) != PT_OK) return PT_ERR_DEVICE;
-        HIP_TRY(c, launch_shade(P, b == 0, st));
+        const WaveShade shade = plan.shade(b, P.depth);
+        if (shade == SHADE_NONE) continue;
+        HIP_TRY(c, launch_shade(plan, shade, b == 0, P, st));
         if (stage_mark(c, PT_STAGE_SHADE) != PT_OK) return PT_ERR_DEVICE;
-        if (nee) {   // this bounce's shadow rays: the same extend kernel over the shadow records, then the resolve
+        if (w.nee) {   // this bounce's shadow rays: the closest-hit extend kernel over the shadow records, then the resolve
             KParams S = P;
             S.wf.ray0_in = P.wf.s_ray0; S.wf.ray1_in = P.wf.s_ray1; S.wf.cnt_in = P.wf.s_cnt; S.wf.hit = P.wf.s_hit;
-            S.wf.queue = queues + ((size_t)P.depth + b) * PT_SHARDS * PT_SHARD_STRIDE;
-            HIP_TRY(c, launch_extend(S, false, st, c->opt_wave_blocks));
+            S.wf.queue = buf.queues + ((size_t)P.depth + b) * PT_SHARDS * PT_SHARD_STRIDE;
+            HIP_TRY(c, launch_extend(plan, EXT_CLOSEST, S, L, c->opt_wave_blocks, st));
             if (stage_mark(c, PT_STAGE_EXTEND) != PT_OK) return PT_ERR_DEVICE;
-            hipLaunchKernelGGL(k_wf_resolve, dim3((unsigned)n_regions), dim3(PT_BLOCK), 0, st, P);
+            hipLaunchKernelGGL(k_wf_resolve, dim3((unsigned)w.n_regions), dim3(PT_BLOCK), 0, st, P);
             HIP_TRY(c, hipGetLastError());
             if (stage_mark(c, PT_STAGE_SHADE) != PT_OK) return PT_ERR_DEVICE;
         }

@@ -40,9 +40,17 @@ struct KScene {
 // in slot i of its REGION (256 consecutive slots = one block of the generate / shade stages); a region's live
 // records are packed at its front and counted in cnt[region], so compaction never leaves the block
 // (ballot + prefix count, no global atomics) and the order of the records is deterministic.
-//   ray0[i] = (o.x, o.y, o.z, d.x)   ray1[i] = (d.y, d.z, bits(pixel), bits(sample << 12 | rng draws))
+//   ray0[i] = (o.x, o.y, o.z, d.x)   ray1[i] = (d.y, d.z, bits(pixel), bits(sample << PT_REC_DRAW_BITS | rng draws))
 //   mask    = three planes [cap] (x, y, z), not stored for the first bounce (1, 1, 1)
 //   hit[i]  = (t, bits(float4 index of the winning record)); t = F32_MAX: no triangle
+// PT_FLAG_NEE: the sphere bits of nee_mask ride above the pixel (ray1.z), its triangle-light bit above the sample (ray1.w).
+// The stages of pt_k_wave.hip pack and unpack the record with these; the limits wave_layout and pt_render check follow from them:
+constexpr uint32_t PT_REC_DRAW_BITS = 12;    // ray1.w: RNG draws of the path so far, below the sample number
+constexpr uint32_t PT_REC_LIGHT_BIT = 31;    // ray1.w, PT_FLAG_NEE: nee_mask bit 8 (the triangle lights)
+constexpr uint32_t PT_REC_PIXEL_BITS = 24;   // ray1.z, PT_FLAG_NEE: the pixel, below nee_mask bits 0-7 (the spheres)
+// exclusive limits: draws per path, samples per call without / with PT_FLAG_NEE
+constexpr uint32_t PT_REC_MAX_DRAWS = 1u << PT_REC_DRAW_BITS, PT_REC_MAX_SAMPLES = 1u << (32 - PT_REC_DRAW_BITS),
+                   PT_REC_MAX_SAMPLES_NEE = 1u << (PT_REC_LIGHT_BIT - PT_REC_DRAW_BITS);
 struct KWave {
     const float4* __restrict__ ray0_in;
     const float4* __restrict__ ray1_in;
@@ -76,7 +84,7 @@ struct KParams {
     pt_sphere_d ksph[PT_KSPHERES];
     float* __restrict__ accum;
     uint32_t* __restrict__ rgba;
-    unsigned long long* counters;      // 6 x u64 when instrumented
+    unsigned long long* counters;      // PT_CNT_N x u64 when instrumented
     pt_camera cam;
     int W, H;
     uint32_t depth;
@@ -130,6 +138,11 @@ struct Hit {
                // fetched once per segment by pt_hit_normal instead of at every improvement (and two
                // registers less to carry through the walk)
 };
+__device__ __forceinline__ Hit pt_no_hit() {
+    Hit h;
+    h.t = PT_F32_MAX; h.tri = -1; h.rec = 0;
+    return h;
+}
 
 // the un-normalised geometric normal of a hit triangle (4th piece of its record)
 __device__ __forceinline__ v3 pt_hit_normal(const KScene& sc, const Hit& h) {
@@ -144,11 +157,25 @@ __device__ __forceinline__ bool pt_first_active_lane() {
 }
 
 struct TravCount {
-    uint32_t inner, tris, leaves;
-    // wave-level schedule statistics (instrumented launches of the wide walk only; identical in
-    // every lane): iterations spent in node / record steps and the lanes active in them
-    uint32_t it_node, act_node, it_rec, act_rec;
+    uint32_t inner = 0, tris = 0, leaves = 0;
+    // wave-level schedule statistics (instrumented launches of the wide walk only; booked by one lane of
+    // those in the step): iterations spent in node / record steps and the lanes active in them
+    uint32_t it_node = 0, act_node = 0, it_rec = 0, act_rec = 0;
 };
+
+// The words of KParams::counters (PT_OPT_COUNTERS): the six of pt_counters, then the PT_WAVE_STATS of pt_get_wave_stats, as include/ptmi.h
+// documents them.  Two wave statistics mean another thing in the stage-split pipeline, whose shade stage has no passes to count.
+enum {
+    PT_CNT_RAYS, PT_CNT_INNER, PT_CNT_TRIS, PT_CNT_LEAVES, PT_CNT_HITS, PT_CNT_PATHS,
+    PT_CNT_WAVE, PT_CNT_IT_NODE = PT_CNT_WAVE, PT_CNT_ACT_NODE, PT_CNT_IT_REC, PT_CNT_ACT_REC,   // node / record steps, their lanes
+    PT_CNT_IT_SHADE, PT_CNT_ACT_SHADE,   // persistent kernel: shading passes, lanes
+    PT_CNT_IT_BEGIN, PT_CNT_ACT_BEGIN,   // path-start (pipeline: refill) passes, lanes
+    PT_CNT_IT_LOOP, PT_CNT_STACK_OVF,    // outer-loop iterations, pushes past the LDS window
+    PT_CNT_N,
+    PT_CNT_PACKET_GROUPS = PT_CNT_IT_SHADE,   // pipeline: 64-ray groups the bounce-0 packet walk walked
+    PT_CNT_ANY_RAYS = PT_CNT_ACT_SHADE        // pipeline: rays of the any-hit launch (PT_OPT_LAST_ANYHIT 2)
+};
+static_assert(PT_CNT_WAVE == sizeof(pt_counters) / sizeof(uint64_t) && PT_CNT_N - PT_CNT_WAVE == PT_WAVE_STATS, "include/ptmi.h");
 
 #include "pt_walks.h"
 #include "pt_shade.h"
@@ -163,8 +190,7 @@ __device__ __forceinline__ v3 pt_get_sample(const KParams& P, int px, int py, ui
     v3 col = V3(0.f, 0.f, 0.f);
     if (P.depth == 0) return col;
     for (;;) {
-        Hit h;
-        h.t = PT_F32_MAX; h.tri = -1; h.rec = 0;
+        Hit h = pt_no_hit();
         if (P.sc.has_bvh) {
             if (ALG >= 2) {
                 TravState ts;
@@ -189,8 +215,7 @@ __device__ __forceinline__ v3 pt_get_sample(const KParams& P, int px, int py, ui
         int done_v = done ? 1 : 0;
         asm volatile("" : "+v"(done_v));
         if (req.want) {   // PT_FLAG_NEE: the shadow ray of this DIFF hit, against the triangles
-            Hit h2;
-            h2.t = PT_F32_MAX; h2.tri = -1; h2.rec = 0;
+            Hit h2 = pt_no_hit();
             if (P.sc.has_bvh) {
                 TravState ts;
                 if (ALG >= 2) {
@@ -220,6 +245,21 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
+}
+
+// books a wave's walk counters: its rays and what their walks fetched, and (STEPS: the kernels whose wave statistics are
+// documented) the wide walk's node / record steps, which the walk books in ONE lane of those inside it, so they are summed over
+// the lanes too.  Every lane of the wave calls it; the lane with `booker` set adds the sums.
+template <bool STEPS>
+__device__ __forceinline__ void pt_book_walk(const KParams& P, bool booker, uint32_t n_rays, const TravCount& tc) {
+    const uint32_t v[8] = {n_rays, tc.inner, tc.tris, tc.leaves, tc.it_node, tc.act_node, tc.it_rec, tc.act_rec};
+    const int word[8] = {PT_CNT_RAYS, PT_CNT_INNER, PT_CNT_TRIS, PT_CNT_LEAVES, PT_CNT_IT_NODE, PT_CNT_ACT_NODE, PT_CNT_IT_REC, PT_CNT_ACT_REC};
+    uint32_t sum[8];
+#pragma unroll
+    for (int k = 0; k < (STEPS ? 8 : 4); k++) sum[k] = wave_sum_u32(v[k]);
+    if (!booker) return;
+#pragma unroll
+    for (int k = 0; k < (STEPS ? 8 : 4); k++) atomicAdd(&P.counters[word[k]], (unsigned long long)sum[k]);
 }
 
 // Maps the launch's linear tile number to the global tile coordinates this partition owns.

@@ -40,6 +40,18 @@ extern __shared__ float4 s_dyn[];
 #define PT_WALK_EXIT_HOOK()
 #endif
 
+// The closest-hit rule of every walk: a nearer hit wins, and of two at the same t the smaller triangle id, so the result does not
+// depend on the order the records are met in (h.tri = -1: no hit yet).  The packet walk calls it; the per-lane walks keep it written
+// out ("= pt_hit_update"): called there it changes SGPR spills around the wide and postponed-leaf walks (profiles/r09_restatement_isa.txt).
+__device__ __forceinline__ Hit pt_hit_update(Hit h, float t, int id, int rec) {
+    if (t > 0.0f && (t < h.t || (t == h.t && h.tri != -1 && id < h.tri))) {
+        h.t = t;
+        h.tri = id;
+        h.rec = rec;
+    }
+    return h;
+}
+
 struct TravState {
     float idx, idy, idz, oodx, oody, oodz;
     int node, leaf, sp;
@@ -111,7 +123,7 @@ __device__ __forceinline__ void trav_begin(TravState& s, v3 o, v3 d, STK& stk, i
     s.sp = 0;
     stk.put(0, PT_SENTINEL);
     s.leaf = 0; s.node = root;
-    s.h.t = PT_F32_MAX; s.h.tri = -1; s.h.rec = 0;
+    s.h = pt_no_hit();
 }
 
 // returns true when the walk is complete
@@ -186,7 +198,7 @@ __device__ __forceinline__ bool trav_run(TravState& s, const KScene& sc, v3 o, v
                 const v3 v0 = V3(r0.x, r0.y, r0.z), e1 = V3(r1.x, r1.y, r1.z), e2 = V3(r2.x, r2.y, r2.z);
                 const float t = pt_mt_intersect(v0, e1, e2, o, d, cull);
                 const int id = __float_as_int(r0.w);
-                if (t > 0.0f && (t < h.t || (t == h.t && h.tri != -1 && id < h.tri))) {
+                if (t > 0.0f && (t < h.t || (t == h.t && h.tri != -1 && id < h.tri))) {   // = pt_hit_update
                     h.t = t;
                     h.tri = id;
                     h.rec = a;
@@ -270,7 +282,7 @@ __device__ __forceinline__ bool trav_run_unified(TravState& s, const KScene& sc,
             const v3 v0 = V3(q0.x, q0.y, q0.z), e1 = V3(q1.x, q1.y, q1.z), e2 = V3(q2.x, q2.y, q2.z);
             const float t = pt_mt_intersect(v0, e1, e2, o, d, cull);
             const int id = __float_as_int(q0.w);
-            if (t > 0.0f && (t < h.t || (t == h.t && h.tri != -1 && id < h.tri))) {
+            if (t > 0.0f && (t < h.t || (t == h.t && h.tri != -1 && id < h.tri))) {   // = pt_hit_update
                 h.t = t;
                 h.tri = id;
                 h.rec = a;
@@ -317,15 +329,20 @@ struct WideNode {
     int l0, l1, l2, l3;                      // links: >= 0 float4 index of a node, < 0 ~(float4 index of a leaf's first record | min(records, 4) - 1)
 };
 
-__device__ __forceinline__ WideNode wide_node_load(const KScene& sc, int a) {
+// a node's four pieces as its fields
+__device__ __forceinline__ WideNode wide_node_decode(float4 q0, float4 q1, float4 q2, float4 q3) {
     WideNode w;
-    const float4 q0 = sc.nodes[a + 0], q1 = sc.nodes[a + 1], q2 = sc.nodes[a + 2], q3 = sc.nodes[a + 3];
     w.ox = q0.x; w.oy = q0.y; w.oz = q0.z;
     w.sx = q0.w; w.sy = q3.z; w.sz = q3.w;
     w.qlx = __float_as_uint(q1.x); w.qly = __float_as_uint(q1.y); w.qlz = __float_as_uint(q1.z);
     w.qhx = __float_as_uint(q1.w); w.qhy = __float_as_uint(q2.x); w.qhz = __float_as_uint(q2.y);
     w.l0 = __float_as_int(q2.z); w.l1 = __float_as_int(q2.w);
     w.l2 = __float_as_int(q3.x); w.l3 = __float_as_int(q3.y);
+    return w;
+}
+
+__device__ __forceinline__ WideNode wide_node_load(const KScene& sc, int a) {
+    WideNode w = wide_node_decode(sc.nodes[a + 0], sc.nodes[a + 1], sc.nodes[a + 2], sc.nodes[a + 3]);
     // keep the link words with the box words: left alone, hipcc sinks their use into the hit branches
     // (two dependent round trips per node)
     asm volatile("" : "+v"(w.l2), "+v"(w.l3));
@@ -490,7 +507,7 @@ __device__ __forceinline__ bool trav_run_wide(TravState& s, const KScene& sc, v3
                 }
                 continue;
             }
-            if (t > 0.0f && (t < h.t || (t == h.t && h.tri != -1 && id < h.tri))) {
+            if (t > 0.0f && (t < h.t || (t == h.t && h.tri != -1 && id < h.tri))) {   // = pt_hit_update
                 h.t = t;
                 h.tri = id;
                 h.rec = a;
@@ -506,7 +523,7 @@ __device__ __forceinline__ bool trav_run_wide(TravState& s, const KScene& sc, v3
                     const float t2 = pt_mt_intersect(V3(x0.x, x0.y, x0.z), V3(x1.x, x1.y, x1.z), V3(x2.x, x2.y, x2.z), o, d, cull);
                     const int id2 = __float_as_int(x0.w);
                     last = __float_as_int(x1.w) != 0;
-                    if (t2 > 0.0f && (t2 < h.t || (t2 == h.t && h.tri != -1 && id2 < h.tri))) {
+                    if (t2 > 0.0f && (t2 < h.t || (t2 == h.t && h.tri != -1 && id2 < h.tri))) {   // = pt_hit_update
                         h.t = t2;
                         h.tri = id2;
                         h.rec = aa;
@@ -520,7 +537,7 @@ __device__ __forceinline__ bool trav_run_wide(TravState& s, const KScene& sc, v3
                     const float t2 = pt_mt_intersect(V3(r0.x, r0.y, r0.z), V3(r1.x, r1.y, r1.z), V3(r2.x, r2.y, r2.z), o, d, cull);
                     const int id2 = __float_as_int(r0.w);
                     last = __float_as_int(r1.w) != 0;
-                    if (t2 > 0.0f && (t2 < h.t || (t2 == h.t && h.tri != -1 && id2 < h.tri))) {
+                    if (t2 > 0.0f && (t2 < h.t || (t2 == h.t && h.tri != -1 && id2 < h.tri))) {   // = pt_hit_update
                         h.t = t2;
                         h.tri = id2;
                         h.rec = aa;
@@ -597,7 +614,7 @@ __device__ __forceinline__ bool trav_run_wide_pend(TravState& s, const KScene& s
             const v3 v0 = V3(q0.x, q0.y, q0.z), e1 = V3(q1.x, q1.y, q1.z), e2 = V3(q2.x, q2.y, q2.z);
             const float t = pt_mt_intersect(v0, e1, e2, o, d, cull);
             const int id = __float_as_int(q0.w);
-            if (t > 0.0f && (t < h.t || (t == h.t && h.tri != -1 && id < h.tri))) {
+            if (t > 0.0f && (t < h.t || (t == h.t && h.tri != -1 && id < h.tri))) {   // = pt_hit_update
                 h.t = t;
                 h.tri = id;
                 h.rec = a;
@@ -650,15 +667,7 @@ __device__ __forceinline__ float4 pt_uld4(const float4* items, int a) {
 
 // one 64-byte wide node at a wave-uniform float4 index: s_load, no vector-memory access
 __device__ __forceinline__ WideNode wide_node_load_uniform(const KScene& sc, int a) {
-    const float4 q0 = pt_uld4(sc.nodes, a), q1 = pt_uld4(sc.nodes, a + 1), q2 = pt_uld4(sc.nodes, a + 2), q3 = pt_uld4(sc.nodes, a + 3);
-    WideNode w;
-    w.ox = q0.x; w.oy = q0.y; w.oz = q0.z;
-    w.sx = q0.w; w.sy = q3.z; w.sz = q3.w;
-    w.qlx = __float_as_uint(q1.x); w.qly = __float_as_uint(q1.y); w.qlz = __float_as_uint(q1.z);
-    w.qhx = __float_as_uint(q1.w); w.qhy = __float_as_uint(q2.x); w.qhz = __float_as_uint(q2.y);
-    w.l0 = __float_as_int(q2.z); w.l1 = __float_as_int(q2.w);
-    w.l2 = __float_as_int(q3.x); w.l3 = __float_as_int(q3.y);
-    return w;
+    return wide_node_decode(pt_uld4(sc.nodes, a), pt_uld4(sc.nodes, a + 1), pt_uld4(sc.nodes, a + 2), pt_uld4(sc.nodes, a + 3));
 }
 
 __device__ __forceinline__ uint64_t pt_pick4(uint32_t k, uint64_t a, uint64_t b, uint64_t c, uint64_t d) {
@@ -674,8 +683,7 @@ __device__ __forceinline__ Hit trav_packet_wide(const KScene& sc, v3 o, v3 d, bo
     TravState s;
     trav_ray(s, o, d);
     const float idx = s.idx, idy = s.idy, idz = s.idz, oodx = s.oodx, oody = s.oody, oodz = s.oodz;
-    Hit h;
-    h.t = PT_F32_MAX; h.tri = -1; h.rec = 0;
+    Hit h = pt_no_hit();
     uint64_t m = __ballot(in);
     int cur = m ? sc.wide_root : PT_SENTINEL;
     int sp = 0;
@@ -685,7 +693,7 @@ __device__ __forceinline__ Hit trav_packet_wide(const KScene& sc, v3 o, v3 d, bo
             const WideNode w = wide_node_load_uniform(sc, cur);
             if (COUNT) {
                 if (act) tc.inner++;
-                if (lane == 0) { tc.it_node++; tc.act_node += (uint32_t)__popcll(m); }
+                if (lane == 0) { tc.it_node++; tc.act_node += (uint32_t)__popcll(m); }   // (lane 0 alone: pt_book_walk sums the lanes)
             }
             uint32_t key[4];
             wide_node_keys_raw(w, idx, idy, idz, oodx, oody, oodz, h.t, key);
@@ -726,15 +734,11 @@ __device__ __forceinline__ Hit trav_packet_wide(const KScene& sc, v3 o, v3 d, bo
                 const float4 q0 = pt_uld4(sc.nodes, a), q1 = pt_uld4(sc.nodes, a + 1), q2 = pt_uld4(sc.nodes, a + 2);
                 if (COUNT) {
                     if (act) tc.tris++;
-                    if (lane == 0) { tc.it_rec++; tc.act_rec += (uint32_t)__popcll(m); }
+                    if (lane == 0) { tc.it_rec++; tc.act_rec += (uint32_t)__popcll(m); }   // (lane 0 alone, as above)
                 }
                 const float t = pt_mt_intersect(V3(q0.x, q0.y, q0.z), V3(q1.x, q1.y, q1.z), V3(q2.x, q2.y, q2.z), o, d, cull);
                 const int id = __float_as_int(q0.w);
-                if (act && t > 0.0f && (t < h.t || (t == h.t && h.tri != -1 && id < h.tri))) {
-                    h.t = t;
-                    h.tri = id;
-                    h.rec = a;
-                }
+                if (act) h = pt_hit_update(h, t, id, a);
                 if (__float_as_int(q1.w) != 0) break;  // last record of the leaf
                 a += 4;
             }

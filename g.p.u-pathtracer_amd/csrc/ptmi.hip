@@ -182,8 +182,8 @@ int pt_create(int device, pt_ctx** out) {
     if ((e = hipSetDevice(device)) != hipSuccess) { delete c; return hip_fail(nullptr, e, "hipSetDevice"); }
     if ((e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking)) != hipSuccess) { delete c; return hip_fail(nullptr, e, "hipStreamCreate"); }
     c->stream = c->own_stream;
-    if ((e = hipMalloc(&c->d_counters, 16 * sizeof(unsigned long long))) != hipSuccess) { pt_destroy(c); return hip_fail(nullptr, e, "hipMalloc"); }
-    if ((e = hipMemset(c->d_counters, 0, 16 * sizeof(unsigned long long))) != hipSuccess) { pt_destroy(c); return hip_fail(nullptr, e, "hipMemset"); }
+    if ((e = hipMalloc(&c->d_counters, PT_CNT_N * sizeof(unsigned long long))) != hipSuccess) { pt_destroy(c); return hip_fail(nullptr, e, "hipMalloc"); }
+    if ((e = hipMemset(c->d_counters, 0, PT_CNT_N * sizeof(unsigned long long))) != hipSuccess) { pt_destroy(c); return hip_fail(nullptr, e, "hipMemset"); }
     if ((e = hipMalloc(&c->d_queue, PT_SHARDS * PT_SHARD_STRIDE * sizeof(unsigned int))) != hipSuccess) { pt_destroy(c); return hip_fail(nullptr, e, "hipMalloc"); }
     hipDeviceProp_t prop;
     if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) { pt_destroy(c); return hip_fail(nullptr, e, "hipGetDeviceProperties"); }
@@ -723,7 +723,7 @@ int pt_render(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, const pt_camera* 
     }
     if (p->flags & PT_FLAG_NEE) {   // shadow rays: the stage-split pipeline has a stage for them, the megakernel a loop; the
                                     // persistent kernel does not (its lanes have no room for a second ray)
-        const bool nee_wave = wave_ok && (uint64_t)p->width * (uint64_t)p->height <= (1ull << 24);   // pixel | nee_mask << 24
+        const bool nee_wave = wave_ok && (uint64_t)p->width * (uint64_t)p->height <= (1ull << PT_REC_PIXEL_BITS);   // the pixel rides below nee_mask in ray1.z
         if (kernel != PT_KERNEL_MEGA_BVH2) kernel = nee_wave ? PT_KERNEL_WAVEFRONT : PT_KERNEL_MEGA_BVH2;
         if (kernel == PT_KERNEL_WAVEFRONT && !nee_wave) kernel = PT_KERNEL_MEGA_BVH2;
     }
@@ -803,7 +803,7 @@ int pt_render(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, const pt_camera* 
         }
     }
 
-    if (c->opt_counters) HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, 16 * sizeof(unsigned long long), c->stream));
+    if (c->opt_counters) HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, PT_CNT_N * sizeof(unsigned long long), c->stream));
     if (probe >= 0 && (probe & 1)) {   // a trial of the pipeline: its path records are allocated BEFORE the timed span
         const int rc = wave_reserve(c, P, work_tiles);
         if (rc != PT_OK) return rc;
@@ -1004,21 +1004,22 @@ int pt_trace_rays(pt_ctx* c, const float* rays_dev, size_t n, int cull, float* t
 
 int pt_get_counters(pt_ctx* c, pt_counters* out) {
     if (!c || !out) return fail(c, PT_ERR_INVALID, "pt_get_counters: null argument");
-    unsigned long long h[8];
+    unsigned long long h[PT_CNT_WAVE];
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipMemcpyAsync(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    out->rays = h[0]; out->inner = h[1]; out->tris = h[2]; out->leaves = h[3]; out->hits = h[4]; out->paths = h[5];
+    out->rays = h[PT_CNT_RAYS]; out->inner = h[PT_CNT_INNER]; out->tris = h[PT_CNT_TRIS]; out->leaves = h[PT_CNT_LEAVES];
+    out->hits = h[PT_CNT_HITS]; out->paths = h[PT_CNT_PATHS];
     return PT_OK;
 }
 
 int pt_get_wave_stats(pt_ctx* c, uint64_t* out, int n) {
     if (!c || !out || n < 0) return fail(c, PT_ERR_INVALID, "pt_get_wave_stats: bad argument");
-    unsigned long long h[16];
+    unsigned long long h[PT_CNT_N];
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipMemcpyAsync(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (int i = 0; i < n && i < PT_WAVE_STATS; i++) out[i] = h[6 + i];   // counters 6..15
+    for (int i = 0; i < n && i < PT_WAVE_STATS; i++) out[i] = h[PT_CNT_WAVE + i];
     return PT_OK;
 }
 
