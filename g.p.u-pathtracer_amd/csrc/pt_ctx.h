@@ -128,6 +128,10 @@ struct pt_ctx {
     // pt_denoise's ping-pong colour frames (pt_denoise.hip): grown on demand, released by pt_destroy
     void* d_denoise = nullptr;
     size_t denoise_bytes = 0;
+    // pt_frame_error's per-block partial results (pt_denoise.hip): [blocks] double sums, then [blocks] uint32 counts; grown on
+    // demand, released with the denoiser's scratch
+    void* d_frame_err = nullptr;
+    size_t frame_err_bytes = 0;
     // Overlap of consecutive calls (PT_OPT_OVERLAP, persistent / mega kernels): the path kernel of call k + 1 runs on
     // a side stream into its own sample buffer while call k's last paths drain; only the folds (which touch the
     // accumulator, in order) stay on the caller's stream.  side[x]: stream, sample buffer, queue counters of slot x.
@@ -219,12 +223,13 @@ struct LaunchCfg {
     int blocks;        // megakernel grid (one wave per work tile)
     int work_blocks;   // persistent grid cap: blocks that have work at all
     int n_cu;
+    bool moments;      // the call keeps luminance moments (pt_render_moments): they are the separate fold launch's job
 };
 hipError_t launch_mega(const LaunchCfg& L, const KParams& P, hipStream_t st);        // pt_k_mega.hip
 hipError_t launch_rays(const KScene& sc, size_t lds, const float4* rays, size_t n, int cull, float* t_out, int* tri_out,
                        float* n_out, hipStream_t st);                                 // pt_k_mega.hip
 hipError_t launch_persist(const LaunchCfg& L, const KParams& P, hipStream_t st);     // pt_k_persist.hip
-hipError_t launch_fold(const KParams& P, hipStream_t st);                            // pt_k_persist.hip
+hipError_t launch_fold(const KParams& P, float2* moments, hipStream_t st);           // pt_k_persist.hip; moments: nullptr = none
 // stage-split pipeline (pt_k_wave.hip): generate -> depth x (extend, shade) ; returns PT_* status; folded = the samples are
 // already folded into the accumulator (PT_OPT_FUSE_STAGES), no launch_fold after it
 int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles, bool& folded);
@@ -243,7 +248,7 @@ int build_bvh_impl(pt_ctx* c, const float* verts, size_t n_verts, const int32_t*
                    const int32_t* id_map = nullptr);
 // pt_refit_bvh's per-tree state (pt_refit.hip): released wherever the tree is replaced or the context destroyed
 void refit_release(pt_ctx* c);
-// pt_denoise's scratch (pt_denoise.hip)
+// pt_denoise's and pt_frame_error's scratch (pt_denoise.hip)
 void denoise_release(pt_ctx* c);
 
 }  // namespace ptmi

@@ -9,6 +9,9 @@
 //                    position only where both ends are hits) and ONE v_exp_f32 (the three terms folded into exp2 with log2(e)
 //                    in the per-launch constants); the last iteration remodulates, clamps, writes out (+ display words)
 //   k_dn_copy        iterations = 0: out = color bit for bit (+ display words)
+//   k_frame_error    pt_frame_error: one lane per pixel, the relative standard error of the mean luminance from the moments
+//                    pt_render_moments keeps; a block adds its 256 values up in LDS, in double, and writes
+//                    ONE partial sum and ONE count to its own slot — the host adds the slots in block order
 // No LDS tile: at step 16 the taps are 64 rows apart, an apron would re-read more than it saves; the packed buffers of a 1080p
 // frame (~100 MB) stay in the 256 MB Infinity Cache.
 #include <cmath>
@@ -172,6 +175,32 @@ __global__ void __launch_bounds__(PTD_BLOCK) k_dn_iter(const DnArgs A) {
     }
 }
 
+// pt_frame_error: rse of pixel i in binary32 (include/ptmi.h states the formula); per block the sum of rse in double and the
+// number of pixels above the threshold, by the tree reduction of k_tree_cost (ptmi.hip): no atomics, no fences, the same
+// figure run after run
+__global__ void __launch_bounds__(256) k_frame_error(const float2* __restrict__ moments, uint32_t n_pix, float nm1, float threshold,
+                                                     double* __restrict__ sums, uint32_t* __restrict__ counts) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    double rse = 0.0;
+    uint32_t above = 0u;
+    if (i < n_pix) {
+        const float2 m = moments[i];
+        const float var = fmaxf(0.f, m.y - m.x * m.x);
+        const float r = sqrtf(var / nm1) / (m.x + 0.01f);
+        rse = (double)r;
+        above = r > threshold ? 1u : 0u;
+    }
+    __shared__ double s_sum[256];
+    __shared__ uint32_t s_cnt[256];
+    s_sum[threadIdx.x] = rse; s_cnt[threadIdx.x] = above;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) { s_sum[threadIdx.x] += s_sum[threadIdx.x + off]; s_cnt[threadIdx.x] += s_cnt[threadIdx.x + off]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { sums[blockIdx.x] = s_sum[0]; counts[blockIdx.x] = s_cnt[0]; }
+}
+
 }  // namespace
 
 namespace ptmi {
@@ -180,6 +209,9 @@ void denoise_release(pt_ctx* c) {
     (void)hipFree(c->d_denoise);
     c->d_denoise = nullptr;
     c->denoise_bytes = 0;
+    (void)hipFree(c->d_frame_err);
+    c->d_frame_err = nullptr;
+    c->frame_err_bytes = 0;
 }
 
 }  // namespace ptmi
@@ -286,5 +318,42 @@ extern "C" int pt_denoise(pt_ctx* c, const pt_denoise_params* dp, const float* c
     }
     HIP_TRY(c, hipGetLastError());
     if (c->opt_timing) { HIP_TRY(c, hipEventRecord(c->ev1, st)); c->timed = true; }
+    return PT_OK;
+}
+
+extern "C" int pt_frame_error(pt_ctx* c, const float* moments_dev, int32_t width, int32_t height, uint64_t n_samples, float threshold,
+                              double* mean_rse, uint64_t* n_above) {
+    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
+    if (!moments_dev || (!mean_rse && !n_above)) return fail(c, PT_ERR_INVALID, "pt_frame_error: null argument");
+    if (width < 1 || height < 1) return fail(c, PT_ERR_INVALID, "pt_frame_error: width and height must be >= 1");
+    if (n_samples < 2) return fail(c, PT_ERR_INVALID, "pt_frame_error: the standard error needs n_samples >= 2");
+    if (!std::isfinite(threshold) || threshold < 0.f) return fail(c, PT_ERR_INVALID, "pt_frame_error: threshold must be finite and >= 0");
+    const size_t n_pix = (size_t)width * (size_t)height;
+    if (n_pix > 0xffffffffull) return fail(c, PT_ERR_INVALID, "pt_frame_error: more than 2^32 - 1 pixels");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n_blocks = (n_pix + 255) / 256;
+    const size_t need = n_blocks * (sizeof(double) + sizeof(uint32_t));
+    if (need > c->frame_err_bytes) {   // nothing reads the old slots: every earlier call synchronised before it returned
+        (void)hipFree(c->d_frame_err);
+        c->d_frame_err = nullptr;
+        c->frame_err_bytes = 0;
+        HIP_TRY(c, hipMalloc(&c->d_frame_err, need));
+        c->frame_err_bytes = need;
+    }
+    double* d_sums = (double*)c->d_frame_err;
+    uint32_t* d_counts = (uint32_t*)(d_sums + n_blocks);
+    hipLaunchKernelGGL(k_frame_error, dim3((unsigned)n_blocks), dim3(256), 0, c->stream, (const float2*)moments_dev, (uint32_t)n_pix,
+                       (float)(n_samples - 1), threshold, d_sums, d_counts);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<unsigned char> h(need);
+    HIP_TRY(c, hipMemcpyAsync(h.data(), c->d_frame_err, need, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const double* sums = (const double*)h.data();
+    const uint32_t* counts = (const uint32_t*)(sums + n_blocks);
+    double total = 0.0;
+    uint64_t above = 0;
+    for (size_t b = 0; b < n_blocks; b++) { total += sums[b]; above += counts[b]; }   // in block order: reproducible
+    if (mean_rse) *mean_rse = total / (double)n_pix;
+    if (n_above) *n_above = above;
     return PT_OK;
 }

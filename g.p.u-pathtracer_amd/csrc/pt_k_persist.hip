@@ -200,7 +200,11 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_trace_persist_bvh2(const KPar
 // Folds the spp sample colours of every owned pixel into the running mean, in sample order,
 // with the reference's per-frame clamp (tracer.cu:386-391) and packs the display word
 // (:394-398): exactly what spp consecutive single-sample launches do to the accumulator.
-__global__ void __launch_bounds__(256) k_fold_samples(const KParams P) {
+// MOM (pt_render_moments): the same lane also carries the pixel's luminance moments through its samples (pt_moments).  They
+// come as an argument of their own: KParams has no free slot, and growing it would move the kernel-argument offsets of
+// every kernel that takes something behind it.
+template <bool MOM>
+__global__ void __launch_bounds__(256) k_fold_samples(const KParams P, float2* __restrict__ moments) {
     const int lane = threadIdx.x & 63;
     const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
     int tx, ty;
@@ -211,10 +215,17 @@ __global__ void __launch_bounds__(256) k_fold_samples(const KParams P) {
     float* acc = P.accum + 3 * pix;
     float ax = 0.f, ay = 0.f, az = 0.f;
     if (P.sample_index != 1) { ax = acc[0]; ay = acc[1]; az = acc[2]; }
+    float m1 = 0.f, m2 = 0.f;
+    if constexpr (MOM) {
+        if (P.sample_index != 1) { const float2 m = moments[pix]; m1 = m.x; m2 = m.y; }
+    }
     for (uint32_t s = 0; s < P.spp; s++) {
         const float* c = pt_sample_ptr(P, s, pix);
-        pt_accumulate(ax, ay, az, pt_sld3(c), P.sample_index + s);
+        const v3 col = pt_sld3(c);
+        pt_accumulate(ax, ay, az, col, P.sample_index + s);
+        if constexpr (MOM) pt_moments(m1, m2, col, P.sample_index + s);
     }
+    if constexpr (MOM) moments[pix] = make_float2(m1, m2);
     acc[0] = ax; acc[1] = ay; acc[2] = az;
     if ((P.flags & PT_FLAG_WRITE_RGBA) && P.rgba) P.rgba[pix] = pt_pack_rgba(ax, ay, az);
 }
@@ -223,15 +234,15 @@ __global__ void __launch_bounds__(256) k_fold_samples(const KParams P) {
 // reading spp / LP consecutive samples in 16-byte pieces (four samples = three pieces; adjacent lanes read adjacent bytes, so a
 // wave covers whole 8-pixel runs of its tile end to end), the running mean handed from lane to lane so that the samples enter it
 // in order 0 .. spp-1 exactly as above.  LP = 4 for 16 samples per call, 2 for 8, 1 for 4 (largest of 4 / 2 / 1 dividing spp / 4).
-template <int LP>
-__global__ void __launch_bounds__(256) k_fold_samples_grouped(const KParams P) {
+template <int LP, bool MOM>
+__global__ void __launch_bounds__(256) k_fold_samples_grouped(const KParams P, float2* __restrict__ moments) {
     const int k = threadIdx.x / LP, part = threadIdx.x % LP;
     const int tile = blockIdx.x * (4 / LP) + (k >> 6);
     int tx = 0, ty = 0;
     const bool have_tile = pt_tile_coords(P, tile, tx, ty);   // the LP lanes of a pixel agree; nobody leaves before the last hand-over
     const int px = tx * PT_TILE + (k & 7), py = ty * PT_TILE + ((k >> 3) & 7);
     const bool in = have_tile && px < P.W && py < P.H;
-    pt_fold_pixel_grouped<LP>(P, in, in ? (size_t)py * (size_t)P.W + (size_t)px : 0, part);   // (pt_shade.h)
+    pt_fold_pixel_grouped<LP, MOM>(P, in, in ? (size_t)py * (size_t)P.W + (size_t)px : 0, part, moments);   // (pt_shade.h)
 }
 
 namespace ptmi {
@@ -254,13 +265,15 @@ hipError_t launch_persist(const LaunchCfg& L, const KParams& P, hipStream_t st) 
     });
 }
 
-hipError_t launch_fold(const KParams& P, hipStream_t st) {
-    if (P.smp_ps > 1u) {   // sample groups: spp is a multiple of 4
-        const uint32_t q = P.spp / 4u;
-        if ((q & 3u) == 0u) hipLaunchKernelGGL(k_fold_samples_grouped<4>, dim3(P.n_tiles), dim3(256), 0, st, P);
-        else if ((q & 1u) == 0u) hipLaunchKernelGGL(k_fold_samples_grouped<2>, dim3((P.n_tiles + 1) / 2), dim3(256), 0, st, P);
-        else hipLaunchKernelGGL(k_fold_samples_grouped<1>, dim3((P.n_tiles + 3) / 4), dim3(256), 0, st, P);
-    } else hipLaunchKernelGGL(k_fold_samples, dim3((P.n_tiles + 3) / 4), dim3(256), 0, st, P);
+hipError_t launch_fold(const KParams& P, float2* moments, hipStream_t st) {
+    with_bool(moments != nullptr, [&](auto mom) {   // pt_render_moments: the instantiations that keep the luminance moments too
+        if (P.smp_ps > 1u) {   // sample groups: spp is a multiple of 4
+            const uint32_t q = P.spp / 4u;
+            if ((q & 3u) == 0u) hipLaunchKernelGGL((k_fold_samples_grouped<4, mom()>), dim3(P.n_tiles), dim3(256), 0, st, P, moments);
+            else if ((q & 1u) == 0u) hipLaunchKernelGGL((k_fold_samples_grouped<2, mom()>), dim3((P.n_tiles + 1) / 2), dim3(256), 0, st, P, moments);
+            else hipLaunchKernelGGL((k_fold_samples_grouped<1, mom()>), dim3((P.n_tiles + 3) / 4), dim3(256), 0, st, P, moments);
+        } else hipLaunchKernelGGL(k_fold_samples<mom()>, dim3((P.n_tiles + 3) / 4), dim3(256), 0, st, P, moments);
+    });
     return hipGetLastError();
 }
 

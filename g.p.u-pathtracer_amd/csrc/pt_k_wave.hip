@@ -629,7 +629,8 @@ static WavePlan wave_plan(const pt_ctx* c, const KParams& P, const LaunchCfg& L,
     p.packet = c->opt_first_walk == 1 && 3 * c->wide_depth + 2 <= (uint32_t)c->opt_packet_stack;
     const bool fuse = c->opt_fuse_stages != 0 && !nee && !L.count, tri_dark = P.tri_emi[0] == 0.f && P.tri_emi[1] == 0.f && P.tri_emi[2] == 0.f;
     p.fuse_first = fuse && p.packet;
-    p.fold_lp = fuse && P.depth >= 2 && P.sgroup_log2 >= 2 && P.sgroup_log2 <= 4 && P.spp == (1u << P.sgroup_log2) ? (int)P.spp / 4 : 0;
+    // ... and the call keeps no luminance moments (pt_render_moments): those are the separate fold launch's job
+    p.fold_lp = fuse && !L.moments && P.depth >= 2 && P.sgroup_log2 >= 2 && P.sgroup_log2 <= 4 && P.spp == (1u << P.sgroup_log2) ? (int)P.spp / 4 : 0;
     p.anyhit = (L.count ? c->opt_last_anyhit == 2 : c->opt_last_anyhit >= 1) && P.depth >= 2 && !nee && !P.tri_matid && tri_dark &&
                P.sc.n_spheres <= PT_KSPHERES && !c->records_woop;
     return p;

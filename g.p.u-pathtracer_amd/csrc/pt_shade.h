@@ -425,6 +425,15 @@ __device__ __forceinline__ void pt_accumulate(float& ax, float& ay, float& az, v
     az = pt_clamp01((az + col.z) * inv);
 }
 
+// pt_render_moments: running mean of the luminance L of the sample colours (before the fold's clamp) and of L * L, N as in
+// pt_accumulate.  Plain * and + (the build has -ffp-contract=off): every step is one binary32 rounding, so that numpy float32
+// restates it exactly (tests/moments_ref.py).  No clamp: a firefly must show in m2.
+__device__ __forceinline__ void pt_moments(float& m1, float& m2, v3 col, uint64_t N) {
+    const float L = (0.2126f * col.x + 0.7152f * col.y) + 0.0722f * col.z;
+    const float fm1 = (float)(N - 1), inv = 1.0f / (float)N;
+    if (N == 1) { m1 = L; m2 = L * L; } else { m1 = (m1 * fm1 + L) * inv; m2 = (m2 * fm1 + L * L) * inv; }
+}
+
 // 8-bit truncating pack 0x00BBGGRR, tracer.cu:394-398 + cudaUtils.h:99-105
 __device__ __forceinline__ uint32_t pt_pack_rgba(float ax, float ay, float az) {
     const uint32_t r = (uint32_t)(unsigned char)(255.0f * ax);
@@ -438,11 +447,17 @@ __device__ __forceinline__ uint32_t pt_pack_rgba(float ax, float ay, float az) {
 // running mean handed from lane to lane so that the samples enter it in order 0 .. spp-1; part 0 writes the accumulator and
 // the display word.  All 64 lanes of the wave call it (the hand-over is a shuffle); `in` is false for pixels that do not exist.
 // k_fold_samples_grouped and the last shade launch of the stage-split pipeline (k_wf_shade, FOLD) both fold through it.
-template <int LP>
-__device__ __forceinline__ void pt_fold_pixel_grouped(const KParams& P, bool in, size_t pix, int part) {
+// MOM (pt_render_moments): the luminance moments `moments` [H*W] travel with the mean — read by part 0, handed on by the same
+// shuffles, written by part 0: one 8-byte load and one store per pixel.
+template <int LP, bool MOM = false>
+__device__ __forceinline__ void pt_fold_pixel_grouped(const KParams& P, bool in, size_t pix, int part, float2* __restrict__ moments = nullptr) {
     float* acc = P.accum + 3 * pix;
     float ax = 0.f, ay = 0.f, az = 0.f;
     if (in && P.sample_index != 1) { ax = acc[0]; ay = acc[1]; az = acc[2]; }
+    float m1 = 0.f, m2 = 0.f;
+    if constexpr (MOM) {
+        if (in && part == 0 && P.sample_index != 1) { const float2 m = moments[pix]; m1 = m.x; m2 = m.y; }
+    }
     const uint32_t per = P.spp / (uint32_t)LP, s0 = (uint32_t)part * per;   // a multiple of 4 samples
     const float4* c4 = (const float4*)pt_sample_ptr(P, s0, pix);
     // one group of four (the 16-, 8- and 4-sample calls): requested before the hand-over chain starts; longer shares stream theirs
@@ -460,14 +475,22 @@ __device__ __forceinline__ void pt_fold_pixel_grouped(const KParams& P, bool in,
                 pt_accumulate(ax, ay, az, V3(qa.w, qb.x, qb.y), P.sample_index + s0 + s + 1);
                 pt_accumulate(ax, ay, az, V3(qb.z, qb.w, qd.x), P.sample_index + s0 + s + 2);
                 pt_accumulate(ax, ay, az, V3(qd.y, qd.z, qd.w), P.sample_index + s0 + s + 3);
+                if constexpr (MOM) {
+                    pt_moments(m1, m2, V3(qa.x, qa.y, qa.z), P.sample_index + s0 + s);
+                    pt_moments(m1, m2, V3(qa.w, qb.x, qb.y), P.sample_index + s0 + s + 1);
+                    pt_moments(m1, m2, V3(qb.z, qb.w, qd.x), P.sample_index + s0 + s + 2);
+                    pt_moments(m1, m2, V3(qd.y, qd.z, qd.w), P.sample_index + s0 + s + 3);
+                }
             }
         }
         if (LP > 1) {   // the share that just ran hands the mean on
             const int src = (lane & ~(LP - 1)) | turn;
             ax = __shfl(ax, src); ay = __shfl(ay, src); az = __shfl(az, src);
+            if constexpr (MOM) { m1 = __shfl(m1, src); m2 = __shfl(m2, src); }
         }
     }
     if (!in || part != 0) return;
+    if constexpr (MOM) moments[pix] = make_float2(m1, m2);
     acc[0] = ax; acc[1] = ay; acc[2] = az;
     if ((P.flags & PT_FLAG_WRITE_RGBA) && P.rgba) P.rgba[pix] = pt_pack_rgba(ax, ay, az);
 }

@@ -597,6 +597,12 @@ int pt_scene_info(pt_ctx* c, uint64_t* n_inner, uint64_t* n_refs, uint64_t* n_le
 
 // ---------------------------------------------------------------------------------------
 int pt_render(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, const pt_camera* cam, const pt_params* p, uint32_t spp) {
+    return pt_render_moments(c, accum_dev, rgba_dev, nullptr, cam, p, spp);
+}
+
+// pt_render's body; moments_dev != NULL: the fold also keeps the luminance moments of the samples
+int pt_render_moments(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, float* moments_dev, const pt_camera* cam, const pt_params* p,
+                      uint32_t spp) {
     if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
     if (!accum_dev || !cam || !p) return fail(c, PT_ERR_INVALID, "pt_render: null argument");
     if (p->width < 2 || p->height < 2) return fail(c, PT_ERR_INVALID, "pt_render: image must be at least 2x2 (the camera divides by w-1, h-1)");
@@ -690,7 +696,8 @@ int pt_render(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, const pt_camera* 
             uint64_t key = 0xcbf29ce484222325ull;
             const uint64_t parts[] = {(uint64_t)p->width, (uint64_t)p->height, (uint64_t)spp, (uint64_t)p->depth,
                                       (uint64_t)(p->part_count > 1 ? p->part_count : 1), (uint64_t)(p->part_count > 1 ? p->part_rows : 0), c->scene_gen,
-                                      (uint64_t)c->n_spheres, (uint64_t)p->tri_mat, (uint64_t)(p->flags & ~(uint32_t)PT_FLAG_WRITE_RGBA)};
+                                      (uint64_t)c->n_spheres, (uint64_t)p->tri_mat, (uint64_t)(p->flags & ~(uint32_t)PT_FLAG_WRITE_RGBA),
+                                      (uint64_t)(moments_dev != nullptr)};   // with moments the pipeline keeps its separate fold and one sample goes through the sample buffer: other trial times
             for (uint64_t v : parts) { key ^= v; key *= 0x100000001b3ull; }
             if (key == 0) key = 1;
             int slot = -1, lru = 0;
@@ -762,7 +769,7 @@ int pt_render(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, const pt_camera* 
             HIP_TRY(c, hipMalloc((void**)&sd->queue, PT_SHARDS * PT_SHARD_STRIDE * sizeof(unsigned int)));
         }
     }
-    if (spp > 1 || wavefront || sd) {
+    if (spp > 1 || wavefront || sd || moments_dev) {   // the moments are the fold's job: such a call always has a sample buffer
         const size_t need = (size_t)spp * (size_t)p->width * (size_t)p->height * 3 * sizeof(float);
         float*& buf = sd ? sd->samples : c->d_samples;
         size_t& have = sd ? sd->samples_bytes : c->samples_bytes;
@@ -856,6 +863,7 @@ int pt_render(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, const pt_camera* 
     L.blocks = (work_tiles + waves_per_block - 1) / waves_per_block;
     L.work_blocks = (int)(((long)work_tiles * 64 + P.chunk * (PT_BLOCK / 64) - 1) / (P.chunk * (PT_BLOCK / 64)));
     L.n_cu = c->n_cu;
+    L.moments = moments_dev != nullptr;
     bool folded = false;
     if (wavefront) {
         const int rc = render_wavefront(c, P, L, work_tiles, folded);
@@ -872,7 +880,7 @@ int pt_render(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, const pt_camera* 
         HIP_TRY(c, hipStreamWaitEvent(c->stream, sd->traced, 0));
     }
     if (P.samples && !folded) {
-        HIP_TRY(c, launch_fold(P, c->stream));
+        HIP_TRY(c, launch_fold(P, (float2*)moments_dev, c->stream));
         if (stage_mark(c, PT_STAGE_FOLD) != PT_OK) return PT_ERR_DEVICE;
     }
     if (sd) {

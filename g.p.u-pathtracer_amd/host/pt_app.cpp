@@ -8,7 +8,7 @@
 //               --depth 4 --mat 0..3 --no-spheres --no-materials --bk r g b --device 0
 //               --out image.ppm|.png|.pfm  --checkpoint state.ckpt [--checkpoint-every N]
 //               --resume state.ckpt --device-build --fix-estimators --nee --gpus N --tile ROWS
-//               --denoise-out image.ppm|.png|.pfm]
+//               --denoise-out image.ppm|.png|.pfm  --variance-out file.pfm  --until-error E --max-frames M]
 // --gpus N splits the framebuffer over N contexts, one per GPU (devices device, device+1, ... modulo the number
 // present, so N > 1 also runs on a one-GPU box): stripes of --tile rows (default 8) are dealt round-robin
 // (pt_params.part_*), every context holds the whole scene and renders only its stripes of every frame — the random
@@ -24,6 +24,13 @@
 // --denoise-out also writes the final accumulator through pt_denoise (guides from pt_render_aux, the library's default
 // filter settings), format by extension as --out; with --gpus N the gathered frame is denoised on the first context.
 // --out is written first and is the same image with or without it.
+// --variance-out and --until-error render through pt_render_moments: every context keeps the luminance moments of its stripes
+// beside its accumulator (gathered with it).  --variance-out writes the variance of the pixel's mean luminance,
+// max(0, m2 - m1^2) / (n - 1), as a PFM (one value per pixel, grey in three channels).  --until-error E keeps rendering calls of
+// --spp samples past --frames (now the minimum) until pt_frame_error's mean_rse <= E, checked after every call, and never past
+// --max-frames samples per pixel (required with it); it prints the samples rendered and the final figure.  With --gpus N the
+// figure is computed on the first context from the gathered moments.  The --out image of such a run equals that of a plain run
+// with the same number of samples byte for byte.  Checkpoints hold no moments, so neither option combines with --resume.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -41,10 +48,12 @@ static int die(const char* what, const char* msg) {
 }
 
 int main(int argc, char** argv) {
-    std::string mesh_path, out_path, ckpt_path, resume_path, denoise_path;
+    std::string mesh_path, out_path, ckpt_path, resume_path, denoise_path, variance_path;
     int W = 1280, H = 720, frames = 16, depth = 4, mat = PT_MAT_DIFF, device = 0, spp = 1, ckpt_every = 0, gpus = 1, tile = 8;
     bool spheres = true, use_materials = true, device_build = false, fix_estimators = false, nee = false;
     float bk[3] = {1.f, 1.f, 1.f};
+    double until_error = -1.0;   // < 0: off
+    long max_frames = -1;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&](const char* name) -> const char* {
@@ -54,6 +63,9 @@ int main(int argc, char** argv) {
         if (a == "--mesh") mesh_path = next("--mesh");
         else if (a == "--out") out_path = next("--out");
         else if (a == "--denoise-out") denoise_path = next("--denoise-out");
+        else if (a == "--variance-out") variance_path = next("--variance-out");
+        else if (a == "--until-error") until_error = std::atof(next("--until-error"));
+        else if (a == "--max-frames") max_frames = std::atol(next("--max-frames"));
         else if (a == "--width") W = std::atoi(next("--width"));
         else if (a == "--height") H = std::atoi(next("--height"));
         else if (a == "--frames") frames = std::atoi(next("--frames"));
@@ -77,6 +89,11 @@ int main(int argc, char** argv) {
     if (mesh_path.empty()) return die("usage", "--mesh <file.obj|file.ptmesh> is required");
     if (spp < 1 || frames < 0 || W < 2 || H < 2) return die("usage", "--spp >= 1, --frames >= 0, --width/--height >= 2");
     if (gpus < 1 || gpus > 64 || tile < 8 || tile % 8) return die("usage", "--gpus 1..64, --tile a positive multiple of 8");
+
+    const bool until = until_error >= 0.0, with_moments = until || !variance_path.empty();
+    if (until && max_frames < (long)frames) return die("usage", "--until-error needs --max-frames >= --frames");
+    if (!until && max_frames >= 0) return die("usage", "--max-frames goes with --until-error");
+    if (with_moments && !resume_path.empty()) return die("usage", "--variance-out / --until-error do not combine with --resume (a checkpoint holds no moments)");
 
     const bool is_ptmesh = mesh_path.size() > 7 && mesh_path.substr(mesh_path.size() - 7) == ".ptmesh";
     pth_mesh* mesh = is_ptmesh ? pth_mesh_load_ptmesh(mesh_path.c_str()) : pth_mesh_load_obj(mesh_path.c_str());
@@ -168,6 +185,15 @@ int main(int argc, char** argv) {
         pt_memset(ctxs[(size_t)g], accums[(size_t)g], 0, (size_t)W * H * 12);
     }
     void *accum = accums[0], *rgba = rgbas[0];
+    // the luminance moments of every context's stripes (pt_render_moments), and on the first context a buffer for the gathered ones
+    std::vector<void*> moments((size_t)gpus, nullptr);
+    void* moments_all = nullptr;
+    if (with_moments) {
+        for (int g = 0; g < gpus; g++)
+            if (pt_malloc(ctxs[(size_t)g], (size_t)W * H * 8, &moments[(size_t)g]) != PT_OK) return die("pt_malloc", pt_last_error(ctxs[(size_t)g]));
+        moments_all = moments[0];
+        if (gpus > 1 && until && pt_malloc(ctx, (size_t)W * H * 8, &moments_all) != PT_OK) return die("pt_malloc", pt_last_error(ctx));
+    }
     // gather: rows of stripe s belong to context s % gpus; `elem` bytes per pixel
     std::vector<unsigned char> part_buf;
     auto gather = [&](std::vector<void*>& dev, void* host, size_t elem) -> int {
@@ -209,26 +235,47 @@ int main(int argc, char** argv) {
         return 0;
     };
 
-    const uint64_t end_frame = frameNumber + (uint64_t)frames;
+    const uint64_t first_frame = frameNumber;
+    uint64_t end_frame = frameNumber + (uint64_t)frames;
+    const uint64_t last_frame = until ? frameNumber + (uint64_t)max_frames : end_frame;   // --until-error: never past --max-frames
+    std::vector<float> host_mom;
+    double mean_rse = -1.0;   // pt_frame_error's figure after the last call, < 0: not computed (fewer than two samples)
     int calls = 0;
     auto t0 = std::chrono::steady_clock::now();
-    while (frameNumber < end_frame) {
-        for (pt_ctx* cx : ctxs)
-            if (pt_sync(cx) != PT_OK) return die("pt_sync", pt_last_error(cx));     // :395
-        const uint32_t n = (uint32_t)std::min<uint64_t>((uint64_t)spp, end_frame - frameNumber);
-        p.frame = frameNumber;                                                      // :397
-        p.sample_index = constantPdf + 1;                                           // :399 (1 on the first frame: overwrite)
-        for (int g = 0; g < gpus; g++) {                                            // :404, once per GPU: asynchronous, so the GPUs run side by side
-            p.part_index = g;
-            if (pt_render(ctxs[(size_t)g], (float*)accums[(size_t)g], (uint32_t*)rgbas[(size_t)g], &cam, &p, n) != PT_OK)
-                return die("pt_render", pt_last_error(ctxs[(size_t)g]));
+    for (;;) {
+        while (frameNumber < end_frame) {
+            for (pt_ctx* cx : ctxs)
+                if (pt_sync(cx) != PT_OK) return die("pt_sync", pt_last_error(cx));     // :395
+            const uint32_t n = (uint32_t)std::min<uint64_t>((uint64_t)spp, end_frame - frameNumber);
+            p.frame = frameNumber;                                                      // :397
+            p.sample_index = constantPdf + 1;                                           // :399 (1 on the first frame: overwrite)
+            for (int g = 0; g < gpus; g++) {                                            // :404, once per GPU: asynchronous, so the GPUs run side by side
+                p.part_index = g;
+                if (pt_render_moments(ctxs[(size_t)g], (float*)accums[(size_t)g], (uint32_t*)rgbas[(size_t)g], (float*)moments[(size_t)g], &cam, &p, n) != PT_OK)
+                    return die("pt_render", pt_last_error(ctxs[(size_t)g]));
+            }
+            frameNumber += n;
+            constantPdf += n;
+            calls++;
+            if (!ckpt_path.empty() && ckpt_every > 0 && calls % ckpt_every == 0 && frameNumber < end_frame)
+                if (int rc = save_checkpoint()) return rc;
         }
-        frameNumber += n;
-        constantPdf += n;
-        calls++;
-        if (!ckpt_path.empty() && ckpt_every > 0 && calls % ckpt_every == 0 && frameNumber < end_frame)
-            if (int rc = save_checkpoint()) return rc;
+        if (!until) break;
+        if (constantPdf >= 2) {   // the frame's error so far: the stripes' moments gathered onto the first context
+            if (gpus > 1) {
+                host_mom.resize((size_t)W * H * 2);
+                if (int grc = gather(moments, host_mom.data(), 8)) return grc;
+                if (pt_upload(ctx, moments_all, host_mom.data(), host_mom.size() * 4) != PT_OK) return die("pt_upload", pt_last_error(ctx));
+            }
+            if (pt_frame_error(ctx, (const float*)moments_all, W, H, constantPdf, 0.f, &mean_rse, nullptr) != PT_OK)
+                return die("pt_frame_error", pt_last_error(ctx));
+            if (mean_rse <= until_error) break;
+        }
+        if (frameNumber >= last_frame) break;
+        end_frame = std::min<uint64_t>(frameNumber + (uint64_t)spp, last_frame);
     }
+    frames = (int)(frameNumber - first_frame);   // what was rendered: more than asked for under --until-error
+    if (until) std::printf("until-error %g: %d frames rendered, mean_rse %.6g\n", until_error, frames, mean_rse);
     for (pt_ctx* cx : ctxs) pt_sync(cx);
     double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     const double rays = (double)W * H * depth * frames;
@@ -259,6 +306,19 @@ int main(int argc, char** argv) {
             rc = ext == ".png" ? pth_write_png(out_path.c_str(), img.data(), W, H) : pth_write_ppm(out_path.c_str(), img.data(), W, H);
         }
         if (rc != 0) return die("write", pth_last_error());
+    }
+    if (!variance_path.empty()) {   // variance of the mean luminance per pixel from the gathered moments
+        if (constantPdf < 2) return die("variance-out", "needs at least two samples per pixel");
+        const size_t n_pix = (size_t)W * H;
+        host_mom.resize(n_pix * 2);
+        if (int grc = gather(moments, host_mom.data(), 8)) return grc;
+        std::vector<float> img(n_pix * 3);
+        const float nm1 = (float)(constantPdf - 1);
+        for (size_t i = 0; i < n_pix; i++) {
+            const float m1 = host_mom[2 * i], m2 = host_mom[2 * i + 1];
+            img[3 * i] = img[3 * i + 1] = img[3 * i + 2] = std::max(0.f, m2 - m1 * m1) / nm1;
+        }
+        if (pth_write_pfm(variance_path.c_str(), img.data(), W, H) != 0) return die("write", pth_last_error());
     }
     if (!denoise_path.empty()) {   // guides of the pixel centres + the a-trous filter of the final accumulator, on the first context
         const size_t n_pix = (size_t)W * H;
@@ -292,7 +352,9 @@ int main(int argc, char** argv) {
         if (color != accum) pt_free(ctx, color);
     }
     (void)accum; (void)rgba;
+    if (moments_all != moments[0]) pt_free(ctx, moments_all);
     for (int g = 0; g < gpus; g++) {
+        if (moments[(size_t)g]) pt_free(ctxs[(size_t)g], moments[(size_t)g]);
         pt_free(ctxs[(size_t)g], accums[(size_t)g]);
         pt_free(ctxs[(size_t)g], rgbas[(size_t)g]);
         pt_destroy(ctxs[(size_t)g]);

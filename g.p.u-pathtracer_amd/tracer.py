@@ -171,9 +171,21 @@ class PathTracer:
         rgba.zero()
         return acc, rgba
 
-    def launch_kernel(self, accum_ptr, rgba_ptr, cam, params, spp=1):
-        """render(accum, bvh, camera, spp): asynchronous until sync()."""
-        self._check(self._lib.pt_render(self._ctx, accum_ptr, rgba_ptr, C.byref(cam), C.byref(params), spp))
+    def launch_kernel(self, accum_ptr, rgba_ptr, cam, params, spp=1, moments_ptr=None):
+        """render(accum, bvh, camera, spp): asynchronous until sync().  moments_ptr: float[H][W][2] device memory that also
+        receives the running (m1, m2) of the samples' luminance (pt_render_moments)."""
+        if moments_ptr is None:
+            self._check(self._lib.pt_render(self._ctx, accum_ptr, rgba_ptr, C.byref(cam), C.byref(params), spp))
+        else:
+            self._check(self._lib.pt_render_moments(self._ctx, accum_ptr, rgba_ptr, moments_ptr, C.byref(cam), C.byref(params), spp))
+
+    def frame_error(self, moments_ptr, width, height, n_samples, threshold=0.0):
+        """(mean relative standard error of the pixels' mean luminance, pixels whose own exceeds `threshold`) from the moments
+        of n_samples samples per pixel (pt_frame_error).  Synchronises."""
+        mean, above = C.c_double(), C.c_uint64()
+        self._check(self._lib.pt_frame_error(self._ctx, moments_ptr, int(width), int(height), int(n_samples), float(threshold),
+                                             C.byref(mean), C.byref(above)))
+        return mean.value, above.value
 
     def trace_rays(self, rays_ptr, n, cull, t_ptr, tri_ptr, normal_ptr=None):
         self._check(self._lib.pt_trace_rays(self._ctx, rays_ptr, n, int(cull), t_ptr, tri_ptr, normal_ptr))

@@ -376,6 +376,37 @@ int pt_upload_tri_materials(pt_ctx* ctx, const pt_material* table, size_t n_mate
 int pt_render(pt_ctx* ctx, float* accum_dev, uint32_t* rgba_dev,
               const pt_camera* cam, const pt_params* params, uint32_t spp);
 
+/* pt_render that also keeps the luminance moments of its samples — an EXTENSION: what an error-driven stop,
+ * adaptive sampling or a variance-aware filter start from (the accumulator is a CLAMPED running mean, so its own history does
+ * not say how noisy a pixel is).  moments_dev: float[height][width][2] = (m1, m2), device memory, 8-byte aligned.
+ * moments_dev == NULL: exactly pt_render.  Otherwise the accumulator and the display words are what pt_render writes, bit for
+ * bit, and for every pixel the call owns (part_* as for the accumulator) and every sample s of the call in order, with
+ * N = sample_index + s and col the sample colour BEFORE the fold's clamp:
+ *     L  = (0.2126f * col.x + 0.7152f * col.y) + 0.0722f * col.z        plain * and +, every step one binary32 rounding
+ *     m1 = N == 1 ? L     : (m1 * (float)(N - 1) + L)     * (1.0f / (float)N)
+ *     m2 = N == 1 ? L * L : (m2 * (float)(N - 1) + L * L) * (1.0f / (float)N)
+ * No clamp (a firefly shows in m2) and no fused multiply-add, so that binary32 arithmetic anywhere restates it exactly.
+ * N == 1 overwrites, as for the accumulator: the moments continue across calls, and spp samples in one call equal any split of
+ * them over several calls bit for bit.  Pixels the call does not own are not touched.  Errors, flags, materials, partitions and
+ * every PT_OPT_* as pt_render; the moments depend on them only through the sample colours.  The moments are kept by the fold
+ * launch over the call's sample buffer, so such a call always has one: a one-sample call of the persistent / mega kernels does
+ * not fold in line, and the stage-split pipeline keeps its separate fold launch (PT_OPT_FUSE_STAGES fuses bounce 0 only).
+ * PT_KERNEL_AUTO decides for calls with and without moments separately. */
+int pt_render_moments(pt_ctx* ctx, float* accum_dev, uint32_t* rgba_dev, float* moments_dev,
+                      const pt_camera* cam, const pt_params* params, uint32_t spp);
+
+/* One error figure for a frame from its moments after n_samples samples per pixel.  Per pixel, in binary32:
+ *     var = max(0, m2 - m1 * m1),   rse = sqrtf(var / (float)(n_samples - 1)) / (m1 + 0.01f)
+ * — the relative standard error of the mean luminance; 0.01 is a floor that keeps a black pixel at 0 instead of 0 / 0 (a
+ * definition, not a tuned value).  *mean_rse = sum of rse over all width x height pixels / their number (summed in double per
+ * 256-pixel block on the device, the blocks added on the host in order: the same figure run after run); *n_above = pixels with
+ * rse > threshold.  Either output may be NULL, not both.  moments_dev: float[height][width][2], device memory.
+ * PT_ERR_INVALID: NULL ctx / moments / both outputs, width or height < 1, n_samples < 2, a threshold that is not finite or is
+ * negative.  No scene needed.  Synchronises the context's stream (hence ordered after the folds of earlier calls).  Its scratch
+ * (12 bytes per 256 pixels) belongs to the context: grown on demand, freed by pt_destroy. */
+int pt_frame_error(pt_ctx* ctx, const float* moments_dev, int32_t width, int32_t height,
+                   uint64_t n_samples, float threshold, double* mean_rse, uint64_t* n_above);
+
 /* Closest-hit query on an explicit ray batch (rows a5–a7 of SURVEY.md §8 in isolation,
  * = intersectBVHandTriangles, cudaUtils.h:256-460).  rays_dev: float[n][8] =
  * (ox,oy,oz,tmin=0, dx,dy,dz,unused); out t_dev float[n] (F32_MAX on miss),

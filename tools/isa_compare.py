@@ -3,7 +3,10 @@
 -Rpass-analysis=kernel-resource-usage remarks and the instruction streams of the two assembly files.
 
   make -C g.p.u-pathtracer_amd isa K=pt_k_wave 2> wave.remarks && cp /tmp/pt_k_wave.gfx950.s wave.s      (at both commits)
-  tools/isa_compare.py parent/wave.remarks parent/wave.s head/wave.remarks head/wave.s
+  tools/isa_compare.py parent/wave.remarks parent/wave.s head/wave.remarks head/wave.s [--rename OLD=NEW ...]
+
+--rename OLD=NEW (mangled names, repeatable): the parent's kernel OLD is compared with the head's NEW — for a kernel whose
+name changed but whose code must not have, such as one that gained a template argument.
 
 A stream is a kernel's lines without comments, directives and blank lines, every local label (.LBBn_m) renamed to one token.
 Prints one line per kernel: VGPRs, then occupancy / scratch / SGPR spill / VGPR spill / LDS on both sides, the instruction
@@ -32,7 +35,7 @@ def resources(path):
 def streams(path):
     out, cur = {}, None
     for line in open(path, errors="replace"):
-        m = re.match(r"(_Z\w+):\s", line)
+        m = re.match(r"([A-Za-z_]\w*):\s", line)   # mangled, or extern "C"
         if m:
             cur = out.setdefault(m.group(1), [])
             continue
@@ -57,6 +60,10 @@ def demangle(names):
 
 def main():
     ra, sa, rb, sb = resources(sys.argv[1]), streams(sys.argv[2]), resources(sys.argv[3]), streams(sys.argv[4])
+    for k in range(5, len(sys.argv) - 1, 2):
+        assert sys.argv[k] == "--rename", sys.argv[k]
+        old, new = sys.argv[k + 1].split("=")
+        ra[new], sa[new] = ra.pop(old), sa.pop(old)
     names = sorted(set(ra) | set(rb))
     pretty = demangle(names)
     bad = False
