@@ -18,7 +18,8 @@
 //     shade    one lane per live record, every wave full: spheres, shading, BRDF sample (tracer.cu:98-296);
 //              emitted light is added to the sample colour in place, a miss writes the background
 //              (tracer.cu:140-142), survivors are packed to the front of their region's next generation with
-//              a ballot + prefix count (v_mbcnt) — dead paths cost nothing in the next stage
+//              a ballot + prefix count (v_mbcnt) — dead paths cost nothing in the next stage; survivors whose new ray
+//              the tree's root turns away are packed behind the others and never queued (PT_OPT_ROOT_CULL)
 //   k_fold_samples folds the sample colours into the running mean (tracer.cu:386-391), as for every kernel.
 // Which of the kernels below a bounce runs: WavePlan, at the end of the file.  Why the split pays: DESIGN.md §5.2.
 #include "pt_ctx.h"
@@ -67,6 +68,12 @@ __global__ void __launch_bounds__(256) k_wf_prepare(const KParams P) {
 __device__ __forceinline__ bool wf_slot_pixel(const KParams& P, uint32_t slot, uint32_t& s_idx, int& px, int& py) {
     if (slot >= P.wf.n_slots) return false;
     return pt_slot_pixel(P, slot, s_idx, px, py);
+}
+
+// the h.t an any-hit lane starts its walk with, for the sphere bound ts of its hit slot: t <= ts as the walk's t < h.t, so one bit up
+// (ts > 0.01; PT_F32_MAX = no sphere stays)
+__device__ __forceinline__ float wf_anyhit_start(float ts) {
+    return ts < PT_F32_MAX ? __uint_as_float(__float_as_uint(ts) + 1u) : ts;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -123,7 +130,7 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_wf_extend(const KParams P) {
                         if (k < shard_regions && r < n_regions) {
                             next = r * PT_REGION;
                             if (FIRST) end = min(next + (uint32_t)PT_REGION, P.wf.n_slots);
-                            else end = next + (uint32_t)__builtin_amdgcn_readfirstlane(P.wf.cnt_in[r]);
+                            else end = next + (uint32_t)__builtin_amdgcn_readfirstlane(P.wf.walk_in[r]);
                             got = true;
                         } else {
                             shard = (shard + 1) & (PT_SHARDS - 1);
@@ -153,8 +160,7 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_wf_extend(const KParams P) {
                         live = true;
                     }
                     if (live) trav_begin(ts, o, d, stk, P.sc.wide_root);
-                    // t <= ts as the walk's t < h.t: one bit up (ts > 0.01; PT_F32_MAX = no sphere stays)
-                    if (ANY) ts.h.t = bound < PT_F32_MAX ? __uint_as_float(__float_as_uint(bound) + 1u) : bound;
+                    if (ANY) ts.h.t = wf_anyhit_start(bound);
                 }
                 next += take;
                 served += take;
@@ -303,6 +309,48 @@ __device__ __forceinline__ float2 wf_sphere_bound(const KParams& P, const PathSt
     return make_float2(sh.t, __int_as_float(sh.sph_id));
 }
 
+// PT_OPT_ROOT_CULL: where a surviving path's record goes inside its region, in two classes that each keep the slot order — the
+// WALKERS at [0, n_walk), then the WALK-FREE records up to `total`: those whose new ray the next extend launch's first node step, on
+// the tree's root with the h.t the lane would start with (ts: the sphere bound of a BOUND launch's survivor), would leave without a
+// child.  That lane would pop the sentinel and report pt_no_hit(), or leave ts in place; here the lane that made the ray runs the
+// step itself — the walk's own functions on the root fetched once per wave with scalar loads, so the verdict is the walk's bit for
+// bit — and the extend launch only draws a region's first n_walk records.  Every lane of the block calls it.
+template <bool BOUND>
+__device__ __forceinline__ int wf_survivor_slot(const KParams& P, bool alive, const PathState& ps, float ts, bool& walk_free, int& n_walk,
+                                                int& total, int* s_cnt, int* s_cnt_free) {
+    walk_free = false;
+    if (P.wf.root_cull) {   // (wave-uniform)
+        const WideNode root = wide_node_load_uniform(P.sc, P.sc.wide_root);
+        if (alive) {
+            TravState s;
+            trav_ray(s, ps.o, ps.d);
+            uint32_t key[4];
+            wide_node_keys_raw(root, s.idx, s.idy, s.idz, s.oodx, s.oody, s.oodz, BOUND ? wf_anyhit_start(ts) : PT_F32_MAX, key);
+            walk_free = (key[0] & key[1] & key[2] & key[3]) == 0xffffffffu;
+        }
+    }
+    const int r = PT_SURVIVOR_RANK(P, alive && !walk_free, ps, n_walk, s_cnt);
+    total = n_walk;
+    if (!P.wf.root_cull) return r;
+    int n_free;
+    const int rf = PT_SURVIVOR_RANK(P, walk_free, ps, n_free, s_cnt_free);
+    total += n_free;
+    return walk_free ? n_walk + rf : r;
+}
+
+// the counts of a region's next generation; an instrumented launch that classifies (PT_OPT_ROOT_CULL 2) books the rays it kept out
+// of the queue, which no extend wave will count
+template <bool COUNT>
+__device__ __forceinline__ void wf_region_counts(const KParams& P, uint32_t region, int n_walk, int total) {
+    if (threadIdx.x != 0) return;
+    P.wf.cnt_out[region] = total;
+    P.wf.walk_out[region] = n_walk;
+    if (COUNT && total != n_walk) {
+        atomicAdd(&P.counters[PT_CNT_RAYS], (unsigned long long)(total - n_walk));
+        atomicAdd(&P.counters[PT_CNT_WALK_FREE], (unsigned long long)(total - n_walk));
+    }
+}
+
 // FOLD (PT_OPT_FUSE_STAGES, LAST only): LP of wf_fold_region — this launch also folds the samples, no k_fold_samples follows
 // BOUND (PT_OPT_LAST_ANYHIT, the shade launch of bounce depth - 2): the survivors' rays are the paths' last segments; their
 // sphere bound goes to the survivor's hit slot for k_wf_extend<.., ANY> and k_wf_shade_last_any
@@ -310,11 +358,12 @@ template <bool COUNT, bool NEE, bool FIRST, bool LAST = false, int FOLD = 0, boo
 __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
     __shared__ int s_cnt[PT_BLOCK / 64];
     __shared__ int s_cnt2[PT_BLOCK / 64];
+    __shared__ int s_cnt_free[PT_BLOCK / 64];
     const uint32_t region = blockIdx.x;
     const int n_in = FIRST ? PT_REGION : P.wf.cnt_in[region];
     const bool last = LAST || P.wf.bounce + 1 >= P.depth;
     if (n_in == 0) {   // (the whole block: before anything is set up — in an open scene most regions are empty after the first bounce)
-        if (!last && threadIdx.x == 0) P.wf.cnt_out[region] = 0;
+        if (!last) wf_region_counts<false>(P, region, 0, 0);
         if (NEE && threadIdx.x == 0) P.wf.s_cnt[region] = 0;
         if constexpr (FOLD > 0) wf_fold_region<FOLD>(P, region);   // every path of the region ended earlier: its samples are final
         return;
@@ -393,8 +442,9 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
         }
         return;
     }
-    int total;
-    const int r = PT_SURVIVOR_RANK(P, alive, ps, total, s_cnt);
+    int n_walk, total;
+    bool walk_free;
+    const int r = wf_survivor_slot<BOUND>(P, alive, ps, bound.x, walk_free, n_walk, total, s_cnt, s_cnt_free);
     if (alive) {
         const size_t j = (size_t)region * PT_REGION + (size_t)r;
         pt_sst4(P.wf.ray0_out + j, make_float4(ps.o.x, ps.o.y, ps.o.z, ps.d.x));
@@ -404,9 +454,10 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
         pt_sst1(P.wf.mask_out + (size_t)P.wf.cap + j, ps.mask.y);
         pt_sst1(P.wf.mask_out + 2 * (size_t)P.wf.cap + j, ps.mask.z);
         // (slot j held another lane's hit of THIS bounce: every lane of the region has read its own before the rank's barrier)
-        if (BOUND) pt_sst2(P.wf.hit + j, bound);
+        if (BOUND) pt_sst2(P.wf.hit + j, bound);   // (walk-free: the bound stands, "no triangle at or before the sphere")
+        else if (walk_free) pt_sst2(P.wf.hit + j, make_float2(pt_no_hit().t, __int_as_float(pt_no_hit().rec)));   // what its walk would have written
     }
-    if (threadIdx.x == 0) P.wf.cnt_out[region] = total;
+    wf_region_counts<COUNT>(P, region, n_walk, total);
 }
 
 // PT_OPT_LAST_ANYHIT: the last shade launch behind k_wf_extend<.., ANY>.  The hit slot holds (ts, sphere) of the segment's nearest
@@ -460,6 +511,7 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade_last_any(const KParams P)
 template <bool BOUND>
 __global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet_shade(const KParams P) {
     __shared__ int s_cnt[PT_BLOCK / 64];
+    __shared__ int s_cnt_free[PT_BLOCK / 64];
     wf_sphere_table();
     const uint32_t region = blockIdx.x;
     const size_t i = (size_t)region * PT_REGION + threadIdx.x;
@@ -481,8 +533,9 @@ __global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet_shade(const KP
     if (P.wf.bounce + 1 >= P.depth) return;   // depth 1
     float2 bound = make_float2(PT_F32_MAX, __int_as_float(-1));
     if (BOUND && alive) bound = wf_sphere_bound(P, ps);
-    int total;
-    const int r = PT_SURVIVOR_RANK(P, alive, ps, total, s_cnt);
+    int n_walk, total;
+    bool walk_free;
+    const int r = wf_survivor_slot<BOUND>(P, alive, ps, bound.x, walk_free, n_walk, total, s_cnt, s_cnt_free);
     if (alive) {
         const size_t j = (size_t)region * PT_REGION + (size_t)r;
         pt_sst4(P.wf.ray0_out + j, make_float4(ps.o.x, ps.o.y, ps.o.z, ps.d.x));
@@ -491,8 +544,9 @@ __global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet_shade(const KP
         pt_sst1(P.wf.mask_out + (size_t)P.wf.cap + j, ps.mask.y);
         pt_sst1(P.wf.mask_out + 2 * (size_t)P.wf.cap + j, ps.mask.z);
         if (BOUND) pt_sst2(P.wf.hit + j, bound);
+        else if (walk_free) pt_sst2(P.wf.hit + j, make_float2(pt_no_hit().t, __int_as_float(pt_no_hit().rec)));   // (as k_wf_shade)
     }
-    if (threadIdx.x == 0) P.wf.cnt_out[region] = total;
+    wf_region_counts<false>(P, region, n_walk, total);
 }
 
 // PT_FLAG_NEE: adds the contribution of every shadow ray that reached its light (nothing closer than t_max) to its path's
@@ -512,7 +566,7 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_resolve(const KParams P) {
 
 namespace ptmi {
 
-// sizes of one call's path records: [ray0 x2][ray1 x2][mask x2 (3 planes)][hit][cnt x2][hashes][queues][shadow records]
+// sizes of one call's path records: [ray0 x2][ray1 x2][mask x2 (3 planes)][hit][cnt x2][walk x2][hashes][queues][shadow records]
 struct WaveLayout {
     size_t n_regions, cap, b_ray, b_mask, b_hit, b_cnt, b_hash, q_words, b_q, b_nee, need;
     bool nee;
@@ -543,7 +597,7 @@ static int wave_layout(pt_ctx* c, const KParams& P, int work_tiles, WaveLayout& 
     w.q_words = (size_t)P.depth * (w.nee ? 2 : 1) * PT_SHARDS * PT_SHARD_STRIDE;   // one set of queue counters per extend launch
     w.b_q = w.q_words * 4;
     w.b_nee = w.nee ? 3 * w.b_ray + w.b_hit + w.b_cnt : 0;   // shadow records: s_ray0, s_ray1, s_con, s_hit, s_cnt
-    w.need = 4 * w.b_ray + 2 * w.b_mask + w.b_hit + 2 * w.b_cnt + w.b_hash + w.b_q + w.b_nee;
+    w.need = 4 * w.b_ray + 2 * w.b_mask + w.b_hit + 4 * w.b_cnt + w.b_hash + w.b_q + w.b_nee;
     return PT_OK;
 }
 
@@ -573,6 +627,7 @@ struct WaveBuffers {
     float* mask[2];
     float2* hit;
     int* cnt[2];
+    int* walk[2];   // the records at the front of every region that the extend launch walks (PT_OPT_ROOT_CULL; = cnt without it)
     unsigned long long* hashes;   // then the queue counters of every extend launch
     unsigned int* queues;
     char* nee;   // the shadow records (PT_FLAG_NEE): s_ray0, s_ray1, s_con, s_hit, s_cnt
@@ -589,7 +644,9 @@ static WaveBuffers wave_carve(char* base, const WaveLayout& w) {
     base += w.b_hit;
     b.cnt[0] = (int*)base;
     b.cnt[1] = (int*)(base + w.b_cnt);
-    base += 2 * w.b_cnt;
+    b.walk[0] = (int*)(base + 2 * w.b_cnt);
+    b.walk[1] = (int*)(base + 3 * w.b_cnt);
+    base += 4 * w.b_cnt;
     b.hashes = (unsigned long long*)base;
     base += w.b_hash;
     b.queues = (unsigned int*)base;
@@ -611,6 +668,9 @@ struct WavePlan {
     // ends on.  The shade launch of bounce depth - 2 leaves the nearest sphere of every survivor's new ray in its hit slot, the walk of bounce
     // depth - 1 is an any-hit query bounded by it, the last shade launch reads the verdict.  Instrumented launches: with the value 2 only.
     bool anyhit;
+    // PT_OPT_ROOT_CULL: the shade launches keep the survivors whose new ray the tree's root turns away out of the next extend launch's
+    // queue (wf_survivor_slot).  Instrumented launches: with the value 2 only.
+    bool root_cull;
     WaveExtend extend(uint32_t b, uint32_t depth) const {
         if (b == 0) return fuse_first ? EXT_FUSED : packet ? EXT_PACKET : EXT_FIRST;
         return anyhit && b + 1 == depth ? EXT_ANY : EXT_CLOSEST;
@@ -633,6 +693,7 @@ static WavePlan wave_plan(const pt_ctx* c, const KParams& P, const LaunchCfg& L,
     p.fold_lp = fuse && !L.moments && P.depth >= 2 && P.sgroup_log2 >= 2 && P.sgroup_log2 <= 4 && P.spp == (1u << P.sgroup_log2) ? (int)P.spp / 4 : 0;
     p.anyhit = (L.count ? c->opt_last_anyhit == 2 : c->opt_last_anyhit >= 1) && P.depth >= 2 && !nee && !P.tri_matid && tri_dark &&
                P.sc.n_spheres <= PT_KSPHERES && !c->records_woop;
+    p.root_cull = L.count ? c->opt_root_cull == 2 : c->opt_root_cull >= 1;
     return p;
 }
 
@@ -700,6 +761,7 @@ int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles, 
     const WavePlan plan = wave_plan(c, P, L, w.nee);
     folded = plan.fold_lp != 0;
     P.wf.nee = w.nee ? 1 : 0;
+    P.wf.root_cull = plan.root_cull ? 1 : 0;
     if (w.nee) {
         P.wf.s_ray0 = (float4*)buf.nee;
         P.wf.s_ray1 = (float4*)(buf.nee + w.b_ray);
@@ -727,8 +789,8 @@ int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles, 
     for (uint32_t b = 0; b < P.depth; b++) {
         const int g = (int)(b & 1u);
         P.wf.bounce = b;
-        P.wf.ray0_in = buf.ray0[g]; P.wf.ray1_in = buf.ray1[g]; P.wf.mask_in = buf.mask[g]; P.wf.cnt_in = buf.cnt[g];
-        P.wf.ray0_out = buf.ray0[g ^ 1]; P.wf.ray1_out = buf.ray1[g ^ 1]; P.wf.mask_out = buf.mask[g ^ 1]; P.wf.cnt_out = buf.cnt[g ^ 1];
+        P.wf.ray0_in = buf.ray0[g]; P.wf.ray1_in = buf.ray1[g]; P.wf.mask_in = buf.mask[g]; P.wf.cnt_in = buf.cnt[g]; P.wf.walk_in = buf.walk[g];
+        P.wf.ray0_out = buf.ray0[g ^ 1]; P.wf.ray1_out = buf.ray1[g ^ 1]; P.wf.mask_out = buf.mask[g ^ 1]; P.wf.cnt_out = buf.cnt[g ^ 1]; P.wf.walk_out = buf.walk[g ^ 1];
         P.wf.queue = buf.queues + (size_t)b * PT_SHARDS * PT_SHARD_STRIDE;
         HIP_TRY(c, launch_extend(plan, plan.extend(b, P.depth), P, L, c->opt_wave_blocks, st));   // (EXT_FUSED: walk + shade, booked as extend)
         if (stage_mark(c, PT_STAGE_EXTEND) != PT_OK) return PT_ERR_DEVICE;
@@ -738,7 +800,7 @@ int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles, 
         if (stage_mark(c, PT_STAGE_SHADE) != PT_OK) return PT_ERR_DEVICE;
         if (w.nee) {   // this bounce's shadow rays: the closest-hit extend kernel over the shadow records, then the resolve
             KParams S = P;
-            S.wf.ray0_in = P.wf.s_ray0; S.wf.ray1_in = P.wf.s_ray1; S.wf.cnt_in = P.wf.s_cnt; S.wf.hit = P.wf.s_hit;
+            S.wf.ray0_in = P.wf.s_ray0; S.wf.ray1_in = P.wf.s_ray1; S.wf.cnt_in = S.wf.walk_in = P.wf.s_cnt; S.wf.hit = P.wf.s_hit;   // (every shadow ray is walked)
             S.wf.queue = buf.queues + ((size_t)P.depth + b) * PT_SHARDS * PT_SHARD_STRIDE;
             HIP_TRY(c, launch_extend(plan, EXT_CLOSEST, S, L, c->opt_wave_blocks, st));
             if (stage_mark(c, PT_STAGE_EXTEND) != PT_OK) return PT_ERR_DEVICE;

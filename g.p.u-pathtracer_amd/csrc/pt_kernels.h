@@ -39,7 +39,8 @@ struct KScene {
 // Stage-split (wavefront) pipeline, pt_k_wave.hip: one generation of path records in HBM.  A record lives
 // in slot i of its REGION (256 consecutive slots = one block of the generate / shade stages); a region's live
 // records are packed at its front and counted in cnt[region], so compaction never leaves the block
-// (ballot + prefix count, no global atomics) and the order of the records is deterministic.
+// (ballot + prefix count, no global atomics) and the order of the records is deterministic.  PT_OPT_ROOT_CULL: the records whose
+// ray the tree's root turns away come last, walk[region] counts the ones before them, and only those are walked.
 //   ray0[i] = (o.x, o.y, o.z, d.x)   ray1[i] = (d.y, d.z, bits(pixel), bits(sample << PT_REC_DRAW_BITS | rng draws))
 //   mask    = three planes [cap] (x, y, z), not stored for the first bounce (1, 1, 1)
 //   hit[i]  = (t, bits(float4 index of the winning record)); t = F32_MAX: no triangle
@@ -59,8 +60,10 @@ struct KWave {
     float4* __restrict__ ray1_out;
     float* __restrict__ mask_out;
     float2* __restrict__ hit;
+    const int* __restrict__ walk_in;   // records at the front of a region that the extend launch walks (<= cnt_in); next to `hit`, its other word
     const int* __restrict__ cnt_in;
     int* __restrict__ cnt_out;
+    int* __restrict__ walk_out;
     unsigned long long* hashes;   // uf::hash(frame + s), s < spp (written by k_wf_prepare)
     unsigned int* queue;          // region queue of THIS bounce's extend launch (PT_SHARDS counters)
     unsigned int* queues_all;     // k_wf_prepare: every bounce's counters, zeroed
@@ -76,6 +79,7 @@ struct KWave {
     float2* __restrict__ s_hit;
     int* __restrict__ s_cnt;
     int nee;                      // 1: ray1.z carries pixel | nee_mask << 24
+    int root_cull;                // 1: this call's shade launches classify their survivors (PT_OPT_ROOT_CULL)
     uint32_t bounce;
 };
 
@@ -171,6 +175,7 @@ enum {
     PT_CNT_IT_SHADE, PT_CNT_ACT_SHADE,   // persistent kernel: shading passes, lanes
     PT_CNT_IT_BEGIN, PT_CNT_ACT_BEGIN,   // path-start (pipeline: refill) passes, lanes
     PT_CNT_IT_LOOP, PT_CNT_STACK_OVF,    // outer-loop iterations, pushes past the LDS window
+    PT_CNT_WALK_FREE,                    // pipeline: rays kept out of the extend queue (PT_OPT_ROOT_CULL 2)
     PT_CNT_N,
     PT_CNT_PACKET_GROUPS = PT_CNT_IT_SHADE,   // pipeline: 64-ray groups the bounce-0 packet walk walked
     PT_CNT_ANY_RAYS = PT_CNT_ACT_SHADE        // pipeline: rays of the any-hit launch (PT_OPT_LAST_ANYHIT 2)

@@ -328,6 +328,10 @@ int pt_set_option(pt_ctx* c, int option, int value) {
             if (value < 0 || value > 2) return fail(c, PT_ERR_INVALID, "pt_set_option: last any-hit must be 0 (off), 1 (product launches) or 2 (instrumented launches too)");
             c->opt_last_anyhit = value;
             return PT_OK;
+        case PT_OPT_ROOT_CULL:
+            if (value < 0 || value > 2) return fail(c, PT_ERR_INVALID, "pt_set_option: root cull must be 0 (off), 1 (product launches) or 2 (instrumented launches too)");
+            c->opt_root_cull = value;
+            return PT_OK;
         default: return fail(c, PT_ERR_INVALID, "pt_set_option: unknown option");
     }
 }

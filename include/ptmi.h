@@ -215,7 +215,7 @@ enum {
                                  all samples of its pixels (PT_OPT_WAVE_SAMPLES groups of spp = 16, 8 or 4, depth >= 2) the last
                                  shade launch folds them into the accumulator (no separate fold launch); 0 = one launch per
                                  stage.  Same images, same counters                                                     */
-    PT_OPT_LAST_ANYHIT = 29   /* PT_KERNEL_WAVEFRONT: after `depth` segments only the gathered light is returned, so a path's last
+    PT_OPT_LAST_ANYHIT = 29,  /* PT_KERNEL_WAVEFRONT: after `depth` segments only the gathered light is returned, so a path's last
                                  segment matters only through the emission of what it ends on.  When no triangle can emit (tri_emi
                                  all zero, no pt_upload_tri_materials table; also depth >= 2, no PT_FLAG_NEE, at most 8 spheres,
                                  PT_OPT_TRI_TEST 0) the shade launch before it records the nearest sphere hit ts of the new ray, and
@@ -224,6 +224,14 @@ enum {
                                  (PT_OPT_COUNTERS) launches too: pt_get_counters then counts the shorter walk and
                                  pt_get_wave_stats [5] the rays of that launch (0 = it did not run); 0 = closest hit on every
                                  segment.  With 0 or 1 the counters are those of the closest-hit walk.  Same images            */
+    PT_OPT_ROOT_CULL = 30     /* PT_KERNEL_WAVEFRONT: a surviving path's new ray that the walk's own first node step would turn away
+                                 at the tree's root (no child box of the 4-wide root entered before t_max: the ray misses the mesh, or
+                                 enters it beyond the sphere bound of PT_OPT_LAST_ANYHIT) is not queued for the next extend launch.
+                                 The shade lane that made the ray runs that node step itself, packs such records behind the region's
+                                 walkers and writes the hit record of a miss for them.  1 (default) = product launches do so; 2 =
+                                 instrumented (PT_OPT_COUNTERS) launches too: pt_get_counters then lacks one node visit per such ray
+                                 (`rays` still counts them) and pt_get_wave_stats [10] is their number; 0 = every survivor is
+                                 queued.  With 0 or 1 the counters are those of the full queue.  Same images                     */
 };
 
 /* CamInfo, GpuPathTracer/CpuStructs.hpp:19-28 (pitch/yaw/dirty/bias/enabled are host-only
@@ -468,8 +476,10 @@ int pt_get_counters(pt_ctx* ctx, pt_counters* out);
  * PT_KERNEL_WAVEFRONT: [0]-[3] and [6]-[9] are the extend stage's ([6]/[7] = refill passes), its
  * shade stage runs one lane per live path ([5] = the rays of the any-hit launch, PT_OPT_LAST_ANYHIT 2, else 0); [4] counts the 64-ray groups the bounce-0
  * packet walk (PT_OPT_FIRST_WALK 1) walked — 0 when bounce 0 ran the per-lane walk — and that
- * launch books its wave node / record steps and the lanes of their masks in [0]-[3]. */
-#define PT_WAVE_STATS 10
+ * launch books its wave node / record steps and the lanes of their masks in [0]-[3].
+ * [10] PT_KERNEL_WAVEFRONT with PT_OPT_ROOT_CULL 2: the rays the shade stage kept out of the extend queue (they
+ * are part of pt_counters.rays, not of [5]); 0 everywhere else. */
+#define PT_WAVE_STATS 11
 int pt_get_wave_stats(pt_ctx* ctx, uint64_t* out, int n);
 int pt_last_kernel_ms(pt_ctx* ctx, float* ms_out);   /* needs PT_OPT_TIMING=1 */
 /* Device time of the last timed pt_render (PT_OPT_TIMING=1) by stage, from HIP events recorded on the
