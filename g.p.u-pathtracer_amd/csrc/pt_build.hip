@@ -223,28 +223,28 @@ int build_bvh_impl(pt_ctx* c, const float* verts, size_t n_verts, const int32_t*
     uint32_t levels = 0;
     while (levels < 66 && level_cnt[levels] > 0) levels++;
     if (level_cnt[std::min<unsigned int>(n_levels_max + 1, 67)] != 0) return fail(c, PT_ERR_DEVICE, "pt_build_bvh: wide collapse did not finish");
-    HIP_TRY(c, hipEventElapsedTime(&c->build_ms, e0, e1));
+    HIP_TRY(c, hipEventElapsedTime(&c->tree.build_ms, e0, e1));
     if (stats[3] > 64) return fail(c, PT_ERR_UNSUPPORTED, "pt_build_bvh: tree deeper than 64 levels (degenerate input); use the host builder");
 
     refit_release(c);
-    (void)hipFree(c->d_nodes);
-    c->d_nodes = items;
+    (void)hipFree(c->tree.d_nodes);
+    c->tree.d_nodes = items;
     guard.p = nullptr;
-    c->d_tris = c->d_nodes;
-    c->records_woop = false;
-    c->wide_root = 4 * ((uint64_t)(n - 1) + (uint64_t)n);
-    c->wide_top_layout = 1;      // level order below the root, not a breadth-first prefix of fixed size
-    c->n_top_layout = 1;
-    c->wide_depth = levels;
-    c->n_wide = stats[0];
-    c->n_inner = (uint64_t)(n - 1);
-    c->n_refs = (uint64_t)n;
-    c->n_leaves = stats[2];
-    c->max_depth = stats[3];
-    c->scene_bytes = n_items * 64;
-    c->max_tri_id = (int32_t)n_tris - 1;
-    if (id_map) for (size_t i = 0; i < n_tris; i++) c->max_tri_id = std::max(c->max_tri_id, id_map[i]);
-    c->has_bvh = true;
+    c->tree.d_tris = c->tree.d_nodes;
+    c->tree.records_woop = false;
+    c->tree.wide_root = 4 * ((uint64_t)(n - 1) + (uint64_t)n);
+    c->tree.wide_top_layout = 1;      // level order below the root, not a breadth-first prefix of fixed size
+    c->tree.n_top_layout = 1;
+    c->tree.wide_depth = levels;
+    c->tree.n_wide = stats[0];
+    c->tree.n_inner = (uint64_t)(n - 1);
+    c->tree.n_refs = (uint64_t)n;
+    c->tree.n_leaves = stats[2];
+    c->tree.max_depth = stats[3];
+    c->tree.scene_bytes = n_items * 64;
+    c->tree.max_tri_id = (int32_t)n_tris - 1;
+    if (id_map) for (size_t i = 0; i < n_tris; i++) c->tree.max_tri_id = std::max(c->tree.max_tri_id, id_map[i]);
+    c->tree.has_bvh = true;
     c->scene_gen++;
     return PT_OK;
 }

@@ -19,14 +19,30 @@
 #define PT_FIRST_WALK_DEFAULT 1
 #endif
 
+// Everything on the context that describes the acceleration structure, written once: a tree is parked and put back by plain
+// assignment (PT_OPT_REBUILD 2 holds two for a moment), so a field added here cannot be forgotten on the way.
+struct TreeState {
+    float4* d_nodes = nullptr;   // one item buffer, [binary nodes][records][wide nodes]: links index it directly
+    float4* d_tris = nullptr;    // (aliases d_nodes)
+    bool records_woop = false;   // what the uploaded records are
+    bool has_bvh = false;
+    uint64_t wide_root = 0;      // float4 index of the 4-wide tree's root, 0 = not built
+    uint64_t n_wide = 0, n_inner = 0, n_refs = 0, n_leaves = 0, scene_bytes = 0;
+    uint32_t wide_top_layout = 0, wide_depth = 0;
+    uint32_t n_top_layout = 0;   // nodes [0, n_top_layout) are in breadth-first order
+    uint32_t max_depth = 0;
+    int32_t max_tri_id = -1;     // largest original triangle id of the uploaded BVH
+    float build_ms = -1.f;       // device time of the last pt_build_bvh
+    double opt_cost[2] = {0.0, 0.0};   // PT_OPT_OPTIMIZE: area cost (inner-node areas / root area) before / after, 0 when it did not run
+};
+
 struct pt_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     std::string err;
     // scene
-    float4* d_nodes = nullptr;
-    float4* d_tris = nullptr;
+    TreeState tree;
     pt_sphere_d* d_spheres = nullptr;
     int* d_tri_matid = nullptr;        // pt_upload_tri_materials
     float4* d_mat_table = nullptr;
@@ -42,17 +58,8 @@ struct pt_ctx {
     // first kernel that may read that generation of the list
     hipEvent_t lights_ev = nullptr;
     uint64_t lights_gen = 0;
-    int32_t max_tri_id = -1;           // largest original triangle id of the uploaded BVH
     int n_spheres = 0;
     pt_sphere_d h_spheres[PT_KSPHERES];   // host copy of the first spheres for the kernel-argument block
-    uint64_t n_inner = 0, n_refs = 0, n_leaves = 0, scene_bytes = 0;
-    uint32_t max_depth = 0;
-    uint32_t n_top_layout = 0;   // nodes [0, n_top_layout) are in breadth-first order
-    uint64_t wide_root = 0;      // float4 index of the 4-wide tree's root, 0 = not built
-    uint32_t wide_top_layout = 0, wide_depth = 0;
-    uint64_t n_wide = 0;
-    bool has_bvh = false;
-    float build_ms = -1.f;       // device time of the last pt_build_bvh
     // options
     int opt_kernel = PT_KERNEL_AUTO;
     int opt_counters = 0;
@@ -66,7 +73,6 @@ struct pt_ctx {
     int opt_batch = 36;
     int opt_presplit = 0;        // pt_build_bvh: 0 off, else the target length in per cent of diag/sqrt(n) (PT_OPT_PRESPLIT)
     int opt_optimize = 0;        // pt_upload_bvh: passes of insertion-based optimisation over the uploaded hierarchy (PT_OPT_OPTIMIZE)
-    double opt_cost[2] = {0.0, 0.0};   // its area cost (inner-node areas / root area) before / after, 0 when it did not run
     int opt_rebuild = 0;         // pt_upload_bvh: 1 = re-cluster the uploaded triangles on the device (PT_OPT_REBUILD)
     int opt_build_algo = 1;      // pt_build_bvh: 0 LBVH (Karras), 1 PLOC (PT_OPT_BUILD_ALGO)
     int opt_sph_lds = 1;         // persistent kernel: sphere attributes from an LDS copy (PT_OPT_SPHERE_LDS)
@@ -78,7 +84,6 @@ struct pt_ctx {
     int opt_walk = 2;            // 0 while-while, 1 unified-step, 2 wide, 4 wide + postponed leaf (PT_OPT_WALK)
     int opt_leaf_max = 2;        // leaves with more references are split at upload (PT_OPT_LEAF_MAX)
     int opt_tri_test = 0;        // 0 Moller-Trumbore records, 1 Woop records (next upload; PT_OPT_TRI_TEST)
-    bool records_woop = false;   // what the uploaded records are
     // stage-split (wavefront) pipeline: path records of one call, two generations (pt_k_wave.hip)
     void* d_wave = nullptr;
     size_t wave_bytes = 0;
@@ -182,8 +187,13 @@ struct DevTemp {  // temporaries of one build, released together
     }
 };
 
-// LDS bytes of a frame-kernel block: top-of-tree planes + stack
-inline size_t lds_bytes(int n_top, int stack_n, int block) { return (size_t)n_top * 64 + (size_t)stack_n * block * 4; }
+// LDS bytes of a frame-kernel block, top-of-tree planes + stack, with the largest n_top (halved from the one asked for) that fits
+// 160 KiB: a deep tree gives the LDS to the stack first
+inline size_t lds_fit(int& n_top, int stack_n, int block) {
+    const size_t stack = (size_t)stack_n * block * 4;
+    while (n_top > 0 && (size_t)n_top * 64 + stack > 160 * 1024) n_top /= 2;
+    return (size_t)n_top * 64 + stack;
+}
 
 template <typename K>
 hipError_t allow_lds(K kernel, size_t bytes) {

@@ -223,23 +223,22 @@ extern "C" int pt_render_aux(pt_ctx* c, const pt_camera* cam, const pt_params* p
     if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
     if (!cam || !p || !albedo_dev || !normal_dev || !position_dev) return fail(c, PT_ERR_INVALID, "pt_render_aux: null argument");
     if (p->width < 1 || p->height < 1) return fail(c, PT_ERR_INVALID, "pt_render_aux: width and height must be >= 1");
-    if (!c->has_bvh) return fail(c, PT_ERR_NO_SCENE, "pt_render_aux: no BVH uploaded");
-    if (c->records_woop) return fail(c, PT_ERR_UNSUPPORTED, "pt_render_aux: the binary walk reads Moller-Trumbore records (upload with PT_OPT_TRI_TEST 0)");
+    if (!c->tree.has_bvh) return fail(c, PT_ERR_NO_SCENE, "pt_render_aux: no BVH uploaded");
+    if (c->tree.records_woop) return fail(c, PT_ERR_UNSUPPORTED, "pt_render_aux: the binary walk reads Moller-Trumbore records (upload with PT_OPT_TRI_TEST 0)");
     HIP_TRY(c, hipSetDevice(c->device));
     KParams P;
     std::memset(&P, 0, sizeof P);
-    P.sc.nodes = c->d_nodes;
-    P.sc.tris = c->d_tris;
+    P.sc.nodes = c->tree.d_nodes;
+    P.sc.tris = c->tree.d_tris;
     P.sc.spheres = c->d_spheres;
     P.sc.n_spheres = c->n_spheres;
     std::memcpy(P.ksph, c->h_spheres, sizeof P.ksph);
     P.sc.has_bvh = 1;
     P.sc.stack_n = PT_STACK_CAP;
     P.sc.top_base = 0;
-    P.sc.wide_root = (int)c->wide_root;
-    P.sc.n_top = (int)std::min<uint32_t>((uint32_t)c->opt_top, c->n_top_layout);
-    size_t lds = lds_bytes(P.sc.n_top, P.sc.stack_n, PT_BLOCK_RAYS);
-    while (lds > 160 * 1024 && P.sc.n_top > 0) { P.sc.n_top /= 2; lds = lds_bytes(P.sc.n_top, P.sc.stack_n, PT_BLOCK_RAYS); }
+    P.sc.wide_root = (int)c->tree.wide_root;
+    P.sc.n_top = (int)std::min<uint32_t>((uint32_t)c->opt_top, c->tree.n_top_layout);
+    const size_t lds = lds_fit(P.sc.n_top, P.sc.stack_n, PT_BLOCK_RAYS);
     P.cam = *cam;
     P.W = p->width; P.H = p->height;
     P.cull = p->cull_backfaces;

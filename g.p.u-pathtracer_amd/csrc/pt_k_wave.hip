@@ -686,13 +686,13 @@ struct WavePlan {
 static WavePlan wave_plan(const pt_ctx* c, const KParams& P, const LaunchCfg& L, bool nee) {
     WavePlan p;
     p.count = L.count; p.nee = nee; p.deep_stack = L.lstk == 24;
-    p.packet = c->opt_first_walk == 1 && 3 * c->wide_depth + 2 <= (uint32_t)c->opt_packet_stack;
+    p.packet = c->opt_first_walk == 1 && 3 * c->tree.wide_depth + 2 <= (uint32_t)c->opt_packet_stack;
     const bool fuse = c->opt_fuse_stages != 0 && !nee && !L.count, tri_dark = P.tri_emi[0] == 0.f && P.tri_emi[1] == 0.f && P.tri_emi[2] == 0.f;
     p.fuse_first = fuse && p.packet;
     // ... and the call keeps no luminance moments (pt_render_moments): those are the separate fold launch's job
     p.fold_lp = fuse && !L.moments && P.depth >= 2 && P.sgroup_log2 >= 2 && P.sgroup_log2 <= 4 && P.spp == (1u << P.sgroup_log2) ? (int)P.spp / 4 : 0;
     p.anyhit = (L.count ? c->opt_last_anyhit == 2 : c->opt_last_anyhit >= 1) && P.depth >= 2 && !nee && !P.tri_matid && tri_dark &&
-               P.sc.n_spheres <= PT_KSPHERES && !c->records_woop;
+               P.sc.n_spheres <= PT_KSPHERES && !c->tree.records_woop;
     p.root_cull = L.count ? c->opt_root_cull == 2 : c->opt_root_cull >= 1;
     return p;
 }

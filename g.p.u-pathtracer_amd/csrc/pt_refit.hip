@@ -203,8 +203,8 @@ void refit_release(pt_ctx* c) {
 // (0: only leaf children), a child count (wide) and the record count of every leaf child, sorted by height.
 static int refit_prepare(pt_ctx* c) {
     refit_release(c);
-    const uint64_t n_bin = c->n_inner, n_rec = c->n_refs, n_wide = c->n_wide;
-    const uint64_t rec_base = 4 * n_bin, wide_root = c->wide_root;
+    const uint64_t n_bin = c->tree.n_inner, n_rec = c->tree.n_refs, n_wide = c->tree.n_wide;
+    const uint64_t rec_base = 4 * n_bin, wide_root = c->tree.wide_root;
     if (n_bin == 0 || n_rec == 0 || n_wide == 0 || wide_root != rec_base + 4 * n_rec || n_rec >= (1ull << 31))
         // (every tree pt_upload_bvh and pt_build_bvh install has an inner root, a lone triangle is doubled: not met in practice)
         return fail(c, PT_ERR_UNSUPPORTED, "pt_refit_bvh: the tree on this context lacks the [binary nodes][records][wide nodes] layout");
@@ -214,7 +214,7 @@ static int refit_prepare(pt_ctx* c) {
         int32_t* d_shape = nullptr;
         HIP_TRY(c, hipMalloc((void**)&d_shape, h.size() * sizeof(int32_t)));
         const uint64_t n_all = n_bin + n_rec + n_wide;
-        hipLaunchKernelGGL(k_refit_shape, dim3((unsigned)((n_all + PTR_BLOCK - 1) / PTR_BLOCK)), dim3(PTR_BLOCK), 0, c->stream, c->d_nodes, n_bin,
+        hipLaunchKernelGGL(k_refit_shape, dim3((unsigned)((n_all + PTR_BLOCK - 1) / PTR_BLOCK)), dim3(PTR_BLOCK), 0, c->stream, c->tree.d_nodes, n_bin,
                            n_rec, n_wide, d_shape);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_shape, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
@@ -311,10 +311,10 @@ static int refit_prepare(pt_ctx* c) {
     // first record of every triangle id: a dropped triangle is counted once however many references it has
     std::vector<uint32_t> first((n_rec + 31) / 32, 0u);
     {
-        std::vector<uint8_t> id_seen((size_t)std::max<int32_t>(c->max_tri_id, 0) + 1, 0);
+        std::vector<uint8_t> id_seen((size_t)std::max<int32_t>(c->tree.max_tri_id, 0) + 1, 0);
         for (uint64_t j = 0; j < n_rec; j++) {
             const int32_t id = rec_w[2 * j];
-            if (id < 0 || id > c->max_tri_id || id_seen[(size_t)id]) continue;
+            if (id < 0 || id > c->tree.max_tri_id || id_seen[(size_t)id]) continue;
             id_seen[(size_t)id] = 1;
             first[j >> 5] |= 1u << (j & 31);
         }
@@ -336,7 +336,7 @@ static int refit_prepare(pt_ctx* c) {
     HIP_TRY(c, hipMemcpy(R.wide_list, wl.data(), wl.size() * sizeof(int4), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(R.first_use, first.data(), first.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     R.scene_gen = c->scene_gen;
-    R.items = c->d_nodes;
+    R.items = c->tree.d_nodes;
     return PT_OK;
 }
 
@@ -347,22 +347,22 @@ using namespace ptmi;
 extern "C" int pt_refit_bvh(pt_ctx* c, const float* tri_verts_dev, size_t n_tris, uint32_t* n_dropped_dev) {
     if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
     if (!tri_verts_dev) return fail(c, PT_ERR_INVALID, "pt_refit_bvh: null vertex array");
-    if (!c->has_bvh) return fail(c, PT_ERR_NO_SCENE, "pt_refit_bvh: no BVH on this context");
-    if (c->records_woop) return fail(c, PT_ERR_UNSUPPORTED, "pt_refit_bvh: Woop records are made on the host only (PT_OPT_TRI_TEST 0)");
-    if (c->max_tri_id < 0 || n_tris <= (size_t)c->max_tri_id)
+    if (!c->tree.has_bvh) return fail(c, PT_ERR_NO_SCENE, "pt_refit_bvh: no BVH on this context");
+    if (c->tree.records_woop) return fail(c, PT_ERR_UNSUPPORTED, "pt_refit_bvh: Woop records are made on the host only (PT_OPT_TRI_TEST 0)");
+    if (c->tree.max_tri_id < 0 || n_tris <= (size_t)c->tree.max_tri_id)
         return fail(c, PT_ERR_INVALID, "pt_refit_bvh: n_tris does not cover the triangle ids of the tree");
     HIP_TRY(c, hipSetDevice(c->device));
     pt_ctx::Refit& R = c->refit;
-    if (!R.d_mem || R.scene_gen != c->scene_gen || R.items != c->d_nodes) {
+    if (!R.d_mem || R.scene_gen != c->scene_gen || R.items != c->tree.d_nodes) {
         const int rc = refit_prepare(c);
         if (rc != PT_OK) { refit_release(c); return rc; }
     }
     RefitArgs A;
-    A.items = c->d_nodes;
+    A.items = c->tree.d_nodes;
     A.verts = tri_verts_dev;
-    A.n_rec = (uint32_t)c->n_refs;
-    A.rec_base = 4 * c->n_inner;
-    A.wide_root = c->wide_root;
+    A.n_rec = (uint32_t)c->tree.n_refs;
+    A.rec_base = 4 * c->tree.n_inner;
+    A.wide_root = c->tree.wide_root;
     A.rec_box = R.rec_box;
     A.bin_box = R.bin_box;
     A.wide_box = R.wide_box;

@@ -27,28 +27,6 @@ using namespace ptmi;
 namespace ptmi {
 static int tree_cost_impl(pt_ctx* c, double* node_visits, double* tri_tests);
 
-// everything on the context that describes the acceleration structure (PT_OPT_REBUILD 2 holds two for a moment)
-struct TreeState {
-    float4 *d_nodes, *d_tris;
-    bool records_woop, has_bvh;
-    uint64_t wide_root, n_wide, n_inner, n_refs, n_leaves, scene_bytes;
-    uint32_t wide_top_layout, wide_depth, n_top_layout, max_depth;
-    int32_t max_tri_id;
-    float build_ms;
-    static TreeState of(const pt_ctx* c) {
-        return {c->d_nodes, c->d_tris, c->records_woop, c->has_bvh, c->wide_root, c->n_wide, c->n_inner, c->n_refs, c->n_leaves, c->scene_bytes,
-                c->wide_top_layout, c->wide_depth, c->n_top_layout, c->max_depth, c->max_tri_id, c->build_ms};
-    }
-    void restore(pt_ctx* c) const {
-        c->d_nodes = d_nodes; c->d_tris = d_tris; c->records_woop = records_woop; c->has_bvh = has_bvh;
-        c->wide_root = wide_root; c->n_wide = n_wide; c->n_inner = n_inner; c->n_refs = n_refs; c->n_leaves = n_leaves; c->scene_bytes = scene_bytes;
-        c->wide_top_layout = wide_top_layout; c->wide_depth = wide_depth; c->n_top_layout = n_top_layout; c->max_depth = max_depth;
-        c->max_tri_id = max_tri_id; c->build_ms = build_ms;
-    }
-};
-}  // namespace ptmi
-
-namespace ptmi {
 // PT_KERNEL_AUTO: reads the trials' events once they have all completed (wait = false: only if that needs no waiting) and decides
 static bool auto_decide(pt_ctx* c, pt_ctx::AutoPick& a, bool wait) {
     using AP = pt_ctx::AutoPick;
@@ -91,17 +69,15 @@ int stage_mark(pt_ctx* c, int kind) {
     c->stage_used++;
     return PT_OK;
 }
-}  // namespace ptmi
 
-
-namespace ptmi {
 // refine (leaves of at most PT_OPT_LEAF_MAX references), optimise (PT_OPT_OPTIMIZE), emit, upload: the tree `X` becomes the context's
 static int install_tree(pt_ctx* c, ptscene::Tree& X, int32_t max_id) {
+    TreeState& t = c->tree;
     ptscene::refine(X, (uint32_t)c->opt_leaf_max);
-    c->opt_cost[0] = c->opt_cost[1] = 0.0;
+    t.opt_cost[0] = t.opt_cost[1] = 0.0;
     if (c->opt_optimize > 0 && c->opt_tri_test == 0) {   // every node re-inserted where the area cost grows least (pt_tree_opt.h)
         double before = 0.0, after = 0.0;
-        if (ptscene::optimize(X, c->opt_optimize, 64, before, after)) { c->opt_cost[0] = before; c->opt_cost[1] = after; }
+        if (ptscene::optimize(X, c->opt_optimize, 64, before, after)) { t.opt_cost[0] = before; t.opt_cost[1] = after; }
     }
     ptscene::Output O;
     ptscene::emit(X, PT_MAX_TOP, O, c->opt_tri_test == 1);
@@ -110,28 +86,28 @@ static int install_tree(pt_ctx* c, ptscene::Tree& X, int32_t max_id) {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     refit_release(c);
-    (void)hipFree(c->d_nodes); c->d_nodes = nullptr;
-    c->d_tris = nullptr;
-    c->has_bvh = false;
-    HIP_TRY(c, hipMalloc((void**)&c->d_nodes, nb + tb + wb));
-    c->d_tris = c->d_nodes;  // one item buffer: links index it directly
-    HIP_TRY(c, hipMemcpy(c->d_nodes, O.bin.data(), nb, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy((char*)c->d_nodes + nb, O.rec.data(), tb, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy((char*)c->d_nodes + nb + tb, O.wide.data(), wb, hipMemcpyHostToDevice));
-    c->records_woop = c->opt_tri_test == 1;
-    c->wide_root = O.wide_root_f4;
-    c->wide_top_layout = O.n_top_wide;
-    c->wide_depth = O.depth_wide;
-    c->n_wide = O.wide.size() / 16;
-    c->n_top_layout = O.n_top_bin;
-    c->n_inner = O.bin.size() / 16;
-    c->n_refs = O.n_refs;
-    c->n_leaves = O.n_leaves;
-    c->max_depth = O.depth_bin;
-    c->scene_bytes = nb + tb + wb;
-    c->max_tri_id = max_id;
-    c->has_bvh = true;
-    c->build_ms = -1.f;   // no device build stands behind this tree (optimise_device_tree puts it back when one does)
+    (void)hipFree(t.d_nodes); t.d_nodes = nullptr;
+    t.d_tris = nullptr;
+    t.has_bvh = false;
+    HIP_TRY(c, hipMalloc((void**)&t.d_nodes, nb + tb + wb));
+    t.d_tris = t.d_nodes;  // one item buffer: links index it directly
+    HIP_TRY(c, hipMemcpy(t.d_nodes, O.bin.data(), nb, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy((char*)t.d_nodes + nb, O.rec.data(), tb, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy((char*)t.d_nodes + nb + tb, O.wide.data(), wb, hipMemcpyHostToDevice));
+    t.records_woop = c->opt_tri_test == 1;
+    t.wide_root = O.wide_root_f4;
+    t.wide_top_layout = O.n_top_wide;
+    t.wide_depth = O.depth_wide;
+    t.n_wide = O.wide.size() / 16;
+    t.n_top_layout = O.n_top_bin;
+    t.n_inner = O.bin.size() / 16;
+    t.n_refs = O.n_refs;
+    t.n_leaves = O.n_leaves;
+    t.max_depth = O.depth_bin;
+    t.scene_bytes = nb + tb + wb;
+    t.max_tri_id = max_id;
+    t.has_bvh = true;
+    t.build_ms = -1.f;   // no device build stands behind this tree (optimise_device_tree puts it back when one does)
     c->scene_gen++;
     return PT_OK;
 }
@@ -140,21 +116,62 @@ static int install_tree(pt_ctx* c, ptscene::Tree& X, int32_t max_id) {
 // hierarchy is optimised like an uploaded one and installed in its place; the device build's time stays on the context.
 // by_id[id] = the nine vertex floats of triangle `id` (the caller's own: records are re-encoded from them bit for bit).
 static int optimise_device_tree(pt_ctx* c, const std::vector<const float*>& by_id, int32_t max_id) {
-    if (c->opt_optimize <= 0 || !c->has_bvh || c->records_woop) return PT_OK;
-    const size_t n_bin = (size_t)c->n_inner, n_rec = (size_t)c->n_refs;
+    if (c->opt_optimize <= 0 || !c->tree.has_bvh || c->tree.records_woop) return PT_OK;
+    const size_t n_bin = (size_t)c->tree.n_inner, n_rec = (size_t)c->tree.n_refs;
     std::vector<float> bin(16 * n_bin), rec(16 * n_rec);
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(bin.data(), c->d_nodes, bin.size() * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(rec.data(), (const char*)c->d_nodes + bin.size() * sizeof(float), rec.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(bin.data(), c->tree.d_nodes, bin.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(rec.data(), (const char*)c->tree.d_nodes + bin.size() * sizeof(float), rec.size() * sizeof(float), hipMemcpyDeviceToHost));
     ptscene::Tree X;
     std::string why;
     if (!ptscene::from_items(bin.data(), n_bin, rec.data(), n_rec, by_id, X, why)) return fail(c, PT_ERR_DEVICE, "device-built tree: " + why);
-    const float device_ms = c->build_ms;
+    const float device_ms = c->tree.build_ms;
     const int rc = install_tree(c, X, max_id);
-    if (rc == PT_OK) c->build_ms = device_ms;
+    if (rc == PT_OK) c->tree.build_ms = device_ms;
     return rc;
 }
+
+// pt_set_option's table, one row per option: the member it sets, the values it takes and what a refused value is answered with.
+// TRI_TEST, LEAF_MAX and OPTIMIZE take effect at the next pt_upload_bvh.
+struct OptionRow {
+    enum Rule { FLAG, RANGE, SET };   // any value, kept as 0 / 1;  v[0]..v[1];  one of v[0..3] (a shorter set repeats its last value)
+    int id;
+    int pt_ctx::*field;
+    Rule rule;
+    int v[4];
+    int code;
+    const char* msg;
+};
+static const OptionRow OPTIONS[] = {
+    {PT_OPT_KERNEL, &pt_ctx::opt_kernel, OptionRow::SET, {PT_KERNEL_AUTO, PT_KERNEL_MEGA_BVH2, PT_KERNEL_PERSISTENT, PT_KERNEL_WAVEFRONT}, PT_ERR_UNSUPPORTED, "pt_set_option: kernel variant not available in this build"},
+    {PT_OPT_COUNTERS, &pt_ctx::opt_counters, OptionRow::FLAG, {}, PT_OK, ""},
+    {PT_OPT_TIMING, &pt_ctx::opt_timing, OptionRow::FLAG, {}, PT_OK, ""},
+    {PT_OPT_SPHERE_LDS, &pt_ctx::opt_sph_lds, OptionRow::FLAG, {}, PT_OK, ""},
+    {PT_OPT_OVERLAP, &pt_ctx::opt_overlap, OptionRow::FLAG, {}, PT_OK, ""},
+    {PT_OPT_TOP_NODES, &pt_ctx::opt_top, OptionRow::RANGE, {0, PT_MAX_TOP}, PT_ERR_INVALID, "pt_set_option: top nodes must be 0..1024"},
+    {PT_OPT_OCCUPANCY, &pt_ctx::opt_occ, OptionRow::SET, {4, 5, 6, 8}, PT_ERR_INVALID, "pt_set_option: occupancy must be 4, 5 (runs as 6), 6 or 8 waves per SIMD"},
+    {PT_OPT_TRI_TEST, &pt_ctx::opt_tri_test, OptionRow::RANGE, {0, 1}, PT_ERR_INVALID, "pt_set_option: tri test must be 0 (Moller-Trumbore) or 1 (Woop)"},
+    {PT_OPT_LEAF_MAX, &pt_ctx::opt_leaf_max, OptionRow::RANGE, {0, 1024}, PT_ERR_INVALID, "pt_set_option: leaf_max must be 0 (keep) .. 1024"},
+    {PT_OPT_WALK, &pt_ctx::opt_walk, OptionRow::SET, {0, 1, 2, 4}, PT_ERR_INVALID, "pt_set_option: walk must be 0 (while-while), 1 (unified-step), 2 (wide) or 4 (wide, postponed leaf)"},
+    {PT_OPT_REBUILD, &pt_ctx::opt_rebuild, OptionRow::RANGE, {0, 2}, PT_ERR_INVALID, "pt_set_option: rebuild must be 0 (keep the hierarchy), 1 (re-cluster) or 2 (keep the cheaper tree)"},
+    {PT_OPT_PRESPLIT, &pt_ctx::opt_presplit, OptionRow::RANGE, {0, 100000}, PT_ERR_INVALID, "pt_set_option: presplit must be 0 (off) .. 100000 (per cent of diag/sqrt(n))"},
+    {PT_OPT_BUILD_ALGO, &pt_ctx::opt_build_algo, OptionRow::RANGE, {0, 1}, PT_ERR_INVALID, "pt_set_option: build algorithm must be 0 (LBVH) or 1 (PLOC)"},
+    {PT_OPT_WAVE_BATCH, &pt_ctx::opt_wave_batch, OptionRow::RANGE, {1, 64}, PT_ERR_INVALID, "pt_set_option: wave batch must be 1..64"},
+    {PT_OPT_VOTE_NODE, &pt_ctx::opt_vote_node, OptionRow::RANGE, {1, 64}, PT_ERR_INVALID, "pt_set_option: vote weight must be 1..64"},
+    {PT_OPT_VOTE_REC, &pt_ctx::opt_vote_rec, OptionRow::RANGE, {1, 64}, PT_ERR_INVALID, "pt_set_option: vote weight must be 1..64"},
+    {PT_OPT_OPTIMIZE, &pt_ctx::opt_optimize, OptionRow::RANGE, {0, 16}, PT_ERR_INVALID, "pt_set_option: optimize passes must be 0 (off) .. 16"},
+    {PT_OPT_WAVE_SAMPLES, &pt_ctx::opt_wave_samples, OptionRow::RANGE, {1, 64}, PT_ERR_INVALID, "pt_set_option: wave samples must be 1 (one sample of a tile per wave) .. 64"},
+    {PT_OPT_WAVE_BLOCKS, &pt_ctx::opt_wave_blocks, OptionRow::RANGE, {1, 8}, PT_ERR_INVALID, "pt_set_option: wave blocks must be 1..8 per CU"},
+    {PT_OPT_LDS_STACK, &pt_ctx::opt_lstk, OptionRow::SET, {0, 16, 24, 24}, PT_ERR_INVALID, "pt_set_option: LDS stack must be 0 (all 72 entries in LDS), 16 or 24 entries"},
+    {PT_OPT_REFILL, &pt_ctx::opt_refill, OptionRow::RANGE, {1, 64}, PT_ERR_INVALID, "pt_set_option: refill must be 1..64"},
+    {PT_OPT_BATCH, &pt_ctx::opt_batch, OptionRow::RANGE, {1, 64}, PT_ERR_INVALID, "pt_set_option: batch must be 1..64"},
+    {PT_OPT_FIRST_WALK, &pt_ctx::opt_first_walk, OptionRow::RANGE, {0, 1}, PT_ERR_INVALID, "pt_set_option: first walk must be 0 (per lane) or 1 (wave-wide packets)"},
+    {PT_OPT_PACKET_STACK, &pt_ctx::opt_packet_stack, OptionRow::RANGE, {2, PT_PACKET_STACK_MAX}, PT_ERR_INVALID, "pt_set_option: packet stack must be 2..72 entries"},
+    {PT_OPT_FUSE_STAGES, &pt_ctx::opt_fuse_stages, OptionRow::RANGE, {0, 1}, PT_ERR_INVALID, "pt_set_option: fuse stages must be 0 (separate launches) or 1"},
+    {PT_OPT_LAST_ANYHIT, &pt_ctx::opt_last_anyhit, OptionRow::RANGE, {0, 2}, PT_ERR_INVALID, "pt_set_option: last any-hit must be 0 (off), 1 (product launches) or 2 (instrumented launches too)"},
+    {PT_OPT_ROOT_CULL, &pt_ctx::opt_root_cull, OptionRow::RANGE, {0, 2}, PT_ERR_INVALID, "pt_set_option: root cull must be 0 (off), 1 (product launches) or 2 (instrumented launches too)"},
+};
 }  // namespace ptmi
 
 extern "C" {
@@ -197,7 +214,7 @@ int pt_destroy(pt_ctx* c) {
     if (!c) return PT_OK;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(c->d_nodes);  // d_tris aliases it
+    (void)hipFree(c->tree.d_nodes);  // d_tris aliases it
     (void)hipFree(c->d_spheres);
     (void)hipFree(c->d_tri_matid);
     (void)hipFree(c->d_mat_table);
@@ -237,103 +254,16 @@ int pt_set_stream(pt_ctx* c, void* s) {
 
 int pt_set_option(pt_ctx* c, int option, int value) {
     if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
-    switch (option) {
-        case PT_OPT_KERNEL:
-            if (value != PT_KERNEL_AUTO && value != PT_KERNEL_MEGA_BVH2 && value != PT_KERNEL_PERSISTENT && value != PT_KERNEL_WAVEFRONT)
-                return fail(c, PT_ERR_UNSUPPORTED, "pt_set_option: kernel variant not available in this build");
-            c->opt_kernel = value;
-            return PT_OK;
-        case PT_OPT_COUNTERS: c->opt_counters = value != 0; return PT_OK;
-        case PT_OPT_TIMING: c->opt_timing = value != 0; return PT_OK;
-        case PT_OPT_TOP_NODES:
-            if (value < 0 || value > PT_MAX_TOP) return fail(c, PT_ERR_INVALID, "pt_set_option: top nodes must be 0..1024");
-            c->opt_top = value;
-            return PT_OK;
-        case PT_OPT_OCCUPANCY:
-            if (value != 4 && value != 5 && value != 6 && value != 8) return fail(c, PT_ERR_INVALID, "pt_set_option: occupancy must be 4, 5 (runs as 6), 6 or 8 waves per SIMD");
-            c->opt_occ = value;
-            return PT_OK;
-        case PT_OPT_TRI_TEST:
-            if (value != 0 && value != 1) return fail(c, PT_ERR_INVALID, "pt_set_option: tri test must be 0 (Moller-Trumbore) or 1 (Woop)");
-            c->opt_tri_test = value;   // takes effect at the next pt_upload_bvh
-            return PT_OK;
-        case PT_OPT_LEAF_MAX:
-            if (value < 0 || value > 1024) return fail(c, PT_ERR_INVALID, "pt_set_option: leaf_max must be 0 (keep) .. 1024");
-            c->opt_leaf_max = value;   // takes effect at the next pt_upload_bvh
-            return PT_OK;
-        case PT_OPT_WALK:
-            if (value < 0 || value > 4 || value == 3) return fail(c, PT_ERR_INVALID, "pt_set_option: walk must be 0 (while-while), 1 (unified-step), 2 (wide) or 4 (wide, postponed leaf)");
-            c->opt_walk = value;
-            return PT_OK;
-        case PT_OPT_SPHERE_LDS: c->opt_sph_lds = value != 0; return PT_OK;
-        case PT_OPT_REBUILD:
-            if (value < 0 || value > 2) return fail(c, PT_ERR_INVALID, "pt_set_option: rebuild must be 0 (keep the hierarchy), 1 (re-cluster) or 2 (keep the cheaper tree)");
-            c->opt_rebuild = value;
-            return PT_OK;
-        case PT_OPT_PRESPLIT:
-            if (value < 0 || value > 100000) return fail(c, PT_ERR_INVALID, "pt_set_option: presplit must be 0 (off) .. 100000 (per cent of diag/sqrt(n))");
-            c->opt_presplit = value;
-            return PT_OK;
-        case PT_OPT_BUILD_ALGO:
-            if (value != 0 && value != 1) return fail(c, PT_ERR_INVALID, "pt_set_option: build algorithm must be 0 (LBVH) or 1 (PLOC)");
-            c->opt_build_algo = value;
-            return PT_OK;
-        case PT_OPT_WAVE_BATCH:
-            if (value < 1 || value > 64) return fail(c, PT_ERR_INVALID, "pt_set_option: wave batch must be 1..64");
-            c->opt_wave_batch = value;
-            return PT_OK;
-        case PT_OPT_VOTE_NODE:
-        case PT_OPT_VOTE_REC:
-            if (value < 1 || value > 64) return fail(c, PT_ERR_INVALID, "pt_set_option: vote weight must be 1..64");
-            (option == PT_OPT_VOTE_NODE ? c->opt_vote_node : c->opt_vote_rec) = value;
-            return PT_OK;
-        case PT_OPT_OVERLAP: c->opt_overlap = value != 0; return PT_OK;
-        case PT_OPT_OPTIMIZE:
-            if (value < 0 || value > 16) return fail(c, PT_ERR_INVALID, "pt_set_option: optimize passes must be 0 (off) .. 16");
-            c->opt_optimize = value;   // takes effect at the next pt_upload_bvh
-            return PT_OK;
-        case PT_OPT_WAVE_SAMPLES:
-            if (value < 1 || value > 64) return fail(c, PT_ERR_INVALID, "pt_set_option: wave samples must be 1 (one sample of a tile per wave) .. 64");
-            c->opt_wave_samples = value;
-            return PT_OK;
-        case PT_OPT_WAVE_BLOCKS:
-            if (value < 1 || value > 8) return fail(c, PT_ERR_INVALID, "pt_set_option: wave blocks must be 1..8 per CU");
-            c->opt_wave_blocks = value;
-            return PT_OK;
-        case PT_OPT_LDS_STACK:
-            if (value != 0 && value != 16 && value != 24) return fail(c, PT_ERR_INVALID, "pt_set_option: LDS stack must be 0 (all 72 entries in LDS), 16 or 24 entries");
-            c->opt_lstk = value;
-            return PT_OK;
-        case PT_OPT_REFILL:
-            if (value < 1 || value > 64) return fail(c, PT_ERR_INVALID, "pt_set_option: refill must be 1..64");
-            c->opt_refill = value;
-            return PT_OK;
-        case PT_OPT_BATCH:
-            if (value < 1 || value > 64) return fail(c, PT_ERR_INVALID, "pt_set_option: batch must be 1..64");
-            c->opt_batch = value;
-            return PT_OK;
-        case PT_OPT_FIRST_WALK:
-            if (value != 0 && value != 1) return fail(c, PT_ERR_INVALID, "pt_set_option: first walk must be 0 (per lane) or 1 (wave-wide packets)");
-            c->opt_first_walk = value;
-            return PT_OK;
-        case PT_OPT_PACKET_STACK:
-            if (value < 2 || value > PT_PACKET_STACK_MAX) return fail(c, PT_ERR_INVALID, "pt_set_option: packet stack must be 2..72 entries");
-            c->opt_packet_stack = value;
-            return PT_OK;
-        case PT_OPT_FUSE_STAGES:
-            if (value != 0 && value != 1) return fail(c, PT_ERR_INVALID, "pt_set_option: fuse stages must be 0 (separate launches) or 1");
-            c->opt_fuse_stages = value;
-            return PT_OK;
-        case PT_OPT_LAST_ANYHIT:
-            if (value < 0 || value > 2) return fail(c, PT_ERR_INVALID, "pt_set_option: last any-hit must be 0 (off), 1 (product launches) or 2 (instrumented launches too)");
-            c->opt_last_anyhit = value;
-            return PT_OK;
-        case PT_OPT_ROOT_CULL:
-            if (value < 0 || value > 2) return fail(c, PT_ERR_INVALID, "pt_set_option: root cull must be 0 (off), 1 (product launches) or 2 (instrumented launches too)");
-            c->opt_root_cull = value;
-            return PT_OK;
-        default: return fail(c, PT_ERR_INVALID, "pt_set_option: unknown option");
+    for (const OptionRow& o : OPTIONS) {
+        if (o.id != option) continue;
+        bool ok = true;
+        if (o.rule == OptionRow::RANGE) ok = value >= o.v[0] && value <= o.v[1];
+        if (o.rule == OptionRow::SET) ok = std::find(o.v, o.v + 4, value) != o.v + 4;
+        if (!ok) return fail(c, o.code, o.msg);
+        c->*o.field = o.rule == OptionRow::FLAG ? value != 0 : value;
+        return PT_OK;
     }
+    return fail(c, PT_ERR_INVALID, "pt_set_option: unknown option");
 }
 
 int pt_sync(pt_ctx* c) {
@@ -445,22 +375,20 @@ int pt_upload_bvh(pt_ctx* c, const float* nodes, size_t n_node_vec4, const float
         const int rc = install(T);
         if (rc != PT_OK) return rc;
     }
-    if (rebuild == 2 && c->n_wide > 0) {
+    if (rebuild == 2 && c->tree.n_wide > 0) {
         // PT_OPT_REBUILD 2: the caller's hierarchy is up; build the re-clustered one beside it and keep whichever costs a
         // random ray fewer wide-node visits (pt_tree_cost).  A failure on the way leaves the caller's tree in place.
         double cost_a = 0.0, cost_b = 0.0, unused = 0.0;
         if (tree_cost_impl(c, &cost_a, &unused) != PT_OK) return PT_OK;
-        const TreeState mine = TreeState::of(c);
-        const double mine_opt[2] = {c->opt_cost[0], c->opt_cost[1]};
-        c->d_nodes = nullptr;   // the builder frees the context's buffer before it installs its own
-        c->d_tris = nullptr;
-        const bool built = recluster() == PT_OK && c->d_nodes != nullptr && optimise_reclustered() == PT_OK && c->d_nodes != nullptr;
+        const TreeState mine = c->tree;
+        c->tree.d_nodes = nullptr;   // the builder frees the context's buffer before it installs its own
+        c->tree.d_tris = nullptr;
+        const bool built = recluster() == PT_OK && c->tree.d_nodes != nullptr && optimise_reclustered() == PT_OK && c->tree.d_nodes != nullptr;
         if (built && tree_cost_impl(c, &cost_b, &unused) == PT_OK && cost_b < cost_a) {
             (void)hipFree(mine.d_nodes);
         } else {
-            if (c->d_nodes != mine.d_nodes) (void)hipFree(c->d_nodes);
-            mine.restore(c);
-            c->opt_cost[0] = mine_opt[0]; c->opt_cost[1] = mine_opt[1];
+            if (c->tree.d_nodes != mine.d_nodes) (void)hipFree(c->tree.d_nodes);
+            c->tree = mine;
             c->err.clear();
         }
         refit_release(c);   // made for neither tree (pt_refit_bvh makes it again for the one kept)
@@ -491,8 +419,8 @@ int pt_build_bvh(pt_ctx* c, const float* verts, size_t n_verts, const int32_t* t
 
 int pt_last_build_ms(pt_ctx* c, float* ms) {
     if (!c || !ms) return fail(c, PT_ERR_INVALID, "pt_last_build_ms: null argument");
-    if (c->build_ms < 0.f) return fail(c, PT_ERR_INVALID, "pt_last_build_ms: the tree on this context was not built on the device");
-    *ms = c->build_ms;
+    if (c->tree.build_ms < 0.f) return fail(c, PT_ERR_INVALID, "pt_last_build_ms: the tree on this context was not built on the device");
+    *ms = c->tree.build_ms;
     return PT_OK;
 }
 
@@ -512,7 +440,7 @@ int pt_upload_tri_materials(pt_ctx* c, const pt_material* table, size_t n_materi
     }
     if (!table || !tri_material) return fail(c, PT_ERR_INVALID, "pt_upload_tri_materials: null array");
     if (n_materials > (1u << 24) || n_tris >= (size_t)0x7fffffff) return fail(c, PT_ERR_INVALID, "pt_upload_tri_materials: table too large");
-    if (c->has_bvh && (size_t)c->max_tri_id >= n_tris && c->max_tri_id >= 0)
+    if (c->tree.has_bvh && (size_t)c->tree.max_tri_id >= n_tris && c->tree.max_tri_id >= 0)
         return fail(c, PT_ERR_INVALID, "pt_upload_tri_materials: n_tris does not cover the triangle ids of the uploaded BVH");
     for (size_t i = 0; i < n_materials; i++)
         if (table[i].mat < PT_MAT_DIFF || table[i].mat > PT_MAT_REFR) return fail(c, PT_ERR_INVALID, "pt_upload_tri_materials: bad material type");
@@ -590,23 +518,21 @@ int pt_upload_spheres(pt_ctx* c, const pt_sphere* spheres, size_t n) {
 
 int pt_scene_info(pt_ctx* c, uint64_t* n_inner, uint64_t* n_refs, uint64_t* n_leaves, uint32_t* max_depth, uint64_t* bytes) {
     if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
-    if (!c->has_bvh) return fail(c, PT_ERR_NO_SCENE, "pt_scene_info: no BVH uploaded");
-    if (n_inner) *n_inner = c->n_inner;
-    if (n_refs) *n_refs = c->n_refs;
-    if (n_leaves) *n_leaves = c->n_leaves;
-    if (max_depth) *max_depth = c->max_depth;
-    if (bytes) *bytes = c->scene_bytes;
+    if (!c->tree.has_bvh) return fail(c, PT_ERR_NO_SCENE, "pt_scene_info: no BVH uploaded");
+    if (n_inner) *n_inner = c->tree.n_inner;
+    if (n_refs) *n_refs = c->tree.n_refs;
+    if (n_leaves) *n_leaves = c->tree.n_leaves;
+    if (max_depth) *max_depth = c->tree.max_depth;
+    if (bytes) *bytes = c->tree.scene_bytes;
     return PT_OK;
 }
 
 // ---------------------------------------------------------------------------------------
-int pt_render(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, const pt_camera* cam, const pt_params* p, uint32_t spp) {
-    return pt_render_moments(c, accum_dev, rgba_dev, nullptr, cam, p, spp);
-}
-
-// pt_render's body; moments_dev != NULL: the fold also keeps the luminance moments of the samples (DESIGN.md §10 f7)
-int pt_render_moments(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, float* moments_dev, const pt_camera* cam, const pt_params* p,
-                      uint32_t spp) {
+// pt_render in steps, in the order pt_render_moments runs them: check the arguments, bring the light list up to date, fill the
+// kernel arguments, PLAN the call (plan_call: every decision about what runs and with which buffers, made once), take the
+// buffers the plan asks for, launch.
+namespace ptmi {
+static int check_call(pt_ctx* c, const float* accum_dev, const uint32_t* rgba_dev, const pt_camera* cam, const pt_params* p, uint32_t spp) {
     if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
     if (!accum_dev || !cam || !p) return fail(c, PT_ERR_INVALID, "pt_render: null argument");
     if (p->width < 2 || p->height < 2) return fail(c, PT_ERR_INVALID, "pt_render: image must be at least 2x2 (the camera divides by w-1, h-1)");
@@ -615,21 +541,50 @@ int pt_render_moments(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, float* mo
     if (p->tri_mat < PT_MAT_DIFF || p->tri_mat > PT_MAT_REFR) return fail(c, PT_ERR_INVALID, "pt_render: bad triangle material");
     if ((p->flags & PT_FLAG_WRITE_RGBA) && !rgba_dev) return fail(c, PT_ERR_INVALID, "pt_render: PT_FLAG_WRITE_RGBA needs rgba_dev");
     if ((p->flags & PT_FLAG_NEE) && !(p->flags & PT_FLAG_COSINE_DIFF)) return fail(c, PT_ERR_INVALID, "pt_render: PT_FLAG_NEE needs PT_FLAG_COSINE_DIFF (the reference's DIFF lobe has no density to weigh a light sample against)");
-    if (!c->has_bvh && c->n_spheres == 0) return fail(c, PT_ERR_NO_SCENE, "pt_render: no scene uploaded");
+    if (!c->tree.has_bvh && c->n_spheres == 0) return fail(c, PT_ERR_NO_SCENE, "pt_render: no scene uploaded");
     if (p->part_count > 1) {
         if (p->part_index < 0 || p->part_index >= p->part_count) return fail(c, PT_ERR_INVALID, "pt_render: part_index out of range");
         if (p->part_rows <= 0 || (p->part_rows % PT_TILE) != 0) return fail(c, PT_ERR_INVALID, "pt_render: part_rows must be a positive multiple of 8");
     }
-    HIP_TRY(c, hipSetDevice(c->device));
+    return PT_OK;
+}
 
-    KParams P;
+// PT_FLAG_NEE over emissive triangles: the call samples the light list
+static bool samples_tri_lights(const pt_ctx* c, const pt_params* p) {
+    return (p->flags & PT_FLAG_NEE) && c->tree.has_bvh && !c->emissive_ids.empty();
+}
+
+// the scene, its geometry (pt_refit_bvh) or the materials changed: copies the lights' vertices out of the records again
+static int refresh_tri_lights(pt_ctx* c, const pt_params* p) {
+    if (!samples_tri_lights(c, p)) return PT_OK;
+    if (c->tree.records_woop) return fail(c, PT_ERR_UNSUPPORTED, "pt_render: PT_FLAG_NEE over emissive triangles needs the exact (Moller-Trumbore) records");
+    const uint64_t key = (c->scene_gen << 32) ^ c->mat_gen;
+    if (c->lights_key == key && c->lights_geom == c->geom_gen) return PT_OK;
+    const uint32_t n_rec = (uint32_t)c->tree.n_refs;
+    HIP_TRY(c, hipMemsetAsync(c->d_tri_lights, 0, c->emissive_ids.size() * 3 * sizeof(float4), c->stream));
+    hipLaunchKernelGGL(k_collect_tri_lights, dim3((n_rec + 255) / 256), dim3(256), 0, c->stream, c->tree.d_nodes + 4 * (size_t)c->tree.n_inner, n_rec,
+                       c->d_light_slot, (uint32_t)c->n_tri_matid, c->d_tri_matid, c->d_mat_table, c->d_tri_lights);
+    HIP_TRY(c, hipGetLastError());
+    c->lights_key = key;
+    c->lights_geom = c->geom_gen;
+    // a path kernel on a side stream (PT_OPT_OVERLAP) must not read the list before it is written
+    if (!c->lights_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->lights_ev, hipEventDisableTiming));
+    HIP_TRY(c, hipEventRecord(c->lights_ev, c->stream));
+    c->lights_gen++;
+    return PT_OK;
+}
+
+// the kernel arguments that the context and the call's arguments give; what the plan decides (samples, LDS layout, queue) is added
+// by pt_render_moments.  A part that owns no tile leaves P.n_tiles <= 0 and PT_OK: nothing to render.
+static int fill_params(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, const pt_camera* cam, const pt_params* p, uint32_t spp, KParams& P) {
     std::memset(&P, 0, sizeof P);
-    P.sc.nodes = c->d_nodes;
-    P.sc.tris = c->d_tris;
+    P.sc.nodes = c->tree.d_nodes;
+    P.sc.tris = c->tree.d_tris;
     P.sc.spheres = c->d_spheres;
     P.sc.n_spheres = c->n_spheres;
     std::memcpy(P.ksph, c->h_spheres, sizeof P.ksph);
-    P.sc.has_bvh = c->has_bvh ? 1 : 0;
+    P.sc.has_bvh = c->tree.has_bvh ? 1 : 0;
+    P.sc.wide_root = (int)c->tree.wide_root;
     P.accum = accum_dev;
     P.rgba = rgba_dev;
     P.counters = c->d_counters;
@@ -644,25 +599,12 @@ int pt_render_moments(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, float* mo
     P.tri_matid = c->d_tri_matid;
     P.mat_table = c->d_mat_table;
     P.flags = p->flags;
-    if ((p->flags & PT_FLAG_NEE) && c->has_bvh && !c->emissive_ids.empty()) {
-        if (c->records_woop) return fail(c, PT_ERR_UNSUPPORTED, "pt_render: PT_FLAG_NEE over emissive triangles needs the exact (Moller-Trumbore) records");
-        const uint64_t key = (c->scene_gen << 32) ^ c->mat_gen;
-        if (c->lights_key != key || c->lights_geom != c->geom_gen) {   // the scene, its geometry (pt_refit_bvh) or the materials changed: copy the lights' vertices out of the records again
-            const uint32_t n_rec = (uint32_t)c->n_refs;
-            HIP_TRY(c, hipMemsetAsync(c->d_tri_lights, 0, c->emissive_ids.size() * 3 * sizeof(float4), c->stream));
-            hipLaunchKernelGGL(k_collect_tri_lights, dim3((n_rec + 255) / 256), dim3(256), 0, c->stream, c->d_nodes + 4 * (size_t)c->n_inner, n_rec,
-                               c->d_light_slot, (uint32_t)c->n_tri_matid, c->d_tri_matid, c->d_mat_table, c->d_tri_lights);
-            HIP_TRY(c, hipGetLastError());
-            c->lights_key = key;
-            c->lights_geom = c->geom_gen;
-            // a path kernel on a side stream (PT_OPT_OVERLAP) must not read the list before it is written
-            if (!c->lights_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->lights_ev, hipEventDisableTiming));
-            HIP_TRY(c, hipEventRecord(c->lights_ev, c->stream));
-            c->lights_gen++;
-        }
+    if (samples_tri_lights(c, p)) {
         P.tri_lights = c->d_tri_lights;
         P.n_tri_lights = (int)c->emissive_ids.size();
     }
+    P.smp_ss = (unsigned long long)p->width * (unsigned long long)p->height;   // one sample per pixel, or sample planes (plan.sgroup_log2 = 0)
+    P.smp_ps = 1u;
     P.tiles_x = (p->width + PT_TILE - 1) / PT_TILE;
     P.tile_rows = (p->height + PT_TILE - 1) / PT_TILE;
     if (p->part_count > 1) {
@@ -675,208 +617,257 @@ int pt_render_moments(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, float* mo
         P.n_tiles = P.tile_rows * P.tiles_x;
     }
     if (P.n_tiles <= 0) return PT_OK;
-    const int waves_per_block = PT_BLOCK / 64;
     if ((uint64_t)P.n_tiles * 64u * (uint64_t)spp >= (1ull << 31)) return fail(c, PT_ERR_INVALID, "pt_render: width*height*spp too large for one call (split the samples over several calls)");
+    return PT_OK;
+}
 
-    // the wide walk pushes up to three entries per level
-    int walk = c->opt_walk;
-    const bool wide_ok = c->has_bvh && 3 * c->wide_depth + 2 <= (uint32_t)PT_STACK_CAP;
-    if (c->has_bvh && c->records_woop) {
-        if (!wide_ok) return fail(c, PT_ERR_UNSUPPORTED, "pt_render: Woop records need the wide walk and this tree is too deep for it");
-        walk = 3;  // Woop records are only understood by the wide walk
-    } else if ((walk == 2 || walk == 4) && !wide_ok) {
-        walk = 1;
+// PT_KERNEL_AUTO: the entry of the call's configuration in the table of picks (a new configuration takes the least recently used one) and
+// what this call is to it.  probe = 0..3: the timed trial of that number (even: the persistent kernel, odd: the pipeline), and the trial is
+// consumed here; -1: no trial, the call runs pick->choice once the trials' events have been read and the persistent kernel until then.
+static int auto_lookup(pt_ctx* c, const pt_params* p, uint32_t spp, bool moments, pt_ctx::AutoPick*& pick, int& probe) {
+    using AP = pt_ctx::AutoPick;
+    // the key holds the SHAPE of the partition, not which part this call renders: the parts of a tile split cost alike
+    uint64_t key = 0xcbf29ce484222325ull;
+    const uint64_t parts[] = {(uint64_t)p->width, (uint64_t)p->height, (uint64_t)spp, (uint64_t)p->depth,
+                              (uint64_t)(p->part_count > 1 ? p->part_count : 1), (uint64_t)(p->part_count > 1 ? p->part_rows : 0), c->scene_gen,
+                              (uint64_t)c->n_spheres, (uint64_t)p->tri_mat, (uint64_t)(p->flags & ~(uint32_t)PT_FLAG_WRITE_RGBA),
+                              (uint64_t)moments};   // with moments the pipeline keeps its separate fold and one sample goes through the sample buffer: other trial times
+    for (uint64_t v : parts) { key ^= v; key *= 0x100000001b3ull; }
+    if (key == 0) key = 1;
+    int slot = -1, lru = 0;
+    for (int i = 0; i < pt_ctx::N_PICKS; i++) {
+        if (c->picks[i].key == key) { slot = i; break; }
+        if (c->picks[i].used < c->picks[lru].used) lru = i;
     }
-    // which frame kernel: the stage-split pipeline needs a BVH, at least one bounce and the wide walk over exact
-    // records; every other request for it runs the persistent kernel (same images)
-    const bool wave_ok = c->has_bvh && P.depth > 0 && walk == 2;
+    if (slot < 0) {
+        slot = lru;
+        AP& n = c->picks[slot];
+        if (n.phase > 0 && n.phase < AP::DECIDED)   // trials of the configuration it held may still be in flight: its events must be idle
+            for (hipEvent_t e : n.e) if (e) (void)hipEventSynchronize(e);
+        n.key = key; n.phase = 0; n.choice = PT_KERNEL_PERSISTENT; n.ms[0] = n.ms[1] = 0.f;
+    }
+    AP& a = c->picks[slot];
+    a.used = ++c->pick_tick;
+    c->pick_last = slot;
+    pick = &a;
+    probe = -1;
+    (void)auto_decide(c, a, false);   // all trials queued: decide once their events have completed, never wait for them
+    if (a.phase < AP::TRIALS) {
+        for (hipEvent_t& e : a.e)
+            if (!e) HIP_TRY(c, hipEventCreate(&e));
+        probe = a.phase++;   // (counted here, before the call's later steps, which can still fail: a trial that never ran stays counted)
+    }
+    return PT_OK;
+}
+
+// What one call runs and with which buffers.  plan_call decides it, once; nothing after it changes the kernel family.
+struct CallPlan {
+    int kernel;               // PT_KERNEL_MEGA_BVH2, PT_KERNEL_PERSISTENT or PT_KERNEL_WAVEFRONT
+    int probe;                // PT_KERNEL_AUTO: this call is timed trial `probe` of `pick`; -1: it is none
+    pt_ctx::AutoPick* pick;
+    bool side;                // the path kernel runs on a side stream (PT_OPT_OVERLAP)
+    bool samples;             // ... into a sample buffer that a fold reads afterwards
+    uint32_t sgroup_log2;     // the samples of a pixel side by side in the slot order and in the sample buffer (wave_sample_group_log2)
+    int n_top, sph_tab;       // LDS: nodes mirrored, first word of the sphere table (-1: none)
+    int chunk, work_tiles;    // queue granularity in slots, 64-slot work items of the call
+    LaunchCfg L;              // walk, stack window, LDS bytes, grids
+};
+
+static int plan_call(pt_ctx* c, const pt_params* p, const KParams& P, uint32_t spp, bool moments, CallPlan& plan) {
+    const TreeState& t = c->tree;
+    LaunchCfg& L = plan.L;
+    const bool nee = (p->flags & PT_FLAG_NEE) != 0;
+    // the walk: the wide walk pushes up to three entries per level
+    L.walk = c->opt_walk;
+    const bool wide_ok = t.has_bvh && 3 * t.wide_depth + 2 <= (uint32_t)PT_STACK_CAP;
+    if (t.has_bvh && t.records_woop) {
+        if (!wide_ok) return fail(c, PT_ERR_UNSUPPORTED, "pt_render: Woop records need the wide walk and this tree is too deep for it");
+        L.walk = 3;  // Woop records are only understood by the wide walk
+    } else if ((L.walk == 2 || L.walk == 4) && !wide_ok) {
+        L.walk = 1;
+    }
+    // the kernel family, every rule once and in this order: the option; PT_KERNEL_AUTO's table; PT_FLAG_NEE; what a family cannot run.
+    // The stage-split pipeline needs a BVH, at least one bounce and the wide walk over exact records.
+    const bool wave_ok = t.has_bvh && P.depth > 0 && L.walk == 2;
     int kernel = c->opt_kernel;
-    int probe = -1;   // PT_KERNEL_AUTO: 0 / 1 = this call is the timed trial of the persistent kernel / the pipeline
-    pt_ctx::AutoPick* pick = nullptr;
+    plan.probe = -1;
+    plan.pick = nullptr;
     if (kernel == PT_KERNEL_AUTO) {
         kernel = PT_KERNEL_PERSISTENT;
-        if (wave_ok && !c->opt_counters && !(p->flags & PT_FLAG_NEE)) {
-            // the key holds the SHAPE of the partition, not which part this call renders: the parts of a tile split cost alike
-            uint64_t key = 0xcbf29ce484222325ull;
-            const uint64_t parts[] = {(uint64_t)p->width, (uint64_t)p->height, (uint64_t)spp, (uint64_t)p->depth,
-                                      (uint64_t)(p->part_count > 1 ? p->part_count : 1), (uint64_t)(p->part_count > 1 ? p->part_rows : 0), c->scene_gen,
-                                      (uint64_t)c->n_spheres, (uint64_t)p->tri_mat, (uint64_t)(p->flags & ~(uint32_t)PT_FLAG_WRITE_RGBA),
-                                      (uint64_t)(moments_dev != nullptr)};   // with moments the pipeline keeps its separate fold and one sample goes through the sample buffer: other trial times
-            for (uint64_t v : parts) { key ^= v; key *= 0x100000001b3ull; }
-            if (key == 0) key = 1;
-            int slot = -1, lru = 0;
-            for (int i = 0; i < pt_ctx::N_PICKS; i++) {
-                if (c->picks[i].key == key) { slot = i; break; }
-                if (c->picks[i].used < c->picks[lru].used) lru = i;
-            }
-            if (slot < 0) {
-                slot = lru;
-                pt_ctx::AutoPick& n = c->picks[slot];
-                if (n.phase > 0 && n.phase < pt_ctx::AutoPick::DECIDED)   // trials of the configuration it held may still be in flight: its events must be idle
-                    for (hipEvent_t e : n.e) if (e) (void)hipEventSynchronize(e);
-                n.key = key; n.phase = 0; n.choice = PT_KERNEL_PERSISTENT; n.ms[0] = n.ms[1] = 0.f;
-            }
-            pt_ctx::AutoPick& a = c->picks[slot];
-            a.used = ++c->pick_tick;
-            c->pick_last = slot;
-            pick = &a;
-            (void)auto_decide(c, a, false);   // all trials queued: decide once their events have completed, never wait for them
-            if (a.phase < pt_ctx::AutoPick::TRIALS) {
-                for (hipEvent_t& e : a.e)
-                    if (!e) HIP_TRY(c, hipEventCreate(&e));
-                probe = a.phase;
-                kernel = (probe & 1) ? PT_KERNEL_WAVEFRONT : PT_KERNEL_PERSISTENT;
-                a.phase++;
-            } else {
-                kernel = a.phase == pt_ctx::AutoPick::DECIDED ? a.choice : PT_KERNEL_PERSISTENT;
-            }
+        if (wave_ok && !c->opt_counters && !nee) {   // (an instrumented call is no trial; a call with shadow rays has no choice)
+            const int rc = auto_lookup(c, p, spp, moments, plan.pick, plan.probe);
+            if (rc != PT_OK) return rc;
+            if (plan.probe >= 0) kernel = (plan.probe & 1) ? PT_KERNEL_WAVEFRONT : PT_KERNEL_PERSISTENT;
+            else if (plan.pick->phase == pt_ctx::AutoPick::DECIDED) kernel = plan.pick->choice;
         }
     }
-    if (p->flags & PT_FLAG_NEE) {   // shadow rays: the stage-split pipeline has a stage for them, the megakernel a loop; the
-                                    // persistent kernel does not (its lanes have no room for a second ray)
-        const bool nee_wave = wave_ok && (uint64_t)p->width * (uint64_t)p->height <= (1ull << PT_REC_PIXEL_BITS);   // the pixel rides below nee_mask in ray1.z
-        if (kernel != PT_KERNEL_MEGA_BVH2) kernel = nee_wave ? PT_KERNEL_WAVEFRONT : PT_KERNEL_MEGA_BVH2;
-        if (kernel == PT_KERNEL_WAVEFRONT && !nee_wave) kernel = PT_KERNEL_MEGA_BVH2;
-    }
-    if (kernel == PT_KERNEL_WAVEFRONT && !wave_ok) kernel = PT_KERNEL_PERSISTENT;
-    if (kernel == PT_KERNEL_MEGA_BVH2 && walk == 3) kernel = PT_KERNEL_PERSISTENT;   // Woop records: persistent kernel only
-    const bool persistent = kernel == PT_KERNEL_PERSISTENT;
-    const bool wavefront = kernel == PT_KERNEL_WAVEFRONT;
+    // shadow rays: the pipeline has a stage for them (the pixel rides below nee_mask in ray1.z, so it must fit), the megakernel a loop;
+    // the persistent kernel has neither (its lanes have no room for a second ray)
+    if (nee && kernel != PT_KERNEL_MEGA_BVH2)
+        kernel = wave_ok && (uint64_t)p->width * (uint64_t)p->height <= (1ull << PT_REC_PIXEL_BITS) ? PT_KERNEL_WAVEFRONT : PT_KERNEL_MEGA_BVH2;
+    if (kernel == PT_KERNEL_WAVEFRONT && !wave_ok) kernel = PT_KERNEL_PERSISTENT;   // same images
+    if (kernel == PT_KERNEL_MEGA_BVH2 && L.walk == 3) kernel = PT_KERNEL_PERSISTENT;   // Woop records: persistent kernel only
+    plan.kernel = kernel;
+    const bool persistent = kernel == PT_KERNEL_PERSISTENT, wavefront = kernel == PT_KERNEL_WAVEFRONT;
 
-    // spp > 1: trace the samples as independent work items, fold them afterwards (k_fold_samples); the
-    // stage-split pipeline always works that way
-    P.samples = nullptr;
     // overlap with the previous call: the path kernel goes to a side stream with its own sample buffer and queue
     // counters, so it can start while the previous call's last paths drain (the tail of a call is as long as its
     // longest path: ~15 % of a one-sample 1080p call); instrumented, timed and trial calls run in line
-    pt_ctx::Side* sd = nullptr;
-    // ... unless the caller's stream is idle: a host that syncs before every launch (BasicScene.cpp:395) leaves nothing to overlap
-    // with, and in line the call is two launches shorter (no cross-stream events; one sample folds inside the path kernel)
+    // ... and so does a call whose caller's stream is idle: a host that syncs before every launch (BasicScene.cpp:395) leaves nothing to
+    // overlap with, and in line the call is two launches shorter (no cross-stream events; one sample folds inside the path kernel)
     bool caller_idle = false;
     if (c->opt_overlap && !wavefront) {
         caller_idle = hipStreamQuery(c->stream) == hipSuccess;
         if (!caller_idle) (void)hipGetLastError();   // hipErrorNotReady is not an error of this call
     }
-    if (c->opt_overlap && !wavefront && !c->opt_counters && !c->opt_timing && probe < 0 && !caller_idle) {
-        sd = &c->side[c->side_next];
-        c->side_next ^= 1;
-        if (!sd->stream) {
-            // a priority of its own: ROCm maps the streams of one priority onto a few hardware queues round-robin (four
-            // by default, GPU_MAX_HW_QUEUES), and a side stream that shares a hardware queue with the caller's stream or
-            // with the other side stream runs in order behind it — no overlap and a 5-9 % LOSS (measured with a second
-            // context alive).  The high-priority class has queues of its own.
-            int prio_lo = 0, prio_hi = 0;
-            HIP_TRY(c, hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-            HIP_TRY(c, hipStreamCreateWithPriority(&sd->stream, hipStreamNonBlocking, prio_hi));
-            HIP_TRY(c, hipEventCreateWithFlags(&sd->traced, hipEventDisableTiming));
-            HIP_TRY(c, hipEventCreateWithFlags(&sd->folded, hipEventDisableTiming));
-            HIP_TRY(c, hipMalloc((void**)&sd->queue, PT_SHARDS * PT_SHARD_STRIDE * sizeof(unsigned int)));
-        }
+    plan.side = c->opt_overlap && !wavefront && !c->opt_counters && !c->opt_timing && plan.probe < 0 && !caller_idle;
+    // spp > 1: trace the samples as independent work items, fold them afterwards (k_fold_samples); the stage-split pipeline always
+    // works that way, and the moments are the fold's job
+    plan.samples = spp > 1 || wavefront || plan.side || moments;
+    plan.sgroup_log2 = plan.samples && (wavefront || persistent) ? wave_sample_group_log2(spp, c->opt_wave_samples) : 0u;
+    plan.work_tiles = P.n_tiles * (plan.samples ? (int)spp : 1);
+
+    L.lstk = c->opt_lstk ? c->opt_lstk : PT_STACK_CAP;   // any depth <= 64 works with every LDS window: deeper entries overflow
+    plan.n_top = t.has_bvh ? (int)std::min<uint32_t>((uint32_t)c->opt_top, L.walk >= 2 ? t.wide_top_layout : t.n_top_layout) : 0;
+    if (L.walk >= 1) plan.n_top = 0;  // only the while-while walk reads the LDS mirror
+    L.lds = lds_fit(plan.n_top, L.lstk, PT_BLOCK);
+    plan.sph_tab = -1;
+    if (persistent && c->opt_sph_lds) {   // sphere table behind the stacks (and the LDS mirror)
+        plan.sph_tab = (int)(L.lds / 4);
+        L.lds += 15 * PT_KSPHERES * 4;
     }
-    if (spp > 1 || wavefront || sd || moments_dev) {   // the moments are the fold's job: such a call always has a sample buffer
-        const size_t need = (size_t)spp * (size_t)p->width * (size_t)p->height * 3 * sizeof(float);
-        float*& buf = sd ? sd->samples : c->d_samples;
-        size_t& have = sd ? sd->samples_bytes : c->samples_bytes;
-        if (need > have) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));   // every path kernel has a fold behind it on this stream
-            (void)hipFree(buf);
-            buf = nullptr;
-            have = 0;
-            HIP_TRY(c, hipMalloc((void**)&buf, need));
-            have = need;
-        }
-        P.samples = buf;
+    // queue granularity: 64-slot chunks when the launch has plenty of them per resident wave, smaller
+    // ones for small launches (an eighth of a 1080p frame per GPU is ~4 000 tiles for ~5 000 waves)
+    const long slots = (long)plan.work_tiles * 64, waves = (long)c->n_cu * 20;
+    plan.chunk = slots / 64 >= 4 * waves ? 64 : (slots / 32 >= 4 * waves ? 32 : 16);
+    const int waves_per_block = PT_BLOCK / 64;
+    L.count = c->opt_counters != 0;
+    L.occ = c->opt_occ;
+    L.blocks = (plan.work_tiles + waves_per_block - 1) / waves_per_block;
+    L.work_blocks = (int)((slots + plan.chunk * waves_per_block - 1) / (plan.chunk * waves_per_block));
+    L.n_cu = c->n_cu;
+    L.moments = moments;
+    return PT_OK;
+}
+
+// the next side slot; its stream, events and queue counters are made on first use
+static int side_acquire(pt_ctx* c, pt_ctx::Side*& sd) {
+    sd = &c->side[c->side_next];
+    c->side_next ^= 1;   // (flipped before the creations below can fail: the slot is then made by its next turn)
+    if (sd->stream) return PT_OK;
+    // a priority of its own: ROCm maps the streams of one priority onto a few hardware queues round-robin (four
+    // by default, GPU_MAX_HW_QUEUES), and a side stream that shares a hardware queue with the caller's stream or
+    // with the other side stream runs in order behind it — no overlap and a 5-9 % LOSS (measured with a second
+    // context alive).  The high-priority class has queues of its own.
+    int prio_lo = 0, prio_hi = 0;
+    HIP_TRY(c, hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+    HIP_TRY(c, hipStreamCreateWithPriority(&sd->stream, hipStreamNonBlocking, prio_hi));
+    HIP_TRY(c, hipEventCreateWithFlags(&sd->traced, hipEventDisableTiming));
+    HIP_TRY(c, hipEventCreateWithFlags(&sd->folded, hipEventDisableTiming));
+    HIP_TRY(c, hipMalloc((void**)&sd->queue, PT_SHARDS * PT_SHARD_STRIDE * sizeof(unsigned int)));
+    return PT_OK;
+}
+
+// the sample buffer of the call, the side slot's own or the context's, grown to `need` bytes
+static int samples_reserve(pt_ctx* c, pt_ctx::Side* sd, size_t need, KParams& P) {
+    float*& buf = sd ? sd->samples : c->d_samples;
+    size_t& have = sd ? sd->samples_bytes : c->samples_bytes;
+    if (need > have) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));   // every path kernel has a fold behind it on this stream
+        (void)hipFree(buf);
+        buf = nullptr;
+        have = 0;
+        HIP_TRY(c, hipMalloc((void**)&buf, need));
+        have = need;
     }
-    P.smp_ss = (unsigned long long)p->width * (unsigned long long)p->height;
-    P.smp_ps = 1u;
-    P.sgroup_log2 = 0u;
-    if (P.samples && (wavefront || persistent)) {   // the samples of a pixel side by side in the slot order and in the sample buffer
-        P.sgroup_log2 = wave_sample_group_log2(spp, c->opt_wave_samples);
-        if (P.sgroup_log2) {
-            P.smp_ss = 1ull;
-            P.smp_ps = spp;
-        }
+    P.samples = buf;
+    return PT_OK;
+}
+
+// the side stream's path kernel may start once the caller's earlier work has been SUBMITTED and needs the scene only, but it must not
+// overwrite its sample buffer before the fold that last read it is done, nor read a light list or a refit tree still being written
+static int side_order(pt_ctx* c, pt_ctx::Side* sd, bool reads_lights) {
+    if (sd->fold_pending) HIP_TRY(c, hipStreamWaitEvent(sd->stream, sd->folded, 0));
+    if (reads_lights && sd->lights_seen != c->lights_gen) {   // the light list was (re)written on the caller's stream
+        HIP_TRY(c, hipStreamWaitEvent(sd->stream, c->lights_ev, 0));
+        sd->lights_seen = c->lights_gen;
     }
-    const int work_tiles = P.n_tiles * (P.samples ? (int)spp : 1);
-    // the stream the path kernel runs on: it may start once the caller's earlier work has been SUBMITTED, needs the
-    // scene only, and must not overwrite its sample buffer before the fold that last read it is done
-    hipStream_t trace_stream = c->stream;
-    if (sd) {
-        trace_stream = sd->stream;
-        if (sd->fold_pending) HIP_TRY(c, hipStreamWaitEvent(sd->stream, sd->folded, 0));
-        if (P.tri_lights && sd->lights_seen != c->lights_gen) {   // the light list was (re)written on the caller's stream
-            HIP_TRY(c, hipStreamWaitEvent(sd->stream, c->lights_ev, 0));
-            sd->lights_seen = c->lights_gen;
-        }
-        if (sd->geom_seen != c->geom_gen) {   // the tree was refit on the caller's stream (pt_refit_bvh)
-            HIP_TRY(c, hipStreamWaitEvent(sd->stream, c->geom_ev, 0));
-            sd->geom_seen = c->geom_gen;
-        }
+    if (sd->geom_seen != c->geom_gen) {   // the tree was refit on the caller's stream (pt_refit_bvh)
+        HIP_TRY(c, hipStreamWaitEvent(sd->stream, c->geom_ev, 0));
+        sd->geom_seen = c->geom_gen;
     }
+    return PT_OK;
+}
+
+// the plan's share of the kernel arguments: where the samples go, the LDS layout, the persistent kernel's queue
+static void apply_plan(const pt_ctx* c, const CallPlan& plan, const pt_ctx::Side* sd, KParams& P) {
+    P.sgroup_log2 = plan.sgroup_log2;
+    if (plan.sgroup_log2) {
+        P.smp_ss = 1ull;
+        P.smp_ps = P.spp;
+    }
+    P.sc.stack_n = plan.L.lstk;
+    P.sc.top_base = plan.L.walk >= 2 ? P.sc.wide_root : 0;
+    P.sc.n_top = plan.n_top;
+    P.sph_tab = plan.sph_tab;
+    P.chunk = plan.chunk;
+    if (plan.kernel != PT_KERNEL_PERSISTENT) return;
+    P.queue = sd ? sd->queue : c->d_queue;
+    P.batch = c->opt_batch;
+    // refill <= batch, or a wave can spin: the walk returns at once because `batch` lanes wait,
+    // none of them has anything to shade and the idle ones are too few to trigger a refill
+    P.refill = c->opt_refill < c->opt_batch ? c->opt_refill : c->opt_batch;
+    P.vote_node = c->opt_vote_node;
+    P.vote_rec = c->opt_vote_rec;
+}
+}  // namespace ptmi
+
+int pt_render(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, const pt_camera* cam, const pt_params* p, uint32_t spp) {
+    return pt_render_moments(c, accum_dev, rgba_dev, nullptr, cam, p, spp);
+}
+
+// pt_render's body; moments_dev != NULL: the fold also keeps the luminance moments of the samples (DESIGN.md §10 f7)
+int pt_render_moments(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, float* moments_dev, const pt_camera* cam, const pt_params* p,
+                      uint32_t spp) {
+    int rc = check_call(c, accum_dev, rgba_dev, cam, p, spp);
+    if (rc != PT_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((rc = refresh_tri_lights(c, p)) != PT_OK) return rc;
+    KParams P;
+    if ((rc = fill_params(c, accum_dev, rgba_dev, cam, p, spp, P)) != PT_OK || P.n_tiles <= 0) return rc;
+    CallPlan plan;
+    if ((rc = plan_call(c, p, P, spp, moments_dev != nullptr, plan)) != PT_OK) return rc;
+    const int probe = plan.probe;
+
+    // the buffers the plan asks for
+    pt_ctx::Side* sd = nullptr;
+    if (plan.side && (rc = side_acquire(c, sd)) != PT_OK) return rc;
+    if (plan.samples && (rc = samples_reserve(c, sd, (size_t)spp * (size_t)p->width * (size_t)p->height * 3 * sizeof(float), P)) != PT_OK) return rc;
+    if (sd && (rc = side_order(c, sd, P.tri_lights != nullptr)) != PT_OK) return rc;
+    hipStream_t trace_stream = sd ? sd->stream : c->stream;   // the stream the path kernel runs on
+    apply_plan(c, plan, sd, P);
 
     if (c->opt_counters) HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, PT_CNT_N * sizeof(unsigned long long), c->stream));
     if (probe >= 0 && (probe & 1)) {   // a trial of the pipeline: its path records are allocated BEFORE the timed span
-        const int rc = wave_reserve(c, P, work_tiles);
+        rc = wave_reserve(c, P, plan.work_tiles);
         if (rc != PT_OK) return rc;
     }
-    if (probe >= 0) HIP_TRY(c, hipEventRecord(pick->e[2 * probe], c->stream));
+    if (probe >= 0) HIP_TRY(c, hipEventRecord(plan.pick->e[2 * probe], c->stream));
     if (c->opt_timing) {
         HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
         c->stage_used = 0;
         if (stage_mark(c, PT_STAGE_NONE) != PT_OK) return PT_ERR_DEVICE;
     }
-    const int lstk = c->opt_lstk ? c->opt_lstk : PT_STACK_CAP;   // any depth <= 64 works with every LDS window: deeper entries overflow
-    P.sc.stack_n = lstk;
-    P.sc.wide_root = (int)c->wide_root;
-    P.sc.top_base = walk >= 2 ? (int)c->wide_root : 0;
-    P.sc.n_top = c->has_bvh ? (int)std::min<uint32_t>((uint32_t)c->opt_top, walk >= 2 ? c->wide_top_layout : c->n_top_layout) : 0;
-    if (walk >= 1) P.sc.n_top = 0;  // only the while-while walk reads the LDS mirror
-    size_t lds = lds_bytes(P.sc.n_top, lstk, PT_BLOCK);
-    while (lds > 160 * 1024 && P.sc.n_top > 0) {  // deep tree: give the LDS to the stack first
-        P.sc.n_top /= 2;
-        lds = lds_bytes(P.sc.n_top, lstk, PT_BLOCK);
-    }
-    P.sph_tab = -1;
-    if (persistent && c->opt_sph_lds) {   // sphere table behind the stacks (and the LDS mirror)
-        P.sph_tab = (int)(lds / 4);
-        lds += 15 * PT_KSPHERES * 4;
-    }
-    if (persistent) {
-        P.queue = c->d_queue;
-        P.batch = c->opt_batch;
-        // refill <= batch, or a wave can spin: the walk returns at once because `batch` lanes wait,
-        // none of them has anything to shade and the idle ones are too few to trigger a refill
-        P.refill = c->opt_refill < c->opt_batch ? c->opt_refill : c->opt_batch;
-        P.vote_node = c->opt_vote_node;
-        P.vote_rec = c->opt_vote_rec;
-        if (sd) P.queue = sd->queue;
-        HIP_TRY(c, hipMemsetAsync(P.queue, 0, PT_SHARDS * PT_SHARD_STRIDE * sizeof(unsigned int), trace_stream));
-    }
-    // queue granularity: 64-slot chunks when the launch has plenty of them per resident wave, smaller
-    // ones for small launches (an eighth of a 1080p frame per GPU is ~4 000 tiles for ~5 000 waves)
-    {
-        const long slots = (long)work_tiles * 64, waves = (long)c->n_cu * 20;
-        P.chunk = slots / 64 >= 4 * waves ? 64 : (slots / 32 >= 4 * waves ? 32 : 16);
-    }
-    LaunchCfg L;
-    L.count = c->opt_counters != 0;
-    L.occ = c->opt_occ;
-    L.lstk = lstk;
-    L.walk = walk;
-    L.lds = lds;
-    L.blocks = (work_tiles + waves_per_block - 1) / waves_per_block;
-    L.work_blocks = (int)(((long)work_tiles * 64 + P.chunk * (PT_BLOCK / 64) - 1) / (P.chunk * (PT_BLOCK / 64)));
-    L.n_cu = c->n_cu;
-    L.moments = moments_dev != nullptr;
     bool folded = false;
-    if (wavefront) {
-        const int rc = render_wavefront(c, P, L, work_tiles, folded);
+    if (plan.kernel == PT_KERNEL_WAVEFRONT) {
+        rc = render_wavefront(c, P, plan.L, plan.work_tiles, folded);
         if (rc != PT_OK) return rc;
-    } else if (persistent) {
-        HIP_TRY(c, launch_persist(L, P, trace_stream));
+    } else if (plan.kernel == PT_KERNEL_PERSISTENT) {
+        HIP_TRY(c, hipMemsetAsync(P.queue, 0, PT_SHARDS * PT_SHARD_STRIDE * sizeof(unsigned int), trace_stream));
+        HIP_TRY(c, launch_persist(plan.L, P, trace_stream));
         if (stage_mark(c, PT_STAGE_FRAME) != PT_OK) return PT_ERR_DEVICE;
     } else {
-        HIP_TRY(c, launch_mega(L, P, trace_stream));
+        HIP_TRY(c, launch_mega(plan.L, P, trace_stream));
         if (stage_mark(c, PT_STAGE_FRAME) != PT_OK) return PT_ERR_DEVICE;
     }
     if (sd) {   // the fold (accumulator, display words) waits for the path kernel on the caller's stream
@@ -891,7 +882,7 @@ int pt_render_moments(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, float* mo
         HIP_TRY(c, hipEventRecord(sd->folded, c->stream));
         sd->fold_pending = true;
     }
-    if (probe >= 0) HIP_TRY(c, hipEventRecord(pick->e[2 * probe + 1], c->stream));
+    if (probe >= 0) HIP_TRY(c, hipEventRecord(plan.pick->e[2 * probe + 1], c->stream));
     if (c->opt_timing) { HIP_TRY(c, hipEventRecord(c->ev1, c->stream)); c->timed = true; }
     return PT_OK;
 }
@@ -950,11 +941,11 @@ __global__ void __launch_bounds__(256) k_tree_cost(const float4* __restrict__ it
 
 namespace ptmi {
 static int tree_cost_impl(pt_ctx* c, double* node_visits, double* tri_tests) {
-    const unsigned n_blocks = (unsigned)((c->n_wide + 255) / 256);
+    const unsigned n_blocks = (unsigned)((c->tree.n_wide + 255) / 256);
     const size_t n_out = 1 + 2 * (size_t)n_blocks;
     double* d_out = nullptr;
     HIP_TRY(c, hipMalloc((void**)&d_out, n_out * sizeof(double)));
-    hipLaunchKernelGGL(k_tree_cost, dim3(n_blocks), dim3(256), 0, c->stream, c->d_nodes, c->wide_root, (uint32_t)c->n_wide, d_out);
+    hipLaunchKernelGGL(k_tree_cost, dim3(n_blocks), dim3(256), 0, c->stream, c->tree.d_nodes, c->tree.wide_root, (uint32_t)c->tree.n_wide, d_out);
     hipError_t e = hipGetLastError();
     std::vector<double> h(n_out, 0.0);
     if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_out, n_out * sizeof(double), hipMemcpyDeviceToHost, c->stream);
@@ -972,8 +963,8 @@ static int tree_cost_impl(pt_ctx* c, double* node_visits, double* tri_tests) {
 
 int pt_tree_cost(pt_ctx* c, double* node_visits, double* tri_tests) {
     if (!c || !node_visits || !tri_tests) return fail(c, PT_ERR_INVALID, "pt_tree_cost: null argument");
-    if (!c->has_bvh || c->wide_root == 0 || c->n_wide == 0) return fail(c, PT_ERR_NO_SCENE, "pt_tree_cost: no 4-wide tree on this context");
-    if (c->records_woop) return fail(c, PT_ERR_UNSUPPORTED, "pt_tree_cost: reads the Moller-Trumbore records' leaf terminators");
+    if (!c->tree.has_bvh || c->tree.wide_root == 0 || c->tree.n_wide == 0) return fail(c, PT_ERR_NO_SCENE, "pt_tree_cost: no 4-wide tree on this context");
+    if (c->tree.records_woop) return fail(c, PT_ERR_UNSUPPORTED, "pt_tree_cost: reads the Moller-Trumbore records' leaf terminators");
     HIP_TRY(c, hipSetDevice(c->device));
     return tree_cost_impl(c, node_visits, tri_tests);
 }
@@ -993,22 +984,21 @@ int pt_auto_choice(pt_ctx* c, int* kernel, float* ms_persistent, float* ms_wavef
 
 int pt_trace_rays(pt_ctx* c, const float* rays_dev, size_t n, int cull, float* t_dev, int32_t* tri_dev, float* normal_dev) {
     if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
-    if (!c->has_bvh) return fail(c, PT_ERR_NO_SCENE, "pt_trace_rays: no BVH uploaded");
-    if (c->records_woop) return fail(c, PT_ERR_UNSUPPORTED, "pt_trace_rays: the ray-batch kernel reads Moller-Trumbore records (upload with PT_OPT_TRI_TEST 0)");
+    if (!c->tree.has_bvh) return fail(c, PT_ERR_NO_SCENE, "pt_trace_rays: no BVH uploaded");
+    if (c->tree.records_woop) return fail(c, PT_ERR_UNSUPPORTED, "pt_trace_rays: the ray-batch kernel reads Moller-Trumbore records (upload with PT_OPT_TRI_TEST 0)");
     if (n == 0) return PT_OK;
     if (!rays_dev || !t_dev || !tri_dev) return fail(c, PT_ERR_INVALID, "pt_trace_rays: null argument");
     HIP_TRY(c, hipSetDevice(c->device));
     KScene sc;
     std::memset(&sc, 0, sizeof sc);
-    sc.nodes = c->d_nodes; sc.tris = c->d_tris; sc.spheres = nullptr; sc.n_spheres = 0; sc.has_bvh = 1;
+    sc.nodes = c->tree.d_nodes; sc.tris = c->tree.d_tris; sc.spheres = nullptr; sc.n_spheres = 0; sc.has_bvh = 1;
     if (c->opt_timing) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
     const float4* r4 = (const float4*)rays_dev;
     sc.stack_n = PT_STACK_CAP;
     sc.top_base = 0;
-    sc.wide_root = (int)c->wide_root;
-    sc.n_top = (int)std::min<uint32_t>((uint32_t)c->opt_top, c->n_top_layout);
-    size_t lds = lds_bytes(sc.n_top, sc.stack_n, PT_BLOCK_RAYS);
-    while (lds > 160 * 1024 && sc.n_top > 0) { sc.n_top /= 2; lds = lds_bytes(sc.n_top, sc.stack_n, PT_BLOCK_RAYS); }
+    sc.wide_root = (int)c->tree.wide_root;
+    sc.n_top = (int)std::min<uint32_t>((uint32_t)c->opt_top, c->tree.n_top_layout);
+    const size_t lds = lds_fit(sc.n_top, sc.stack_n, PT_BLOCK_RAYS);
     HIP_TRY(c, launch_rays(sc, lds, r4, n, cull, t_dev, tri_dev, normal_dev, c->stream));
     if (c->opt_timing) { HIP_TRY(c, hipEventRecord(c->ev1, c->stream)); c->timed = true; }
     return PT_OK;
