@@ -95,6 +95,7 @@ struct pt_ctx {
     int opt_fuse_stages = 1;     // bounce 0's shade in the packet walk's launch, the fold in the last shade launch (PT_OPT_FUSE_STAGES)
     int opt_last_anyhit = 1;     // the last segment as a sphere-bounded any-hit query: 0 off, 1 product launches, 2 instrumented too (PT_OPT_LAST_ANYHIT)
     int opt_root_cull = 1;       // new rays the root node step turns away stay out of the extend queue: 0 off, 1 product launches, 2 instrumented too (PT_OPT_ROOT_CULL)
+    int opt_root_entry = 1;      // ... and the walkers' records carry the root step's result, the extend launches start below the root: 0 off, 1 product launches, 2 instrumented too (PT_OPT_ROOT_ENTRY)
     // PT_KERNEL_AUTO: which stage layout is faster depends on the workload (long paths and many samples per call:
     // the stage-split pipeline; short paths or few samples: the persistent kernel), so the first FOUR calls of a
     // configuration are timed trials, two per layout, alternating (HIP events on the stream, buffers allocated before the

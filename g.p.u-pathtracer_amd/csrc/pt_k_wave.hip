@@ -83,8 +83,13 @@ __device__ __forceinline__ float wf_anyhit_start(float ts) {
 // ray's nearest sphere in the ray's hit slot, and all the picture still needs is whether a triangle is hit at t <= ts.  The
 // lane starts the walk bounded by the next float above ts and leaves at the first record it accepts (trav_run_wide<.., ANY>);
 // it writes t = 0 over ts when there is one and leaves the slot alone otherwise.
-template <bool COUNT, int OCC, int LSTK, bool FIRST, bool ANY = false>
+// ENTRY (PT_OPT_ROOT_ENTRY; never FIRST): the record carries what the walk's node step on the root found for its ray (the entry code
+// of pt_kernels.h, left by the shade lane that made the ray), so the lane starts BEHIND that step: the far children on the stack, in
+// the order the step pushes them, and the nearest one — a node or a leaf — as its item.  Stack, item and h.t are the walk's own after
+// its first step, and everything after it is the same bit for bit.
+template <bool COUNT, int OCC, int LSTK, bool FIRST, bool ANY = false, bool ENTRY = false>
 __global__ void __launch_bounds__(PT_BLOCK, OCC) k_wf_extend(const KParams P) {
+    static_assert(!(FIRST && ENTRY), "bounce 0's rays come from the camera: nobody ran their root step");
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     TravOverflow<LSTK> stk_ovf;
@@ -107,6 +112,12 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_wf_extend(const KParams P) {
     ts.h = pt_no_hit();
     TravCount tc;
     uint32_t n_rays = 0, it_begin = 0, act_begin = 0, it_loop = 0;
+    int root_l0 = 0, root_l1 = 0, root_l2 = 0, root_l3 = 0;   // ENTRY: the root's four links (wave-uniform: scalar loads, once)
+    if (ENTRY) {
+        const float4 q2 = pt_uld4(P.sc.nodes, P.sc.wide_root + 2), q3 = pt_uld4(P.sc.nodes, P.sc.wide_root + 3);   // (wide_node_decode)
+        root_l0 = __float_as_int(q2.z); root_l1 = __float_as_int(q2.w);
+        root_l2 = __float_as_int(q3.x); root_l3 = __float_as_int(q3.y);
+    }
 
     for (;;) {
         if (COUNT) it_loop++;
@@ -141,7 +152,7 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_wf_extend(const KParams P) {
                 const uint32_t take = min((uint32_t)n_idle - served, end - next);
                 if (!live && rank >= served && rank < served + take) {
                     idx = next + (rank - served);
-                    float bound = PT_F32_MAX;
+                    float bound = PT_F32_MAX, b_w = 0.f;
                     if (FIRST) {
                         uint32_t s_idx = 0;
                         int px = 0, py = 0;
@@ -157,10 +168,23 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_wf_extend(const KParams P) {
                         if (ANY) bound = pt_sld1((const float*)(P.wf.hit + idx));
                         o = V3(a.x, a.y, a.z);
                         d = V3(a.w, b.x, b.y);
+                        b_w = b.w;
                         live = true;
                     }
                     if (live) trav_begin(ts, o, d, stk, P.sc.wide_root);
                     if (ANY) ts.h.t = wf_anyhit_start(bound);
+                    if constexpr (ENTRY) {   // what the root step would leave: trav_run_wide's pushes, far to near, then the nearest child
+                        const uint32_t code = __float_as_uint(b_w) >> PT_REC_ENTRY_SHIFT, n = pt_entry_count(code);
+                        auto link = [&](uint32_t k) {   // (wide_link of the root)
+                            const uint32_t c = pt_entry_child(code, k);
+                            return c == 0u ? root_l0 : (c == 1u ? root_l1 : (c == 2u ? root_l2 : root_l3));
+                        };
+                        if (n == 4u) { ts.sp++; stk.put(ts.sp, link(3)); }
+                        if (n >= 3u) { ts.sp++; stk.put(ts.sp, link(2)); }
+                        if (n >= 2u) { ts.sp++; stk.put(ts.sp, link(1)); }
+                        ts.node = link(0);
+                        if (COUNT && ts.node < 0) tc.leaves++;
+                    }
                 }
                 next += take;
                 served += take;
@@ -315,10 +339,13 @@ __device__ __forceinline__ float2 wf_sphere_bound(const KParams& P, const PathSt
 // child.  That lane would pop the sentinel and report pt_no_hit(), or leave ts in place; here the lane that made the ray runs the
 // step itself — the walk's own functions on the root fetched once per wave with scalar loads, so the verdict is the walk's bit for
 // bit — and the extend launch only draws a region's first n_walk records.  Every lane of the block calls it.
+// PT_OPT_ROOT_ENTRY: the rest of that step is kept too — the keys sorted as the walk sorts them, so the order is the walk's, ties
+// included — as the walker's entry code in `entry`, already at its place in ray1.w (0 without the option, and for the walk-free).
 template <bool BOUND>
 __device__ __forceinline__ int wf_survivor_slot(const KParams& P, bool alive, const PathState& ps, float ts, bool& walk_free, int& n_walk,
-                                                int& total, int* s_cnt, int* s_cnt_free) {
+                                                int& total, int* s_cnt, int* s_cnt_free, uint32_t& entry) {
     walk_free = false;
+    entry = 0u;
     if (P.wf.root_cull) {   // (wave-uniform)
         const WideNode root = wide_node_load_uniform(P.sc, P.sc.wide_root);
         if (alive) {
@@ -327,6 +354,11 @@ __device__ __forceinline__ int wf_survivor_slot(const KParams& P, bool alive, co
             uint32_t key[4];
             wide_node_keys_raw(root, s.idx, s.idy, s.idz, s.oodx, s.oody, s.oodz, BOUND ? wf_anyhit_start(ts) : PT_F32_MAX, key);
             walk_free = (key[0] & key[1] & key[2] & key[3]) == 0xffffffffu;
+            if (P.wf.root_entry && !walk_free) {   // (the flag is wave-uniform)
+                wide_sort4(key);   // the hit children first, nearest first
+                const uint32_t n = 1u + (key[1] != 0xffffffffu ? 1u : 0u) + (key[2] != 0xffffffffu ? 1u : 0u) + (key[3] != 0xffffffffu ? 1u : 0u);
+                entry = pt_entry_pack(n, key[0], key[1], key[2]) << PT_REC_ENTRY_SHIFT;
+            }
         }
     }
     const int r = PT_SURVIVOR_RANK(P, alive && !walk_free, ps, n_walk, s_cnt);
@@ -393,7 +425,7 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
                 ps.nee_mask = (pix >> PT_REC_PIXEL_BITS) | ((sn >> PT_REC_LIGHT_BIT) << 8);
                 pix &= (1u << PT_REC_PIXEL_BITS) - 1u;
                 sn &= (1u << PT_REC_LIGHT_BIT) - 1u;
-            }
+            } else if (P.wf.root_entry) sn &= (1u << PT_REC_ENTRY_SHIFT) - 1u;   // (the entry code was the walk's)
             s_idx = sn >> PT_REC_DRAW_BITS;
             ps.mask = V3(pt_sld1(P.wf.mask_in + i), pt_sld1(P.wf.mask_in + (size_t)P.wf.cap + i), pt_sld1(P.wf.mask_in + 2 * (size_t)P.wf.cap + i));
             ps.accu = V3(0.f, 0.f, 0.f);   // this segment's emission only: the running sum lives in the sample buffer
@@ -444,12 +476,13 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
     }
     int n_walk, total;
     bool walk_free;
-    const int r = wf_survivor_slot<BOUND>(P, alive, ps, bound.x, walk_free, n_walk, total, s_cnt, s_cnt_free);
+    uint32_t entry;
+    const int r = wf_survivor_slot<BOUND>(P, alive, ps, bound.x, walk_free, n_walk, total, s_cnt, s_cnt_free, entry);
     if (alive) {
         const size_t j = (size_t)region * PT_REGION + (size_t)r;
         pt_sst4(P.wf.ray0_out + j, make_float4(ps.o.x, ps.o.y, ps.o.z, ps.d.x));
         pt_sst4(P.wf.ray1_out + j, make_float4(ps.d.y, ps.d.z, __uint_as_float(NEE ? (pix | ((ps.nee_mask & 0xffu) << PT_REC_PIXEL_BITS)) : pix),
-                                              __uint_as_float((s_idx << PT_REC_DRAW_BITS) | ps.rng.n | (NEE ? (ps.nee_mask >> 8) << PT_REC_LIGHT_BIT : 0u))));
+                                              __uint_as_float((s_idx << PT_REC_DRAW_BITS) | ps.rng.n | (NEE ? (ps.nee_mask >> 8) << PT_REC_LIGHT_BIT : entry))));
         pt_sst1(P.wf.mask_out + j, ps.mask.x);
         pt_sst1(P.wf.mask_out + (size_t)P.wf.cap + j, ps.mask.y);
         pt_sst1(P.wf.mask_out + 2 * (size_t)P.wf.cap + j, ps.mask.z);
@@ -479,7 +512,8 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade_last_any(const KParams P)
         const float4 b = pt_sld4(P.wf.ray1_in + i);
         const float2 hh = pt_sld2(P.wf.hit + i);
         const v3 mask = V3(pt_sld1(P.wf.mask_in + i), pt_sld1(P.wf.mask_in + (size_t)P.wf.cap + i), pt_sld1(P.wf.mask_in + 2 * (size_t)P.wf.cap + i));
-        const uint32_t pix = __float_as_uint(b.z), s_idx = __float_as_uint(b.w) >> PT_REC_DRAW_BITS;
+        const uint32_t pix = __float_as_uint(b.z);
+        const uint32_t s_idx = (__float_as_uint(b.w) & (P.wf.root_entry ? (1u << PT_REC_ENTRY_SHIFT) - 1u : ~0u)) >> PT_REC_DRAW_BITS;
         float* smp = pt_sample_ptr(P, s_idx, (size_t)pix);
         const int sph = __float_as_int(hh.y);
         tri_hit = hh.x == 0.0f;
@@ -535,11 +569,12 @@ __global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet_shade(const KP
     if (BOUND && alive) bound = wf_sphere_bound(P, ps);
     int n_walk, total;
     bool walk_free;
-    const int r = wf_survivor_slot<BOUND>(P, alive, ps, bound.x, walk_free, n_walk, total, s_cnt, s_cnt_free);
+    uint32_t entry;
+    const int r = wf_survivor_slot<BOUND>(P, alive, ps, bound.x, walk_free, n_walk, total, s_cnt, s_cnt_free, entry);
     if (alive) {
         const size_t j = (size_t)region * PT_REGION + (size_t)r;
         pt_sst4(P.wf.ray0_out + j, make_float4(ps.o.x, ps.o.y, ps.o.z, ps.d.x));
-        pt_sst4(P.wf.ray1_out + j, make_float4(ps.d.y, ps.d.z, __uint_as_float(pix), __uint_as_float((s_idx << PT_REC_DRAW_BITS) | ps.rng.n)));
+        pt_sst4(P.wf.ray1_out + j, make_float4(ps.d.y, ps.d.z, __uint_as_float(pix), __uint_as_float((s_idx << PT_REC_DRAW_BITS) | ps.rng.n | entry)));
         pt_sst1(P.wf.mask_out + j, ps.mask.x);
         pt_sst1(P.wf.mask_out + (size_t)P.wf.cap + j, ps.mask.y);
         pt_sst1(P.wf.mask_out + 2 * (size_t)P.wf.cap + j, ps.mask.z);
@@ -671,6 +706,11 @@ struct WavePlan {
     // PT_OPT_ROOT_CULL: the shade launches keep the survivors whose new ray the tree's root turns away out of the next extend launch's
     // queue (wf_survivor_slot).  Instrumented launches: with the value 2 only.
     bool root_cull;
+    // PT_OPT_ROOT_ENTRY: ... and leave the rest of that node step in the walkers' records as an entry code, from which the extend launches
+    // of bounces >= 1 start below the root (k_wf_extend<.., ENTRY>).  Only with root_cull, without PT_FLAG_NEE (its shadow records carry
+    // no code, and ray1.w's top bit is taken) and when spp fits the narrowed sample field; every other call keeps the plain record.
+    // Instrumented launches: with the value 2 only.
+    bool root_entry;
     WaveExtend extend(uint32_t b, uint32_t depth) const {
         if (b == 0) return fuse_first ? EXT_FUSED : packet ? EXT_PACKET : EXT_FIRST;
         return anyhit && b + 1 == depth ? EXT_ANY : EXT_CLOSEST;
@@ -694,6 +734,7 @@ static WavePlan wave_plan(const pt_ctx* c, const KParams& P, const LaunchCfg& L,
     p.anyhit = (L.count ? c->opt_last_anyhit == 2 : c->opt_last_anyhit >= 1) && P.depth >= 2 && !nee && !P.tri_matid && tri_dark &&
                P.sc.n_spheres <= PT_KSPHERES && !c->tree.records_woop;
     p.root_cull = L.count ? c->opt_root_cull == 2 : c->opt_root_cull >= 1;
+    p.root_entry = p.root_cull && !nee && P.spp < PT_REC_MAX_SAMPLES_ENTRY && (L.count ? c->opt_root_entry == 2 : c->opt_root_entry >= 1);
     return p;
 }
 
@@ -719,13 +760,15 @@ static hipError_t launch_extend(const WavePlan& p, WaveExtend kind, const KParam
     return with_bool(p.count, [&](auto count) {
         return with_bool(p.deep_stack, [&](auto deep) {
             constexpr int OCC = deep() ? 6 : 8, LSTK = deep() ? 24 : 16;
-            auto go = [&](auto first, auto any) {
-                return launch_resident(k_wf_extend<count(), OCC, LSTK, first(), any()>, (size_t)LSTK * PT_BLOCK * 4, blocks_per_cu, L.n_cu,
+            auto go = [&](auto first, auto any, auto entry) {
+                return launch_resident(k_wf_extend<count(), OCC, LSTK, first(), any(), entry()>, (size_t)LSTK * PT_BLOCK * 4, blocks_per_cu, L.n_cu,
                                        (size_t)Q.wf.n_regions, s, Q);
             };
-            if (kind == EXT_FIRST) return go(std::true_type{}, std::false_type{});
-            if (kind == EXT_ANY) return go(std::false_type{}, std::true_type{});
-            return go(std::false_type{}, std::false_type{});
+            if (kind == EXT_FIRST) return go(std::true_type{}, std::false_type{}, std::false_type{});
+            return with_bool(p.root_entry, [&](auto entry) {
+                if (kind == EXT_ANY) return go(std::false_type{}, std::true_type{}, entry);
+                return go(std::false_type{}, std::false_type{}, entry);
+            });
         });
     });
 }
@@ -762,6 +805,7 @@ int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles, 
     folded = plan.fold_lp != 0;
     P.wf.nee = w.nee ? 1 : 0;
     P.wf.root_cull = plan.root_cull ? 1 : 0;
+    P.wf.root_entry = plan.root_entry ? 1 : 0;
     if (w.nee) {
         P.wf.s_ray0 = (float4*)buf.nee;
         P.wf.s_ray1 = (float4*)(buf.nee + w.b_ray);

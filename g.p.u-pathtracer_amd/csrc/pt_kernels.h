@@ -42,6 +42,7 @@ struct KScene {
 // (ballot + prefix count, no global atomics) and the order of the records is deterministic.  PT_OPT_ROOT_CULL: the records whose
 // ray the tree's root turns away come last, walk[region] counts the ones before them, and only those are walked.
 //   ray0[i] = (o.x, o.y, o.z, d.x)   ray1[i] = (d.y, d.z, bits(pixel), bits(sample << PT_REC_DRAW_BITS | rng draws))
+//             (PT_OPT_ROOT_ENTRY: ray1.w = bits(entry code << PT_REC_ENTRY_SHIFT | sample << PT_REC_DRAW_BITS | rng draws), below)
 //   mask    = three planes [cap] (x, y, z), not stored for the first bounce (1, 1, 1)
 //   hit[i]  = (t, bits(float4 index of the winning record)); t = F32_MAX: no triangle
 // PT_FLAG_NEE: the sphere bits of nee_mask ride above the pixel (ray1.z), its triangle-light bit above the sample (ray1.w).
@@ -52,6 +53,43 @@ constexpr uint32_t PT_REC_PIXEL_BITS = 24;   // ray1.z, PT_FLAG_NEE: the pixel, 
 // exclusive limits: draws per path, samples per call without / with PT_FLAG_NEE
 constexpr uint32_t PT_REC_MAX_DRAWS = 1u << PT_REC_DRAW_BITS, PT_REC_MAX_SAMPLES = 1u << (32 - PT_REC_DRAW_BITS),
                    PT_REC_MAX_SAMPLES_NEE = 1u << (PT_REC_LIGHT_BIT - PT_REC_DRAW_BITS);
+// PT_OPT_ROOT_ENTRY (KWave::root_entry; never with PT_FLAG_NEE): the top PT_REC_ENTRY_BITS of ray1.w hold the walker's ENTRY CODE, what the
+// walk's node step on the tree's root found for the record's ray — the shade lane that made the ray ran that step (PT_OPT_ROOT_CULL) —
+// and the sample number keeps the bits between.  A call whose spp does not fit them keeps the format above.
+constexpr uint32_t PT_REC_ENTRY_BITS = 8, PT_REC_ENTRY_SHIFT = 32 - PT_REC_ENTRY_BITS;
+constexpr uint32_t PT_REC_MAX_SAMPLES_ENTRY = 1u << (PT_REC_ENTRY_SHIFT - PT_REC_DRAW_BITS);   // exclusive, as the limits above
+// The entry code: the root's hit children nearest first, as wide_sort4 orders them — three 2-bit child numbers below (hit children - 1).
+// A walker has 1..4 hit children; with four the last one is the XOR of the other three (0 ^ 1 ^ 2 ^ 3 = 0).  The fields of children
+// that are not hit are not read.
+constexpr uint32_t pt_entry_pack(uint32_t n, uint32_t c0, uint32_t c1, uint32_t c2) {
+    return (c0 & 3u) | ((c1 & 3u) << 2) | ((c2 & 3u) << 4) | ((n - 1u) << 6);
+}
+constexpr uint32_t pt_entry_count(uint32_t code) { return (code >> 6) + 1u; }
+// the k-th nearest hit child, k < pt_entry_count(code)
+constexpr uint32_t pt_entry_child(uint32_t code, uint32_t k) {
+    return k < 3u ? (code >> (2u * k)) & 3u : (code ^ (code >> 2) ^ (code >> 4)) & 3u;
+}
+// every ordered selection of 1..4 of the four children (4 + 12 + 24 + 24 = 64) comes back from its code, and the code fits its field
+constexpr bool pt_entry_round_trips() {
+    uint32_t seen = 0;
+    for (uint32_t n = 1; n <= 4; n++)
+        for (uint32_t s = 0; s < 256; s++) {   // s: four 2-bit child numbers; the first n must differ
+            const uint32_t c[4] = {s & 3u, (s >> 2) & 3u, (s >> 4) & 3u, (s >> 6) & 3u};
+            bool distinct = true;
+            for (uint32_t i = 0; i < n; i++)
+                for (uint32_t j = i + 1; j < n; j++) distinct = distinct && c[i] != c[j];
+            bool rest_zero = true;   // (one representative per selection)
+            for (uint32_t i = n; i < 4; i++) rest_zero = rest_zero && c[i] == 0u;
+            if (!distinct || !rest_zero) continue;
+            const uint32_t code = pt_entry_pack(n, c[0], c[1], c[2]);
+            if (code >= (1u << PT_REC_ENTRY_BITS) || pt_entry_count(code) != n) return false;
+            for (uint32_t k = 0; k < n; k++)
+                if (pt_entry_child(code, k) != c[k]) return false;
+            seen++;
+        }
+    return seen == 64u;
+}
+static_assert(pt_entry_round_trips(), "the entry code of PT_OPT_ROOT_ENTRY");
 struct KWave {
     const float4* __restrict__ ray0_in;
     const float4* __restrict__ ray1_in;
@@ -80,6 +118,7 @@ struct KWave {
     int* __restrict__ s_cnt;
     int nee;                      // 1: ray1.z carries pixel | nee_mask << 24
     int root_cull;                // 1: this call's shade launches classify their survivors (PT_OPT_ROOT_CULL)
+    int root_entry;               // 1: ... and leave the walkers' entry codes in ray1.w, where the extend launches start from (PT_OPT_ROOT_ENTRY)
     uint32_t bounce;
 };
 

@@ -224,7 +224,7 @@ enum {
                                  (PT_OPT_COUNTERS) launches too: pt_get_counters then counts the shorter walk and
                                  pt_get_wave_stats [5] the rays of that launch (0 = it did not run); 0 = closest hit on every
                                  segment.  With 0 or 1 the counters are those of the closest-hit walk.  Same images            */
-    PT_OPT_ROOT_CULL = 30     /* PT_KERNEL_WAVEFRONT: a surviving path's new ray that the walk's own first node step would turn away
+    PT_OPT_ROOT_CULL = 30,    /* PT_KERNEL_WAVEFRONT: a surviving path's new ray that the walk's own first node step would turn away
                                  at the tree's root (no child box of the 4-wide root entered before t_max: the ray misses the mesh, or
                                  enters it beyond the sphere bound of PT_OPT_LAST_ANYHIT) is not queued for the next extend launch.
                                  The shade lane that made the ray runs that node step itself, packs such records behind the region's
@@ -232,6 +232,17 @@ enum {
                                  instrumented (PT_OPT_COUNTERS) launches too: pt_get_counters then lacks one node visit per such ray
                                  (`rays` still counts them) and pt_get_wave_stats [10] is their number; 0 = every survivor is
                                  queued.  With 0 or 1 the counters are those of the full queue.  Same images                     */
+    PT_OPT_ROOT_ENTRY = 33    /* PT_KERNEL_WAVEFRONT with PT_OPT_ROOT_CULL: the shade lane keeps the rest of that node step as well —
+                                 which of the root's four children the new ray enters, nearest first — as an 8-bit code in the
+                                 record's sample word, and the extend launches of the later bounces start every walk behind the
+                                 root: the far children on the stack, the nearest one as the first item, without fetching or testing
+                                 the root again.  Needs PT_OPT_ROOT_CULL on for the call, no PT_FLAG_NEE and spp < 4096 (the sample
+                                 number gives up eight bits); any other call keeps the plain record and walks from the root, with
+                                 every limit unchanged.  1 (default) = product launches do so; 2 = instrumented (PT_OPT_COUNTERS)
+                                 launches too (with PT_OPT_ROOT_CULL 2): pt_get_counters then lacks one more node visit per ray the
+                                 extend launches of bounces >= 1 drew (pt_get_wave_stats [7] is their number while bounce 0 is the
+                                 packet walk, PT_OPT_FIRST_WALK 1); 0 = every walk starts at the root.
+                                 With 0 or 1 the counters are unchanged.  Same images                                           */
 };
 
 /* CamInfo, GpuPathTracer/CpuStructs.hpp:19-28 (pitch/yaw/dirty/bias/enabled are host-only
