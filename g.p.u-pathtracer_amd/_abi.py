@@ -41,6 +41,12 @@ class DenoiseParams(C.Structure):
                 ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float)]
 
 
+class TemporalParams(C.Structure):
+    """pt_temporal_params — the reprojection of pt_temporal (extension, include/ptmi.h; 24 bytes)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("max_history", C.c_float),
+                ("plane_tolerance", C.c_float), ("normal_threshold", C.c_float), ("_pad", C.c_int32)]
+
+
 class CheckpointInfo(C.Structure):
     """pth_checkpoint_info (host/pthost.h)."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("next_frame", C.c_uint64),
@@ -114,6 +120,7 @@ PTMI_SYMBOLS = [
     ("pt_trace_rays", _i, [_vp, _vp, _sz, _i, _vp, _vp, _vp]),
     ("pt_render_aux", _i, [_vp, C.POINTER(Camera), C.POINTER(Params), _vp, _vp, _vp, _vp]),
     ("pt_denoise", _i, [_vp, C.POINTER(DenoiseParams), _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("pt_temporal", _i, [_vp, C.POINTER(TemporalParams), C.POINTER(Camera), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("pt_build_bvh", _i, [_vp, _vp, C.c_size_t, _vp, C.c_size_t]),
     ("pt_last_build_ms", _i, [_vp, C.POINTER(C.c_float)]),
     ("pt_refit_bvh", _i, [_vp, _vp, _sz, _vp]),

@@ -1,5 +1,6 @@
-// pt_denoise.hip — pt_render_aux (first-hit guide buffers) and pt_denoise (edge-avoiding a-trous wavelet filter, Dammertz et
-// al. 2010).  One translation unit of libptmi.so (pt_ctx.h).
+// pt_denoise.hip — pt_render_aux (first-hit guide buffers), pt_denoise (edge-avoiding a-trous wavelet filter, Dammertz et
+// al. 2010) and pt_temporal (the history of earlier frames reprojected into a new one, §10 f8).  One
+// translation unit of libptmi.so (pt_ctx.h).
 //   k_render_aux     one lane per pixel, a 256-thread block per 16x16 tile (one wave per 8x8 quadrant): the pixel-centre camera
 //                    ray, the binary closest-hit walk of pt_trace_rays, the spheres by pt_closest_sphere; albedo, normal,
 //                    position (+ t) as float4 rows, the hit id
@@ -9,6 +10,11 @@
 //                    position only where both ends are hits) and ONE v_exp_f32 (the three terms folded into exp2 with log2(e)
 //                    in the per-launch constants); the last iteration remodulates, clamps, writes out (+ display words)
 //   k_dn_copy        iterations = 0: out = color bit for bit (+ display words)
+//   k_temporal<IDS>  pt_temporal: one lane per pixel in the same 16x16 tiles; the current hit point projected
+//                    into the previous camera, up to four bilinear taps of the history — per tap the id (when given) first, then
+//                    normal and position as one dwordx4 each, colour and length only for a tap that passed every test; no LDS
+//                    (neighbouring lanes share their taps through L1 / L2)
+//   k_tm_first       pt_temporal without a history: out = cur bit for bit, length 1 (+ display words)
 //   k_frame_error    pt_frame_error: one lane per pixel, the relative standard error of the mean luminance from the moments
 //                    pt_render_moments keeps; a block adds its 256 values up in LDS, in double, and writes
 //                    ONE partial sum and ONE count to its own slot — the host adds the slots in block order
@@ -93,7 +99,8 @@ struct DnArgs {
 };
 
 __device__ __forceinline__ float ptd_demod_div(float a) { return a > 1e-3f ? a : 1.0f; }
-__device__ __forceinline__ bool ptd_pixel(const DnArgs& A, int& x, int& y) {
+template <class Args>
+__device__ __forceinline__ bool ptd_pixel(const Args& A, int& x, int& y) {
     x = blockIdx.x * PTD_TILE + (threadIdx.x & (PTD_TILE - 1));
     y = blockIdx.y * PTD_TILE + (threadIdx.x / PTD_TILE);
     return x < A.W && y < A.H;
@@ -173,6 +180,98 @@ __global__ void __launch_bounds__(PTD_BLOCK) k_dn_iter(const DnArgs A) {
         A.out[3 * p] = o0; A.out[3 * p + 1] = o1; A.out[3 * p + 2] = o2;
         if (A.rgba) A.rgba[p] = pt_pack_rgba(o0, o1, o2);
     }
+}
+
+// pt_temporal (include/ptmi.h states the arithmetic, tests/temporal_ref.py restates it)
+struct TmArgs {
+    const float* __restrict__ prev_color;      // [H][W][3]; never the out buffers (checked on the host)
+    const float* __restrict__ prev_len;        // [H][W]
+    const float4* __restrict__ prev_normal;
+    const float4* __restrict__ prev_position;
+    const int32_t* __restrict__ prev_id;       // null = ids not compared
+    const float* cur_color;                    // [H][W][3] (out_color may alias it)
+    const float4* __restrict__ cur_normal;
+    const float4* __restrict__ cur_position;
+    const int32_t* __restrict__ cur_id;
+    float* out_color;
+    float* __restrict__ out_len;
+    uint32_t* __restrict__ rgba;               // may be null
+    int W, H;
+    float pos[3], front[3], right[3], up[3];   // the previous camera
+    float sx, sy, cx, cy;                      // fx = b / a * sx + cx
+    float max_history, plane_tol, normal_thr;
+};
+
+__global__ void __launch_bounds__(PTD_BLOCK) k_tm_first(const TmArgs A) {
+    int x, y;
+    if (!ptd_pixel(A, x, y)) return;
+    const size_t p = (size_t)y * (size_t)A.W + (size_t)x;
+    const float r = A.cur_color[3 * p], g = A.cur_color[3 * p + 1], b = A.cur_color[3 * p + 2];
+    A.out_color[3 * p] = r; A.out_color[3 * p + 1] = g; A.out_color[3 * p + 2] = b;
+    A.out_len[p] = 1.0f;
+    if (A.rgba) A.rgba[p] = pt_pack_rgba(r, g, b);
+}
+
+template <bool IDS>
+__global__ void __launch_bounds__(PTD_BLOCK) k_temporal(const TmArgs A) {
+    int x, y;
+    if (!ptd_pixel(A, x, y)) return;
+    const size_t p = (size_t)y * (size_t)A.W + (size_t)x;
+    const float cr = A.cur_color[3 * p], cg = A.cur_color[3 * p + 1], cb = A.cur_color[3 * p + 2];
+    const float4 n4 = A.cur_normal[p];
+    float o0 = cr, o1 = cg, o2 = cb, on = 1.0f;   // no history accepted: the current frame, bit for bit
+    if (n4.x != 0.f || n4.y != 0.f || n4.z != 0.f) {
+        const float4 x4 = A.cur_position[p];
+        const v3 np = V3(n4.x, n4.y, n4.z), xp = V3(x4.x, x4.y, x4.z);
+        const v3 v = vsub(xp, V3(A.pos[0], A.pos[1], A.pos[2]));
+        const float a = vdot(v, V3(A.front[0], A.front[1], A.front[2]));
+        if (a > 0.f) {
+            const float fx = fmaf(vdot(v, V3(A.right[0], A.right[1], A.right[2])) / a, A.sx, A.cx);
+            const float fy = fmaf(vdot(v, V3(A.up[0], A.up[1], A.up[2])) / a, A.sy, A.cy);
+            // outside (-1, W) x (-1, H) no tap is inside the image; NaN and infinities fail here too, before the conversion to int
+            if (fx > -1.0f && fx < (float)A.W && fy > -1.0f && fy < (float)A.H) {
+                const float x0f = floorf(fx), y0f = floorf(fy);
+                const float wx = fx - x0f, wy = fy - y0f;
+                const int x0 = (int)x0f, y0 = (int)y0f;
+                const float tol = A.plane_tol * x4.w;
+                int idp = 0;
+                if (IDS) idp = A.cur_id[p];
+                float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sl = 0.f;
+#pragma unroll
+                for (int j = 0; j < 2; j++) {
+#pragma unroll
+                    for (int i = 0; i < 2; i++) {
+                        const int xq = x0 + i, yq = y0 + j;
+                        const float w = (i ? wx : 1.0f - wx) * (j ? wy : 1.0f - wy);
+                        if (xq < 0 || xq >= A.W || yq < 0 || yq >= A.H || !(w > 0.f)) continue;
+                        const size_t q = (size_t)yq * (size_t)A.W + (size_t)xq;
+                        if (IDS) {
+                            if (A.prev_id[q] != idp) continue;
+                        }
+                        const float4 nq = A.prev_normal[q], xq4 = A.prev_position[q];
+                        if (nq.x == 0.f && nq.y == 0.f && nq.z == 0.f) continue;   // the history pixel is a miss
+                        if (!(vdot(np, V3(nq.x, nq.y, nq.z)) >= A.normal_thr)) continue;
+                        const v3 dq = vsub(V3(xq4.x, xq4.y, xq4.z), xp);
+                        if (!(fabsf(vdot(np, dq)) <= tol)) continue;
+                        const float* c = A.prev_color + 3 * q;
+                        sr = fmaf(w, c[0], sr); sg = fmaf(w, c[1], sg); sb = fmaf(w, c[2], sb);
+                        sl = fmaf(w, A.prev_len[q], sl);
+                        sw += w;
+                    }
+                }
+                if (sw >= 0.01f) {
+                    const float inv = 1.0f / sw;
+                    const float hr = sr * inv, hg = sg * inv, hb = sb * inv;
+                    on = fminf(sl * inv + 1.0f, A.max_history);
+                    const float k = 1.0f / on;
+                    o0 = fmaf(cr - hr, k, hr); o1 = fmaf(cg - hg, k, hg); o2 = fmaf(cb - hb, k, hb);
+                }
+            }
+        }
+    }
+    A.out_color[3 * p] = o0; A.out_color[3 * p + 1] = o1; A.out_color[3 * p + 2] = o2;
+    A.out_len[p] = on;
+    if (A.rgba) A.rgba[p] = pt_pack_rgba(o0, o1, o2);
 }
 
 // pt_frame_error: rse of pixel i in binary32 (include/ptmi.h states the formula); per block the sum of rse in double and the
@@ -315,6 +414,67 @@ extern "C" int pt_denoise(pt_ctx* c, const pt_denoise_params* dp, const float* c
             else hipLaunchKernelGGL(k_dn_iter<true>, grid, dim3(PTD_BLOCK), 0, st, A);
         }
     }
+    HIP_TRY(c, hipGetLastError());
+    if (c->opt_timing) { HIP_TRY(c, hipEventRecord(c->ev1, st)); c->timed = true; }
+    return PT_OK;
+}
+
+extern "C" int pt_temporal(pt_ctx* c, const pt_temporal_params* tp, const pt_camera* prev_cam, const float* prev_color_dev,
+                           const float* prev_length_dev, const float* prev_normal_dev, const float* prev_position_dev,
+                           const int32_t* prev_id_dev, const float* cur_color_dev, const float* cur_normal_dev,
+                           const float* cur_position_dev, const int32_t* cur_id_dev, float* out_color_dev, float* out_length_dev,
+                           uint32_t* rgba_dev) {
+    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
+    if (!tp || !cur_color_dev || !cur_normal_dev || !cur_position_dev || !out_color_dev || !out_length_dev)
+        return fail(c, PT_ERR_INVALID, "pt_temporal: null argument");
+    if (tp->width < 2 || tp->height < 2) return fail(c, PT_ERR_INVALID, "pt_temporal: width and height must be >= 2");
+    if (!std::isfinite(tp->max_history) || tp->max_history < 1.f) return fail(c, PT_ERR_INVALID, "pt_temporal: max_history must be finite and >= 1");
+    if (!std::isfinite(tp->plane_tolerance) || tp->plane_tolerance < 0.f)
+        return fail(c, PT_ERR_INVALID, "pt_temporal: plane_tolerance must be finite and >= 0");
+    if (!(tp->normal_threshold >= -1.f && tp->normal_threshold <= 1.f)) return fail(c, PT_ERR_INVALID, "pt_temporal: normal_threshold must be in -1..1");
+    const bool history = prev_color_dev != nullptr;
+    if (history) {
+        if (!prev_cam || !prev_length_dev || !prev_normal_dev || !prev_position_dev)
+            return fail(c, PT_ERR_INVALID, "pt_temporal: a history needs its camera, lengths, normals and positions");
+        if ((prev_id_dev == nullptr) != (cur_id_dev == nullptr)) return fail(c, PT_ERR_INVALID, "pt_temporal: ids of both frames or of neither");
+        if (out_color_dev == prev_color_dev || out_length_dev == prev_length_dev)
+            return fail(c, PT_ERR_INVALID, "pt_temporal: the new history may not overwrite the old one (ping-pong the buffers)");
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    TmArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.cur_color = cur_color_dev;
+    A.cur_normal = (const float4*)cur_normal_dev;
+    A.cur_position = (const float4*)cur_position_dev;
+    A.out_color = out_color_dev;
+    A.out_len = out_length_dev;
+    A.rgba = rgba_dev;
+    A.W = tp->width; A.H = tp->height;
+    if (history) {
+        A.prev_color = prev_color_dev;
+        A.prev_len = prev_length_dev;
+        A.prev_normal = (const float4*)prev_normal_dev;
+        A.prev_position = (const float4*)prev_position_dev;
+        A.prev_id = prev_id_dev;
+        A.cur_id = cur_id_dev;
+        for (int i = 0; i < 3; i++) {
+            A.pos[i] = prev_cam->pos[i]; A.front[i] = prev_cam->front[i]; A.right[i] = prev_cam->right[i]; A.up[i] = prev_cam->up[i];
+        }
+        // the inverse of pt_camera_ray's pixel mapping, every step one binary32 rounding
+        A.sx = (float)(tp->width - 1) / (prev_cam->aspect * prev_cam->fov);
+        A.sy = (float)(tp->height - 1) / prev_cam->fov;
+        A.cx = (float)tp->width / 2.0f - 0.5f;
+        A.cy = (float)tp->height / 2.0f - 0.5f;
+        A.max_history = tp->max_history;
+        A.plane_tol = tp->plane_tolerance;
+        A.normal_thr = tp->normal_threshold;
+    }
+    const dim3 grid((unsigned)((tp->width + PTD_TILE - 1) / PTD_TILE), (unsigned)((tp->height + PTD_TILE - 1) / PTD_TILE));
+    hipStream_t st = c->stream;
+    if (c->opt_timing) HIP_TRY(c, hipEventRecord(c->ev0, st));
+    if (!history) hipLaunchKernelGGL(k_tm_first, grid, dim3(PTD_BLOCK), 0, st, A);
+    else if (A.prev_id) hipLaunchKernelGGL(k_temporal<true>, grid, dim3(PTD_BLOCK), 0, st, A);
+    else hipLaunchKernelGGL(k_temporal<false>, grid, dim3(PTD_BLOCK), 0, st, A);
     HIP_TRY(c, hipGetLastError());
     if (c->opt_timing) { HIP_TRY(c, hipEventRecord(c->ev1, st)); c->timed = true; }
     return PT_OK;

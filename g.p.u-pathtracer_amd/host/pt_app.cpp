@@ -8,7 +8,8 @@
 //               --depth 4 --mat 0..3 --no-spheres --no-materials --bk r g b --device 0
 //               --out image.ppm|.png|.pfm  --checkpoint state.ckpt [--checkpoint-every N]
 //               --resume state.ckpt --device-build --fix-estimators --nee --gpus N --tile ROWS
-//               --denoise-out image.ppm|.png|.pfm  --variance-out file.pfm  --until-error E --max-frames M]
+//               --denoise-out image.ppm|.png|.pfm  --variance-out file.pfm  --until-error E --max-frames M
+//               --pan-deg D --dolly S --temporal-out image.ppm|.png|.pfm]
 // --gpus N splits the framebuffer over N contexts, one per GPU (devices device, device+1, ... modulo the number
 // present, so N > 1 also runs on a one-GPU box): stripes of --tile rows (default 8) are dealt round-robin
 // (pt_params.part_*), every context holds the whole scene and renders only its stripes of every frame — the random
@@ -31,8 +32,19 @@
 // --max-frames samples per pixel (required with it); it prints the samples rendered and the final figure.  With --gpus N the
 // figure is computed on the first context from the gathered moments.  The --out image of such a run equals that of a plain run
 // with the same number of samples byte for byte.  Checkpoints hold no moments, so neither option combines with --resume.
+// --pan-deg D / --dolly S move the camera after every displayed frame (one pt_render call of --spp samples): front and right turn
+// by D degrees about up, pos moves S along front.  A camera that moves restarts the accumulation, as the reference does when its
+// camera is dirty: every displayed frame starts at sample_index = 1 and --out is the last frame alone.  --temporal-out runs the
+// loop of a host with temporal accumulation (gpu_pathtracer_amd.TemporalHistory.push) after every displayed frame — pt_render_aux
+// for the frame's camera, pt_temporal against the history of the frames before it, swap — and writes the history after the last
+// frame, format by extension as --out; --denoise-out then filters the history instead of the last frame.  While the camera
+// stands still the accumulator already is the mean of every sample from that viewpoint, so it enters the history once, after the
+// last call, and --out is what it is without the flag, byte for byte.  --temporal-out works on one context over the whole frame
+// and keeps no state a checkpoint could hold: it is refused with --gpus > 1, --resume, --checkpoint, --variance-out and
+// --until-error; so are the motion options with --resume, --checkpoint and --until-error (nothing accumulates across frames).
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -48,12 +60,13 @@ static int die(const char* what, const char* msg) {
 }
 
 int main(int argc, char** argv) {
-    std::string mesh_path, out_path, ckpt_path, resume_path, denoise_path, variance_path;
+    std::string mesh_path, out_path, ckpt_path, resume_path, denoise_path, variance_path, temporal_path;
     int W = 1280, H = 720, frames = 16, depth = 4, mat = PT_MAT_DIFF, device = 0, spp = 1, ckpt_every = 0, gpus = 1, tile = 8;
     bool spheres = true, use_materials = true, device_build = false, fix_estimators = false, nee = false;
     float bk[3] = {1.f, 1.f, 1.f};
     double until_error = -1.0;   // < 0: off
     long max_frames = -1;
+    double pan_deg = 0.0, dolly = 0.0;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&](const char* name) -> const char* {
@@ -63,6 +76,9 @@ int main(int argc, char** argv) {
         if (a == "--mesh") mesh_path = next("--mesh");
         else if (a == "--out") out_path = next("--out");
         else if (a == "--denoise-out") denoise_path = next("--denoise-out");
+        else if (a == "--temporal-out") temporal_path = next("--temporal-out");
+        else if (a == "--pan-deg") pan_deg = std::atof(next("--pan-deg"));
+        else if (a == "--dolly") dolly = std::atof(next("--dolly"));
         else if (a == "--variance-out") variance_path = next("--variance-out");
         else if (a == "--until-error") until_error = std::atof(next("--until-error"));
         else if (a == "--max-frames") max_frames = std::atol(next("--max-frames"));
@@ -94,6 +110,12 @@ int main(int argc, char** argv) {
     if (until && max_frames < (long)frames) return die("usage", "--until-error needs --max-frames >= --frames");
     if (!until && max_frames >= 0) return die("usage", "--max-frames goes with --until-error");
     if (with_moments && !resume_path.empty()) return die("usage", "--variance-out / --until-error do not combine with --resume (a checkpoint holds no moments)");
+    const bool moving = pan_deg != 0.0 || dolly != 0.0, temporal = !temporal_path.empty();
+    if (!std::isfinite(pan_deg) || !std::isfinite(dolly)) return die("usage", "--pan-deg and --dolly must be finite");
+    if (temporal && (gpus > 1 || !resume_path.empty() || !ckpt_path.empty() || with_moments))
+        return die("usage", "--temporal-out does not combine with --gpus > 1, --resume, --checkpoint, --variance-out or --until-error");
+    if (moving && (!resume_path.empty() || !ckpt_path.empty() || until))
+        return die("usage", "--pan-deg / --dolly do not combine with --resume, --checkpoint or --until-error (a moving camera restarts the accumulation every frame)");
 
     const bool is_ptmesh = mesh_path.size() > 7 && mesh_path.substr(mesh_path.size() - 7) == ".ptmesh";
     pth_mesh* mesh = is_ptmesh ? pth_mesh_load_ptmesh(mesh_path.c_str()) : pth_mesh_load_obj(mesh_path.c_str());
@@ -235,6 +257,52 @@ int main(int argc, char** argv) {
         return 0;
     };
 
+    // --temporal-out: the ping-pong history (colour, length, guides) of TemporalHistory, on the one context
+    const size_t n_pix_all = (size_t)W * H;
+    void *t_color[2] = {nullptr, nullptr}, *t_len[2] = {nullptr, nullptr}, *t_alb[2] = {nullptr, nullptr}, *t_nrm[2] = {nullptr, nullptr},
+         *t_pos[2] = {nullptr, nullptr}, *t_rgba = nullptr;
+    int t_cur = 0;          // the set the next push writes
+    bool t_has = false;     // a history exists
+    pt_camera t_cam{};      // its camera
+    const pt_temporal_params tpar = {W, H, 32.0f, 0.02f, 0.9f, 0};   // = gpu_pathtracer_amd.TEMPORAL_DEFAULTS
+    if (temporal) {
+        for (int k = 0; k < 2; k++)
+            if (pt_malloc(ctx, n_pix_all * 12, &t_color[k]) != PT_OK || pt_malloc(ctx, n_pix_all * 4, &t_len[k]) != PT_OK ||
+                pt_malloc(ctx, n_pix_all * 16, &t_alb[k]) != PT_OK || pt_malloc(ctx, n_pix_all * 16, &t_nrm[k]) != PT_OK ||
+                pt_malloc(ctx, n_pix_all * 16, &t_pos[k]) != PT_OK)
+                return die("pt_malloc", pt_last_error(ctx));
+        if (pt_malloc(ctx, n_pix_all * 4, &t_rgba) != PT_OK) return die("pt_malloc", pt_last_error(ctx));
+    }
+    auto temporal_push = [&]() -> int {   // guides of `cam`, the frame in `accum` against the history, swap
+        const int k = t_cur, o = 1 - t_cur;
+        if (pt_render_aux(ctx, &cam, &p, (float*)t_alb[k], (float*)t_nrm[k], (float*)t_pos[k], nullptr) != PT_OK) return die("pt_render_aux", pt_last_error(ctx));
+        if (pt_temporal(ctx, &tpar, t_has ? &t_cam : nullptr, t_has ? (const float*)t_color[o] : nullptr, (const float*)t_len[o],
+                        (const float*)t_nrm[o], (const float*)t_pos[o], nullptr, (const float*)accum, (const float*)t_nrm[k],
+                        (const float*)t_pos[k], nullptr, (float*)t_color[k], (float*)t_len[k], (uint32_t*)t_rgba) != PT_OK)
+            return die("pt_temporal", pt_last_error(ctx));
+        t_cam = cam;
+        t_has = true;
+        t_cur = o;
+        return 0;
+    };
+    // the camera of displayed frame k: the first one turned by k x pan_deg about up (from the first basis, in double: no drift),
+    // pos moved `dolly` along each frame's front in turn
+    const pt_camera cam0 = cam;
+    double cam_pos[3] = {cam.pos[0], cam.pos[1], cam.pos[2]};
+    auto move_camera = [&](int k) {
+        const double th = pan_deg * (double)k * 3.14159265358979323846 / 180.0, cs = std::cos(th), sn = std::sin(th);
+        const double u[3] = {cam0.up[0], cam0.up[1], cam0.up[2]};
+        auto rot = [&](const float* v, float* out) {   // Rodrigues: v cos + (u x v) sin + u (u . v)(1 - cos)
+            const double x[3] = {v[0], v[1], v[2]};
+            const double cr[3] = {u[1] * x[2] - u[2] * x[1], u[2] * x[0] - u[0] * x[2], u[0] * x[1] - u[1] * x[0]};
+            const double ud = u[0] * x[0] + u[1] * x[1] + u[2] * x[2];
+            for (int i = 0; i < 3; i++) out[i] = (float)(x[i] * cs + cr[i] * sn + u[i] * ud * (1.0 - cs));
+        };
+        rot(cam0.front, cam.front);
+        rot(cam0.right, cam.right);
+        for (int i = 0; i < 3; i++) { cam_pos[i] += dolly * (double)cam.front[i]; cam.pos[i] = (float)cam_pos[i]; }
+    };
+
     const uint64_t first_frame = frameNumber;
     uint64_t end_frame = frameNumber + (uint64_t)frames;
     const uint64_t last_frame = until ? frameNumber + (uint64_t)max_frames : end_frame;   // --until-error: never past --max-frames
@@ -247,16 +315,19 @@ int main(int argc, char** argv) {
             for (pt_ctx* cx : ctxs)
                 if (pt_sync(cx) != PT_OK) return die("pt_sync", pt_last_error(cx));     // :395
             const uint32_t n = (uint32_t)std::min<uint64_t>((uint64_t)spp, end_frame - frameNumber);
+            if (moving && calls > 0) move_camera(calls);                                // the camera is dirty: start over (:399)
             p.frame = frameNumber;                                                      // :397
-            p.sample_index = constantPdf + 1;                                           // :399 (1 on the first frame: overwrite)
+            p.sample_index = moving ? 1 : constantPdf + 1;                              // :399 (1 on the first frame: overwrite)
             for (int g = 0; g < gpus; g++) {                                            // :404, once per GPU: asynchronous, so the GPUs run side by side
                 p.part_index = g;
                 if (pt_render_moments(ctxs[(size_t)g], (float*)accums[(size_t)g], (uint32_t*)rgbas[(size_t)g], (float*)moments[(size_t)g], &cam, &p, n) != PT_OK)
                     return die("pt_render", pt_last_error(ctxs[(size_t)g]));
             }
             frameNumber += n;
-            constantPdf += n;
+            constantPdf = moving ? n : constantPdf + n;
             calls++;
+            if (temporal && moving)
+                if (int rc = temporal_push()) return rc;
             if (!ckpt_path.empty() && ckpt_every > 0 && calls % ckpt_every == 0 && frameNumber < end_frame)
                 if (int rc = save_checkpoint()) return rc;
         }
@@ -275,6 +346,8 @@ int main(int argc, char** argv) {
         end_frame = std::min<uint64_t>(frameNumber + (uint64_t)spp, last_frame);
     }
     frames = (int)(frameNumber - first_frame);   // what was rendered: more than asked for under --until-error
+    if (temporal && !t_has)   // the camera stood still: the accumulator is the one frame of the history
+        if (int rc = temporal_push()) return rc;
     if (until) std::printf("until-error %g: %d frames rendered, mean_rse %.6g\n", until_error, frames, mean_rse);
     for (pt_ctx* cx : ctxs) pt_sync(cx);
     double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -320,9 +393,25 @@ int main(int argc, char** argv) {
         }
         if (pth_write_pfm(variance_path.c_str(), img.data(), W, H) != 0) return die("write", pth_last_error());
     }
+    if (temporal) {   // the history after the last frame
+        const int k = 1 - t_cur;
+        const std::string ext = temporal_path.size() > 4 ? temporal_path.substr(temporal_path.size() - 4) : std::string();
+        int rc;
+        if (ext == ".pfm") {
+            std::vector<float> img(n_pix_all * 3);
+            if (pt_download(ctx, img.data(), t_color[k], img.size() * 4) != PT_OK) return die("pt_download", pt_last_error(ctx));
+            rc = pth_write_pfm(temporal_path.c_str(), img.data(), W, H);
+        } else {
+            std::vector<uint32_t> img(n_pix_all);
+            if (pt_download(ctx, img.data(), t_rgba, img.size() * 4) != PT_OK) return die("pt_download", pt_last_error(ctx));
+            rc = ext == ".png" ? pth_write_png(temporal_path.c_str(), img.data(), W, H) : pth_write_ppm(temporal_path.c_str(), img.data(), W, H);
+        }
+        if (rc != 0) return die("write", pth_last_error());
+    }
     if (!denoise_path.empty()) {   // guides of the pixel centres + the a-trous filter of the final accumulator, on the first context
         const size_t n_pix = (size_t)W * H;
-        void *color = accum, *alb = nullptr, *nrm = nullptr, *pos = nullptr, *dout = nullptr, *drgba = nullptr;
+        // with --temporal-out the history is filtered, not the last frame
+        void *color = temporal ? t_color[1 - t_cur] : accum, *alb = nullptr, *nrm = nullptr, *pos = nullptr, *dout = nullptr, *drgba = nullptr;
         if (pt_malloc(ctx, n_pix * 16, &alb) != PT_OK || pt_malloc(ctx, n_pix * 16, &nrm) != PT_OK || pt_malloc(ctx, n_pix * 16, &pos) != PT_OK ||
             pt_malloc(ctx, n_pix * 12, &dout) != PT_OK || pt_malloc(ctx, n_pix * 4, &drgba) != PT_OK)
             return die("pt_malloc", pt_last_error(ctx));
@@ -349,7 +438,12 @@ int main(int argc, char** argv) {
         }
         if (rc != 0) return die("write", pth_last_error());
         for (void* b : {alb, nrm, pos, dout, drgba}) pt_free(ctx, b);
-        if (color != accum) pt_free(ctx, color);
+        if (gpus > 1) pt_free(ctx, color);
+    }
+    if (temporal) {
+        for (int k = 0; k < 2; k++)
+            for (void* b : {t_color[k], t_len[k], t_alb[k], t_nrm[k], t_pos[k]}) pt_free(ctx, b);
+        pt_free(ctx, t_rgba);
     }
     (void)accum; (void)rgba;
     if (moments_all != moments[0]) pt_free(ctx, moments_all);

@@ -13,11 +13,13 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import Camera, Counters, DenoiseParams, Material, Params, Sphere
+from ._abi import Camera, Counters, DenoiseParams, Material, Params, Sphere, TemporalParams
 
 # pt_denoise defaults (iterations, sigma_color, sigma_normal, sigma_position): chosen by the CPU sweep of DESIGN.md §10 f6;
 # host/pt_app.cpp uses the same values
 DENOISE_DEFAULTS = dict(iterations=4, sigma_color=0.0, sigma_normal=1.0, sigma_position=0.03)
+# pt_temporal defaults: starting values by definition, not tuned figures; host/pt_app.cpp uses the same values
+TEMPORAL_DEFAULTS = dict(max_history=32.0, plane_tolerance=0.02, normal_threshold=0.9)
 
 
 class PtError(RuntimeError):
@@ -203,6 +205,19 @@ class PathTracer:
         dp = DenoiseParams(int(width), int(height), int(iterations), float(sigma_color), float(sigma_normal), float(sigma_position))
         self._check(self._lib.pt_denoise(self._ctx, C.byref(dp), color_ptr, albedo_ptr, normal_ptr, position_ptr, out_ptr, rgba_ptr))
 
+    def temporal(self, width, height, prev_cam, prev_color_ptr, prev_length_ptr, prev_normal_ptr, prev_position_ptr, prev_id_ptr,
+                 cur_color_ptr, cur_normal_ptr, cur_position_ptr, cur_id_ptr, out_color_ptr, out_length_ptr, rgba_ptr=None,
+                 max_history=TEMPORAL_DEFAULTS["max_history"], plane_tolerance=TEMPORAL_DEFAULTS["plane_tolerance"],
+                 normal_threshold=TEMPORAL_DEFAULTS["normal_threshold"]):
+        """Temporal reprojection (pt_temporal): the history (colour float[H][W][3], length float[H][W], the guides of render_aux
+        at prev_cam) carried into the current frame (cur colour and guides); the new history into out colour / length, its
+        display words into rgba (optional).  prev_color_ptr=None: no history yet (prev_cam and the other prev_* are ignored).
+        out colour may be cur colour, never prev colour.  Asynchronous until sync()."""
+        tp = TemporalParams(int(width), int(height), float(max_history), float(plane_tolerance), float(normal_threshold), 0)
+        self._check(self._lib.pt_temporal(self._ctx, C.byref(tp), C.byref(prev_cam) if prev_cam is not None else None,
+                                          prev_color_ptr, prev_length_ptr, prev_normal_ptr, prev_position_ptr, prev_id_ptr,
+                                          cur_color_ptr, cur_normal_ptr, cur_position_ptr, cur_id_ptr, out_color_ptr, out_length_ptr, rgba_ptr))
+
     # ------------------------------------------------------------------ measurement
     def counters(self):
         c = Counters()
@@ -248,6 +263,50 @@ class PathTracer:
         ms = C.c_float()
         self._check(self._lib.pt_last_kernel_ms(self._ctx, C.byref(ms)))
         return ms.value
+
+
+class TemporalHistory:
+    """The ping-pong buffers of a host's temporal accumulation: two history colours, two lengths, two sets of guide buffers and the
+    camera of the frame pushed last.  push() is one displayed frame of the loop: guides, reprojection, swap."""
+
+    def __init__(self, tracer, width, height, with_ids=True):
+        self.t, self.W, self.H = tracer, int(width), int(height)
+        n = self.W * self.H
+        self.color = [tracer.malloc(n * 12) for _ in range(2)]
+        self.length = [tracer.malloc(n * 4) for _ in range(2)]
+        self.guides = [[tracer.malloc(n * 16) for _ in range(3)] + [tracer.malloc(n * 4) if with_ids else None] for _ in range(2)]
+        self.cam = None     # the camera of the history; None = nothing pushed yet
+        self.cur = 0        # the set the NEXT push writes
+
+    def reset(self):
+        """Forget the history (a cut: the next push starts over)."""
+        self.cam = None
+
+    def _ptrs(self, k):
+        return [b.ptr if b is not None else None for b in self.guides[k]]
+
+    def push(self, cam, params, color_ptr, rgba_ptr=None, **temporal):
+        """One frame: render_aux for `cam` (params: the frame's pt_params), then temporal() of the frame in color_ptr (rendered
+        with sample_index = 1; never written) against the stored history — or with no history the first time — then the swap.
+        Returns (color_ptr, length_ptr, (albedo, normal, position, id) ptrs) of the new history; the colour and the guides can be
+        passed to denoise() directly.  **temporal: max_history, plane_tolerance, normal_threshold.  Asynchronous."""
+        k, o = self.cur, 1 - self.cur
+        alb, nrm, pos, ids = self._ptrs(k)
+        self.t.render_aux(cam, params, alb, nrm, pos, ids)
+        if self.cam is None:
+            prev = (None,) * 6
+        else:
+            _, pn, pp, pi = self._ptrs(o)
+            prev = (self.cam, self.color[o].ptr, self.length[o].ptr, pn, pp, pi)
+        self.t.temporal(self.W, self.H, *prev, color_ptr, nrm, pos, ids, self.color[k].ptr, self.length[k].ptr, rgba_ptr, **temporal)
+        self.cam = Camera.from_buffer_copy(cam)
+        self.cur = o
+        return self.color[k].ptr, self.length[k].ptr, (alb, nrm, pos, ids)
+
+    def free(self):
+        for b in self.color + self.length + [x for gset in self.guides for x in gset if x is not None]:
+            b.free()
+        self.color, self.length, self.guides, self.cam = [], [], [], None
 
 
 def algorithmic_bytes(counters, n_spheres):

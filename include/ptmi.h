@@ -476,6 +476,61 @@ int pt_denoise(pt_ctx* ctx, const pt_denoise_params* dp, const float* color_dev,
                const float* albedo_dev, const float* normal_dev, const float* position_dev,
                float* out_dev, uint32_t* rgba_dev);
 
+/* ---- temporal reprojection — an EXTENSION ---------------------------------
+ * pt_temporal: carries a history of earlier frames into a new frame rendered from a camera that has moved (the first stage of
+ * SVGF-style chains), so that a displayed pixel keeps the samples of the frames before it instead of restarting at
+ * sample_index = 1.  The scene is static and the camera moves; the hit point pt_render_aux wrote for a pixel is projected into
+ * the previous camera, and the history is read there with a bilinear footprint whose taps must lie on the same surface.
+ *   colours float[h][w][3] (the accumulator layout), lengths float[h][w] (a history length counts FRAMES, so the host keeps
+ *   the samples per frame constant), guides as pt_render_aux writes them (float[4] rows, int32 ids).  prev_* describe the
+ *   history as seen from prev_cam; cur_color_dev is the new frame (rendered with sample_index = 1), cur_* its guides.
+ * For pixel p = (x, y) of the current frame, with n_p, x_p (xyz) and t_p (.w) its normal and position rows, in binary32 and in
+ * this order (vdot(u, v) = fmaf(u.z, v.z, fmaf(u.y, v.y, u.x * v.x)); no other fused multiply-add than the ones written):
+ *   1. n_p == (0, 0, 0), a current miss: out = cur, out_length = 1.
+ *   2. v = x_p - prev_cam.pos;  a = vdot(v, front), b = vdot(v, right), c = vdot(v, up).  The history is rejected unless a > 0.
+ *      fx = fmaf(b / a, sx, (float)w / 2.0f - 0.5f),  fy = fmaf(c / a, sy, (float)h / 2.0f - 0.5f),  with
+ *      sx = (float)(w - 1) / (aspect * fov),  sy = (float)(h - 1) / fov  of prev_cam, computed once on the host — the inverse of
+ *      the pixel mapping of pt_render's camera ray for an orthonormal basis (every ray passes through pos; an integer fx is a
+ *      pixel centre).  The history is rejected when fx or fy is not finite.
+ *   3. x0 = floorf(fx), wx = fx - x0 (y likewise); the taps are q = (x0 + i, y0 + j), i, j in 0..1, with the weights
+ *      w_q = (i ? wx : 1.0f - wx) * (j ? wy : 1.0f - wy).
+ *   4. A tap counts when it is inside the image, w_q > 0, the history pixel is a hit (n_q != 0), the ids are equal (compared
+ *      only when both id pointers are given), vdot(n_p, n_q) >= normal_threshold and
+ *      fabsf(vdot(n_p, x_q - x_p)) <= plane_tolerance * t_p: its hit point lies within that fraction of the ray distance of the
+ *      current pixel's tangent plane.
+ *   5. sw = sum of w_q, sc = sum of w_q c_q, sl = sum of w_q len_q over the taps that count (j outer, i inner; fmaf(w, c, sc)).
+ *      The history is accepted when sw >= 0.01 (a definition that keeps 1 / sw finite).  Then, with inv = 1.0f / sw:
+ *          hist = sc * inv,  n = fminf(sl * inv + 1.0f, max_history),  out = fmaf(cur - hist, 1.0f / n, hist),  out_length = n.
+ *      Not accepted (or rejected in 2.): out = cur bit for bit, out_length = 1.
+ * prev_color_dev == NULL: there is no history yet; prev_cam and every prev_* are ignored, out = cur bit for bit and
+ * out_length = 1 everywhere — a host's first frame goes through the same call as every later one.
+ * rgba_dev (may be NULL) receives the 0x00BBGGRR display word of out, as pt_render packs it; there is no clamp, out is a convex
+ * combination of its inputs.  out_color_dev may alias cur_color_dev (a lane reads only its own current pixel); the caller
+ * ping-pongs the history: out_color_dev == prev_color_dev or out_length_dev == prev_length_dev is refused.
+ * PT_ERR_INVALID: NULL ctx, params, cur_* colour / normal / position or out_* pointer; with a history a NULL prev_cam, length,
+ * normal or position pointer, exactly one of the two id pointers, or the aliasing above; width or height < 2 (the camera mapping
+ * divides by w - 1, h - 1); max_history not finite or < 1; plane_tolerance not finite or < 0; normal_threshold outside -1..1.
+ * No scene needed; no scratch, no allocation, no synchronisation.  Asynchronous on the context's stream, hence ordered after
+ * the fold of an earlier pt_render (which stays on that stream under PT_OPT_OVERLAP) and after pt_render_aux; the outputs can go
+ * straight into pt_denoise.  With PT_OPT_TIMING=1, pt_last_kernel_ms reports its device time.
+ * Triangles moved by pt_refit_bvh fail the plane test where they moved: their history is dropped, which is safe but not useful.
+ * Out of scope: motion vectors for moving geometry, reprojecting pt_render_moments' moments, following specular first hits (a
+ * mirror's history is looked up where its surface was, not where its reflection was), per-stripe operation in the multi-GPU
+ * tile split (the call is full-frame). */
+typedef struct pt_temporal_params {
+    int32_t width, height;      /* >= 2 each                                                          */
+    float max_history;          /* >= 1: cap on the history length in frames                          */
+    float plane_tolerance;      /* >= 0: fraction of t_p a tap's hit point may lie off the tangent plane */
+    float normal_threshold;     /* -1..1: smallest dot(n_p, n_q) of a tap on the same surface          */
+    int32_t _pad;
+} pt_temporal_params;           /* 24 bytes */
+int pt_temporal(pt_ctx* ctx, const pt_temporal_params* tp, const pt_camera* prev_cam,
+                const float* prev_color_dev, const float* prev_length_dev,
+                const float* prev_normal_dev, const float* prev_position_dev, const int32_t* prev_id_dev,
+                const float* cur_color_dev,
+                const float* cur_normal_dev, const float* cur_position_dev, const int32_t* cur_id_dev,
+                float* out_color_dev, float* out_length_dev, uint32_t* rgba_dev);
+
 /* ---- measurement --------------------------------------------------------------- */
 int pt_get_counters(pt_ctx* ctx, pt_counters* out);
 /* Schedule statistics of the last instrumented launch of the persistent wide walk

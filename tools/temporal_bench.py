@@ -1,0 +1,106 @@
+#!/usr/bin/env python3
+"""pt_temporal measured: device time (PT_OPT_TIMING, pt_last_kernel_ms) at 1920x1080 on the bench scene (cornell_dragon + the
+sphere room, golden camera), the camera panning 1 degree between frames, the median of repeated timed calls — with and without
+ids, the first frame's copy path, and beside them the guide pass and pt_denoise at 4 iterations from the same run.
+Usage: python tools/temporal_bench.py [--out FILE] [--reps 20]"""
+import argparse
+import math
+import os
+import sys
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path[:0] = [ROOT]
+import numpy as np  # noqa: E402
+import gpu_pathtracer_amd as g  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--out", default=None, help="also write the report here")
+ap.add_argument("--reps", type=int, default=20)
+ap.add_argument("--scene", default="cornell_dragon")
+ap.add_argument("--pan-deg", type=float, default=1.0)
+a = ap.parse_args()
+W, H = 1920, 1080
+lines = []
+
+
+def say(s):
+    print(s, flush=True)
+    lines.append(s)
+
+
+def panned(cam, deg):
+    """front and right turned by deg about up = (0, 1, 0) of the default camera."""
+    c = g.Camera.from_buffer_copy(cam)
+    th = math.radians(deg)
+    for name in ("front", "right"):
+        x, y, z = getattr(cam, name)
+        getattr(c, name)[:] = (x * math.cos(th) + z * math.sin(th), y, -x * math.sin(th) + z * math.cos(th))
+    return c
+
+
+t = g.PathTracer(0)
+mesh = g.scene_mesh(a.scene)
+t.upload_bvh(g.Bvh(mesh))
+t.upload_spheres(g.reference_spheres())
+cam0 = g.default_camera(W, H)
+cam0.dist = 18.0 * H / 1080.0
+cam1 = panned(cam0, a.pan_deg)
+p = g.default_params(W, H)
+p.flags = g.FLAG_WRITE_RGBA
+acc, rgba = t.alloc_frame(W, H)
+out, orgba = t.malloc(W * H * 12), t.malloc(W * H * 4)
+th = g.TemporalHistory(t, W, H)
+# frame 0 at cam0 becomes the history, frame 1 at cam1 is the current frame
+p.frame, p.sample_index = 0, 1
+t.launch_kernel(acc.ptr, rgba.ptr, cam0, p, 4)
+th.push(cam0, p, acc.ptr)
+p.frame = 4
+t.launch_kernel(acc.ptr, rgba.ptr, cam1, p, 4)
+prev, cur = 1 - th.cur, th.cur
+alb, nrm, pos, ids = th._ptrs(cur)
+_, pn, pp, pi = th._ptrs(prev)
+t.sync()
+
+
+def timed(fn):
+    ms = []
+    for _ in range(a.reps + 2):
+        fn()
+        ms.append(t.last_kernel_ms())
+    return float(np.median(ms[2:])), float(np.min(ms[2:]))
+
+
+t.set_option(g.OPT_TIMING, 1)
+say(f"{a.scene} ({mesh.n_tris} triangles) + 8 spheres, {W}x{H}, pan {a.pan_deg} deg between the frames; device ms (PT_OPT_TIMING), "
+    f"median / min of {a.reps} calls")
+med, mn = timed(lambda: t.render_aux(cam1, p, alb, nrm, pos, ids))
+say(f"pt_render_aux                        {med:7.3f} / {mn:7.3f} ms")
+
+
+def temporal(with_ids, history=True, with_rgba=True):
+    t.temporal(W, H, cam0 if history else None, th.color[prev].ptr if history else None, th.length[prev].ptr, pn, pp, pi if with_ids else None,
+               acc.ptr, nrm, pos, ids if with_ids else None, th.color[cur].ptr, th.length[cur].ptr, orgba.ptr if with_rgba else None)
+
+
+for name, fn in (("pt_temporal, ids, display words    ", lambda: temporal(True)),
+                 ("pt_temporal, no ids, display words ", lambda: temporal(False)),
+                 ("pt_temporal, ids, no display words ", lambda: temporal(True, with_rgba=False)),
+                 ("pt_temporal, no history (the copy) ", lambda: temporal(True, history=False))):
+    med, mn = timed(fn)
+    say(f"{name}  {med:7.3f} / {mn:7.3f} ms")
+temporal(True)
+t.sync()
+length = th.length[cur].download(np.float32, (H, W))
+say(f"  history accepted at {(length > 1).mean() * 100:.1f} % of the pixels")
+dflt = {k: v for k, v in g.DENOISE_DEFAULTS.items() if k != "iterations"}
+for it in (1, 4):
+    med, mn = timed(lambda: t.denoise(th.color[cur].ptr, alb, nrm, pos, W, H, out.ptr, orgba.ptr, iterations=it, **dflt))
+    say(f"pt_denoise of the history, {it} iteration{'s' if it > 1 else ' '}  {med:7.3f} / {mn:7.3f} ms")
+t.set_option(g.OPT_TIMING, 0)
+for b in (acc, rgba, out, orgba):
+    b.free()
+th.free()
+t.close()
+if a.out:
+    with open(a.out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
