@@ -2,14 +2,16 @@
 // One translation unit of libptmi.so (pt_ctx.h).
 #include <cmath>
 #include <cstring>
+#include <utility>
 
 #include "pt_ctx.h"
 #include "pt_build.h"
 
 namespace ptmi {
 
-int build_bvh_impl(pt_ctx* c, const float* verts, size_t n_verts, const int32_t* tris, size_t n_tris, int algo, bool* too_deep,
-                          const int32_t* id_map) {
+// one build with `algo`; too_deep: it failed because PLOC's tree got too deep (the LBVH can still do it)
+static int build_with(pt_ctx* c, const float* verts, size_t n_verts, const int32_t* tris, size_t n_tris, int algo, bool* too_deep,
+                      DevTree& out, const int32_t* id_map) {
     *too_deep = false;
     if (!verts || !tris || n_verts == 0 || n_tris == 0) return fail(c, PT_ERR_INVALID, "pt_build_bvh: empty mesh or null array");
     if (n_tris > (1u << 27) || n_verts > (1u << 30)) return fail(c, PT_ERR_INVALID, "pt_build_bvh: mesh too large for 32-bit links");
@@ -106,10 +108,10 @@ int build_bvh_impl(pt_ctx* c, const float* verts, size_t n_verts, const int32_t*
     }
     const size_t n_items = (size_t)(n - 1) + (size_t)n + (size_t)(n - 1);   // binary, records, wide (upper bound)
     if (n_items * 4 >= (size_t)PT_SENTINEL) return fail(c, PT_ERR_INVALID, "pt_build_bvh: scene too large for 32-bit links");
-    float4* items = nullptr;
-    HIP_TRY(c, hipMalloc((void**)&items, n_items * 64));
+    DevTree made;
+    HIP_TRY(c, hipMalloc((void**)&made.s.d_nodes, n_items * 64));
+    float4* const items = made.s.d_nodes;
     B.items = items;
-    struct ItemsGuard { float4* p; ~ItemsGuard() { if (p) (void)hipFree(p); } } guard{items};
 
     const unsigned int cb0[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
     const unsigned int st0[4] = {1u, 0u, 0u, 0u};   // wide slot 0 is the root's
@@ -223,30 +225,34 @@ int build_bvh_impl(pt_ctx* c, const float* verts, size_t n_verts, const int32_t*
     uint32_t levels = 0;
     while (levels < 66 && level_cnt[levels] > 0) levels++;
     if (level_cnt[std::min<unsigned int>(n_levels_max + 1, 67)] != 0) return fail(c, PT_ERR_DEVICE, "pt_build_bvh: wide collapse did not finish");
-    HIP_TRY(c, hipEventElapsedTime(&c->tree.build_ms, e0, e1));
+    TreeState& t = made.s;
+    HIP_TRY(c, hipEventElapsedTime(&t.build_ms, e0, e1));
     if (stats[3] > 64) return fail(c, PT_ERR_UNSUPPORTED, "pt_build_bvh: tree deeper than 64 levels (degenerate input); use the host builder");
 
-    refit_release(c);
-    (void)hipFree(c->tree.d_nodes);
-    c->tree.d_nodes = items;
-    guard.p = nullptr;
-    c->tree.d_tris = c->tree.d_nodes;
-    c->tree.records_woop = false;
-    c->tree.wide_root = 4 * ((uint64_t)(n - 1) + (uint64_t)n);
-    c->tree.wide_top_layout = 1;      // level order below the root, not a breadth-first prefix of fixed size
-    c->tree.n_top_layout = 1;
-    c->tree.wide_depth = levels;
-    c->tree.n_wide = stats[0];
-    c->tree.n_inner = (uint64_t)(n - 1);
-    c->tree.n_refs = (uint64_t)n;
-    c->tree.n_leaves = stats[2];
-    c->tree.max_depth = stats[3];
-    c->tree.scene_bytes = n_items * 64;
-    c->tree.max_tri_id = (int32_t)n_tris - 1;
-    if (id_map) for (size_t i = 0; i < n_tris; i++) c->tree.max_tri_id = std::max(c->tree.max_tri_id, id_map[i]);
-    c->tree.has_bvh = true;
-    c->scene_gen++;
+    t.wide_root = 4 * ((uint64_t)(n - 1) + (uint64_t)n);
+    t.wide_top_layout = 1;      // level order below the root, not a breadth-first prefix of fixed size
+    t.n_top_layout = 1;
+    t.wide_depth = levels;
+    t.n_wide = stats[0];
+    t.n_inner = (uint64_t)(n - 1);
+    t.n_refs = (uint64_t)n;
+    t.n_leaves = stats[2];
+    t.max_depth = stats[3];
+    t.scene_bytes = n_items * 64;
+    t.max_tri_id = (int32_t)n_tris - 1;
+    if (id_map) for (size_t i = 0; i < n_tris; i++) t.max_tri_id = std::max(t.max_tri_id, id_map[i]);
+    t.has_bvh = true;
+    out = std::move(made);
     return PT_OK;
+}
+
+int build_bvh_impl(pt_ctx* c, const float* verts, size_t n_verts, const int32_t* tris, size_t n_tris, DevTree& out, const int32_t* id_map) {
+    bool too_deep = false;
+    int rc = build_with(c, verts, n_verts, tris, n_tris, c->opt_build_algo, &too_deep, out, id_map);
+    // PLOC on degenerate input (hundreds of identical boxes: one merge per round, a chain): the Karras
+    // hierarchy separates equal keys by position and stays balanced
+    if (rc != PT_OK && too_deep && c->opt_build_algo == 1) rc = build_with(c, verts, n_verts, tris, n_tris, 0, &too_deep, out, id_map);
+    return rc;
 }
 
 }  // namespace ptmi

@@ -1,6 +1,6 @@
 // pt_ctx.h — the context behind the C ABI (include/ptmi.h) and the host-side helpers shared by the
-// translation units of libptmi.so: ptmi.hip (API), pt_build.hip (device BVH builder),
-// pt_k_*.hip (kernel families + their launchers).  Host code only.
+// translation units of libptmi.so: ptmi.hip (API), pt_tree.hip (trees: makers, adoption, cost), pt_build.hip (device BVH
+// builder), pt_k_*.hip (kernel families + their launchers).  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,11 +19,14 @@
 #define PT_FIRST_WALK_DEFAULT 1
 #endif
 
-// Everything on the context that describes the acceleration structure, written once: a tree is parked and put back by plain
-// assignment (PT_OPT_REBUILD 2 holds two for a moment), so a field added here cannot be forgotten on the way.
+// Everything that describes an acceleration structure.  A tree is a VALUE: the makers (pt_tree.hip, pt_build.hip) fill one inside a
+// DevTree without touching the context, and adopt_tree (pt_tree.hip) is the only code that writes pt_ctx::tree.  So
+//   * a call that fails before adoption leaves the context exactly as it was: tree, build_ms, scene_gen, refit state;
+//   * the previous tree lives until the new one is complete: one more tree at the peak of a plain upload, two more for a moment
+//     under PT_OPT_REBUILD 2 (3 n items of 64 B: ~150 MB at 800 k triangles);
+//   * scene_gen advances by one per successful call (only equality is ever tested on it).
 struct TreeState {
-    float4* d_nodes = nullptr;   // one item buffer, [binary nodes][records][wide nodes]: links index it directly
-    float4* d_tris = nullptr;    // (aliases d_nodes)
+    float4* d_nodes = nullptr;   // one item buffer, [binary nodes][records][wide nodes]: links index it directly (KScene::nodes and ::tris)
     bool records_woop = false;   // what the uploaded records are
     bool has_bvh = false;
     uint64_t wide_root = 0;      // float4 index of the 4-wide tree's root, 0 = not built
@@ -32,8 +35,22 @@ struct TreeState {
     uint32_t n_top_layout = 0;   // nodes [0, n_top_layout) are in breadth-first order
     uint32_t max_depth = 0;
     int32_t max_tri_id = -1;     // largest original triangle id of the uploaded BVH
-    float build_ms = -1.f;       // device time of the last pt_build_bvh
+    float build_ms = -1.f;       // device time of the build behind this tree, -1: no device build stands behind it
     double opt_cost[2] = {0.0, 0.0};   // PT_OPT_OPTIMIZE: area cost (inner-node areas / root area) before / after, 0 when it did not run
+};
+
+// A tree that owns its item buffer: whatever a maker allocated is released on every early return, and the loser of
+// PT_OPT_REBUILD 2 when it goes out of scope.
+struct DevTree {
+    TreeState s;
+    DevTree() = default;
+    DevTree(DevTree&& o) noexcept : s(o.release()) {}
+    DevTree& operator=(DevTree&& o) noexcept {
+        if (this != &o) { (void)hipFree(s.d_nodes); s = o.release(); }
+        return *this;
+    }
+    ~DevTree() { (void)hipFree(s.d_nodes); }
+    TreeState release() { const TreeState r = s; s = TreeState(); return r; }   // the caller owns the buffer now
 };
 
 struct pt_ctx {
@@ -114,7 +131,7 @@ struct pt_ctx {
     AutoPick picks[N_PICKS];
     int pick_last = -1;          // entry of the last PT_KERNEL_AUTO call (pt_auto_choice), -1 = none
     uint64_t pick_tick = 0;
-    uint64_t scene_gen = 0;      // bumped by every upload / build
+    uint64_t scene_gen = 0;      // bumped once by every adopted tree (adopt_tree)
     // pt_refit_bvh: the boxes and records of the tree are rewritten on the caller's stream; geom_gen counts the refits and a side
     // stream (PT_OPT_OVERLAP) waits for geom_ev before its first path kernel after one (the light list is re-collected too)
     uint64_t geom_gen = 0;
@@ -255,10 +272,11 @@ inline uint32_t wave_sample_group_log2(uint32_t spp, int cap) {
 int wave_reserve(pt_ctx* c, const KParams& P, int work_tiles);   // path records for this call, allocated now
 // PT_OPT_TIMING: marks the end of a stage of the running call on the context's stream (no-op when timing is off)
 int stage_mark(pt_ctx* c, int kind_of_work_since_last_mark);
-// device BVH builder (pt_build.hip)
-int build_bvh_impl(pt_ctx* c, const float* verts, size_t n_verts, const int32_t* tris, size_t n_tris, int algo, bool* too_deep,
+// device BVH builder (pt_build.hip), a maker: the tree over the mesh into `out` (its build_ms set), the context's own tree untouched.
+// PT_OPT_BUILD_ALGO 1 falls back to the LBVH inside when PLOC's tree gets too deep.  id_map: the id triangle t reports (default t)
+int build_bvh_impl(pt_ctx* c, const float* verts, size_t n_verts, const int32_t* tris, size_t n_tris, DevTree& out,
                    const int32_t* id_map = nullptr);
-// pt_refit_bvh's per-tree state (pt_refit.hip): released wherever the tree is replaced or the context destroyed
+// pt_refit_bvh's per-tree state (pt_refit.hip): released where the tree is replaced (adopt_tree) or the context destroyed
 void refit_release(pt_ctx* c);
 // pt_denoise's and pt_frame_error's scratch (pt_denoise.hip)
 void denoise_release(pt_ctx* c);

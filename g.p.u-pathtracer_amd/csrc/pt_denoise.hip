@@ -275,7 +275,7 @@ __global__ void __launch_bounds__(PTD_BLOCK) k_temporal(const TmArgs A) {
 }
 
 // pt_frame_error: rse of pixel i in binary32 (include/ptmi.h states the formula); per block the sum of rse in double and the
-// number of pixels above the threshold, by the tree reduction of k_tree_cost (ptmi.hip): no atomics, no fences, the same
+// number of pixels above the threshold, by the tree reduction of k_tree_cost (pt_tree.hip): no atomics, no fences, the same
 // figure run after run
 __global__ void __launch_bounds__(256) k_frame_error(const float2* __restrict__ moments, uint32_t n_pix, float nm1, float threshold,
                                                      double* __restrict__ sums, uint32_t* __restrict__ counts) {
@@ -328,7 +328,7 @@ extern "C" int pt_render_aux(pt_ctx* c, const pt_camera* cam, const pt_params* p
     KParams P;
     std::memset(&P, 0, sizeof P);
     P.sc.nodes = c->tree.d_nodes;
-    P.sc.tris = c->tree.d_tris;
+    P.sc.tris = c->tree.d_nodes;
     P.sc.spheres = c->d_spheres;
     P.sc.n_spheres = c->n_spheres;
     std::memcpy(P.ksph, c->h_spheres, sizeof P.ksph);

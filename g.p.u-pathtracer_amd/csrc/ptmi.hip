@@ -1,5 +1,5 @@
-// ptmi.hip — C ABI of libptmi.so (include/ptmi.h): context, scene upload + gfx950
-// re-layout, launches.  The kernels are in pt_kernels.h.
+// ptmi.hip — C ABI of libptmi.so (include/ptmi.h): context, materials and spheres, launches.
+// The kernels are in pt_kernels.h; the tree (pt_upload_bvh, pt_build_bvh) is pt_tree.hip's.
 //
 // Replaces BasicScene::launchKernel (GpuPathTracer/tracer.cu:405-415) and the device
 // buffer set-up of GpuPathTracer/BasicScene.cpp:138-149,:214-215,:297-313.
@@ -13,7 +13,6 @@
 #include <vector>
 
 #include "pt_ctx.h"
-#include "pt_scene_build.h"
 
 static_assert(sizeof(pt_sphere) == 44, "pt_sphere must match the reference Sphere (44 B)");
 static_assert(sizeof(pt_sphere_d) == sizeof(pt_sphere), "device sphere mirror");
@@ -25,8 +24,6 @@ thread_local std::string g_err;
 using namespace ptmi;
 
 namespace ptmi {
-static int tree_cost_impl(pt_ctx* c, double* node_visits, double* tri_tests);
-
 // PT_KERNEL_AUTO: reads the trials' events once they have all completed (wait = false: only if that needs no waiting) and decides
 static bool auto_decide(pt_ctx* c, pt_ctx::AutoPick& a, bool wait) {
     using AP = pt_ctx::AutoPick;
@@ -68,68 +65,6 @@ int stage_mark(pt_ctx* c, int kind) {
     c->stage_kind[c->stage_used] = kind;   // kind of the work that ENDS at this event
     c->stage_used++;
     return PT_OK;
-}
-
-// refine (leaves of at most PT_OPT_LEAF_MAX references), optimise (PT_OPT_OPTIMIZE), emit, upload: the tree `X` becomes the context's
-static int install_tree(pt_ctx* c, ptscene::Tree& X, int32_t max_id) {
-    TreeState& t = c->tree;
-    ptscene::refine(X, (uint32_t)c->opt_leaf_max);
-    t.opt_cost[0] = t.opt_cost[1] = 0.0;
-    if (c->opt_optimize > 0 && c->opt_tri_test == 0) {   // every node re-inserted where the area cost grows least (pt_tree_opt.h)
-        double before = 0.0, after = 0.0;
-        if (ptscene::optimize(X, c->opt_optimize, 64, before, after)) { t.opt_cost[0] = before; t.opt_cost[1] = after; }
-    }
-    ptscene::Output O;
-    ptscene::emit(X, PT_MAX_TOP, O, c->opt_tri_test == 1);
-    const size_t nb = O.bin.size() * sizeof(float), tb = O.rec.size() * sizeof(float), wb = O.wide.size() * sizeof(float);
-    if ((nb + tb + wb) / 16 >= (size_t)PT_SENTINEL) return fail(c, PT_ERR_INVALID, "pt_upload_bvh: scene too large for 32-bit links");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    refit_release(c);
-    (void)hipFree(t.d_nodes); t.d_nodes = nullptr;
-    t.d_tris = nullptr;
-    t.has_bvh = false;
-    HIP_TRY(c, hipMalloc((void**)&t.d_nodes, nb + tb + wb));
-    t.d_tris = t.d_nodes;  // one item buffer: links index it directly
-    HIP_TRY(c, hipMemcpy(t.d_nodes, O.bin.data(), nb, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy((char*)t.d_nodes + nb, O.rec.data(), tb, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy((char*)t.d_nodes + nb + tb, O.wide.data(), wb, hipMemcpyHostToDevice));
-    t.records_woop = c->opt_tri_test == 1;
-    t.wide_root = O.wide_root_f4;
-    t.wide_top_layout = O.n_top_wide;
-    t.wide_depth = O.depth_wide;
-    t.n_wide = O.wide.size() / 16;
-    t.n_top_layout = O.n_top_bin;
-    t.n_inner = O.bin.size() / 16;
-    t.n_refs = O.n_refs;
-    t.n_leaves = O.n_leaves;
-    t.max_depth = O.depth_bin;
-    t.scene_bytes = nb + tb + wb;
-    t.max_tri_id = max_id;
-    t.has_bvh = true;
-    t.build_ms = -1.f;   // no device build stands behind this tree (optimise_device_tree puts it back when one does)
-    c->scene_gen++;
-    return PT_OK;
-}
-
-// PT_OPT_OPTIMIZE on a tree the DEVICE built (pt_build_bvh, PT_OPT_REBUILD): binary nodes + the records' ids come back to the host, the
-// hierarchy is optimised like an uploaded one and installed in its place; the device build's time stays on the context.
-// by_id[id] = the nine vertex floats of triangle `id` (the caller's own: records are re-encoded from them bit for bit).
-static int optimise_device_tree(pt_ctx* c, const std::vector<const float*>& by_id, int32_t max_id) {
-    if (c->opt_optimize <= 0 || !c->tree.has_bvh || c->tree.records_woop) return PT_OK;
-    const size_t n_bin = (size_t)c->tree.n_inner, n_rec = (size_t)c->tree.n_refs;
-    std::vector<float> bin(16 * n_bin), rec(16 * n_rec);
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(bin.data(), c->tree.d_nodes, bin.size() * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(rec.data(), (const char*)c->tree.d_nodes + bin.size() * sizeof(float), rec.size() * sizeof(float), hipMemcpyDeviceToHost));
-    ptscene::Tree X;
-    std::string why;
-    if (!ptscene::from_items(bin.data(), n_bin, rec.data(), n_rec, by_id, X, why)) return fail(c, PT_ERR_DEVICE, "device-built tree: " + why);
-    const float device_ms = c->tree.build_ms;
-    const int rc = install_tree(c, X, max_id);
-    if (rc == PT_OK) c->tree.build_ms = device_ms;
-    return rc;
 }
 
 // pt_set_option's table, one row per option: the member it sets, the values it takes and what a refused value is answered with.
@@ -215,7 +150,7 @@ int pt_destroy(pt_ctx* c) {
     if (!c) return PT_OK;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(c->tree.d_nodes);  // d_tris aliases it
+    (void)hipFree(c->tree.d_nodes);
     (void)hipFree(c->d_spheres);
     (void)hipFree(c->d_tri_matid);
     (void)hipFree(c->d_mat_table);
@@ -305,123 +240,6 @@ int pt_upload(pt_ctx* c, void* dst, const void* src, size_t bytes) {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return PT_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-// Scene upload: validate the reference Compact arrays (CudaBVH.cpp:121-270), then re-lay
-// them out for the gfx950 kernels:
-//   nodes  : same 64-byte record; the top PT_MAX_TOP nodes in breadth-first order (any prefix
-//            of them can be mirrored in LDS), the rest depth-first (a parent next to its first
-//            inner child); links rewritten from byte offsets to float4 indices
-//   tris   : 48-byte records {v0.xyz, id | e1.xyz, last | e2.xyz, 0}: the edge subtraction
-//            of cudaUtils.h:177-178 is hoisted to upload (same IEEE result), the index
-//            remap of :452-456 and the 16-byte terminator fetch of :410-413 disappear
-int pt_upload_bvh(pt_ctx* c, const float* nodes, size_t n_node_vec4, const float* tri_verts, size_t n_tri_vec4,
-                  const int32_t* tri_index, size_t n_index) {
-    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
-    if (!nodes || !tri_verts || !tri_index) return fail(c, PT_ERR_INVALID, "pt_upload_bvh: null array");
-    if (n_node_vec4 < 4 || (n_node_vec4 % 4) != 0) return fail(c, PT_ERR_INVALID, "pt_upload_bvh: node array must hold whole 4-vec4 nodes");
-    if (n_index != n_tri_vec4) return fail(c, PT_ERR_INVALID, "pt_upload_bvh: index array must parallel the triangle array");
-    if (n_node_vec4 * 16 >= (size_t)PT_SENTINEL || n_tri_vec4 >= (size_t)0x7fffffff)
-        return fail(c, PT_ERR_INVALID, "pt_upload_bvh: scene too large for 32-bit links");
-
-    ptscene::Tree T;
-    std::string perr;
-    if (!ptscene::parse(nodes, n_node_vec4, tri_verts, n_tri_vec4, tri_index, T, perr))
-        return fail(c, PT_ERR_INVALID, "pt_upload_bvh: " + perr);
-    int32_t max_id = -1;
-    for (const ptscene::Ref& r : T.refs) max_id = std::max(max_id, r.id);
-    if (c->d_tri_matid && (size_t)max_id >= c->n_tri_matid)
-        return fail(c, PT_ERR_INVALID, "pt_upload_bvh: the triangle-material array on this context does not cover this BVH's triangle ids (clear or re-upload it first)");
-    const int rebuild = c->opt_tri_test == 0 ? c->opt_rebuild : 0;
-    auto recluster = [&]() -> int {
-        // PT_OPT_REBUILD: keep the caller's TRIANGLES, not its hierarchy — the distinct triangles of the
-        // Compact arrays (a spatial-split builder lists some more than once, each time in full) are
-        // clustered again on the device (pt_build.h).  The closest hit does not depend on the tree, so the
-        // images are the same bit for bit; whether the new tree is faster depends on the scene.
-        std::vector<int32_t> ids;
-        std::vector<float> verts;
-        {
-            std::vector<const ptscene::Ref*> sorted;
-            sorted.reserve(T.refs.size());
-            for (const ptscene::Ref& r : T.refs) sorted.push_back(&r);
-            std::sort(sorted.begin(), sorted.end(), [](const ptscene::Ref* a, const ptscene::Ref* b) { return a->id < b->id; });
-            for (const ptscene::Ref* r : sorted) {
-                if (!ids.empty() && ids.back() == r->id) continue;
-                ids.push_back(r->id);
-                verts.insert(verts.end(), r->v, r->v + 9);
-            }
-        }
-        std::vector<int32_t> tri_rows(3 * ids.size());
-        for (size_t i = 0; i < tri_rows.size(); i++) tri_rows[i] = (int32_t)i;
-        bool too_deep = false;
-        int rc = build_bvh_impl(c, verts.data(), verts.size() / 3, tri_rows.data(), ids.size(), c->opt_build_algo, &too_deep, ids.data());
-        if (rc != PT_OK && too_deep && c->opt_build_algo == 1)
-            rc = build_bvh_impl(c, verts.data(), verts.size() / 3, tri_rows.data(), ids.size(), 0, &too_deep, ids.data());
-        return rc;
-    };
-    auto install = [&](ptscene::Tree& X) -> int { return install_tree(c, X, max_id); };
-    auto optimise_reclustered = [&]() -> int {
-        if (c->opt_optimize <= 0) return PT_OK;
-        std::vector<const float*> by_id((size_t)max_id + 1, nullptr);
-        for (const ptscene::Ref& r : T.refs) if (!by_id[(size_t)r.id]) by_id[(size_t)r.id] = r.v;
-        return optimise_device_tree(c, by_id, max_id);
-    };
-    if (rebuild == 1) {
-        const int rc = recluster();
-        return rc == PT_OK ? optimise_reclustered() : rc;
-    }
-    {
-        const int rc = install(T);
-        if (rc != PT_OK) return rc;
-    }
-    if (rebuild == 2 && c->tree.n_wide > 0) {
-        // PT_OPT_REBUILD 2: the caller's hierarchy is up; build the re-clustered one beside it and keep whichever costs a
-        // random ray fewer wide-node visits (pt_tree_cost).  A failure on the way leaves the caller's tree in place.
-        double cost_a = 0.0, cost_b = 0.0, unused = 0.0;
-        if (tree_cost_impl(c, &cost_a, &unused) != PT_OK) return PT_OK;
-        const TreeState mine = c->tree;
-        c->tree.d_nodes = nullptr;   // the builder frees the context's buffer before it installs its own
-        c->tree.d_tris = nullptr;
-        const bool built = recluster() == PT_OK && c->tree.d_nodes != nullptr && optimise_reclustered() == PT_OK && c->tree.d_nodes != nullptr;
-        if (built && tree_cost_impl(c, &cost_b, &unused) == PT_OK && cost_b < cost_a) {
-            (void)hipFree(mine.d_nodes);
-        } else {
-            if (c->tree.d_nodes != mine.d_nodes) (void)hipFree(c->tree.d_nodes);
-            c->tree = mine;
-            c->err.clear();
-        }
-        refit_release(c);   // made for neither tree (pt_refit_bvh makes it again for the one kept)
-        c->scene_gen++;
-    }
-    return PT_OK;
-}
-
-// ---- pt_build_bvh: the BVH built on the device (pt_build.h) ---------------------------------
-int pt_build_bvh(pt_ctx* c, const float* verts, size_t n_verts, const int32_t* tris, size_t n_tris) {
-    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
-    bool too_deep = false;
-    int rc = build_bvh_impl(c, verts, n_verts, tris, n_tris, c->opt_build_algo, &too_deep);
-    // PLOC on degenerate input (hundreds of identical boxes: one merge per round, a chain): the Karras
-    // hierarchy separates equal keys by position and stays balanced
-    if (rc != PT_OK && too_deep && c->opt_build_algo == 1) rc = build_bvh_impl(c, verts, n_verts, tris, n_tris, 0, &too_deep);
-    if (rc == PT_OK && c->opt_optimize > 0 && c->opt_presplit == 0) {   // PT_OPT_OPTIMIZE: the built hierarchy goes through the host optimiser
-        std::vector<float> flat(9 * n_tris);
-        std::vector<const float*> by_id(n_tris);
-        for (size_t t = 0; t < n_tris; t++) {
-            for (int k = 0; k < 3; k++) std::memcpy(&flat[9 * t + 3 * (size_t)k], verts + 3 * (size_t)tris[3 * t + (size_t)k], 3 * sizeof(float));
-            by_id[t] = &flat[9 * t];
-        }
-        rc = optimise_device_tree(c, by_id, (int32_t)n_tris - 1);
-    }
-    return rc;
-}
-
-int pt_last_build_ms(pt_ctx* c, float* ms) {
-    if (!c || !ms) return fail(c, PT_ERR_INVALID, "pt_last_build_ms: null argument");
-    if (c->tree.build_ms < 0.f) return fail(c, PT_ERR_INVALID, "pt_last_build_ms: the tree on this context was not built on the device");
-    *ms = c->tree.build_ms;
     return PT_OK;
 }
 
@@ -517,17 +335,6 @@ int pt_upload_spheres(pt_ctx* c, const pt_sphere* spheres, size_t n) {
     return PT_OK;
 }
 
-int pt_scene_info(pt_ctx* c, uint64_t* n_inner, uint64_t* n_refs, uint64_t* n_leaves, uint32_t* max_depth, uint64_t* bytes) {
-    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
-    if (!c->tree.has_bvh) return fail(c, PT_ERR_NO_SCENE, "pt_scene_info: no BVH uploaded");
-    if (n_inner) *n_inner = c->tree.n_inner;
-    if (n_refs) *n_refs = c->tree.n_refs;
-    if (n_leaves) *n_leaves = c->tree.n_leaves;
-    if (max_depth) *max_depth = c->tree.max_depth;
-    if (bytes) *bytes = c->tree.scene_bytes;
-    return PT_OK;
-}
-
 // ---------------------------------------------------------------------------------------
 // pt_render in steps, in the order pt_render_moments runs them: check the arguments, bring the light list up to date, fill the
 // kernel arguments, PLAN the call (plan_call: every decision about what runs and with which buffers, made once), take the
@@ -580,7 +387,7 @@ static int refresh_tri_lights(pt_ctx* c, const pt_params* p) {
 static int fill_params(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, const pt_camera* cam, const pt_params* p, uint32_t spp, KParams& P) {
     std::memset(&P, 0, sizeof P);
     P.sc.nodes = c->tree.d_nodes;
-    P.sc.tris = c->tree.d_tris;
+    P.sc.tris = c->tree.d_nodes;   // one item buffer
     P.sc.spheres = c->d_spheres;
     P.sc.n_spheres = c->n_spheres;
     std::memcpy(P.ksph, c->h_spheres, sizeof P.ksph);
@@ -888,88 +695,6 @@ int pt_render_moments(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, float* mo
     return PT_OK;
 }
 
-// pt_tree_cost: one lane per wide node; out[0] = root area, out[1] = sum of inner-child areas, out[2] = sum of leaf area x records
-// (per-block partial sums, added up on the host in block order: the figure is reproducible, so a choice made on it is too)
-__global__ void __launch_bounds__(256) k_tree_cost(const float4* __restrict__ items, uint64_t wide_root, uint32_t n_wide, double* out) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    double inner = 0.0, leaf = 0.0, root = 0.0;
-    if (i < n_wide) {
-        const float4* nd = items + wide_root + 4 * (size_t)i;
-        const float4 q0 = nd[0], q1 = nd[1], q2 = nd[2], q3 = nd[3];
-        const float sc[3] = {q0.w, q3.z, q3.w};
-        const uint32_t ql[3] = {__float_as_uint(q1.x), __float_as_uint(q1.y), __float_as_uint(q1.z)};
-        const uint32_t qh[3] = {__float_as_uint(q1.w), __float_as_uint(q2.x), __float_as_uint(q2.y)};
-        const int link[4] = {__float_as_int(q2.z), __float_as_int(q2.w), __float_as_int(q3.x), __float_as_int(q3.y)};
-        float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-        for (int k = 0; k < 4; k++) {
-            float d[3];
-            bool used = true;
-            for (int a = 0; a < 3; a++) {
-                const int l = (int)((ql[a] >> (8 * k)) & 0xffu), h = (int)((qh[a] >> (8 * k)) & 0xffu);
-                if (l > h) used = false;   // an unused slot holds an inverted box
-                d[a] = (float)(h - l) * sc[a];
-                if (l <= h) { lo[a] = fminf(lo[a], (float)l * sc[a]); hi[a] = fmaxf(hi[a], (float)h * sc[a]); }
-            }
-            if (!used) continue;
-            const double area = 2.0 * ((double)d[0] * d[1] + (double)d[1] * d[2] + (double)d[2] * d[0]);
-            if (link[k] >= 0) {
-                inner += area;
-            } else {
-                int n = 0;
-                for (size_t r = (size_t)(~link[k] & ~3);; r += 4) {
-                    n++;
-                    if (__float_as_int(items[r + 1].w) != 0 || n >= 64) break;   // the record's `last` flag
-                }
-                leaf += area * (double)n;
-            }
-        }
-        if (i == 0) {
-            const double dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
-            root = 2.0 * (dx * dy + dy * dz + dz * dx);
-        }
-    }
-    // block reduction through LDS, one atomic per block and term
-    __shared__ double s_in[256], s_lf[256];
-    s_in[threadIdx.x] = inner; s_lf[threadIdx.x] = leaf;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) { s_in[threadIdx.x] += s_in[threadIdx.x + off]; s_lf[threadIdx.x] += s_lf[threadIdx.x + off]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { out[1 + 2 * (size_t)blockIdx.x] = s_in[0]; out[2 + 2 * (size_t)blockIdx.x] = s_lf[0]; }
-    if (i == 0) out[0] = root;
-}
-
-namespace ptmi {
-static int tree_cost_impl(pt_ctx* c, double* node_visits, double* tri_tests) {
-    const unsigned n_blocks = (unsigned)((c->tree.n_wide + 255) / 256);
-    const size_t n_out = 1 + 2 * (size_t)n_blocks;
-    double* d_out = nullptr;
-    HIP_TRY(c, hipMalloc((void**)&d_out, n_out * sizeof(double)));
-    hipLaunchKernelGGL(k_tree_cost, dim3(n_blocks), dim3(256), 0, c->stream, c->tree.d_nodes, c->tree.wide_root, (uint32_t)c->tree.n_wide, d_out);
-    hipError_t e = hipGetLastError();
-    std::vector<double> h(n_out, 0.0);
-    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_out, n_out * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_out);
-    if (e != hipSuccess) return hip_fail(c, e, "pt_tree_cost");
-    if (!(h[0] > 0.0)) return fail(c, PT_ERR_INVALID, "pt_tree_cost: degenerate root box");
-    double inner = 0.0, leaf = 0.0;
-    for (unsigned b = 0; b < n_blocks; b++) { inner += h[1 + 2 * (size_t)b]; leaf += h[2 + 2 * (size_t)b]; }
-    *node_visits = (h[0] + inner) / h[0];
-    *tri_tests = leaf / h[0];
-    return PT_OK;
-}
-}  // namespace ptmi
-
-int pt_tree_cost(pt_ctx* c, double* node_visits, double* tri_tests) {
-    if (!c || !node_visits || !tri_tests) return fail(c, PT_ERR_INVALID, "pt_tree_cost: null argument");
-    if (!c->tree.has_bvh || c->tree.wide_root == 0 || c->tree.n_wide == 0) return fail(c, PT_ERR_NO_SCENE, "pt_tree_cost: no 4-wide tree on this context");
-    if (c->tree.records_woop) return fail(c, PT_ERR_UNSUPPORTED, "pt_tree_cost: reads the Moller-Trumbore records' leaf terminators");
-    HIP_TRY(c, hipSetDevice(c->device));
-    return tree_cost_impl(c, node_visits, tri_tests);
-}
-
 int pt_auto_choice(pt_ctx* c, int* kernel, float* ms_persistent, float* ms_wavefront) {
     if (!c || !kernel) return fail(c, PT_ERR_INVALID, "pt_auto_choice: null argument");
     *kernel = PT_KERNEL_AUTO;
@@ -992,7 +717,7 @@ int pt_trace_rays(pt_ctx* c, const float* rays_dev, size_t n, int cull, float* t
     HIP_TRY(c, hipSetDevice(c->device));
     KScene sc;
     std::memset(&sc, 0, sizeof sc);
-    sc.nodes = c->tree.d_nodes; sc.tris = c->tree.d_tris; sc.spheres = nullptr; sc.n_spheres = 0; sc.has_bvh = 1;
+    sc.nodes = sc.tris = c->tree.d_nodes; sc.spheres = nullptr; sc.n_spheres = 0; sc.has_bvh = 1;
     if (c->opt_timing) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
     const float4* r4 = (const float4*)rays_dev;
     sc.stack_n = PT_STACK_CAP;
