@@ -20,6 +20,12 @@ static int build_with(pt_ctx* c, const float* verts, size_t n_verts, const int32
         if (tris[i] < 0 || (size_t)tris[i] >= n_verts) return fail(c, PT_ERR_INVALID, "pt_build_bvh: vertex index out of range");
     for (size_t i = 0; i < 3 * n_verts; i++)
         if (!(std::fabs(verts[i]) <= 3.0e38f)) return fail(c, PT_ERR_INVALID, "pt_build_bvh: non-finite vertex");
+    {   // the extent of the mesh must be a finite binary32 on every axis: the 4-wide encoder's grid step is ext / 255 (pt_items.h)
+        float lo[3] = {verts[0], verts[1], verts[2]}, hi[3] = {verts[0], verts[1], verts[2]};
+        for (size_t i = 0; i < 3 * n_verts; i++) { lo[i % 3] = std::min(lo[i % 3], verts[i]); hi[i % 3] = std::max(hi[i % 3], verts[i]); }
+        for (int a = 0; a < 3; a++)
+            if (!(hi[a] - lo[a] <= 3.402823466e+38f)) return fail(c, PT_ERR_INVALID, "pt_build_bvh: the mesh's extent overflows binary32");
+    }
     if (c->d_tri_matid && n_tris > c->n_tri_matid)
         return fail(c, PT_ERR_INVALID, "pt_build_bvh: the triangle-material array on this context does not cover this mesh (clear or re-upload it first)");
 
@@ -165,7 +171,8 @@ static int build_with(pt_ctx* c, const float* verts, size_t n_verts, const int32
             HIP_TRY(c, hipMemcpyAsync(&last_keep, Q.keep + (Q.n_c - 1), sizeof(int), hipMemcpyDeviceToHost, st));
             HIP_TRY(c, hipStreamSynchronize(st));
             const int next = last_pos + last_keep;
-            if (next >= Q.n_c || next < 1) return fail(c, PT_ERR_DEVICE, "pt_build_bvh: PLOC round made no progress");
+            // no pair chose each other: every union's area overflowed binary32 (coordinates near 1e30) — the Karras hierarchy needs no areas
+            if (next >= Q.n_c || next < 1) { *too_deep = true; return fail(c, PT_ERR_DEVICE, "pt_build_bvh: PLOC round made no progress"); }
             Q.n_c = next;
             std::swap(Q.cl, Q.cl_next);
         }

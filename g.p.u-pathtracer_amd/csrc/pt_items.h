@@ -1,6 +1,8 @@
 // pt_items.h — encoders of the two 64-byte items the walks fetch, shared by the host re-layout
 // (pt_scene_build.h: trees that arrive through pt_upload_bvh) and the device builder
 // (pt_build.h: pt_build_bvh), so both produce bit-identical items from the same boxes / vertices.
+// The words of every item, links and the dummy record included, are written down once in DESIGN.md 3.5; tests/tree_audit.py restates
+// both encoders in numpy and tests/test_gpu_tree_audit.py holds the trees in device memory against them, bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,7 +1,7 @@
 // pt_tree.hip — the acceleration structure of a context: the makers that produce a tree as a value (DevTree, pt_ctx.h) from the
 // caller's hierarchy, from the device builder (pt_build.hip) or from a device-built tree run through the host optimiser; its
 // area cost; adopt_tree, the one place that puts a tree on the context; and the entry points made of them (pt_upload_bvh,
-// pt_build_bvh, pt_last_build_ms, pt_scene_info, pt_tree_cost).  One translation unit of libptmi.so (pt_ctx.h).
+// pt_build_bvh, pt_last_build_ms, pt_scene_info, pt_tree_cost, pt_tree_items).  One translation unit of libptmi.so (pt_ctx.h).
 #include <cstring>
 #include <utility>
 
@@ -261,6 +261,20 @@ int pt_tree_cost(pt_ctx* c, double* node_visits, double* tri_tests) {
     if (c->tree.records_woop) return fail(c, PT_ERR_UNSUPPORTED, "pt_tree_cost: reads the Moller-Trumbore records' leaf terminators");
     HIP_TRY(c, hipSetDevice(c->device));
     return tree_cost(c, c->tree, node_visits, tri_tests);
+}
+
+// read-only view of the item buffer: what an audit of the tree downloads
+int pt_tree_items(pt_ctx* c, const void** items_dev, uint64_t* n_binary, uint64_t* n_records, uint64_t* n_wide, uint32_t* wide_depth) {
+    if (!c || !items_dev) return fail(c, PT_ERR_INVALID, "pt_tree_items: null argument");
+    if (!c->tree.has_bvh || !c->tree.d_nodes) return fail(c, PT_ERR_NO_SCENE, "pt_tree_items: no BVH on this context");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // a pending pt_refit_bvh has written its boxes
+    *items_dev = c->tree.d_nodes;
+    if (n_binary) *n_binary = c->tree.n_inner;
+    if (n_records) *n_records = c->tree.n_refs;
+    if (n_wide) *n_wide = c->tree.n_wide;
+    if (wide_depth) *wide_depth = c->tree.wide_depth;
+    return PT_OK;
 }
 
 }  // extern "C"

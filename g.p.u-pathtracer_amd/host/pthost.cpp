@@ -175,11 +175,20 @@ struct Builder {
             if (pa <= pos) left.box.grow(a);
             if (pa >= pos) right.box.grow(a);
             if ((pa < pos && pb > pos) || (pa > pos && pb < pos)) {
-                float t = std::min(1.f, std::max(0.f, (pos - pa) / (pb - pa)));
-                Vec3 p{a.x + (b.x - a.x) * t, a.y + (b.y - a.y) * t, a.z + (b.z - a.z) * t};
-                p.at(ax) = pos;
-                left.box.grow(p);
-                right.box.grow(p);
+                // the crossing in binary64, then one binary32 step to either side: a crossing rounded to nearest left the part of
+                // the edge between it and the exact point outside both boxes (tests/test_gpu_tree_audit.py: coverage); the clip
+                // below keeps the boxes inside the reference's own
+                const double t = std::min(1.0, std::max(0.0, ((double)pos - pa) / ((double)pb - pa)));
+                const float px = (float)(a.x + ((double)b.x - a.x) * t), py = (float)(a.y + ((double)b.y - a.y) * t),
+                            pz = (float)(a.z + ((double)b.z - a.z) * t);
+                Vec3 plo{std::nextafter(px, -INFINITY), std::nextafter(py, -INFINITY), std::nextafter(pz, -INFINITY)};
+                Vec3 phi{std::nextafter(px, INFINITY), std::nextafter(py, INFINITY), std::nextafter(pz, INFINITY)};
+                plo.at(ax) = pos;
+                phi.at(ax) = pos;
+                left.box.grow(plo);
+                left.box.grow(phi);
+                right.box.grow(plo);
+                right.box.grow(phi);
             }
         }
         left.box.hi.at(ax) = pos;

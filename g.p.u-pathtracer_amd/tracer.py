@@ -242,6 +242,17 @@ class PathTracer:
         self._check(self._lib.pt_tree_cost(self._ctx, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def tree_items(self):
+        """The item buffer of the tree on the context, downloaded (pt_tree_items; layout: DESIGN.md 3.5): three float32 arrays of
+        shape (n, 16) — binary nodes, records, wide nodes (views of one buffer; integer words through .view(np.int32)) — and the
+        depth of the 4-wide tree.  Synchronises."""
+        p, nb, nr, nw, d = C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint32()
+        self._check(self._lib.pt_tree_items(self._ctx, C.byref(p), C.byref(nb), C.byref(nr), C.byref(nw), C.byref(d)))
+        n = nb.value + nr.value + nw.value
+        buf = np.empty((n, 16), np.float32)
+        self._check(self._lib.pt_download(self._ctx, buf.ctypes.data, p.value, buf.nbytes))
+        return buf[:nb.value], buf[nb.value:nb.value + nr.value], buf[nb.value + nr.value:], d.value
+
     def wave_stats(self):
         """pt_get_wave_stats of the last instrumented launch.  Under PT_KERNEL_WAVEFRONT "it_shade" holds the 64-ray groups walked by
         the bounce-0 packet walk (PT_OPT_FIRST_WALK 1; include/ptmi.h), not shading passes; "walk_free" the rays PT_OPT_ROOT_CULL 2 kept

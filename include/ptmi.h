@@ -345,7 +345,10 @@ int pt_upload_spheres(pt_ctx* ctx, const pt_sphere* spheres, size_t n_spheres);
  * SAH/SBVH builder's.  Rendered images equal those over an uploaded hierarchy except for rays that graze a
  * bounding plane (see PT_OPT_REBUILD: a handful of pixels per 2 M at 800 k triangles, none on the small
  * scenes of the test suite).  Triangle ids are the row numbers of `tris`.  PT_OPT_LEAF_MAX (default 2)
- * = triangles per leaf.  verts: float[n_verts][3], tris: int32[n_tris][3]; host arrays, copied. */
+ * = triangles per leaf.  verts: float[n_verts][3], tris: int32[n_tris][3]; host arrays, copied.
+ * PT_ERR_INVALID: a coordinate that is not finite or has |x| > 3.0e38, or a mesh whose extent max - min on an axis is not a finite
+ * binary32 (-2e38 beside +2e38: the 4-wide node's grid step is extent / 255, pt_items.h).  pt_refit_bvh cannot refuse: its caller
+ * keeps the moved mesh within that extent.  pt_upload_bvh takes the caller's boxes as they are (the same limit holds for them). */
 int pt_build_bvh(pt_ctx* ctx, const float* verts, size_t n_verts, const int32_t* tris, size_t n_tris);
 int pt_last_build_ms(pt_ctx* ctx, float* ms_out);   /* device time of the build behind the tree on the context (pt_build_bvh or a
                                                        kept PT_OPT_REBUILD tree); PT_ERR_INVALID for an uploaded hierarchy */
@@ -570,6 +573,15 @@ int pt_auto_choice(pt_ctx* ctx, int* kernel, float* ms_persistent, float* ms_wav
  * *tri_tests   = sum over leaves of (area of the leaf's box x its triangle records) / area of the root.
  * Areas are those of the quantised boxes the walk tests.  Synchronises the context's stream. */
 int pt_tree_cost(pt_ctx* ctx, double* node_visits, double* tri_tests);
+/* The item buffer of the tree on the context, read-only (measurement; what tests/tree_audit.py reads): *items_dev = its device
+ * pointer, 64-byte items laid out [binary nodes][records][wide nodes] with *n_binary, *n_records and *n_wide items in the three
+ * sections (any of the counts may be NULL), *wide_depth = levels of the 4-wide tree.  The words of every item are written down in
+ * DESIGN.md 3.5.  *n_binary is the size of the section (what the links are relative to): a device-built tree with
+ * PT_OPT_LEAF_MAX > 1 keeps the binary nodes below its multi-record leaves there, unreachable.  Synchronises the context's stream,
+ * so a pending pt_refit_bvh is complete; the pointer is valid until the tree is replaced (pt_upload_bvh, pt_build_bvh) or the
+ * context destroyed.  PT_ERR_NO_SCENE without a tree, PT_ERR_INVALID for a NULL ctx or items_dev. */
+int pt_tree_items(pt_ctx* ctx, const void** items_dev, uint64_t* n_binary, uint64_t* n_records,
+                  uint64_t* n_wide, uint32_t* wide_depth);
 int pt_scene_info(pt_ctx* ctx, uint64_t* n_inner, uint64_t* n_tri_refs,
                   uint64_t* n_leaves, uint32_t* max_depth, uint64_t* device_bytes);
 
