@@ -84,6 +84,36 @@ def test_a_failed_call_changes_nothing(tree):
         t.close()
 
 
+def test_a_tree_deeper_than_64_is_refused_and_changes_nothing():
+    """comb(66) of tests/deep_trees.py: its last inner node is 65 edges below the root, one more than pt_upload_bvh parses, so the
+    call answers PT_ERR_INVALID under every PT_OPT_REBUILD; comb(65), the deepest tree it takes (stack depth 65), is still on the
+    context afterwards and still traces every half-cell ray as brute force does"""
+    import deep_trees as dt
+    held, deeper = dt.comb(65), dt.comb(66)
+    assert (held.max_depth, deeper.max_depth) == (65, 66)
+    rays = dt.cell_rays(held)
+    assert dt.binary_stack_depth(held, rays).min() == 65
+    t0, tri0, nrm0 = orc.trace_brute(held.mesh, rays, True)
+    t = g.PathTracer(0)
+    try:
+        t.upload_bvh(held)
+        before = t.scene_info(), t.tree_items()[3]
+        assert before[0]["max_depth"] == 65 and before[1] == 22
+        n, tr, ix = (np.ascontiguousarray(deeper.nodes, np.float32), np.ascontiguousarray(deeper.tris, np.float32),
+                     np.ascontiguousarray(deeper.index, np.int32))
+        for rebuild in (0, 1, 2):
+            t.set_option(g.OPT_REBUILD, rebuild)
+            rc = t._lib.pt_upload_bvh(t._ctx, n.ctypes.data, n.size // 4, tr.ctypes.data, tr.size // 4, ix.ctypes.data, ix.size)
+            assert rc == -1, rebuild                 # PT_ERR_INVALID
+        t.set_option(g.OPT_REBUILD, 0)
+        assert (t.scene_info(), t.tree_items()[3]) == before and t.last_build_ms() == -1.0
+        tg, ig, ng = gpu_trace(t, rays)
+        assert np.array_equal(ig, tri0) and np.array_equal(tg.view(np.int32), t0.view(np.int32))
+        assert np.array_equal(ng[tri0 >= 0], nrm0[tri0 >= 0]) and (tri0 >= 0).sum() == 66
+    finally:
+        t.close()
+
+
 # --------------------------------------------------------------------------------------- 2. every route hands refit a fresh tree
 @pytest.mark.parametrize("scene", ["cornell", "gto_sixteen"])
 def test_every_route_hands_refit_a_fresh_tree(scene):
