@@ -12,6 +12,9 @@ import orc
 
 F32 = np.float32
 H5 = np.array([1.0, 4.0, 6.0, 4.0, 1.0]) / 16.0
+# MSE(noisy 4 spp) / MSE(denoised 4 spp), both against many samples, that the defaults must reach on cornell_box:
+# the bar of test_denoise (the numpy filter over oracle renders) and of test_gpu_denoise (pt_denoise)
+QUALITY_K = 2.5
 
 
 # ---------------------------------------------------------------------------------------------------- float32 arithmetic

@@ -28,14 +28,9 @@ ROOT = os.path.join(HERE, "..", "..")
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import gpu_pathtracer_amd as g  # noqa: E402
 import orc  # noqa: E402
+from gpu_support import golden_camera  # noqa: E402
 
 REF_ASSETS = "/root/reference/Assets"
-
-
-def golden_camera(W, H):
-    cam = g.default_camera(W, H)
-    cam.dist = 18.0 * H / 1080.0  # the 1080p field of view at any test resolution
-    return cam
 
 
 def make_ref_hits():

@@ -227,3 +227,41 @@ def run_ref_config1(tmp_dir):
 def config1_blocks(img):
     B = CONFIG1_BLOCK
     return img.reshape(CONFIG1_H // B, B, CONFIG1_W // B, B, 3).mean(axis=(1, 3), dtype=np.float64).astype(np.float32)
+
+
+# ---- the room of the reference's CPU tracer (tests/golden/ref_room_radiance.npz) ------------------------------------------
+ROOM_GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_room_radiance.npz")
+EMISSION_SCALE = 0.4   # emission is scaled on this side (light transport is linear) so that no sample exceeds 1
+
+
+def reference_room():
+    """(fixture, mesh, spheres, camera, params) of the room of the reference's CpuRayTracer main.cpp:26-35 with the mesh of
+    tests/golden/ref_room_radiance.npz in it, for PT_FLAGS_CPU_TRACER (see test_reference_radiance): test_reference_radiance,
+    test_oracle."""
+    z = np.load(ROOM_GOLD)
+    W, H = int(z["width"]), int(z["height"])
+    mesh = g.Mesh.from_arrays(z["verts"] + z["mesh_pos"][None, :], z["tris"])
+
+    def sph(c, r, col, emi=(0, 0, 0)):
+        s = g.Sphere()
+        s.pos_rad[:] = (*c, r)
+        s.col[:] = col
+        s.emi[:] = emi
+        s.mat = g.MAT_DIFF
+        return s
+    # main.cpp:30-34; the EMIT sphere becomes a DIFF sphere with col 0 (its paths end there) and emission x 0.4
+    spheres = (g.Sphere * 5)(sph((0, 0, -1000), 1000, (1, 1, 1)), sph((-1004, 0, 0), 1000, (.85, .4, .4)),
+                             sph((1004, 0, 0), 1000, (.4, .4, .85)), sph((0, 1006, 0), 1000, (1, 1, 1)),
+                             sph((0, 0, 110), 100, (0, 0, 0), (2.2 * EMISSION_SCALE,) * 3))
+    pos = np.array([-2.0, -5.0, 2.5])                      # main.cpp:26
+    d = -pos / np.linalg.norm(pos)
+    xdir = np.cross([0, 0, 1], -d)                         # camera.cpp:23 (not normalised there either)
+    ydir = np.cross(xdir, d)
+    ydir /= np.linalg.norm(ydir)
+    cam = g.Camera()
+    cam.pos[:], cam.front[:], cam.right[:], cam.up[:] = pos, d, xdir, -ydir
+    cam.dist, cam.aspect, cam.fov = 2.0, W / H, 1.0
+    p = g.default_params(W, H, depth=64)
+    p.flags, p.cull_backfaces, p.tri_mat = g.FLAGS_CPU_TRACER, 0, g.MAT_DIFF
+    p.bk_color[:], p.tri_col[:], p.tri_emi[:] = (0, 0, 0), (.9, .9, .9), (0, 0, 0)
+    return z, mesh, spheres, cam, p

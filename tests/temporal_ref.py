@@ -4,11 +4,39 @@ temporal():  the contract of include/ptmi.h (pt_temporal): the projection into t
              bilinear weights) and every test of a tap in float32, in the stated order; the tap sums in float64.  Also returns
              the mask of FRAGILE pixels, where one rounding of difference between two float32 restatements could flip a decision.
 moved():     a camera panned about its `up`, moved along its `front` (dolly) or along its `right` (sideways).
+Also the inputs and bars that the CPU tests (test_temporal) and the GPU tests (test_gpu_temporal) of the feature share.
 """
 import numpy as np
 
 import gpu_pathtracer_amd as g
 from denoise_ref import F32, fma, vdot
+
+# The camera moves of the GPU comparison, applied to the golden camera (previous frame) to get the current one
+MOVES = {"static": {}, "pan": dict(pan_deg=2.0), "dolly": dict(dolly=0.5), "side": dict(side=0.3)}
+# The parameter sets of the GPU comparison
+PARAM_SETS = {"defaults": {}, "history1": dict(max_history=1.0), "plane0": dict(plane_tolerance=0.0), "normal-1": dict(normal_threshold=-1.0)}
+FRAGILE_MAX = 0.02
+# The quality sequence: cornell_box, QUALITY_FRAMES frames of QUALITY_SPP samples, the camera panning QUALITY_PAN degrees a frame.
+QUALITY_FRAMES, QUALITY_SPP, QUALITY_PAN = 8, 4, 1.0
+# gain = MSE(last frame alone) / MSE(history), both against 1024 spp at the last camera.  The numpy reference over oracle renders
+# at 80x60 measures 3.48 (test_reference_gain_on_oracle_renders asserts it); the bar for the GPU at 320x240 is 0.8 x that figure,
+# the margin for the other sample sets at the other resolution (DESIGN.md §10 f8).
+QUALITY_GAIN_CPU = 3.48
+QUALITY_K = 0.8 * QUALITY_GAIN_CPU
+ACCEPTED_MIN = 0.70
+
+
+def params(**kw):
+    d = dict(g.TEMPORAL_DEFAULTS)
+    d.update(kw)
+    return d
+
+
+def random_frames(W, H, seed):
+    rng = np.random.default_rng(seed)
+    cur, prev = (rng.uniform(0, 1, (H, W, 3)).astype(np.float32) for _ in range(2))
+    ln = rng.integers(1, 41, (H, W)).astype(np.float32)
+    return cur, prev, ln
 
 
 def moved(cam, pan_deg=0.0, dolly=0.0, side=0.0):

@@ -12,10 +12,9 @@ import pytest
 import gpu_pathtracer_amd as g
 import orc
 import denoise_ref as R
+from denoise_ref import QUALITY_K
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-# MSE(noisy 4 spp) / MSE(denoised 4 spp), both against many samples, that the defaults must reach on cornell_box
-QUALITY_K = 2.5
 
 
 def test_aux_and_denoise_are_declared_bound_and_exported():

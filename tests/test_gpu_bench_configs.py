@@ -12,7 +12,7 @@ import pytest
 
 import gpu_pathtracer_amd as g
 import orc
-from test_gpu_parity import gpu_render, golden_camera, l2, bvh_of
+from gpu_support import arbitrate, bvh_of, check, golden_camera, gpu_render, gpu_trace, oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -37,24 +37,6 @@ def ptd(request):
     t.upload_tree = (lambda name: bvh_of(name, split_alpha=-1.0)[1]) if request.param == "cheaper-tree" else (lambda name: bvh_of(name)[1])
     yield t
     t.close()
-
-
-_oracle_cache = {}
-
-
-def oracle(key, fn):
-    """one oracle render per configuration, shared by the kernel variants"""
-    if key not in _oracle_cache:
-        _oracle_cache[key] = fn()
-    return _oracle_cache[key]
-
-
-def check(acc, ref, what, max_diff):
-    n_diff = int(np.any(acc != ref, axis=-1).sum())
-    err = l2(acc, ref)
-    print(f"{what}: L2 {err:.3e}, differing pixels {n_diff} of {acc.shape[0] * acc.shape[1]}")
-    assert err < 1e-3
-    assert n_diff <= max_diff
 
 
 def test_bench_step_16spp_800k_full_frame(ptd):
@@ -213,45 +195,6 @@ def test_auto_times_both_layouts_and_keeps_one():
         t.close()
 
 
-def arbitrate(pt, mesh, bvh, sph, cam, p, frames, what, max_diff, oracle_key=None, materials=None, tri_material=None):
-    """Sample by sample (one pt_render per frame, N = 1) against the oracle's walk over `bvh`; every (frame, pixel) where the
-    two differ is replayed with the BRUTE-FORCE closest hit (orc.sample_pixels over the raw triangles: no tree, so no box
-    can cull anything) and the GPU must hold brute force's colour.  Returns (differing, of which the oracle's walk was off).
-    materials / tri_material: the per-triangle material table on the context, handed to both oracle renderers."""
-    mk = dict(materials=materials, tri_material=tri_material)
-    W, H = p.width, p.height
-    acc, rgba = pt.alloc_frame(W, H)
-    diffs = []
-    for f in frames:
-        q = g.Params.from_buffer_copy(p)
-        q.frame, q.sample_index = f, 1
-        pt.launch_kernel(acc.ptr, rgba.ptr, cam, q, 1)
-        pt.sync()
-        got = acc.download(np.float32, (H, W, 3))
-        ref = oracle((oracle_key, f), lambda: orc.render(bvh, sph, cam, q, 1, want_rgba=False, **mk)[0]) if oracle_key else \
-            orc.render(bvh, sph, cam, q, 1, want_rgba=False, **mk)[0]
-        ys, xs = np.nonzero(np.any(got != ref, axis=-1))
-        diffs += [(f, int(x), int(y), got[y, x].copy(), ref[y, x].copy()) for x, y in zip(xs, ys)]
-    acc.free()
-    rgba.free()
-    n_oracle_off = 0
-    for f, x, y, got, ref in diffs:
-        q = g.Params.from_buffer_copy(p)
-        q.frame, q.sample_index = f, 1
-        col, t_b, id_b = orc.sample_pixels([(x, y)], sph, cam, q, 1, mesh=mesh, **mk)
-        _, t_o, id_o = orc.sample_pixels([(x, y)], sph, cam, q, 1, bvh=bvh, **mk)
-        brute = orc.fold_samples(col, 1)[0]
-        seg = int(np.argmax((t_b[0, 0] != t_o[0, 0]) | (id_b[0, 0] != id_o[0, 0]))) if (np.any(t_b != t_o) or np.any(id_b != id_o)) else -1
-        print(f"  {what}: frame {f} pixel ({x},{y}) gpu {got} oracle {ref} brute {brute}; oracle's walk leaves brute force at segment {seg}: "
-              f"t {t_o[0, 0, seg] if seg >= 0 else None} id {id_o[0, 0, seg] if seg >= 0 else None} vs t {t_b[0, 0, seg] if seg >= 0 else None} id {id_b[0, 0, seg] if seg >= 0 else None}")
-        assert np.array_equal(got, brute), f"{what}: GPU differs from the brute-force arbiter at frame {f} pixel ({x},{y})"
-        n_oracle_off += int(not np.array_equal(ref, brute))
-    print(f"{what}: {len(diffs)} differing (frame, pixel) pairs of {len(frames) * W * H}, all equal to brute force on the GPU side; "
-          f"the oracle's binary walk was the one off in {n_oracle_off}")
-    assert len(diffs) <= max_diff
-    return len(diffs), n_oracle_off
-
-
 def test_bench_step_differing_pixels_are_brute_force_hits(ptd):
     """The 16 frames of the bench step, one by one: wherever the GPU's sample differs from the oracle's (the wide walk's
     outward-rounded boxes keep a grazing candidate that the binary tree's slab rounding culls), the GPU's colour is the
@@ -295,7 +238,6 @@ def test_big_scene_6400k_parity():
     (1) 200k incoherent rays + the primary rays of a 480x270 frame: (t, id, normal) == the brute-force oracle bit for bit;
     (2) one 1920x1080 frame, 2 spp, against the oracle's walk over the HOST tree of the same mesh: L2 < 1e-3, and every
     differing pixel arbitrated by brute force."""
-    from test_gpu_parity import gpu_trace
     mesh = g.scene_mesh("cornell_dragon_6400k")
     t = g.PathTracer(0)
     try:

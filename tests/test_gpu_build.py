@@ -11,7 +11,7 @@ import pytest
 
 import gpu_pathtracer_amd as g
 import orc
-from test_gpu_parity import gpu_trace, golden_camera
+from gpu_support import gpu_trace
 
 pytestmark = pytest.mark.gpu
 

@@ -11,7 +11,7 @@ every parity test and only show as a slowdown; and the options' ranges are writt
 import pytest
 
 import gpu_pathtracer_amd as g
-from test_gpu_parity import golden_camera, bvh_of
+from gpu_support import bvh_of, golden_camera, is_frame_kernel, is_pipeline
 
 pytestmark = pytest.mark.gpu
 W, H = 64, 32
@@ -42,14 +42,6 @@ def call(t, frame, depth=4, spp=1, flags=0, moments=None, call_no=0):
     ms = t.stage_ms()
     print(ms)
     return ms
-
-
-def is_pipeline(ms):
-    return ms["generate"] > 0 and ms["extend"] > 0 and ms["frame"] == 0
-
-
-def is_frame_kernel(ms):
-    return ms["frame"] > 0 and ms["generate"] == 0 and ms["extend"] == 0 and ms["shade"] == 0
 
 
 # id: (kernel, context arguments, call arguments, moments buffer, pipeline?, {stage: ran?})

@@ -21,8 +21,7 @@ import deep_trees as dt
 import gpu_pathtracer_amd as g
 import orc
 from scene_matrix import make_camera, spheres, tilted_grid_table
-from test_gpu_parity import gpu_trace, l2
-from test_materials import material
+from gpu_support import gpu_trace, is_frame_kernel, is_pipeline, l2, material
 
 pytestmark = pytest.mark.gpu
 
@@ -410,14 +409,6 @@ def test_woop_records_over_comb(D):
 
 
 # ------------------------------------------------------------------------------------------------ f. the wide / binary boundary
-def is_pipeline(ms):
-    return ms["generate"] > 0 and ms["extend"] > 0 and ms["frame"] == 0
-
-
-def is_frame_kernel(ms):
-    return ms["frame"] > 0 and ms["generate"] == 0 and ms["extend"] == 0 and ms["shade"] == 0
-
-
 @pytest.mark.parametrize("Wd", [23, 24])
 def test_wide_walk_gives_way_to_the_binary_walk(Wd):
     """stair(23): wide depth 23, 3 * 23 + 2 = 71 entries, the last tree the wide walk takes (three pushes at each level);

@@ -11,9 +11,8 @@ import pytest
 import gpu_pathtracer_amd as g
 import orc
 import denoise_ref as R
-from test_denoise import QUALITY_K
-from test_gpu_parity import golden_camera
-from test_gpu_refit import cornell_dragon_moved, soup_mesh
+from denoise_ref import QUALITY_K
+from gpu_support import Guides, compare_guides, cornell_dragon_moved, golden_camera, setup_scene, soup_mesh
 
 pytestmark = pytest.mark.gpu
 
@@ -26,78 +25,6 @@ def t():
     tr = g.PathTracer(0)
     yield tr
     tr.close()
-
-
-class Guides:
-    """Device guide buffers of one frame."""
-
-    def __init__(self, t, W, H):
-        self.t, self.W, self.H = t, W, H
-        self.alb, self.nrm, self.pos = (t.malloc(W * H * 16) for _ in range(3))
-        self.ids = t.malloc(W * H * 4)
-
-    def render(self, cam, p, with_ids=True):
-        self.t.render_aux(cam, p, self.alb.ptr, self.nrm.ptr, self.pos.ptr, self.ids.ptr if with_ids else None)
-
-    def download(self):
-        self.t.sync()
-        W, H = self.W, self.H
-        return (self.alb.download(np.float32, (H, W, 4)), self.nrm.download(np.float32, (H, W, 4)),
-                self.pos.download(np.float32, (H, W, 4)), self.ids.download(np.int32, (H, W)))
-
-    def free(self):
-        for b in (self.alb, self.nrm, self.pos, self.ids):
-            b.free()
-
-
-def ordered(x):
-    i = np.asarray(x, np.float32).view(np.int32).astype(np.int64)
-    return np.where(i < 0, -(i & 0x7FFFFFFF), i)
-
-
-def ulps(a, b):
-    return np.abs(ordered(a) - ordered(b))
-
-
-def compare_guides(got, ref, what):
-    """ids equal except at sphere / triangle ties (1e-6 relative in t); albedo exact; triangle t exact; positions and normals
-    within 2 ulp.  Returns the largest position / normal ulp distances seen."""
-    ga, gn, gp, gi = got
-    ra, rn, rp, ri, t_tri, t_sph = ref
-    tie = (ri != -1) & np.isfinite(t_sph) & (t_tri < 3e38) & (np.abs(t_tri.astype(np.float64) - t_sph) <= 1e-6 * np.abs(t_tri))
-    ok = ~tie
-    bad = np.argwhere(ok & (gi != ri))
-    assert len(bad) == 0, f"{what}: {len(bad)} ids differ, first {bad[:4].tolist()}: {gi[tuple(bad[0])]} vs {ri[tuple(bad[0])]}"
-    assert np.array_equal(ga[ok].view(np.int32), ra[ok].view(np.int32)), f"{what}: albedo"
-    tri = ok & (ri >= 0)
-    assert np.array_equal(gp[tri][:, 3].view(np.int32), rp[tri][:, 3].view(np.int32)), f"{what}: triangle t"
-    miss = ok & (ri == -1)
-    for b in (ga, gn, gp):
-        assert not np.any(b[miss]), f"{what}: a miss must be all zero"
-    assert np.array_equal(np.any(gn[..., :3] != 0, -1), gi != -1), f"{what}: miss <=> normal (0, 0, 0)"
-    hit = ok & (ri != -1)
-    du_p, du_n = int(ulps(gp[hit], rp[hit]).max(initial=0)), int(ulps(gn[hit], rn[hit]).max(initial=0))
-    assert du_p <= 2 and du_n <= 2, f"{what}: position {du_p} ulp, normal {du_n} ulp"
-    return du_p, du_n, int(tie.sum())
-
-
-def setup_scene(t, scene, materials):
-    """(bvh, spheres, materials, tri_material) of a test scene, installed on the context."""
-    t.upload_tri_materials(None, None)
-    if scene == "room":
-        mesh, sph = g.scene_mesh("cornell"), g.reference_spheres()
-    elif scene == "cornell_dragon":
-        mesh, sph = g.scene_mesh("cornell_dragon"), g.reference_spheres()
-    else:
-        mesh, sph = g.scene_mesh("cornell_box"), None
-    bvh = g.Bvh(mesh)
-    t.upload_bvh(bvh)
-    t.upload_spheres(sph or [])
-    mats = tm = None
-    if materials:
-        mats, tm = mesh.materials, mesh.tri_material
-        t.upload_tri_materials(mats, tm)
-    return bvh, sph, mats, tm
 
 
 # ---------------------------------------------------------------------------------------------------- guide buffers

@@ -1,55 +1,16 @@
 """PT_OPT_FUSE_STAGES: bounce 0's shade inside the packet walk's launch and the fold inside the last shade launch (1, default)
 against one launch per stage (0).  The fused launches run the same arithmetic on the same paths, so the accumulator and the display
 words must be the same bit for bit, and the instrumented counters (which always run the separate launches) must agree."""
-import numpy as np
 import pytest
 
 import gpu_pathtracer_amd as g
-from test_gpu_parity import golden_camera, bvh_of
+from gpu_support import COUNTERS, pipeline_render, same
 
 pytestmark = pytest.mark.gpu
 
 
-def render(fuse, scene, W, H, spp, depth=4, flags=0, spheres=True, calls=1, prefill=False, counters=False, options=()):
-    """accumulator + display words after `calls` pt_render calls of the stage-split pipeline with PT_OPT_FUSE_STAGES = fuse; with
-    prefill the accumulator starts as a fixed frame and the first call's sample_index is 5 (a running mean already under way)"""
-    t = g.PathTracer(0)
-    try:
-        t.set_option(g.OPT_KERNEL, g.KERNEL_WAVEFRONT)
-        t.set_option(g.OPT_FUSE_STAGES, fuse)
-        for o, v in options:
-            t.set_option(o, v)
-        if counters:
-            t.set_option(g.OPT_COUNTERS, 1)
-        t.upload_bvh(bvh_of(scene)[1])
-        t.upload_spheres(g.reference_spheres() if spheres else None)
-        cam = golden_camera(W, H)
-        acc, rgba = t.alloc_frame(W, H)
-        first = 1
-        if prefill:
-            acc.upload(np.random.default_rng(3).random((H, W, 3), dtype=np.float32))
-            first = 5
-        for call in range(calls):
-            p = g.default_params(W, H)
-            p.flags = flags | g.FLAG_WRITE_RGBA
-            p.depth = depth
-            p.frame, p.sample_index = 7 + call * spp, first + call * spp
-            t.launch_kernel(acc.ptr, rgba.ptr, cam, p, spp)
-        t.sync()
-        out = (acc.download(np.float32, (H, W, 3)), rgba.download(np.uint32, (H, W)))
-        if counters:
-            out += (t.counters(), t.wave_stats())
-        acc.free()
-        rgba.free()
-        return out
-    finally:
-        t.close()
-
-
-def same(a, b, what):
-    assert np.array_equal(a[0], b[0]), f"{what}: accumulator differs"
-    assert np.array_equal(a[1], b[1]), f"{what}: display words differ"
-    assert a[0].any(), what
+def render(fuse, *args, options=(), **kw):
+    return pipeline_render(((g.OPT_FUSE_STAGES, fuse),) + tuple(options), *args, **kw)
 
 
 @pytest.mark.parametrize("size", [(640, 360), (257, 131)], ids=["640x360", "257x131"])
@@ -99,8 +60,9 @@ def test_counters_equal():
     region) vary from run to run whatever the option, so they are not compared"""
     a, b = (render(f, "cornell_dragon", 320, 180, 16, counters=True) for f in (0, 1))
     same(b, a, "instrumented")
-    assert a[2] == b[2]
-    assert a[3]["it_shade"] == b[3]["it_shade"] > 0
+    for k in COUNTERS:
+        assert a[2][k] == b[2][k], k
+    assert a[2]["it_shade"] == b[2]["it_shade"] > 0
 
 
 def test_fuse_option_values():

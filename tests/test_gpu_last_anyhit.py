@@ -3,71 +3,17 @@ by the segment's nearest sphere hit (1, default; 2 = instrumented launches too) 
 picture only needs to know whether a triangle lies at or before the sphere, so the accumulator and the display words must be the
 same bit for bit, calls that are not eligible must not run the any-hit launch at all (wave stat "act_shade" counts its rays), and
 where it runs it must visit fewer items."""
-import numpy as np
 import pytest
 
 import gpu_pathtracer_amd as g
 import orc
-from scene_matrix import make_camera, red_copies_table
-from test_gpu_parity import golden_camera, bvh_of
-from test_gpu_scene_matrix import judge
+from gpu_support import TIE_H, TIE_SPP, TIE_W, bvh_of, dark_table, judge, pipeline_render, same, tie_camera
 
 pytestmark = pytest.mark.gpu
 
 
-def render(anyhit, scene, W, H, spp, depth=4, flags=0, spheres=True, calls=1, prefill=False, counters=False, options=(), cam=None,
-           tri_emi=(0, 0, 0), table=None, parts=1, before_upload=()):
-    """accumulator + display words after `calls` pt_render calls of the stage-split pipeline with PT_OPT_LAST_ANYHIT = anyhit; with
-    prefill the accumulator starts as a fixed frame and the first call's sample_index is 5; parts > 1 renders every call as that
-    many tile-split parts of 8 rows"""
-    t = g.PathTracer(0)
-    try:
-        t.set_option(g.OPT_KERNEL, g.KERNEL_WAVEFRONT)
-        t.set_option(g.OPT_LAST_ANYHIT, anyhit)
-        for o, v in tuple(options) + tuple(before_upload):
-            t.set_option(o, v)
-        if counters:
-            t.set_option(g.OPT_COUNTERS, 1)
-        mesh, bvh = bvh_of(scene)
-        t.upload_bvh(bvh)
-        t.upload_spheres(g.reference_spheres() if spheres else None)
-        if table is not None:
-            t.upload_tri_materials(*table(mesh))
-        cam = golden_camera(W, H) if cam is None else cam
-        acc, rgba = t.alloc_frame(W, H)
-        first = 1
-        if prefill:
-            acc.upload(np.random.default_rng(3).random((H, W, 3), dtype=np.float32))
-            first = 5
-        total = {}
-        for call in range(calls):
-            for part in range(parts):
-                p = g.default_params(W, H)
-                p.flags = flags | g.FLAG_WRITE_RGBA
-                p.depth = depth
-                p.tri_emi[:] = tri_emi
-                p.frame, p.sample_index = 7 + call * spp, first + call * spp
-                if parts > 1:
-                    p.part_index, p.part_count, p.part_rows = part, parts, 8
-                t.launch_kernel(acc.ptr, rgba.ptr, cam, p, spp)
-                if counters:   # (the counters are those of the last launch: add the parts up)
-                    for k, v in {**t.counters(), **t.wave_stats()}.items():
-                        total[k] = total.get(k, 0) + v
-        t.sync()
-        out = (acc.download(np.float32, (H, W, 3)), rgba.download(np.uint32, (H, W)))
-        if counters:
-            out += (total,)
-        acc.free()
-        rgba.free()
-        return out
-    finally:
-        t.close()
-
-
-def same(a, b, what):
-    assert np.array_equal(a[0], b[0]), f"{what}: accumulator differs"
-    assert np.array_equal(a[1], b[1]), f"{what}: display words differ"
-    assert a[0].any(), what
+def render(anyhit, *args, options=(), **kw):
+    return pipeline_render(((g.OPT_LAST_ANYHIT, anyhit),) + tuple(options), *args, **kw)
 
 
 @pytest.mark.parametrize("size", [(640, 360), (257, 131)], ids=["640x360", "257x131"])
@@ -117,15 +63,6 @@ def test_anyhit_running_mean(spp):
     same(b, a, f"running mean, spp {spp}")
 
 
-# the Cornell floor (y = -15) touches the floor sphere's top at (0, -15, -20): t and ts agree to the last bits for segments that
-# land near that point
-TIE_W, TIE_H, TIE_SPP = 96, 64, 16
-
-
-def tie_camera():
-    return make_camera(TIE_W, TIE_H, pos=(0.0, -9.0, -12.0), front=(0.0, -6.0, -8.0), fov=1.2)
-
-
 @pytest.mark.parametrize("depth", [2, 4])
 def test_anyhit_floor_sphere_tie(depth):
     cam = tie_camera()
@@ -133,7 +70,7 @@ def test_anyhit_floor_sphere_tie(depth):
     same(b, a, f"floor / sphere tie, depth {depth}")
     same(c, a, f"floor / sphere tie, instrumented, depth {depth}")
     assert c[2]["act_shade"] > 0
-    # parity with the oracle for that frame, at the bars of test_gpu_scene_matrix.judge
+    # parity with the oracle for that frame, at the bars of gpu_support.judge
     mesh, bvh = bvh_of("cornell_dragon")
     sph = g.reference_spheres()
     p = g.default_params(TIE_W, TIE_H, depth=depth)
@@ -143,14 +80,6 @@ def test_anyhit_floor_sphere_tie(depth):
     class T:
         name, exact = "wavefront-last-anyhit", False
     judge(T, f"floor / sphere tie depth {depth}", b[:2], ref, mesh, sph, cam, p, TIE_SPP)
-
-
-def dark_table(mesh):
-    """a per-triangle material table whose rows emit nothing: a table is on the context, so the call is not eligible"""
-    p = g.default_params(8, 8)
-    n = len(np.asarray(mesh.tris))
-    table, ids = red_copies_table(n, n, p)
-    return table, ids
 
 
 INELIGIBLE = {

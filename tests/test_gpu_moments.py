@@ -13,7 +13,7 @@ import gpu_pathtracer_amd as g
 import orc
 import denoise_ref as R
 import moments_ref as M
-from test_gpu_parity import golden_camera
+from gpu_support import bits, golden_camera
 
 pytestmark = pytest.mark.gpu
 
@@ -94,10 +94,6 @@ class Frame:
     def free(self):
         for b in (self.acc, self.rgba, self.mom):
             b.free()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int32)
 
 
 def options(t, kernel, walk):

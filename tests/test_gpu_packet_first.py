@@ -9,56 +9,14 @@ import pytest
 
 import gpu_pathtracer_amd as g
 import orc
-from test_gpu_parity import golden_camera, bvh_of
+from gpu_support import bvh_of, golden_camera, pipeline_render, same, upload
 
 pytestmark = pytest.mark.gpu
 
 
-def render(walk, install, W, H, spp, flags=0, parts=1, calls=2, cull=None, depth=None, options=(), counters=False):
-    """accumulator + display words of `calls` pt_render calls (each over `parts` tile-split parts) with PT_OPT_FIRST_WALK = walk;
-    install(t) puts the scene on the tracer.  With counters: also the work and wave counters of the last call."""
-    t = g.PathTracer(0)
-    try:
-        t.set_option(g.OPT_KERNEL, g.KERNEL_WAVEFRONT)
-        t.set_option(g.OPT_FIRST_WALK, walk)
-        for o, v in options:
-            t.set_option(o, v)
-        if counters:
-            t.set_option(g.OPT_COUNTERS, 1)
-        install(t)
-        t.upload_spheres(g.reference_spheres())
-        cam = golden_camera(W, H)
-        acc, rgba = t.alloc_frame(W, H)
-        for call in range(calls):
-            for part in range(parts):
-                p = g.default_params(W, H)
-                p.flags = flags | g.FLAG_WRITE_RGBA
-                if cull is not None:
-                    p.cull_backfaces = cull
-                if depth is not None:
-                    p.depth = depth
-                p.frame, p.sample_index = 7 + call * spp, 1 + call * spp
-                p.part_index, p.part_count, p.part_rows = part, parts, 8
-                t.launch_kernel(acc.ptr, rgba.ptr, cam, p, spp)
-        t.sync()
-        out = (acc.download(np.float32, (H, W, 3)), rgba.download(np.uint32, (H, W)))
-        if counters:
-            out += (t.counters(), t.wave_stats())
-        acc.free()
-        rgba.free()
-        return out
-    finally:
-        t.close()
-
-
-def upload(bvh):
-    return lambda t: t.upload_bvh(bvh)
-
-
-def same(a, b, what):
-    assert np.array_equal(a[0], b[0]), f"{what}: accumulator differs"
-    assert np.array_equal(a[1], b[1]), f"{what}: display words differ"
-    assert a[0].any(), what
+def render(walk, install, W, H, spp, flags=0, parts=1, calls=2, options=(), **kw):
+    opts = ((g.OPT_FIRST_WALK, walk),) + tuple(options)
+    return pipeline_render(opts, install, W, H, spp, flags=flags, parts=parts, calls=calls, **kw)
 
 
 @pytest.mark.parametrize("cfg", [((333, 187), 16, 0, 1), ((640, 360), 8, 0, 3), ((640, 360), 12, g.FLAG_NEE | g.FLAG_COSINE_DIFF, 1),
@@ -120,8 +78,8 @@ def test_packet_stack_budget_falls_back_to_per_lane():
     for f, what in ((pkt, "packet"), (low, "fallback")):
         same(f, base, what)
     groups = (W + 7) // 8 * ((H + 7) // 8) * spp
-    assert pkt[3]["it_shade"] == groups
-    assert low[3]["it_shade"] == 0 and base[3]["it_shade"] == 0
+    assert pkt[2]["it_shade"] == groups
+    assert low[2]["it_shade"] == 0 and base[2]["it_shade"] == 0
     t = g.PathTracer(0)
     try:
         for bad in (1, 73):
@@ -141,7 +99,8 @@ def test_packet_counters_keep_per_ray_meaning():
     a = render(0, upload(bvh), W, H, spp, calls=1, depth=1, counters=True)
     b = render(1, upload(bvh), W, H, spp, calls=1, depth=1, counters=True)
     same(b, a, "depth 1")
-    ca, cb, wb = a[2], b[2], b[3]
+    ca, cb = a[2], b[2]
+    wb = cb   # (one dict holds the work counters and the wave statistics)
     assert ca["rays"] == cb["rays"] == W * H * spp
     assert cb["inner"] > 0 and cb["tris"] > 0 and cb["leaves"] > 0
     assert wb["act_node"] == cb["inner"] and wb["act_rec"] == cb["tris"]

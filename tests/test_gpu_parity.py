@@ -10,20 +10,11 @@ import pytest
 
 import gpu_pathtracer_amd as g
 import orc
+from gpu_support import bvh_of, golden_camera, gpu_render, gpu_trace, l2
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 L2_TOL = 1e-3  # BASELINE.json north_star: per-pixel L2 vs CPU ref < 1e-3
-
-
-def golden_camera(W, H):
-    cam = g.default_camera(W, H)
-    cam.dist = 18.0 * H / 1080.0
-    return cam
-
-
-def l2(a, b):
-    return float(np.sqrt(np.mean(np.sum((a.astype(np.float64) - b) ** 2, axis=-1))))
 
 
 VARIANTS = {
@@ -50,51 +41,6 @@ def pt(request):
     t.walk = walk
     yield t
     t.close()
-
-
-_bvh_cache = {}
-
-
-def bvh_of(name, **kw):
-    key = (name, tuple(sorted(kw.items())))
-    if key not in _bvh_cache:
-        mesh = g.scene_mesh(name)
-        _bvh_cache[key] = (mesh, g.Bvh(mesh, **kw))
-    return _bvh_cache[key]
-
-
-def gpu_render(pt, bvh, spheres, cam, p, spp=1, accum_init=None):
-    W, H = p.width, p.height
-    if bvh is not None:
-        pt.upload_bvh(bvh)
-    pt.upload_spheres(spheres)
-    acc, rgba = pt.alloc_frame(W, H)
-    if accum_init is not None:
-        acc.upload(accum_init)
-    pt.launch_kernel(acc.ptr, rgba.ptr, cam, p, spp)
-    pt.sync()
-    a = acc.download(np.float32, (H, W, 3))
-    r = rgba.download(np.uint32, (H, W))
-    acc.free()
-    rgba.free()
-    return a, r
-
-
-def gpu_trace(pt, rays, cull=True):
-    n = len(rays)
-    d_r = pt.malloc(rays.nbytes)
-    d_r.upload(rays)
-    d_t, d_i, d_n = pt.malloc(4 * n), pt.malloc(4 * n), pt.malloc(12 * n)
-    pt.trace_rays(d_r.ptr, n, cull, d_t.ptr, d_i.ptr, d_n.ptr)
-    pt.sync()
-    out = d_t.download(np.float32, (n,)), d_i.download(np.int32, (n,)), d_n.download(np.float32, (n, 3))
-    for b in (d_r, d_t, d_i, d_n):
-        b.free()
-    return out
-
-
-def gpu_trace_frame_free(*a, **k):  # re-export hook for the sibling test modules
-    return gpu_trace(*a, **k)
 
 
 # ---------------------------------------------------------------- rows a5-a7: closest hit

@@ -11,56 +11,13 @@ import pytest
 
 import gpu_pathtracer_amd as g
 import orc
-from test_gpu_bench_configs import arbitrate
-from test_gpu_parity import gpu_trace, golden_camera
+from gpu_support import arbitrate, cornell_dragon_moved, golden_camera, gpu_trace, rays_for, soup_mesh, twist
 
 pytestmark = pytest.mark.gpu
 
 PT_ERR_INVALID, PT_ERR_NO_SCENE, PT_ERR_UNSUPPORTED = -1, -3, -5
 WALKS = {"mega-0": (g.KERNEL_MEGA_BVH2, 0), "mega-2": (g.KERNEL_MEGA_BVH2, 2), "persistent-1": (g.KERNEL_PERSISTENT, 1),
          "persistent-4": (g.KERNEL_PERSISTENT, 4), "wavefront": (g.KERNEL_WAVEFRONT, 2), "auto": (g.KERNEL_AUTO, 2)}
-
-
-# ---------------------------------------------------------------------------------------------------- moved geometry
-def soup_mesh(soup):
-    """A Mesh whose triangle t is row t of the soup (the ids the refit tree reports)."""
-    s = np.ascontiguousarray(soup, np.float32).reshape(-1, 9)
-    return g.Mesh.from_arrays(s.reshape(-1, 3), np.arange(3 * len(s), dtype=np.int32).reshape(-1, 3))
-
-
-def twist(soup, amount, shift):
-    """Non-rigid: every vertex turns about the vertical axis through the mesh centre by an angle that grows with its height,
-    then moves by `shift` x the extent.  A function of the vertex alone, so shared vertices stay shared."""
-    v = soup.reshape(-1, 3).astype(np.float64)
-    lo, hi = v.min(0), v.max(0)
-    c, ext = 0.5 * (lo + hi), float(np.max(hi - lo))
-    a = amount * (v[:, 1] - c[1]) / ext
-    x, z = v[:, 0] - c[0], v[:, 2] - c[2]
-    out = np.stack([c[0] + np.cos(a) * x - np.sin(a) * z, v[:, 1], c[2] + np.sin(a) * x + np.cos(a) * z], 1) + shift * ext
-    return out.astype(np.float32).reshape(soup.shape)
-
-
-def turn_rows(soup, rows, deg, shift):
-    """Rigid: rows `rows` turn by `deg` about the vertical axis through their centre and move by `shift`."""
-    out = soup.copy()
-    v = soup[rows].reshape(-1, 3).astype(np.float64)
-    c = 0.5 * (v.min(0) + v.max(0))
-    a = np.radians(deg)
-    R = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
-    out[rows] = ((v - c) @ R.T + c + np.asarray(shift)).astype(np.float32).reshape(-1, 9)
-    return out
-
-
-def cornell_dragon_moved(deg=25.0, shift=(1.5, 0.5, -1.0)):
-    mesh = g.scene_mesh("cornell_dragon")
-    n_box = g.Mesh.asset("cornell").n_tris
-    soup = mesh.triangle_soup()
-    return mesh, soup, turn_rows(soup, np.arange(n_box, len(soup)), deg, shift)
-
-
-def rays_for(soup, n, seed):
-    v = soup.reshape(-1, 3)
-    return orc.random_rays(n, v.min(0), v.max(0), seed=seed)
 
 
 TREES = ("device", "lbvh", "host", "optimize", "rebuild2", "presplit")

@@ -9,60 +9,13 @@ import pytest
 
 import gpu_pathtracer_amd as g
 import orc
-from test_gpu_last_anyhit import dark_table, same, tie_camera, TIE_W, TIE_H, TIE_SPP
-from test_gpu_parity import golden_camera, bvh_of
-from test_gpu_scene_matrix import judge
+from gpu_support import COUNTERS, TIE_H, TIE_SPP, TIE_W, bvh_of, dark_table, golden_camera, judge, pipeline_render, same, tie_camera
 
 pytestmark = pytest.mark.gpu
-COUNTERS = ("rays", "inner", "tris", "leaves", "hits", "paths")
 
 
-def render(cull, scene, W, H, spp, depth=4, flags=0, spheres=True, calls=1, prefill=False, counters=False, options=(), cam=None,
-           table=None, parts=1, tri_mat=g.MAT_DIFF):
-    """accumulator + display words after `calls` pt_render calls with PT_KERNEL_WAVEFRONT asked for and PT_OPT_ROOT_CULL = cull;
-    scene None: no tree on the context; prefill: the accumulator starts as a fixed frame and the first call's sample_index is 5;
-    parts > 1: every call as that many tile-split parts of 8 rows; counters: + the summed counters and wave statistics"""
-    t = g.PathTracer(0)
-    try:
-        t.set_option(g.OPT_KERNEL, g.KERNEL_WAVEFRONT)
-        t.set_option(g.OPT_ROOT_CULL, cull)
-        for o, v in options:
-            t.set_option(o, v)
-        if counters:
-            t.set_option(g.OPT_COUNTERS, 1)
-        if scene is not None:
-            mesh, bvh = bvh_of(scene)
-            t.upload_bvh(bvh)
-        t.upload_spheres(g.reference_spheres() if spheres else None)
-        if table is not None:
-            t.upload_tri_materials(*table(mesh))
-        cam = golden_camera(W, H) if cam is None else cam
-        acc, rgba = t.alloc_frame(W, H)
-        first = 1
-        if prefill:
-            acc.upload(np.random.default_rng(3).random((H, W, 3), dtype=np.float32))
-            first = 5
-        total = {}
-        for call in range(calls):
-            for part in range(parts):
-                p = g.default_params(W, H, depth=depth, tri_mat=tri_mat)
-                p.flags = flags | g.FLAG_WRITE_RGBA
-                p.frame, p.sample_index = 7 + call * spp, first + call * spp
-                if parts > 1:
-                    p.part_index, p.part_count, p.part_rows = part, parts, 8
-                t.launch_kernel(acc.ptr, rgba.ptr, cam, p, spp)
-                if counters:   # (the counters are those of the last launch: add the parts up)
-                    for k, v in {**t.counters(), **t.wave_stats()}.items():
-                        total[k] = total.get(k, 0) + v
-        t.sync()
-        out = (acc.download(np.float32, (H, W, 3)), rgba.download(np.uint32, (H, W)))
-        if counters:
-            out += (total,)
-        acc.free()
-        rgba.free()
-        return out
-    finally:
-        t.close()
+def render(cull, *args, options=(), **kw):
+    return pipeline_render(((g.OPT_ROOT_CULL, cull),) + tuple(options), *args, **kw)
 
 
 @pytest.mark.parametrize("size", [(640, 360), (257, 131)], ids=["640x360", "257x131"])
@@ -204,7 +157,7 @@ def test_camera_in_a_bounding_plane_against_the_oracle(axis, side, tri_mat):
     """The oracle walks the binary tree, whose exact root box drops a ray that lies IN one of its faces with a zero direction
     component (the slab test is not watertight: test_edge_case_rays, tests/test_oracle.py), while the wide root is rounded outward
     and keeps it — with the option on or off.  A frame made of nothing but such rays is therefore not what the wide walk's bars
-    (test_gpu_scene_matrix.judge) were set for; they are set for frames in which a grazing ray is the exception.  So this
+    (gpu_support.judge) were set for; they are set for frames in which a grazing ray is the exception.  So this
     comparison takes an ordinary camera basis with the camera IN the plane (or 1 / 3 ulps beside it): every camera ray starts on
     the face of the root box, half of them leave it at once, the frame's middle column (row) runs along it."""
     mesh, bvh = bvh_of("cornell_dragon")

@@ -10,10 +10,7 @@ import pytest
 
 import gpu_pathtracer_amd as g
 from scene_matrix import make_camera
-from test_gpu_last_anyhit import dark_table
-from test_gpu_parity import golden_camera
-from test_gpu_refit import cornell_dragon_moved
-from test_gpu_root_cull import render, same, COUNTERS
+from gpu_support import COUNTERS, cornell_dragon_moved, dark_table, golden_camera, pipeline_render, same
 
 pytestmark = pytest.mark.gpu
 ENTRY = g._abi.OPT_ROOT_ENTRY   # 33 (kept out of the package's exported OPT_* names)
@@ -22,7 +19,7 @@ MAX_SPP = (1 << 12) - 1           # the largest spp the narrowed sample field ho
 
 def pair(scene, W, H, spp, values=(0, 1), cull=1, options=(), **kw):
     """the frames (and counters) of the same call with PT_OPT_ROOT_ENTRY at each of `values`"""
-    return [render(cull, scene, W, H, spp, options=tuple(options) + ((ENTRY, v),), **kw) for v in values]
+    return [pipeline_render(((g.OPT_ROOT_CULL, cull),) + tuple(options) + ((ENTRY, v),), scene, W, H, spp, **kw) for v in values]
 
 
 def test_option_number_and_values():

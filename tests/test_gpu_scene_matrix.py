@@ -14,17 +14,13 @@ import pytest
 import gpu_pathtracer_amd as g
 import orc
 import denoise_ref as R
-from test_gpu_bench_configs import arbitrate, oracle
-from test_gpu_denoise import compare_guides, setup_scene
-from test_gpu_parity import bvh_of, gpu_trace, l2
-from test_gpu_refit import turn_rows
+from gpu_support import MAX_DIFF, STAGE_SPLIT, arbitrate, bvh_of, compare_guides, gpu_trace, judge, n_diff_seen, oracle, setup_scene, turn_rows
 from scene_matrix import (N_ROOM, PINHOLE_SIDES, POSES, SPHERE_SETS, SPHERES_ONLY, STALE_THREE, axis_rays, copy_rows, duplicated,
                           grid_mesh, grid_rays, many_spheres, pinhole_camera, pinhole_params, pose_camera, pose_spheres,
                           red_copies_table, tilted_grid, tilted_grid_table, unreachable_spheres)
 
 pytestmark = pytest.mark.gpu
 
-MAX_DIFF = 2   # the cap of test_materials.py / test_gpu_build.py for the wide walks at these sizes
 VARIANTS = {
     # id: (kernel, walk, other options)
     "mega-unified": (g.KERNEL_MEGA_BVH2, 1, ()),
@@ -36,8 +32,7 @@ VARIANTS = {
     "wavefront-unfused": (g.KERNEL_WAVEFRONT, 2, ((g.OPT_FUSE_STAGES, 0),)),
 }
 WAVEFRONT = [v for v in VARIANTS if v.startswith("wavefront")]
-_wf_frames = {}     # case -> (variant, accumulator, display words) of the first stage-split variant that ran it
-_n_diff = {}        # variant -> differing pixels seen, all arbitrated
+assert tuple(WAVEFRONT) == STAGE_SPLIT   # the variants gpu_support.judge holds to one another
 
 
 def make_tracer(name):
@@ -55,7 +50,7 @@ def make_tracer(name):
 def pt(request):
     t = make_tracer(request.param)
     yield t
-    print(f"[{t.name}] differing pixels against the oracle, all equal to brute force: {_n_diff.get(t.name, 0)}")
+    print(f"[{t.name}] differing pixels against the oracle, all equal to brute force: {n_diff_seen.get(t.name, 0)}")
     t.close()
 
 
@@ -70,30 +65,6 @@ def frame_of(t, cam, p, spp, prev=None):
     acc.free()
     rgba.free()
     return out
-
-
-def judge(t, case, got, ref, mesh, sph, cam, p, spp, prev=None, materials=None, tri_material=None):
-    """the bars of the module docstring; `ref` = the oracle's (accumulator, display words) of the same call"""
-    acc, rgba = got
-    ref_acc, ref_rgba = ref
-    diff = np.any(acc != ref_acc, axis=-1)
-    n_diff = int(diff.sum())
-    assert l2(acc, ref_acc) < 1e-3, case
-    if t.exact:
-        assert n_diff == 0, f"[{t.name}] {case}: {n_diff} pixels differ from the oracle"
-        assert np.array_equal(rgba, ref_rgba), case
-    else:
-        assert n_diff <= MAX_DIFF, f"[{t.name}] {case}: {n_diff} pixels differ from the oracle"
-        assert not np.any((rgba != ref_rgba) & ~diff), case
-        for y, x in zip(*np.nonzero(diff)):
-            col, _, _ = orc.sample_pixels([(int(x), int(y))], sph, cam, p, spp, mesh=mesh, materials=materials, tri_material=tri_material)
-            brute = orc.fold_samples(col, p.sample_index, None if prev is None else prev[y, x][None])[0]
-            print(f"  [{t.name}] {case}: pixel ({x},{y}) gpu {acc[y, x]} oracle {ref_acc[y, x]} brute {brute}")
-            assert np.array_equal(acc[y, x], brute), f"[{t.name}] {case}: pixel ({x},{y}) is neither the oracle's nor brute force's"
-        _n_diff[t.name] = _n_diff.get(t.name, 0) + n_diff
-    if t.name in WAVEFRONT:
-        first = _wf_frames.setdefault(case, (t.name, acc, rgba))
-        assert np.array_equal(acc, first[1]) and np.array_equal(rgba, first[2]), f"[{t.name}] {case}: differs from [{first[0]}]"
 
 
 def render_case(t, case, mesh, bvh, sph, cam, p, spp, prev=None, materials=None, tri_material=None, upload=True):

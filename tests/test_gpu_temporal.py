@@ -12,10 +12,9 @@ import gpu_pathtracer_amd as g
 import orc
 import denoise_ref as R
 import temporal_ref as T
-from test_gpu_denoise import Guides, setup_scene
-from test_gpu_parity import golden_camera
-from test_temporal import (ACCEPTED_MIN, FRAGILE_MAX, MOVES, PARAM_SETS, QUALITY_FRAMES, QUALITY_K, QUALITY_PAN, QUALITY_SPP, params,
-                           random_frames)
+from gpu_support import Guides, bits, golden_camera, setup_scene
+from temporal_ref import (ACCEPTED_MIN, FRAGILE_MAX, MOVES, PARAM_SETS, QUALITY_FRAMES, QUALITY_K, QUALITY_PAN, QUALITY_SPP, params,
+                          random_frames)
 
 pytestmark = pytest.mark.gpu
 
@@ -28,10 +27,6 @@ def t():
     tr = g.PathTracer(0)
     yield tr
     tr.close()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int32)
 
 
 _guides = {}

@@ -8,9 +8,7 @@ import pytest
 
 import gpu_pathtracer_amd as g
 import orc
-from test_gpu_parity import golden_camera, gpu_trace
-from test_gpu_refit import rays_for, soup_mesh
-from test_materials import material
+from gpu_support import golden_camera, gpu_trace, material, rays_for, soup_mesh
 
 pytestmark = pytest.mark.gpu
 

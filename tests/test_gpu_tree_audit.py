@@ -20,6 +20,7 @@ import pytest
 
 import gpu_pathtracer_amd as g
 import tree_audit as ta
+from gpu_support import soup_mesh, twist
 
 pytestmark = pytest.mark.gpu
 
@@ -27,11 +28,6 @@ PT_ERR_INVALID, PT_ERR_NO_SCENE = -1, -3
 
 
 # ---------------------------------------------------------------------------------------------------------------- meshes
-def soup_mesh(soup):
-    s = np.ascontiguousarray(soup, np.float32).reshape(-1, 9)
-    return g.Mesh.from_arrays(s.reshape(-1, 3), np.arange(3 * len(s), dtype=np.int32).reshape(-1, 3))
-
-
 def needles():
     """A 16 x 16 patch of small triangles beside needles 1000 x longer than wide, at 45 degrees to the axes, of lengths that
     ask the pre-split for 2..8 slabs."""
@@ -68,14 +64,7 @@ def mesh_of(name):
     return soup_mesh(soup_of(name)) if name == "needles" else g.scene_mesh(name)
 
 
-def twist(soup, amount=0.8, shift=(0.05, -0.02, 0.03)):
-    v = soup.reshape(-1, 3).astype(np.float64)
-    lo, hi = v.min(0), v.max(0)
-    c, ext = 0.5 * (lo + hi), float(np.max(hi - lo))
-    a = amount * (v[:, 1] - c[1]) / ext
-    x, z = v[:, 0] - c[0], v[:, 2] - c[2]
-    out = np.stack([c[0] + np.cos(a) * x - np.sin(a) * z, v[:, 1], c[2] + np.sin(a) * x + np.cos(a) * z], 1) + np.array(shift) * ext
-    return out.astype(np.float32).reshape(soup.shape)
+TWIST = (0.8, (0.05, -0.02, 0.03))   # gpu_support.twist's amount and shift for every refit of this module
 
 
 # --------------------------------------------------------------------------------------------------------------- helpers
@@ -225,7 +214,7 @@ def test_refit_round_trip_is_byte_exact(t, kind):
     own = items(t)
     if kind in ("device", "lbvh"):
         assert same_items(own, built), "a refit to the vertices the device tree was built from changed it"
-    t.refit_bvh(twist(soup))
+    t.refit_bvh(twist(soup, *TWIST))
     assert not same_items(items(t), own)
     t.refit_bvh(np.array(soup))
     assert same_items(items(t), own), "a refit back does not reproduce the refit to the own vertices"
@@ -236,7 +225,7 @@ def test_refit_round_trip_is_byte_exact(t, kind):
 def test_refit_to_twisted_vertices_is_strict_and_covers(t, kind):
     name = refit_mesh(kind)
     kw = install(t, name, kind)
-    moved = twist(soup_of(name))
+    moved = twist(soup_of(name), *TWIST)
     t.refit_bvh(moved)
     check(t, moved, f"{name} {kind} twisted", strict=True, coverage=True, **kw)
 

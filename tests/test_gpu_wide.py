@@ -12,7 +12,7 @@ import pytest
 
 import gpu_pathtracer_amd as g
 import orc
-from test_gpu_parity import gpu_render, golden_camera, l2, bvh_of
+from gpu_support import bvh_of, golden_camera, gpu_render, l2
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")

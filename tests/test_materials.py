@@ -12,14 +12,7 @@ import pytest
 
 import gpu_pathtracer_amd as g
 import orc
-
-
-def material(col, emi=(0, 0, 0), mat=g.MAT_DIFF, phong=0.0):
-    m = g.Material()
-    m.col[:] = col
-    m.emi[:] = emi
-    m.mat, m.phong_expo = mat, phong
-    return m
+from gpu_support import material
 
 
 def mixed_table():

@@ -8,14 +8,9 @@ import pytest
 
 import gpu_pathtracer_amd as g
 import orc
+from gpu_support import golden_camera
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def golden_camera(W, H):
-    cam = g.default_camera(W, H)
-    cam.dist = 18.0 * H / 1080.0
-    return cam
 
 
 # ---------------------------------------------------------------- pin vs the reference
@@ -278,8 +273,7 @@ def test_config1_cornell_256_through_the_reference_cpu_tracer(tmp_path):
     assert z["blocks"].shape == (H // orc.CONFIG1_BLOCK, W // orc.CONFIG1_BLOCK, 3)
     assert abs(float(z["blocks"].mean(dtype=np.float64)) - float(z["mean"])) < 1e-5
 
-    import test_reference_radiance as rr
-    _, _, spheres, cam, q = rr.room()                       # main.cpp's room and camera, emission x EMISSION_SCALE
+    _, _, spheres, cam, q = orc.reference_room()                       # main.cpp's room and camera, emission x EMISSION_SCALE
     v, f = orc.config1_mesh()
     v = np.loadtxt([f"{x:.6f} {y:.6f} {w:.6f}" for x, y, w in v])   # the vertices exactly as the .obj holds them
     cam.aspect = W / H
@@ -287,7 +281,7 @@ def test_config1_cornell_256_through_the_reference_cpu_tracer(tmp_path):
     p.flags, p.cull_backfaces, p.tri_mat = q.flags, q.cull_backfaces, q.tri_mat
     p.bk_color[:], p.tri_col[:], p.tri_emi[:] = q.bk_color, q.tri_col, q.tri_emi
     acc, _, _ = orc.render(g.Bvh(g.Mesh.from_arrays(v.astype(np.float32), f)), spheres, cam, p, spp=16, want_rgba=False)
-    r = float(acc.mean(dtype=np.float64)) / rr.EMISSION_SCALE / float(z["mean"])
+    r = float(acc.mean(dtype=np.float64)) / orc.EMISSION_SCALE / float(z["mean"])
     print(f"oracle / reference global mean, config 1: {r:.4f}")
     assert 0.98 < r < 1.10
 

@@ -14,28 +14,11 @@ import gpu_pathtracer_amd as g
 import orc
 import denoise_ref as R
 import temporal_ref as T
-from test_gpu_parity import golden_camera
+from gpu_support import golden_camera
+from temporal_ref import (ACCEPTED_MIN, FRAGILE_MAX, MOVES, PARAM_SETS, QUALITY_FRAMES, QUALITY_GAIN_CPU, QUALITY_PAN, QUALITY_SPP, params,
+                          random_frames)
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-# The camera moves of the GPU comparison, applied to the golden camera (previous frame) to get the current one
-MOVES = {"static": {}, "pan": dict(pan_deg=2.0), "dolly": dict(dolly=0.5), "side": dict(side=0.3)}
-# The parameter sets of the GPU comparison
-PARAM_SETS = {"defaults": {}, "history1": dict(max_history=1.0), "plane0": dict(plane_tolerance=0.0), "normal-1": dict(normal_threshold=-1.0)}
-FRAGILE_MAX = 0.02
-# The quality sequence: cornell_box, QUALITY_FRAMES frames of QUALITY_SPP samples, the camera panning QUALITY_PAN degrees a frame.
-QUALITY_FRAMES, QUALITY_SPP, QUALITY_PAN = 8, 4, 1.0
-# gain = MSE(last frame alone) / MSE(history), both against 1024 spp at the last camera.  The numpy reference over oracle renders
-# at 80x60 measures 3.48 (test_reference_gain_on_oracle_renders asserts it); the bar for the GPU at 320x240 is 0.8 x that figure,
-# the margin for the other sample sets at the other resolution.
-QUALITY_GAIN_CPU = 3.48
-QUALITY_K = 0.8 * QUALITY_GAIN_CPU
-ACCEPTED_MIN = 0.70
-
-
-def params(**kw):
-    d = dict(g.TEMPORAL_DEFAULTS)
-    d.update(kw)
-    return d
 
 
 # ---------------------------------------------------------------------------------------------------- the ABI
@@ -216,13 +199,6 @@ def room_inputs(W, H, move):
         gc = gp if move == "static" else R.guides(_room["bvh"], _room["sph"], T.moved(prev_cam, **MOVES[move]), p)[1:4]
         _room[key] = (prev_cam, gp, gc)
     return _room[key]
-
-
-def random_frames(W, H, seed):
-    rng = np.random.default_rng(seed)
-    cur, prev = (rng.uniform(0, 1, (H, W, 3)).astype(np.float32) for _ in range(2))
-    ln = rng.integers(1, 41, (H, W)).astype(np.float32)
-    return cur, prev, ln
 
 
 @pytest.mark.parametrize("W,H", [(37, 23), (257, 131)])
