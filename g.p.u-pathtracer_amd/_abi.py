@@ -118,6 +118,8 @@ PTMI_SYMBOLS = [
     ("pt_render_moments", _i, [_vp, _vp, _vp, _vp, C.POINTER(Camera), C.POINTER(Params), _u32]),
     ("pt_frame_error", _i, [_vp, _vp, C.c_int32, C.c_int32, C.c_uint64, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     ("pt_trace_rays", _i, [_vp, _vp, _sz, _i, _vp, _vp, _vp]),
+    ("pt_closest_hits", _i, [_vp, _vp, _sz, _i, _vp, _vp, _vp]),
+    ("pt_any_hits", _i, [_vp, _vp, _sz, _i, _vp]),
     ("pt_render_aux", _i, [_vp, C.POINTER(Camera), C.POINTER(Params), _vp, _vp, _vp, _vp]),
     ("pt_denoise", _i, [_vp, C.POINTER(DenoiseParams), _vp, _vp, _vp, _vp, _vp, _vp]),
     ("pt_temporal", _i, [_vp, C.POINTER(TemporalParams), C.POINTER(Camera), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -83,7 +83,7 @@ struct pt_ctx {
     int opt_timing = 0;
     // measurement
     unsigned long long* d_counters = nullptr;
-    unsigned int* d_queue = nullptr;   // persistent kernel's work counter
+    unsigned int* d_queue = nullptr;   // work counters of the persistent kernel and of the ray-batch queries (pt_k_query.hip), on the caller's stream: reset there before every launch
     float* d_samples = nullptr;        // [spp][H*W][3] sample colours of a multi-sample call
     size_t samples_bytes = 0;
     int n_cu = 0;
@@ -231,8 +231,8 @@ auto with_int(int v, F&& f) {
 
 // A grid of resident blocks for a kernel whose waves draw work from a queue: what the device holds at once (at most `max_per_cu` per
 // CU), never more than `work_cap`.  No grid-wide wait anywhere: an over-estimate only means a few late blocks find the queue empty.
-template <class K>
-hipError_t launch_resident(K kernel, size_t lds, int max_per_cu, int n_cu, size_t work_cap, hipStream_t st, const KParams& P) {
+template <class K, class A>
+hipError_t launch_resident(K kernel, size_t lds, int max_per_cu, int n_cu, size_t work_cap, hipStream_t st, const A& P) {
     int per_cu = 0;
     const hipError_t e = allow_lds(kernel, lds);
     if (e != hipSuccess) return e;
@@ -270,6 +270,19 @@ inline uint32_t wave_sample_group_log2(uint32_t spp, int cap) {
     return 0u;
 }
 int wave_reserve(pt_ctx* c, const KParams& P, int work_tiles);   // path records for this call, allocated now
+// ray-batch queries over the tree on the context (pt_k_query.hip): pt_closest_hits (hit = nullptr) and pt_any_hits (hit given; t, tri and
+// normal unused).  Resets the work counters on the stream, then one launch: the wide walk on a resident grid, or the binary walk with
+// the bound applied to its answer when the tree is too deep for the wide one
+struct QueryCall {
+    const float* rays;   // float[n][8] = (o, ignored, d, t_max)
+    size_t n;            // 0 < n < 2^32
+    int cull;
+    float* t;
+    int32_t* tri;
+    float* normal;       // may be nullptr
+    uint8_t* hit;
+};
+hipError_t launch_query(pt_ctx* c, const QueryCall& q);
 // PT_OPT_TIMING: marks the end of a stage of the running call on the context's stream (no-op when timing is off)
 int stage_mark(pt_ctx* c, int kind_of_work_since_last_mark);
 // device BVH builder (pt_build.hip), a maker: the tree over the mesh into `out` (its build_ms set), the context's own tree untouched.

@@ -730,6 +730,30 @@ int pt_trace_rays(pt_ctx* c, const float* rays_dev, size_t n, int cull, float* t
     return PT_OK;
 }
 
+// the checks pt_closest_hits and pt_any_hits share, in pt_trace_rays' order; `outputs`: every required output pointer is given
+static int query_call(pt_ctx* c, const char* who, bool outputs, const ptmi::QueryCall& q) {
+    const std::string name(who);
+    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
+    if (!c->tree.has_bvh) return fail(c, PT_ERR_NO_SCENE, name + ": no BVH uploaded");
+    if (c->tree.records_woop) return fail(c, PT_ERR_UNSUPPORTED, name + ": ray-batch queries read Moller-Trumbore records (upload with PT_OPT_TRI_TEST 0)");
+    if (q.n == 0) return PT_OK;
+    if (!q.rays || !outputs) return fail(c, PT_ERR_INVALID, name + ": null argument");
+    if (q.n >= (1ull << 32)) return fail(c, PT_ERR_INVALID, name + ": more than 2^32 - 1 rays in one call");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->opt_timing) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    HIP_TRY(c, launch_query(c, q));
+    if (c->opt_timing) { HIP_TRY(c, hipEventRecord(c->ev1, c->stream)); c->timed = true; }
+    return PT_OK;
+}
+
+int pt_closest_hits(pt_ctx* c, const float* rays_dev, size_t n, int cull, float* t_dev, int32_t* tri_dev, float* normal_dev) {
+    return query_call(c, "pt_closest_hits", t_dev && tri_dev, ptmi::QueryCall{rays_dev, n, cull, t_dev, tri_dev, normal_dev, nullptr});
+}
+
+int pt_any_hits(pt_ctx* c, const float* rays_dev, size_t n, int cull, uint8_t* hit_dev) {
+    return query_call(c, "pt_any_hits", hit_dev != nullptr, ptmi::QueryCall{rays_dev, n, cull, nullptr, nullptr, nullptr, hit_dev});
+}
+
 int pt_get_counters(pt_ctx* c, pt_counters* out) {
     if (!c || !out) return fail(c, PT_ERR_INVALID, "pt_get_counters: null argument");
     unsigned long long h[PT_CNT_WAVE];

@@ -192,6 +192,17 @@ class PathTracer:
     def trace_rays(self, rays_ptr, n, cull, t_ptr, tri_ptr, normal_ptr=None):
         self._check(self._lib.pt_trace_rays(self._ctx, rays_ptr, n, int(cull), t_ptr, tri_ptr, normal_ptr))
 
+    def closest_hits(self, rays_ptr, n, cull, t_ptr, tri_ptr, normal_ptr=None):
+        """The nearest triangle inside (0, t_max) of every ray (pt_closest_hits): rays float[n][8] = (o, ignored, d, t_max);
+        t float[n] (FLT_MAX on a miss), the original id int32[n] (-1), the un-normalised normal float[n][3] (optional).
+        Asynchronous until sync()."""
+        self._check(self._lib.pt_closest_hits(self._ctx, rays_ptr, n, int(cull), t_ptr, tri_ptr, normal_ptr))
+
+    def any_hits(self, rays_ptr, n, cull, hit_ptr):
+        """Whether any triangle lies inside (0, t_max) of every ray (pt_any_hits): one byte per ray, 1 or 0 — a torch.bool
+        tensor's data_ptr() will do.  Asynchronous until sync()."""
+        self._check(self._lib.pt_any_hits(self._ctx, rays_ptr, n, int(cull), hit_ptr))
+
     def render_aux(self, cam, params, albedo_ptr, normal_ptr, position_ptr, id_ptr=None):
         """First-hit guide buffers of the pixel-centre rays (pt_render_aux): albedo, normal, position as float[H][W][4], the hit
         id as int32[H][W] (optional).  Asynchronous until sync()."""

@@ -437,6 +437,37 @@ int pt_frame_error(pt_ctx* ctx, const float* moments_dev, int32_t width, int32_t
 int pt_trace_rays(pt_ctx* ctx, const float* rays_dev, size_t n_rays, int cull_backfaces,
                   float* t_dev, int32_t* tri_dev, float* normal_dev);
 
+/* ---- bounded ray-batch queries — an EXTENSION ---------------------------
+ * pt_closest_hits and pt_any_hits answer "what does this ray hit" and "is this segment blocked" for a caller's rays: shadow and
+ * visibility tests, ambient occlusion, picking, line of sight.  Both run the 4-wide walk of the stage-split pipeline's extend
+ * stage on persistent waves (a tree too deep for that walk takes the binary walk of pt_trace_rays and gives the same results).
+ *   rays_dev: float[n][8] = (ox, oy, oz, ignored, dx, dy, dz, t_max) — pt_trace_rays' stride; word 3 is never read.
+ * A triangle is hit when 0 < t < t_max in binary32, strict on both sides, with t from the records and the arithmetic of
+ * pt_trace_rays (cull_backfaces included).  t_max = +inf or any value >= FLT_MAX: unbounded.  A ray whose t_max is not greater
+ * than 0 (0, negative, NaN) is a miss and is not walked.  Triangles only: the spheres take no part, as in pt_trace_rays.
+ * The walk prunes boxes with the bound too, and a box's entry distance is not rounded as a triangle's t is; so that a hit just
+ * below t_max is not lost with its box, every ray's box tests (never its triangle tests) are widened by a margin above the
+ * rounding error of both: t_max = the next float above a hit's t finds the hit, t_max = t does not.
+ *   pt_closest_hits, for the nearest such hit (of two at the same t the smaller id): t_dev float[n] (FLT_MAX on a miss, not the
+ *     bound), tri_dev int32[n] (original id, -1 on a miss), normal_dev float[n][3] as pt_trace_rays writes it (0 on a miss; may
+ *     be NULL).  With t_max = +inf these are pt_trace_rays' outputs, except that a grazing ray may pass between the two trees'
+ *     boxes differently (see PT_OPT_REBUILD).
+ *   pt_any_hits: hit_dev uint8[n], 1 when such a hit exists, else 0; one byte per ray and nothing beyond byte n - 1 (the
+ *     storage of a torch.bool tensor qualifies).
+ * The outputs must not overlap rays_dev (a lane reads rays that another lane's result could already have overwritten); this is
+ * not checked.  Errors, in this order: NULL ctx PT_ERR_INVALID; no tree PT_ERR_NO_SCENE; Woop records (PT_OPT_TRI_TEST 1)
+ * PT_ERR_UNSUPPORTED; n_rays == 0 PT_OK, nothing written; a NULL rays_dev, t_dev, tri_dev or hit_dev PT_ERR_INVALID;
+ * n_rays >= 2^32 PT_ERR_INVALID.  Asynchronous on the context's stream: ordered after pt_refit_bvh, usable between pt_render
+ * calls, and no call allocates or synchronises (the work counters belong to the context and are reset on the stream before
+ * each launch).  With PT_OPT_TIMING=1, pt_last_kernel_ms covers the call.  PT_OPT_WAVE_BATCH, PT_OPT_WAVE_BLOCKS and
+ * PT_OPT_LDS_STACK 24 apply as to the extend stage: speed, never results.  PT_OPT_COUNTERS is ignored (pt_get_counters keeps
+ * the last render's figures).  Left out: a t_min other than 0, spheres, Woop records, per-ray cull flags, which triangle an
+ * any-hit query found. */
+int pt_closest_hits(pt_ctx* ctx, const float* rays_dev, size_t n_rays, int cull_backfaces,
+                    float* t_dev, int32_t* tri_dev, float* normal_dev);
+int pt_any_hits(pt_ctx* ctx, const float* rays_dev, size_t n_rays, int cull_backfaces,
+                uint8_t* hit_dev);
+
 /* ---- guide buffers and denoiser — an EXTENSION --------------------------
  * pt_render_aux: the first hit of ONE ray through every pixel centre (the camera ray of pt_render with zero jitter), for a
  * denoiser or for picking.  Triangles by the binary closest-hit walk of pt_trace_rays, then the spheres with the path kernels'
