@@ -2,6 +2,7 @@
 // of the hot path.  The reference builds on the host (SplitBVHBuilder.cpp, 1.7 s per 100 k
 // triangles) and so does host/pthost.cpp (SAH/SBVH, ~1.4 s for 800 k; here 1.8 ms); this is the fast
 // alternative for scenes that change: Morton order, then PLOC clustering (default) or a linear BVH
+//   0. k_build_reset  the counters' initial values (nothing is copied from the host for them)
 //   1. k_tri_bounds   triangle boxes + bounds of the box centres (ordered-int atomics)
 //   2. k_morton       63-bit Morton key of every centre (21 bits per axis)
 //   3. hipcub radix sort of (key, triangle)
@@ -24,6 +25,7 @@
 #include "pt_items.h"
 
 #define PTB_BLOCK 256
+#define PTB_LEVEL_CNT 68     // entries of BuildArrays::level_cnt (k_collapse of level l <= 64 counts into entry l + 1)
 
 struct BuildArrays {
     // inputs
@@ -50,8 +52,8 @@ struct BuildArrays {
     unsigned int* arrive;    // [n-1] depth of the inner node (level of the bottom-up fit)
     // outputs
     float4* items;           // [binary nodes n-1][records n][wide nodes <= n-1]
-    unsigned int* stats;     // [0] wide nodes allocated [1] - [2] leaves [3] max binary depth
-    unsigned int* level_cnt; // [66] frontier size of every wide level (level 0 = 1: the root)
+    unsigned int* stats;     // [0] wide nodes allocated [1] PLOC's merges so far (k_ploc_merge) [2] leaves [3] max binary depth
+    unsigned int* level_cnt; // [PTB_LEVEL_CNT] frontier size of every wide level (level 0 = 1: the root)
     int2* frontier_a; int2* frontier_b;   // (inner node, wide slot)
 };
 
@@ -61,6 +63,16 @@ __device__ __forceinline__ unsigned int ptb_ordered(float f) {
 }
 __device__ __forceinline__ float ptb_unordered(unsigned int u) {
     return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+
+// Initial values, written on the device so that no launch waits for a copy from host memory that must outlive it: empty centre
+// bounds, wide slot 0 taken (the root's), one entry in the first frontier: (node 0, slot 0).  One block of PTB_LEVEL_CNT threads.
+__global__ void k_build_reset(const BuildArrays B) {
+    const unsigned int i = threadIdx.x;
+    if (i < 6) B.cbounds[i] = i < 3 ? 0xffffffffu : 0u;
+    if (i < 4) B.stats[i] = i == 0 ? 1u : 0u;
+    if (i < PTB_LEVEL_CNT) B.level_cnt[i] = i == 0 ? 1u : 0u;
+    if (i == 0) B.frontier_a[0] = make_int2(0, 0);
 }
 
 // ---- pre-splitting (early split clipping, Ernst & Greiner 2007) -----------------------------------

@@ -12,6 +12,7 @@ import pytest
 import gpu_pathtracer_amd as g
 import orc
 from gpu_support import gpu_trace
+from tree_audit import canonical_form
 
 pytestmark = pytest.mark.gpu
 
@@ -183,6 +184,46 @@ def test_degenerate_inputs():
         # ... and the context still works afterwards
         t.build_bvh(g.Mesh.from_arrays(v, ok))
         assert gpu_trace(t, rays, False)[1].tolist() == [0, -1, -1]
+    finally:
+        t.close()
+
+
+def built(t, mesh, algo):
+    """(canonical form, scene_info, wide depth) of the tree pt_build_bvh makes of `mesh` with hierarchy `algo`."""
+    t.set_option(g.OPT_BUILD_ALGO, algo)
+    t.build_bvh(mesh)
+    B, R, W, wide_depth = t.tree_items()
+    return canonical_form(B, R, W), t.scene_info(), wide_depth
+
+
+def test_a_ploc_build_that_gives_up_yields_the_tree_a_direct_lbvh_build_yields():
+    """The mesh of test_degenerate_inputs, 300 copies of one triangle plus 5 of another (305 primitives): among identical boxes
+    PLOC merges one pair per round, so it runs out of its 192 rounds and the driver starts again with the Karras hierarchy.
+    What comes out must be what PT_OPT_BUILD_ALGO 0 makes directly, up to the numbering of the nodes (tree_audit.canonical_form).
+    (Were PLOC to finish on this mesh, its chain would differ from the LBVH's balanced tree and the test would fail.)"""
+    v = np.array([[-1, -1, -5], [1, -1, -5], [0, 1, -5], [3, -1, -6], [5, -1, -6], [4, 1, -6]], np.float32)
+    m = g.Mesh.from_arrays(v, np.array([[0, 1, 2]] * 300 + [[3, 4, 5]] * 5, np.int32))
+    t = g.PathTracer(0)
+    try:
+        for leaf_max in (1, 2, 8):
+            t.set_option(g.OPT_LEAF_MAX, leaf_max)
+            (form1, info1, depth1), (form0, info0, depth0) = built(t, m, 1), built(t, m, 0)
+            print(f"leaf_max {leaf_max}: {info0}, wide depth {depth0}, {len(form0)} bytes")
+            assert form1 == form0
+            assert info1 == info0 and depth1 == depth0
+    finally:
+        t.close()
+
+
+@pytest.mark.parametrize("algo", [0, 1])
+def test_a_build_is_reproducible(algo):
+    """Two builds of one mesh on one context give the same tree up to the numbering of the nodes."""
+    mesh = g.scene_mesh("bunny_low")
+    t = g.PathTracer(0)
+    try:
+        first, second = built(t, mesh, algo), built(t, mesh, algo)
+        assert first[0] == second[0]
+        assert first[1:] == second[1:]
     finally:
         t.close()
 

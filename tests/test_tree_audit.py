@@ -346,6 +346,48 @@ def test_coverage_sees_a_leaf_box_that_misses_a_part_of_its_triangle(tree):
     assert ta.audit(B, R, W, info, soup, wide_depth=wd, split_refs=True, coverage=False) == []
 
 
+# -------------------------------------------------------------------------------------------------------- canonical form
+def permuted(A, link_words, base, seed):
+    """A's rows under a random renumbering that keeps row 0, every inner link following its target."""
+    perm = np.concatenate([[0], 1 + np.random.default_rng(seed).permutation(len(A) - 1)])     # old row -> new row
+    out = np.empty_like(A)
+    out[perm] = A
+    Oi = out.view(np.int32)
+    for w in link_words:
+        inner = Oi[:, w] >= 0
+        Oi[inner, w] = base + 4 * perm[(Oi[inner, w] - base) // 4]
+    return out
+
+
+def test_the_canonical_form_does_not_depend_on_the_numbering(tree):
+    soup, B, R, W, info, wd = tree
+    form = ta.canonical_form(B, R, W)
+    wide_base = 4 * (len(B) + len(R))
+    assert form[:R.nbytes + B.nbytes] == R.tobytes() + B.tobytes()       # numpy_tree numbers its binary nodes depth-first already
+    for seed in (1, 2, 3):
+        Bp, Wp = permuted(B, (12, 13), 0, seed), permuted(W, (10, 11, 12, 13), wide_base, 10 + seed)
+        assert not np.array_equal(Bp, B) and not np.array_equal(Wp, W)
+        assert ta.audit(Bp, R, Wp, info, soup, wide_depth=wd, leaf_max=3, strict=True, coverage=True) == []     # still the same valid tree
+        assert ta.canonical_form(Bp, R, Wp) == form
+        assert ta.canonical_form(Bp, R, W) == form and ta.canonical_form(B, R, Wp) == form
+
+
+def test_the_canonical_form_sees_what_is_not_numbering(tree):
+    soup, B, R, W, info, wd = tree
+    form = ta.canonical_form(B, R, W)
+    Bs = B.copy()                                  # the root's children change places: another child order
+    Bs[0, 0:4], Bs[0, 4:8] = B[0, 4:8], B[0, 0:4]
+    Bs[0, 8:10], Bs[0, 10:12] = B[0, 10:12], B[0, 8:10]
+    Bs[0, 12], Bs[0, 13] = B[0, 13], B[0, 12]
+    assert ta.canonical_form(Bs, R, W) != form
+    Ws = W.copy()                                  # a wide node's first two links change places
+    Ws.view(np.int32)[0, 10], Ws.view(np.int32)[0, 11] = W.view(np.int32)[0, 11], W.view(np.int32)[0, 10]
+    assert ta.canonical_form(B, R, Ws) != form
+    Rs = R.copy()
+    Rs.view(np.int32)[5, 5] += 1                   # one ulp in a record
+    assert ta.canonical_form(B, Rs, W) != form
+
+
 # ----------------------------------------------------------------------------------------------------------------- fma32
 def f32(x):
     return np.float32(x)

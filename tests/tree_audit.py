@@ -2,6 +2,7 @@
 item and checks it against the exact geometry.  numpy only: no GPU, no library of the project.
 
     audit(binary, records, wide, info, soup, wide_depth=..., ...) -> [Violation(kind, item, what), ...]      ([] = pass)
+    canonical_form(binary, records, wide) -> bytes         (equal for two trees that differ only in how their nodes are numbered)
 
 Everything is exact: the trees are deterministic data.  fma32 is the one piece of arithmetic numpy lacks — a fused multiply-add
 rounded ONCE to binary32; it is computed in rational arithmetic.  fma32_fast runs a vector through binary64 and sends to fma32
@@ -196,6 +197,47 @@ def triangle_points(v9):
                 p[:, ax] = x
                 pts = np.concatenate([pts, p])
     return np.clip(pts, lo, hi)
+
+
+# ------------------------------------------------------------------------------------------------------- canonical form
+def _renumbered(A, link_words, base, n_children):
+    """The rows of A reachable from row 0 in depth-first order (children in the order of link_words), every inner link
+    (>= 0: base + 4 * row) rewritten to the new numbers; leaf links (< 0) untouched."""
+    Ai = A.view(np.int32)
+    new, order, stack = {}, [], [0]
+    while stack:
+        i = stack.pop()
+        if i in new:
+            raise ValueError(f"row {i} is reached twice")
+        new[i] = len(order)
+        order.append(i)
+        kids = [(int(Ai[i, w]) - base) // 4 for w in link_words[:n_children(Ai[i])] if Ai[i, w] >= 0]
+        stack.extend(reversed(kids))
+    out = A[order].copy()
+    Oi = out.view(np.int32)
+    for w in link_words:
+        inner = Oi[:, w] >= 0
+        Oi[inner, w] = [base + 4 * new[(int(x) - base) // 4] for x in Oi[inner, w]]
+    return out
+
+
+def _wide_children(row):
+    n = 1
+    while n < 4 and row[10 + n] != row[10]:
+        n += 1
+    return n
+
+
+def canonical_form(binary, records, wide):
+    """The bytes of a tree up to the numbering of its nodes.  The device builder hands out inner-node numbers (k_ploc_merge) and
+    wide slots (k_collapse) from atomic counters, so they depend on scheduling; topology, child order and record order do not.
+    The form is the record section as it is, the binary nodes renumbered depth-first from node 0 (child 0 before child 1), the
+    wide nodes renumbered depth-first from slot 0 (children in slot order), every node link rewritten to the new numbers and
+    every leaf link untouched.  Nodes that no link reaches (below the multi-record leaves of a device-built tree: ptb_is_cut)
+    have no place in that order and are left out."""
+    B, R, W = (np.ascontiguousarray(x, np.float32).reshape(-1, 16) for x in (binary, records, wide))
+    return (R.tobytes() + _renumbered(B, (12, 13), 0, lambda row: 2).tobytes()
+            + _renumbered(W, (10, 11, 12, 13), 4 * (len(B) + len(R)), _wide_children).tobytes())
 
 
 # ---------------------------------------------------------------------------------------------------------------- audit
