@@ -90,6 +90,7 @@ FLAG_RR_CPU_TRACER = 1 << 7
 FLAG_NEE = 1 << 8
 FLAGS_SMALLPT = FLAG_FACE_FORWARD | FLAG_COSINE_DIFF | FLAG_RUSSIAN_ROULETTE | FLAG_MISS_KEEPS_PATH
 FLAGS_CPU_TRACER = FLAG_FACE_FORWARD | FLAG_COSINE_DIFF | FLAG_RR_CPU_TRACER | FLAG_MISS_KEEPS_PATH
+RAYS_CLAMPED, RAYS_HDR = 0, 1
 KERNEL_AUTO, KERNEL_MEGA_BVH2, KERNEL_PERSISTENT, KERNEL_WAVEFRONT = 0, 1, 3, 5
 OPT_KERNEL, OPT_COUNTERS, OPT_TIMING, OPT_BATCH, OPT_TOP_NODES, OPT_OCCUPANCY, OPT_LDS_STACK, OPT_WALK, OPT_LEAF_MAX, OPT_TRI_TEST, OPT_REFILL, OPT_VOTE_NODE, OPT_VOTE_REC, OPT_WAVE_BATCH, OPT_SPHERE_LDS, OPT_BUILD_ALGO, OPT_REBUILD, OPT_PRESPLIT, OPT_WAVE_BLOCKS, OPT_OVERLAP, OPT_OPTIMIZE, OPT_WAVE_SAMPLES = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 21, 24, 25
 OPT_FIRST_WALK, OPT_PACKET_STACK, OPT_FUSE_STAGES, OPT_LAST_ANYHIT = 26, 27, 28, 29
@@ -120,6 +121,7 @@ PTMI_SYMBOLS = [
     ("pt_trace_rays", _i, [_vp, _vp, _sz, _i, _vp, _vp, _vp]),
     ("pt_closest_hits", _i, [_vp, _vp, _sz, _i, _vp, _vp, _vp]),
     ("pt_any_hits", _i, [_vp, _vp, _sz, _i, _vp]),
+    ("pt_render_rays", _i, [_vp, _vp, _sz, C.c_uint64, _vp, C.POINTER(Params), _u32, _i]),
     ("pt_render_aux", _i, [_vp, C.POINTER(Camera), C.POINTER(Params), _vp, _vp, _vp, _vp]),
     ("pt_denoise", _i, [_vp, C.POINTER(DenoiseParams), _vp, _vp, _vp, _vp, _vp, _vp]),
     ("pt_temporal", _i, [_vp, C.POINTER(TemporalParams), C.POINTER(Camera), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

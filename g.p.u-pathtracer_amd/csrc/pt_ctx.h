@@ -1,6 +1,6 @@
 // pt_ctx.h — the context behind the C ABI (include/ptmi.h) and the host-side helpers shared by the
 // translation units of libptmi.so: ptmi.hip (API), pt_tree.hip (trees: makers, adoption, cost), pt_build.hip (device BVH
-// builder), pt_k_*.hip (kernel families + their launchers).  Host code only.
+// builder), pt_k_*.hip (kernel families + their launchers; pt_k_rays.hip also holds its API function).  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -83,8 +83,8 @@ struct pt_ctx {
     int opt_timing = 0;
     // measurement
     unsigned long long* d_counters = nullptr;
-    unsigned int* d_queue = nullptr;   // work counters of the persistent kernel and of the ray-batch queries (pt_k_query.hip), on the caller's stream: reset there before every launch
-    float* d_samples = nullptr;        // [spp][H*W][3] sample colours of a multi-sample call
+    unsigned int* d_queue = nullptr;   // work counters of the persistent kernel, of the ray-batch queries (pt_k_query.hip) and of pt_render_rays (pt_k_rays.hip), on the caller's stream: reset there before every launch
+    float* d_samples = nullptr;        // [spp][H*W][3] sample colours of a multi-sample call; pt_render_rays: [spp][n][3] (both on the caller's stream)
     size_t samples_bytes = 0;
     int n_cu = 0;
     int opt_batch = 36;
@@ -231,14 +231,14 @@ auto with_int(int v, F&& f) {
 
 // A grid of resident blocks for a kernel whose waves draw work from a queue: what the device holds at once (at most `max_per_cu` per
 // CU), never more than `work_cap`.  No grid-wide wait anywhere: an over-estimate only means a few late blocks find the queue empty.
-template <class K, class A>
-hipError_t launch_resident(K kernel, size_t lds, int max_per_cu, int n_cu, size_t work_cap, hipStream_t st, const A& P) {
+template <class K, class... A>
+hipError_t launch_resident(K kernel, size_t lds, int max_per_cu, int n_cu, size_t work_cap, hipStream_t st, const A&... args) {
     int per_cu = 0;
     const hipError_t e = allow_lds(kernel, lds);
     if (e != hipSuccess) return e;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, PT_BLOCK, lds) != hipSuccess || per_cu < 1) per_cu = 1;
     per_cu = std::min(per_cu, max_per_cu);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<size_t>((size_t)per_cu * n_cu, work_cap)), dim3(PT_BLOCK), lds, st, P);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<size_t>((size_t)per_cu * n_cu, work_cap)), dim3(PT_BLOCK), lds, st, args...);
     return hipGetLastError();
 }
 
@@ -283,6 +283,13 @@ struct QueryCall {
     uint8_t* hit;
 };
 hipError_t launch_query(pt_ctx* c, const QueryCall& q);
+// what pt_render and pt_render_rays (pt_k_rays.hip) share of a path call's set-up (ptmi.hip):
+// the kernel arguments that the context and pt_params give to ANY path kernel — scene, materials, estimator, frame numbers; zeroes the rest
+void fill_path_params(const pt_ctx* c, const pt_params* p, uint32_t spp, KParams& P);
+// PT_FLAG_NEE over emissive triangles: brings the light list up to date on the caller's stream
+int refresh_tri_lights(pt_ctx* c, const pt_params* p);
+// the call's sample buffer into P.samples, the side slot's own or (sd = nullptr) the context's, grown to `need` bytes
+int samples_reserve(pt_ctx* c, pt_ctx::Side* sd, size_t need, KParams& P);
 // PT_OPT_TIMING: marks the end of a stage of the running call on the context's stream (no-op when timing is off)
 int stage_mark(pt_ctx* c, int kind_of_work_since_last_mark);
 // device BVH builder (pt_build.hip), a maker: the tree over the mesh into `out` (its build_ms set), the context's own tree untouched.

@@ -1,0 +1,316 @@
+// pt_k_rays.hip — pt_render_rays: the path loop over a caller's rays (other cameras, probes, baking), its fold and its launcher.
+// One translation unit of libptmi.so (pt_ctx.h).  DESIGN.md §10 f10.
+//
+// k_render_rays is k_trace_persist_bvh2 (pt_k_persist.hip) with another path start: persistent waves draw chunks of (sample, ray)
+// slots from the context's sharded queue, idle lanes take the next slots by a ballot + prefix count, lanes with a segment in flight
+// run the resumable walk, lanes whose walk finished shade.  A slot q is sample q / n of ray q % n: its path starts at the ray as it
+// stands in the buffer, with the RNG of pixel first_index + ray behind the camera's two jitter draws, and from there on it is
+// path_shade and the walks of the frame kernels, so a batch that equals a camera's rays gives that camera's image bit for bit.
+// What the frame kernels do not have and this one does: a guard in front of the walk (a ray that is not finite or has no direction
+// ends as a first-segment miss) and, in the NEE instantiations, the shadow ray of PT_FLAG_NEE as a second walk of the same lane —
+// the loop of pt_get_sample (pt_kernels.h) laid out over the phases, which the frame kernel leaves to the other two families.
+// The ray buffer, the output, n and first_index travel as a second kernel argument: KParams stays the first one, at offset 0, for
+// PT_KARGS and pt_closest_sphere, and keeps its layout.
+#include <cstring>
+
+#include "pt_ctx.h"
+
+struct KRays {
+    const float4* __restrict__ rays;   // [n][2]: (o.xyz, ignored) (d.xyz, ignored)
+    float* __restrict__ out;           // [n][3] running mean of the samples' radiance
+    unsigned long long first_index;    // RNG key of ray 0
+    uint32_t n;
+    int hdr;                           // PT_RAYS_HDR: the fold does not clamp
+};
+
+enum { RP_IDLE = 0, RP_TRAV = 1, RP_SHADE = 2, RP_MISS = 3 };   // RP_MISS: shaded as a first segment that hit nothing, never walked
+
+// pt_accumulate, or with HDR the same running mean without its clamp: a = (a * (N - 1) + col) * (1 / N), N == 1 overwrites
+template <bool HDR>
+__device__ __forceinline__ void rays_accumulate(float& ax, float& ay, float& az, v3 col, uint64_t N) {
+    if (!HDR) { pt_accumulate(ax, ay, az, col, N); return; }
+    const float fm1 = (float)(N - 1), inv = 1.0f / (float)N;
+    if (N == 1) { ax = 0.f; ay = 0.f; az = 0.f; } else { ax *= fm1; ay *= fm1; az *= fm1; }
+    ax = (ax + col.x) * inv;
+    ay = (ay + col.y) * inv;
+    az = (az + col.z) * inv;
+}
+
+__device__ __forceinline__ bool rays_finite(v3 a) {
+    return fabsf(a.x) <= PT_F32_MAX && fabsf(a.y) <= PT_F32_MAX && fabsf(a.z) <= PT_F32_MAX;   // false for a NaN
+}
+
+// NEE: the lane can walk the shadow ray path_shade asks for (PT_FLAG_NEE) before it goes on with the path
+template <bool NEE, int OCC, int LSTK, int ALG>
+__global__ void __launch_bounds__(PT_BLOCK, OCC) k_render_rays(const KParams P, const KRays R) {
+    // sphere attributes + centres for the shading code (see path_shade): the table of k_trace_persist_bvh2, filled from the device
+    // array (the first PT_KSPHERES spheres there are the ones in the kernel arguments; rows past n_spheres are never read)
+    if (P.sph_tab >= 0 && (int)threadIdx.x < 11 * min(P.sc.n_spheres, PT_KSPHERES)) {
+        const float v = ((const float*)P.sc.spheres)[threadIdx.x];
+        ((float*)s_dyn)[P.sph_tab + threadIdx.x] = v;
+        if (threadIdx.x % 11 < 4) ((float*)s_dyn)[P.sph_tab + 88 + 4 * (threadIdx.x / 11) + threadIdx.x % 11] = v;
+    }
+    __syncthreads();
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    TravOverflow<LSTK> stk_ovf;
+    TravStack<LSTK, PT_BLOCK> stk(__builtin_amdgcn_readfirstlane(tid & ~63), stk_ovf);
+    const bool cull = P.cull != 0;
+    const unsigned long long total = (unsigned long long)R.n * (P.samples ? P.spp : 1u);   // (the launcher keeps it below 2^32)
+
+    uint32_t chunk_next = 0, chunk_end = 0;  // wave-uniform
+    bool queue_empty = false;                // wave-uniform
+    int shard = (int)(blockIdx.x & (PT_SHARDS - 1));
+    const uint32_t chunk = (uint32_t)P.chunk;
+    const uint32_t shard_chunks = (uint32_t)(((total + chunk - 1) / chunk + PT_SHARDS - 1) / PT_SHARDS);
+
+    int phase = RP_IDLE;
+    uint32_t ray = 0, s_idx = 0;
+    PathState ps;
+    TravState ts;
+    ps.o = ps.d = ps.mask = ps.accu = V3(0.f, 0.f, 0.f);
+    ps.depth = 0; ps.rng.s0 = ps.rng.s1 = ps.rng.n = 0; ps.nee_mask = 0;
+    ts.idx = ts.idy = ts.idz = ts.oodx = ts.oody = ts.oodz = 0.f;
+    ts.node = PT_SENTINEL; ts.leaf = 0; ts.sp = 0;
+    ts.h = pt_no_hit();
+    // NEE: the shadow ray in flight (sh & 1) instead of the path's own segment, which waits in ps; sh & 2: the path ended with the
+    // bounce that asked for it
+    int sh = 0;
+    v3 sh_o = V3(0.f, 0.f, 0.f), sh_d = sh_o, sh_con = sh_o;
+    float sh_tmax = 0.f;
+    TravCount tc;
+
+    for (;;) {
+        // ---- A. refill idle lanes (all 64 lanes are converged here)
+        const unsigned long long idle = __ballot(phase == RP_IDLE);
+        const int n_idle = __popcll(idle);
+        const int n_busy = __popcll(__ballot(phase == RP_TRAV));
+        if (!queue_empty && (n_idle >= P.refill || (n_idle > 0 && n_busy == 0))) {
+            if (chunk_next == chunk_end) {
+                // shard s owns chunks s, s + 8, ...; an empty shard is left for the next one (k_trace_persist_bvh2)
+                for (int tries = 0; tries < PT_SHARDS; tries++) {
+                    uint32_t k = 0;
+                    if (lane == 0) k = atomicAdd(P.queue + shard * PT_SHARD_STRIDE, 1u);
+                    k = (uint32_t)__builtin_amdgcn_readfirstlane((int)k);
+                    const unsigned long long first = ((unsigned long long)k * PT_SHARDS + (unsigned long long)shard) * chunk;
+                    if (k < shard_chunks && first < total) {
+                        chunk_next = (uint32_t)first;
+                        chunk_end = (uint32_t)min(first + chunk, total);
+                        break;
+                    }
+                    shard = (shard + 1) & (PT_SHARDS - 1);
+                }
+                if (chunk_next == chunk_end) queue_empty = true;
+            }
+            const uint32_t avail = chunk_end - chunk_next;
+            const uint32_t take = min((uint32_t)n_idle, avail);
+            if (phase == RP_IDLE) {
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+                if (rank < take) {
+                    const uint32_t q = chunk_next + rank;   // < total
+                    s_idx = q / R.n;
+                    ray = q - s_idx * R.n;
+                    const float4 a = pt_sld4(R.rays + 2 * (size_t)ray), b = pt_sld4(R.rays + 2 * (size_t)ray + 1);
+                    ps.o = V3(a.x, a.y, a.z);
+                    ps.d = V3(b.x, b.y, b.z);
+                    // the stream a camera path of this (frame, pixel) sees behind its two jitter draws (path_begin_hashed)
+                    ps.rng = pt_rng_init(pt_wang64(P.frame + s_idx), R.first_index + ray);
+                    ps.rng.n = 2;
+                    ps.mask = V3(1.f, 1.f, 1.f);
+                    ps.accu = V3(0.f, 0.f, 0.f);
+                    ps.depth = 0;
+                    ps.nee_mask = 0;
+                    sh = 0;
+                    ts.h = pt_no_hit();
+                    // the guard: only a finite ray with a direction is ever walked or tested against a sphere
+                    const bool good = rays_finite(ps.o) && rays_finite(ps.d) && !(ps.d.x == 0.f && ps.d.y == 0.f && ps.d.z == 0.f);
+                    if (P.depth == 0) {
+                        phase = RP_SHADE;
+                    } else if (!good) {
+                        phase = RP_MISS;
+                    } else if (P.sc.has_bvh) {
+                        trav_begin(ts, ps.o, ps.d, stk, ALG >= 2 ? P.sc.wide_root : 0);
+                        phase = RP_TRAV;
+                    } else {
+                        phase = RP_SHADE;
+                    }
+                }
+            }
+            chunk_next += take;
+        }
+
+        // ---- B. closest-hit walk for the lanes with a segment (or a shadow ray) in flight
+        {
+            const int n_dead = queue_empty ? __popcll(__ballot(phase == RP_IDLE)) : 0;
+            if (phase == RP_TRAV) {
+                const v3 wo = NEE && (sh & 1) ? sh_o : ps.o, wd = NEE && (sh & 1) ? sh_d : ps.d;
+                const bool fin = (ALG >= 2) ? trav_run_wide<false, true, ALG == 3>(ts, P.sc, wo, wd, cull, stk, tc, n_dead, P.batch)
+                                            : trav_run_unified<false, true>(ts, P.sc, wo, wd, cull, stk, tc, n_dead, P.batch);
+                if (fin) phase = RP_SHADE;
+            }
+        }
+
+        // ---- C. shade finished segments
+        if (phase >= RP_SHADE) {
+            v3 col = V3(0.f, 0.f, 0.f);
+            bool done, walk_shadow = false;
+            if (P.depth == 0) {
+                done = true;
+            } else if (phase == RP_MISS) {
+                // path_shade_hit's miss branch for the first segment: the background, by the rule of the flags
+                col = V3(P.bk[0], P.bk[1], P.bk[2]);
+                if (P.flags & PT_FLAG_MISS_KEEPS_PATH) col = vadd(ps.accu, vmul(ps.mask, col));
+                done = true;
+            } else if (NEE && (sh & 1)) {
+                // the shadow ray's walk is back (pt_get_sample): unoccluded up to the light -> its contribution joins the gathered light
+                if (!(ts.h.t < sh_tmax)) ps.accu = vadd(ps.accu, sh_con);
+                done = (sh & 2) != 0;
+                col = ps.accu;   // (a path that ended with that bounce returned the gathered light: path_shade_hit's last line)
+                sh = 0;
+            } else {
+                NeeReq req;
+                req.want = false;
+                done = path_shade(P, ps, ts.h, col, P.sph_tab, NEE && (P.flags & PT_FLAG_NEE) ? &req : nullptr);
+                if (NEE && req.want) {
+                    if (P.sc.has_bvh) {
+                        walk_shadow = true;
+                        sh = done ? 3 : 1;
+                        sh_o = req.o; sh_d = req.d; sh_con = req.contrib; sh_tmax = req.t_max;
+                    } else {   // no triangle can be in the way
+                        ps.accu = vadd(ps.accu, req.contrib);
+                        if (done) col = ps.accu;
+                    }
+                }
+            }
+            if (NEE && walk_shadow) {
+                trav_begin(ts, sh_o, sh_d, stk, ALG >= 2 ? P.sc.wide_root : 0);
+                phase = RP_TRAV;
+            } else if (!done) {
+                if (P.sc.has_bvh) {
+                    trav_begin(ts, ps.o, ps.d, stk, ALG >= 2 ? P.sc.wide_root : 0);
+                    phase = RP_TRAV;
+                }  // else: stays RP_SHADE with the (miss) hit record, shaded again next round
+            } else if (P.samples) {
+                pt_sst3(pt_sample_ptr(P, s_idx, (size_t)ray), col);   // read once, by the fold
+                phase = RP_IDLE;
+            } else {
+                // one sample per launch: folded straight into the caller's running mean
+                float* acc = R.out + 3 * (size_t)ray;
+                float ax = 0.f, ay = 0.f, az = 0.f;
+                if (P.sample_index != 1) { ax = acc[0]; ay = acc[1]; az = acc[2]; }
+                if (R.hdr) rays_accumulate<true>(ax, ay, az, col, P.sample_index);
+                else rays_accumulate<false>(ax, ay, az, col, P.sample_index);
+                acc[0] = ax; acc[1] = ay; acc[2] = az;
+                phase = RP_IDLE;
+            }
+        }
+
+        if (queue_empty && !__ballot(phase != RP_IDLE)) break;
+    }
+}
+
+// Folds the launch's samples [spp][n][3] into the running mean of every ray, in sample order: one lane per ray.
+template <bool HDR>
+__global__ void __launch_bounds__(256) k_fold_rays(const KParams P, const KRays R) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)R.n) return;
+    float* acc = R.out + 3 * i;
+    float ax = 0.f, ay = 0.f, az = 0.f;
+    if (P.sample_index != 1) { ax = acc[0]; ay = acc[1]; az = acc[2]; }
+    for (uint32_t s = 0; s < P.spp; s++) rays_accumulate<HDR>(ax, ay, az, pt_sld3(pt_sample_ptr(P, s, i)), P.sample_index + s);
+    acc[0] = ax; acc[1] = ay; acc[2] = az;
+}
+
+namespace ptmi {
+
+// Instantiated: the wide walk (2; 3 = Woop records) and the unified binary walk (1: trees too deep for the wide one, PT_OPT_WALK 0 / 1),
+// each at 6 waves per SIMD without and at 4 with the shadow-ray state, 16 stack entries per lane in LDS.
+static hipError_t launch_render_rays(const pt_ctx* c, int walk, bool nee, size_t lds, int work_blocks, const KParams& P, const KRays& R) {
+    return with_bool(nee, [&](auto n) {
+        return with_int<3, 2, 1>(walk, [&](auto alg) {
+            constexpr int OCC = n() ? 4 : 6;
+            return launch_resident(k_render_rays<n(), OCC, 16, alg()>, lds, INT_MAX, c->n_cu, (size_t)std::max(1, work_blocks), c->stream, P, R);
+        });
+    });
+}
+
+// slots of one launch: what keeps its sample buffer below 768 MiB; more samples than that go out as several launches, which the
+// fold's order makes the same thing
+static constexpr uint64_t RAYS_MAX_SLOTS = 1ull << 26;
+
+}  // namespace ptmi
+
+extern "C" int pt_render_rays(pt_ctx* c, const float* rays_dev, size_t n_rays, uint64_t first_index, float* radiance_dev,
+                              const pt_params* p, uint32_t spp, int mode) {
+    using namespace ptmi;
+    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
+    if (!c->tree.has_bvh && c->n_spheres == 0) return fail(c, PT_ERR_NO_SCENE, "pt_render_rays: no scene uploaded");
+    if (n_rays == 0 || spp == 0) return PT_OK;
+    if (!rays_dev || !radiance_dev || !p) return fail(c, PT_ERR_INVALID, "pt_render_rays: null argument");
+    if (mode != PT_RAYS_CLAMPED && mode != PT_RAYS_HDR) return fail(c, PT_ERR_INVALID, "pt_render_rays: mode must be PT_RAYS_CLAMPED or PT_RAYS_HDR");
+    if (n_rays >= (1ull << 32)) return fail(c, PT_ERR_INVALID, "pt_render_rays: more than 2^32 - 1 rays in one call");
+    // ... then pt_render's own conditions on the fields both read
+    if (p->sample_index == 0) return fail(c, PT_ERR_INVALID, "pt_render_rays: sample_index starts at 1");
+    if (p->tri_mat < PT_MAT_DIFF || p->tri_mat > PT_MAT_REFR) return fail(c, PT_ERR_INVALID, "pt_render_rays: bad triangle material");
+    if ((p->flags & PT_FLAG_NEE) && !(p->flags & PT_FLAG_COSINE_DIFF)) return fail(c, PT_ERR_INVALID, "pt_render_rays: PT_FLAG_NEE needs PT_FLAG_COSINE_DIFF");
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = refresh_tri_lights(c, p);
+    if (rc != PT_OK) return rc;
+
+    // the walk, by the persistent kernel's rules (plan_call): Woop records and trees too deep for the wide walk
+    const TreeState& t = c->tree;
+    const bool wide_ok = t.has_bvh && 3 * t.wide_depth + 2 <= (uint32_t)PT_STACK_CAP;
+    int walk = c->opt_walk >= 2 ? 2 : 1;
+    if (t.has_bvh && t.records_woop) {
+        if (!wide_ok) return fail(c, PT_ERR_UNSUPPORTED, "pt_render_rays: Woop records need the wide walk and this tree is too deep for it");
+        walk = 3;
+    } else if (walk == 2 && !wide_ok) {
+        walk = 1;
+    }
+
+    KParams P;
+    fill_path_params(c, p, spp, P);
+    P.sc.stack_n = 16;
+    P.sc.top_base = walk >= 2 ? P.sc.wide_root : 0;
+    size_t lds = (size_t)16 * PT_BLOCK * 4;
+    P.sph_tab = -1;
+    if (c->opt_sph_lds) {   // sphere table behind the stacks
+        P.sph_tab = (int)(lds / 4);
+        lds += 15 * PT_KSPHERES * 4;
+    }
+    P.queue = c->d_queue;   // the context's counters: every use is on the caller's stream, behind a reset of its own
+    P.batch = c->opt_batch;
+    P.refill = c->opt_refill < c->opt_batch ? c->opt_refill : c->opt_batch;
+    KRays R;
+    std::memset(&R, 0, sizeof R);
+    R.rays = (const float4*)rays_dev;
+    R.out = radiance_dev;
+    R.first_index = first_index;
+    R.n = (uint32_t)n_rays;
+    R.hdr = mode == PT_RAYS_HDR;
+
+    const uint32_t per_launch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(spp, RAYS_MAX_SLOTS / n_rays));
+    if (per_launch > 1 && (rc = samples_reserve(c, nullptr, (size_t)per_launch * n_rays * 3 * sizeof(float), P)) != PT_OK) return rc;
+    P.smp_ss = n_rays;
+    P.smp_ps = 1u;
+    if (c->opt_timing) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    for (uint32_t s0 = 0; s0 < spp; s0 += per_launch) {
+        P.spp = std::min(per_launch, spp - s0);
+        P.frame = p->frame + s0;
+        P.sample_index = p->sample_index + s0;
+        const uint64_t slots = (uint64_t)n_rays * (per_launch > 1 ? P.spp : 1u);
+        const uint64_t waves = (uint64_t)c->n_cu * 20;   // queue granularity as plan_call: smaller chunks for small launches
+        P.chunk = slots / 64 >= 4 * waves ? 64 : (slots / 32 >= 4 * waves ? 32 : 16);
+        const int work_blocks = (int)std::min<uint64_t>((slots + (uint64_t)P.chunk * 4 - 1) / ((uint64_t)P.chunk * 4), (uint64_t)INT_MAX);
+        HIP_TRY(c, hipMemsetAsync(P.queue, 0, PT_SHARDS * PT_SHARD_STRIDE * sizeof(unsigned int), c->stream));
+        HIP_TRY(c, launch_render_rays(c, walk, (p->flags & PT_FLAG_NEE) != 0, lds, work_blocks, P, R));
+        if (per_launch > 1) {
+            with_bool(R.hdr != 0, [&](auto hdr) {
+                hipLaunchKernelGGL(k_fold_rays<hdr()>, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, c->stream, P, R);
+            });
+            HIP_TRY(c, hipGetLastError());
+        }
+    }
+    if (c->opt_timing) { HIP_TRY(c, hipEventRecord(c->ev1, c->stream)); c->timed = true; }
+    return PT_OK;
+}

@@ -363,7 +363,7 @@ static bool samples_tri_lights(const pt_ctx* c, const pt_params* p) {
 }
 
 // the scene, its geometry (pt_refit_bvh) or the materials changed: copies the lights' vertices out of the records again
-static int refresh_tri_lights(pt_ctx* c, const pt_params* p) {
+extern "C++" int refresh_tri_lights(pt_ctx* c, const pt_params* p) {   // (pt_ctx.h; this namespace block sits inside extern "C")
     if (!samples_tri_lights(c, p)) return PT_OK;
     if (c->tree.records_woop) return fail(c, PT_ERR_UNSUPPORTED, "pt_render: PT_FLAG_NEE over emissive triangles needs the exact (Moller-Trumbore) records");
     const uint64_t key = (c->scene_gen << 32) ^ c->mat_gen;
@@ -382,9 +382,8 @@ static int refresh_tri_lights(pt_ctx* c, const pt_params* p) {
     return PT_OK;
 }
 
-// the kernel arguments that the context and the call's arguments give; what the plan decides (samples, LDS layout, queue) is added
-// by pt_render_moments.  A part that owns no tile leaves P.n_tiles <= 0 and PT_OK: nothing to render.
-static int fill_params(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, const pt_camera* cam, const pt_params* p, uint32_t spp, KParams& P) {
+// the kernel arguments that the context and pt_params give to any path kernel, a frame's or a ray batch's (pt_ctx.h)
+extern "C++" void fill_path_params(const pt_ctx* c, const pt_params* p, uint32_t spp, KParams& P) {
     std::memset(&P, 0, sizeof P);
     P.sc.nodes = c->tree.d_nodes;
     P.sc.tris = c->tree.d_nodes;   // one item buffer
@@ -393,10 +392,7 @@ static int fill_params(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, const pt
     std::memcpy(P.ksph, c->h_spheres, sizeof P.ksph);
     P.sc.has_bvh = c->tree.has_bvh ? 1 : 0;
     P.sc.wide_root = (int)c->tree.wide_root;
-    P.accum = accum_dev;
-    P.rgba = rgba_dev;
     P.counters = c->d_counters;
-    P.cam = *cam;
     P.W = p->width; P.H = p->height;
     P.depth = p->depth;
     P.cull = p->cull_backfaces;
@@ -411,6 +407,15 @@ static int fill_params(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, const pt
         P.tri_lights = c->d_tri_lights;
         P.n_tri_lights = (int)c->emissive_ids.size();
     }
+}
+
+// the kernel arguments that the context and the call's arguments give; what the plan decides (samples, LDS layout, queue) is added
+// by pt_render_moments.  A part that owns no tile leaves P.n_tiles <= 0 and PT_OK: nothing to render.
+static int fill_params(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, const pt_camera* cam, const pt_params* p, uint32_t spp, KParams& P) {
+    fill_path_params(c, p, spp, P);
+    P.accum = accum_dev;
+    P.rgba = rgba_dev;
+    P.cam = *cam;
     P.smp_ss = (unsigned long long)p->width * (unsigned long long)p->height;   // one sample per pixel, or sample planes (plan.sgroup_log2 = 0)
     P.smp_ps = 1u;
     P.tiles_x = (p->width + PT_TILE - 1) / PT_TILE;
@@ -577,7 +582,7 @@ static int side_acquire(pt_ctx* c, pt_ctx::Side*& sd) {
 }
 
 // the sample buffer of the call, the side slot's own or the context's, grown to `need` bytes
-static int samples_reserve(pt_ctx* c, pt_ctx::Side* sd, size_t need, KParams& P) {
+extern "C++" int samples_reserve(pt_ctx* c, pt_ctx::Side* sd, size_t need, KParams& P) {
     float*& buf = sd ? sd->samples : c->d_samples;
     size_t& have = sd ? sd->samples_bytes : c->samples_bytes;
     if (need > have) {

@@ -9,7 +9,7 @@
 //               --out image.ppm|.png|.pfm  --checkpoint state.ckpt [--checkpoint-every N]
 //               --resume state.ckpt --device-build --fix-estimators --nee --gpus N --tile ROWS
 //               --denoise-out image.ppm|.png|.pfm  --variance-out file.pfm  --until-error E --max-frames M
-//               --pan-deg D --dolly S --temporal-out image.ppm|.png|.pfm]
+//               --pan-deg D --dolly S --temporal-out image.ppm|.png|.pfm  --equirect]
 // --gpus N splits the framebuffer over N contexts, one per GPU (devices device, device+1, ... modulo the number
 // present, so N > 1 also runs on a one-GPU box): stripes of --tile rows (default 8) are dealt round-robin
 // (pt_params.part_*), every context holds the whole scene and renders only its stripes of every frame — the random
@@ -42,6 +42,12 @@
 // last call, and --out is what it is without the flag, byte for byte.  --temporal-out works on one context over the whole frame
 // and keeps no state a checkpoint could hold: it is refused with --gpus > 1, --resume, --checkpoint, --variance-out and
 // --until-error; so are the motion options with --resume, --checkpoint and --until-error (nothing accumulates across frames).
+// --equirect renders a 360 x 180 degree latitude-longitude image seen from the camera position instead of the pinhole frame: column x
+// looks at longitude (x - W/2) 2 pi / W from `front` towards `right`, row y at latitude (y - H/2) pi / H towards `up` (the pole), so
+// the centre pixel looks along `front` and column 0 meets column W-1 behind it.  The rays are made on the host, one per pixel, and
+// every call renders them through pt_render_rays (pixel y W + x draws the random numbers of that pixel of a pinhole frame):
+// clamped mode when --out is a .png / .ppm, HDR when it is a .pfm.  There is no pinhole frame, so --equirect is refused with
+// --denoise-out, --temporal-out, --variance-out, --until-error, --gpus > 1, --checkpoint, --resume and the motion options.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -62,7 +68,7 @@ static int die(const char* what, const char* msg) {
 int main(int argc, char** argv) {
     std::string mesh_path, out_path, ckpt_path, resume_path, denoise_path, variance_path, temporal_path;
     int W = 1280, H = 720, frames = 16, depth = 4, mat = PT_MAT_DIFF, device = 0, spp = 1, ckpt_every = 0, gpus = 1, tile = 8;
-    bool spheres = true, use_materials = true, device_build = false, fix_estimators = false, nee = false;
+    bool spheres = true, use_materials = true, device_build = false, fix_estimators = false, nee = false, equirect = false;
     float bk[3] = {1.f, 1.f, 1.f};
     double until_error = -1.0;   // < 0: off
     long max_frames = -1;
@@ -93,6 +99,7 @@ int main(int argc, char** argv) {
         else if (a == "--device-build") device_build = true;
         else if (a == "--fix-estimators") fix_estimators = true;
         else if (a == "--nee") nee = true;   // next-event estimation (implies the cosine-weighted DIFF lobe and keeps a path's light on a miss)
+        else if (a == "--equirect") equirect = true;
         else if (a == "--spp") spp = std::atoi(next("--spp"));
         else if (a == "--checkpoint") ckpt_path = next("--checkpoint");
         else if (a == "--checkpoint-every") ckpt_every = std::atoi(next("--checkpoint-every"));
@@ -116,6 +123,8 @@ int main(int argc, char** argv) {
         return die("usage", "--temporal-out does not combine with --gpus > 1, --resume, --checkpoint, --variance-out or --until-error");
     if (moving && (!resume_path.empty() || !ckpt_path.empty() || until))
         return die("usage", "--pan-deg / --dolly do not combine with --resume, --checkpoint or --until-error (a moving camera restarts the accumulation every frame)");
+    if (equirect && (!denoise_path.empty() || temporal || with_moments || gpus > 1 || !ckpt_path.empty() || !resume_path.empty() || moving))
+        return die("usage", "--equirect does not combine with --denoise-out, --temporal-out, --variance-out, --until-error, --gpus > 1, --checkpoint, --resume, --pan-deg or --dolly (they need the pinhole frame)");
 
     const bool is_ptmesh = mesh_path.size() > 7 && mesh_path.substr(mesh_path.size() - 7) == ".ptmesh";
     pth_mesh* mesh = is_ptmesh ? pth_mesh_load_ptmesh(mesh_path.c_str()) : pth_mesh_load_obj(mesh_path.c_str());
@@ -303,6 +312,27 @@ int main(int argc, char** argv) {
         for (int i = 0; i < 3; i++) { cam_pos[i] += dolly * (double)cam.front[i]; cam.pos[i] = (float)cam_pos[i]; }
     };
 
+    // --equirect: the latitude-longitude rays of the pixels, float[H W][8], made once (the camera stands still)
+    void* eq_rays = nullptr;
+    const bool out_pfm = out_path.size() > 4 && out_path.substr(out_path.size() - 4) == ".pfm";
+    if (equirect) {
+        const double pi = 3.14159265358979323846;
+        std::vector<float> rays((size_t)W * H * 8, 0.f);
+        for (int y = 0; y < H; y++)
+            for (int x = 0; x < W; x++) {
+                const double lon = (x - W / 2.0) * 2.0 * pi / W, lat = (y - H / 2.0) * pi / H;
+                double d[3], len = 0.0;
+                for (int i = 0; i < 3; i++) {
+                    d[i] = std::cos(lat) * (std::cos(lon) * cam.front[i] + std::sin(lon) * cam.right[i]) + std::sin(lat) * cam.up[i];
+                    len += d[i] * d[i];
+                }
+                float* r = &rays[((size_t)y * W + x) * 8];
+                for (int i = 0; i < 3; i++) { r[i] = cam.pos[i]; r[4 + i] = (float)(d[i] / std::sqrt(len)); }
+            }
+        if (pt_malloc(ctx, rays.size() * 4, &eq_rays) != PT_OK || pt_upload(ctx, eq_rays, rays.data(), rays.size() * 4) != PT_OK)
+            return die("equirect rays", pt_last_error(ctx));
+    }
+
     const uint64_t first_frame = frameNumber;
     uint64_t end_frame = frameNumber + (uint64_t)frames;
     const uint64_t last_frame = until ? frameNumber + (uint64_t)max_frames : end_frame;   // --until-error: never past --max-frames
@@ -318,6 +348,10 @@ int main(int argc, char** argv) {
             if (moving && calls > 0) move_camera(calls);                                // the camera is dirty: start over (:399)
             p.frame = frameNumber;                                                      // :397
             p.sample_index = moving ? 1 : constantPdf + 1;                              // :399 (1 on the first frame: overwrite)
+            if (equirect) {
+                if (pt_render_rays(ctx, (const float*)eq_rays, (size_t)W * H, 0, (float*)accum, &p, n, out_pfm ? PT_RAYS_HDR : PT_RAYS_CLAMPED) != PT_OK)
+                    return die("pt_render_rays", pt_last_error(ctx));
+            } else
             for (int g = 0; g < gpus; g++) {                                            // :404, once per GPU: asynchronous, so the GPUs run side by side
                 p.part_index = g;
                 if (pt_render_moments(ctxs[(size_t)g], (float*)accums[(size_t)g], (uint32_t*)rgbas[(size_t)g], (float*)moments[(size_t)g], &cam, &p, n) != PT_OK)
@@ -366,7 +400,7 @@ int main(int argc, char** argv) {
             rc = pth_write_pfm(out_path.c_str(), host_acc.data(), W, H);
         } else {
             std::vector<uint32_t> img((size_t)W * H);
-            if (frames == 0) {  // nothing rendered in this run (e.g. --resume only to convert): pack the accumulator here
+            if (frames == 0 || equirect) {  // nothing rendered in this run (e.g. --resume only to convert), or no display words (pt_render_rays): pack the accumulator here
                 host_acc.resize((size_t)W * H * 3);
                 if (int grc = gather(accums, host_acc.data(), 12)) return grc;
                 for (size_t i = 0; i < img.size(); i++) {   // rgbToUint, cudaUtils.h:99-105
@@ -445,6 +479,7 @@ int main(int argc, char** argv) {
             for (void* b : {t_color[k], t_len[k], t_alb[k], t_nrm[k], t_pos[k]}) pt_free(ctx, b);
         pt_free(ctx, t_rgba);
     }
+    if (eq_rays) pt_free(ctx, eq_rays);
     (void)accum; (void)rgba;
     if (moments_all != moments[0]) pt_free(ctx, moments_all);
     for (int g = 0; g < gpus; g++) {

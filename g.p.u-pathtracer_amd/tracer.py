@@ -203,6 +203,13 @@ class PathTracer:
         tensor's data_ptr() will do.  Asynchronous until sync()."""
         self._check(self._lib.pt_any_hits(self._ctx, rays_ptr, n, int(cull), hit_ptr))
 
+    def render_rays(self, rays_ptr, n, out_ptr, params, spp=1, first_index=0, hdr=False):
+        """Path-trace a caller's rays (pt_render_rays): rays float[n][8] = (o, ignored, d, ignored) with unit d; out float[n][3], the
+        running mean of the radiance per ray, N = params.sample_index ..; ray i draws the random numbers of pixel first_index + i.
+        hdr: the mean is not clamped to 0..1.  Asynchronous until sync()."""
+        self._check(self._lib.pt_render_rays(self._ctx, rays_ptr, int(n), int(first_index), out_ptr, C.byref(params), int(spp),
+                                             _abi.RAYS_HDR if hdr else _abi.RAYS_CLAMPED))
+
     def render_aux(self, cam, params, albedo_ptr, normal_ptr, position_ptr, id_ptr=None):
         """First-hit guide buffers of the pixel-centre rays (pt_render_aux): albedo, normal, position as float[H][W][4], the hit
         id as int32[H][W] (optional).  Asynchronous until sync()."""

@@ -468,6 +468,52 @@ int pt_closest_hits(pt_ctx* ctx, const float* rays_dev, size_t n_rays, int cull_
 int pt_any_hits(pt_ctx* ctx, const float* rays_dev, size_t n_rays, int cull_backfaces,
                 uint8_t* hit_dev);
 
+/* ---- radiance along a caller's rays — an EXTENSION -----------------------
+ * pt_render_rays path-traces rays the caller made: other cameras (fisheye, equirectangular, orthographic, thin lens, stereo),
+ * light probes, baking, paths continued from a host's own visibility pass.  pt_render derives a path's first segment from the pinhole
+ * camera and the pixel; here it is read from a buffer, and everything behind it is the path kernels' loop unchanged: depth,
+ * cull_backfaces, spheres, the global or per-triangle materials, every PT_FLAG_* estimator switch, next-event estimation, roulette.
+ *   rays_dev: float[n][8] = (ox, oy, oz, ignored, dx, dy, dz, ignored) — pt_trace_rays' stride; words 3 and 7 are never read.  d is
+ *     used as given, NOT normalised: pass unit directions, as pt_render's camera makes them (the spheres' test and every lobe
+ *     assume them).
+ *   radiance_dev: float[n][3], the running mean per ray; must not overlap rays_dev (not checked).
+ * Ray i, sample s = 0 .. spp-1: a path that starts at (o, d) with the random stream of pt_render's pixel number first_index + i in
+ * frame params->frame + s, positioned behind the two draws a camera path spends on its sub-pixel jitter.  So a batch equal to a
+ * camera's rays of frame f (jitter included), with first_index = 0, width = the image's and frame = f, reproduces that frame's
+ * samples bit for bit.  All spp samples of a ray start from the same ray; a caller who wants anti-aliasing jitters its rays
+ * across calls.  The samples are folded in order with N = params->sample_index + s, N == 1 overwrites:
+ *   PT_RAYS_CLAMPED  pt_render's fold exactly: a = clamp01((a * (N - 1) + col) * (1 / N)) per component;
+ *   PT_RAYS_HDR      a = (a * (N - 1) + col) * (1 / N), no clamp, plain binary32 * and + (a = 0 in front of the sum when N == 1):
+ *                    for probes and baking.
+ * spp samples in one call equal any split of them over several calls (frame and sample_index advanced alike) bit for bit, and one
+ * call over n rays equals calls over its parts with first_index advanced by the rays before each part: first_index splits a batch
+ * over calls or contexts.
+ * pt_params: depth, cull_backfaces, frame, sample_index, tri_mat / tri_col / tri_emi, bk_color, air_ior, glass_ior, phong_expo and
+ * flags are read as by pt_render; width only by PT_FLAG_METAL_LITERAL_W; height, part_* and PT_FLAG_WRITE_RGBA are ignored.
+ * depth == 0 folds black samples, as pt_render does.
+ * A ray whose direction has a component that is not finite or is (0, 0, 0), or whose origin is not finite, is never walked or
+ * tested against a sphere: its samples are those of a path whose first segment hit nothing — bk_color (under
+ * PT_FLAG_MISS_KEEPS_PATH the same value as 0 + 1 * bk_color); at depth 0 black like every other ray.
+ * Errors, in this order: NULL ctx PT_ERR_INVALID; neither a tree nor spheres PT_ERR_NO_SCENE; n_rays == 0 or spp == 0 PT_OK,
+ * nothing written; a NULL rays_dev, radiance_dev or params PT_ERR_INVALID; a mode other than the two PT_ERR_INVALID;
+ * n_rays >= 2^32 PT_ERR_INVALID; then pt_render's own: sample_index == 0, a bad tri_mat, PT_FLAG_NEE without PT_FLAG_COSINE_DIFF
+ * PT_ERR_INVALID; PT_FLAG_NEE over emissive triangles with Woop records PT_ERR_UNSUPPORTED.  Woop records (PT_OPT_TRI_TEST 1)
+ * otherwise run, as in pt_render's persistent kernel: the wide walk with tolerance-class parity, PT_ERR_UNSUPPORTED when the tree is
+ * too deep for that walk.
+ * The kernel is the persistent kernel's loop — (sample, ray) slots drawn from a work queue by resident waves, the 4-wide walk, or
+ * the binary one for PT_OPT_WALK 0 / 1 and for trees too deep — so a few rays with many samples fill the device as well as many
+ * rays with one.  PT_OPT_BATCH, PT_OPT_REFILL and PT_OPT_SPHERE_LDS apply: speed, never results.  PT_OPT_KERNEL, PT_OPT_COUNTERS and
+ * PT_KERNEL_AUTO's table are neither read nor changed (pt_get_counters keeps the last render's figures).
+ * Asynchronous on the context's stream: ordered after pt_refit_bvh, usable between pt_render calls.  With spp > 1 the samples go
+ * through the context's sample buffer ([spp][n][3] floats, at most 768 MiB: more samples run as several launches), which pt_render
+ * shares: grown on demand — that call synchronises the stream once — freed by pt_destroy, not counted in pt_scene_info.  With
+ * PT_OPT_TIMING=1, pt_last_kernel_ms covers the call.
+ * Left out: the stage-split pipeline and its packet walk for ray batches; a per-ray t_max or t_min; per-ray RNG keys other than
+ * first_index + i; luminance moments; display words. */
+enum { PT_RAYS_CLAMPED = 0, PT_RAYS_HDR = 1 };
+int pt_render_rays(pt_ctx* ctx, const float* rays_dev, size_t n_rays, uint64_t first_index,
+                   float* radiance_dev, const pt_params* params, uint32_t spp, int mode);
+
 /* ---- guide buffers and denoiser — an EXTENSION --------------------------
  * pt_render_aux: the first hit of ONE ray through every pixel centre (the camera ray of pt_render with zero jitter), for a
  * denoiser or for picking.  Triangles by the binary closest-hit walk of pt_trace_rays, then the spheres with the path kernels'
