@@ -47,6 +47,12 @@ class TemporalParams(C.Structure):
                 ("plane_tolerance", C.c_float), ("normal_threshold", C.c_float), ("_pad", C.c_int32)]
 
 
+class Environment(C.Structure):
+    """pt_environment — the latitude-longitude map of pt_upload_environment (extension, include/ptmi.h; 64 bytes)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("front", C.c_float * 3), ("right", C.c_float * 3),
+                ("up", C.c_float * 3), ("scale", C.c_float * 3), ("filter", C.c_int32), ("_pad", C.c_int32)]
+
+
 class CheckpointInfo(C.Structure):
     """pth_checkpoint_info (host/pthost.h)."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("next_frame", C.c_uint64),
@@ -91,6 +97,7 @@ FLAG_NEE = 1 << 8
 FLAGS_SMALLPT = FLAG_FACE_FORWARD | FLAG_COSINE_DIFF | FLAG_RUSSIAN_ROULETTE | FLAG_MISS_KEEPS_PATH
 FLAGS_CPU_TRACER = FLAG_FACE_FORWARD | FLAG_COSINE_DIFF | FLAG_RR_CPU_TRACER | FLAG_MISS_KEEPS_PATH
 RAYS_CLAMPED, RAYS_HDR = 0, 1
+ENV_NEAREST, ENV_BILINEAR = 0, 1
 KERNEL_AUTO, KERNEL_MEGA_BVH2, KERNEL_PERSISTENT, KERNEL_WAVEFRONT = 0, 1, 3, 5
 OPT_KERNEL, OPT_COUNTERS, OPT_TIMING, OPT_BATCH, OPT_TOP_NODES, OPT_OCCUPANCY, OPT_LDS_STACK, OPT_WALK, OPT_LEAF_MAX, OPT_TRI_TEST, OPT_REFILL, OPT_VOTE_NODE, OPT_VOTE_REC, OPT_WAVE_BATCH, OPT_SPHERE_LDS, OPT_BUILD_ALGO, OPT_REBUILD, OPT_PRESPLIT, OPT_WAVE_BLOCKS, OPT_OVERLAP, OPT_OPTIMIZE, OPT_WAVE_SAMPLES = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 21, 24, 25
 OPT_FIRST_WALK, OPT_PACKET_STACK, OPT_FUSE_STAGES, OPT_LAST_ANYHIT = 26, 27, 28, 29
@@ -122,6 +129,8 @@ PTMI_SYMBOLS = [
     ("pt_closest_hits", _i, [_vp, _vp, _sz, _i, _vp, _vp, _vp]),
     ("pt_any_hits", _i, [_vp, _vp, _sz, _i, _vp]),
     ("pt_render_rays", _i, [_vp, _vp, _sz, C.c_uint64, _vp, C.POINTER(Params), _u32, _i]),
+    ("pt_upload_environment", _i, [_vp, C.POINTER(Environment), _vp]),
+    ("pt_eval_environment", _i, [_vp, _vp, _sz, _vp]),
     ("pt_render_aux", _i, [_vp, C.POINTER(Camera), C.POINTER(Params), _vp, _vp, _vp, _vp]),
     ("pt_denoise", _i, [_vp, C.POINTER(DenoiseParams), _vp, _vp, _vp, _vp, _vp, _vp]),
     ("pt_temporal", _i, [_vp, C.POINTER(TemporalParams), C.POINTER(Camera), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -170,6 +179,8 @@ PTHOST_SYMBOLS = [
     ("pth_write_ppm", _i, [C.c_char_p, _vp, _i, _i]),
     ("pth_write_png", _i, [C.c_char_p, _vp, _i, _i]),
     ("pth_write_pfm", _i, [C.c_char_p, _vp, _i, _i]),
+    ("pth_read_pfm", _i, [C.c_char_p, C.POINTER(_i), C.POINTER(_i), C.POINTER(_vp)]),
+    ("pth_free_pfm", None, [_vp]),
     ("pth_checkpoint_save", _i, [C.c_char_p, C.POINTER(CheckpointInfo), _vp]),
     ("pth_checkpoint_load", _i, [C.c_char_p, C.POINTER(CheckpointInfo), _vp]),
     ("pth_frame_hash", C.c_uint64, [C.c_uint64]),

@@ -1,6 +1,6 @@
 // pt_ctx.h — the context behind the C ABI (include/ptmi.h) and the host-side helpers shared by the
 // translation units of libptmi.so: ptmi.hip (API), pt_tree.hip (trees: makers, adoption, cost), pt_build.hip (device BVH
-// builder), pt_k_*.hip (kernel families + their launchers; pt_k_rays.hip also holds its API function).  Host code only.
+// builder), pt_k_*.hip (kernel families + their launchers; pt_k_rays.hip also holds its API function), pt_env.hip (environment map).  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -77,6 +77,10 @@ struct pt_ctx {
     uint64_t lights_gen = 0;
     int n_spheres = 0;
     pt_sphere_d h_spheres[PT_KSPHERES];   // host copy of the first spheres for the kernel-argument block
+    // pt_upload_environment (pt_env.hip): the map as the kernels get it, env.texels the context's own device copy (nullptr: no map);
+    // env_gen counts the uploads and clears, part of PT_KERNEL_AUTO's key like scene_gen
+    KEnv env = {};
+    uint64_t env_gen = 0;
     // options
     int opt_kernel = PT_KERNEL_AUTO;
     int opt_counters = 0;
@@ -253,6 +257,7 @@ struct LaunchCfg {
     int work_blocks;   // persistent grid cap: blocks that have work at all
     int n_cu;
     bool moments;      // the call keeps luminance moments (pt_render_moments): they are the separate fold launch's job
+    bool env;          // the context has an environment map: the instantiations whose miss looks it up (pt_env.h)
 };
 hipError_t launch_mega(const LaunchCfg& L, const KParams& P, hipStream_t st);        // pt_k_mega.hip
 hipError_t launch_rays(const KScene& sc, size_t lds, const float4* rays, size_t n, int cull, float* t_out, int* tri_out,
@@ -300,6 +305,8 @@ int build_bvh_impl(pt_ctx* c, const float* verts, size_t n_verts, const int32_t*
 void refit_release(pt_ctx* c);
 // pt_denoise's and pt_frame_error's scratch (pt_denoise.hip)
 void denoise_release(pt_ctx* c);
+// the environment map's texels (pt_env.hip)
+void env_release(pt_ctx* c);
 
 }  // namespace ptmi
 

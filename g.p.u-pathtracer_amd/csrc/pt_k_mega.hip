@@ -7,7 +7,7 @@
 // OCC = waves per SIMD the register allocator must leave room for (4 / 6 / 8)
 // ALG = 0 while-while walk (Aila-Laine), 1 unified-step walk, 2 wide (4-way quantised) walk,
 //       3 wide walk over Woop records
-template <bool COUNT, int OCC, int LSTK, int ALG>
+template <bool COUNT, int OCC, int LSTK, int ALG, bool ENV>
 __global__ void __launch_bounds__(PT_BLOCK, OCC) k_trace_mega_bvh2(const KParams P) {
     float4* s_top = s_dyn;
     lds_load_top<PT_BLOCK>(P.sc, s_top);
@@ -33,7 +33,7 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_trace_mega_bvh2(const KParams
 
     uint32_t n_done = P.spp;
     if (P.samples) {
-        const v3 col = pt_get_sample<COUNT, ALG>(P, px, py, pix, P.frame + s_only, stk, s_top, tc, n_rays, n_hits);
+        const v3 col = pt_get_sample<COUNT, ALG, ENV>(P, px, py, pix, P.frame + s_only, stk, s_top, tc, n_rays, n_hits);
         float* dst = pt_sample_ptr(P, (uint32_t)s_only, (size_t)pix);
         dst[0] = col.x; dst[1] = col.y; dst[2] = col.z;
         n_done = 1;
@@ -42,7 +42,7 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_trace_mega_bvh2(const KParams
         float ax = 0.f, ay = 0.f, az = 0.f;
         if (P.sample_index != 1) { ax = acc[0]; ay = acc[1]; az = acc[2]; }
         for (uint32_t s = 0; s < P.spp; s++) {
-            const v3 col = pt_get_sample<COUNT, ALG>(P, px, py, pix, P.frame + s, stk, s_top, tc, n_rays, n_hits);
+            const v3 col = pt_get_sample<COUNT, ALG, ENV>(P, px, py, pix, P.frame + s, stk, s_top, tc, n_rays, n_hits);
             pt_accumulate(ax, ay, az, col, P.sample_index + s);
         }
         acc[0] = ax; acc[1] = ay; acc[2] = az;
@@ -87,11 +87,13 @@ namespace ptmi {
 hipError_t launch_mega(const LaunchCfg& L, const KParams& P, hipStream_t st) {
     auto go = [&](auto count, auto occ, auto lstk) {
         return with_int<2, 1, 0>(std::min(L.walk, 2), [&](auto alg) {
-            const auto kernel = k_trace_mega_bvh2<count(), occ(), lstk(), alg()>;
-            const hipError_t e = allow_lds(kernel, L.lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kernel, dim3(L.blocks), dim3(PT_BLOCK), L.lds, st, P);
-            return hipGetLastError();
+            return with_bool(L.env, [&](auto env) {   // a map on the context: the instantiation that looks it up
+                const auto kernel = k_trace_mega_bvh2<count(), occ(), lstk(), alg(), env()>;
+                const hipError_t e = allow_lds(kernel, L.lds);
+                if (e != hipSuccess) return e;
+                hipLaunchKernelGGL(kernel, dim3(L.blocks), dim3(PT_BLOCK), L.lds, st, P);
+                return hipGetLastError();
+            });
         });
     };
     return with_bool(L.count, [&](auto count) {

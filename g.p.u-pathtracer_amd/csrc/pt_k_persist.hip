@@ -18,7 +18,7 @@
 #define PT_CHUNK 64
 enum { PH_IDLE = 0, PH_TRAV = 1, PH_SHADE = 2 };
 
-template <bool COUNT, int OCC, int LSTK, int ALG>
+template <bool COUNT, int OCC, int LSTK, int ALG, bool ENV>
 __global__ void __launch_bounds__(PT_BLOCK, OCC) k_trace_persist_bvh2(const KParams P) {
     float4* s_top = s_dyn;
     if (P.sph_tab >= 0 && threadIdx.x < 11 * PT_KSPHERES) {  // sphere attributes + centres for the shading code (see path_shade)
@@ -150,7 +150,7 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_trace_persist_bvh2(const KPar
                 done = true;
             } else {
                 if (COUNT) { n_rays++; n_hits += (ts.h.tri != -1); }
-                done = path_shade(P, ps, ts.h, col, P.sph_tab);
+                done = path_shade<ENV>(P, ps, ts.h, col, P.sph_tab);
             }
             if (!done) {
                 if (P.sc.has_bvh) {
@@ -253,8 +253,10 @@ namespace ptmi {
 hipError_t launch_persist(const LaunchCfg& L, const KParams& P, hipStream_t st) {
     return with_bool(L.count, [&](auto count) {
         auto go = [&](auto occ, auto lstk, auto alg) {
-            return launch_resident(k_trace_persist_bvh2<count(), occ(), lstk(), alg()>, L.lds, INT_MAX, L.n_cu,
-                                   (size_t)std::max(1, L.work_blocks), st, P);
+            return with_bool(L.env, [&](auto env) {   // a map on the context: the instantiation that looks it up
+                return launch_resident(k_trace_persist_bvh2<count(), occ(), lstk(), alg(), env()>, L.lds, INT_MAX, L.n_cu,
+                                       (size_t)std::max(1, L.work_blocks), st, P);
+            });
         };
         auto binary = [&](auto occ, auto lstk) { return L.walk == 1 ? go(occ, lstk, int_c<1>) : go(occ, lstk, int_c<0>); };
         auto wide = [&](auto occ, auto lstk) { return with_int<4, 3, 2>(L.walk, [&](auto alg) { return go(occ, lstk, alg); }); };

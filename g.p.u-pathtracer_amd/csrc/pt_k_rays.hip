@@ -41,7 +41,7 @@ __device__ __forceinline__ bool rays_finite(v3 a) {
 }
 
 // NEE: the lane can walk the shadow ray path_shade asks for (PT_FLAG_NEE) before it goes on with the path
-template <bool NEE, int OCC, int LSTK, int ALG>
+template <bool NEE, int OCC, int LSTK, int ALG, bool ENV>
 __global__ void __launch_bounds__(PT_BLOCK, OCC) k_render_rays(const KParams P, const KRays R) {
     // sphere attributes + centres for the shading code (see path_shade): the table of k_trace_persist_bvh2, filled from the device
     // array (the first PT_KSPHERES spheres there are the ones in the kernel arguments; rows past n_spheres are never read)
@@ -157,7 +157,8 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_render_rays(const KParams P, 
             if (P.depth == 0) {
                 done = true;
             } else if (phase == RP_MISS) {
-                // path_shade_hit's miss branch for the first segment: the background, by the rule of the flags
+                // path_shade_hit's miss branch for the first segment: the background, by the rule of the flags.  bk_color even with an
+                // environment map on the context (pt_upload_environment): such a ray has no direction to look up (include/ptmi.h)
                 col = V3(P.bk[0], P.bk[1], P.bk[2]);
                 if (P.flags & PT_FLAG_MISS_KEEPS_PATH) col = vadd(ps.accu, vmul(ps.mask, col));
                 done = true;
@@ -170,7 +171,7 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_render_rays(const KParams P, 
             } else {
                 NeeReq req;
                 req.want = false;
-                done = path_shade(P, ps, ts.h, col, P.sph_tab, NEE && (P.flags & PT_FLAG_NEE) ? &req : nullptr);
+                done = path_shade<ENV>(P, ps, ts.h, col, P.sph_tab, NEE && (P.flags & PT_FLAG_NEE) ? &req : nullptr);
                 if (NEE && req.want) {
                     if (P.sc.has_bvh) {
                         walk_shadow = true;
@@ -224,12 +225,15 @@ __global__ void __launch_bounds__(256) k_fold_rays(const KParams P, const KRays 
 namespace ptmi {
 
 // Instantiated: the wide walk (2; 3 = Woop records) and the unified binary walk (1: trees too deep for the wide one, PT_OPT_WALK 0 / 1),
-// each at 6 waves per SIMD without and at 4 with the shadow-ray state, 16 stack entries per lane in LDS.
+// each at 6 waves per SIMD without and at 4 with the shadow-ray state, 16 stack entries per lane in LDS; each of those without and
+// with the environment-map lookup (ENV).
 static hipError_t launch_render_rays(const pt_ctx* c, int walk, bool nee, size_t lds, int work_blocks, const KParams& P, const KRays& R) {
     return with_bool(nee, [&](auto n) {
         return with_int<3, 2, 1>(walk, [&](auto alg) {
             constexpr int OCC = n() ? 4 : 6;
-            return launch_resident(k_render_rays<n(), OCC, 16, alg()>, lds, INT_MAX, c->n_cu, (size_t)std::max(1, work_blocks), c->stream, P, R);
+            return with_bool(c->env.texels != nullptr, [&](auto env) {   // a map on the context: the instantiation that looks it up
+                return launch_resident(k_render_rays<n(), OCC, 16, alg(), env()>, lds, INT_MAX, c->n_cu, (size_t)std::max(1, work_blocks), c->stream, P, R);
+            });
         });
     });
 }

@@ -7,6 +7,7 @@
 // scene, counter RNG keyed by pixel.
 #pragma once
 #include "pt_math.h"
+#include "pt_env.h"
 #include "../../include/ptmi.h"
 
 #define PT_BLOCK 256          // frame kernels: 4 waves; one wave = one 8x8 pixel tile
@@ -168,6 +169,16 @@ struct KParams {
     uint32_t sgroup_log2;          // 64 consecutive (sample, pixel) slots = 2^k samples x (64 >> k) pixels of a tile (pt_slot_pixel)
     KWave wf;
 };
+// The environment map of pt_upload_environment (KEnv, pt_env.h) rides in KParams WITHOUT making it larger: it is laid over the first
+// bytes of `wf`.  A call runs either the stage-split pipeline, which reads wf and never a map (plan_call: a context with a map does
+// not choose it), or a kernel that shades in the lane that walked, which reads the map (texels == nullptr: none, bk_color) and
+// never wf.  fill_path_params zeroes the block and copies the map in (pt_set_env); only render_wavefront writes wf.  So the size
+// of KParams, the offset of every kernel's second argument and the instruction streams of the pipeline's kernels are what they
+// were (a union of the two members already reorders two of k_wf_shade's stores).  The block is kernel-argument memory: written
+// by the host, only ever read on the device, through PT_KENV.
+static_assert(sizeof(KEnv) <= sizeof(KWave) && alignof(KEnv) <= alignof(KWave) && sizeof(KParams) == 872, "KParams must not grow: the map lies over wf");
+#define PT_KENV(K) (*(pt_kenv*)&(K).wf)   // K: PT_KARGS' reference to the kernel-argument block
+inline void pt_set_env(KParams& P, const KEnv& e) { __builtin_memcpy(&P.wf, &e, sizeof e); }
 
 // the three colour floats of (sample s, pixel pix) in the call's sample buffer
 __device__ __forceinline__ float* pt_sample_ptr(const KParams& P, uint32_t s, size_t pix) {
@@ -224,7 +235,7 @@ static_assert(PT_CNT_WAVE == sizeof(pt_counters) / sizeof(uint64_t) && PT_CNT_N 
 #include "pt_walks.h"
 #include "pt_shade.h"
 
-template <bool COUNT, int ALG, class STK>
+template <bool COUNT, int ALG, bool ENV, class STK>
 __device__ __forceinline__ v3 pt_get_sample(const KParams& P, int px, int py, uint64_t pix, uint64_t frame,
                                             STK& stk, const float4* __restrict__ s_top, TravCount& tc,
                                             uint32_t& n_rays, uint32_t& n_hits) {
@@ -253,7 +264,7 @@ __device__ __forceinline__ v3 pt_get_sample(const KParams& P, int px, int py, ui
         if (COUNT) { n_rays++; n_hits += (h.tri != -1); }
         NeeReq req;
         req.want = false;
-        const bool done = path_shade(P, ps, h, col, -1, (P.flags & PT_FLAG_NEE) ? &req : nullptr);
+        const bool done = path_shade<ENV>(P, ps, h, col, -1, (P.flags & PT_FLAG_NEE) ? &req : nullptr);
         // the loop's exit condition crosses the shadow walk below in a VGPR: kept as a lane mask in SGPRs, hipcc (ROCm 7.2)
         // lost it across the walk's wave-uniform loop and a finished path ran one more bounce
         int done_v = done ? 1 : 0;

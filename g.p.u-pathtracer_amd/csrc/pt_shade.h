@@ -1,6 +1,7 @@
 // pt_shade.h — one sample of one pixel cut into pieces: camera ray, sphere tests, shading / BRDF, accumulate
 // (getSample, tracer.cu:27-339; rows a2-a4, a8-a10).  Included by pt_kernels.h.
 #pragma once
+#include "pt_env.h"
 
 // ---------------------------------------------------------------------------------------
 // One sample of one pixel: getSample, tracer.cu:27-339, cut into the pieces both kernels
@@ -130,6 +131,11 @@ __device__ __forceinline__ SceneHit pt_closest_sphere(const KParams& P, v3 o, v3
 // gather instead of a global one.
 // tri_n: pt_hit_normal of the walk's triangle hit (read only when the triangle is what was hit; the
 // caller fetches it early so that the latency hides behind other work).
+// ENV: a segment that hits nothing looks the context's environment map up along its direction when one is set
+// (pt_upload_environment, pt_env.h) — the ENV instantiations of the kernels that shade in the lane that walked (path_shade), which
+// the launchers pick when the context has a map.  The stage-split pipeline's shade stage keeps ENV = false: it never runs with a
+// map on the context (plan_call).  ENV = false compiles to the code there was before maps existed.
+template <bool ENV = false>
 __device__ __forceinline__ bool path_shade_hit(const KParams& P, PathState& ps, const Hit& h, const SceneHit& sh, v3 tri_n, v3& col_out, int sph_tab = -1,
                                                NeeReq* nee = nullptr) {
     if (nee) nee->want = false;
@@ -178,6 +184,7 @@ __device__ __forceinline__ bool path_shade_hit(const KParams& P, PathState& ps, 
         }
     } else {
         col_out = V3(K.bk[0], K.bk[1], K.bk[2]);  // tracer.cu:140-142: unmasked background
+        if (ENV && PT_KENV(K).texels) col_out = pt_env_lookup(PT_KENV(K), d);   // extension: the map instead of the constant, by the same rules
         if (K.flags & PT_FLAG_MISS_KEEPS_PATH) col_out = vadd(accu, vmul(mask, col_out));  // extension
         return true;
     }
@@ -407,13 +414,15 @@ __device__ __forceinline__ v3 path_last_emission(const KParams& P, const PathSta
     return vadd(V3(0.f, 0.f, 0.f), vmul(ps.mask, emit));
 }
 
-// spheres + shading in one go (the kernels that shade in the lane that walked)
+// spheres + shading in one go (the kernels that shade in the lane that walked).  ENV: the instantiation for a context with an
+// environment map; without one the kernels run the ENV = false instantiations, whose code is what it was before maps existed
+template <bool ENV>
 __device__ __forceinline__ bool path_shade(const KParams& P, PathState& ps, const Hit& h, v3& col_out, int sph_tab = -1, NeeReq* nee = nullptr) {
     // the triangle's normal is asked for NOW so that its latency hides behind the sphere tests
     v3 tri_n = V3(0.f, 0.f, 0.f);
     if (h.tri != -1) tri_n = pt_hit_normal(P.sc, h);
     const SceneHit sh = pt_closest_sphere(P, ps.o, ps.d, h, sph_tab);
-    return path_shade_hit(P, ps, h, sh, tri_n, col_out, sph_tab, nee);
+    return path_shade_hit<ENV>(P, ps, h, sh, tri_n, col_out, sph_tab, nee);
 }
 
 // running mean with per-frame clamp, tracer.cu:386-391

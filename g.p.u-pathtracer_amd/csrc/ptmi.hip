@@ -170,6 +170,7 @@ int pt_destroy(pt_ctx* c) {
         if (s.folded) (void)hipEventDestroy(s.folded);
         if (s.stream) (void)hipStreamDestroy(s.stream);
     }
+    env_release(c);   // (behind the side streams' last kernels)
     for (hipEvent_t e : c->stage_ev) (void)hipEventDestroy(e);
     for (pt_ctx::AutoPick& a : c->picks)
         for (hipEvent_t e : a.e) if (e) (void)hipEventDestroy(e);
@@ -407,6 +408,7 @@ extern "C++" void fill_path_params(const pt_ctx* c, const pt_params* p, uint32_t
         P.tri_lights = c->d_tri_lights;
         P.n_tri_lights = (int)c->emissive_ids.size();
     }
+    pt_set_env(P, c->env);   // (all zero without a map; with one the stage-split pipeline, which writes wf over these bytes, is never chosen)
 }
 
 // the kernel arguments that the context and the call's arguments give; what the plan decides (samples, LDS layout, queue) is added
@@ -444,7 +446,7 @@ static int auto_lookup(pt_ctx* c, const pt_params* p, uint32_t spp, bool moments
     const uint64_t parts[] = {(uint64_t)p->width, (uint64_t)p->height, (uint64_t)spp, (uint64_t)p->depth,
                               (uint64_t)(p->part_count > 1 ? p->part_count : 1), (uint64_t)(p->part_count > 1 ? p->part_rows : 0), c->scene_gen,
                               (uint64_t)c->n_spheres, (uint64_t)p->tri_mat, (uint64_t)(p->flags & ~(uint32_t)PT_FLAG_WRITE_RGBA),
-                              (uint64_t)moments};   // with moments the pipeline keeps its separate fold and one sample goes through the sample buffer: other trial times
+                              (uint64_t)moments, c->env_gen};   // with moments the pipeline keeps its separate fold and one sample goes through the sample buffer: other trial times
     for (uint64_t v : parts) { key ^= v; key *= 0x100000001b3ull; }
     if (key == 0) key = 1;
     int slot = -1, lru = 0;
@@ -500,8 +502,9 @@ static int plan_call(pt_ctx* c, const pt_params* p, const KParams& P, uint32_t s
         L.walk = 1;
     }
     // the kernel family, every rule once and in this order: the option; PT_KERNEL_AUTO's table; PT_FLAG_NEE; what a family cannot run.
-    // The stage-split pipeline needs a BVH, at least one bounce and the wide walk over exact records.
-    const bool wave_ok = t.has_bvh && P.depth > 0 && L.walk == 2;
+    // The stage-split pipeline needs a BVH, at least one bounce, the wide walk over exact records and a context without an
+    // environment map (its last-segment any-hit launch shades misses without a ray in hand).
+    const bool wave_ok = t.has_bvh && P.depth > 0 && L.walk == 2 && !c->env.texels;
     int kernel = c->opt_kernel;
     plan.probe = -1;
     plan.pick = nullptr;
@@ -560,6 +563,7 @@ static int plan_call(pt_ctx* c, const pt_params* p, const KParams& P, uint32_t s
     L.work_blocks = (int)((slots + plan.chunk * waves_per_block - 1) / (plan.chunk * waves_per_block));
     L.n_cu = c->n_cu;
     L.moments = moments;
+    L.env = c->env.texels != nullptr;
     return PT_OK;
 }
 

@@ -170,6 +170,18 @@ def write_image(path, frame):
         _host_call(fn(path.encode(), a.ctypes.data, a.shape[1], a.shape[0]))
 
 
+def read_pfm(path):
+    """A colour PFM of either endianness -> float32 [H][W][3], rows in the file's order: what write_image(".pfm") stored, bit for
+    bit (pth_read_pfm).  An environment map for PathTracer.upload_environment."""
+    lib = _abi.pthost()
+    w, h, p = C.c_int(), C.c_int(), C.c_void_p()
+    _host_call(lib.pth_read_pfm(path.encode(), C.byref(w), C.byref(h), C.byref(p)))
+    try:
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), (h.value, w.value, 3)).copy()
+    finally:
+        lib.pth_free_pfm(p)
+
+
 def save_checkpoint(path, accum, next_frame, constant_pdf, scene_tag=0):
     a = np.ascontiguousarray(accum, np.float32)
     ci = _abi.CheckpointInfo(a.shape[1], a.shape[0], next_frame, constant_pdf, scene_tag)

@@ -9,7 +9,8 @@
 //               --out image.ppm|.png|.pfm  --checkpoint state.ckpt [--checkpoint-every N]
 //               --resume state.ckpt --device-build --fix-estimators --nee --gpus N --tile ROWS
 //               --denoise-out image.ppm|.png|.pfm  --variance-out file.pfm  --until-error E --max-frames M
-//               --pan-deg D --dolly S --temporal-out image.ppm|.png|.pfm  --equirect]
+//               --pan-deg D --dolly S --temporal-out image.ppm|.png|.pfm  --equirect
+//               --env file.pfm [--env-scale S] [--env-nearest]]
 // --gpus N splits the framebuffer over N contexts, one per GPU (devices device, device+1, ... modulo the number
 // present, so N > 1 also runs on a one-GPU box): stripes of --tile rows (default 8) are dealt round-robin
 // (pt_params.part_*), every context holds the whole scene and renders only its stripes of every frame — the random
@@ -48,6 +49,15 @@
 // every call renders them through pt_render_rays (pixel y W + x draws the random numbers of that pixel of a pinhole frame):
 // clamped mode when --out is a .png / .ppm, HDR when it is a .pfm.  There is no pinhole frame, so --equirect is refused with
 // --denoise-out, --temporal-out, --variance-out, --until-error, --gpus > 1, --checkpoint, --resume and the motion options.
+// --env file.pfm lights the scene with a latitude-longitude radiance map (pt_upload_environment): a path that leaves the scene gathers
+// the map along its direction instead of --bk.  The map lies in the world frame front = (0, 0, -1), right = (1, 0, 0), up = (0, 1, 0)
+// — the frame of this app's camera, hence of the frames --equirect writes — and is looked up bilinearly (--env-nearest: the nearest
+// texel); --env-scale S multiplies its texels.  With --gpus N every context gets it.  A checkpoint does not hold the map: pass --env
+// again with --resume.  The probe round trip: render a probe of one scene,
+//     pt_app --mesh room.ptmesh --equirect --width 512 --height 256 --out probe.pfm
+// then light another mesh with it, usually without the reference's sphere room around it:
+//     pt_app --mesh statue.ptmesh --no-spheres --env probe.pfm --out lit.png
+// With a map the stage-split pipeline is not chosen (include/ptmi.h): the persistent kernel renders, the megakernel under --nee.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -66,7 +76,9 @@ static int die(const char* what, const char* msg) {
 }
 
 int main(int argc, char** argv) {
-    std::string mesh_path, out_path, ckpt_path, resume_path, denoise_path, variance_path, temporal_path;
+    std::string mesh_path, out_path, ckpt_path, resume_path, denoise_path, variance_path, temporal_path, env_path;
+    double env_scale = 1.0;
+    bool env_scale_set = false, env_nearest = false;
     int W = 1280, H = 720, frames = 16, depth = 4, mat = PT_MAT_DIFF, device = 0, spp = 1, ckpt_every = 0, gpus = 1, tile = 8;
     bool spheres = true, use_materials = true, device_build = false, fix_estimators = false, nee = false, equirect = false;
     float bk[3] = {1.f, 1.f, 1.f};
@@ -100,6 +112,9 @@ int main(int argc, char** argv) {
         else if (a == "--fix-estimators") fix_estimators = true;
         else if (a == "--nee") nee = true;   // next-event estimation (implies the cosine-weighted DIFF lobe and keeps a path's light on a miss)
         else if (a == "--equirect") equirect = true;
+        else if (a == "--env") env_path = next("--env");
+        else if (a == "--env-scale") { env_scale = std::atof(next("--env-scale")); env_scale_set = true; }
+        else if (a == "--env-nearest") env_nearest = true;
         else if (a == "--spp") spp = std::atoi(next("--spp"));
         else if (a == "--checkpoint") ckpt_path = next("--checkpoint");
         else if (a == "--checkpoint-every") ckpt_every = std::atoi(next("--checkpoint-every"));
@@ -125,6 +140,17 @@ int main(int argc, char** argv) {
         return die("usage", "--pan-deg / --dolly do not combine with --resume, --checkpoint or --until-error (a moving camera restarts the accumulation every frame)");
     if (equirect && (!denoise_path.empty() || temporal || with_moments || gpus > 1 || !ckpt_path.empty() || !resume_path.empty() || moving))
         return die("usage", "--equirect does not combine with --denoise-out, --temporal-out, --variance-out, --until-error, --gpus > 1, --checkpoint, --resume, --pan-deg or --dolly (they need the pinhole frame)");
+
+    // --env: the map is read and checked before anything is built or rendered
+    int env_w = 0, env_h = 0;
+    float* env_px = nullptr;
+    if (env_path.empty() && env_scale_set) return die("--env-scale", "goes with --env");
+    if (env_path.empty() && env_nearest) return die("--env-nearest", "goes with --env");
+    if (!env_path.empty()) {
+        if (!std::isfinite(env_scale) || env_scale < 0.0) return die("--env-scale", "must be finite and not negative");
+        if (pth_read_pfm(env_path.c_str(), &env_w, &env_h, &env_px) != 0) return die("--env", pth_last_error());
+        if (env_w > 16384 || env_h > 16384 || (uint64_t)env_w * (uint64_t)env_h > (1ull << 26)) return die("--env", "the map is larger than 16384 texels a side or 2^26 texels");
+    }
 
     const bool is_ptmesh = mesh_path.size() > 7 && mesh_path.substr(mesh_path.size() - 7) == ".ptmesh";
     pth_mesh* mesh = is_ptmesh ? pth_mesh_load_ptmesh(mesh_path.c_str()) : pth_mesh_load_obj(mesh_path.c_str());
@@ -166,6 +192,18 @@ int main(int argc, char** argv) {
         }
     }
     if (has_materials) std::printf("%zu materials from the mesh file\n", pth_mesh_n_materials(mesh));
+    if (env_px) {   // the map in the world frame, on every context
+        pt_environment ev{};
+        ev.width = env_w; ev.height = env_h;
+        ev.front[2] = -1.f; ev.right[0] = 1.f; ev.up[1] = 1.f;
+        ev.scale[0] = ev.scale[1] = ev.scale[2] = (float)env_scale;
+        ev.filter = env_nearest ? PT_ENV_NEAREST : PT_ENV_BILINEAR;
+        for (pt_ctx* cx : ctxs)
+            if (pt_upload_environment(cx, &ev, env_px) != PT_OK) return die("--env", pt_last_error(cx));
+        pth_free_pfm(env_px);
+        env_px = nullptr;
+        std::printf("environment map %s: %d x %d, %s\n", env_path.c_str(), env_w, env_h, env_nearest ? "nearest" : "bilinear");
+    }
 
     // the reference's sphere room, BasicScene.cpp:181-202
     std::vector<pt_sphere> sph;

@@ -8,6 +8,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <memory>
@@ -897,6 +898,36 @@ int pth_write_pfm(const char* path, const float* accum, int W, int H) {
     if (!ok) { set_err(std::string("write failed: ") + path); return -1; }
     return 0;
 }
+
+int pth_read_pfm(const char* path, int* W, int* H, float** data) {
+    if (!path || !W || !H || !data) { set_err("pth_read_pfm: bad argument"); return -1; }
+    *data = nullptr;
+    FILE* f = std::fopen(path, "rb");
+    if (!f) { set_err(std::string("cannot open ") + path); return -1; }
+    // "PF" width height scale, separated by white space, ONE white-space byte, then the rows; scale < 0: little endian
+    char magic[3] = {0, 0, 0};
+    int w = 0, h = 0;
+    float scale = 0.f;
+    bool ok = std::fscanf(f, "%2s %d %d %f", magic, &w, &h, &scale) == 4 && std::strcmp(magic, "PF") == 0 && w > 0 && h > 0 &&
+              scale != 0.f && std::isfinite(scale) && (uint64_t)w * (uint64_t)h <= (1ull << 28);
+    if (ok) { const int ch = std::fgetc(f); ok = ch == '\n' || ch == ' ' || ch == '\t' || ch == '\r'; }
+    float* px = nullptr;
+    if (ok) {
+        const size_t n = (size_t)w * h * 3;
+        px = (float*)std::malloc(n * 4);
+        ok = px && std::fread(px, 4, n, f) == n;   // rows as pth_write_pfm stores them: bottom-up, in the frame buffers' own order
+        if (ok && scale > 0.f) {                   // big endian
+            unsigned char* b = (unsigned char*)px;
+            for (size_t i = 0; i < n; i++) { std::swap(b[4 * i], b[4 * i + 3]); std::swap(b[4 * i + 1], b[4 * i + 2]); }
+        }
+    }
+    std::fclose(f);
+    if (!ok) { std::free(px); set_err(std::string("bad or truncated PFM file (colour \"PF\" expected) ") + path); return -1; }
+    *W = w; *H = h; *data = px;
+    return 0;
+}
+
+void pth_free_pfm(float* data) { std::free(data); }
 
 int pth_checkpoint_save(const char* path, const pth_checkpoint_info* info, const float* accum) {
     if (!path || !info || !accum || info->width <= 0 || info->height <= 0) { set_err("pth_checkpoint_save: bad argument"); return -1; }

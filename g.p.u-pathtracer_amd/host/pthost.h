@@ -104,11 +104,17 @@ void pth_bvh_free(pth_bvh* b);
  *   pth_write_ppm / pth_write_png : the display words (0x00BBGGRR, rgbToUint cudaUtils.h:99-105),
  *                                   written top row first; PNG uses stored (uncompressed) deflate
  *   pth_write_pfm                 : the float accumulator (PFM "PF", little endian, bottom-up)
+ *   pth_read_pfm                  : a colour PFM ("PF") of either endianness (the sign of its scale line; the scale's size is
+ *                                   ignored) into a malloc'ed float[height][width][3], rows in the file's order — exactly what
+ *                                   pth_write_pfm stored, so read(write(a)) == a bit for bit; release with pth_free_pfm.
+ *                                   An environment map for pt_upload_environment, e.g. a frame `pt_app --equirect` wrote
  *   pth_checkpoint_save / _load   : accumulator + the loop state needed to continue a progressive
  *                                   render bit-identically: next frame number and constantPdf */
 int pth_write_ppm(const char* path, const uint32_t* rgba, int width, int height);
 int pth_write_png(const char* path, const uint32_t* rgba, int width, int height);
 int pth_write_pfm(const char* path, const float* accum, int width, int height);
+int pth_read_pfm(const char* path, int* width, int* height, float** data);
+void pth_free_pfm(float* data);
 typedef struct pth_checkpoint_info {
     int32_t width, height;
     uint64_t next_frame;      /* frameNumber of the next launch (BasicScene.cpp:397)  */

@@ -70,3 +70,13 @@ def gather_stripes(frame, layout, dst=0, group=None, staging=None, force=False):
             if r != dst:
                 view[:, r, :].copy_(recv[r])
     return staging
+
+
+def upload_environment(tracers, texels, **kw):
+    """The environment map of PathTracer.upload_environment on every context of a tile split: each rank holds the whole scene, the
+    map included, since any of its pixels' paths may leave the scene in any direction.  texels=None clears it everywhere."""
+    for t in tracers:
+        if texels is None:
+            t.clear_environment()
+        else:
+            t.upload_environment(texels, **kw)

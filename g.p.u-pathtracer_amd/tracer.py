@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import Camera, Counters, DenoiseParams, Material, Params, Sphere, TemporalParams
+from ._abi import Camera, Counters, DenoiseParams, Environment, Material, Params, Sphere, TemporalParams
 
 # pt_denoise defaults (iterations, sigma_color, sigma_normal, sigma_position): chosen by the CPU sweep of DESIGN.md §10 f6;
 # host/pt_app.cpp uses the same values
@@ -209,6 +209,30 @@ class PathTracer:
         hdr: the mean is not clamped to 0..1.  Asynchronous until sync()."""
         self._check(self._lib.pt_render_rays(self._ctx, rays_ptr, int(n), int(first_index), out_ptr, C.byref(params), int(spp),
                                              _abi.RAYS_HDR if hdr else _abi.RAYS_CLAMPED))
+
+    def upload_environment(self, texels, front=(0, 0, -1), right=(1, 0, 0), up=(0, 1, 0), scale=(1, 1, 1), filter=_abi.ENV_BILINEAR):
+        """Light the paths that leave the scene with a latitude-longitude map (pt_upload_environment) instead of bk_color: texels
+        float32 [H][W][3] on the host, in the layout `pt_app --equirect` writes for a camera with this front / right / up (the
+        defaults: the default camera's, i.e. the world frame); scale multiplies the texels per channel; filter ENV_BILINEAR or
+        ENV_NEAREST.  Waits for renders in flight; a render issued afterwards sees the new map.  With a map the stage-split
+        pipeline is not chosen."""
+        a = np.ascontiguousarray(texels, np.float32)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError("upload_environment: a float32 array of shape (H, W, 3) expected")
+        ev = Environment()
+        ev.width, ev.height = a.shape[1], a.shape[0]
+        ev.front[:], ev.right[:], ev.up[:], ev.scale[:] = front, right, up, scale
+        ev.filter = int(filter)
+        self._check(self._lib.pt_upload_environment(self._ctx, C.byref(ev), a.ctypes.data))
+
+    def clear_environment(self):
+        """Back to bk_color (and to the stage-split pipeline): pt_upload_environment with no map."""
+        self._check(self._lib.pt_upload_environment(self._ctx, None, None))
+
+    def eval_environment(self, rays_ptr, n, out_ptr):
+        """What the map sends along the directions of a ray batch (pt_eval_environment): rays float[n][8], words 4-6 read (any
+        length); out float[n][3].  Asynchronous until sync()."""
+        self._check(self._lib.pt_eval_environment(self._ctx, rays_ptr, int(n), out_ptr))
 
     def render_aux(self, cam, params, albedo_ptr, normal_ptr, position_ptr, id_ptr=None):
         """First-hit guide buffers of the pixel-centre rays (pt_render_aux): albedo, normal, position as float[H][W][4], the hit

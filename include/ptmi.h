@@ -123,7 +123,10 @@ enum {
                                 BVH, lanes refilled from the ray queue) and shade (one lane per
                                 live path; survivors compacted with a ballot / prefix count into
                                 the next generation).  Needs a BVH, depth >= 1 and the wide walk
-                                over exact records; anything else runs PT_KERNEL_PERSISTENT.  Same images */
+                                over exact records; anything else runs PT_KERNEL_PERSISTENT.  Same images.
+                                A context with an environment map (pt_upload_environment) is such a case:
+                                this value and PT_KERNEL_AUTO (no trials) run PT_KERNEL_PERSISTENT, and with
+                                PT_FLAG_NEE PT_KERNEL_MEGA_BVH2, until the map is cleared                  */
 };
 
 enum {
@@ -493,7 +496,8 @@ int pt_any_hits(pt_ctx* ctx, const float* rays_dev, size_t n_rays, int cull_back
  * depth == 0 folds black samples, as pt_render does.
  * A ray whose direction has a component that is not finite or is (0, 0, 0), or whose origin is not finite, is never walked or
  * tested against a sphere: its samples are those of a path whose first segment hit nothing — bk_color (under
- * PT_FLAG_MISS_KEEPS_PATH the same value as 0 + 1 * bk_color); at depth 0 black like every other ray.
+ * PT_FLAG_MISS_KEEPS_PATH the same value as 0 + 1 * bk_color), also when the context has an environment map
+ * (pt_upload_environment): there is no direction to look up; at depth 0 black like every other ray.
  * Errors, in this order: NULL ctx PT_ERR_INVALID; neither a tree nor spheres PT_ERR_NO_SCENE; n_rays == 0 or spp == 0 PT_OK,
  * nothing written; a NULL rays_dev, radiance_dev or params PT_ERR_INVALID; a mode other than the two PT_ERR_INVALID;
  * n_rays >= 2^32 PT_ERR_INVALID; then pt_render's own: sample_index == 0, a bad tri_mat, PT_FLAG_NEE without PT_FLAG_COSINE_DIFF
@@ -513,6 +517,56 @@ int pt_any_hits(pt_ctx* ctx, const float* rays_dev, size_t n_rays, int cull_back
 enum { PT_RAYS_CLAMPED = 0, PT_RAYS_HDR = 1 };
 int pt_render_rays(pt_ctx* ctx, const float* rays_dev, size_t n_rays, uint64_t first_index,
                    float* radiance_dev, const pt_params* params, uint32_t spp, int mode);
+
+/* ---- environment map — an EXTENSION -----------------------------------------
+ * pt_upload_environment gives the context a latitude-longitude (equirectangular) radiance map: what a path segment that hits
+ * nothing gathers instead of the one constant bk_color, so that open scenes — a mesh on its own, a probe rendered elsewhere — are
+ * lit by an image.  The layout is the one `pt_app --equirect` writes: with (front, right, up) the frame the map is laid out in,
+ * column x looks at longitude (x - W/2) 2 pi / W from `front` towards `right`, row y at latitude (y - H/2) pi / H towards `up`.
+ *   texels: host float[height][width][3], copied; the device copy is float4[height][width] = (r, g, b, 0) with `scale` folded in
+ *   (texel * scale, one binary32 rounding), so a lookup is one or four 16-byte gathers.
+ * The lookup of a direction d (any length; pt_render_rays' directions need not be unit for it), in binary32 with plain * and +,
+ * the only fused operations those of vdot(u, v) = fmaf(u.z, v.z, fmaf(u.y, v.y, u.x * v.x)), in this order:
+ *   1. a = vdot(d, front), b = vdot(d, right), c = vdot(d, up); one of them not finite, or all three 0: the result is (0, 0, 0).
+ *   2. lon = atan2f(b, a), lat = atan2f(c, sqrtf(a * a + b * b)).
+ *   3. fx = lon * kx + hx, fy = lat * ky + hy with kx = W / 2 pi, ky = H / pi, hx = W / 2, hy = H / 2, each computed in double and
+ *      rounded once.  An integer (fx, fy) is a texel.
+ *   4. PT_ENV_NEAREST: column floorf(fx + 0.5f) wrapped into 0..W-1, row floorf(fy + 0.5f) clamped into 0..H-1.
+ *   5. PT_ENV_BILINEAR: x0 = floorf(fx), wx = fx - x0, columns x0 and x0 + 1 wrapped; y0 = floorf(fy), wy = fy - y0, rows y0 and
+ *      y0 + 1 clamped; per component lerp(p, q, w) = p + w * (q - p), the columns within each row first, then the two rows — so
+ *      a constant map returns its constant exactly.
+ * Where it applies: in pt_render, pt_render_moments and pt_render_rays a segment that hits neither a triangle nor a sphere returns
+ * the lookup of its direction where it returned bk_color, by the same rule of the flags — the bare value, or accu + mask * value
+ * under PT_FLAG_MISS_KEEPS_PATH (the reference's quirk that a miss without that flag is NOT masked holds for a map too).  Every
+ * flag, partitions and PT_FLAG_NEE work; under NEE the map is gathered by bounce rays only, like a sphere the path is inside of —
+ * it is not sampled as a light, so a map with a small sun is noisy.  pt_render_rays' guard keeps writing bk_color for a ray that
+ * is not finite or has no direction (there is nothing to look up).  pt_render_aux, pt_denoise and pt_temporal are untouched: a
+ * pixel that sees the map is still a miss.  With a map on the context the stage-split pipeline is not chosen (see
+ * PT_KERNEL_WAVEFRONT); clearing the map brings it back.  A map change is a scene change for PT_KERNEL_AUTO's table.
+ * env == NULL clears the map: every call then behaves exactly as before, bk_color included.
+ * The call waits for the context's streams, the side streams of PT_OPT_OVERLAP included, before it replaces or frees texels: a
+ * render in flight reads the old map to its end, a render issued after the call reads the new one without the caller syncing.
+ * The memory belongs to the context: freed by pt_destroy or a clear, not counted in pt_scene_info.
+ * Errors, in this order: NULL ctx PT_ERR_INVALID; then with env != NULL, each PT_ERR_INVALID: a NULL texels; a dimension out of
+ * range; an unknown filter; a basis vector or scale that is not finite, a zero basis vector, a negative scale (these four before
+ * texels is dereferenced); a texel that is not finite or is negative after scaling.  The old map stays in place on any error.
+ * Left out: sampling the map as a light under PT_FLAG_NEE, the stage-split pipeline for scenes with a map, mip levels, cube or
+ * octahedral layouts, the map in pt_render_aux's albedo. */
+enum { PT_ENV_NEAREST = 0, PT_ENV_BILINEAR = 1 };
+typedef struct pt_environment {
+    int32_t width, height;               /* texels: 1..16384 each, width * height <= 2^26 */
+    float front[3], right[3], up[3];     /* the frame the map is laid out in (pt_app --equirect's cam.front / right / up) */
+    float scale[3];                      /* rgb factor, folded into the texels at upload: texel * scale, one rounding */
+    int32_t filter;                      /* PT_ENV_* */
+    int32_t _pad;
+} pt_environment;                        /* 64 bytes */
+int pt_upload_environment(pt_ctx* ctx, const pt_environment* env, const float* texels /* host float[h][w][3] */);
+/* The lookup above for a ray batch — "what does the sky send from here": rays_dev float[n][8], pt_trace_rays' stride, words 4-6
+ * (the direction) read, the rest ignored; radiance_dev float[n][3], must not overlap rays_dev (not checked).  One thread per ray.
+ * Errors, in this order: NULL ctx PT_ERR_INVALID; no map PT_ERR_NO_SCENE; n_rays == 0 PT_OK, nothing written; a NULL pointer
+ * PT_ERR_INVALID; n_rays >= 2^32 PT_ERR_INVALID.  Asynchronous on the context's stream; with PT_OPT_TIMING=1, pt_last_kernel_ms
+ * covers it. */
+int pt_eval_environment(pt_ctx* ctx, const float* rays_dev, size_t n_rays, float* radiance_dev /* float[n][3] */);
 
 /* ---- guide buffers and denoiser — an EXTENSION --------------------------
  * pt_render_aux: the first hit of ONE ray through every pixel centre (the camera ray of pt_render with zero jitter), for a
