@@ -1,12 +1,13 @@
 // pt_ctx.h — the context behind the C ABI (include/ptmi.h) and the host-side helpers shared by the
 // translation units of libptmi.so: ptmi.hip (API), pt_tree.hip (trees: makers, adoption, cost), pt_build.hip (device BVH
-// builder), pt_k_*.hip (kernel families + their launchers; pt_k_rays.hip also holds its API function), pt_env.hip (environment map).  Host code only.
+// builder), pt_k_*.hip (kernel families + their launchers, no API function), pt_env.hip (environment map).  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <climits>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -222,6 +223,64 @@ hipError_t allow_lds(K kernel, size_t bytes) {
     return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
+// ---- the rules every entry point shares, each written here once ----------------
+// The wide walk pushes up to three entries per level: whether a stack of `cap` entries holds it for this tree.
+inline bool wide_walk_fits(const TreeState& t, int cap) { return t.has_bvh && 3 * t.wide_depth + 2 <= (uint32_t)cap; }
+// The walk a path call runs (LaunchCfg::walk) under PT_OPT_WALK, or PT_ERR_UNSUPPORTED (< 0) in `who`'s name: Woop records are only
+// understood by the wide walk, a tree too deep for it takes the unified binary walk.  postponed: the caller has walk 4, else it runs as 2.
+inline int choose_walk(pt_ctx* c, const char* who, bool postponed) {
+    const bool wide_ok = wide_walk_fits(c->tree, PT_STACK_CAP);
+    if (c->tree.has_bvh && c->tree.records_woop)
+        return wide_ok ? 3 : fail(c, PT_ERR_UNSUPPORTED, std::string(who) + ": Woop records need the wide walk and this tree is too deep for it");
+    const int walk = c->opt_walk == 4 && !postponed ? 2 : c->opt_walk;
+    return walk >= 2 && !wide_ok ? 1 : walk;
+}
+// The scene as a kernel sees it: one item buffer for nodes and records, the wide tree's root and, where ksph (KParams::ksph) is
+// given, the spheres: a ray-batch query sees none.  Zeroes the rest; the stack and LDS layout is the caller's.
+inline void scene_view(const pt_ctx* c, KScene& sc, pt_sphere_d* ksph = nullptr) {
+    sc = KScene();
+    sc.nodes = sc.tris = c->tree.d_nodes;
+    sc.has_bvh = c->tree.has_bvh ? 1 : 0;
+    sc.wide_root = (int)c->tree.wide_root;
+    if (!ksph) return;
+    sc.spheres = c->d_spheres; sc.n_spheres = c->n_spheres;
+    std::memcpy(ksph, c->h_spheres, sizeof c->h_spheres);
+}
+// The binary walk with one thread per ray (pt_trace_rays, the deep-tree queries, pt_render_aux): all PT_STACK_CAP entries and the top
+// of the tree in LDS.  Returns the LDS bytes of a block of PT_BLOCK_RAYS.
+inline size_t binary_ray_layout(const pt_ctx* c, KScene& sc) {
+    sc.stack_n = PT_STACK_CAP; sc.top_base = 0;
+    sc.n_top = (int)std::min<uint32_t>((uint32_t)c->opt_top, c->tree.n_top_layout);
+    return lds_fit(sc.n_top, sc.stack_n, PT_BLOCK_RAYS);
+}
+// The work counters of a persistent launch: PT_SHARDS of them, a cache line apart, zero when the launch starts.
+constexpr size_t QUEUE_BYTES = PT_SHARDS * PT_SHARD_STRIDE * sizeof(unsigned int);
+inline hipError_t queue_alloc(unsigned int** q) { return hipMalloc((void**)q, QUEUE_BYTES); }
+inline hipError_t queue_reset(unsigned int* q, hipStream_t st) { return hipMemsetAsync(q, 0, QUEUE_BYTES, st); }
+// queue granularity: 64-slot chunks when the launch has plenty of them per resident wave, smaller ones for small launches (an
+// eighth of a 1080p frame per GPU is ~4 000 tiles for ~5 000 waves)
+inline int queue_chunk(const pt_ctx* c, uint64_t slots) {
+    const uint64_t waves = (uint64_t)c->n_cu * 20;
+    return slots / 64 >= 4 * waves ? 64 : (slots / 32 >= 4 * waves ? 32 : 16);
+}
+inline void queue_params(const pt_ctx* c, unsigned int* queue, KParams& P) {
+    P.queue = queue; P.batch = c->opt_batch;
+    // refill <= batch, or a wave can spin: the walk returns at once because `batch` lanes wait,
+    // none of them has anything to shade and the idle ones are too few to trigger a refill
+    P.refill = std::min(c->opt_refill, c->opt_batch);
+    P.vote_node = c->opt_vote_node; P.vote_rec = c->opt_vote_rec;
+}
+// the sphere table of a persistent kernel's block (PT_OPT_SPHERE_LDS) behind what `lds` holds: its first word; `lds` grows by it
+inline int lds_sphere_table(size_t& lds) { lds += 15 * PT_KSPHERES * 4; return (int)(lds / 4) - 15 * PT_KSPHERES; }
+// PT_OPT_TIMING: the span pt_last_kernel_ms reads, around a call's launches on the caller's stream (HIP_TRY(c, span_begin(c)) ...);
+// the context counts as timed only once the end event is recorded
+inline hipError_t span_begin(pt_ctx* c) { return c->opt_timing ? hipEventRecord(c->ev0, c->stream) : hipSuccess; }
+inline hipError_t span_end(pt_ctx* c) {
+    const hipError_t e = c->opt_timing ? hipEventRecord(c->ev1, c->stream) : hipSuccess;
+    if (c->opt_timing && e == hipSuccess) c->timed = true;
+    return e;
+}
+
 // ---- compile-time dispatch: generic lambdas take template arguments as std::integral_constant values; only the combinations a
 // lambda is CALLED with are instantiated
 template <int V> constexpr std::integral_constant<int, V> int_c{};
@@ -288,13 +347,17 @@ struct QueryCall {
     uint8_t* hit;
 };
 hipError_t launch_query(pt_ctx* c, const QueryCall& q);
-// what pt_render and pt_render_rays (pt_k_rays.hip) share of a path call's set-up (ptmi.hip):
-// the kernel arguments that the context and pt_params give to ANY path kernel — scene, materials, estimator, frame numbers; zeroes the rest
-void fill_path_params(const pt_ctx* c, const pt_params* p, uint32_t spp, KParams& P);
-// PT_FLAG_NEE over emissive triangles: brings the light list up to date on the caller's stream
-int refresh_tri_lights(pt_ctx* c, const pt_params* p);
-// the call's sample buffer into P.samples, the side slot's own or (sd = nullptr) the context's, grown to `need` bytes
-int samples_reserve(pt_ctx* c, pt_ctx::Side* sd, size_t need, KParams& P);
+// the path loop over a caller's rays (pt_k_rays.hip), one launch of pt_render_rays: the persistent grid over the (sample, ray) slots
+// that P and the batch describe, on the context's stream, and the fold of a launch's sample buffer into the running means
+struct RaysCall {
+    const float* rays;      // float[n][8] = (o, ignored, d, ignored)
+    float* out;             // float[n][3]
+    uint64_t first_index;   // RNG key of ray 0
+    size_t n;               // 0 < n < 2^32
+    int hdr;                // mode == PT_RAYS_HDR
+};
+hipError_t launch_render_rays(const pt_ctx* c, int walk, bool nee, size_t lds, int work_blocks, const KParams& P, const RaysCall& r);
+hipError_t launch_fold_rays(const pt_ctx* c, const KParams& P, const RaysCall& r);
 // PT_OPT_TIMING: marks the end of a stage of the running call on the context's stream (no-op when timing is off)
 int stage_mark(pt_ctx* c, int kind_of_work_since_last_mark);
 // device BVH builder (pt_build.hip), a maker: the tree over the mesh into `out` (its build_ms set), the context's own tree untouched.

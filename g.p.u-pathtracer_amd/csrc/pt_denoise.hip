@@ -327,17 +327,8 @@ extern "C" int pt_render_aux(pt_ctx* c, const pt_camera* cam, const pt_params* p
     HIP_TRY(c, hipSetDevice(c->device));
     KParams P;
     std::memset(&P, 0, sizeof P);
-    P.sc.nodes = c->tree.d_nodes;
-    P.sc.tris = c->tree.d_nodes;
-    P.sc.spheres = c->d_spheres;
-    P.sc.n_spheres = c->n_spheres;
-    std::memcpy(P.ksph, c->h_spheres, sizeof P.ksph);
-    P.sc.has_bvh = 1;
-    P.sc.stack_n = PT_STACK_CAP;
-    P.sc.top_base = 0;
-    P.sc.wide_root = (int)c->tree.wide_root;
-    P.sc.n_top = (int)std::min<uint32_t>((uint32_t)c->opt_top, c->tree.n_top_layout);
-    const size_t lds = lds_fit(P.sc.n_top, P.sc.stack_n, PT_BLOCK_RAYS);
+    scene_view(c, P.sc, P.ksph);
+    const size_t lds = binary_ray_layout(c, P.sc);
     P.cam = *cam;
     P.W = p->width; P.H = p->height;
     P.cull = p->cull_backfaces;
@@ -350,11 +341,11 @@ extern "C" int pt_render_aux(pt_ctx* c, const pt_camera* cam, const pt_params* p
     A.position = (float4*)position_dev;
     A.id = id_dev;
     HIP_TRY(c, allow_lds(k_render_aux, lds));
-    if (c->opt_timing) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    HIP_TRY(c, span_begin(c));
     const dim3 grid((unsigned)((p->width + 15) / 16), (unsigned)((p->height + 15) / 16));
     hipLaunchKernelGGL(k_render_aux, grid, dim3(PT_BLOCK_RAYS), lds, c->stream, P, A);
     HIP_TRY(c, hipGetLastError());
-    if (c->opt_timing) { HIP_TRY(c, hipEventRecord(c->ev1, c->stream)); c->timed = true; }
+    HIP_TRY(c, span_end(c));
     return PT_OK;
 }
 
@@ -397,7 +388,7 @@ extern "C" int pt_denoise(pt_ctx* c, const pt_denoise_params* dp, const float* c
         return (float)std::min(1.4426950408889634 * scale / (sigma * sigma), 1e30);
     };
     hipStream_t st = c->stream;
-    if (c->opt_timing) HIP_TRY(c, hipEventRecord(c->ev0, st));
+    HIP_TRY(c, span_begin(c));
     if (L == 0) {
         hipLaunchKernelGGL(k_dn_copy, grid, dim3(PTD_BLOCK), 0, st, A);
     } else {
@@ -415,7 +406,7 @@ extern "C" int pt_denoise(pt_ctx* c, const pt_denoise_params* dp, const float* c
         }
     }
     HIP_TRY(c, hipGetLastError());
-    if (c->opt_timing) { HIP_TRY(c, hipEventRecord(c->ev1, st)); c->timed = true; }
+    HIP_TRY(c, span_end(c));
     return PT_OK;
 }
 
@@ -471,12 +462,12 @@ extern "C" int pt_temporal(pt_ctx* c, const pt_temporal_params* tp, const pt_cam
     }
     const dim3 grid((unsigned)((tp->width + PTD_TILE - 1) / PTD_TILE), (unsigned)((tp->height + PTD_TILE - 1) / PTD_TILE));
     hipStream_t st = c->stream;
-    if (c->opt_timing) HIP_TRY(c, hipEventRecord(c->ev0, st));
+    HIP_TRY(c, span_begin(c));
     if (!history) hipLaunchKernelGGL(k_tm_first, grid, dim3(PTD_BLOCK), 0, st, A);
     else if (A.prev_id) hipLaunchKernelGGL(k_temporal<true>, grid, dim3(PTD_BLOCK), 0, st, A);
     else hipLaunchKernelGGL(k_temporal<false>, grid, dim3(PTD_BLOCK), 0, st, A);
     HIP_TRY(c, hipGetLastError());
-    if (c->opt_timing) { HIP_TRY(c, hipEventRecord(c->ev1, st)); c->timed = true; }
+    HIP_TRY(c, span_end(c));
     return PT_OK;
 }
 

@@ -96,10 +96,10 @@ extern "C" int pt_eval_environment(pt_ctx* c, const float* rays_dev, size_t n_ra
     if (!rays_dev || !radiance_dev) return fail(c, PT_ERR_INVALID, "pt_eval_environment: null argument");
     if (n_rays >= (1ull << 32)) return fail(c, PT_ERR_INVALID, "pt_eval_environment: more than 2^32 - 1 rays in one call");
     HIP_TRY(c, hipSetDevice(c->device));
-    if (c->opt_timing) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    HIP_TRY(c, span_begin(c));
     hipLaunchKernelGGL(k_eval_environment, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, c->stream, c->env, (const float4*)rays_dev,
                        (uint32_t)n_rays, radiance_dev);
     HIP_TRY(c, hipGetLastError());
-    if (c->opt_timing) { HIP_TRY(c, hipEventRecord(c->ev1, c->stream)); c->timed = true; }
+    HIP_TRY(c, span_end(c));
     return PT_OK;
 }

@@ -9,7 +9,7 @@
 // the boxes beyond it are never opened.  A ray whose t_max is not greater than 0 (0, negative, NaN) writes its miss where it is
 // drawn and never becomes live.
 //
-// A tree too deep for the wide walk's stack (3 levels' pushes per level: pt_render's rule) takes k_query_rays_bvh2: the binary walk
+// A tree too deep for the wide walk's stack (wide_walk_fits, pt_ctx.h: the rule of every call) takes k_query_rays_bvh2: the binary walk
 // of pt_trace_rays, unbounded, and the bound applied to its answer — the nearest hit inside (0, t_max) is the nearest hit when it
 // lies inside and nothing otherwise, so both kernels give the same results.
 #include <cstring>
@@ -180,12 +180,9 @@ __global__ void __launch_bounds__(PT_BLOCK_RAYS) k_query_rays_bvh2(const KQuery 
 namespace ptmi {
 
 hipError_t launch_query(pt_ctx* c, const QueryCall& q) {
-    const TreeState& t = c->tree;
     KQuery Q;
     std::memset(&Q, 0, sizeof Q);
-    Q.sc.nodes = Q.sc.tris = t.d_nodes;
-    Q.sc.has_bvh = 1;
-    Q.sc.wide_root = (int)t.wide_root;
+    scene_view(c, Q.sc);
     Q.rays = (const float4*)q.rays;
     Q.t_out = q.t; Q.tri_out = q.tri; Q.n_out = q.normal; Q.hit_out = q.hit;
     Q.queue = c->d_queue;   // the context's counters: every use is on the caller's stream, behind a reset of its own
@@ -194,16 +191,14 @@ hipError_t launch_query(pt_ctx* c, const QueryCall& q) {
     Q.cull = q.cull;
     Q.batch = c->opt_wave_batch;
     hipStream_t st = c->stream;
-    if (3 * t.wide_depth + 2 > (uint32_t)PT_STACK_CAP) {   // too deep for the wide walk (pt_render's rule): pt_trace_rays' launch
-        Q.sc.stack_n = PT_STACK_CAP;
-        Q.sc.n_top = (int)std::min<uint32_t>((uint32_t)c->opt_top, t.n_top_layout);
-        const size_t lds = lds_fit(Q.sc.n_top, Q.sc.stack_n, PT_BLOCK_RAYS);
+    if (!wide_walk_fits(c->tree, PT_STACK_CAP)) {   // pt_trace_rays' launch
+        const size_t lds = binary_ray_layout(c, Q.sc);
         const hipError_t e = allow_lds(k_query_rays_bvh2, lds);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_query_rays_bvh2, dim3((unsigned)((q.n + PT_BLOCK_RAYS - 1) / PT_BLOCK_RAYS)), dim3(PT_BLOCK_RAYS), lds, st, Q);
         return hipGetLastError();
     }
-    const hipError_t e = hipMemsetAsync(Q.queue, 0, PT_SHARDS * PT_SHARD_STRIDE * sizeof(unsigned int), st);
+    const hipError_t e = queue_reset(Q.queue, st);
     if (e != hipSuccess) return e;
     // the extend stage's two budgets: (8 waves per SIMD, 16 stack entries in LDS), or (6, 24) under PT_OPT_LDS_STACK 24
     return with_bool(q.hit != nullptr, [&](auto any) {

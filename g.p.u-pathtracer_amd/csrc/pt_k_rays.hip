@@ -1,5 +1,5 @@
-// pt_k_rays.hip — pt_render_rays: the path loop over a caller's rays (other cameras, probes, baking), its fold and its launcher.
-// One translation unit of libptmi.so (pt_ctx.h).  DESIGN.md §10 f10.
+// pt_k_rays.hip — pt_render_rays: the path loop over a caller's rays (other cameras, probes, baking), its fold and their launchers.
+// One translation unit of libptmi.so (pt_ctx.h); the API function is ptmi.hip's.  DESIGN.md §10 f10.
 //
 // k_render_rays is k_trace_persist_bvh2 (pt_k_persist.hip) with another path start: persistent waves draw chunks of (sample, ray)
 // slots from the context's sharded queue, idle lanes take the next slots by a ballot + prefix count, lanes with a segment in flight
@@ -11,8 +11,6 @@
 // the loop of pt_get_sample (pt_kernels.h) laid out over the phases, which the frame kernel leaves to the other two families.
 // The ray buffer, the output, n and first_index travel as a second kernel argument: KParams stays the first one, at offset 0, for
 // PT_KARGS and pt_closest_sphere, and keeps its layout.
-#include <cstring>
-
 #include "pt_ctx.h"
 
 struct KRays {
@@ -224,10 +222,13 @@ __global__ void __launch_bounds__(256) k_fold_rays(const KParams P, const KRays 
 
 namespace ptmi {
 
+static KRays rays_args(const RaysCall& r) { return KRays{(const float4*)r.rays, r.out, r.first_index, (uint32_t)r.n, r.hdr}; }
+
 // Instantiated: the wide walk (2; 3 = Woop records) and the unified binary walk (1: trees too deep for the wide one, PT_OPT_WALK 0 / 1),
 // each at 6 waves per SIMD without and at 4 with the shadow-ray state, 16 stack entries per lane in LDS; each of those without and
 // with the environment-map lookup (ENV).
-static hipError_t launch_render_rays(const pt_ctx* c, int walk, bool nee, size_t lds, int work_blocks, const KParams& P, const KRays& R) {
+hipError_t launch_render_rays(const pt_ctx* c, int walk, bool nee, size_t lds, int work_blocks, const KParams& P, const RaysCall& r) {
+    const KRays R = rays_args(r);
     return with_bool(nee, [&](auto n) {
         return with_int<3, 2, 1>(walk, [&](auto alg) {
             constexpr int OCC = n() ? 4 : 6;
@@ -238,83 +239,12 @@ static hipError_t launch_render_rays(const pt_ctx* c, int walk, bool nee, size_t
     });
 }
 
-// slots of one launch: what keeps its sample buffer below 768 MiB; more samples than that go out as several launches, which the
-// fold's order makes the same thing
-static constexpr uint64_t RAYS_MAX_SLOTS = 1ull << 26;
+hipError_t launch_fold_rays(const pt_ctx* c, const KParams& P, const RaysCall& r) {
+    const KRays R = rays_args(r);
+    with_bool(r.hdr != 0, [&](auto hdr) {
+        hipLaunchKernelGGL(k_fold_rays<hdr()>, dim3((unsigned)((r.n + 255) / 256)), dim3(256), 0, c->stream, P, R);
+    });
+    return hipGetLastError();
+}
 
 }  // namespace ptmi
-
-extern "C" int pt_render_rays(pt_ctx* c, const float* rays_dev, size_t n_rays, uint64_t first_index, float* radiance_dev,
-                              const pt_params* p, uint32_t spp, int mode) {
-    using namespace ptmi;
-    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
-    if (!c->tree.has_bvh && c->n_spheres == 0) return fail(c, PT_ERR_NO_SCENE, "pt_render_rays: no scene uploaded");
-    if (n_rays == 0 || spp == 0) return PT_OK;
-    if (!rays_dev || !radiance_dev || !p) return fail(c, PT_ERR_INVALID, "pt_render_rays: null argument");
-    if (mode != PT_RAYS_CLAMPED && mode != PT_RAYS_HDR) return fail(c, PT_ERR_INVALID, "pt_render_rays: mode must be PT_RAYS_CLAMPED or PT_RAYS_HDR");
-    if (n_rays >= (1ull << 32)) return fail(c, PT_ERR_INVALID, "pt_render_rays: more than 2^32 - 1 rays in one call");
-    // ... then pt_render's own conditions on the fields both read
-    if (p->sample_index == 0) return fail(c, PT_ERR_INVALID, "pt_render_rays: sample_index starts at 1");
-    if (p->tri_mat < PT_MAT_DIFF || p->tri_mat > PT_MAT_REFR) return fail(c, PT_ERR_INVALID, "pt_render_rays: bad triangle material");
-    if ((p->flags & PT_FLAG_NEE) && !(p->flags & PT_FLAG_COSINE_DIFF)) return fail(c, PT_ERR_INVALID, "pt_render_rays: PT_FLAG_NEE needs PT_FLAG_COSINE_DIFF");
-    HIP_TRY(c, hipSetDevice(c->device));
-    int rc = refresh_tri_lights(c, p);
-    if (rc != PT_OK) return rc;
-
-    // the walk, by the persistent kernel's rules (plan_call): Woop records and trees too deep for the wide walk
-    const TreeState& t = c->tree;
-    const bool wide_ok = t.has_bvh && 3 * t.wide_depth + 2 <= (uint32_t)PT_STACK_CAP;
-    int walk = c->opt_walk >= 2 ? 2 : 1;
-    if (t.has_bvh && t.records_woop) {
-        if (!wide_ok) return fail(c, PT_ERR_UNSUPPORTED, "pt_render_rays: Woop records need the wide walk and this tree is too deep for it");
-        walk = 3;
-    } else if (walk == 2 && !wide_ok) {
-        walk = 1;
-    }
-
-    KParams P;
-    fill_path_params(c, p, spp, P);
-    P.sc.stack_n = 16;
-    P.sc.top_base = walk >= 2 ? P.sc.wide_root : 0;
-    size_t lds = (size_t)16 * PT_BLOCK * 4;
-    P.sph_tab = -1;
-    if (c->opt_sph_lds) {   // sphere table behind the stacks
-        P.sph_tab = (int)(lds / 4);
-        lds += 15 * PT_KSPHERES * 4;
-    }
-    P.queue = c->d_queue;   // the context's counters: every use is on the caller's stream, behind a reset of its own
-    P.batch = c->opt_batch;
-    P.refill = c->opt_refill < c->opt_batch ? c->opt_refill : c->opt_batch;
-    KRays R;
-    std::memset(&R, 0, sizeof R);
-    R.rays = (const float4*)rays_dev;
-    R.out = radiance_dev;
-    R.first_index = first_index;
-    R.n = (uint32_t)n_rays;
-    R.hdr = mode == PT_RAYS_HDR;
-
-    const uint32_t per_launch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(spp, RAYS_MAX_SLOTS / n_rays));
-    if (per_launch > 1 && (rc = samples_reserve(c, nullptr, (size_t)per_launch * n_rays * 3 * sizeof(float), P)) != PT_OK) return rc;
-    P.smp_ss = n_rays;
-    P.smp_ps = 1u;
-    if (c->opt_timing) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-    for (uint32_t s0 = 0; s0 < spp; s0 += per_launch) {
-        P.spp = std::min(per_launch, spp - s0);
-        P.frame = p->frame + s0;
-        P.sample_index = p->sample_index + s0;
-        const uint64_t slots = (uint64_t)n_rays * (per_launch > 1 ? P.spp : 1u);
-        const uint64_t waves = (uint64_t)c->n_cu * 20;   // queue granularity as plan_call: smaller chunks for small launches
-        P.chunk = slots / 64 >= 4 * waves ? 64 : (slots / 32 >= 4 * waves ? 32 : 16);
-        const int work_blocks = (int)std::min<uint64_t>((slots + (uint64_t)P.chunk * 4 - 1) / ((uint64_t)P.chunk * 4), (uint64_t)INT_MAX);
-        HIP_TRY(c, hipMemsetAsync(P.queue, 0, PT_SHARDS * PT_SHARD_STRIDE * sizeof(unsigned int), c->stream));
-        HIP_TRY(c, launch_render_rays(c, walk, (p->flags & PT_FLAG_NEE) != 0, lds, work_blocks, P, R));
-        if (per_launch > 1) {
-            with_bool(R.hdr != 0, [&](auto hdr) {
-                hipLaunchKernelGGL(k_fold_rays<hdr()>, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, c->stream, P, R);
-            });
-            HIP_TRY(c, hipGetLastError());
-        }
-    }
-    if (c->opt_timing) { HIP_TRY(c, hipEventRecord(c->ev1, c->stream)); c->timed = true; }
-    return PT_OK;
-}

@@ -726,7 +726,7 @@ struct WavePlan {
 static WavePlan wave_plan(const pt_ctx* c, const KParams& P, const LaunchCfg& L, bool nee) {
     WavePlan p;
     p.count = L.count; p.nee = nee; p.deep_stack = L.lstk == 24;
-    p.packet = c->opt_first_walk == 1 && 3 * c->tree.wide_depth + 2 <= (uint32_t)c->opt_packet_stack;
+    p.packet = c->opt_first_walk == 1 && wide_walk_fits(c->tree, c->opt_packet_stack);
     const bool fuse = c->opt_fuse_stages != 0 && !nee && !L.count, tri_dark = P.tri_emi[0] == 0.f && P.tri_emi[1] == 0.f && P.tri_emi[2] == 0.f;
     p.fuse_first = fuse && p.packet;
     // ... and the call keeps no luminance moments (pt_render_moments): those are the separate fold launch's job

@@ -369,7 +369,7 @@ extern "C" int pt_refit_bvh(pt_ctx* c, const float* tri_verts_dev, size_t n_tris
     A.first_use = R.first_use;
     A.n_dropped = n_dropped_dev;
     hipStream_t st = c->stream;
-    if (c->opt_timing) HIP_TRY(c, hipEventRecord(c->ev0, st));
+    HIP_TRY(c, span_begin(c));
     if (n_dropped_dev) HIP_TRY(c, hipMemsetAsync(n_dropped_dev, 0, sizeof(uint32_t), st));
     hipLaunchKernelGGL(k_refit_records, dim3((A.n_rec + PTR_BLOCK - 1) / PTR_BLOCK), dim3(PTR_BLOCK), 0, st, A);
     for (size_t ht = 0; ht + 1 < R.bin_off.size(); ht++) {
@@ -379,7 +379,7 @@ extern "C" int pt_refit_bvh(pt_ctx* c, const float* tri_verts_dev, size_t n_tris
                            R.wide_list + R.wide_off[ht], nw);
     }
     HIP_TRY(c, hipGetLastError());
-    if (c->opt_timing) { HIP_TRY(c, hipEventRecord(c->ev1, st)); c->timed = true; }
+    HIP_TRY(c, span_end(c));
     // a path kernel on a side stream (PT_OPT_OVERLAP) waits for this before it reads the tree; the light list is collected again
     if (!c->geom_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->geom_ev, hipEventDisableTiming));
     HIP_TRY(c, hipEventRecord(c->geom_ev, st));

@@ -137,7 +137,7 @@ int pt_create(int device, pt_ctx** out) {
     c->stream = c->own_stream;
     if ((e = hipMalloc(&c->d_counters, PT_CNT_N * sizeof(unsigned long long))) != hipSuccess) { pt_destroy(c); return hip_fail(nullptr, e, "hipMalloc"); }
     if ((e = hipMemset(c->d_counters, 0, PT_CNT_N * sizeof(unsigned long long))) != hipSuccess) { pt_destroy(c); return hip_fail(nullptr, e, "hipMemset"); }
-    if ((e = hipMalloc(&c->d_queue, PT_SHARDS * PT_SHARD_STRIDE * sizeof(unsigned int))) != hipSuccess) { pt_destroy(c); return hip_fail(nullptr, e, "hipMalloc"); }
+    if ((e = queue_alloc(&c->d_queue)) != hipSuccess) { pt_destroy(c); return hip_fail(nullptr, e, "hipMalloc"); }
     hipDeviceProp_t prop;
     if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) { pt_destroy(c); return hip_fail(nullptr, e, "hipGetDeviceProperties"); }
     c->n_cu = prop.multiProcessorCount;
@@ -364,7 +364,7 @@ static bool samples_tri_lights(const pt_ctx* c, const pt_params* p) {
 }
 
 // the scene, its geometry (pt_refit_bvh) or the materials changed: copies the lights' vertices out of the records again
-extern "C++" int refresh_tri_lights(pt_ctx* c, const pt_params* p) {   // (pt_ctx.h; this namespace block sits inside extern "C")
+static int refresh_tri_lights(pt_ctx* c, const pt_params* p) {
     if (!samples_tri_lights(c, p)) return PT_OK;
     if (c->tree.records_woop) return fail(c, PT_ERR_UNSUPPORTED, "pt_render: PT_FLAG_NEE over emissive triangles needs the exact (Moller-Trumbore) records");
     const uint64_t key = (c->scene_gen << 32) ^ c->mat_gen;
@@ -383,16 +383,10 @@ extern "C++" int refresh_tri_lights(pt_ctx* c, const pt_params* p) {   // (pt_ct
     return PT_OK;
 }
 
-// the kernel arguments that the context and pt_params give to any path kernel, a frame's or a ray batch's (pt_ctx.h)
-extern "C++" void fill_path_params(const pt_ctx* c, const pt_params* p, uint32_t spp, KParams& P) {
+// the kernel arguments that the context and pt_params give to any path kernel, a frame's or a ray batch's; zeroes the rest
+static void fill_path_params(const pt_ctx* c, const pt_params* p, uint32_t spp, KParams& P) {
     std::memset(&P, 0, sizeof P);
-    P.sc.nodes = c->tree.d_nodes;
-    P.sc.tris = c->tree.d_nodes;   // one item buffer
-    P.sc.spheres = c->d_spheres;
-    P.sc.n_spheres = c->n_spheres;
-    std::memcpy(P.ksph, c->h_spheres, sizeof P.ksph);
-    P.sc.has_bvh = c->tree.has_bvh ? 1 : 0;
-    P.sc.wide_root = (int)c->tree.wide_root;
+    scene_view(c, P.sc, P.ksph);
     P.counters = c->d_counters;
     P.W = p->width; P.H = p->height;
     P.depth = p->depth;
@@ -492,15 +486,7 @@ static int plan_call(pt_ctx* c, const pt_params* p, const KParams& P, uint32_t s
     const TreeState& t = c->tree;
     LaunchCfg& L = plan.L;
     const bool nee = (p->flags & PT_FLAG_NEE) != 0;
-    // the walk: the wide walk pushes up to three entries per level
-    L.walk = c->opt_walk;
-    const bool wide_ok = t.has_bvh && 3 * t.wide_depth + 2 <= (uint32_t)PT_STACK_CAP;
-    if (t.has_bvh && t.records_woop) {
-        if (!wide_ok) return fail(c, PT_ERR_UNSUPPORTED, "pt_render: Woop records need the wide walk and this tree is too deep for it");
-        L.walk = 3;  // Woop records are only understood by the wide walk
-    } else if ((L.walk == 2 || L.walk == 4) && !wide_ok) {
-        L.walk = 1;
-    }
+    if ((L.walk = choose_walk(c, "pt_render", true)) < 0) return L.walk;
     // the kernel family, every rule once and in this order: the option; PT_KERNEL_AUTO's table; PT_FLAG_NEE; what a family cannot run.
     // The stage-split pipeline needs a BVH, at least one bounce, the wide walk over exact records and a context without an
     // environment map (its last-segment any-hit launch shades misses without a ray in hand).
@@ -547,15 +533,9 @@ static int plan_call(pt_ctx* c, const pt_params* p, const KParams& P, uint32_t s
     plan.n_top = t.has_bvh ? (int)std::min<uint32_t>((uint32_t)c->opt_top, L.walk >= 2 ? t.wide_top_layout : t.n_top_layout) : 0;
     if (L.walk >= 1) plan.n_top = 0;  // only the while-while walk reads the LDS mirror
     L.lds = lds_fit(plan.n_top, L.lstk, PT_BLOCK);
-    plan.sph_tab = -1;
-    if (persistent && c->opt_sph_lds) {   // sphere table behind the stacks (and the LDS mirror)
-        plan.sph_tab = (int)(L.lds / 4);
-        L.lds += 15 * PT_KSPHERES * 4;
-    }
-    // queue granularity: 64-slot chunks when the launch has plenty of them per resident wave, smaller
-    // ones for small launches (an eighth of a 1080p frame per GPU is ~4 000 tiles for ~5 000 waves)
-    const long slots = (long)plan.work_tiles * 64, waves = (long)c->n_cu * 20;
-    plan.chunk = slots / 64 >= 4 * waves ? 64 : (slots / 32 >= 4 * waves ? 32 : 16);
+    plan.sph_tab = persistent && c->opt_sph_lds ? lds_sphere_table(L.lds) : -1;   // behind the stacks (and the LDS mirror)
+    const long slots = (long)plan.work_tiles * 64;
+    plan.chunk = queue_chunk(c, (uint64_t)slots);
     const int waves_per_block = PT_BLOCK / 64;
     L.count = c->opt_counters != 0;
     L.occ = c->opt_occ;
@@ -581,12 +561,12 @@ static int side_acquire(pt_ctx* c, pt_ctx::Side*& sd) {
     HIP_TRY(c, hipStreamCreateWithPriority(&sd->stream, hipStreamNonBlocking, prio_hi));
     HIP_TRY(c, hipEventCreateWithFlags(&sd->traced, hipEventDisableTiming));
     HIP_TRY(c, hipEventCreateWithFlags(&sd->folded, hipEventDisableTiming));
-    HIP_TRY(c, hipMalloc((void**)&sd->queue, PT_SHARDS * PT_SHARD_STRIDE * sizeof(unsigned int)));
+    HIP_TRY(c, queue_alloc(&sd->queue));
     return PT_OK;
 }
 
 // the sample buffer of the call, the side slot's own or the context's, grown to `need` bytes
-extern "C++" int samples_reserve(pt_ctx* c, pt_ctx::Side* sd, size_t need, KParams& P) {
+static int samples_reserve(pt_ctx* c, pt_ctx::Side* sd, size_t need, KParams& P) {
     float*& buf = sd ? sd->samples : c->d_samples;
     size_t& have = sd ? sd->samples_bytes : c->samples_bytes;
     if (need > have) {
@@ -628,14 +608,7 @@ static void apply_plan(const pt_ctx* c, const CallPlan& plan, const pt_ctx::Side
     P.sc.n_top = plan.n_top;
     P.sph_tab = plan.sph_tab;
     P.chunk = plan.chunk;
-    if (plan.kernel != PT_KERNEL_PERSISTENT) return;
-    P.queue = sd ? sd->queue : c->d_queue;
-    P.batch = c->opt_batch;
-    // refill <= batch, or a wave can spin: the walk returns at once because `batch` lanes wait,
-    // none of them has anything to shade and the idle ones are too few to trigger a refill
-    P.refill = c->opt_refill < c->opt_batch ? c->opt_refill : c->opt_batch;
-    P.vote_node = c->opt_vote_node;
-    P.vote_rec = c->opt_vote_rec;
+    if (plan.kernel == PT_KERNEL_PERSISTENT) queue_params(c, sd ? sd->queue : c->d_queue, P);
 }
 }  // namespace ptmi
 
@@ -670,8 +643,8 @@ int pt_render_moments(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, float* mo
         if (rc != PT_OK) return rc;
     }
     if (probe >= 0) HIP_TRY(c, hipEventRecord(plan.pick->e[2 * probe], c->stream));
+    HIP_TRY(c, span_begin(c));
     if (c->opt_timing) {
-        HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
         c->stage_used = 0;
         if (stage_mark(c, PT_STAGE_NONE) != PT_OK) return PT_ERR_DEVICE;
     }
@@ -680,7 +653,7 @@ int pt_render_moments(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, float* mo
         rc = render_wavefront(c, P, plan.L, plan.work_tiles, folded);
         if (rc != PT_OK) return rc;
     } else if (plan.kernel == PT_KERNEL_PERSISTENT) {
-        HIP_TRY(c, hipMemsetAsync(P.queue, 0, PT_SHARDS * PT_SHARD_STRIDE * sizeof(unsigned int), trace_stream));
+        HIP_TRY(c, queue_reset(P.queue, trace_stream));
         HIP_TRY(c, launch_persist(plan.L, P, trace_stream));
         if (stage_mark(c, PT_STAGE_FRAME) != PT_OK) return PT_ERR_DEVICE;
     } else {
@@ -700,7 +673,7 @@ int pt_render_moments(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, float* mo
         sd->fold_pending = true;
     }
     if (probe >= 0) HIP_TRY(c, hipEventRecord(plan.pick->e[2 * probe + 1], c->stream));
-    if (c->opt_timing) { HIP_TRY(c, hipEventRecord(c->ev1, c->stream)); c->timed = true; }
+    HIP_TRY(c, span_end(c));
     return PT_OK;
 }
 
@@ -725,17 +698,11 @@ int pt_trace_rays(pt_ctx* c, const float* rays_dev, size_t n, int cull, float* t
     if (!rays_dev || !t_dev || !tri_dev) return fail(c, PT_ERR_INVALID, "pt_trace_rays: null argument");
     HIP_TRY(c, hipSetDevice(c->device));
     KScene sc;
-    std::memset(&sc, 0, sizeof sc);
-    sc.nodes = sc.tris = c->tree.d_nodes; sc.spheres = nullptr; sc.n_spheres = 0; sc.has_bvh = 1;
-    if (c->opt_timing) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-    const float4* r4 = (const float4*)rays_dev;
-    sc.stack_n = PT_STACK_CAP;
-    sc.top_base = 0;
-    sc.wide_root = (int)c->tree.wide_root;
-    sc.n_top = (int)std::min<uint32_t>((uint32_t)c->opt_top, c->tree.n_top_layout);
-    const size_t lds = lds_fit(sc.n_top, sc.stack_n, PT_BLOCK_RAYS);
-    HIP_TRY(c, launch_rays(sc, lds, r4, n, cull, t_dev, tri_dev, normal_dev, c->stream));
-    if (c->opt_timing) { HIP_TRY(c, hipEventRecord(c->ev1, c->stream)); c->timed = true; }
+    scene_view(c, sc);
+    HIP_TRY(c, span_begin(c));
+    const size_t lds = binary_ray_layout(c, sc);
+    HIP_TRY(c, launch_rays(sc, lds, (const float4*)rays_dev, n, cull, t_dev, tri_dev, normal_dev, c->stream));
+    HIP_TRY(c, span_end(c));
     return PT_OK;
 }
 
@@ -749,9 +716,9 @@ static int query_call(pt_ctx* c, const char* who, bool outputs, const ptmi::Quer
     if (!q.rays || !outputs) return fail(c, PT_ERR_INVALID, name + ": null argument");
     if (q.n >= (1ull << 32)) return fail(c, PT_ERR_INVALID, name + ": more than 2^32 - 1 rays in one call");
     HIP_TRY(c, hipSetDevice(c->device));
-    if (c->opt_timing) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    HIP_TRY(c, span_begin(c));
     HIP_TRY(c, launch_query(c, q));
-    if (c->opt_timing) { HIP_TRY(c, hipEventRecord(c->ev1, c->stream)); c->timed = true; }
+    HIP_TRY(c, span_end(c));
     return PT_OK;
 }
 
@@ -761,6 +728,55 @@ int pt_closest_hits(pt_ctx* c, const float* rays_dev, size_t n, int cull, float*
 
 int pt_any_hits(pt_ctx* c, const float* rays_dev, size_t n, int cull, uint8_t* hit_dev) {
     return query_call(c, "pt_any_hits", hit_dev != nullptr, ptmi::QueryCall{rays_dev, n, cull, nullptr, nullptr, nullptr, hit_dev});
+}
+
+// slots of one pt_render_rays launch: what keeps its sample buffer below 768 MiB; more samples than that go out as several
+// launches, which the fold's order makes the same thing
+static constexpr uint64_t RAYS_MAX_SLOTS = 1ull << 26;
+
+int pt_render_rays(pt_ctx* c, const float* rays_dev, size_t n_rays, uint64_t first_index, float* radiance_dev, const pt_params* p,
+                   uint32_t spp, int mode) {
+    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
+    if (!c->tree.has_bvh && c->n_spheres == 0) return fail(c, PT_ERR_NO_SCENE, "pt_render_rays: no scene uploaded");
+    if (n_rays == 0 || spp == 0) return PT_OK;
+    if (!rays_dev || !radiance_dev || !p) return fail(c, PT_ERR_INVALID, "pt_render_rays: null argument");
+    if (mode != PT_RAYS_CLAMPED && mode != PT_RAYS_HDR) return fail(c, PT_ERR_INVALID, "pt_render_rays: mode must be PT_RAYS_CLAMPED or PT_RAYS_HDR");
+    if (n_rays >= (1ull << 32)) return fail(c, PT_ERR_INVALID, "pt_render_rays: more than 2^32 - 1 rays in one call");
+    // ... then pt_render's own conditions on the fields both read
+    if (p->sample_index == 0) return fail(c, PT_ERR_INVALID, "pt_render_rays: sample_index starts at 1");
+    if (p->tri_mat < PT_MAT_DIFF || p->tri_mat > PT_MAT_REFR) return fail(c, PT_ERR_INVALID, "pt_render_rays: bad triangle material");
+    if ((p->flags & PT_FLAG_NEE) && !(p->flags & PT_FLAG_COSINE_DIFF)) return fail(c, PT_ERR_INVALID, "pt_render_rays: PT_FLAG_NEE needs PT_FLAG_COSINE_DIFF");
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = refresh_tri_lights(c, p);
+    if (rc != PT_OK) return rc;
+    const int walk = choose_walk(c, "pt_render_rays", false);   // (0 runs as 1: launch_render_rays has no while-while walk)
+    if (walk < 0) return walk;
+    KParams P;
+    fill_path_params(c, p, spp, P);
+    P.sc.stack_n = 16;
+    P.sc.top_base = walk >= 2 ? P.sc.wide_root : 0;
+    size_t lds = (size_t)16 * PT_BLOCK * 4;
+    P.sph_tab = c->opt_sph_lds ? lds_sphere_table(lds) : -1;
+    queue_params(c, c->d_queue, P);   // the context's counters: every use is on the caller's stream, behind a reset of its own
+    const ptmi::RaysCall R{rays_dev, radiance_dev, first_index, n_rays, mode == PT_RAYS_HDR};
+    const uint32_t per_launch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(spp, RAYS_MAX_SLOTS / n_rays));
+    if (per_launch > 1 && (rc = samples_reserve(c, nullptr, (size_t)per_launch * n_rays * 3 * sizeof(float), P)) != PT_OK) return rc;
+    P.smp_ss = n_rays;
+    P.smp_ps = 1u;
+    HIP_TRY(c, span_begin(c));
+    for (uint32_t s0 = 0; s0 < spp; s0 += per_launch) {
+        P.spp = std::min(per_launch, spp - s0);
+        P.frame = p->frame + s0;
+        P.sample_index = p->sample_index + s0;
+        const uint64_t slots = (uint64_t)n_rays * (per_launch > 1 ? P.spp : 1u);
+        P.chunk = queue_chunk(c, slots);
+        const int work_blocks = (int)std::min<uint64_t>((slots + (uint64_t)P.chunk * 4 - 1) / ((uint64_t)P.chunk * 4), (uint64_t)INT_MAX);
+        HIP_TRY(c, queue_reset(P.queue, c->stream));
+        HIP_TRY(c, launch_render_rays(c, walk, (p->flags & PT_FLAG_NEE) != 0, lds, work_blocks, P, R));
+        if (per_launch > 1) HIP_TRY(c, launch_fold_rays(c, P, R));
+    }
+    HIP_TRY(c, span_end(c));
+    return PT_OK;
 }
 
 int pt_get_counters(pt_ctx* c, pt_counters* out) {

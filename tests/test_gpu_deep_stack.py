@@ -182,13 +182,18 @@ def same_frame(got, ref, what):
 @pytest.mark.parametrize("D", DEPTHS)
 def test_ray_batch_over_comb(D, cull):
     """stack depth D (every one of the 128 rays pushes D entries; pt_trace_rays keeps all 72 in LDS): t, id and normal of every
-    half-cell ray equal brute force, no mismatch allowed"""
+    half-cell ray equal brute force, no mismatch allowed.  The first case also reads pt_trace_rays' timed span (PT_OPT_TIMING)."""
     s = scene(f"comb-{D}")
     s.check_tree(D, math.ceil(D / 3))
     rays = dt.cell_rays(s.fx)
     depth = dt.binary_stack_depth(s.fx, rays)
     assert depth.min() == depth.max() == D
+    timed = D == DEPTHS[0] and cull
+    s.t.set_option(g.OPT_TIMING, int(timed))
     t, tri, nrm = gpu_trace(s.t, rays, cull)
+    if timed:
+        assert s.t.last_kernel_ms() > 0
+        s.t.set_option(g.OPT_TIMING, 0)
     t0, tri0, nrm0 = orc.trace_brute(s.fx.mesh, rays, cull)
     assert np.array_equal(tri0, dt.expected_ids(s.fx, rays)) and (tri0 >= 0).sum() == D + 1
     assert np.array_equal(tri, tri0), f"ids differ for rays {np.nonzero(tri != tri0)[0][:8]}"

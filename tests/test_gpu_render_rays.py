@@ -11,10 +11,12 @@ import subprocess
 import numpy as np
 import pytest
 
+import deep_trees as dt
 import gpu_pathtracer_amd as g
 import orc
 from denoise_ref import sphere_intersect
 from gpu_support import bits, golden_camera, setup_scene, soup_mesh, twist
+from scene_matrix import tilted_grid_table
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
@@ -456,3 +458,107 @@ def test_pt_app_equirect(tmp_path):
         tr.close()
     rows = [img[H // 2, W // 2], img[H - 1 - H // 2, W // 2]]   # (whichever way the writer orders the rows)
     assert any(np.array_equal(bits(r), bits(want)) for r in rows), (rows, want)
+
+
+# ---------------------------------------------------------------------------------------------------- 9: deep trees
+DEEP_BK = (0.125, 0.75, 0.375)
+_deep = {}
+
+
+def deep_case(name):
+    """(fixture, its 128 half-cell rays, the radiance every ray must return at depth 1 under tilted_grid_table) of a tree of
+    tests/deep_trees.py: the emission of the triangle deep_trees.expected_ids names, which brute force confirms, or DEEP_BK."""
+    if name not in _deep:
+        kind, n = name.split("-")
+        fx = dt.stair(int(n)) if kind == "stair" else dt.comb(int(n))
+        rays = dt.cell_rays(fx)
+        ids = dt.expected_ids(fx, rays)
+        assert np.array_equal(orc.trace_brute(fx.mesh, rays, True)[1], ids) and 16 < (ids >= 0).sum() < 128
+        want = np.tile(np.array(DEEP_BK, np.float32), (len(rays), 1))
+        want[ids >= 0] = np.stack([(ids[ids >= 0] + 1) / 256.0, np.full((ids >= 0).sum(), 0.5), np.full((ids >= 0).sum(), 0.25)], 1)
+        _deep[name] = fx, rays, ids, want
+    return _deep[name]
+
+
+def deep_context(fx, woop=False):
+    tr = g.PathTracer(0)
+    tr.set_option(g.OPT_TRI_TEST, int(woop))
+    tr.upload_bvh(fx)
+    tr.upload_spheres(None)
+    tr.upload_tri_materials(*tilted_grid_table(fx.n_tris))
+    return tr
+
+
+def deep_params():
+    p = params(64, 64, depth=1)
+    p.bk_color[:] = DEEP_BK
+    return p
+
+
+# stair(23): 3 * 23 + 2 = 71 entries, the last tree the wide walk takes; stair(24): 74 > 72, the unified binary walk takes over;
+# comb(17): stack depth 17, the first overflow of the 16-entry LDS window this call always uses
+DEEP_TREES = {"stair-23": (24, 23), "stair-24": (25, 24), "comb-17": (17, 6)}   # name -> (max_depth, wide depth)
+
+
+@pytest.mark.parametrize("name", list(DEEP_TREES))
+def test_deep_trees_under_every_walk(name):
+    """pt_render_rays over the trees on both sides of the wide walk's stack rule and past the LDS window, under the default walk and
+    PT_OPT_WALK 0, 1 (both run the unified binary walk here) and 4 (runs as 2): depth 1, every triangle emitting its id, so a ray's
+    radiance names the triangle it hit.  Equal to the brute-force answer bit for bit."""
+    fx, rays, ids, want = deep_case(name)
+    assert (fx.max_depth, fx.wide_depth) == DEEP_TREES[name]
+    if name == "comb-17":
+        depth = dt.binary_stack_depth(fx, rays)
+        assert depth.min() == depth.max() == 17
+    tr = deep_context(fx)
+    try:
+        assert tr.scene_info()["max_depth"] == fx.max_depth and tr.tree_items()[3] == fx.wide_depth
+        for walk in (2, 0, 1, 4):
+            tr.set_option(g.OPT_WALK, walk)
+            for hdr in (True, False):
+                b = Batch(tr, rays)
+                b.render(deep_params(), 1, hdr=hdr)
+                got = b.get()
+                b.free()
+                bad = np.nonzero(np.any(bits(got) != bits(want), axis=1))[0]
+                assert len(bad) == 0, f"{name} walk {walk} hdr {hdr}: rays {bad[:8]} return {got[bad[:4]]}, brute force {want[bad[:4]]}"
+    finally:
+        tr.close()
+
+
+def test_deep_trees_with_woop_records():
+    """Woop records (PT_OPT_TRI_TEST 1 before the upload) are read by the wide walk only.  stair(24) is too deep for it: the call
+    answers PT_ERR_UNSUPPORTED, names itself in the message and writes nothing.  stair(23) renders: which triangle a ray hits, or
+    that it hits none, equals brute force for every ray (Woop's t differs in its last bits; the ids, and with them the emission
+    returned at depth 1, do not)."""
+    lib = g._abi.ptmi()
+    fx, rays, ids, want = deep_case("stair-24")
+    tr = deep_context(fx, woop=True)
+    try:
+        assert tr.tree_items()[3] == 24
+        b, p = Batch(tr, rays), deep_params()
+        canary = b.get().copy()
+        for walk in (2, 1):
+            tr.set_option(g.OPT_WALK, walk)
+            assert lib.pt_render_rays(tr._ctx, b.rays.ptr, b.n, 0, b.out.ptr, C.byref(p), 1, 0) == -5
+            msg = lib.pt_last_error(tr._ctx).decode()
+            assert msg.startswith("pt_render_rays:") and "Woop" in msg, msg
+        assert np.array_equal(b.get(), canary)
+        b.free()
+    finally:
+        tr.close()
+    fx, rays, ids, want = deep_case("stair-23")
+    tr = deep_context(fx, woop=True)
+    try:
+        assert tr.tree_items()[3] == 23
+        for walk in (2, 1):     # (the option does not choose the walk of Woop records)
+            tr.set_option(g.OPT_WALK, walk)
+            b = Batch(tr, rays)
+            b.render(deep_params(), 1, hdr=True)
+            got = b.get()
+            b.free()
+            hit = np.any(bits(got) != bits(np.array(DEEP_BK, np.float32)), axis=1)
+            assert np.array_equal(hit, ids >= 0), f"walk {walk}: hit / miss differs for rays {np.nonzero(hit != (ids >= 0))[0][:8]}"
+            assert np.array_equal(bits(got), bits(want)), f"walk {walk}: rays {np.nonzero(np.any(got != want, axis=1))[0][:8]} name another triangle"
+    finally:
+        tr.close()
