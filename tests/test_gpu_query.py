@@ -393,13 +393,18 @@ def test_queries_leave_no_trace_in_render():
 
         before = frame(t)
         mesh, rays, cls, b, ref = qr.case("cornell", N, SEED, True)      # the room's mesh
-        for lstk, batch in ((16, 16), (24, 5), (16, 64)):
+        # the answers at every setting are compared, not looked at: both range ends of the two schedule knobs of the refill
+        # loop of k_query_rays, each stack window, against brute force filtered by the bound (as the parity tests above)
+        for lstk, batch, blocks in ((16, 16, 8), (24, 5, 8), (16, 64, 8), (16, 1, 8), (24, 1, 1), (16, 64, 1), (16, 16, 1)):
             t.set_option(g.OPT_LDS_STACK, lstk)
             t.set_option(g.OPT_WAVE_BATCH, batch)
-            gt, gi, gn, gb = query(t, rays, True)
-            assert (gi >= 0).mean() > 0.2 and gb.any() and not gb.all()
+            t.set_option(g.OPT_WAVE_BLOCKS, blocks)
+            got = query(t, rays, True)
+            compare(f"room, PT_OPT_LDS_STACK {lstk} PT_OPT_WAVE_BATCH {batch} PT_OPT_WAVE_BLOCKS {blocks}", got, ref, rays, MAX_DIFF)
+            assert got[3].any() and not got[3].all()
         t.set_option(g.OPT_LDS_STACK, 16)
         t.set_option(g.OPT_WAVE_BATCH, 16)
+        t.set_option(g.OPT_WAVE_BLOCKS, 8)
         after = frame(t)
         clean = g.PathTracer(0)
         try:

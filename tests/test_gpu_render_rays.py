@@ -15,8 +15,8 @@ import deep_trees as dt
 import gpu_pathtracer_amd as g
 import orc
 from denoise_ref import sphere_intersect
-from gpu_support import bits, golden_camera, setup_scene, soup_mesh, twist
-from scene_matrix import tilted_grid_table
+from gpu_support import MAX_DIFF, bits, golden_camera, setup_scene, soup_mesh, twist
+from scene_matrix import make_camera, tilted_grid_table
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
@@ -230,6 +230,109 @@ def test_first_index_beyond_32_bits(t):
     assert not np.array_equal(low.get(), got1), "the upper word of first_index is part of the key"
     low.free()
     b.free()
+
+
+# ---------------------------------------------------------------------------------------------------- 3b: the schedule knobs
+# include/ptmi.h: "PT_OPT_BATCH, PT_OPT_REFILL and PT_OPT_SPHERE_LDS apply: speed, never results".  k_render_rays carries its own copy
+# of the persistent kernel's refill loop (ballot / mbcnt lane -> slot map, sharded chunk counter, refill <= batch clamp), so the copy
+# is rendered at the same corners as tests/test_gpu_schedule_knobs.py renders the original (which also says why no setting can spin).
+KNOB_SETTINGS = [((g.OPT_BATCH, b), (g.OPT_REFILL, r)) for b, r in ((1, 1), (1, 64), (64, 1), (64, 64), (36, 8), (2, 64))] + \
+                [((g.OPT_SPHERE_LDS, 0),), ((g.OPT_SPHERE_LDS, 1),)]
+POISON = 1000
+
+
+FIXED_FRONTS = ((0.3, -0.4, -1.0), (-0.5, 0.2, -1.0), (0.0, -1.0, -0.9), (0.8, 0.1, -1.0), (-0.2, 0.7, -1.0), (0.1, -0.3, -1.0), (-0.9, -0.6, -1.0))
+
+
+def fixed_ray_camera(W, H, front):
+    """A camera with fov 0: every pixel's ray is pos + dist * front along front whatever the jitter, so ALL samples of orc.render
+    start from the ray pt_render_rays is given once — its spp samples of one ray are then the oracle's samples of that pixel."""
+    return make_camera(W, H, pos=(0.0, 0.0, 0.0), front=front, fov=0.0)
+
+
+def knob_cases():
+    """name -> (W, H, rays, calls, spp per call): the camera's rays of one frame, three one-sample calls (camera_frames: each
+    frame's own jitter), and 7 rays x 512 samples in one call — few rays and many samples, so almost every slot of a wave is the
+    same ray and the samples go through the sample buffer ([spp][n][3]) and the fold.  The seven rays are seven different
+    ones, ray i that of a zero-fov camera looking along FIXED_FRONTS[i]: a slot that read another ray's origin or direction,
+    or another ray's random stream, would show."""
+    return {"129x71x3": (129, 71, 129 * 71, 3, 1), "7x512": (7, 2, 7, 1, 512)}
+
+
+def knob_rays(name, k):
+    """The rays of call k of the case."""
+    W, H, n, calls, spp = knob_cases()[name]
+    if name == "7x512":
+        return np.stack([orc.primary_rays(fixed_ray_camera(W, H, f), W, H, frame=F0)[i] for i, f in enumerate(FIXED_FRONTS)])
+    return orc.primary_rays(golden_camera(W, H), W, H, frame=F0 + k)[:n]
+
+
+_knob_ref = {}
+
+
+def knob_reference(name):
+    """orc.render's accumulator for the case, one row per ray, once per run.  The 7-ray case: row i is pixel i (the random stream
+    of key i, which first_index = 0 gives ray i) of the oracle's frame through camera i, after its premise is checked."""
+    if name not in _knob_ref:
+        W, H, n, calls, spp = knob_cases()[name]
+        bvh, sph = g.Bvh(g.scene_mesh("cornell")), g.reference_spheres()
+        if name == "7x512":
+            ref = np.zeros((n, 3), np.float32)
+            for i, f in enumerate(FIXED_FRONTS):
+                cam = fixed_ray_camera(W, H, f)
+                r0, r1 = orc.primary_rays(cam, W, H, frame=F0), orc.primary_rays(cam, W, H, frame=F0 + 5)
+                assert np.isfinite(r0).all() and np.array_equal(bits(r0), bits(r1)) and len(np.unique(r0, axis=0)) == 1, "the ray depends on the jitter"
+                ref[i] = orc.render(bvh, sph, cam, params(W, H), spp, want_rgba=False)[0][0, i]
+            assert len(np.unique(knob_rays(name, 0)[:, 4:7], axis=0)) == n and len(np.unique(ref, axis=0)) == n
+        else:
+            ref = orc.render(bvh, sph, golden_camera(W, H), params(W, H), calls * spp, want_rgba=False)[0].reshape(-1, 3)[:n]
+        _knob_ref[name] = ref
+    return _knob_ref[name]
+
+
+def knob_render(name, walk, options):
+    """The case on a fresh context with `options`, behind a poison call: the same buffers rendered with other frame numbers
+    first, so a slot that is never traced leaves a value of the wrong frame in the sample buffer or the output."""
+    W, H, n, calls, spp = knob_cases()[name]
+    tr = g.PathTracer(0)
+    try:
+        tr.set_option(g.OPT_WALK, walk)
+        for o, v in options:
+            tr.set_option(o, v)
+        setup_scene(tr, "room", False)
+        b = Batch(tr, knob_rays(name, 0))
+        b.render(params(W, H, frame=F0 + POISON), spp)
+        poison = b.get().copy()
+        for k in range(calls):
+            if k:
+                tr.sync()   # the next upload must not overtake the launch
+                b.set_rays(knob_rays(name, k))
+            b.render(params(W, H, frame=F0 + k * spp, sample_index=1 + k * spp), spp)
+        got = b.get()
+        b.free()
+        assert got.any() and not np.array_equal(got, poison), f"{name} walk {walk} {options}: empty, or the poison call's result"
+        return got
+    finally:
+        tr.close()
+
+
+@pytest.mark.parametrize("walk", [1, 2])
+@pytest.mark.parametrize("name", list(knob_cases()))
+def test_schedule_knobs_change_no_radiance(name, walk):
+    """PT_OPT_BATCH x PT_OPT_REFILL at the corners of their ranges (in (1, 64) and (2, 64) the clamp works) and PT_OPT_SPHERE_LDS
+    0 / 1.  Walk 1 (the unified binary walk, exact): the radiance equals orc.render's accumulator bit for bit at every setting.
+    Walk 2 (wide): it equals the default-knob result bit for bit, which may leave the oracle at no more than MAX_DIFF grazing rays."""
+    ref = knob_reference(name)
+    if walk == 2:
+        base = knob_render(name, walk, ())
+        n_off = int(np.any(bits(base) != bits(ref), axis=1).sum())
+        print(f"{name}: the wide walk's default-knob result differs from the oracle at {n_off} rays")
+        assert n_off <= MAX_DIFF
+        ref = base
+    for options in KNOB_SETTINGS:
+        got = knob_render(name, walk, options)
+        bad = np.nonzero(np.any(bits(got) != bits(ref), axis=1))[0]
+        assert len(bad) == 0, f"{name} walk {walk} {options}: {len(bad)} rays differ, first {bad[:6]}"
 
 
 # ---------------------------------------------------------------------------------------------------- 4: rays no camera makes
