@@ -103,6 +103,7 @@ OPT_KERNEL, OPT_COUNTERS, OPT_TIMING, OPT_BATCH, OPT_TOP_NODES, OPT_OCCUPANCY, O
 OPT_FIRST_WALK, OPT_PACKET_STACK, OPT_FUSE_STAGES, OPT_LAST_ANYHIT = 26, 27, 28, 29
 OPT_ROOT_CULL = 30
 OPT_ROOT_ENTRY = 33   # (not re-exported by the package: gpu_pathtracer_amd._abi.OPT_ROOT_ENTRY)
+OPT_PATH_HISTORY = 34   # (not re-exported either)
 
 # every symbol include/ptmi.h declares: (name, restype, argtypes)
 _vp, _sz, _i, _u32 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32

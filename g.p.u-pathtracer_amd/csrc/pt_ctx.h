@@ -118,6 +118,7 @@ struct pt_ctx {
     int opt_last_anyhit = 1;     // the last segment as a sphere-bounded any-hit query: 0 off, 1 product launches, 2 instrumented too (PT_OPT_LAST_ANYHIT)
     int opt_root_cull = 1;       // new rays the root node step turns away stay out of the extend queue: 0 off, 1 product launches, 2 instrumented too (PT_OPT_ROOT_CULL)
     int opt_root_entry = 1;      // ... and the walkers' records carry the root step's result, the extend launches start below the root: 0 off, 1 product launches, 2 instrumented too (PT_OPT_ROOT_ENTRY)
+    int opt_path_history = 1;    // the records carry the objects a path has hit instead of its mask, its sample colour is written once: 0 off, 1 product launches, 2 instrumented too (PT_OPT_PATH_HISTORY)
     // PT_KERNEL_AUTO: which stage layout is faster depends on the workload (long paths and many samples per call:
     // the stage-split pipeline; short paths or few samples: the persistent kernel), so the first FOUR calls of a
     // configuration are timed trials, two per layout, alternating (HIP events on the stream, buffers allocated before the
@@ -234,6 +235,18 @@ inline int choose_walk(pt_ctx* c, const char* who, bool postponed) {
         return wide_ok ? 3 : fail(c, PT_ERR_UNSUPPORTED, std::string(who) + ": Woop records need the wide walk and this tree is too deep for it");
     const int walk = c->opt_walk == 4 && !postponed ? 2 : c->opt_walk;
     return walk >= 2 && !wide_ok ? 1 : walk;
+}
+// PT_OPT_PATH_HISTORY: whether a call's masks and gathered light are functions of the objects its paths hit, in path_shade_hit's
+// DIFF / SPEC / METAL arithmetic (mask *= colour, accu += mask * emission) — nothing scales the colour (the roulettes), nothing adds in
+// place beside the shade lanes (PT_FLAG_NEE: k_wf_resolve), every object has a history code and a row in the shade stage's table (the
+// spheres of the kernel-argument block, ONE triangle material), no REFR branch scales the mask, and the word holds the codes.
+inline bool path_history_holds(const KParams& P) {
+    if ((P.flags & (PT_FLAG_NEE | PT_FLAG_RUSSIAN_ROULETTE | PT_FLAG_RR_CPU_TRACER)) || P.tri_matid || P.sc.n_spheres > PT_KSPHERES ||
+        P.tri_mat == PT_MAT_REFR || P.depth > PT_HIST_MAX_DEPTH)
+        return false;
+    for (int i = 0; i < P.sc.n_spheres; i++)
+        if (P.ksph[i].mat == PT_MAT_REFR) return false;
+    return true;
 }
 // The scene as a kernel sees it: one item buffer for nodes and records, the wide tree's root and, where ksph (KParams::ksph) is
 // given, the spheres: a ray-batch query sees none.  Zeroes the rest; the stack and LDS layout is the caller's.

@@ -20,6 +20,9 @@
 //              (tracer.cu:140-142), survivors are packed to the front of their region's next generation with
 //              a ballot + prefix count (v_mbcnt) — dead paths cost nothing in the next stage; survivors whose new ray
 //              the tree's root turns away are packed behind the others and never queued (PT_OPT_ROOT_CULL)
+//   PT_OPT_PATH_HISTORY (the default where it holds: path_history_holds, pt_ctx.h): the record carries which objects the path has
+//              hit instead of its mask, the shade lane rebuilds mask and accu from that word, and the sample colour is written once,
+//              by the lane the path ends in — no write at bounce 0 for a path that goes on, no add in place
 //   k_fold_samples folds the sample colours into the running mean (tracer.cu:386-391), as for every kernel.
 // Which of the kernels below a bounce runs: WavePlan, at the end of the file.  Why the split pays: DESIGN.md §5.2.
 #include "pt_ctx.h"
@@ -45,6 +48,9 @@ __device__ __forceinline__ int wf_block_rank(bool keep, int& total, int* s_cnt) 
 }
 
 // copies the first PT_KSPHERES spheres' attributes from the kernel arguments into LDS (path_shade's sph_tab = 0)
+// HIST (PT_OPT_PATH_HISTORY): one more row behind them, the call's triangle material as code PT_HIST_TRI reads it (wf_history_row)
+constexpr int WF_TRI_ROW = 15 * PT_KSPHERES - 4;   // its emission at [4..6] and colour at [7..9], where a sphere's row has them
+template <bool HIST = false>
 __device__ __forceinline__ void wf_sphere_table() {
     if (threadIdx.x < 11 * PT_KSPHERES) {
         PT_KARGS(K);
@@ -52,7 +58,29 @@ __device__ __forceinline__ void wf_sphere_table() {
         ((float*)s_dyn)[threadIdx.x] = v;
         if (threadIdx.x % 11 < 4) ((float*)s_dyn)[88 + 4 * (threadIdx.x / 11) + threadIdx.x % 11] = v;
     }
+    if (HIST && threadIdx.x >= 128 && threadIdx.x < 134) {   // (another wave than the spheres'; tri_col and tri_emi lie side by side)
+        PT_KARGS(K);
+        const int k = (int)threadIdx.x - 128;
+        ((float*)s_dyn)[WF_TRI_ROW + (k < 3 ? 7 + k : 1 + k)] = ((const __attribute__((address_space(4))) float*)&K.tri_col[0])[k];
+    }
     __syncthreads();
+}
+
+// PT_OPT_PATH_HISTORY: the row of the object behind a history code (pt_kernels.h) in the table above
+__device__ __forceinline__ const float* wf_history_row(uint32_t code) {
+    return (const float*)s_dyn + (code == PT_HIST_TRI ? (uint32_t)WF_TRI_ROW : 11u * code);
+}
+// ... and a path's mask and gathered light in front of bounce n, from the objects its bounces 0 .. n - 1 ended on: the operations,
+// operands and order of path_shade_hit (DIFF, SPEC and METAL: accu += mask * emit, then mask *= colour), so both are what the lane
+// that carries them from bounce to bounce holds, bit for bit
+__device__ __forceinline__ void wf_history_replay(uint32_t word, uint32_t n, v3& mask, v3& accu) {
+    mask = V3(1.f, 1.f, 1.f);
+    accu = V3(0.f, 0.f, 0.f);
+    for (uint32_t k = 0; k < n; k++) {   // (n = the bounce: wave-uniform)
+        const float* t = wf_history_row(pt_hist_code(word, k));
+        accu = vadd(accu, vmul(mask, V3(t[4], t[5], t[6])));
+        mask = vmul(mask, V3(t[7], t[8], t[9]));
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -280,6 +308,12 @@ __device__ __forceinline__ void wf_shade_miss(float* smp, v3 mask) {
         smp[0] = K.bk[0]; smp[1] = K.bk[1]; smp[2] = K.bk[2];
     }
 }
+// PT_OPT_PATH_HISTORY: the same rule for a lane that holds the path's whole accu — the sample's one store (accu is 0 at bounce 0)
+__device__ __forceinline__ void wf_shade_miss_history(float* smp, v3 accu, v3 mask) {
+    PT_KARGS(K);
+    if (K.flags & PT_FLAG_MISS_KEEPS_PATH) pt_sst3(smp, V3(accu.x + mask.x * K.bk[0], accu.y + mask.y * K.bk[1], accu.z + mask.z * K.bk[2]));
+    else pt_sst3(smp, V3(K.bk[0], K.bk[1], K.bk[2]));
+}
 // mask * emission of a later bounce's hit, added to the sample colour in place; nothing is touched when it is all zero
 __device__ __forceinline__ void wf_add_emission(float* smp, v3 e) {
     if (!(e.x == 0.f) || !(e.y == 0.f) || !(e.z == 0.f)) {
@@ -290,8 +324,11 @@ __device__ __forceinline__ void wf_add_emission(float* smp, v3 e) {
 // one path's segment after the walk: h = its closest triangle hit (h.tri 0, or the triangle's id with P.tri_matid; -1 on a
 // miss); the spheres, then the background, the emission alone (LAST) or shading + the BRDF sample, the emission going to the
 // sample colour smp (FIRST: written, not added to).  True when the path goes on.
-template <bool NEE, bool FIRST, bool LAST>
-__device__ __forceinline__ bool wf_shade_segment(const KParams& P, PathState& ps, const Hit& h, bool tri_hit, float* smp, NeeReq* req) {
+// HIST (PT_OPT_PATH_HISTORY): ps came in with the path's whole mask and accu (wf_history_replay), so smp is written ONCE, here, when
+// the path ends with this segment, and not touched when it goes on; `code` = the history code of what the segment ended on.
+template <bool NEE, bool FIRST, bool LAST, bool HIST = false>
+__device__ __forceinline__ bool wf_shade_segment(const KParams& P, PathState& ps, const Hit& h, bool tri_hit, float* smp, NeeReq* req, uint32_t& code) {
+    static_assert(!(NEE && HIST), "k_wf_resolve adds to the sample colour in place");
     v3 tri_n = V3(0.f, 0.f, 0.f);
     if (!LAST && tri_hit) {   // the triangle's un-normalised normal (4th piece)
         const float4 q3 = P.sc.nodes[h.rec + 3];
@@ -299,10 +336,21 @@ __device__ __forceinline__ bool wf_shade_segment(const KParams& P, PathState& ps
     }
     const SceneHit sh = pt_closest_sphere(P, ps.o, ps.d, h, 0);
     if (sh.geom == 3) {
-        wf_shade_miss<FIRST>(smp, ps.mask);
+        if (HIST) wf_shade_miss_history(smp, ps.accu, ps.mask);
+        else wf_shade_miss<FIRST>(smp, ps.mask);
         return false;
     }
     v3 col;
+    if (HIST) {
+        code = sh.geom == 1 ? (uint32_t)sh.sph_id : PT_HIST_TRI;
+        if (LAST) {   // (tracer.cu:305: accu after the last hit's emission)
+            pt_sst3(smp, vadd(ps.accu, path_last_emission(P, ps, h, sh, 0)));
+            return false;
+        }
+        const bool ended = path_shade_hit(P, ps, h, sh, tri_n, col, 0, nullptr);
+        if (ended) pt_sst3(smp, FIRST ? V3(0.f + col.x, 0.f + col.y, 0.f + col.z) : col);   // col = accu
+        return !ended;
+    }
     const bool done = LAST ? true : path_shade_hit(P, ps, h, sh, tri_n, col, 0, NEE ? req : nullptr);
     if (LAST) col = path_last_emission(P, ps, h, sh, 0);
     const v3 e = done ? col : ps.accu;   // mask * emission of this hit (accu entered as 0)
@@ -386,7 +434,9 @@ __device__ __forceinline__ void wf_region_counts(const KParams& P, uint32_t regi
 // FOLD (PT_OPT_FUSE_STAGES, LAST only): LP of wf_fold_region — this launch also folds the samples, no k_fold_samples follows
 // BOUND (PT_OPT_LAST_ANYHIT, the shade launch of bounce depth - 2): the survivors' rays are the paths' last segments; their
 // sphere bound goes to the survivor's hit slot for k_wf_extend<.., ANY> and k_wf_shade_last_any
-template <bool COUNT, bool NEE, bool FIRST, bool LAST = false, int FOLD = 0, bool BOUND = false>
+// HIST (PT_OPT_PATH_HISTORY, never NEE): plane 0 of the mask generations holds the path's history word instead of mask.x, the other two
+// planes are not touched; the lane rebuilds mask and accu from it, and the sample colour is written by the lane the path ends in
+template <bool COUNT, bool NEE, bool FIRST, bool LAST = false, int FOLD = 0, bool BOUND = false, bool HIST = false>
 __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
     __shared__ int s_cnt[PT_BLOCK / 64];
     __shared__ int s_cnt2[PT_BLOCK / 64];
@@ -400,10 +450,11 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
         if constexpr (FOLD > 0) wf_fold_region<FOLD>(P, region);   // every path of the region ended earlier: its samples are final
         return;
     }
-    wf_sphere_table();
+    wf_sphere_table<HIST>();
     const size_t i = (size_t)region * PT_REGION + threadIdx.x;
     bool have = (int)threadIdx.x < n_in;
     bool alive = false, tri_hit = false;
+    uint32_t hist = 0, code = 0;
     PathState ps;
     NeeReq req;
     req.want = false;
@@ -427,8 +478,13 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
                 sn &= (1u << PT_REC_LIGHT_BIT) - 1u;
             } else if (P.wf.root_entry) sn &= (1u << PT_REC_ENTRY_SHIFT) - 1u;   // (the entry code was the walk's)
             s_idx = sn >> PT_REC_DRAW_BITS;
-            ps.mask = V3(pt_sld1(P.wf.mask_in + i), pt_sld1(P.wf.mask_in + (size_t)P.wf.cap + i), pt_sld1(P.wf.mask_in + 2 * (size_t)P.wf.cap + i));
-            ps.accu = V3(0.f, 0.f, 0.f);   // this segment's emission only: the running sum lives in the sample buffer
+            if (HIST) {
+                hist = __float_as_uint(pt_sld1(P.wf.mask_in + i));
+                wf_history_replay(hist, P.wf.bounce, ps.mask, ps.accu);
+            } else {
+                ps.mask = V3(pt_sld1(P.wf.mask_in + i), pt_sld1(P.wf.mask_in + (size_t)P.wf.cap + i), pt_sld1(P.wf.mask_in + 2 * (size_t)P.wf.cap + i));
+                ps.accu = V3(0.f, 0.f, 0.f);   // this segment's emission only: the running sum lives in the sample buffer
+            }
             ps.depth = P.wf.bounce;
             ps.rng = pt_rng_init(P.wf.hashes[s_idx], (uint64_t)pix);
             ps.rng.n = sn & (PT_REC_MAX_DRAWS - 1u);
@@ -443,7 +499,7 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
             h.tri = 0;
             if (P.tri_matid) h.tri = __float_as_int(P.sc.nodes[h.rec].w);
         }
-        alive = wf_shade_segment<NEE, FIRST, LAST>(P, ps, h, tri_hit, pt_sample_ptr(P, s_idx, (size_t)pix), &req);
+        alive = wf_shade_segment<NEE, FIRST, LAST, HIST>(P, ps, h, tri_hit, pt_sample_ptr(P, s_idx, (size_t)pix), &req, code);
     }
     float2 bound = make_float2(PT_F32_MAX, __int_as_float(-1));
     if (BOUND && alive) bound = wf_sphere_bound(P, ps);
@@ -467,8 +523,8 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
     }
     if (last) {   // every path ends with this bounce (tracer.cu:305)
         if constexpr (FOLD > 0) {
-            // workgroup-scope release / acquire (vmcnt(0) + s_barrier): the emission adds above reach the folding wave; the
-            // block is on one CU, and no other block writes these samples in this launch
+            // workgroup-scope release / acquire (vmcnt(0) + s_barrier): the emission adds above (HIST: the samples' stores) reach the
+            // folding wave; the block is on one CU, and no other block writes these samples in this launch
             __syncthreads();
             wf_fold_region<FOLD>(P, region);
         }
@@ -483,9 +539,12 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
         pt_sst4(P.wf.ray0_out + j, make_float4(ps.o.x, ps.o.y, ps.o.z, ps.d.x));
         pt_sst4(P.wf.ray1_out + j, make_float4(ps.d.y, ps.d.z, __uint_as_float(NEE ? (pix | ((ps.nee_mask & 0xffu) << PT_REC_PIXEL_BITS)) : pix),
                                               __uint_as_float((s_idx << PT_REC_DRAW_BITS) | ps.rng.n | (NEE ? (ps.nee_mask >> 8) << PT_REC_LIGHT_BIT : entry))));
-        pt_sst1(P.wf.mask_out + j, ps.mask.x);
-        pt_sst1(P.wf.mask_out + (size_t)P.wf.cap + j, ps.mask.y);
-        pt_sst1(P.wf.mask_out + 2 * (size_t)P.wf.cap + j, ps.mask.z);
+        if (HIST) pt_sst1(P.wf.mask_out + j, __uint_as_float(pt_hist_push(hist, P.wf.bounce, code)));
+        else {
+            pt_sst1(P.wf.mask_out + j, ps.mask.x);
+            pt_sst1(P.wf.mask_out + (size_t)P.wf.cap + j, ps.mask.y);
+            pt_sst1(P.wf.mask_out + 2 * (size_t)P.wf.cap + j, ps.mask.z);
+        }
         // (slot j held another lane's hit of THIS bounce: every lane of the region has read its own before the rank's barrier)
         if (BOUND) pt_sst2(P.wf.hit + j, bound);   // (walk-free: the bound stands, "no triangle at or before the sphere")
         else if (walk_free) pt_sst2(P.wf.hit + j, make_float2(pt_no_hit().t, __int_as_float(pt_no_hit().rec)));   // what its walk would have written
@@ -496,7 +555,8 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
 // PT_OPT_LAST_ANYHIT: the last shade launch behind k_wf_extend<.., ANY>.  The hit slot holds (ts, sphere) of the segment's nearest
 // sphere, t = 0 when a triangle lies at or before it: a triangle emits nothing (the launch is only chosen when none can), a sphere
 // adds path_last_emission's 0 + mask * emission, neither is the background rule of wf_shade_segment.  No ray, no sphere tests.
-template <bool COUNT, int FOLD>
+// HIST: as k_wf_shade's — the lane holds the path's accu, and every verdict stores the sample once: accu when a triangle is in the way.
+template <bool COUNT, int FOLD, bool HIST = false>
 __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade_last_any(const KParams P) {
     const uint32_t region = blockIdx.x;
     const int n_in = P.wf.cnt_in[region];
@@ -504,20 +564,28 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade_last_any(const KParams P)
         if constexpr (FOLD > 0) wf_fold_region<FOLD>(P, region);
         return;
     }
-    wf_sphere_table();
+    wf_sphere_table<HIST>();
     const size_t i = (size_t)region * PT_REGION + threadIdx.x;
     const bool have = (int)threadIdx.x < n_in;
     bool tri_hit = false;
     if (have) {
         const float4 b = pt_sld4(P.wf.ray1_in + i);
         const float2 hh = pt_sld2(P.wf.hit + i);
-        const v3 mask = V3(pt_sld1(P.wf.mask_in + i), pt_sld1(P.wf.mask_in + (size_t)P.wf.cap + i), pt_sld1(P.wf.mask_in + 2 * (size_t)P.wf.cap + i));
+        v3 mask, accu = V3(0.f, 0.f, 0.f);
+        if (HIST) wf_history_replay(__float_as_uint(pt_sld1(P.wf.mask_in + i)), P.wf.bounce, mask, accu);
+        else mask = V3(pt_sld1(P.wf.mask_in + i), pt_sld1(P.wf.mask_in + (size_t)P.wf.cap + i), pt_sld1(P.wf.mask_in + 2 * (size_t)P.wf.cap + i));
         const uint32_t pix = __float_as_uint(b.z);
         const uint32_t s_idx = (__float_as_uint(b.w) & (P.wf.root_entry ? (1u << PT_REC_ENTRY_SHIFT) - 1u : ~0u)) >> PT_REC_DRAW_BITS;
         float* smp = pt_sample_ptr(P, s_idx, (size_t)pix);
         const int sph = __float_as_int(hh.y);
         tri_hit = hh.x == 0.0f;
-        if (!tri_hit && sph >= 0) {
+        if (HIST) {
+            if (tri_hit) pt_sst3(smp, accu);
+            else if (sph >= 0) {
+                const float* t = (const float*)s_dyn + 11 * sph;
+                pt_sst3(smp, vadd(accu, vadd(V3(0.f, 0.f, 0.f), vmul(mask, V3(t[4], t[5], t[6])))));
+            } else wf_shade_miss_history(smp, accu, mask);
+        } else if (!tri_hit && sph >= 0) {
             const float* t = (const float*)s_dyn + 11 * sph;
             wf_add_emission(smp, vadd(V3(0.f, 0.f, 0.f), vmul(mask, V3(t[4], t[5], t[6]))));
         } else if (!tri_hit) {
@@ -532,7 +600,7 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade_last_any(const KParams P)
         }
     }
     if constexpr (FOLD > 0) {
-        __syncthreads();   // (as in k_wf_shade: the emission adds above reach the folding wave)
+        __syncthreads();   // (as in k_wf_shade: the emission adds, or the stores, above reach the folding wave)
         wf_fold_region<FOLD>(P, region);
     }
 }
@@ -542,11 +610,12 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade_last_any(const KParams P)
 // own hit with the camera ray and RNG state it started the walk with — no hit record written and read back, no camera ray
 // computed twice — and the survivors are packed as k_wf_shade<FIRST> packs them (same records, same order).
 // BOUND: as k_wf_shade's (depth 2: bounce 0's survivors are the last segments).
-template <bool BOUND>
+// HIST: as k_wf_shade's (a path that goes on leaves its first code and no sample colour).
+template <bool BOUND, bool HIST = false>
 __global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet_shade(const KParams P) {
     __shared__ int s_cnt[PT_BLOCK / 64];
     __shared__ int s_cnt_free[PT_BLOCK / 64];
-    wf_sphere_table();
+    wf_sphere_table<HIST>();
     const uint32_t region = blockIdx.x;
     const size_t i = (size_t)region * PT_REGION + threadIdx.x;
     uint32_t s_idx = 0;
@@ -559,10 +628,11 @@ __global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet_shade(const KP
     TravCount tc;
     Hit h = trav_packet_wide<false>(P.sc, ps.o, ps.d, P.cull != 0, have, tc);   // (every lane of the wave: EXEC = all 64)
     bool alive = false;
+    uint32_t code = 0;
     if (have) {
         const bool tri_hit = h.t < PT_F32_MAX;
         if (tri_hit && !P.tri_matid) h.tri = 0;   // (else the walk's id: the record's v0.w, what k_wf_shade reads back)
-        alive = wf_shade_segment<false, true, false>(P, ps, h, tri_hit, pt_sample_ptr(P, s_idx, (size_t)pix), nullptr);
+        alive = wf_shade_segment<false, true, false, HIST>(P, ps, h, tri_hit, pt_sample_ptr(P, s_idx, (size_t)pix), nullptr, code);
     }
     if (P.wf.bounce + 1 >= P.depth) return;   // depth 1
     float2 bound = make_float2(PT_F32_MAX, __int_as_float(-1));
@@ -575,9 +645,12 @@ __global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet_shade(const KP
         const size_t j = (size_t)region * PT_REGION + (size_t)r;
         pt_sst4(P.wf.ray0_out + j, make_float4(ps.o.x, ps.o.y, ps.o.z, ps.d.x));
         pt_sst4(P.wf.ray1_out + j, make_float4(ps.d.y, ps.d.z, __uint_as_float(pix), __uint_as_float((s_idx << PT_REC_DRAW_BITS) | ps.rng.n | entry)));
-        pt_sst1(P.wf.mask_out + j, ps.mask.x);
-        pt_sst1(P.wf.mask_out + (size_t)P.wf.cap + j, ps.mask.y);
-        pt_sst1(P.wf.mask_out + 2 * (size_t)P.wf.cap + j, ps.mask.z);
+        if (HIST) pt_sst1(P.wf.mask_out + j, __uint_as_float(pt_hist_push(0u, 0u, code)));
+        else {
+            pt_sst1(P.wf.mask_out + j, ps.mask.x);
+            pt_sst1(P.wf.mask_out + (size_t)P.wf.cap + j, ps.mask.y);
+            pt_sst1(P.wf.mask_out + 2 * (size_t)P.wf.cap + j, ps.mask.z);
+        }
         if (BOUND) pt_sst2(P.wf.hit + j, bound);
         else if (walk_free) pt_sst2(P.wf.hit + j, make_float2(pt_no_hit().t, __int_as_float(pt_no_hit().rec)));   // (as k_wf_shade)
     }
@@ -601,7 +674,7 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_resolve(const KParams P) {
 
 namespace ptmi {
 
-// sizes of one call's path records: [ray0 x2][ray1 x2][mask x2 (3 planes)][hit][cnt x2][walk x2][hashes][queues][shadow records]
+// sizes of one call's path records: [ray0 x2][ray1 x2][mask x2 (3 planes; PT_OPT_PATH_HISTORY uses the first: the history words)][hit][cnt x2][walk x2][hashes][queues][shadow records]
 struct WaveLayout {
     size_t n_regions, cap, b_ray, b_mask, b_hit, b_cnt, b_hash, q_words, b_q, b_nee, need;
     bool nee;
@@ -711,6 +784,10 @@ struct WavePlan {
     // no code, and ray1.w's top bit is taken) and when spp fits the narrowed sample field; every other call keeps the plain record.
     // Instrumented launches: with the value 2 only.
     bool root_entry;
+    // PT_OPT_PATH_HISTORY: the records carry the objects the path has hit (the history word of pt_kernels.h) in place of its mask, a
+    // shade lane rebuilds mask and accu from it, and a path's sample colour is written once, by the lane it ends in (path_history_holds).
+    // Instrumented launches: with the value 2 only.
+    bool history;
     WaveExtend extend(uint32_t b, uint32_t depth) const {
         if (b == 0) return fuse_first ? EXT_FUSED : packet ? EXT_PACKET : EXT_FIRST;
         return anyhit && b + 1 == depth ? EXT_ANY : EXT_CLOSEST;
@@ -734,11 +811,12 @@ static WavePlan wave_plan(const pt_ctx* c, const KParams& P, const LaunchCfg& L,
     p.anyhit = (L.count ? c->opt_last_anyhit == 2 : c->opt_last_anyhit >= 1) && P.depth >= 2 && !nee && !P.tri_matid && tri_dark &&
                P.sc.n_spheres <= PT_KSPHERES && !c->tree.records_woop;
     p.root_cull = L.count ? c->opt_root_cull == 2 : c->opt_root_cull >= 1;
+    p.history = (L.count ? c->opt_path_history == 2 : c->opt_path_history >= 1) && path_history_holds(P);
     p.root_entry = p.root_cull && !nee && P.spp < PT_REC_MAX_SAMPLES_ENTRY && (L.count ? c->opt_root_entry == 2 : c->opt_root_entry >= 1);
     return p;
 }
 
-constexpr size_t WF_LDS_SHADE = 15 * PT_KSPHERES * 4;   // wf_sphere_table
+constexpr size_t WF_LDS_SHADE = (15 * PT_KSPHERES + 6) * 4;   // wf_sphere_table, with the triangle material's row
 // the extend stage's persistent grid (resident blocks, at most `blocks_per_cu` per CU) over the records of Q
 static hipError_t launch_extend(const WavePlan& p, WaveExtend kind, const KParams& Q, const LaunchCfg& L, int blocks_per_cu, hipStream_t s) {
     auto plain = [&](auto kernel, size_t n_blk, size_t lds) {
@@ -747,7 +825,9 @@ static hipError_t launch_extend(const WavePlan& p, WaveExtend kind, const KParam
     };
     const size_t n_reg = (size_t)Q.wf.n_regions;
     if (kind == EXT_FUSED)   // (BOUND at depth 2: bounce 0's survivors are the last segments)
-        return p.anyhit && Q.depth == 2 ? plain(k_wf_extend_packet_shade<true>, n_reg, WF_LDS_SHADE) : plain(k_wf_extend_packet_shade<false>, n_reg, WF_LDS_SHADE);
+        return with_bool(p.history, [&](auto hist) {
+            return p.anyhit && Q.depth == 2 ? plain(k_wf_extend_packet_shade<true, hist()>, n_reg, WF_LDS_SHADE) : plain(k_wf_extend_packet_shade<false, hist()>, n_reg, WF_LDS_SHADE);
+        });
     if (kind == EXT_PACKET) {   // one block per region (4 groups); instrumented: the resident grid, 8 blocks per CU
 #ifdef PT_PACKET_RESIDENT_GRID   // experiment (tools/build_variant.sh): the product launch on the resident grid too
         const bool resident = true;
@@ -779,18 +859,23 @@ static hipError_t launch_shade(const WavePlan& p, WaveShade kind, bool first, co
         hipLaunchKernelGGL(kernel, dim3((unsigned)Q.wf.n_regions), dim3(PT_BLOCK), WF_LDS_SHADE, s, Q);
         return hipGetLastError();
     };
-    if (p.count) {   // (never SHADE_LAST, never a fold)
-        if (kind == SHADE_LAST_ANY) return go(k_wf_shade_last_any<true, 0>);
+    if (p.nee) return with_bool(p.count, [&](auto count) {   // (never SHADE_BOUND, SHADE_LAST or a fold; never a history)
+        return with_bool(first, [&](auto f) { return go(k_wf_shade<count(), true, f()>); });
+    });
+    return with_bool(p.history, [&](auto hist) {
+        if (p.count) {   // (never SHADE_LAST, never a fold)
+            if (kind == SHADE_LAST_ANY) return go(k_wf_shade_last_any<true, 0, hist()>);
+            return with_bool(first, [&](auto f) {
+                if (kind == SHADE_BOUND) return go(k_wf_shade<true, false, f(), false, 0, true, hist()>);
+                return go(k_wf_shade<true, false, f(), false, 0, false, hist()>);
+            });
+        }
+        if (kind == SHADE_LAST_ANY) return with_int<4, 2, 1, 0>(p.fold_lp, [&](auto lp) { return go(k_wf_shade_last_any<false, lp(), hist()>); });
+        if (kind == SHADE_LAST) return with_int<4, 2, 1, 0>(p.fold_lp, [&](auto lp) { return go(k_wf_shade<false, false, false, true, lp(), false, hist()>); });
         return with_bool(first, [&](auto f) {
-            if (kind == SHADE_BOUND) return go(k_wf_shade<true, false, f(), false, 0, true>);
-            return p.nee ? go(k_wf_shade<true, true, f()>) : go(k_wf_shade<true, false, f()>);
+            if (kind == SHADE_BOUND) return go(k_wf_shade<false, false, f(), false, 0, true, hist()>);
+            return go(k_wf_shade<false, false, f(), false, 0, false, hist()>);
         });
-    }
-    if (kind == SHADE_LAST_ANY) return with_int<4, 2, 1, 0>(p.fold_lp, [&](auto lp) { return go(k_wf_shade_last_any<false, lp()>); });
-    if (kind == SHADE_LAST) return with_int<4, 2, 1, 0>(p.fold_lp, [&](auto lp) { return go(k_wf_shade<false, false, false, true, lp()>); });
-    return with_bool(first, [&](auto f) {
-        if (kind == SHADE_BOUND) return go(k_wf_shade<false, false, f(), false, 0, true>);
-        return p.nee ? go(k_wf_shade<false, true, f()>) : go(k_wf_shade<false, false, f()>);
     });
 }
 

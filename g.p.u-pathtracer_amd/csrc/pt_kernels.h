@@ -45,6 +45,7 @@ struct KScene {
 //   ray0[i] = (o.x, o.y, o.z, d.x)   ray1[i] = (d.y, d.z, bits(pixel), bits(sample << PT_REC_DRAW_BITS | rng draws))
 //             (PT_OPT_ROOT_ENTRY: ray1.w = bits(entry code << PT_REC_ENTRY_SHIFT | sample << PT_REC_DRAW_BITS | rng draws), below)
 //   mask    = three planes [cap] (x, y, z), not stored for the first bounce (1, 1, 1)
+//             (PT_OPT_PATH_HISTORY: plane 0 = the path's history word, below; the sample colour is then written once, where the path ends)
 //   hit[i]  = (t, bits(float4 index of the winning record)); t = F32_MAX: no triangle
 // PT_FLAG_NEE: the sphere bits of nee_mask ride above the pixel (ray1.z), its triangle-light bit above the sample (ray1.w).
 // The stages of pt_k_wave.hip pack and unpack the record with these; the limits wave_layout and pt_render check follow from them:
@@ -91,6 +92,27 @@ constexpr bool pt_entry_round_trips() {
     return seen == 64u;
 }
 static_assert(pt_entry_round_trips(), "the entry code of PT_OPT_ROOT_ENTRY");
+// PT_OPT_PATH_HISTORY (WavePlan::history): plane 0 of `mask` holds the path's HISTORY WORD instead of mask.x, and the other two planes are
+// neither read nor written.  The word has PT_HIST_BITS per finished bounce, bounce b's at bits 4b .. 4b + 3: the code of the object that
+// bounce ended on, 0-7 = sphere k (of the kernel-argument block), PT_HIST_TRI = a triangle (the call's one triangle material).  32 bits
+// hold the 8 bounces a path of depth 9 survives.  Mask and gathered light are functions of it (wf_history_replay, pt_k_wave.hip).
+constexpr uint32_t PT_HIST_BITS = 4, PT_HIST_TRI = 8, PT_HIST_MAX_DEPTH = 32 / PT_HIST_BITS + 1;
+constexpr uint32_t pt_hist_push(uint32_t word, uint32_t bounce, uint32_t code) { return word | (code << (PT_HIST_BITS * bounce)); }
+constexpr uint32_t pt_hist_code(uint32_t word, uint32_t bounce) { return (word >> (PT_HIST_BITS * bounce)) & ((1u << PT_HIST_BITS) - 1u); }
+// every code comes back from every bounce's field, whatever the other fields hold, and the lower fields stay what they were
+constexpr bool pt_hist_round_trips() {
+    for (uint32_t b = 0; b + 1 < PT_HIST_MAX_DEPTH; b++)
+        for (uint32_t code = 0; code <= PT_HIST_TRI; code++) {
+            uint32_t w = 0;
+            for (uint32_t k = 0; k < b; k++) w = pt_hist_push(w, k, (code + k) % (PT_HIST_TRI + 1u));
+            w = pt_hist_push(w, b, code);
+            if (pt_hist_code(w, b) != code) return false;
+            for (uint32_t k = 0; k < b; k++)
+                if (pt_hist_code(w, k) != (code + k) % (PT_HIST_TRI + 1u)) return false;
+        }
+    return PT_HIST_TRI >= PT_KSPHERES && PT_HIST_TRI < (1u << PT_HIST_BITS);
+}
+static_assert(pt_hist_round_trips(), "the history word of PT_OPT_PATH_HISTORY");
 struct KWave {
     const float4* __restrict__ ray0_in;
     const float4* __restrict__ ray1_in;

@@ -107,6 +107,7 @@ static const OptionRow OPTIONS[] = {
     {PT_OPT_LAST_ANYHIT, &pt_ctx::opt_last_anyhit, OptionRow::RANGE, {0, 2}, PT_ERR_INVALID, "pt_set_option: last any-hit must be 0 (off), 1 (product launches) or 2 (instrumented launches too)"},
     {PT_OPT_ROOT_CULL, &pt_ctx::opt_root_cull, OptionRow::RANGE, {0, 2}, PT_ERR_INVALID, "pt_set_option: root cull must be 0 (off), 1 (product launches) or 2 (instrumented launches too)"},
     {PT_OPT_ROOT_ENTRY, &pt_ctx::opt_root_entry, OptionRow::RANGE, {0, 2}, PT_ERR_INVALID, "pt_set_option: root entry must be 0 (off), 1 (product launches) or 2 (instrumented launches too)"},
+    {PT_OPT_PATH_HISTORY, &pt_ctx::opt_path_history, OptionRow::RANGE, {0, 2}, PT_ERR_INVALID, "pt_set_option: path history must be 0 (off), 1 (product launches) or 2 (instrumented launches too)"},
 };
 }  // namespace ptmi
 

@@ -235,7 +235,7 @@ enum {
                                  instrumented (PT_OPT_COUNTERS) launches too: pt_get_counters then lacks one node visit per such ray
                                  (`rays` still counts them) and pt_get_wave_stats [10] is their number; 0 = every survivor is
                                  queued.  With 0 or 1 the counters are those of the full queue.  Same images                     */
-    PT_OPT_ROOT_ENTRY = 33    /* PT_KERNEL_WAVEFRONT with PT_OPT_ROOT_CULL: the shade lane keeps the rest of that node step as well —
+    PT_OPT_ROOT_ENTRY = 33,   /* PT_KERNEL_WAVEFRONT with PT_OPT_ROOT_CULL: the shade lane keeps the rest of that node step as well —
                                  which of the root's four children the new ray enters, nearest first — as an 8-bit code in the
                                  record's sample word, and the extend launches of the later bounces start every walk behind the
                                  root: the far children on the stack, the nearest one as the first item, without fetching or testing
@@ -246,6 +246,15 @@ enum {
                                  extend launches of bounces >= 1 drew (pt_get_wave_stats [7] is their number while bounce 0 is the
                                  packet walk, PT_OPT_FIRST_WALK 1); 0 = every walk starts at the root.
                                  With 0 or 1 the counters are unchanged.  Same images                                           */
+    PT_OPT_PATH_HISTORY = 34  /* PT_KERNEL_WAVEFRONT: a path's record carries WHICH objects the path has hit so far — four bits per
+                                 bounce, sphere 0-7 or "a triangle" — in one word instead of its mask as three floats; a shade lane
+                                 rebuilds the mask and the light gathered so far from that word with the arithmetic the path itself
+                                 would have done, and the path's sample colour is written once, by the lane the path ends in, not
+                                 added to at every bounce.  Holds for calls whose mask and gathered light depend on nothing else: no
+                                 PT_FLAG_NEE, PT_FLAG_RUSSIAN_ROULETTE or PT_FLAG_RR_CPU_TRACER, no per-triangle materials, at most
+                                 8 spheres, no PT_MAT_REFR triangle material or sphere, depth <= 9; any other call keeps the three
+                                 mask planes and the in-place adds.  1 (default) = product launches do so; 2 = instrumented
+                                 (PT_OPT_COUNTERS) launches too; 0 = off.  No counter changes under any value.  Same images         */
 };
 
 /* CamInfo, GpuPathTracer/CpuStructs.hpp:19-28 (pitch/yaw/dirty/bias/enabled are host-only
