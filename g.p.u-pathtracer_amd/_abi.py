@@ -104,6 +104,7 @@ OPT_FIRST_WALK, OPT_PACKET_STACK, OPT_FUSE_STAGES, OPT_LAST_ANYHIT = 26, 27, 28,
 OPT_ROOT_CULL = 30
 OPT_ROOT_ENTRY = 33   # (not re-exported by the package: gpu_pathtracer_amd._abi.OPT_ROOT_ENTRY)
 OPT_PATH_HISTORY = 34   # (not re-exported either)
+OPT_ENV_LIGHT = 35   # (not re-exported either: gpu_pathtracer_amd._abi.OPT_ENV_LIGHT, or upload_environment(light=True))
 
 # every symbol include/ptmi.h declares: (name, restype, argtypes)
 _vp, _sz, _i, _u32 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32
@@ -132,6 +133,9 @@ PTMI_SYMBOLS = [
     ("pt_render_rays", _i, [_vp, _vp, _sz, C.c_uint64, _vp, C.POINTER(Params), _u32, _i]),
     ("pt_upload_environment", _i, [_vp, C.POINTER(Environment), _vp]),
     ("pt_eval_environment", _i, [_vp, _vp, _sz, _vp]),
+    ("pt_environment_is_light", _i, [_vp, C.POINTER(_i)]),
+    ("pt_sample_environment", _i, [_vp, _vp, _sz, _vp, _vp]),
+    ("pt_environment_pdf", _i, [_vp, _vp, _sz, _vp]),
     ("pt_render_aux", _i, [_vp, C.POINTER(Camera), C.POINTER(Params), _vp, _vp, _vp, _vp]),
     ("pt_denoise", _i, [_vp, C.POINTER(DenoiseParams), _vp, _vp, _vp, _vp, _vp, _vp]),
     ("pt_temporal", _i, [_vp, C.POINTER(TemporalParams), C.POINTER(Camera), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -78,7 +78,8 @@ struct pt_ctx {
     uint64_t lights_gen = 0;
     int n_spheres = 0;
     pt_sphere_d h_spheres[PT_KSPHERES];   // host copy of the first spheres for the kernel-argument block
-    // pt_upload_environment (pt_env.hip): the map as the kernels get it, env.texels the context's own device copy (nullptr: no map);
+    // pt_upload_environment (pt_env.hip): the map as the kernels get it, env.texels the context's own device copy (nullptr: no map),
+    // env.cx its sampling tables' (nullptr: the map is no light; PT_OPT_ENV_LIGHT);
     // env_gen counts the uploads and clears, part of PT_KERNEL_AUTO's key like scene_gen
     KEnv env = {};
     uint64_t env_gen = 0;
@@ -118,6 +119,7 @@ struct pt_ctx {
     int opt_last_anyhit = 1;     // the last segment as a sphere-bounded any-hit query: 0 off, 1 product launches, 2 instrumented too (PT_OPT_LAST_ANYHIT)
     int opt_root_cull = 1;       // new rays the root node step turns away stay out of the extend queue: 0 off, 1 product launches, 2 instrumented too (PT_OPT_ROOT_CULL)
     int opt_root_entry = 1;      // ... and the walkers' records carry the root step's result, the extend launches start below the root: 0 off, 1 product launches, 2 instrumented too (PT_OPT_ROOT_ENTRY)
+    int opt_env_light = 0;       // the next pt_upload_environment builds the map's sampling tables: under PT_FLAG_NEE it is a light (PT_OPT_ENV_LIGHT)
     int opt_path_history = 1;    // the records carry the objects a path has hit instead of its mask, its sample colour is written once: 0 off, 1 product launches, 2 instrumented too (PT_OPT_PATH_HISTORY)
     // PT_KERNEL_AUTO: which stage layout is faster depends on the workload (long paths and many samples per call:
     // the stage-split pipeline; short paths or few samples: the persistent kernel), so the first FOUR calls of a
@@ -329,7 +331,8 @@ struct LaunchCfg {
     int work_blocks;   // persistent grid cap: blocks that have work at all
     int n_cu;
     bool moments;      // the call keeps luminance moments (pt_render_moments): they are the separate fold launch's job
-    bool env;          // the context has an environment map: the instantiations whose miss looks it up (pt_env.h)
+    int env;           // 1: the context has an environment map: the instantiations whose miss looks it up (pt_env.h); 2: the map is a
+                       // light too (PT_OPT_ENV_LIGHT): the megakernel's instantiation whose NEE branch draws from it; 0: no map
 };
 hipError_t launch_mega(const LaunchCfg& L, const KParams& P, hipStream_t st);        // pt_k_mega.hip
 hipError_t launch_rays(const KScene& sc, size_t lds, const float4* rays, size_t n, int cull, float* t_out, int* tri_out,

@@ -2,6 +2,9 @@
 // pt_eval_environment answers for a caller's rays.  One lookup for both (include/ptmi.h states it): the kernels
 // that shade in the lane that walked call it from path_shade_hit's miss branch (pt_shade.h), k_eval_environment (pt_env.hip) for
 // every ray of a batch.  Included by pt_kernels.h in front of KParams (KEnv is its last member) and by pt_shade.h.
+// A map uploaded under PT_OPT_ENV_LIGHT carries a sampling distribution too: pt_env_draw turns two uniform
+// numbers into a direction and its density, pt_env_pdf answers the density of a given direction — path_shade_hit's NEE branch and
+// the batch kernels of pt_sample_environment / pt_environment_pdf (pt_env.hip) share them.
 #pragma once
 #include "pt_math.h"
 
@@ -14,6 +17,12 @@ struct KEnv {
     float kx, ky, hx, hy;
     int filter;   // PT_ENV_NEAREST 0, PT_ENV_BILINEAR 1
     int _pad;
+    // PT_OPT_ENV_LIGHT: the distribution the map is sampled by as a light, built on the host at upload (include/ptmi.h states the
+    // rule); nullptr = the map is no light.  cx: float[H][W + 1], per row the CDF over the columns; cy: float[H + 1], the CDF over
+    // the rows; zs: float[H + 1], sin(latitude) of the row edges.  One allocation, cx its start.
+    const float* __restrict__ cx;
+    const float* __restrict__ cy;
+    const float* __restrict__ zs;
 };
 
 __device__ __forceinline__ bool pt_env_finite(float v) { return fabsf(v) <= PT_F32_MAX; }   // false for a NaN
@@ -65,4 +74,71 @@ static __device__ __noinline__ v3 pt_env_lookup(pt_kenv& E, v3 d) {
     const float4 t00 = tex[r0 + c0], t01 = tex[r0 + c1], t10 = tex[r1 + c0], t11 = tex[r1 + c1];
     const v3 lo = pt_env_lerp(t00, t01, wx), hi = pt_env_lerp(t10, t11, wx);
     return V3(lo.x + wy * (hi.x - lo.x), lo.y + wy * (hi.y - lo.y), lo.z + wy * (hi.z - lo.z));
+}
+
+// ---- the map as a light (PT_OPT_ENV_LIGHT).  binary32, plain * and +.
+
+// the largest i in 0 .. n - 1 with cdf[i] <= u (cdf[0] = 0 <= u): an entry of zero width is never the answer
+__device__ __forceinline__ int pt_env_search(const float* __restrict__ cdf, int n, float u) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (cdf[mid] <= u) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// the density per steradian of texel (x, y), constant over it: from the CDF differences, so that it is the density of what
+// pt_env_draw draws whatever the rounding of the tables.  A texel that is never drawn has density 0 (a row near a pole of a tall
+// map can have dz == 0 in binary32; its py is 0 then as well)
+__device__ __forceinline__ float pt_env_texel_pdf(float py, float px, float kx, float dz) {
+    const float p = py * px;
+    return p > 0.0f ? (p * kx) / dz : 0.0f;
+}
+
+// (u1, u2) in [0, 1) -> (direction, density): the row by u1, the column within it by u2, a point uniform in solid angle inside
+// the texel.  Only called for a map with tables (E.cx != nullptr).  __noinline__ for pt_env_lookup's reason.
+static __device__ __noinline__ float4 pt_env_draw(pt_kenv& E, float u1, float u2) {
+    const int W = E.W, H = E.H;
+    const float* cy = E.cy;
+    const float* zs = E.zs;
+    const int y = pt_env_search(cy, H, u1);
+    const float cy0 = cy[y], py = cy[y + 1] - cy0;
+    const float v1 = fminf((u1 - cy0) / py, 0x1.fffffep-1f);
+    const float* cx = E.cx + (size_t)y * (size_t)(W + 1);
+    const int x = pt_env_search(cx, W, u2);
+    const float cx0 = cx[x], px = cx[x + 1] - cx0;
+    const float v2 = fminf((u2 - cx0) / px, 0x1.fffffep-1f);
+    const float z0 = zs[y], dz = zs[y + 1] - z0;
+    const float z = z0 + v1 * dz;
+    const float r = sqrtf(fmaxf(0.0f, 1.0f - z * z));
+    const float lon = ((((float)x - 0.5f) + v2) - E.hx) / E.kx;
+    const float cl = r * cosf(lon), sl = r * sinf(lon);
+    float4 o;
+    o.x = (E.front[0] * cl + E.right[0] * sl) + E.up[0] * z;
+    o.y = (E.front[1] * cl + E.right[1] * sl) + E.up[1] * z;
+    o.z = (E.front[2] * cl + E.right[2] * sl) + E.up[2] * z;
+    o.w = pt_env_texel_pdf(py, px, E.kx, dz);
+    return o;
+}
+
+// the density pt_env_draw has along direction d (any length): the texel a nearest lookup of d picks, the same formula; 0 for a
+// direction the lookup calls invalid.  Only called for a map with tables.
+static __device__ __noinline__ float pt_env_pdf(pt_kenv& E, v3 d) {
+    const float a = vdot(d, V3(E.front[0], E.front[1], E.front[2]));
+    const float b = vdot(d, V3(E.right[0], E.right[1], E.right[2]));
+    const float c = vdot(d, V3(E.up[0], E.up[1], E.up[2]));
+    if (!(pt_env_finite(a) && pt_env_finite(b) && pt_env_finite(c)) || (a == 0.0f && b == 0.0f && c == 0.0f)) return 0.0f;
+    const float lon = atan2f(b, a);
+    const float lat = atan2f(c, sqrtf(a * a + b * b));
+    const float fx = lon * E.kx + E.hx;
+    const float fy = lat * E.ky + E.hy;
+    const int W = E.W, H = E.H;
+    int x = (int)floorf(fx + 0.5f);
+    if (x >= W) x -= W;
+    if (x < 0) x += W;
+    x = min(max(x, 0), W - 1);
+    const int y = min(max((int)floorf(fy + 0.5f), 0), H - 1);
+    const float* cx = E.cx + (size_t)y * (size_t)(W + 1);
+    return pt_env_texel_pdf(E.cy[y + 1] - E.cy[y], cx[x + 1] - cx[x], E.kx, E.zs[y + 1] - E.zs[y]);
 }

@@ -7,7 +7,7 @@
 // OCC = waves per SIMD the register allocator must leave room for (4 / 6 / 8)
 // ALG = 0 while-while walk (Aila-Laine), 1 unified-step walk, 2 wide (4-way quantised) walk,
 //       3 wide walk over Woop records
-template <bool COUNT, int OCC, int LSTK, int ALG, bool ENV>
+template <bool COUNT, int OCC, int LSTK, int ALG, int ENV>
 __global__ void __launch_bounds__(PT_BLOCK, OCC) k_trace_mega_bvh2(const KParams P) {
     float4* s_top = s_dyn;
     lds_load_top<PT_BLOCK>(P.sc, s_top);
@@ -87,7 +87,7 @@ namespace ptmi {
 hipError_t launch_mega(const LaunchCfg& L, const KParams& P, hipStream_t st) {
     auto go = [&](auto count, auto occ, auto lstk) {
         return with_int<2, 1, 0>(std::min(L.walk, 2), [&](auto alg) {
-            return with_bool(L.env, [&](auto env) {   // a map on the context: the instantiation that looks it up
+            return with_int<2, 1, 0>(L.env, [&](auto env) {   // a map on the context: the instantiation that looks it up (1), and samples it under PT_FLAG_NEE (2)
                 const auto kernel = k_trace_mega_bvh2<count(), occ(), lstk(), alg(), env()>;
                 const hipError_t e = allow_lds(kernel, L.lds);
                 if (e != hipSuccess) return e;

@@ -253,7 +253,7 @@ namespace ptmi {
 hipError_t launch_persist(const LaunchCfg& L, const KParams& P, hipStream_t st) {
     return with_bool(L.count, [&](auto count) {
         auto go = [&](auto occ, auto lstk, auto alg) {
-            return with_bool(L.env, [&](auto env) {   // a map on the context: the instantiation that looks it up
+            return with_bool(L.env != 0, [&](auto env) {   // a map on the context: the instantiation that looks it up (this kernel runs no NEE: a light or not)
                 return launch_resident(k_trace_persist_bvh2<count(), occ(), lstk(), alg(), env()>, L.lds, INT_MAX, L.n_cu,
                                        (size_t)std::max(1, L.work_blocks), st, P);
             });

@@ -39,7 +39,7 @@ __device__ __forceinline__ bool rays_finite(v3 a) {
 }
 
 // NEE: the lane can walk the shadow ray path_shade asks for (PT_FLAG_NEE) before it goes on with the path
-template <bool NEE, int OCC, int LSTK, int ALG, bool ENV>
+template <bool NEE, int OCC, int LSTK, int ALG, int ENV>
 __global__ void __launch_bounds__(PT_BLOCK, OCC) k_render_rays(const KParams P, const KRays R) {
     // sphere attributes + centres for the shading code (see path_shade): the table of k_trace_persist_bvh2, filled from the device
     // array (the first PT_KSPHERES spheres there are the ones in the kernel arguments; rows past n_spheres are never read)
@@ -226,14 +226,16 @@ static KRays rays_args(const RaysCall& r) { return KRays{(const float4*)r.rays, 
 
 // Instantiated: the wide walk (2; 3 = Woop records) and the unified binary walk (1: trees too deep for the wide one, PT_OPT_WALK 0 / 1),
 // each at 6 waves per SIMD without and at 4 with the shadow-ray state, 16 stack entries per lane in LDS; each of those without and
-// with the environment-map lookup (ENV).
+// with the environment-map lookup (ENV 1), the NEE ones also with the draw from a map that is a light (ENV 2).
 hipError_t launch_render_rays(const pt_ctx* c, int walk, bool nee, size_t lds, int work_blocks, const KParams& P, const RaysCall& r) {
     const KRays R = rays_args(r);
     return with_bool(nee, [&](auto n) {
         return with_int<3, 2, 1>(walk, [&](auto alg) {
             constexpr int OCC = n() ? 4 : 6;
-            return with_bool(c->env.texels != nullptr, [&](auto env) {   // a map on the context: the instantiation that looks it up
-                return launch_resident(k_render_rays<n(), OCC, 16, alg(), env()>, lds, INT_MAX, c->n_cu, (size_t)std::max(1, work_blocks), c->stream, P, R);
+            // a map on the context: the instantiation that looks it up (1); a map that is a light, in a call that runs NEE: the one that samples it (2)
+            return with_int<2, 1, 0>(c->env.texels ? (c->env.cx ? 2 : 1) : 0, [&](auto env) {
+                constexpr int ENV = (env() == 2 && !n()) ? 1 : env();
+                return launch_resident(k_render_rays<n(), OCC, 16, alg(), ENV>, lds, INT_MAX, c->n_cu, (size_t)std::max(1, work_blocks), c->stream, P, R);
             });
         });
     });

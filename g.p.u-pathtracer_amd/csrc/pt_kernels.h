@@ -257,7 +257,7 @@ static_assert(PT_CNT_WAVE == sizeof(pt_counters) / sizeof(uint64_t) && PT_CNT_N 
 #include "pt_walks.h"
 #include "pt_shade.h"
 
-template <bool COUNT, int ALG, bool ENV, class STK>
+template <bool COUNT, int ALG, int ENV, class STK>
 __device__ __forceinline__ v3 pt_get_sample(const KParams& P, int px, int py, uint64_t pix, uint64_t frame,
                                             STK& stk, const float4* __restrict__ s_top, TravCount& tc,
                                             uint32_t& n_rays, uint32_t& n_hits) {

@@ -134,8 +134,10 @@ __device__ __forceinline__ SceneHit pt_closest_sphere(const KParams& P, v3 o, v3
 // ENV: a segment that hits nothing looks the context's environment map up along its direction when one is set
 // (pt_upload_environment, pt_env.h) — the ENV instantiations of the kernels that shade in the lane that walked (path_shade), which
 // the launchers pick when the context has a map.  The stage-split pipeline's shade stage keeps ENV = false: it never runs with a
-// map on the context (plan_call).  ENV = false compiles to the code there was before maps existed.
-template <bool ENV = false>
+// map on the context (plan_call).  ENV = 0 compiles to the code there was before maps existed, 1 to the lookup in the miss branch
+// alone; 2, for a map with sampling tables (PT_OPT_ENV_LIGHT), also draws from them in the NEE branch: the kernels that run NEE
+// with a map have that instantiation beside the other two, so that a map that is no light costs what it did.
+template <int ENV = 0>
 __device__ __forceinline__ bool path_shade_hit(const KParams& P, PathState& ps, const Hit& h, const SceneHit& sh, v3 tri_n, v3& col_out, int sph_tab = -1,
                                                NeeReq* nee = nullptr) {
     if (nee) nee->want = false;
@@ -184,11 +186,15 @@ __device__ __forceinline__ bool path_shade_hit(const KParams& P, PathState& ps, 
         }
     } else {
         col_out = V3(K.bk[0], K.bk[1], K.bk[2]);  // tracer.cu:140-142: unmasked background
-        if (ENV && PT_KENV(K).texels) col_out = pt_env_lookup(PT_KENV(K), d);   // extension: the map instead of the constant, by the same rules
+        // extension: the map instead of the constant, by the same rules; nothing where the DIFF hit before sampled the map as a light
+        // (nee_mask bit 9): its shadow ray has gathered it
+        if (ENV == 1 && PT_KENV(K).texels) col_out = pt_env_lookup(PT_KENV(K), d);
+        if (ENV == 2 && PT_KENV(K).texels) col_out = (ps.nee_mask & 0x200u) ? V3(0.f, 0.f, 0.f) : pt_env_lookup(PT_KENV(K), d);
         if (K.flags & PT_FLAG_MISS_KEEPS_PATH) col_out = vadd(accu, vmul(mask, col_out));  // extension
         return true;
     }
     // not already gathered by a shadow ray (PT_FLAG_NEE): bits 0-7 the spheres that were eligible, bit 8 the emissive triangles
+    // (bit 9, the environment map as a light, is the miss branch's above)
     if (!(geom == 1 && sph_id < 8 && ((ps.nee_mask >> sph_id) & 1u)) && !(geom == 0 && (ps.nee_mask & 0x100u)))
         accu = vadd(accu, vmul(mask, emit));
     ps.nee_mask = 0;
@@ -241,13 +247,41 @@ __device__ __forceinline__ bool path_shade_hit(const KParams& P, PathState& ps, 
                     if (lit && vdot(w, w) > (kp[11 * i + 3] * kp[11 * i + 3]) * 1.001f) { el |= 1u << i; n_el++; }
                 }
             }
-            const int n_tl = K.n_tri_lights, n_all = n_el + n_tl;
-            ps.nee_mask = el | (n_tl > 0 ? 0x100u : 0u);
+            // ENV == 2: a map with sampling tables (PT_OPT_ENV_LIGHT) is one more light, the last of the pick — where a miss keeps the
+            // path's light (without PT_FLAG_MISS_KEEPS_PATH a miss returns the bare value and the shadow rays' light would be lost),
+            // and not at the path's last hit: the bounce ray that would have gathered the map from there is never traced, so that
+            // light lies beyond the call's depth and the call's expectation is the same with and without the tables
+            bool env_light = false;
+            if constexpr (ENV == 2) env_light = (K.flags & PT_FLAG_MISS_KEEPS_PATH) != 0 && ps.depth + 1 < P.depth;
+            const int n_tl = K.n_tri_lights, n_all = n_el + n_tl + (env_light ? 1 : 0);
+            ps.nee_mask = el | (n_tl > 0 ? 0x100u : 0u) | (env_light ? 0x200u : 0u);
             if (n_all > 0) {
                 const float u0 = pt_rng_next(rng), u1 = pt_rng_next(rng), u2 = pt_rng_next(rng);
                 int pick = (int)(u0 * (float)n_all);
                 if (pick > n_all - 1) pick = n_all - 1;
-                if (pick >= n_el) {
+                if (env_light && pick == n_all - 1) {
+                    if constexpr (ENV == 2) {
+                        // the map: a direction drawn from its tables (u1 the row, u2 the column), any sphere in the way blocks it
+                        // as it would end the bounce ray; contribution = mask * L * cos(surface) * lights / (pi * pdf)
+                        const float4 s = pt_env_draw(PT_KENV(K), u1, u2);
+                        const v3 l = V3(s.x, s.y, s.z);
+                        const float cosl = vdot(nl, l);
+                        bool blocked = !(cosl > 0.0f) || !(s.w > 0.0f);
+                        for (int j = 0; j < P.sc.n_spheres; j++) {
+                            const pt_sphere_d& sj = P.sc.spheres[j];
+                            const float ts = pt_sphere_intersect(sj.px, sj.py, sj.pz, sj.rad, hitpos, l);
+                            if (ts != 0.0f && ts > 0.01f) blocked = true;
+                        }
+                        if (!blocked) {
+                            const float k = (cosl * (float)n_all) / (3.14159274f * s.w);
+                            nee->want = true;
+                            nee->o = hitpos;
+                            nee->d = l;
+                            nee->t_max = PT_F32_MAX;
+                            nee->contrib = vscale(vmul(mask, pt_env_lookup(PT_KENV(K), l)), k);
+                        }
+                    }
+                } else if (pick >= n_el) {
                     // an emissive triangle: a point uniform on it; the faces a path can hit emit (see `blocked`).  contribution = mask * Le * cos(surface) * cos(light) * area / (pi * dist^2) * lights
                     const float4* tl = P.tri_lights + 3 * (size_t)(pick - n_el);
                     const float4 t0 = tl[0], t1 = tl[1], t2 = tl[2];
@@ -415,8 +449,9 @@ __device__ __forceinline__ v3 path_last_emission(const KParams& P, const PathSta
 }
 
 // spheres + shading in one go (the kernels that shade in the lane that walked).  ENV: the instantiation for a context with an
-// environment map; without one the kernels run the ENV = false instantiations, whose code is what it was before maps existed
-template <bool ENV>
+// environment map (1; 2 when it is a light too); without one the kernels run the ENV = 0 instantiations, whose code is what it
+// was before maps existed
+template <int ENV>
 __device__ __forceinline__ bool path_shade(const KParams& P, PathState& ps, const Hit& h, v3& col_out, int sph_tab = -1, NeeReq* nee = nullptr) {
     // the triangle's normal is asked for NOW so that its latency hides behind the sphere tests
     v3 tri_n = V3(0.f, 0.f, 0.f);

@@ -68,7 +68,7 @@ int stage_mark(pt_ctx* c, int kind) {
 }
 
 // pt_set_option's table, one row per option: the member it sets, the values it takes and what a refused value is answered with.
-// TRI_TEST, LEAF_MAX and OPTIMIZE take effect at the next pt_upload_bvh.
+// TRI_TEST, LEAF_MAX and OPTIMIZE take effect at the next pt_upload_bvh, ENV_LIGHT at the next pt_upload_environment.
 struct OptionRow {
     enum Rule { FLAG, RANGE, SET };   // any value, kept as 0 / 1;  v[0]..v[1];  one of v[0..3] (a shorter set repeats its last value)
     int id;
@@ -107,6 +107,7 @@ static const OptionRow OPTIONS[] = {
     {PT_OPT_LAST_ANYHIT, &pt_ctx::opt_last_anyhit, OptionRow::RANGE, {0, 2}, PT_ERR_INVALID, "pt_set_option: last any-hit must be 0 (off), 1 (product launches) or 2 (instrumented launches too)"},
     {PT_OPT_ROOT_CULL, &pt_ctx::opt_root_cull, OptionRow::RANGE, {0, 2}, PT_ERR_INVALID, "pt_set_option: root cull must be 0 (off), 1 (product launches) or 2 (instrumented launches too)"},
     {PT_OPT_ROOT_ENTRY, &pt_ctx::opt_root_entry, OptionRow::RANGE, {0, 2}, PT_ERR_INVALID, "pt_set_option: root entry must be 0 (off), 1 (product launches) or 2 (instrumented launches too)"},
+    {PT_OPT_ENV_LIGHT, &pt_ctx::opt_env_light, OptionRow::RANGE, {0, 1}, PT_ERR_INVALID, "pt_set_option: env light must be 0 (the map is no light) or 1 (sampled under PT_FLAG_NEE)"},
     {PT_OPT_PATH_HISTORY, &pt_ctx::opt_path_history, OptionRow::RANGE, {0, 2}, PT_ERR_INVALID, "pt_set_option: path history must be 0 (off), 1 (product launches) or 2 (instrumented launches too)"},
 };
 }  // namespace ptmi
@@ -544,7 +545,7 @@ static int plan_call(pt_ctx* c, const pt_params* p, const KParams& P, uint32_t s
     L.work_blocks = (int)((slots + plan.chunk * waves_per_block - 1) / (plan.chunk * waves_per_block));
     L.n_cu = c->n_cu;
     L.moments = moments;
-    L.env = c->env.texels != nullptr;
+    L.env = c->env.texels ? (c->env.cx ? 2 : 1) : 0;
     return PT_OK;
 }
 

@@ -10,7 +10,7 @@
 //               --resume state.ckpt --device-build --fix-estimators --nee --gpus N --tile ROWS
 //               --denoise-out image.ppm|.png|.pfm  --variance-out file.pfm  --until-error E --max-frames M
 //               --pan-deg D --dolly S --temporal-out image.ppm|.png|.pfm  --equirect
-//               --env file.pfm [--env-scale S] [--env-nearest]]
+//               --env file.pfm [--env-scale S] [--env-nearest] [--env-light]]
 // --gpus N splits the framebuffer over N contexts, one per GPU (devices device, device+1, ... modulo the number
 // present, so N > 1 also runs on a one-GPU box): stripes of --tile rows (default 8) are dealt round-robin
 // (pt_params.part_*), every context holds the whole scene and renders only its stripes of every frame — the random
@@ -58,6 +58,9 @@
 // then light another mesh with it, usually without the reference's sphere room around it:
 //     pt_app --mesh statue.ptmesh --no-spheres --env probe.pfm --out lit.png
 // With a map the stage-split pipeline is not chosen (include/ptmi.h): the persistent kernel renders, the megakernel under --nee.
+// --env-light also samples the map as a light (PT_OPT_ENV_LIGHT): every diffuse hit may send its shadow ray towards the map, drawn
+// in proportion to the texels' brightness — what a map with a small, bright sun needs to converge.  It turns --nee on (next-event
+// estimation with the cosine-weighted DIFF lobe, a miss keeping the path's light); a black map is lit by nothing and stays no light.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -78,7 +81,7 @@ static int die(const char* what, const char* msg) {
 int main(int argc, char** argv) {
     std::string mesh_path, out_path, ckpt_path, resume_path, denoise_path, variance_path, temporal_path, env_path;
     double env_scale = 1.0;
-    bool env_scale_set = false, env_nearest = false;
+    bool env_scale_set = false, env_nearest = false, env_light = false;
     int W = 1280, H = 720, frames = 16, depth = 4, mat = PT_MAT_DIFF, device = 0, spp = 1, ckpt_every = 0, gpus = 1, tile = 8;
     bool spheres = true, use_materials = true, device_build = false, fix_estimators = false, nee = false, equirect = false;
     float bk[3] = {1.f, 1.f, 1.f};
@@ -115,6 +118,7 @@ int main(int argc, char** argv) {
         else if (a == "--env") env_path = next("--env");
         else if (a == "--env-scale") { env_scale = std::atof(next("--env-scale")); env_scale_set = true; }
         else if (a == "--env-nearest") env_nearest = true;
+        else if (a == "--env-light") env_light = true;
         else if (a == "--spp") spp = std::atoi(next("--spp"));
         else if (a == "--checkpoint") ckpt_path = next("--checkpoint");
         else if (a == "--checkpoint-every") ckpt_every = std::atoi(next("--checkpoint-every"));
@@ -146,6 +150,8 @@ int main(int argc, char** argv) {
     float* env_px = nullptr;
     if (env_path.empty() && env_scale_set) return die("--env-scale", "goes with --env");
     if (env_path.empty() && env_nearest) return die("--env-nearest", "goes with --env");
+    if (env_path.empty() && env_light) return die("--env-light", "goes with --env");
+    if (env_light) nee = true;   // the map is one of next-event estimation's lights
     if (!env_path.empty()) {
         if (!std::isfinite(env_scale) || env_scale < 0.0) return die("--env-scale", "must be finite and not negative");
         if (pth_read_pfm(env_path.c_str(), &env_w, &env_h, &env_px) != 0) return die("--env", pth_last_error());
@@ -198,11 +204,16 @@ int main(int argc, char** argv) {
         ev.front[2] = -1.f; ev.right[0] = 1.f; ev.up[1] = 1.f;
         ev.scale[0] = ev.scale[1] = ev.scale[2] = (float)env_scale;
         ev.filter = env_nearest ? PT_ENV_NEAREST : PT_ENV_BILINEAR;
-        for (pt_ctx* cx : ctxs)
+        int is_light = 0;
+        for (pt_ctx* cx : ctxs) {
+            if (pt_set_option(cx, PT_OPT_ENV_LIGHT, env_light ? 1 : 0) != PT_OK) return die("--env-light", pt_last_error(cx));
             if (pt_upload_environment(cx, &ev, env_px) != PT_OK) return die("--env", pt_last_error(cx));
+            if (pt_environment_is_light(cx, &is_light) != PT_OK) return die("--env-light", pt_last_error(cx));
+        }
         pth_free_pfm(env_px);
         env_px = nullptr;
-        std::printf("environment map %s: %d x %d, %s\n", env_path.c_str(), env_w, env_h, env_nearest ? "nearest" : "bilinear");
+        std::printf("environment map %s: %d x %d, %s%s\n", env_path.c_str(), env_w, env_h, env_nearest ? "nearest" : "bilinear",
+                    is_light ? ", sampled as a light" : env_light ? ", black: not a light" : "");
     }
 
     // the reference's sphere room, BasicScene.cpp:181-202

@@ -210,12 +210,14 @@ class PathTracer:
         self._check(self._lib.pt_render_rays(self._ctx, rays_ptr, int(n), int(first_index), out_ptr, C.byref(params), int(spp),
                                              _abi.RAYS_HDR if hdr else _abi.RAYS_CLAMPED))
 
-    def upload_environment(self, texels, front=(0, 0, -1), right=(1, 0, 0), up=(0, 1, 0), scale=(1, 1, 1), filter=_abi.ENV_BILINEAR):
+    def upload_environment(self, texels, front=(0, 0, -1), right=(1, 0, 0), up=(0, 1, 0), scale=(1, 1, 1), filter=_abi.ENV_BILINEAR, light=False):
         """Light the paths that leave the scene with a latitude-longitude map (pt_upload_environment) instead of bk_color: texels
         float32 [H][W][3] on the host, in the layout `pt_app --equirect` writes for a camera with this front / right / up (the
         defaults: the default camera's, i.e. the world frame); scale multiplies the texels per channel; filter ENV_BILINEAR or
         ENV_NEAREST.  Waits for renders in flight; a render issued afterwards sees the new map.  With a map the stage-split
-        pipeline is not chosen."""
+        pipeline is not chosen.  light: the map also gets a sampling distribution (PT_OPT_ENV_LIGHT for this upload; the option is
+        0 again afterwards) and is one of FLAG_NEE's lights in calls that have FLAG_MISS_KEEPS_PATH too — what a map with a small,
+        bright sun needs; environment_is_light() tells whether it took (an orthonormal basis, a map that is not black)."""
         a = np.ascontiguousarray(texels, np.float32)
         if a.ndim != 3 or a.shape[2] != 3:
             raise ValueError("upload_environment: a float32 array of shape (H, W, 3) expected")
@@ -223,7 +225,11 @@ class PathTracer:
         ev.width, ev.height = a.shape[1], a.shape[0]
         ev.front[:], ev.right[:], ev.up[:], ev.scale[:] = front, right, up, scale
         ev.filter = int(filter)
-        self._check(self._lib.pt_upload_environment(self._ctx, C.byref(ev), a.ctypes.data))
+        self.set_option(_abi.OPT_ENV_LIGHT, 1 if light else 0)
+        try:
+            self._check(self._lib.pt_upload_environment(self._ctx, C.byref(ev), a.ctypes.data))
+        finally:
+            self.set_option(_abi.OPT_ENV_LIGHT, 0)
 
     def clear_environment(self):
         """Back to bk_color (and to the stage-split pipeline): pt_upload_environment with no map."""
@@ -233,6 +239,23 @@ class PathTracer:
         """What the map sends along the directions of a ray batch (pt_eval_environment): rays float[n][8], words 4-6 read (any
         length); out float[n][3].  Asynchronous until sync()."""
         self._check(self._lib.pt_eval_environment(self._ctx, rays_ptr, int(n), out_ptr))
+
+    def environment_is_light(self):
+        """Whether the context's map carries a sampling distribution (pt_environment_is_light): uploaded with light=True, basis
+        orthonormal, not black.  False without a map."""
+        out = C.c_int(0)
+        self._check(self._lib.pt_environment_is_light(self._ctx, C.byref(out)))
+        return bool(out.value)
+
+    def sample_environment(self, u_ptr, n, dir_pdf_ptr, radiance_ptr=None):
+        """Draw directions from the map's distribution (pt_sample_environment): u float[n][2] in [0, 1); dir_pdf float[n][4] =
+        (d.xyz, density per steradian); radiance float[n][3], the lookup along d (optional).  Asynchronous until sync()."""
+        self._check(self._lib.pt_sample_environment(self._ctx, u_ptr, int(n), dir_pdf_ptr, radiance_ptr))
+
+    def environment_pdf(self, rays_ptr, n, pdf_ptr):
+        """The density sample_environment has along the directions of a ray batch (pt_environment_pdf): rays float[n][8], words 4-6
+        read (any length); pdf float[n].  Asynchronous until sync()."""
+        self._check(self._lib.pt_environment_pdf(self._ctx, rays_ptr, int(n), pdf_ptr))
 
     def render_aux(self, cam, params, albedo_ptr, normal_ptr, position_ptr, id_ptr=None):
         """First-hit guide buffers of the pixel-centre rays (pt_render_aux): albedo, normal, position as float[H][W][4], the hit

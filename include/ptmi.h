@@ -90,7 +90,9 @@ enum {
                                         Spheres the path is inside of (the reference room's glowing walls) and triangles
                                         lit by the one global material of pt_params are gathered by the bounce as before.
                                         Same expectation, less noise for small lights; runs in the stage-split pipeline
-                                        (a shadow-ray stage per bounce) or the megakernel                                   */
+                                        (a shadow-ray stage per bounce) or the megakernel.  An environment map uploaded
+                                        under PT_OPT_ENV_LIGHT is one more light of the pick where the call also has
+                                        PT_FLAG_MISS_KEEPS_PATH (the environment section states the rule)                    */
     PT_FLAG_MISS_KEEPS_PATH = 1u << 6  /* a segment that hits nothing ends the path with
                                         accu + mask * bk_color (smallpt, and the reference's own CPU
                                         tracer: CpuRayTracer/src/scene.cpp:27 returns black for the
@@ -246,7 +248,7 @@ enum {
                                  extend launches of bounces >= 1 drew (pt_get_wave_stats [7] is their number while bounce 0 is the
                                  packet walk, PT_OPT_FIRST_WALK 1); 0 = every walk starts at the root.
                                  With 0 or 1 the counters are unchanged.  Same images                                           */
-    PT_OPT_PATH_HISTORY = 34  /* PT_KERNEL_WAVEFRONT: a path's record carries WHICH objects the path has hit so far — four bits per
+    PT_OPT_PATH_HISTORY = 34, /* PT_KERNEL_WAVEFRONT: a path's record carries WHICH objects the path has hit so far — four bits per
                                  bounce, sphere 0-7 or "a triangle" — in one word instead of its mask as three floats; a shade lane
                                  rebuilds the mask and the light gathered so far from that word with the arithmetic the path itself
                                  would have done, and the path's sample colour is written once, by the lane the path ends in, not
@@ -255,6 +257,9 @@ enum {
                                  8 spheres, no PT_MAT_REFR triangle material or sphere, depth <= 9; any other call keeps the three
                                  mask planes and the in-place adds.  1 (default) = product launches do so; 2 = instrumented
                                  (PT_OPT_COUNTERS) launches too; 0 = off.  No counter changes under any value.  Same images         */
+    PT_OPT_ENV_LIGHT = 35     /* read by the next pt_upload_environment: 0 (default) = the map is what a miss gathers and nothing
+                                 else; 1 = the map also gets a sampling distribution and is a LIGHT under PT_FLAG_NEE (see the
+                                 environment section).  Any other value PT_ERR_INVALID                                            */
 };
 
 /* CamInfo, GpuPathTracer/CpuStructs.hpp:19-28 (pitch/yaw/dirty/bias/enabled are host-only
@@ -548,7 +553,7 @@ int pt_render_rays(pt_ctx* ctx, const float* rays_dev, size_t n_rays, uint64_t f
  * the lookup of its direction where it returned bk_color, by the same rule of the flags — the bare value, or accu + mask * value
  * under PT_FLAG_MISS_KEEPS_PATH (the reference's quirk that a miss without that flag is NOT masked holds for a map too).  Every
  * flag, partitions and PT_FLAG_NEE work; under NEE the map is gathered by bounce rays only, like a sphere the path is inside of —
- * it is not sampled as a light, so a map with a small sun is noisy.  pt_render_rays' guard keeps writing bk_color for a ray that
+ * unless it was uploaded under PT_OPT_ENV_LIGHT (below), a map with a small sun is noisy.  pt_render_rays' guard keeps writing bk_color for a ray that
  * is not finite or has no direction (there is nothing to look up).  pt_render_aux, pt_denoise and pt_temporal are untouched: a
  * pixel that sees the map is still a miss.  With a map on the context the stage-split pipeline is not chosen (see
  * PT_KERNEL_WAVEFRONT); clearing the map brings it back.  A map change is a scene change for PT_KERNEL_AUTO's table.
@@ -559,8 +564,47 @@ int pt_render_rays(pt_ctx* ctx, const float* rays_dev, size_t n_rays, uint64_t f
  * Errors, in this order: NULL ctx PT_ERR_INVALID; then with env != NULL, each PT_ERR_INVALID: a NULL texels; a dimension out of
  * range; an unknown filter; a basis vector or scale that is not finite, a zero basis vector, a negative scale (these four before
  * texels is dereferenced); a texel that is not finite or is negative after scaling.  The old map stays in place on any error.
- * Left out: sampling the map as a light under PT_FLAG_NEE, the stage-split pipeline for scenes with a map, mip levels, cube or
- * octahedral layouts, the map in pt_render_aux's albedo. */
+ * Left out: the stage-split pipeline for scenes with a map, mip levels, cube or octahedral layouts, the map in pt_render_aux's
+ * albedo.
+ *
+ * The map as a light.  A map carries a sampling distribution when PT_OPT_ENV_LIGHT was 1 at its upload, its
+ * basis is orthonormal (in double: |len(v) - 1| <= 1e-4 for front, right and up, |dot| <= 1e-4 for each pair — the draw's inverse
+ * mapping assumes it) and it is not black (T > 0 below); otherwise the upload succeeds as before and the map is no light.
+ * pt_environment_is_light tells which.  The tables, built on the host in double, t the scaled device texel, every sum sequential
+ * in ascending index:
+ *   m[y][x] = max(t.r, t.g, t.b); for PT_ENV_BILINEAR the maximum of that over the 3 x 3 neighbourhood, columns wrapped and rows
+ *     clamped, so that the density is positive wherever a bilinear lookup can be.
+ *   Row edges by the lookup's nearest rule (row 0 owns fy in [0, 0.5), row H - 1 owns [H - 1.5, H]): e_0 = -pi/2,
+ *     e_i = (i - 0.5 - H/2) * pi / H for 0 < i < H, e_H = +pi/2; zs[i] = (float)sin(e_i), zs[0] = -1 and zs[H] = 1 exactly.
+ *   S_y = sum_x m[y][x]; cx[y][i] = (float)(sum_{j<i} m[y][j] / S_y) for i = 0..W, cx[y][0] = 0 and cx[y][W] = 1 exactly; a row
+ *     with S_y = 0 gets i / W and is never picked.
+ *   A_y = S_y * ((double)zs[y+1] - (double)zs[y]), T = sum A_y; cy[i] = (float)(sum_{j<i} A_j / T), cy[0] = 0, cy[H] = 1 exactly.
+ * On the device float cx[H][W+1], cy[H+1], zs[H+1]: about 4 bytes per texel more, owned and freed with the map, not counted in
+ * pt_scene_info; "the old map stays in place on any error" covers them.
+ * The draw for (u1, u2) in [0, 1), binary32 with plain * and +:
+ *   y = the largest i in 0..H-1 with cy[i] <= u1 (binary search: a zero-width row is never picked), py = cy[y+1] - cy[y],
+ *     v1 = min((u1 - cy[y]) / py, 0x1.fffffep-1f); the same in row y with u2: x, px, v2.
+ *   z = zs[y] + v1 * (zs[y+1] - zs[y]), r = sqrtf(max(0, 1 - z * z)), lon = ((((float)x - 0.5f) + v2) - hx) / kx,
+ *     d = front * (r * cosf(lon)) + right * (r * sinf(lon)) + up * z.
+ *   pdf = ((py * px) * kx) / (zs[y+1] - zs[y]) per steradian, constant over the texel — from the CDF DIFFERENCES, not m / T, so it is
+ *     the density of what is drawn whatever the rounding of the tables; 0 where py * px is 0.
+ *   (u1 = 0 in row 0, or v1 rounding to the far edge of row H - 1, is a pole itself: r = 0, where the columns of the row meet and the
+ *   lookup of d takes longitude atan2f(0, 0) = 0, column W / 2, whatever column was drawn.)
+ * The density of a given direction: a, b, c, fx, fy as in the lookup, column and row the lookup's nearest ones, the same formula;
+ * 0 for a direction the lookup calls invalid.
+ * The estimator: in pt_render, pt_render_moments and pt_render_rays, at a DIFF hit of a call with PT_FLAG_NEE,
+ * PT_FLAG_COSINE_DIFF and PT_FLAG_MISS_KEEPS_PATH that is not the path's last (hit number `depth`: the bounce ray from there is
+ * never traced, so what the map sends there lies beyond the call's depth and the call's expectation is the same with and without
+ * the tables), such a map is the LAST light of PT_FLAG_NEE's uniform pick (n_all = eligible spheres + emissive triangles + 1); the draws are unchanged: u0 picks the light, u1 the row, u2 the column.  The shadow ray leaves
+ * the hit point along d with no far end; it is dropped when dot(nl, d) <= 0, when pdf is not > 0 or when ANY sphere is hit at
+ * ts > 0.01 (a point inside one of the room's wall spheres never sees the sky, as its bounce ray would not), else traced against
+ * the triangles, and adds mask * lookup(d) * (cosl * n_all / (pi * pdf)) — the lookup the call renders with, either filter.  The
+ * bounce ray of such a hit gathers nothing from the map when it leaves the scene (accu + mask * 0): the exclusive scheme the
+ * spheres and emissive triangles use.  Camera rays, mirror / glass / metal bounces and calls without the three flags gather the
+ * map as before; a context whose map is no light renders exactly what it rendered.
+ * Left out: multiple importance sampling between the shadow ray and the bounce ray (pt_sample_environment and
+ * pt_environment_pdf let a host do its own), mip or hierarchical warps, building the tables on the device, the stage-split
+ * pipeline with a map, the map as a light without PT_FLAG_MISS_KEEPS_PATH (a miss then discards the gathered light). */
 enum { PT_ENV_NEAREST = 0, PT_ENV_BILINEAR = 1 };
 typedef struct pt_environment {
     int32_t width, height;               /* texels: 1..16384 each, width * height <= 2^26 */
@@ -576,6 +620,18 @@ int pt_upload_environment(pt_ctx* ctx, const pt_environment* env, const float* t
  * PT_ERR_INVALID; n_rays >= 2^32 PT_ERR_INVALID.  Asynchronous on the context's stream; with PT_OPT_TIMING=1, pt_last_kernel_ms
  * covers it. */
 int pt_eval_environment(pt_ctx* ctx, const float* rays_dev, size_t n_rays, float* radiance_dev /* float[n][3] */);
+/* *out = 1 when the context's map carries a sampling distribution (see "The map as a light"), 0 when it does not or there is no
+ * map.  NULL ctx or out: PT_ERR_INVALID. */
+int pt_environment_is_light(pt_ctx* ctx, int* out);
+/* The draw and the density above for a batch, one thread per element.  pt_sample_environment: u_dev float[n][2] = (u1, u2), a
+ * value outside [0, 1) or a NaN clamped into [0, 0x1.fffffep-1] (a NaN to 0); dir_pdf_dev float[n][4] = (d.xyz, pdf);
+ * radiance_dev float[n][3], the lookup along d (what pt_eval_environment answers for it), may be NULL.  pt_environment_pdf:
+ * rays_dev float[n][8], words 4-6 read (any length); pdf_dev float[n].  Buffers must not overlap (not checked).
+ * Errors, in this order: NULL ctx PT_ERR_INVALID; no map PT_ERR_NO_SCENE; a map that is no light PT_ERR_UNSUPPORTED; n == 0 PT_OK,
+ * nothing written; a NULL required pointer PT_ERR_INVALID; n >= 2^32 PT_ERR_INVALID.  Asynchronous on the context's stream; with
+ * PT_OPT_TIMING=1, pt_last_kernel_ms covers them. */
+int pt_sample_environment(pt_ctx* ctx, const float* u_dev, size_t n, float* dir_pdf_dev, float* radiance_dev);
+int pt_environment_pdf(pt_ctx* ctx, const float* rays_dev, size_t n, float* pdf_dev);
 
 /* ---- guide buffers and denoiser — an EXTENSION --------------------------
  * pt_render_aux: the first hit of ONE ray through every pixel centre (the camera ray of pt_render with zero jitter), for a

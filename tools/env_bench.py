@@ -9,7 +9,18 @@ scene — the dragon alone, no spheres, the tree built on the device, a camera i
   (d) pt_eval_environment over 2 M random directions, both map sizes, bilinear
 and the share of the call's segments that hit nothing, from one instrumented call (PT_OPT_COUNTERS).  The figures to read are
 (b) / (a) and (c) / (a).
-Usage: python tools/env_bench.py [--out FILE] [--reps 9] [--warmup 2] [--scene dragon]"""
+
+--mode light: what sampling the map as a light (PT_OPT_ENV_LIGHT, upload_environment(light=True)) buys on the same scene and
+camera under next-event estimation (PT_FLAGS_SMALLPT | PT_FLAG_NEE; the megakernel renders): a 4096 x 2048 bilinear map, dim sky
+with a sun of a few texels (radiance 20 000, 3 x 3 texels, 45 degrees up behind the camera's right shoulder),
+  (e) the step time with the light off and on
+  (f) pt_frame_error's mean relative standard error of the frame after equal TIME: --budget-ms of device time each, whole calls,
+      with the frame's mean luminance and the number of pixels the sun has reached beside it: the error is estimated from the
+      samples, so a pixel whose bounce rays never found the sun reports a small error around the wrong mean
+  (g) pt_sample_environment: 2 M draws, with and without the radiance
+--skip-light runs (e) and (f) with the light off only and nothing that needs the option: the same file run in a checkout of an
+earlier commit gives that commit's time for the same frame.
+Usage: python tools/env_bench.py [--mode map|light] [--out FILE] [--reps 9] [--warmup 2] [--scene dragon]"""
 import argparse
 import os
 import sys
@@ -28,6 +39,9 @@ ap.add_argument("--scene", default="dragon")
 ap.add_argument("--spp", type=int, default=16)
 ap.add_argument("--depth", type=int, default=4)
 ap.add_argument("--eval-rays", type=int, default=2_000_000)
+ap.add_argument("--mode", choices=("map", "light"), default="map")
+ap.add_argument("--skip-light", action="store_true", help="--mode light: the light-off figures only (for a checkout without PT_OPT_ENV_LIGHT)")
+ap.add_argument("--budget-ms", type=float, default=400.0, help="--mode light: device time per equal-time comparison")
 a = ap.parse_args()
 W, H = 1920, 1080
 lines = []
@@ -56,6 +70,50 @@ def timed(name, fn, unit, count):
     return med
 
 
+def sun_map(w, h):
+    """a dim sky and a sun of 3 x 3 texels, float32 [h][w][3]: 45 degrees up, 135 degrees from `front` towards `right`"""
+    y = np.linspace(0.0, 1.0, h, dtype=np.float32)[:, None, None]
+    tex = np.broadcast_to(np.array([0.05, 0.07, 0.1], np.float32) * (0.5 + y), (h, w, 3)).copy()
+    r, c = int(h * 0.75), int(w * (0.5 + 135.0 / 360.0))
+    tex[r - 1:r + 2, c - 1:c + 2] = (20000.0, 19000.0, 17000.0)
+    return tex
+
+
+def light_mode():
+    """(e) - (g) of the module's text"""
+    p.flags = g.FLAGS_SMALLPT | g.FLAG_NEE
+    t.set_option(g.OPT_KERNEL, g.KERNEL_AUTO)
+    tex = sun_map(4096, 2048)
+    mom = t.malloc(W * H * 8)
+    say(f"--mode light: PT_FLAGS_SMALLPT | PT_FLAG_NEE, 4096 x 2048 bilinear map with a 3 x 3 texel sun; equal time = {a.budget_ms:.0f} ms of device time")
+    for light in ((False,) if a.skip_light else (False, True)):
+        t.upload_environment(tex, **({"light": True} if light else {}))
+        tag = "on " if light else "off"
+        ms = timed(f"(e) light {tag}: step", lambda: t.launch_kernel(acc.ptr, rgba.ptr, cam, p, a.spp), "paths", W * H * a.spp)
+        calls = max(1, int(a.budget_ms / ms))
+        q = g.Params.from_buffer_copy(p)
+        spent = 0.0
+        for k in range(calls):
+            q.frame, q.sample_index = k * a.spp, 1 + k * a.spp
+            t.launch_kernel(acc.ptr, rgba.ptr, cam, q, a.spp, mom.ptr)
+            spent += t.last_kernel_ms()
+        rse, _ = t.frame_error(mom.ptr, W, H, calls * a.spp)
+        m1 = mom.download(np.float32, (H, W, 2))[..., 0].astype(np.float64)
+        say(f"  (f) light {tag}: {calls} calls = {calls * a.spp} samples per pixel in {spent:.1f} ms: mean relative standard error {rse:.5f}, "
+            f"mean luminance of the frame {m1.mean():.4f}, pixels brighter than 0.3 (three times the brightest sky texel: the sun reached them) {int((m1 > 0.3).sum())}")
+    if not a.skip_light:
+        n = a.eval_rays
+        u = np.random.default_rng(7).random((n, 2), dtype=np.float32)
+        d_u, d_o, d_r = t.malloc(u.nbytes), t.malloc(16 * n), t.malloc(12 * n)
+        d_u.upload(u)
+        timed("(g) pt_sample_environment, directions and densities", lambda: t.sample_environment(d_u.ptr, n, d_o.ptr), "draws", n)
+        timed("(g) pt_sample_environment, with the radiance", lambda: t.sample_environment(d_u.ptr, n, d_o.ptr, d_r.ptr), "draws", n)
+        for b in (d_u, d_o, d_r):
+            b.free()
+    mom.free()
+    t.clear_environment()
+
+
 t = g.PathTracer(0)
 mesh = g.scene_mesh(a.scene)
 build_ms = t.build_bvh(mesh)
@@ -82,6 +140,16 @@ say(f"  segments {c['rays']}, of them ending on a triangle {c['hits']}: {100.0 *
 
 t.set_option(g.OPT_TIMING, 1)
 paths = W * H * a.spp
+if a.mode == "light":
+    light_mode()
+    acc.free()
+    rgba.free()
+    t.set_option(g.OPT_TIMING, 0)
+    t.close()
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+    sys.exit(0)
 render = lambda: t.launch_kernel(acc.ptr, rgba.ptr, cam, p, a.spp)   # noqa: E731
 ms_bk = timed("(a) bk_color", render, "paths", paths)
 rng = np.random.default_rng(6)
