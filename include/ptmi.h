@@ -66,8 +66,9 @@ enum {
                                         computes and then discards (nl = n in the reference)           */
     PT_FLAG_COSINE_DIFF = 1u << 3,   /* DIFF lobe: cosine-weighted direction from TWO draws (smallpt's
                                         estimator; mask *= col is then exact) instead of the reference's
-                                        uniform hemisphere with no cosine term and two discarded draws
-                                        (tracer.cu:159-186)                                            */
+                                        lobe, which draws sin(theta) uniformly in [0, 1] (density
+                                        cos(theta) / (2 pi sin(theta)) per steradian about the normal, no
+                                        weight), and its two discarded draws (tracer.cu:159-186)       */
     PT_FLAG_GLASS_FIX = 1u << 4,     /* REFR: R0 = ((nt-nc)/(nt+nc))^2 (the reference's :230 multiplies
                                         where it should divide), reflection chosen with probability
                                         P = .25 + .5 Re (the weights RP/TP assume it; the reference

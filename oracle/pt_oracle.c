@@ -389,8 +389,9 @@ void orc_camera_ray(const pt_camera* cam, int px, int py, int w, int h, float u0
 /* PT_FLAG_NEE over emissive triangles (ptmi.h): the light list the product derives from the material table —
  * every triangle whose row emits, ascending original id, as (v0, emi.r) (e1 = v1 - v0, emi.g) (e2 = v2 - v0, emi.b),
  * binary32 subtraction as at upload.  The tests build it from the mesh and hand it over before a render. */
-/* The ARBITER (orc_sample_pixels): with a raw mesh set, get_sample's closest hit is the brute-force loop over every
- * triangle instead of the BVH walk, and each segment's (t, triangle) can be logged.  Thread-local: set per worker. */
+/* The ARBITER (orc_sample_pixels): with a raw mesh set, get_sample's closest hit — of a path segment and of a PT_FLAG_NEE shadow
+ * ray alike — is the brute-force loop over every triangle instead of the BVH walk, and each segment's (t, triangle) can be
+ * logged.  Thread-local: set per worker. */
 static _Thread_local const float* tl_brute_verts = 0;
 static _Thread_local const int32_t* tl_brute_vidx = 0;
 static _Thread_local size_t tl_brute_n = 0;
@@ -402,6 +403,16 @@ static size_t g_n_tri_lights = 0;
 void orc_set_tri_lights(const float* lights12, size_t n) {
     g_tri_lights = n ? lights12 : 0;
     g_n_tri_lights = lights12 ? n : 0;
+}
+
+/* The closest triangle hit of a segment of get_sample, camera, bounce or shadow ray alike: the arbiter's brute-force loop when a raw
+ * mesh is set, else the walk over the tree, else (spheres only) a miss. */
+static hit_t closest_hit(const float* nodes, const float* tris, const int32_t* tidx, v3 o, v3 d, int cull, orc_counters* cnt) {
+    hit_t h = {F32_MAX, -1, {0, 0, 0}};
+    if (tl_brute_n) { h = brute_intersect(tl_brute_verts, tl_brute_vidx, tl_brute_n, o, d, cull); if (cnt) cnt->rays++; }
+    else if (nodes) h = bvh_intersect(nodes, tris, tidx, o, d, cull, cnt);
+    else if (cnt) cnt->rays++;
+    return h;
 }
 
 static v3 get_sample(const float* nodes, const float* tris, const int32_t* tidx,
@@ -421,9 +432,7 @@ static v3 get_sample(const float* nodes, const float* tris, const int32_t* tidx,
         int geom = 3; /* GeoType::NONE */
         int sph_id = -1;
         hit_t h = {F32_MAX, -1, {0, 0, 0}};
-        if (tl_brute_n) { h = brute_intersect(tl_brute_verts, tl_brute_vidx, tl_brute_n, o, d, P->cull_backfaces); if (cnt) cnt->rays++; }
-        else if (nodes) h = bvh_intersect(nodes, tris, tidx, o, d, P->cull_backfaces, cnt);
-        else if (cnt) cnt->rays++;
+        h = closest_hit(nodes, tris, tidx, o, d, P->cull_backfaces, cnt);
         if (tl_seg_log && depth < tl_seg_cap) { tl_seg_log[2 * depth] = h.t; tl_seg_log[2 * depth + 1] = bits2f((uint32_t)h.tri); }
         float scene_t = h.t;
         if (h.tri != -1) geom = 0; /* TRI */
@@ -535,9 +544,7 @@ static v3 get_sample(const float* nodes, const float* tris, const int32_t* tidx,
                             if (ts != 0.0f && ts < t_light && ts > 0.01f) blocked = 1;
                         }
                         if (!blocked) {
-                            hit_t h2 = {F32_MAX, -1, {0, 0, 0}};
-                            if (nodes) h2 = bvh_intersect(nodes, tris, tidx, hitpos, l, P->cull_backfaces, cnt);
-                            else if (cnt) cnt->rays++;
+                            const hit_t h2 = closest_hit(nodes, tris, tidx, hitpos, l, P->cull_backfaces, cnt);
                             if (!(h2.t < t_light)) {
                                 float k = ((cosl * (0.5f * proj)) * (float)n_all) / (3.14159274f * d2);
                                 accu = vadd(accu, vscale(vmul(mask, V(tl[3], tl[7], tl[11])), k));
@@ -569,9 +576,7 @@ static v3 get_sample(const float* nodes, const float* tris, const int32_t* tidx,
                         if (ts != 0.0f && ts < t_light && ts > 0.01f) blocked = 1;
                     }
                     if (!blocked) {
-                        hit_t h2 = {F32_MAX, -1, {0, 0, 0}};
-                        if (nodes) h2 = bvh_intersect(nodes, tris, tidx, hitpos, l, P->cull_backfaces, cnt);
-                        else if (cnt) cnt->rays++;
+                        const hit_t h2 = closest_hit(nodes, tris, tidx, hitpos, l, P->cull_backfaces, cnt);
                         if (!(h2.t < t_light)) {
                             float k = (cosl * (2.0f * (1.0f - cos_max))) * (float)n_all;
                             accu = vadd(accu, vscale(vmul(mask, V(L->emi[0], L->emi[1], L->emi[2])), k));

@@ -266,13 +266,21 @@ def check(acc, ref, what, max_diff):
     assert n_diff <= max_diff, f"{what}: {n_diff} differing pixels, more than {max_diff}"
 
 
+def emitters(mesh, materials, tri_material):
+    """orc.tri_lights of a material table with emitters, None without one: the light list PT_FLAG_NEE samples, which both oracle
+    renderers need to restate such a call.  `arbitrate` and `judge` below."""
+    if materials is None or not any(any(m.emi) for m in materials):
+        return None
+    return orc.tri_lights(mesh, materials, tri_material)
+
+
 def arbitrate(pt, mesh, bvh, sph, cam, p, frames, what, max_diff, oracle_key=None, materials=None, tri_material=None):
     """Sample by sample (one pt_render per frame, N = 1) against the oracle's walk over `bvh`; every (frame, pixel) where the
     two differ is replayed with the BRUTE-FORCE closest hit (orc.sample_pixels over the raw triangles: no tree, so no box
     can cull anything) and the GPU must hold brute force's colour.  Returns (differing, of which the oracle's walk was off).
     materials / tri_material: the per-triangle material table on the context, handed to both oracle renderers.
     test_gpu_bench_configs, test_gpu_refit, test_gpu_scene_matrix."""
-    mk = dict(materials=materials, tri_material=tri_material)
+    mk = dict(materials=materials, tri_material=tri_material, lights=emitters(mesh, materials, tri_material))
     W, H = p.width, p.height
     acc, rgba = pt.alloc_frame(W, H)
     diffs = []
@@ -332,7 +340,8 @@ def judge(t, case, got, ref, mesh, sph, cam, p, spp, prev=None, materials=None, 
         assert n_diff <= MAX_DIFF, f"[{t.name}] {case}: {n_diff} pixels differ from the oracle"
         assert not np.any((rgba != ref_rgba) & ~diff), f"[{t.name}] {case}: display words differ where the accumulator does not"
         for y, x in zip(*np.nonzero(diff)):
-            col, _, _ = orc.sample_pixels([(int(x), int(y))], sph, cam, p, spp, mesh=mesh, materials=materials, tri_material=tri_material)
+            col, _, _ = orc.sample_pixels([(int(x), int(y))], sph, cam, p, spp, mesh=mesh, materials=materials, tri_material=tri_material,
+                                          lights=emitters(mesh, materials, tri_material))
             brute = orc.fold_samples(col, p.sample_index, None if prev is None else prev[y, x][None])[0]
             print(f"  [{t.name}] {case}: pixel ({x},{y}) gpu {acc[y, x]} oracle {ref_acc[y, x]} brute {brute}")
             assert np.array_equal(acc[y, x], brute), f"[{t.name}] {case}: pixel ({x},{y}) is neither the oracle's nor brute force's"

@@ -109,11 +109,11 @@ def render(bvh, spheres, cam, params, spp=1, accum=None, want_rgba=True, materia
     return accum, rgba, counters_dict(cnt)
 
 
-def sample_pixels(pixels_xy, spheres, cam, params, spp, bvh=None, mesh=None, materials=None, tri_material=None):
+def sample_pixels(pixels_xy, spheres, cam, params, spp, bvh=None, mesh=None, materials=None, tri_material=None, lights=None):
     """Selected pixels sample by sample: the colours before the fold [n][spp][3] and every segment's (t, triangle id)
     [n][spp][depth].  bvh: hits from the oracle's walk over the Compact arrays; mesh (bvh None): hits from the
-    BRUTE-FORCE loop over the raw triangles — the arbiter for pixels where two renders differ.  materials / tri_material:
-    the per-triangle material table, as in render()."""
+    BRUTE-FORCE loop over the raw triangles, shadow rays included — the arbiter for pixels where two renders differ.
+    materials / tri_material, lights: the per-triangle material table and tri_lights(...), as in render()."""
     px = np.ascontiguousarray(pixels_xy, np.int32).reshape(-1, 2)
     n, depth = len(px), params.depth
     col = np.zeros((n, spp, 3), np.float32)
@@ -124,6 +124,8 @@ def sample_pixels(pixels_xy, spheres, cam, params, spp, bvh=None, mesh=None, mat
         mtab = (g.Material * len(materials))(*materials)
         ids = np.ascontiguousarray(tri_material, np.int32)
     tab = (C.cast(mtab, C.c_void_p), ids.ctypes.data) if mtab is not None else (None, None)
+    n_l = len(lights) if lights is not None and mtab is not None else 0
+    lib().orc_set_tri_lights(lights.ctypes.data if n_l else None, n_l)
     if bvh is not None:
         rc = lib().orc_sample_pixels_mat(bvh.nodes.ctypes.data, bvh.tris.ctypes.data, bvh.index.ctypes.data, None, None, 0,
                                          spheres if n_s else None, n_s, *tab, C.byref(cam), C.byref(params), spp, px.ctypes.data,
@@ -132,6 +134,7 @@ def sample_pixels(pixels_xy, spheres, cam, params, spp, bvh=None, mesh=None, mat
         v, f = np.ascontiguousarray(mesh.verts), np.ascontiguousarray(mesh.tris)
         rc = lib().orc_sample_pixels_mat(None, None, None, v.ctypes.data, f.ctypes.data, len(f), spheres if n_s else None, n_s, *tab,
                                          C.byref(cam), C.byref(params), spp, px.ctypes.data, n, col.ctypes.data, seg.ctypes.data)
+    lib().orc_set_tri_lights(None, 0)
     assert rc == 0
     return col, seg[..., 0], seg[..., 1].view(np.int32)
 
