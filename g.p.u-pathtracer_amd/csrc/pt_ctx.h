@@ -58,6 +58,7 @@ struct pt_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
+    hipEvent_t switch_ev = nullptr;    // pt_set_stream: the new stream waits for what the old one was given (recorded there at the switch)
     std::string err;
     // scene
     TreeState tree;

@@ -178,6 +178,7 @@ int pt_destroy(pt_ctx* c) {
         for (hipEvent_t e : a.e) if (e) (void)hipEventDestroy(e);
     if (c->lights_ev) (void)hipEventDestroy(c->lights_ev);
     if (c->geom_ev) (void)hipEventDestroy(c->geom_ev);
+    if (c->switch_ev) (void)hipEventDestroy(c->switch_ev);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -187,7 +188,17 @@ int pt_destroy(pt_ctx* c) {
 
 int pt_set_stream(pt_ctx* c, void* s) {
     if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
-    c->stream = s ? (hipStream_t)s : c->own_stream;
+    hipStream_t next = s ? (hipStream_t)s : c->own_stream;
+    if (next != c->stream) {
+        // The context's scratch (sample buffers, path records, queue and work counters, the light list, a refit tree) is written by the
+        // calls on whichever stream is current, and a side stream's fold waits on the stream it was issued on: what the new stream is
+        // given starts behind everything the old one has been given.  No host synchronisation.
+        HIP_TRY(c, hipSetDevice(c->device));
+        if (!c->switch_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->switch_ev, hipEventDisableTiming));
+        HIP_TRY(c, hipEventRecord(c->switch_ev, c->stream));
+        HIP_TRY(c, hipStreamWaitEvent(next, c->switch_ev, 0));
+    }
+    c->stream = next;
     return PT_OK;
 }
 
@@ -438,11 +449,12 @@ static int fill_params(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, const pt
 static int auto_lookup(pt_ctx* c, const pt_params* p, uint32_t spp, bool moments, pt_ctx::AutoPick*& pick, int& probe) {
     using AP = pt_ctx::AutoPick;
     // the key holds the SHAPE of the partition, not which part this call renders: the parts of a tile split cost alike
+    // mat_gen: a material table decides what the pipeline launches (the last segment's any-hit query and the path history need "no table")
     uint64_t key = 0xcbf29ce484222325ull;
     const uint64_t parts[] = {(uint64_t)p->width, (uint64_t)p->height, (uint64_t)spp, (uint64_t)p->depth,
                               (uint64_t)(p->part_count > 1 ? p->part_count : 1), (uint64_t)(p->part_count > 1 ? p->part_rows : 0), c->scene_gen,
                               (uint64_t)c->n_spheres, (uint64_t)p->tri_mat, (uint64_t)(p->flags & ~(uint32_t)PT_FLAG_WRITE_RGBA),
-                              (uint64_t)moments, c->env_gen};   // with moments the pipeline keeps its separate fold and one sample goes through the sample buffer: other trial times
+                              (uint64_t)moments, c->env_gen, c->mat_gen};   // with moments the pipeline keeps its separate fold and one sample goes through the sample buffer: other trial times
     for (uint64_t v : parts) { key ^= v; key *= 0x100000001b3ull; }
     if (key == 0) key = 1;
     int slot = -1, lru = 0;

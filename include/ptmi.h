@@ -113,8 +113,8 @@ enum {
  * round-1 role-split experiment) are gone with ABI 3: pt_set_option rejects them with PT_ERR_UNSUPPORTED. */
 enum {
     PT_KERNEL_AUTO = 0,      /* PT_KERNEL_PERSISTENT or PT_KERNEL_WAVEFRONT, whichever is faster for the
-                                configuration (image, samples per call, depth, partition shape, scene, material,
-                                flags): the first four pt_render calls of a configuration are timed trials, two per
+                                configuration (image, samples per call, depth, partition shape, scene, material and
+                                material table, environment map, flags): the first four pt_render calls of a configuration are timed trials, two per
                                 layout (HIP events; buffers are allocated before the timed span; the faster trial
                                 of each layout counts) and the following ones run the faster; the images are the same.  The decision never blocks the
                                 host: while a trial's events are still pending, calls run the persistent kernel.
@@ -329,7 +329,11 @@ int pt_device_count(void);                       /* <0 on error                 
 int pt_create(int device, pt_ctx** out);
 int pt_destroy(pt_ctx* ctx);
 const char* pt_last_error(const pt_ctx* ctx);     /* ctx may be NULL: global message  */
-int pt_set_stream(pt_ctx* ctx, void* hip_stream); /* NULL = ctx's own stream          */
+/* pt_set_stream: the stream the following calls are issued on; NULL = the ctx's own.  A switch in the middle of a session needs no
+ * pt_sync: the new stream waits (on the device, an event) for everything the old one has been given — the context's scratch buffers, its
+ * light list and a refit tree are shared by the calls on either — so the calls of one ctx keep their order across the switch.  The old
+ * stream must still exist at the switch. */
+int pt_set_stream(pt_ctx* ctx, void* hip_stream);
 int pt_set_option(pt_ctx* ctx, int option, int value);
 int pt_sync(pt_ctx* ctx);
 

@@ -152,6 +152,16 @@ def rays_for(soup, n, seed):
 COUNTERS = ("rays", "inner", "tris", "leaves", "hits", "paths")   # the work counters: test_gpu_root_cull, test_gpu_root_entry
 
 
+def set_options(t, pairs):
+    """The (option, value) pairs on a context that has no scene yet, in the order given.  The one ordering rule: an option is set
+    BEFORE the upload that reads it — PT_OPT_TRI_TEST, PT_OPT_LEAF_MAX, PT_OPT_REBUILD, PT_OPT_OPTIMIZE and PT_OPT_PRESPLIT before
+    pt_upload_bvh, PT_OPT_BUILD_ALGO and PT_OPT_LEAF_MAX before pt_build_bvh, PT_OPT_ENV_LIGHT before pt_upload_environment (which
+    PathTracer.upload_environment's `light` does itself) — and every other option is read by the calls, so all of them go on first and
+    the scene afterwards.  `pipeline_render` below and call_sequences.install."""
+    for o, v in pairs:
+        t.set_option(o, v)
+
+
 def pipeline_render(options, scene, W, H, spp, depth=4, flags=0, spheres=True, calls=1, prefill=False, counters=False, cam=None,
                     tri_emi=(0, 0, 0), tri_mat=g.MAT_DIFF, table=None, parts=1, cull=None, before_upload=()):
     """(accumulator, display words) after `calls` pt_render calls on a fresh context with PT_KERNEL_WAVEFRONT asked for and the
@@ -166,11 +176,7 @@ def pipeline_render(options, scene, W, H, spp, depth=4, flags=0, spheres=True, c
     launch (both report the last launch only; their keys do not collide)."""
     t = g.PathTracer(0)
     try:
-        t.set_option(g.OPT_KERNEL, g.KERNEL_WAVEFRONT)
-        for o, v in tuple(options) + tuple(before_upload):
-            t.set_option(o, v)
-        if counters:
-            t.set_option(g.OPT_COUNTERS, 1)
+        set_options(t, ((g.OPT_KERNEL, g.KERNEL_WAVEFRONT),) + tuple(options) + tuple(before_upload) + (((g.OPT_COUNTERS, 1),) if counters else ()))
         mesh = None
         if callable(scene):
             scene(t)
