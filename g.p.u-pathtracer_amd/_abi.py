@@ -105,6 +105,8 @@ OPT_ROOT_CULL = 30
 OPT_ROOT_ENTRY = 33   # (not re-exported by the package: gpu_pathtracer_amd._abi.OPT_ROOT_ENTRY)
 OPT_PATH_HISTORY = 34   # (not re-exported either)
 OPT_ENV_LIGHT = 35   # (not re-exported either: gpu_pathtracer_amd._abi.OPT_ENV_LIGHT, or upload_environment(light=True))
+OPT_LAST_OCCLUDERS = 36   # (not re-exported either)
+OCCLUDERS_MAX = 12   # PT_OCCLUDERS_MAX: the most ids pt_occluder_ids returns
 
 # every symbol include/ptmi.h declares: (name, restype, argtypes)
 _vp, _sz, _i, _u32 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32
@@ -142,6 +144,7 @@ PTMI_SYMBOLS = [
     ("pt_build_bvh", _i, [_vp, _vp, C.c_size_t, _vp, C.c_size_t]),
     ("pt_last_build_ms", _i, [_vp, C.POINTER(C.c_float)]),
     ("pt_refit_bvh", _i, [_vp, _vp, _sz, _vp]),
+    ("pt_occluder_ids", _i, [_vp, _sz, _vp, _sz, _vp, _i]),
     ("pt_upload_tri_materials", _i, [_vp, C.POINTER(Material), C.c_size_t, C.POINTER(C.c_int32), C.c_size_t]),
     ("pt_get_counters", _i, [_vp, C.POINTER(Counters)]),
     ("pt_get_wave_stats", _i, [_vp, C.POINTER(C.c_uint64), _i]),

@@ -19,6 +19,13 @@
 #ifndef PT_FIRST_WALK_DEFAULT
 #define PT_FIRST_WALK_DEFAULT 1
 #endif
+// most triangles a tree's occluder list holds (PT_OPT_LAST_OCCLUDERS; the sweep of profiles/r18_last_occluders.txt chose it)
+#ifndef PT_OCCLUDERS_MAX
+#define PT_OCCLUDERS_MAX 12
+#endif
+// ... and the share of the mesh's triangle area one of them has at least, as 1 / N: the walls of a room hold 6-8 % each and decide
+// most occluded last segments; the two ground triangles of gto_sixteen hold 3.1 % each and a list of them decides too few to pay
+#define PT_OCCLUDER_AREA_DIV 24
 
 // Everything that describes an acceleration structure.  A tree is a VALUE: the makers (pt_tree.hip, pt_build.hip) fill one inside a
 // DevTree without touching the context, and adopt_tree (pt_tree.hip) is the only code that writes pt_ctx::tree.  So
@@ -38,6 +45,10 @@ struct TreeState {
     int32_t max_tri_id = -1;     // largest original triangle id of the uploaded BVH
     float build_ms = -1.f;       // device time of the build behind this tree, -1: no device build stands behind it
     double opt_cost[2] = {0.0, 0.0};   // PT_OPT_OPTIMIZE: area cost (inner-node areas / root area) before / after, 0 when it did not run
+    // PT_OPT_LAST_OCCLUDERS: the ids of the mesh's largest triangles, largest first (select_occluders), chosen where the tree is adopted;
+    // the context's table (pt_ctx::d_occ) holds their records as THIS tree's item buffer has them
+    int32_t occ_ids[PT_OCCLUDERS_MAX] = {};
+    uint32_t n_occ = 0;
 };
 
 // A tree that owns its item buffer: whatever a maker allocated is released on every early return, and the loser of
@@ -121,6 +132,7 @@ struct pt_ctx {
     int opt_root_cull = 1;       // new rays the root node step turns away stay out of the extend queue: 0 off, 1 product launches, 2 instrumented too (PT_OPT_ROOT_CULL)
     int opt_root_entry = 1;      // ... and the walkers' records carry the root step's result, the extend launches start below the root: 0 off, 1 product launches, 2 instrumented too (PT_OPT_ROOT_ENTRY)
     int opt_env_light = 0;       // the next pt_upload_environment builds the map's sampling tables: under PT_FLAG_NEE it is a light (PT_OPT_ENV_LIGHT)
+    int opt_last_occluders = 1;  // last-segment walkers that one of the tree's largest triangles occludes stay out of the any-hit queue: 0 off, 1 product launches, 2 instrumented too (PT_OPT_LAST_OCCLUDERS)
     int opt_path_history = 1;    // the records carry the objects a path has hit instead of its mask, its sample colour is written once: 0 off, 1 product launches, 2 instrumented too (PT_OPT_PATH_HISTORY)
     // PT_KERNEL_AUTO: which stage layout is faster depends on the workload (long paths and many samples per call:
     // the stage-split pipeline; short paths or few samples: the persistent kernel), so the first FOUR calls of a
@@ -145,6 +157,9 @@ struct pt_ctx {
     // stream (PT_OPT_OVERLAP) waits for geom_ev before its first path kernel after one (the light list is re-collected too)
     uint64_t geom_gen = 0;
     hipEvent_t geom_ev = nullptr;
+    // PT_OPT_LAST_OCCLUDERS: the first three pieces of the records of tree.occ_ids, copied out of the tree's item buffer on the caller's
+    // stream by whoever writes those records: adopt_tree and pt_refit_bvh (occluders_collect).  3 float4 each, the last one's `last` set.
+    float4* d_occ = nullptr;
     // what the refit of one tree needs on the device, made by its first refit (pt_refit.hip) and released with the tree
     struct Refit {
         uint64_t scene_gen = 0;
@@ -251,6 +266,10 @@ inline bool path_history_holds(const KParams& P) {
         if (P.ksph[i].mat == PT_MAT_REFR) return false;
     return true;
 }
+// PT_OPT_LAST_OCCLUDERS: whether the shade launch that bounds the last segments (SHADE_BOUND, or the fused packet launch at depth 2) also
+// tests its walkers against the tree's occluder list: the any-hit launch runs behind it (that launch's own rule: WavePlan::anyhit), the
+// launch classifies its survivors at all (root cull: the decided lanes join the walk-free class), and the tree has a list.
+inline bool last_occluders_hold(const TreeState& t, bool anyhit_launch, bool root_cull) { return anyhit_launch && root_cull && t.n_occ > 0; }
 // The scene as a kernel sees it: one item buffer for nodes and records, the wide tree's root and, where ksph (KParams::ksph) is
 // given, the spheres: a ray-batch query sees none.  Zeroes the rest; the stack and LDS layout is the caller's.
 inline void scene_view(const pt_ctx* c, KScene& sc, pt_sphere_d* ksph = nullptr) {
@@ -381,6 +400,12 @@ int stage_mark(pt_ctx* c, int kind_of_work_since_last_mark);
 // PT_OPT_BUILD_ALGO 1 falls back to the LBVH inside when PLOC's tree gets too deep.  id_map: the id triangle t reports (default t)
 int build_bvh_impl(pt_ctx* c, const float* verts, size_t n_verts, const int32_t* tris, size_t n_tris, DevTree& out,
                    const int32_t* id_map = nullptr);
+// PT_OPT_LAST_OCCLUDERS (pt_tree.hip).  select_occluders: the rule — of the triangles (id, nine vertex floats; a triangle may be listed
+// more than once, each time in full) those whose area is at least 1/24 (PT_OCCLUDER_AREA_DIV) of the mesh's, largest first, ties to the smaller id, at most
+// `cap`; returns how many ids it wrote.  occluders_collect: copies the records of c->tree.occ_ids into c->d_occ on the context's stream.
+struct OccTri { int32_t id; const float *v0, *v1, *v2; };
+int select_occluders(std::vector<OccTri>& tris, int32_t* ids, int cap);
+int occluders_collect(pt_ctx* c);
 // pt_refit_bvh's per-tree state (pt_refit.hip): released where the tree is replaced (adopt_tree) or the context destroyed
 void refit_release(pt_ctx* c);
 // pt_denoise's and pt_frame_error's scratch (pt_denoise.hip)

@@ -381,6 +381,26 @@ __device__ __forceinline__ float2 wf_sphere_bound(const KParams& P, const PathSt
     return make_float2(sh.t, __int_as_float(sh.sph_id));
 }
 
+// PT_OPT_LAST_OCCLUDERS: whether one of the tree's occluders — the mesh's largest triangles, their records' first three pieces in the
+// table P.wf.s_con, fetched once per wave with scalar loads as trav_packet_wide fetches its items — answers the any-hit query of a
+// walker's last segment: the walk's test on the walk's record with trav_run_wide<.., ANY>'s acceptance (t > 0 && t < h.t, h.t the bound
+// the lane would start that walk with), so a positive verdict is one the walk reaches at the record's leaf.  The order in which an
+// any-hit query tries triangles does not matter.  The loop is wave-uniform: every lane of the wave calls it, `walker` set in the lanes
+// that ask, and it ends with the table or when no lane is left undecided.
+__device__ __forceinline__ bool wf_occluded(const KParams& P, bool walker, const PathState& ps, float ts) {
+    const float4* tab = P.wf.s_con;
+    const float t_max = wf_anyhit_start(ts);
+    const bool cull = P.cull != 0;
+    bool open = walker, hit = false;
+    for (int a = 0; a < 3 * PT_OCCLUDERS_MAX && __ballot(open) != 0ull; a += 3) {
+        const float4 q0 = pt_uld4(tab, a), q1 = pt_uld4(tab, a + 1), q2 = pt_uld4(tab, a + 2);
+        const float t = pt_mt_intersect(V3(q0.x, q0.y, q0.z), V3(q1.x, q1.y, q1.z), V3(q2.x, q2.y, q2.z), ps.o, ps.d, cull);
+        if (open && t > 0.0f && t < t_max) { hit = true; open = false; }
+        if (__float_as_int(q1.w) != 0) break;   // the list's last record
+    }
+    return hit;
+}
+
 // PT_OPT_ROOT_CULL: where a surviving path's record goes inside its region, in two classes that each keep the slot order — the
 // WALKERS at [0, n_walk), then the WALK-FREE records up to `total`: those whose new ray the next extend launch's first node step, on
 // the tree's root with the h.t the lane would start with (ts: the sphere bound of a BOUND launch's survivor), would leave without a
@@ -389,10 +409,15 @@ __device__ __forceinline__ float2 wf_sphere_bound(const KParams& P, const PathSt
 // bit — and the extend launch only draws a region's first n_walk records.  Every lane of the block calls it.
 // PT_OPT_ROOT_ENTRY: the rest of that step is kept too — the keys sorted as the walk sorts them, so the order is the walk's, ties
 // included — as the walker's entry code in `entry`, already at its place in ray1.w (0 without the option, and for the walk-free).
-template <bool BOUND>
+// OCCL (PT_OPT_LAST_OCCLUDERS; BOUND launches with root_cull on): a walker's ray is the path's last segment, an any-hit query, and any
+// accepted triangle answers it — so the lane tries the tree's occluder table first (wf_occluded) and a decided lane joins the walk-free
+// class with `occluded` set: its hit slot gets the verdict k_wf_extend<.., ANY> would have written.
+template <bool BOUND, bool OCCL = false>
 __device__ __forceinline__ int wf_survivor_slot(const KParams& P, bool alive, const PathState& ps, float ts, bool& walk_free, int& n_walk,
-                                                int& total, int* s_cnt, int* s_cnt_free, uint32_t& entry) {
+                                                int& total, int* s_cnt, int* s_cnt_free, uint32_t& entry, bool& occluded) {
+    static_assert(BOUND || !OCCL, "only a last segment is an any-hit query");
     walk_free = false;
+    occluded = false;
     entry = 0u;
     if (P.wf.root_cull) {   // (wave-uniform)
         const WideNode root = wide_node_load_uniform(P.sc, P.sc.wide_root);
@@ -408,6 +433,10 @@ __device__ __forceinline__ int wf_survivor_slot(const KParams& P, bool alive, co
                 entry = pt_entry_pack(n, key[0], key[1], key[2]) << PT_REC_ENTRY_SHIFT;
             }
         }
+    }
+    if constexpr (OCCL) {   // (every lane of the wave; the sort above was for nothing in a lane decided here)
+        occluded = wf_occluded(P, alive && !walk_free, ps, ts);
+        if (occluded) { walk_free = true; entry = 0u; }
     }
     const int r = PT_SURVIVOR_RANK(P, alive && !walk_free, ps, n_walk, s_cnt);
     total = n_walk;
@@ -436,7 +465,9 @@ __device__ __forceinline__ void wf_region_counts(const KParams& P, uint32_t regi
 // sphere bound goes to the survivor's hit slot for k_wf_extend<.., ANY> and k_wf_shade_last_any
 // HIST (PT_OPT_PATH_HISTORY, never NEE): plane 0 of the mask generations holds the path's history word instead of mask.x, the other two
 // planes are not touched; the lane rebuilds mask and accu from it, and the sample colour is written by the lane the path ends in
-template <bool COUNT, bool NEE, bool FIRST, bool LAST = false, int FOLD = 0, bool BOUND = false, bool HIST = false>
+// OCCL (PT_OPT_LAST_OCCLUDERS, BOUND only): the walkers among the survivors are tested against the tree's occluder table first
+// (wf_survivor_slot); an instrumented launch books the rays it decided
+template <bool COUNT, bool NEE, bool FIRST, bool LAST = false, int FOLD = 0, bool BOUND = false, bool HIST = false, bool OCCL = false>
 __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
     __shared__ int s_cnt[PT_BLOCK / 64];
     __shared__ int s_cnt2[PT_BLOCK / 64];
@@ -531,9 +562,17 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
         return;
     }
     int n_walk, total;
-    bool walk_free;
+    bool walk_free, occluded;
     uint32_t entry;
-    const int r = wf_survivor_slot<BOUND>(P, alive, ps, bound.x, walk_free, n_walk, total, s_cnt, s_cnt_free, entry);
+    const int r = wf_survivor_slot<BOUND, OCCL>(P, alive, ps, bound.x, walk_free, n_walk, total, s_cnt, s_cnt_free, entry, occluded);
+    if constexpr (OCCL) bound.x = occluded ? 0.0f : bound.x;   // k_wf_extend<.., ANY>'s verdict: t = 0 over ts, the sphere stays
+    if (COUNT && OCCL) {   // all 64 lanes of every wave are here; wf_region_counts books every walk-free ray as the root's
+        const unsigned long long no = (unsigned long long)__popcll(__ballot(occluded));
+        if ((threadIdx.x & 63) == 0 && no) {
+            atomicAdd(&P.counters[PT_CNT_OCCLUDED], no);
+            atomicAdd(&P.counters[PT_CNT_WALK_FREE], 0ull - no);
+        }
+    }
     if (alive) {
         const size_t j = (size_t)region * PT_REGION + (size_t)r;
         pt_sst4(P.wf.ray0_out + j, make_float4(ps.o.x, ps.o.y, ps.o.z, ps.d.x));
@@ -611,7 +650,8 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade_last_any(const KParams P)
 // computed twice — and the survivors are packed as k_wf_shade<FIRST> packs them (same records, same order).
 // BOUND: as k_wf_shade's (depth 2: bounce 0's survivors are the last segments).
 // HIST: as k_wf_shade's (a path that goes on leaves its first code and no sample colour).
-template <bool BOUND, bool HIST = false>
+// OCCL: as k_wf_shade's.
+template <bool BOUND, bool HIST = false, bool OCCL = false>
 __global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet_shade(const KParams P) {
     __shared__ int s_cnt[PT_BLOCK / 64];
     __shared__ int s_cnt_free[PT_BLOCK / 64];
@@ -638,9 +678,10 @@ __global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet_shade(const KP
     float2 bound = make_float2(PT_F32_MAX, __int_as_float(-1));
     if (BOUND && alive) bound = wf_sphere_bound(P, ps);
     int n_walk, total;
-    bool walk_free;
+    bool walk_free, occluded;
     uint32_t entry;
-    const int r = wf_survivor_slot<BOUND>(P, alive, ps, bound.x, walk_free, n_walk, total, s_cnt, s_cnt_free, entry);
+    const int r = wf_survivor_slot<BOUND, OCCL>(P, alive, ps, bound.x, walk_free, n_walk, total, s_cnt, s_cnt_free, entry, occluded);
+    if constexpr (OCCL) bound.x = occluded ? 0.0f : bound.x;   // (as k_wf_shade)
     if (alive) {
         const size_t j = (size_t)region * PT_REGION + (size_t)r;
         pt_sst4(P.wf.ray0_out + j, make_float4(ps.o.x, ps.o.y, ps.o.z, ps.d.x));
@@ -788,6 +829,10 @@ struct WavePlan {
     // shade lane rebuilds mask and accu from it, and a path's sample colour is written once, by the lane it ends in (path_history_holds).
     // Instrumented launches: with the value 2 only.
     bool history;
+    // PT_OPT_LAST_OCCLUDERS: the launch that bounds the last segments (SHADE_BOUND, or EXT_FUSED at depth 2) tests its walkers against the
+    // tree's occluder table and keeps the decided ones out of the any-hit launch's queue (last_occluders_hold).  Instrumented launches:
+    // with the value 2 only.
+    bool occluders;
     WaveExtend extend(uint32_t b, uint32_t depth) const {
         if (b == 0) return fuse_first ? EXT_FUSED : packet ? EXT_PACKET : EXT_FIRST;
         return anyhit && b + 1 == depth ? EXT_ANY : EXT_CLOSEST;
@@ -812,6 +857,7 @@ static WavePlan wave_plan(const pt_ctx* c, const KParams& P, const LaunchCfg& L,
                P.sc.n_spheres <= PT_KSPHERES && !c->tree.records_woop;
     p.root_cull = L.count ? c->opt_root_cull == 2 : c->opt_root_cull >= 1;
     p.history = (L.count ? c->opt_path_history == 2 : c->opt_path_history >= 1) && path_history_holds(P);
+    p.occluders = (L.count ? c->opt_last_occluders == 2 : c->opt_last_occluders >= 1) && last_occluders_hold(c->tree, p.anyhit, p.root_cull);
     p.root_entry = p.root_cull && !nee && P.spp < PT_REC_MAX_SAMPLES_ENTRY && (L.count ? c->opt_root_entry == 2 : c->opt_root_entry >= 1);
     return p;
 }
@@ -826,7 +872,9 @@ static hipError_t launch_extend(const WavePlan& p, WaveExtend kind, const KParam
     const size_t n_reg = (size_t)Q.wf.n_regions;
     if (kind == EXT_FUSED)   // (BOUND at depth 2: bounce 0's survivors are the last segments)
         return with_bool(p.history, [&](auto hist) {
-            return p.anyhit && Q.depth == 2 ? plain(k_wf_extend_packet_shade<true, hist()>, n_reg, WF_LDS_SHADE) : plain(k_wf_extend_packet_shade<false, hist()>, n_reg, WF_LDS_SHADE);
+            if (p.anyhit && Q.depth == 2)
+                return with_bool(p.occluders, [&](auto occl) { return plain(k_wf_extend_packet_shade<true, hist(), occl()>, n_reg, WF_LDS_SHADE); });
+            return plain(k_wf_extend_packet_shade<false, hist()>, n_reg, WF_LDS_SHADE);
         });
     if (kind == EXT_PACKET) {   // one block per region (4 groups); instrumented: the resident grid, 8 blocks per CU
 #ifdef PT_PACKET_RESIDENT_GRID   // experiment (tools/build_variant.sh): the product launch on the resident grid too
@@ -866,14 +914,14 @@ static hipError_t launch_shade(const WavePlan& p, WaveShade kind, bool first, co
         if (p.count) {   // (never SHADE_LAST, never a fold)
             if (kind == SHADE_LAST_ANY) return go(k_wf_shade_last_any<true, 0, hist()>);
             return with_bool(first, [&](auto f) {
-                if (kind == SHADE_BOUND) return go(k_wf_shade<true, false, f(), false, 0, true, hist()>);
+                if (kind == SHADE_BOUND) return with_bool(p.occluders, [&](auto occl) { return go(k_wf_shade<true, false, f(), false, 0, true, hist(), occl()>); });
                 return go(k_wf_shade<true, false, f(), false, 0, false, hist()>);
             });
         }
         if (kind == SHADE_LAST_ANY) return with_int<4, 2, 1, 0>(p.fold_lp, [&](auto lp) { return go(k_wf_shade_last_any<false, lp(), hist()>); });
         if (kind == SHADE_LAST) return with_int<4, 2, 1, 0>(p.fold_lp, [&](auto lp) { return go(k_wf_shade<false, false, false, true, lp(), false, hist()>); });
         return with_bool(first, [&](auto f) {
-            if (kind == SHADE_BOUND) return go(k_wf_shade<false, false, f(), false, 0, true, hist()>);
+            if (kind == SHADE_BOUND) return with_bool(p.occluders, [&](auto occl) { return go(k_wf_shade<false, false, f(), false, 0, true, hist(), occl()>); });
             return go(k_wf_shade<false, false, f(), false, 0, false, hist()>);
         });
     });
@@ -897,7 +945,7 @@ int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles, 
         P.wf.s_con = (float4*)(buf.nee + 2 * w.b_ray);
         P.wf.s_hit = (float2*)(buf.nee + 3 * w.b_ray);
         P.wf.s_cnt = (int*)(buf.nee + 3 * w.b_ray + w.b_hit);
-    }
+    } else P.wf.s_con = plan.occluders ? c->d_occ : nullptr;   // (the table of the tree on the context: occluders_collect)
 
     hipStream_t st = c->stream;
     P.sc.n_top = 0;

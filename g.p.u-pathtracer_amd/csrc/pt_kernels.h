@@ -136,7 +136,8 @@ struct KWave {
     // extend launch and resolved by k_wf_resolve: s_ray0/s_ray1 as ray0/ray1, s_con = (contribution rgb, t_max), s_hit
     float4* __restrict__ s_ray0;
     float4* __restrict__ s_ray1;
-    float4* __restrict__ s_con;
+    float4* __restrict__ s_con;   // without PT_FLAG_NEE: the tree's occluder table when the call tests it (PT_OPT_LAST_OCCLUDERS), read only:
+                                  // 3 float4 per occluder = the first three pieces of its record, the last one's `last` flag set
     float2* __restrict__ s_hit;
     int* __restrict__ s_cnt;
     int nee;                      // 1: ray1.z carries pixel | nee_mask << 24
@@ -248,6 +249,7 @@ enum {
     PT_CNT_IT_BEGIN, PT_CNT_ACT_BEGIN,   // path-start (pipeline: refill) passes, lanes
     PT_CNT_IT_LOOP, PT_CNT_STACK_OVF,    // outer-loop iterations, pushes past the LDS window
     PT_CNT_WALK_FREE,                    // pipeline: rays kept out of the extend queue (PT_OPT_ROOT_CULL 2)
+    PT_CNT_OCCLUDED,                     // pipeline: last-segment rays an occluder decided in the shade stage (PT_OPT_LAST_OCCLUDERS 2)
     PT_CNT_N,
     PT_CNT_PACKET_GROUPS = PT_CNT_IT_SHADE,   // pipeline: 64-ray groups the bounce-0 packet walk walked
     PT_CNT_ANY_RAYS = PT_CNT_ACT_SHADE        // pipeline: rays of the any-hit launch (PT_OPT_LAST_ANYHIT 2)

@@ -379,6 +379,9 @@ extern "C" int pt_refit_bvh(pt_ctx* c, const float* tri_verts_dev, size_t n_tris
                            R.wide_list + R.wide_off[ht], nw);
     }
     HIP_TRY(c, hipGetLastError());
+    // PT_OPT_LAST_OCCLUDERS: the listed triangles' records moved with the rest; their copies follow on the same stream, so no call
+    // behind this one tests the old vertices (the list keeps its ids: it is the mesh's by area at adoption)
+    if (const int rc = occluders_collect(c); rc != PT_OK) { c->tree.n_occ = 0; return rc; }
     HIP_TRY(c, span_end(c));
     // a path kernel on a side stream (PT_OPT_OVERLAP) waits for this before it reads the tree; the light list is collected again
     if (!c->geom_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->geom_ev, hipEventDisableTiming));

@@ -62,7 +62,63 @@ extern "C" __global__ void __launch_bounds__(256) k_tree_cost(const float4* __re
     if (i == 0) out[0] = root;
 }
 
+// PT_OPT_LAST_OCCLUDERS: one lane per record; a record of listed triangle k goes to slot k of the table as its first three pieces, the
+// `last` flag set on the list's final slot alone (the shade lanes' loop ends there, as a leaf's does).  A triangle a spatial split lists
+// more than once is listed in full each time: the copies write the same values.
+struct OccList { int32_t id[PT_OCCLUDERS_MAX]; uint32_t n = 0; };
+__global__ void __launch_bounds__(256) k_collect_occluders(const float4* __restrict__ rec, uint32_t n_rec, const OccList L, float4* __restrict__ table) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_rec) return;
+    const float4 q0 = rec[4 * (size_t)i];
+    const int id = __float_as_int(q0.w);
+    for (uint32_t k = 0; k < L.n; k++) {
+        if (L.id[k] != id) continue;
+        const float4 q1 = rec[4 * (size_t)i + 1], q2 = rec[4 * (size_t)i + 2];
+        table[3 * k + 0] = q0;
+        table[3 * k + 1] = make_float4(q1.x, q1.y, q1.z, __int_as_float(k + 1 == L.n ? 1 : 0));
+        table[3 * k + 2] = q2;
+    }
+}
+
 namespace ptmi {
+int select_occluders(std::vector<OccTri>& tris, int32_t* ids, int cap) {
+    std::stable_sort(tris.begin(), tris.end(), [](const OccTri& a, const OccTri& b) { return a.id < b.id; });
+    tris.erase(std::unique(tris.begin(), tris.end(), [](const OccTri& a, const OccTri& b) { return a.id == b.id; }), tris.end());
+    // half the length of e1 x e2 in binary64, from the binary32 vertices; the mesh's area summed in id order: reproducible
+    std::vector<double> area(tris.size());
+    double total = 0.0;
+    for (size_t i = 0; i < tris.size(); i++) {
+        const OccTri& t = tris[i];
+        const double a[3] = {(double)t.v1[0] - t.v0[0], (double)t.v1[1] - t.v0[1], (double)t.v1[2] - t.v0[2]};
+        const double b[3] = {(double)t.v2[0] - t.v0[0], (double)t.v2[1] - t.v0[1], (double)t.v2[2] - t.v0[2]};
+        const double x = a[1] * b[2] - a[2] * b[1], y = a[2] * b[0] - a[0] * b[2], z = a[0] * b[1] - a[1] * b[0];
+        area[i] = 0.5 * std::sqrt(x * x + y * y + z * z);
+        total += area[i];
+    }
+    std::vector<size_t> big;   // (at most PT_OCCLUDER_AREA_DIV can qualify)
+    for (size_t i = 0; i < tris.size(); i++)
+        if (area[i] * (double)PT_OCCLUDER_AREA_DIV >= total && area[i] > 0.0) big.push_back(i);
+    std::stable_sort(big.begin(), big.end(), [&](size_t a, size_t b) { return area[a] > area[b]; });   // (stable: ties keep the id order)
+    const int n = (int)std::min<size_t>(big.size(), (size_t)std::max(cap, 0));
+    for (int k = 0; k < n; k++) ids[k] = tris[big[(size_t)k]].id;
+    return n;
+}
+
+int occluders_collect(pt_ctx* c) {
+    const TreeState& t = c->tree;
+    if (t.n_occ == 0 || !t.has_bvh || t.records_woop) return PT_OK;
+    if (!c->d_occ) HIP_TRY(c, hipMalloc((void**)&c->d_occ, 3 * PT_OCCLUDERS_MAX * sizeof(float4)));
+    OccList L;
+    L.n = t.n_occ;
+    std::memcpy(L.id, t.occ_ids, sizeof L.id);
+    const uint32_t n_rec = (uint32_t)t.n_refs;
+    // (a slot whose triangle the tree holds no record of stays all zero: a record no ray hits)
+    HIP_TRY(c, hipMemsetAsync(c->d_occ, 0, 3 * PT_OCCLUDERS_MAX * sizeof(float4), c->stream));
+    hipLaunchKernelGGL(k_collect_occluders, dim3((n_rec + 255) / 256), dim3(256), 0, c->stream, t.d_nodes + 4 * (size_t)t.n_inner, n_rec, L, c->d_occ);
+    HIP_TRY(c, hipGetLastError());
+    return PT_OK;
+}
+
 // ---- makers: none reads or writes the context's tree, refit state or generations ------------------------------------------------
 
 // the area cost of the 4-wide tree of `t` (Moller-Trumbore records), in expected node visits / triangle tests of a random ray
@@ -146,14 +202,21 @@ static int optimise_device_tree(pt_ctx* c, DevTree& tree, const float* soup, con
 }
 
 // ---- adoption: the only writer of pt_ctx::tree (pt_destroy frees it) ----------------------------------------------------------------
-static int adopt_tree(pt_ctx* c, DevTree&& t) {
+// `occ`: the occluder list of the mesh the tree was made of (PT_OPT_LAST_OCCLUDERS; Woop records are not what the list's test reads).
+// The list and its table change with the tree and scene_gen: the old tree's table is overwritten behind the wait below, on the stream
+// every later launch of the context is ordered behind.  Should the copy fail the tree stands without a list.
+static int adopt_tree(pt_ctx* c, DevTree&& t, const OccList& occ) {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));   // nothing in flight reads the old tree
     refit_release(c);   // made for the old tree (pt_refit_bvh makes it again for this one)
     (void)hipFree(c->tree.d_nodes);
     c->tree = t.release();
     c->scene_gen++;
-    return PT_OK;
+    c->tree.n_occ = c->tree.records_woop ? 0u : occ.n;
+    std::memcpy(c->tree.occ_ids, occ.id, sizeof occ.id);
+    const int rc = occluders_collect(c);
+    if (rc != PT_OK) c->tree.n_occ = 0;
+    return rc;
 }
 }  // namespace ptmi
 
@@ -185,6 +248,13 @@ int pt_upload_bvh(pt_ctx* c, const float* nodes, size_t n_node_vec4, const float
     for (const ptscene::Ref& r : T.refs) max_id = std::max(max_id, r.id);
     if (c->d_tri_matid && (size_t)max_id >= c->n_tri_matid)
         return fail(c, PT_ERR_INVALID, "pt_upload_bvh: the triangle-material array on this context does not cover this BVH's triangle ids (clear or re-upload it first)");
+    OccList occ;   // (from the parsed tree too, before a maker re-arranges its references)
+    {
+        std::vector<OccTri> soup;
+        soup.reserve(T.refs.size());
+        for (const ptscene::Ref& r : T.refs) soup.push_back({r.id, r.v, r.v + 3, r.v + 6});
+        occ.n = (uint32_t)select_occluders(soup, occ.id, PT_OCCLUDERS_MAX);
+    }
     const int rebuild = c->opt_tri_test == 0 ? c->opt_rebuild : 0;
     // PT_OPT_REBUILD: keep the caller's TRIANGLES, not its hierarchy — the distinct triangles of the
     // Compact arrays (a spatial-split builder lists some more than once, each time in full), in id order,
@@ -221,7 +291,7 @@ int pt_upload_bvh(pt_ctx* c, const float* nodes, size_t n_node_vec4, const float
         if (reclustered(b) == PT_OK && tree_cost(c, b.s, &cost_b, &unused) == PT_OK && cost_b < cost_a) a = std::move(b);
         else c->err.clear();
     }
-    return adopt_tree(c, std::move(a));
+    return adopt_tree(c, std::move(a), occ);
 }
 
 // ---- pt_build_bvh: the BVH built on the device (pt_build.h) ---------------------------------
@@ -234,7 +304,26 @@ int pt_build_bvh(pt_ctx* c, const float* verts, size_t n_verts, const int32_t* t
         for (size_t i = 0; i < 3 * n_tris; i++) std::memcpy(&flat[3 * i], verts + 3 * (size_t)tris[i], 3 * sizeof(float));
         rc = optimise_device_tree(c, t, flat.data(), nullptr, n_tris);
     }
-    return rc == PT_OK ? adopt_tree(c, std::move(t)) : rc;
+    if (rc != PT_OK) return rc;
+    OccList occ;   // (the build checked the indices)
+    {
+        std::vector<OccTri> soup(n_tris);
+        for (size_t i = 0; i < n_tris; i++)
+            soup[i] = {(int32_t)i, verts + 3 * (size_t)tris[3 * i], verts + 3 * (size_t)tris[3 * i + 1], verts + 3 * (size_t)tris[3 * i + 2]};
+        occ.n = (uint32_t)select_occluders(soup, occ.id, PT_OCCLUDERS_MAX);
+    }
+    return adopt_tree(c, std::move(t), occ);
+}
+
+int pt_occluder_ids(const float* verts, size_t n_verts, const int32_t* tris, size_t n_tris, int32_t* ids_out, int cap) {
+    if (!verts || !tris || !ids_out || cap < 0) return fail(nullptr, PT_ERR_INVALID, "pt_occluder_ids: null array or negative cap");
+    std::vector<OccTri> soup(n_tris);
+    for (size_t i = 0; i < n_tris; i++) {
+        for (int k = 0; k < 3; k++)
+            if (tris[3 * i + k] < 0 || (size_t)tris[3 * i + k] >= n_verts) return fail(nullptr, PT_ERR_INVALID, "pt_occluder_ids: vertex index out of range");
+        soup[i] = {(int32_t)i, verts + 3 * (size_t)tris[3 * i], verts + 3 * (size_t)tris[3 * i + 1], verts + 3 * (size_t)tris[3 * i + 2]};
+    }
+    return select_occluders(soup, ids_out, std::min(cap, PT_OCCLUDERS_MAX));
 }
 
 int pt_last_build_ms(pt_ctx* c, float* ms) {

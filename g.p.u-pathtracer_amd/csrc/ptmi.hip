@@ -107,6 +107,7 @@ static const OptionRow OPTIONS[] = {
     {PT_OPT_LAST_ANYHIT, &pt_ctx::opt_last_anyhit, OptionRow::RANGE, {0, 2}, PT_ERR_INVALID, "pt_set_option: last any-hit must be 0 (off), 1 (product launches) or 2 (instrumented launches too)"},
     {PT_OPT_ROOT_CULL, &pt_ctx::opt_root_cull, OptionRow::RANGE, {0, 2}, PT_ERR_INVALID, "pt_set_option: root cull must be 0 (off), 1 (product launches) or 2 (instrumented launches too)"},
     {PT_OPT_ROOT_ENTRY, &pt_ctx::opt_root_entry, OptionRow::RANGE, {0, 2}, PT_ERR_INVALID, "pt_set_option: root entry must be 0 (off), 1 (product launches) or 2 (instrumented launches too)"},
+    {PT_OPT_LAST_OCCLUDERS, &pt_ctx::opt_last_occluders, OptionRow::RANGE, {0, 2}, PT_ERR_INVALID, "pt_set_option: last occluders must be 0 (off), 1 (product launches) or 2 (instrumented launches too)"},
     {PT_OPT_ENV_LIGHT, &pt_ctx::opt_env_light, OptionRow::RANGE, {0, 1}, PT_ERR_INVALID, "pt_set_option: env light must be 0 (the map is no light) or 1 (sampled under PT_FLAG_NEE)"},
     {PT_OPT_PATH_HISTORY, &pt_ctx::opt_path_history, OptionRow::RANGE, {0, 2}, PT_ERR_INVALID, "pt_set_option: path history must be 0 (off), 1 (product launches) or 2 (instrumented launches too)"},
 };
@@ -158,6 +159,7 @@ int pt_destroy(pt_ctx* c) {
     (void)hipFree(c->d_mat_table);
     (void)hipFree(c->d_light_slot);
     (void)hipFree(c->d_tri_lights);
+    (void)hipFree(c->d_occ);
     (void)hipFree(c->d_counters);
     (void)hipFree(c->d_queue);
     (void)hipFree(c->d_samples);

@@ -321,11 +321,11 @@ class PathTracer:
     def wave_stats(self):
         """pt_get_wave_stats of the last instrumented launch.  Under PT_KERNEL_WAVEFRONT "it_shade" holds the 64-ray groups walked by
         the bounce-0 packet walk (PT_OPT_FIRST_WALK 1; include/ptmi.h), not shading passes; "walk_free" the rays PT_OPT_ROOT_CULL 2 kept
-        out of the extend queue."""
-        out = (C.c_uint64 * 11)()
-        self._check(self._lib.pt_get_wave_stats(self._ctx, out, 11))
+        out of the extend queue, "occluded" the last-segment rays PT_OPT_LAST_OCCLUDERS 2 decided in the shade stage."""
+        out = (C.c_uint64 * 12)()
+        self._check(self._lib.pt_get_wave_stats(self._ctx, out, 12))
         names = ("it_node", "act_node", "it_rec", "act_rec", "it_shade", "act_shade", "it_begin", "act_begin", "it_loop", "stack_overflows",
-                 "walk_free")
+                 "walk_free", "occluded")
         return dict(zip(names, [int(v) for v in out]))
 
     def last_build_ms(self):

@@ -258,9 +258,20 @@ enum {
                                  8 spheres, no PT_MAT_REFR triangle material or sphere, depth <= 9; any other call keeps the three
                                  mask planes and the in-place adds.  1 (default) = product launches do so; 2 = instrumented
                                  (PT_OPT_COUNTERS) launches too; 0 = off.  No counter changes under any value.  Same images         */
-    PT_OPT_ENV_LIGHT = 35     /* read by the next pt_upload_environment: 0 (default) = the map is what a miss gathers and nothing
+    PT_OPT_ENV_LIGHT = 35,    /* read by the next pt_upload_environment: 0 (default) = the map is what a miss gathers and nothing
                                  else; 1 = the map also gets a sampling distribution and is a LIGHT under PT_FLAG_NEE (see the
                                  environment section).  Any other value PT_ERR_INVALID                                            */
+    PT_OPT_LAST_OCCLUDERS = 36 /* PT_KERNEL_WAVEFRONT with PT_OPT_LAST_ANYHIT and PT_OPT_ROOT_CULL on for the call: the last segment
+                                 only asks whether SOME triangle lies at t <= ts, so the shade lane that makes the ray first tests it
+                                 against the mesh's largest triangles (pt_occluder_ids: the walls of a room), read from a small table
+                                 with scalar loads, with the walk's own test on the walk's own records.  A ray one of them occludes is
+                                 packed with the rays the root turns away and gets the verdict the any-hit walk would have written;
+                                 it is never queued.  A mesh without such triangles has no list and runs the launches it ran before.
+                                 pt_refit_bvh copies the listed triangles' moved records on its stream.  1 (default) = product
+                                 launches do so; 2 = instrumented (PT_OPT_COUNTERS) launches too (with PT_OPT_LAST_ANYHIT 2 and
+                                 PT_OPT_ROOT_CULL 2): `rays` still counts those rays, pt_get_wave_stats [11] is their number, [5] and
+                                 `inner`, `tris`, `leaves` lack their walks; 0 = off.  With 0 or 1 the counters are unchanged.
+                                 Same images                                                                                    */
 };
 
 /* CamInfo, GpuPathTracer/CpuStructs.hpp:19-28 (pitch/yaw/dirty/bias/enabled are host-only
@@ -394,6 +405,12 @@ int pt_last_build_ms(pt_ctx* ctx, float* ms_out);   /* device time of the build 
  * generation are unchanged.  Every tree this library installs has an inner root (pt_build_bvh doubles a lone triangle); a
  * tree without the [binary nodes][records][wide nodes] layout would give PT_ERR_UNSUPPORTED. */
 int pt_refit_bvh(pt_ctx* ctx, const float* tri_verts_dev, size_t n_tris, uint32_t* n_dropped_dev);
+/* The occluder list pt_upload_bvh and pt_build_bvh choose for a mesh (PT_OPT_LAST_OCCLUDERS), host only, no context: the triangles
+ * whose area (half |e1 x e2|, binary64 from the binary32 vertices) is at least 1/24 of the mesh's (summed in id order), largest first,
+ * equal areas by the smaller id, at most min(cap, 12).  Writes their ids to ids_out and returns their number (0: no list, as for a
+ * mesh without walls); PT_ERR_INVALID for a NULL array, a negative cap or an index >= n_verts.  pt_upload_bvh applies the rule to the
+ * distinct triangle ids of its Compact arrays. */
+int pt_occluder_ids(const float* verts, size_t n_verts, const int32_t* tris, size_t n_tris, int32_t* ids_out, int cap);
 
 /* Per-triangle materials — an EXTENSION.  The reference parses the .mtl into
  * `materials` but never reads it (utilfun.cpp:458-462) and shades every triangle with the ONE
@@ -748,8 +765,10 @@ int pt_get_counters(pt_ctx* ctx, pt_counters* out);
  * packet walk (PT_OPT_FIRST_WALK 1) walked — 0 when bounce 0 ran the per-lane walk — and that
  * launch books its wave node / record steps and the lanes of their masks in [0]-[3].
  * [10] PT_KERNEL_WAVEFRONT with PT_OPT_ROOT_CULL 2: the rays the shade stage kept out of the extend queue (they
- * are part of pt_counters.rays, not of [5]); 0 everywhere else. */
-#define PT_WAVE_STATS 11
+ * are part of pt_counters.rays, not of [5]); 0 everywhere else.
+ * [11] PT_KERNEL_WAVEFRONT with PT_OPT_LAST_OCCLUDERS 2: the last-segment rays one of the tree's occluders decided in the shade stage
+ * (part of pt_counters.rays, not of [5] or [10]); 0 everywhere else. */
+#define PT_WAVE_STATS 12
 int pt_get_wave_stats(pt_ctx* ctx, uint64_t* out, int n);
 int pt_last_kernel_ms(pt_ctx* ctx, float* ms_out);   /* needs PT_OPT_TIMING=1 */
 /* Device time of the last timed pt_render (PT_OPT_TIMING=1) by stage, from HIP events recorded on the
