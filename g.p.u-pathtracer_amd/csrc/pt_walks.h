@@ -479,6 +479,8 @@ __device__ __forceinline__ bool trav_run_wide(TravState& s, const KScene& sc, v3
                 last = __float_as_int(q1.w) != 0;
             }
             if constexpr (ANY) {
+                // the follow-up records below are tested with pt_mt_intersect whatever WOOP says
+                static_assert(!WOOP, "trav_run_wide: the any-hit branch reads Moller-Trumbore records only");
                 bool occ = t > 0.0f && t < h.t;
                 int aa = a;
                 if (AHEAD && !last && !occ) {   // the record requested ahead

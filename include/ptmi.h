@@ -212,7 +212,15 @@ enum {
                                  for Moller-Trumbore, what the reference kernel runs
                                  (cudaUtils.h:135-172; default, bit-exact vs the oracle);
                                  1 = Woop affine rows (north_star; CudaBVH.cpp:274-305 done
-                                 right), tolerance-class parity, wide walk only               */
+                                 right), tolerance-class parity, wide walk only.  Tolerance-class
+                                 parity: the triangle a ray reports agrees with exact geometry
+                                 outside the margins tests/woop_ref.py derives from the test's
+                                 rounding steps (du = 6 * 2^-24 * (|rx.w| + sum |o_i rx_i| +
+                                 |t| sum |d_i rx_i|) + t's own error); dyadic axis-plane geometry
+                                 (unit axis edges, integer translations) is exact.  The margin
+                                 grows with |v2| / edge length (the cancellation in rx.w +
+                                 dot(o, rx)): measured median du 2.2e-5 on bunny_low at the
+                                 origin, 1.7e-2 moved by (2^10, -2^12, 2^8)        */
     PT_OPT_LEAF_MAX = 9,      /* leaves holding more triangle references than this are split
                                  at the next pt_upload_bvh (0 = keep the producer's leaves;
                                  default 2)                                                   */

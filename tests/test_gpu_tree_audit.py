@@ -7,7 +7,8 @@ Audit level per tree kind (README of the checks: tree_audit.audit):
   ... optimised on the host (PT_OPT_OPTIMIZE)        shape, records, containment, coverage
   pt_upload_bvh of the host builder's hierarchy      shape, records, containment, coverage (its spatial splits clip leaf boxes)
   PT_OPT_PRESPLIT                                    shape, records, containment, coverage; n_tri_refs > n_tris
-  Woop records (PT_OPT_TRI_TEST 1)                   shape and containment of the node part only: the records are not restated
+  Woop records (PT_OPT_TRI_TEST 1)                   shape and containment of the node part; the records against the restated encoder
+                                                     (1 ulp per row float, N and the id word exact) and against their own vertices
   any tree after pt_refit_bvh                        strict against the moved soup (+ coverage after the twist)
 Two checks are narrower on device-built trees, for reasons in the builder's code: with PT_OPT_LEAF_MAX > 1 the binary section keeps
 the nodes below its multi-record leaves (ptb_is_cut, pt_build.h: unreachable, n_inner is the section's size) and max_depth counts
@@ -160,9 +161,11 @@ def test_host_route(t, name, leaf_max, optimize, rebuild):
 
 
 @pytest.mark.parametrize("name", ["cornell", "gto_sixteen"])
-def test_woop_records_node_part_only(t, name):
-    """Woop rows are made in binary64 on the host and not restated here: shape, counts and containment of the NODE part only (the
-    wide boxes against the binary tree's leaf boxes); neither records nor coverage."""
+def test_woop_records(t, name):
+    """Woop rows are made in binary64 on the host.  The node part: shape, counts and containment (the wide boxes against the binary
+    tree's leaf boxes).  The record part (tree_audit.audit, woop=True): every row float within 1 ulp of the restated encoder's
+    (tree_audit.encode_woop_records), N and the id << 1 | last word bit for bit, and the stored rows, taken in binary64, send the
+    triangle's own vertices to (1,0,0), (0,1,0), (0,0,0) within 2^-24 per entry times the magnitudes summed.  No coverage."""
     t.set_option(g.OPT_TRI_TEST, 1)
     t.upload_bvh(host_bvh(name))
     check(t, soup_of(name), f"{name} woop", woop=True, split_refs=True, leaf_max=2)

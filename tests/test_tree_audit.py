@@ -452,3 +452,55 @@ def test_the_restated_encoder_contains_and_is_tight():
                 assert np.all(qlo == 255) and np.all(qhi == 0) and d.view(np.int32)[10 + k] == -8
                 continue
             assert np.all(ta.fma32_fast(qlo, step, origin) <= lo[k]) and np.all(ta.fma32_fast(qhi, step, origin) >= hi[k])
+
+
+# ----------------------------------------------------------------------------------------------------------- Woop records
+def woop_tree(tree):
+    """the tree with its records restated as Woop records (PT_OPT_TRI_TEST 1): same ids, same runs"""
+    soup, B, R, W, info, wd = tree
+    Ri = R.view(np.int32)
+    return ta.encode_woop_records(soup[Ri[:, 3]], Ri[:, 3], Ri[:, 7])
+
+
+def test_the_valid_tree_passes_with_woop_records(tree):
+    stats = {}
+    assert run(tree, R=woop_tree(tree), woop=True, stats=stats) == []
+    assert stats == dict(woop_floats=12 * len(tree[2]), woop_floats_differ=0)
+
+
+def test_woop_rows_send_the_vertices_to_the_unit_points(tree):
+    """what the audit's identity check rests on, seen from outside it: in binary64 the rows are M^-1 to a few ulp of binary32"""
+    soup, R = tree[0], woop_tree(tree)
+    ids = R.view(np.int32)[:, 15] >> 1
+    v = soup[ids].astype(np.float64).reshape(-1, 3, 3)
+    r = R.astype(np.float64)
+    u = np.einsum("ni,nki->nk", r[:, 4:7], v) + r[:, 7:8]
+    w = np.einsum("ni,nki->nk", r[:, 8:11], v) + r[:, 11:12]
+    z = np.einsum("ni,nki->nk", r[:, 0:3], v) - r[:, 3:4]
+    assert np.allclose(u, [[1, 0, 0]], atol=1e-4) and np.allclose(w, [[0, 1, 0]], atol=1e-4) and np.allclose(z, 0, atol=1e-4)
+
+
+@pytest.mark.parametrize("what", ["rows-swapped", "translation-sign", "two-ulp", "normal-one-ulp", "id-word", "last-bit-into-id"])
+def test_a_wrong_woop_record_is_reported(tree, what):
+    R = woop_tree(tree).copy()
+    Ri = R.view(np.int32)
+    j = 5
+    if what == "rows-swapped":
+        R[j, 4:12] = R[j, [8, 9, 10, 11, 4, 5, 6, 7]]
+    elif what == "translation-sign":
+        R[j, 7] = -R[j, 7]
+    elif what == "two-ulp":
+        Ri[j, 9] += 2
+    elif what == "normal-one-ulp":
+        Ri[j, 13] += 1
+    elif what == "id-word":
+        other = next(k for k in range(len(R)) if (Ri[k, 15] & 1) == (Ri[j, 15] & 1) and k != j)
+        Ri[j, 15], Ri[other, 15] = Ri[other, 15], Ri[j, 15]
+    else:
+        Ri[j, 15] = Ri[j, 15] >> 1     # the bare id where id << 1 | last belongs
+    v = run(tree, R=R, woop=True)
+    assert kinds(v) & {"woop-rows", "woop-record", "ids", "partition", "containment", "leaf-size"}, v
+    if what in ("rows-swapped", "translation-sign"):
+        assert "woop-rows" in kinds(v)
+    if what in ("two-ulp", "normal-one-ulp"):
+        assert kinds(v) == {"woop-record"}

@@ -10,7 +10,8 @@ every element whose binary64 sum sits exactly on a binary32 tie (or below the no
 numbers and rounding is monotonic, so a binary64 sum that is NOT a tie lies on the same side of every tie as the exact sum and
 rounds to the same binary32.  The fast path therefore returns fma32's bits for every input, at any triangle count.
 
-The encoders of csrc/pt_items.h are restated here (encode_records, encode_wide_node): float64 where the C uses double, fma32
+The encoders of csrc/pt_items.h are restated here (encode_records, encode_wide_node), and emit()'s Woop record of
+csrc/pt_scene_build.h (encode_woop_records): float64 where the C uses double, fma32
 where it uses fmaf, numpy's binary32 operators (one IEEE rounding each) for the rest.
 """
 import math
@@ -68,7 +69,8 @@ def fma32_fast(a, b, c):
         s = a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)   # the product is exact (48 bits), the sum rounds once
         out = s.astype(np.float32)
     bits = np.ascontiguousarray(s).view(np.int64)
-    redo = ((bits & ((1 << 29) - 1)) == (1 << 28)) | ~np.isfinite(s) | (np.abs(s) < 2.0 ** -125) | ~np.isfinite(out)
+    # (an exact zero needs no second look: the product is exact and a binary64 sum is zero only when the exact sum is, with IEEE's sign)
+    redo = ((bits & ((1 << 29) - 1)) == (1 << 28)) | ~np.isfinite(s) | ((np.abs(s) < 2.0 ** -125) & (s != 0)) | ~np.isfinite(out)
     out = np.array(out, np.float32)
     for i in zip(*np.nonzero(redo)):
         out[i] = fma32(a[i], b[i], c[i])
@@ -111,6 +113,42 @@ def encode_records(v, ids, last):
     o = out.view(np.int32)
     o[:, 3], o[:, 7] = ids, last
     return out
+
+
+def encode_woop_records(v, ids, last):
+    """emit()'s Woop record (csrc/pt_scene_build.h, PT_OPT_TRI_TEST 1) over rows v (float32 [n][9], v0.x's -0.0 -> +0.0 as the host
+    tree stores it): float32 [n][16] = [row z, -translation z][row x, translation x][row y, translation y][N, id << 1 | last].
+    The rows are those of M^-1, M = columns (a, b, n, v2), a = v0 - v2, b = v1 - v2, n = a x b: (b x n, n x a, n) / |n|^2, every
+    step in binary64 in emit()'s own order (its translation unit is compiled without contraction), rounded once to binary32; a
+    triangle with |n|^2 == 0 gets zero rows.  N = cross(v0 - v1, v0 - v2) in the kernels' vcross arithmetic, as in encode_records."""
+    v = np.array(v, np.float32).reshape(-1, 9)
+    v[:, 0] = np.where(v[:, 0] == 0, np.float32(0.0), v[:, 0])
+    out = np.zeros((len(v), 16), np.float32)
+    out[:, 12:15] = encode_records(v, 0, 0)[:, 12:15]
+    d = v.astype(np.float64)
+    v0, v1, v2 = d[:, 0:3], d[:, 3:6], d[:, 6:9]
+
+    def cross(p, q):
+        return np.stack([p[:, 1] * q[:, 2] - p[:, 2] * q[:, 1], p[:, 2] * q[:, 0] - p[:, 0] * q[:, 2], p[:, 0] * q[:, 1] - p[:, 1] * q[:, 0]], 1)
+
+    with np.errstate(all="ignore"):
+        A, B = v0 - v2, v1 - v2
+        n = cross(A, B)
+        nn = n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1] + n[:, 2] * n[:, 2]
+        ok = (nn > 0.0)[:, None]
+        den = np.where(ok, nn[:, None], 1.0)
+        rows = [np.where(ok, r / den, 0.0) for r in (cross(B, n), cross(n, A), n)]
+        tr = [-(r[:, 0] * v2[:, 0] + r[:, 1] * v2[:, 1] + r[:, 2] * v2[:, 2]) for r in rows]
+        out[:, 0:3], out[:, 3] = rows[2], -tr[2]
+        out[:, 4:7], out[:, 7] = rows[0], tr[0]
+        out[:, 8:11], out[:, 11] = rows[1], tr[1]
+    out.view(np.int32)[:, 15] = (np.asarray(ids, np.int64) << 1 | np.asarray(last, np.int64)).astype(np.int32)
+    return out
+
+
+def _ordered_bits(x):
+    i = _bits(x).astype(np.int64)
+    return np.where(i < 0, -(i & 0x7FFFFFFF), i)
 
 
 def tri_boxes(v):
@@ -272,7 +310,7 @@ def _inside(outer, inner):
 
 
 def audit(binary, records, wide, info, soup, wide_depth, leaf_max=0, split_refs=False, strict=False, coverage=False,
-          cut_subtrees=False, depth_exact=True, woop=False, dropped=None, max_violations=40):
+          cut_subtrees=False, depth_exact=True, woop=False, dropped=None, max_violations=40, stats=None):
     """binary / records / wide: float32 [n][16] (PathTracer.tree_items); info: pt_scene_info's dict (n_inner, n_tri_refs, n_leaves,
     max_depth); soup: float32 [n][9] by original id; wide_depth: the accessor's.
       split_refs    a triangle may be listed by several leaves whose boxes hold only a part of it (host SBVH, PT_OPT_PRESPLIT):
@@ -281,7 +319,9 @@ def audit(binary, records, wide, info, soup, wide_depth, leaf_max=0, split_refs=
       cut_subtrees  a device-built tree: the binary section keeps the nodes below its multi-record leaves (ptb_is_cut, pt_build.h),
                     unreachable, and n_inner is the size of the section
       depth_exact   max_depth equals the walked depth (False: it bounds it — k_depth, pt_build.h, counts the cut-off levels too)
-      woop          Woop records: only the shape and the containment of the node part are audited
+      woop          Woop records (PT_OPT_TRI_TEST 1): the records are audited against encode_woop_records and against the triangle's
+                    own vertices (below); the node part as for any tree; no coverage
+      stats         a dict that receives counts which are recorded, not judged (woop_floats, woop_floats_differ)
       dropped       bool [n] by id: triangles a refit dropped (zero vertices in the record, nothing in any box)
     """
     V = []
@@ -336,6 +376,36 @@ def audit(binary, records, wide, info, soup, wide_depth, leaf_max=0, split_refs=
         for j in np.nonzero(np.any(_bits(want) != Ri, axis=1))[0]:
             w = np.nonzero(_bits(want[j]) != Ri[j])[0]
             bad("record", f"record {j}", f"id {ids[j]}: words {w.tolist()} are {R[j, w].tolist()}, pt_encode_record gives {want[j, w].tolist()}")
+    else:
+        # Woop records.  (1) The stored rows, taken in binary64, send the triangle's own vertices to (1,0,0), (0,1,0), (0,0,0).
+        # Each stored entry is its exact value within 2^-24 relative (one rounding of a binary64 value to binary32), and the exact rows
+        # satisfy the identity exactly, so |row . v + translation - target| <= 2^-24 * (sum |row_i v_i| + |translation|).
+        # (2) Every float is within 1 ulp of the restated encoder's (bit-equality is the expectation: stats["woop_floats_differ"]
+        # counts the floats that are not); N and the id / last word are equal bit for bit; an empty leaf's record is zero rows with
+        # the word -1.
+        vv = soup[np.maximum(ids, 0)].copy()
+        vv[:, 0] = np.where(vv[:, 0] == 0, np.float32(0.0), vv[:, 0])
+        want = encode_woop_records(vv, ids, last)
+        want[~live, :15] = 0
+        R64, v64 = R.astype(np.float64), vv.astype(np.float64).reshape(-1, 3, 3)
+        target = np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 0.0]])     # [vertex][row x, row y, row z]
+        flat = ~np.any(want[:, 0:12].view(np.int32) & 0x7FFFFFFF, axis=1)         # zero rows: a triangle without area
+        for k, (c, sign) in enumerate(((4, 1.0), (8, 1.0), (0, -1.0))):
+            prod = R64[:, None, c:c + 3] * v64                                      # [record][vertex][axis]
+            val = prod.sum(2) + sign * R64[:, None, c + 3]
+            bound = 2.0 ** -24 * (np.abs(prod).sum(2) + np.abs(R64[:, None, c + 3]))
+            off = live[:, None] & ~flat[:, None] & ~(np.abs(val - target[None, :, k]) <= bound)
+            for j, i in zip(*np.nonzero(off)):
+                bad("woop-rows", f"record {j}", f"id {ids[j]}: row {'xyz'[k]} sends vertex {i} to {val[j, i]!r}, not to {target[i, k]} within {bound[j, i]:.3e}")
+        ulps = np.abs(_ordered_bits(want[:, :12]) - _ordered_bits(R[:, :12]))
+        if stats is not None:
+            stats["woop_floats"] = stats.get("woop_floats", 0) + int(ulps.size)
+            stats["woop_floats_differ"] = stats.get("woop_floats_differ", 0) + int((_bits(want[:, :12]) != Ri[:, :12]).sum())
+        for j in np.nonzero(np.any((ulps > 1) | ~np.isfinite(R[:, :12]), axis=1))[0]:
+            w = np.nonzero((ulps[j] > 1) | ~np.isfinite(R[j, :12]))[0]
+            bad("woop-record", f"record {j}", f"id {ids[j]}: floats {w.tolist()} are {R[j, w].tolist()}, emit()'s rows give {want[j, w].tolist()}")
+        for j in np.nonzero(np.any(_bits(want[:, 12:16]) != Ri[:, 12:16], axis=1))[0]:
+            bad("woop-record", f"record {j}", f"id {ids[j]}: N / id << 1 | last are {Ri[j, 12:16].tolist()}, expected {_bits(want[j, 12:16]).tolist()}")
     geo = live & ~dropped[np.maximum(ids, 0)]
     tbox[geo] = tri_boxes(soup[ids[geo]])
     seen_ids = np.bincount(ids[live], minlength=len(soup))
