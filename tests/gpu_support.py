@@ -108,6 +108,54 @@ def soup_mesh(soup):
     return g.Mesh.from_arrays(s.reshape(-1, 3), np.arange(3 * len(s), dtype=np.int32).reshape(-1, 3))
 
 
+def needles():
+    """A 16 x 16 patch of small triangles beside needles 1000 x longer than wide, at 45 degrees to the axes, of lengths that
+    ask the pre-split for 2..8 slabs (float32 [560][9], the 48 needles last).  test_gpu_tree_audit, test_build_ref,
+    test_gpu_build_ref."""
+    tris = []
+    h = 0.05
+    for i in range(16):
+        for j in range(16):
+            p = np.array([i * h, j * h, 0.0])
+            tris.append([p, p + [h, 0, 0], p + [0, h, 0.01]])
+            tris.append([p + [h, 0, 0], p + [h, h, 0.02], p + [0, h, 0.01]])
+    dirs = [np.array(d) / np.sqrt(2.0) for d in ([1, 1, 0], [1, 0, 1], [0, 1, 1], [1, -1, 0])]
+    for k in range(48):
+        L = 0.08 * 1.09 ** k
+        d = dirs[k % 4]
+        side = np.cross(d, [0.3, 0.5, 0.8])
+        side = side / np.linalg.norm(side) * (L / 1000.0)
+        o = np.array([1.0 + 0.03 * k, 0.02 * k, 0.1 + 0.01 * k])
+        tris.append([o, o + L * d, o + 0.5 * L * d + side])
+    return np.array(tris, np.float32).reshape(-1, 9)
+
+
+BUILDER_ASSETS = ("cube", "cornell", "bunny_low", "gto_sixteen")
+_builder_meshes = {}
+
+
+def builder_mesh(name):
+    """(Mesh, verts, tris, soup) of a mesh of the builder tests, made once: a committed asset, "needles", "needles-63" / "needles-64"
+    (the first 63 / 64 rows of needles() with its 48 long triangles moved to the front: either side of the pre-split's triangle
+    threshold) or a synthetic case of build_ref.case_soup.  verts / tris are the arrays pt_build_bvh receives.  test_build_ref,
+    test_gpu_build_ref."""
+    if name not in _builder_meshes:
+        import build_ref
+        if name in BUILDER_ASSETS:
+            mesh = g.scene_mesh(name)
+        elif name.startswith("needles"):
+            s = needles()
+            mesh = soup_mesh(s if name == "needles" else np.concatenate([s[-48:], s[:-48]])[:int(name[8:])])
+        else:
+            mesh = soup_mesh(build_ref.case_soup(name))
+        verts, tris = np.ascontiguousarray(mesh.verts, np.float32), np.ascontiguousarray(mesh.tris, np.int32)
+        soup = mesh.triangle_soup()
+        for a in (verts, tris, soup):
+            a.setflags(write=False)
+        _builder_meshes[name] = (mesh, verts, tris, soup)
+    return _builder_meshes[name]
+
+
 def twist(soup, amount, shift):
     """Non-rigid: every vertex turns about the vertical axis through the mesh centre by an angle that grows with its height,
     then moves by `shift` (a number, a tuple or an array) x the extent.  A function of the vertex alone, so shared vertices stay

@@ -21,7 +21,7 @@ import pytest
 
 import gpu_pathtracer_amd as g
 import tree_audit as ta
-from gpu_support import soup_mesh, twist
+from gpu_support import needles, soup_mesh, twist
 
 pytestmark = pytest.mark.gpu
 
@@ -29,27 +29,6 @@ PT_ERR_INVALID, PT_ERR_NO_SCENE = -1, -3
 
 
 # ---------------------------------------------------------------------------------------------------------------- meshes
-def needles():
-    """A 16 x 16 patch of small triangles beside needles 1000 x longer than wide, at 45 degrees to the axes, of lengths that
-    ask the pre-split for 2..8 slabs."""
-    tris = []
-    h = 0.05
-    for i in range(16):
-        for j in range(16):
-            p = np.array([i * h, j * h, 0.0])
-            tris.append([p, p + [h, 0, 0], p + [0, h, 0.01]])
-            tris.append([p + [h, 0, 0], p + [h, h, 0.02], p + [0, h, 0.01]])
-    dirs = [np.array(d) / np.sqrt(2.0) for d in ([1, 1, 0], [1, 0, 1], [0, 1, 1], [1, -1, 0])]
-    for k in range(48):
-        L = 0.08 * 1.09 ** k
-        d = dirs[k % 4]
-        side = np.cross(d, [0.3, 0.5, 0.8])
-        side = side / np.linalg.norm(side) * (L / 1000.0)
-        o = np.array([1.0 + 0.03 * k, 0.02 * k, 0.1 + 0.01 * k])
-        tris.append([o, o + L * d, o + 0.5 * L * d + side])
-    return np.array(tris, np.float32).reshape(-1, 9)
-
-
 _SOUPS = {}
 
 
