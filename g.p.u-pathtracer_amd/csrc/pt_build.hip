@@ -34,7 +34,7 @@ static int check_mesh(pt_ctx* c, Mesh& m) {
     for (size_t i = 0; i < 3 * m.n_verts; i++) { m.lo[i % 3] = std::min(m.lo[i % 3], m.verts[i]); m.hi[i % 3] = std::max(m.hi[i % 3], m.verts[i]); }
     for (int a = 0; a < 3; a++)
         if (!(m.hi[a] - m.lo[a] <= 3.402823466e+38f)) return fail(c, PT_ERR_INVALID, "pt_build_bvh: the mesh's extent overflows binary32");
-    if (c->d_tri_matid && m.n_tris > c->n_tri_matid)
+    if (c->mat.d_tri_matid && m.n_tris > c->mat.n_tri_matid)
         return fail(c, PT_ERR_INVALID, "pt_build_bvh: the triangle-material array on this context does not cover this mesh (clear or re-upload it first)");
     for (int k = 0; k < 6; k++) m.two[k] = m.tris[k % 3];
     m.max_tri_id = (int32_t)m.n_tris - 1;
@@ -51,10 +51,9 @@ struct Job {
     int n = 0;                        // primitives: max(triangles, 2), more after pre-splitting
     size_t n_items = 0;
     unsigned int n_levels_max = 64;   // binary levels of the hierarchy: what the collapse has to cover
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    Event e0, e1;   // the attempt's device time: between the uploads and the last emit launch
     DevTree made;
     explicit Job(const Mesh& mesh) : m(mesh) {}
-    ~Job() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
     dim3 grid() const { return dim3((unsigned)((n + PTB_BLOCK - 1) / PTB_BLOCK)); }
 };
 static const dim3 blk(PTB_BLOCK);
@@ -80,8 +79,8 @@ static int stage_inputs(pt_ctx* c, Job& j) {
     HIP_TRY(c, hipMemcpyAsync(d_tris_idx, m.rows(), 3 * (size_t)j.n * sizeof(int32_t), hipMemcpyHostToDevice, st));
     B.verts = d_verts;
     B.tris = d_tris_idx;
-    HIP_TRY(c, hipEventCreate(&j.e0));
-    HIP_TRY(c, hipEventCreate(&j.e1));
+    HIP_TRY(c, j.e0.ensure());
+    HIP_TRY(c, j.e1.ensure());
     HIP_TRY(c, hipEventRecord(j.e0, st));
     if (c->opt_presplit && n_tris >= 64) {
         // pre-splitting: long triangles enter as several primitives (pt_build.h); the target length is a
@@ -147,8 +146,8 @@ static int stage_arrays(pt_ctx* c, Job& j) {
     HIP_TRY(c, j.tmp.get(&B.frontier_b, n));
     j.n_items = (n - 1) + n + (n - 1);   // binary, records, wide (upper bound)
     if (j.n_items * 4 >= (size_t)PT_SENTINEL) return fail(c, PT_ERR_INVALID, "pt_build_bvh: scene too large for 32-bit links");
-    HIP_TRY(c, hipMalloc((void**)&j.made.s.d_nodes, j.n_items * 64));
-    B.items = j.made.s.d_nodes;
+    HIP_TRY(c, j.made.alloc_items(j.n_items * 4));
+    B.items = j.made.d_nodes;
     hipLaunchKernelGGL(k_build_reset, dim3(1), dim3(PTB_LEVEL_CNT), 0, c->stream, B);
     HIP_TRY(c, hipMemsetAsync(B.items, 0, j.n_items * 64, c->stream));
     return PT_OK;
@@ -274,7 +273,7 @@ static int stage_finish(pt_ctx* c, Job& j) {
     uint32_t levels = 0;
     while (levels < 66 && level_cnt[levels] > 0) levels++;
     if (level_cnt[std::min<unsigned int>(j.n_levels_max + 1, 67)] != 0) return fail(c, PT_ERR_DEVICE, "pt_build_bvh: wide collapse did not finish");
-    TreeState& t = j.made.s;
+    TreeState& t = j.made;
     HIP_TRY(c, hipEventElapsedTime(&t.build_ms, j.e0, j.e1));
     if (stats[3] > 64) return fail(c, PT_ERR_UNSUPPORTED, "pt_build_bvh: tree deeper than 64 levels (degenerate input); use the host builder");
     t.wide_root = 4 * ((uint64_t)(j.n - 1) + (uint64_t)j.n);

@@ -1,6 +1,9 @@
 // pt_ctx.h — the context behind the C ABI (include/ptmi.h) and the host-side helpers shared by the
 // translation units of libptmi.so: ptmi.hip (API), pt_tree.hip (trees: makers, adoption, cost), pt_build.hip (device BVH
-// builder), pt_k_*.hip (kernel families + their launchers, no API function), pt_env.hip (environment map).  Host code only.
+// builder), pt_refit.hip (refit), pt_denoise.hip (guide buffers, denoiser, temporal filter, frame error), pt_k_*.hip (kernel families +
+// their launchers, no API function), pt_env.hip (environment map).  Host code only.
+// Every device buffer, event and stream of the context is a member that owns it (pt_own.h): pt_destroy waits and deletes.  The scene's
+// resources — tree, spheres, materials, environment — are values: built in a local, adopted behind quiesce().
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,6 +17,7 @@
 
 #include "../../include/ptmi.h"
 #include "pt_kernels.h"
+#include "pt_own.h"
 
 // the bounce-0 walk of a new context (PT_OPT_FIRST_WALK); -DPT_FIRST_WALK_DEFAULT=0 builds the per-lane one for A/B timing
 #ifndef PT_FIRST_WALK_DEFAULT
@@ -34,7 +38,7 @@
 //     under PT_OPT_REBUILD 2 (3 n items of 64 B: ~150 MB at 800 k triangles);
 //   * scene_gen advances by one per successful call (only equality is ever tested on it).
 struct TreeState {
-    float4* d_nodes = nullptr;   // one item buffer, [binary nodes][records][wide nodes]: links index it directly (KScene::nodes and ::tris)
+    float4* d_nodes = nullptr;   // one item buffer, [binary nodes][records][wide nodes]: links index it directly (KScene::nodes and ::tris); a view of DevTree::items
     bool records_woop = false;   // what the uploaded records are
     bool has_bvh = false;
     uint64_t wide_root = 0;      // float4 index of the 4-wide tree's root, 0 = not built
@@ -51,59 +55,97 @@ struct TreeState {
     uint32_t n_occ = 0;
 };
 
-// A tree that owns its item buffer: whatever a maker allocated is released on every early return, and the loser of
-// PT_OPT_REBUILD 2 when it goes out of scope.
-struct DevTree {
-    TreeState s;
+// A tree with the item buffer it describes: whatever a maker allocated is released on every early return, the loser of
+// PT_OPT_REBUILD 2 when it goes out of scope, the context's tree when another is adopted over it.  A moved-from tree is "no tree".
+struct DevTree : TreeState {
+    ptmi::DevBuf<float4> items;
     DevTree() = default;
-    DevTree(DevTree&& o) noexcept : s(o.release()) {}
+    DevTree(DevTree&& o) noexcept : TreeState(o), items(std::move(o.items)) { static_cast<TreeState&>(o) = TreeState(); }
     DevTree& operator=(DevTree&& o) noexcept {
-        if (this != &o) { (void)hipFree(s.d_nodes); s = o.release(); }
+        if (this != &o) {
+            TreeState::operator=(o);
+            items = std::move(o.items);
+            static_cast<TreeState&>(o) = TreeState();
+        }
         return *this;
     }
-    ~DevTree() { (void)hipFree(s.d_nodes); }
-    TreeState release() { const TreeState r = s; s = TreeState(); return r; }   // the caller owns the buffer now
+    hipError_t alloc_items(size_t n_float4) {
+        const hipError_t e = items.alloc(n_float4);
+        d_nodes = items.get();
+        return e;
+    }
 };
 
-struct pt_ctx {
-    int device = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t switch_ev = nullptr;    // pt_set_stream: the new stream waits for what the old one was given (recorded there at the switch)
-    std::string err;
-    // scene
-    TreeState tree;
-    pt_sphere_d* d_spheres = nullptr;
-    int* d_tri_matid = nullptr;        // pt_upload_tri_materials
-    float4* d_mat_table = nullptr;
+// pt_upload_tri_materials' table and the light list it implies, a value like a tree: filled in a local, move-assigned onto the context
+// once every allocation and copy has succeeded (the only place mat_gen advances).  Empty: the one global material of pt_params.
+struct Materials {
+    ptmi::DevBuf<int32_t> d_tri_matid;   // material row of every triangle id
+    ptmi::DevBuf<float4> d_mat_table;    // two rows per pt_material
     size_t n_tri_matid = 0;
     // PT_FLAG_NEE over emissive triangles: ids whose material row emits (host, ascending), id -> light slot (device),
     // the light records (device; rebuilt from the triangle records when the scene or the materials changed)
     std::vector<int32_t> emissive_ids;
-    int32_t* d_light_slot = nullptr;
-    float4* d_tri_lights = nullptr;
+    ptmi::DevBuf<int32_t> d_light_slot;
+    ptmi::DevBuf<float4> d_tri_lights;
+};
+
+// pt_upload_environment's map (pt_env.hip), a value too: the context's own device copy of the texels, the sampling tables
+// (PT_OPT_ENV_LIGHT; empty: the map is no light) and the map as the kernels get it, computed from them: k.texels == nullptr: no map,
+// k.cx == nullptr: no light.
+struct EnvMap {
+    ptmi::DevBuf<float4> d_texels;
+    ptmi::DevBuf<float> d_tables;   // cx, cy, zs
+    KEnv k = {};
+};
+
+struct pt_ctx {
+    using Event = ptmi::Event;
+    using Stream = ptmi::Stream;
+    template <class T> using DevBuf = ptmi::DevBuf<T>;
+    int device = 0;
+    // the streams first: members go in reverse order, so whatever ran on a stream is released before the stream (pt_destroy has waited
+    // for all of them by then)
+    Stream own_stream;
+    hipStream_t stream = nullptr;      // the caller's (pt_set_stream) or own_stream: borrowed
+    // Overlap of consecutive calls (PT_OPT_OVERLAP, persistent / mega kernels): the path kernel of call k + 1 runs on
+    // a side stream into its own sample buffer while call k's last paths drain; only the folds (which touch the
+    // accumulator, in order) stay on the caller's stream.  side[x]: stream, sample buffer, queue counters of slot x.
+    int opt_overlap = 1;
+    struct Side {
+        Stream stream;
+        Event traced, folded;   // path kernel done / the fold that read the buffer done
+        bool fold_pending = false;
+        DevBuf<float> samples;
+        DevBuf<unsigned int> queue;
+        uint64_t lights_seen = 0;   // the light list generation this stream has been ordered behind (lights_gen)
+        uint64_t geom_seen = 0;     // the refit generation this stream has been ordered behind (geom_gen)
+    } side[2];
+    int side_next = 0;
+    Event switch_ev;                   // pt_set_stream: the new stream waits for what the old one was given (recorded there at the switch)
+    std::string err;
+    // scene
+    DevTree tree;                      // written by adopt_tree (pt_tree.hip) only
+    DevBuf<pt_sphere_d> d_spheres;
+    Materials mat;                     // pt_upload_tri_materials
     uint64_t mat_gen = 0, lights_key = ~0ull;
     uint64_t lights_geom = 0;          // the refit generation (geom_gen) the light list was collected at
     // the light list is (re)written on the caller's stream; a side stream (PT_OPT_OVERLAP) waits for lights_ev before its
     // first kernel that may read that generation of the list
-    hipEvent_t lights_ev = nullptr;
+    Event lights_ev;
     uint64_t lights_gen = 0;
     int n_spheres = 0;
     pt_sphere_d h_spheres[PT_KSPHERES];   // host copy of the first spheres for the kernel-argument block
-    // pt_upload_environment (pt_env.hip): the map as the kernels get it, env.texels the context's own device copy (nullptr: no map),
-    // env.cx its sampling tables' (nullptr: the map is no light; PT_OPT_ENV_LIGHT);
-    // env_gen counts the uploads and clears, part of PT_KERNEL_AUTO's key like scene_gen
-    KEnv env = {};
+    // pt_upload_environment (pt_env.hip); env_gen counts the uploads and clears, part of PT_KERNEL_AUTO's key like scene_gen
+    EnvMap env;
     uint64_t env_gen = 0;
     // options
     int opt_kernel = PT_KERNEL_AUTO;
     int opt_counters = 0;
     int opt_timing = 0;
     // measurement
-    unsigned long long* d_counters = nullptr;
-    unsigned int* d_queue = nullptr;   // work counters of the persistent kernel, of the ray-batch queries (pt_k_query.hip) and of pt_render_rays (pt_k_rays.hip), on the caller's stream: reset there before every launch
-    float* d_samples = nullptr;        // [spp][H*W][3] sample colours of a multi-sample call; pt_render_rays: [spp][n][3] (both on the caller's stream)
-    size_t samples_bytes = 0;
+    DevBuf<unsigned long long> d_counters;
+    DevBuf<unsigned int> d_queue;      // work counters of the persistent kernel, of the ray-batch queries (pt_k_query.hip) and of pt_render_rays (pt_k_rays.hip), on the caller's stream: reset there before every launch
+    DevBuf<float> d_samples;           // [spp][H*W][3] sample colours of a multi-sample call; pt_render_rays: [spp][n][3] (both on the caller's stream); grow-only
     int n_cu = 0;
     int opt_batch = 36;
     int opt_presplit = 0;        // pt_build_bvh: 0 off, else the target length in per cent of diag/sqrt(n) (PT_OPT_PRESPLIT)
@@ -120,8 +162,7 @@ struct pt_ctx {
     int opt_leaf_max = 2;        // leaves with more references are split at upload (PT_OPT_LEAF_MAX)
     int opt_tri_test = 0;        // 0 Moller-Trumbore records, 1 Woop records (next upload; PT_OPT_TRI_TEST)
     // stage-split (wavefront) pipeline: path records of one call, two generations (pt_k_wave.hip)
-    void* d_wave = nullptr;
-    size_t wave_bytes = 0;
+    DevBuf<char> d_wave;         // grow-only; dropped again once PT_KERNEL_AUTO has decided against the pipeline everywhere (auto_decide)
     int opt_wave_batch = 16;     // extend kernel: finished lanes that make a wave leave the walk to write hits / refill
     int opt_wave_samples = 16;   // bounce 0 of the stage-split pipeline: samples of one pixel per wave (PT_OPT_WAVE_SAMPLES)
     int opt_wave_blocks = 8;     // extend kernel: resident 256-thread blocks per CU the grid is sized for (PT_OPT_WAVE_BLOCKS)
@@ -144,7 +185,7 @@ struct pt_ctx {
         uint64_t key = 0;        // what the choice was made for: image, spp, depth, partition shape, scene generation, material, flags
         int phase = 0;           // 0..3: this call is timed trial `phase` (even: persistent kernel, odd: pipeline)  4: events pending  5: decided
         int choice = PT_KERNEL_PERSISTENT;
-        hipEvent_t e[2 * TRIALS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // start / end of every trial
+        Event e[2 * TRIALS];     // start / end of every trial
         float ms[2] = {0.f, 0.f};   // the faster of each layout's two trials (a context's very first launch is slow: code upload)
         uint64_t used = 0;       // tick of the last pt_render that looked this entry up
     };
@@ -156,15 +197,15 @@ struct pt_ctx {
     // pt_refit_bvh: the boxes and records of the tree are rewritten on the caller's stream; geom_gen counts the refits and a side
     // stream (PT_OPT_OVERLAP) waits for geom_ev before its first path kernel after one (the light list is re-collected too)
     uint64_t geom_gen = 0;
-    hipEvent_t geom_ev = nullptr;
+    Event geom_ev;
     // PT_OPT_LAST_OCCLUDERS: the first three pieces of the records of tree.occ_ids, copied out of the tree's item buffer on the caller's
     // stream by whoever writes those records: adopt_tree and pt_refit_bvh (occluders_collect).  3 float4 each, the last one's `last` set.
-    float4* d_occ = nullptr;
-    // what the refit of one tree needs on the device, made by its first refit (pt_refit.hip) and released with the tree
+    DevBuf<float4> d_occ;
+    // what the refit of one tree needs on the device, made by its first refit (pt_refit.hip) and dropped (= Refit()) where the tree is replaced
     struct Refit {
         uint64_t scene_gen = 0;
         const float4* items = nullptr;           // the tree it was made for: (scene_gen, item buffer)
-        void* d_mem = nullptr;                   // one allocation: the lists and scratch below
+        DevBuf<char> d_mem;                      // one allocation: the lists and scratch below
         int4* bin_list = nullptr;                // binary nodes by height: {node, records of leaf child 0 (0: inner), of child 1, 0}
         int4* wide_list = nullptr;               // wide nodes by height: {slot, children, records of 0 | 1 << 16, of 2 | 3 << 16}
         float* bin_box = nullptr;                // [n_inner][6] exact union of a binary node's triangles (lo > hi: all dropped)
@@ -173,33 +214,15 @@ struct pt_ctx {
         uint32_t* first_use = nullptr;           // bit per record: the first record of its triangle (counts a dropped triangle once)
         std::vector<uint32_t> bin_off, wide_off; // list offsets per height (size heights + 1)
     } refit;
-    // pt_denoise's ping-pong colour frames (pt_denoise.hip): grown on demand, released by pt_destroy
-    void* d_denoise = nullptr;
-    size_t denoise_bytes = 0;
-    // pt_frame_error's per-block partial results (pt_denoise.hip): [blocks] double sums, then [blocks] uint32 counts; grown on
-    // demand, released with the denoiser's scratch
-    void* d_frame_err = nullptr;
-    size_t frame_err_bytes = 0;
-    // Overlap of consecutive calls (PT_OPT_OVERLAP, persistent / mega kernels): the path kernel of call k + 1 runs on
-    // a side stream into its own sample buffer while call k's last paths drain; only the folds (which touch the
-    // accumulator, in order) stay on the caller's stream.  side[x]: stream, sample buffer, queue counters of slot x.
-    int opt_overlap = 1;
-    struct Side {
-        hipStream_t stream = nullptr;
-        hipEvent_t traced = nullptr, folded = nullptr;   // path kernel done / the fold that read the buffer done
-        bool fold_pending = false;
-        float* samples = nullptr;
-        size_t samples_bytes = 0;
-        unsigned int* queue = nullptr;
-        uint64_t lights_seen = 0;   // the light list generation this stream has been ordered behind (lights_gen)
-        uint64_t geom_seen = 0;     // the refit generation this stream has been ordered behind (geom_gen)
-    } side[2];
-    int side_next = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // pt_denoise's two ping-pong colour frames (pt_denoise.hip): grow-only
+    DevBuf<float4> d_denoise;
+    // pt_frame_error's per-block partial results (pt_denoise.hip): [blocks] double sums, then [blocks] uint32 counts; grow-only
+    DevBuf<char> d_frame_err;
+    Event ev0, ev1;
     bool timed = false;
     // PT_OPT_TIMING: events between the stages of the last call (pt_get_stage_ms); stage_kind[i] is the
     // PT_STAGE_* of the work between event i and event i + 1
-    std::vector<hipEvent_t> stage_ev;
+    std::vector<Event> stage_ev;
     std::vector<int> stage_kind;
     size_t stage_used = 0;
 };
@@ -217,17 +240,16 @@ inline int hip_fail(pt_ctx* c, hipError_t e, const char* what) {
     return fail(c, PT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
 }
 
-struct DevTemp {  // temporaries of one build, released together
-    std::vector<void*> ptrs;
-    ~DevTemp() { for (void* p : ptrs) (void)hipFree(p); }
-    template <class T> hipError_t get(T** out, size_t count) {
-        void* p = nullptr;
-        const hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(p);
-        *out = (T*)p;
-        return e;
-    }
-};
+// Every stream a launch that reads the scene can still be running on: the caller's, the context's own, both side streams
+// (PT_OPT_OVERLAP).  What replaces a scene resource — adopt_tree, pt_upload_spheres, pt_upload_tri_materials, pt_upload_environment —
+// and pt_destroy wait here first; the owners themselves never wait.
+inline hipError_t quiesce(pt_ctx* c) {
+    hipError_t e = c->stream ? hipStreamSynchronize(c->stream) : hipSuccess;
+    if (e == hipSuccess && c->own_stream && c->own_stream != c->stream) e = hipStreamSynchronize(c->own_stream);
+    for (pt_ctx::Side& s : c->side)
+        if (e == hipSuccess && s.stream) e = hipStreamSynchronize(s.stream);
+    return e;
+}
 
 // LDS bytes of a frame-kernel block, top-of-tree planes + stack, with the largest n_top (halved from the one asked for) that fits
 // 160 KiB: a deep tree gives the LDS to the stack first
@@ -278,7 +300,7 @@ inline void scene_view(const pt_ctx* c, KScene& sc, pt_sphere_d* ksph = nullptr)
     sc.has_bvh = c->tree.has_bvh ? 1 : 0;
     sc.wide_root = (int)c->tree.wide_root;
     if (!ksph) return;
-    sc.spheres = c->d_spheres; sc.n_spheres = c->n_spheres;
+    sc.spheres = c->d_spheres.get(); sc.n_spheres = c->n_spheres;
     std::memcpy(ksph, c->h_spheres, sizeof c->h_spheres);
 }
 // The binary walk with one thread per ray (pt_trace_rays, the deep-tree queries, pt_render_aux): all PT_STACK_CAP entries and the top
@@ -289,8 +311,7 @@ inline size_t binary_ray_layout(const pt_ctx* c, KScene& sc) {
     return lds_fit(sc.n_top, sc.stack_n, PT_BLOCK_RAYS);
 }
 // The work counters of a persistent launch: PT_SHARDS of them, a cache line apart, zero when the launch starts.
-constexpr size_t QUEUE_BYTES = PT_SHARDS * PT_SHARD_STRIDE * sizeof(unsigned int);
-inline hipError_t queue_alloc(unsigned int** q) { return hipMalloc((void**)q, QUEUE_BYTES); }
+constexpr size_t QUEUE_WORDS = PT_SHARDS * PT_SHARD_STRIDE, QUEUE_BYTES = QUEUE_WORDS * sizeof(unsigned int);
 inline hipError_t queue_reset(unsigned int* q, hipStream_t st) { return hipMemsetAsync(q, 0, QUEUE_BYTES, st); }
 // queue granularity: 64-slot chunks when the launch has plenty of them per resident wave, smaller ones for small launches (an
 // eighth of a 1080p frame per GPU is ~4 000 tiles for ~5 000 waves)
@@ -406,12 +427,6 @@ int build_bvh_impl(pt_ctx* c, const float* verts, size_t n_verts, const int32_t*
 struct OccTri { int32_t id; const float *v0, *v1, *v2; };
 int select_occluders(std::vector<OccTri>& tris, int32_t* ids, int cap);
 int occluders_collect(pt_ctx* c);
-// pt_refit_bvh's per-tree state (pt_refit.hip): released where the tree is replaced (adopt_tree) or the context destroyed
-void refit_release(pt_ctx* c);
-// pt_denoise's and pt_frame_error's scratch (pt_denoise.hip)
-void denoise_release(pt_ctx* c);
-// the environment map's texels (pt_env.hip)
-void env_release(pt_ctx* c);
 
 }  // namespace ptmi
 

@@ -302,19 +302,6 @@ __global__ void __launch_bounds__(256) k_frame_error(const float2* __restrict__ 
 
 }  // namespace
 
-namespace ptmi {
-
-void denoise_release(pt_ctx* c) {
-    (void)hipFree(c->d_denoise);
-    c->d_denoise = nullptr;
-    c->denoise_bytes = 0;
-    (void)hipFree(c->d_frame_err);
-    c->d_frame_err = nullptr;
-    c->frame_err_bytes = 0;
-}
-
-}  // namespace ptmi
-
 using namespace ptmi;
 
 extern "C" int pt_render_aux(pt_ctx* c, const pt_camera* cam, const pt_params* p, float* albedo_dev, float* normal_dev,
@@ -333,8 +320,8 @@ extern "C" int pt_render_aux(pt_ctx* c, const pt_camera* cam, const pt_params* p
     P.W = p->width; P.H = p->height;
     P.cull = p->cull_backfaces;
     for (int i = 0; i < 3; i++) P.tri_col[i] = p->tri_col[i];
-    P.tri_matid = c->d_tri_matid;
-    P.mat_table = c->d_mat_table;
+    P.tri_matid = c->mat.d_tri_matid.get();
+    P.mat_table = c->mat.d_mat_table.get();
     AuxOut A;
     A.albedo = (float4*)albedo_dev;
     A.normal = (float4*)normal_dev;
@@ -372,14 +359,9 @@ extern "C" int pt_denoise(pt_ctx* c, const pt_denoise_params* dp, const float* c
     const int L = dp->iterations;
     float4* ping[2] = {nullptr, nullptr};
     if (L > 0) {
-        const size_t need = 2 * n_pix * sizeof(float4);
-        if (need > c->denoise_bytes) {   // the old buffers may still be read by an earlier call's launches
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            denoise_release(c);
-            HIP_TRY(c, hipMalloc(&c->d_denoise, need));
-            c->denoise_bytes = need;
-        }
-        ping[0] = (float4*)c->d_denoise;
+        if (2 * n_pix > c->d_denoise.count()) HIP_TRY(c, hipStreamSynchronize(c->stream));   // the old frames may still be read by an earlier call's launches
+        HIP_TRY(c, c->d_denoise.reserve(2 * n_pix));
+        ping[0] = c->d_denoise.get();
         ping[1] = ping[0] + n_pix;
     }
     // log2(e) / sigma^2, in double; a term with sigma <= 0 is off (0); capped so that 0 x constant stays 0
@@ -483,20 +465,14 @@ extern "C" int pt_frame_error(pt_ctx* c, const float* moments_dev, int32_t width
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t n_blocks = (n_pix + 255) / 256;
     const size_t need = n_blocks * (sizeof(double) + sizeof(uint32_t));
-    if (need > c->frame_err_bytes) {   // nothing reads the old slots: every earlier call synchronised before it returned
-        (void)hipFree(c->d_frame_err);
-        c->d_frame_err = nullptr;
-        c->frame_err_bytes = 0;
-        HIP_TRY(c, hipMalloc(&c->d_frame_err, need));
-        c->frame_err_bytes = need;
-    }
-    double* d_sums = (double*)c->d_frame_err;
+    HIP_TRY(c, c->d_frame_err.reserve(need));   // (no wait: nothing reads the old slots, every earlier call synchronised before it returned)
+    double* d_sums = (double*)c->d_frame_err.get();
     uint32_t* d_counts = (uint32_t*)(d_sums + n_blocks);
     hipLaunchKernelGGL(k_frame_error, dim3((unsigned)n_blocks), dim3(256), 0, c->stream, (const float2*)moments_dev, (uint32_t)n_pix,
                        (float)(n_samples - 1), threshold, d_sums, d_counts);
     HIP_TRY(c, hipGetLastError());
     std::vector<unsigned char> h(need);
-    HIP_TRY(c, hipMemcpyAsync(h.data(), c->d_frame_err, need, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h.data(), c->d_frame_err.get(), need, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     const double* sums = (const double*)h.data();
     const uint32_t* counts = (const uint32_t*)(sums + n_blocks);

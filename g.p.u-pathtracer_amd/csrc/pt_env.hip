@@ -48,21 +48,6 @@ __global__ void __launch_bounds__(256) k_environment_pdf(const KEnv E_arg, const
 
 namespace ptmi {
 
-// every stream a kernel that reads the map can still be running on
-static hipError_t env_quiesce(pt_ctx* c) {
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess && c->own_stream != c->stream) e = hipStreamSynchronize(c->own_stream);
-    for (pt_ctx::Side& s : c->side)
-        if (e == hipSuccess && s.stream) e = hipStreamSynchronize(s.stream);
-    return e;
-}
-
-void env_release(pt_ctx* c) {
-    (void)hipFree((void*)c->env.texels);
-    (void)hipFree((void*)c->env.cx);   // (cy and zs lie behind it)
-    c->env = KEnv{};
-}
-
 static bool finite3(const float* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 
 // PT_OPT_ENV_LIGHT: the sampling tables of a map (include/ptmi.h states the rule; tests/env_light_ref.py restates it), in double,
@@ -129,8 +114,8 @@ extern "C" int pt_upload_environment(pt_ctx* c, const pt_environment* env, const
     if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
     HIP_TRY(c, hipSetDevice(c->device));
     if (!env) {   // clear: bk_color again, and the stage-split pipeline with it
-        HIP_TRY(c, env_quiesce(c));
-        env_release(c);
+        HIP_TRY(c, quiesce(c));
+        c->env = EnvMap();
         c->env_gen++;
         return PT_OK;
     }
@@ -155,21 +140,16 @@ extern "C" int pt_upload_environment(pt_ctx* c, const pt_environment* env, const
     }
     std::vector<float> tab;   // PT_OPT_ENV_LIGHT: stays empty when the map is no light
     if (c->opt_env_light && !env_tables(env, host, tab)) tab.clear();
-    // the new copy is complete before anything of the old one is touched: any failure up to here leaves the old map, and its
+    // the new map is complete before anything of the old one is touched: any failure up to the adoption leaves the old map, and its
     // tables, in place
-    float4* dev = nullptr;
-    float* dev_tab = nullptr;
-    HIP_TRY(c, hipMalloc((void**)&dev, n * sizeof(float4)));
-    hipError_t e = hipMemcpy(dev, host.data(), n * sizeof(float4), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !tab.empty()) e = hipMalloc((void**)&dev_tab, tab.size() * sizeof(float));
-    if (e == hipSuccess && !tab.empty()) e = hipMemcpy(dev_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
-    // a render in flight, on a side stream (PT_OPT_OVERLAP) too, reads the old map to its end
-    if (e == hipSuccess) e = env_quiesce(c);
-    if (e != hipSuccess) { (void)hipFree(dev); (void)hipFree(dev_tab); return hip_fail(c, e, "pt_upload_environment"); }
-    env_release(c);
-    KEnv& k = c->env;
-    k.texels = dev;
-    if (dev_tab) {
+    EnvMap m;
+    HIP_TRY(c, m.d_texels.alloc(n));
+    HIP_TRY(c, hipMemcpy(m.d_texels.get(), host.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_TRY(c, m.d_tables.alloc(tab.size()));
+    if (!tab.empty()) HIP_TRY(c, hipMemcpy(m.d_tables.get(), tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    KEnv& k = m.k;
+    k.texels = m.d_texels.get();
+    if (const float* dev_tab = m.d_tables.get()) {
         const size_t W = (size_t)env->width, H = (size_t)env->height;
         k.cx = dev_tab; k.cy = dev_tab + H * (W + 1); k.zs = dev_tab + H * (W + 1) + (H + 1);
     }
@@ -179,19 +159,21 @@ extern "C" int pt_upload_environment(pt_ctx* c, const pt_environment* env, const
     k.kx = (float)((double)env->width / (2.0 * pi)); k.ky = (float)((double)env->height / pi);
     k.hx = (float)((double)env->width / 2.0); k.hy = (float)((double)env->height / 2.0);
     k.filter = env->filter;
+    HIP_TRY(c, quiesce(c));   // a render in flight, on a side stream (PT_OPT_OVERLAP) too, reads the old map to its end
+    c->env = std::move(m);
     c->env_gen++;
     return PT_OK;
 }
 
 extern "C" int pt_eval_environment(pt_ctx* c, const float* rays_dev, size_t n_rays, float* radiance_dev) {
     if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
-    if (!c->env.texels) return fail(c, PT_ERR_NO_SCENE, "pt_eval_environment: no environment map uploaded");
+    if (!c->env.k.texels) return fail(c, PT_ERR_NO_SCENE, "pt_eval_environment: no environment map uploaded");
     if (n_rays == 0) return PT_OK;
     if (!rays_dev || !radiance_dev) return fail(c, PT_ERR_INVALID, "pt_eval_environment: null argument");
     if (n_rays >= (1ull << 32)) return fail(c, PT_ERR_INVALID, "pt_eval_environment: more than 2^32 - 1 rays in one call");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, span_begin(c));
-    hipLaunchKernelGGL(k_eval_environment, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, c->stream, c->env, (const float4*)rays_dev,
+    hipLaunchKernelGGL(k_eval_environment, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, c->stream, c->env.k, (const float4*)rays_dev,
                        (uint32_t)n_rays, radiance_dev);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, span_end(c));
@@ -201,20 +183,20 @@ extern "C" int pt_eval_environment(pt_ctx* c, const float* rays_dev, size_t n_ra
 extern "C" int pt_environment_is_light(pt_ctx* c, int* out) {
     if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
     if (!out) return fail(c, PT_ERR_INVALID, "pt_environment_is_light: null argument");
-    *out = c->env.texels && c->env.cx ? 1 : 0;
+    *out = c->env.k.texels && c->env.k.cx ? 1 : 0;
     return PT_OK;
 }
 
 extern "C" int pt_sample_environment(pt_ctx* c, const float* u_dev, size_t n, float* dir_pdf_dev, float* radiance_dev) {
     if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
-    if (!c->env.texels) return fail(c, PT_ERR_NO_SCENE, "pt_sample_environment: no environment map uploaded");
-    if (!c->env.cx) return fail(c, PT_ERR_UNSUPPORTED, "pt_sample_environment: the map is no light (PT_OPT_ENV_LIGHT at its upload, an orthonormal basis, not black)");
+    if (!c->env.k.texels) return fail(c, PT_ERR_NO_SCENE, "pt_sample_environment: no environment map uploaded");
+    if (!c->env.k.cx) return fail(c, PT_ERR_UNSUPPORTED, "pt_sample_environment: the map is no light (PT_OPT_ENV_LIGHT at its upload, an orthonormal basis, not black)");
     if (n == 0) return PT_OK;
     if (!u_dev || !dir_pdf_dev) return fail(c, PT_ERR_INVALID, "pt_sample_environment: null argument");
     if (n >= (1ull << 32)) return fail(c, PT_ERR_INVALID, "pt_sample_environment: more than 2^32 - 1 draws in one call");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, span_begin(c));
-    hipLaunchKernelGGL(k_sample_environment, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->env, (const float2*)u_dev, (uint32_t)n,
+    hipLaunchKernelGGL(k_sample_environment, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->env.k, (const float2*)u_dev, (uint32_t)n,
                        (float4*)dir_pdf_dev, radiance_dev);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, span_end(c));
@@ -223,14 +205,14 @@ extern "C" int pt_sample_environment(pt_ctx* c, const float* u_dev, size_t n, fl
 
 extern "C" int pt_environment_pdf(pt_ctx* c, const float* rays_dev, size_t n, float* pdf_dev) {
     if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
-    if (!c->env.texels) return fail(c, PT_ERR_NO_SCENE, "pt_environment_pdf: no environment map uploaded");
-    if (!c->env.cx) return fail(c, PT_ERR_UNSUPPORTED, "pt_environment_pdf: the map is no light (PT_OPT_ENV_LIGHT at its upload, an orthonormal basis, not black)");
+    if (!c->env.k.texels) return fail(c, PT_ERR_NO_SCENE, "pt_environment_pdf: no environment map uploaded");
+    if (!c->env.k.cx) return fail(c, PT_ERR_UNSUPPORTED, "pt_environment_pdf: the map is no light (PT_OPT_ENV_LIGHT at its upload, an orthonormal basis, not black)");
     if (n == 0) return PT_OK;
     if (!rays_dev || !pdf_dev) return fail(c, PT_ERR_INVALID, "pt_environment_pdf: null argument");
     if (n >= (1ull << 32)) return fail(c, PT_ERR_INVALID, "pt_environment_pdf: more than 2^32 - 1 rays in one call");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, span_begin(c));
-    hipLaunchKernelGGL(k_environment_pdf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->env, (const float4*)rays_dev, (uint32_t)n, pdf_dev);
+    hipLaunchKernelGGL(k_environment_pdf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->env.k, (const float4*)rays_dev, (uint32_t)n, pdf_dev);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, span_end(c));
     return PT_OK;

@@ -185,7 +185,7 @@ hipError_t launch_query(pt_ctx* c, const QueryCall& q) {
     scene_view(c, Q.sc);
     Q.rays = (const float4*)q.rays;
     Q.t_out = q.t; Q.tri_out = q.tri; Q.n_out = q.normal; Q.hit_out = q.hit;
-    Q.queue = c->d_queue;   // the context's counters: every use is on the caller's stream, behind a reset of its own
+    Q.queue = c->d_queue.get();   // the context's counters: every use is on the caller's stream, behind a reset of its own
     Q.n = (uint32_t)q.n;
     Q.n_regions = (uint32_t)((q.n + PT_REGION - 1) / PT_REGION);
     Q.cull = q.cull;

@@ -233,7 +233,7 @@ hipError_t launch_render_rays(const pt_ctx* c, int walk, bool nee, size_t lds, i
         return with_int<3, 2, 1>(walk, [&](auto alg) {
             constexpr int OCC = n() ? 4 : 6;
             // a map on the context: the instantiation that looks it up (1); a map that is a light, in a call that runs NEE: the one that samples it (2)
-            return with_int<2, 1, 0>(c->env.texels ? (c->env.cx ? 2 : 1) : 0, [&](auto env) {
+            return with_int<2, 1, 0>(c->env.k.texels ? (c->env.k.cx ? 2 : 1) : 0, [&](auto env) {
                 constexpr int ENV = (env() == 2 && !n()) ? 1 : env();
                 return launch_resident(k_render_rays<n(), OCC, 16, alg(), ENV>, lds, INT_MAX, c->n_cu, (size_t)std::max(1, work_blocks), c->stream, P, R);
             });

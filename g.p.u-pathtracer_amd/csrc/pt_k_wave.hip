@@ -752,14 +752,8 @@ static int wave_layout(pt_ctx* c, const KParams& P, int work_tiles, WaveLayout& 
 
 // makes sure the context holds the path records of layout w
 static int wave_reserve(pt_ctx* c, const WaveLayout& w) {
-    if (w.need > c->wave_bytes) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(c->d_wave);
-        c->d_wave = nullptr;
-        c->wave_bytes = 0;
-        HIP_TRY(c, hipMalloc(&c->d_wave, w.need));
-        c->wave_bytes = w.need;
-    }
+    if (w.need > c->d_wave.count()) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, c->d_wave.reserve(w.need));
     return PT_OK;
 }
 
@@ -933,7 +927,7 @@ int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles, 
     int rc = wave_layout(c, P, work_tiles, w);
     if (rc == PT_OK) rc = wave_reserve(c, w);
     if (rc != PT_OK) return rc;
-    const WaveBuffers buf = wave_carve((char*)c->d_wave, w);
+    const WaveBuffers buf = wave_carve(c->d_wave.get(), w);
     const WavePlan plan = wave_plan(c, P, L, w.nee);
     folded = plan.fold_lp != 0;
     P.wf.nee = w.nee ? 1 : 0;
@@ -945,7 +939,7 @@ int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles, 
         P.wf.s_con = (float4*)(buf.nee + 2 * w.b_ray);
         P.wf.s_hit = (float2*)(buf.nee + 3 * w.b_ray);
         P.wf.s_cnt = (int*)(buf.nee + 3 * w.b_ray + w.b_hit);
-    } else P.wf.s_con = plan.occluders ? c->d_occ : nullptr;   // (the table of the tree on the context: occluders_collect)
+    } else P.wf.s_con = plan.occluders ? c->d_occ.get() : nullptr;   // (the table of the tree on the context: occluders_collect)
 
     hipStream_t st = c->stream;
     P.sc.n_top = 0;

@@ -194,15 +194,10 @@ __global__ void __launch_bounds__(PTR_BLOCK) k_refit_level(const RefitArgs A, co
 
 namespace ptmi {
 
-void refit_release(pt_ctx* c) {
-    (void)hipFree(c->refit.d_mem);
-    c->refit = pt_ctx::Refit();
-}
-
 // The schedule of the tree on the context: its item buffer comes back once, the reachable nodes of both trees get a height
 // (0: only leaf children), a child count (wide) and the record count of every leaf child, sorted by height.
 static int refit_prepare(pt_ctx* c) {
-    refit_release(c);
+    c->refit = pt_ctx::Refit();
     const uint64_t n_bin = c->tree.n_inner, n_rec = c->tree.n_refs, n_wide = c->tree.n_wide;
     const uint64_t rec_base = 4 * n_bin, wide_root = c->tree.wide_root;
     if (n_bin == 0 || n_rec == 0 || n_wide == 0 || wide_root != rec_base + 4 * n_rec || n_rec >= (1ull << 31))
@@ -211,16 +206,14 @@ static int refit_prepare(pt_ctx* c) {
     // the links, ids and `last` flags come back packed (k_refit_shape), not the item buffer
     std::vector<int32_t> h(2 * (n_bin + n_rec) + 4 * n_wide);
     {
-        int32_t* d_shape = nullptr;
-        HIP_TRY(c, hipMalloc((void**)&d_shape, h.size() * sizeof(int32_t)));
+        DevBuf<int32_t> d_shape;
+        HIP_TRY(c, d_shape.alloc(h.size()));
         const uint64_t n_all = n_bin + n_rec + n_wide;
         hipLaunchKernelGGL(k_refit_shape, dim3((unsigned)((n_all + PTR_BLOCK - 1) / PTR_BLOCK)), dim3(PTR_BLOCK), 0, c->stream, c->tree.d_nodes, n_bin,
-                           n_rec, n_wide, d_shape);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_shape, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(d_shape);
-        if (e != hipSuccess) return hip_fail(c, e, "pt_refit_bvh: reading the tree's shape");
+                           n_rec, n_wide, d_shape.get());
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(h.data(), d_shape.get(), d_shape.bytes(), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
     const int32_t* bl_links = h.data();                       // [n_bin][2]
     const int32_t* rec_w = h.data() + 2 * n_bin;              // [n_rec] id, last
@@ -323,9 +316,8 @@ static int refit_prepare(pt_ctx* c) {
     const size_t b_bl = up16(bl.size() * sizeof(int4)), b_wl = up16(wl.size() * sizeof(int4));
     const size_t b_bb = up16(6 * n_bin * sizeof(float)), b_wb = up16(6 * n_wide * sizeof(float)), b_rb = up16(6 * n_rec * sizeof(float));
     const size_t b_fu = up16(first.size() * sizeof(uint32_t));
-    char* m = nullptr;
-    HIP_TRY(c, hipMalloc((void**)&m, b_bl + b_wl + b_bb + b_wb + b_rb + b_fu));
-    R.d_mem = m;
+    HIP_TRY(c, R.d_mem.alloc(b_bl + b_wl + b_bb + b_wb + b_rb + b_fu));
+    char* m = R.d_mem.get();
     R.bin_list = (int4*)m; m += b_bl;
     R.wide_list = (int4*)m; m += b_wl;
     R.bin_box = (float*)m; m += b_bb;
@@ -355,7 +347,7 @@ extern "C" int pt_refit_bvh(pt_ctx* c, const float* tri_verts_dev, size_t n_tris
     pt_ctx::Refit& R = c->refit;
     if (!R.d_mem || R.scene_gen != c->scene_gen || R.items != c->tree.d_nodes) {
         const int rc = refit_prepare(c);
-        if (rc != PT_OK) { refit_release(c); return rc; }
+        if (rc != PT_OK) { c->refit = pt_ctx::Refit(); return rc; }
     }
     RefitArgs A;
     A.items = c->tree.d_nodes;
@@ -384,7 +376,7 @@ extern "C" int pt_refit_bvh(pt_ctx* c, const float* tri_verts_dev, size_t n_tris
     if (const int rc = occluders_collect(c); rc != PT_OK) { c->tree.n_occ = 0; return rc; }
     HIP_TRY(c, span_end(c));
     // a path kernel on a side stream (PT_OPT_OVERLAP) waits for this before it reads the tree; the light list is collected again
-    if (!c->geom_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->geom_ev, hipEventDisableTiming));
+    HIP_TRY(c, c->geom_ev.ensure(hipEventDisableTiming));
     HIP_TRY(c, hipEventRecord(c->geom_ev, st));
     c->geom_gen++;
     return PT_OK;

@@ -107,14 +107,14 @@ int select_occluders(std::vector<OccTri>& tris, int32_t* ids, int cap) {
 int occluders_collect(pt_ctx* c) {
     const TreeState& t = c->tree;
     if (t.n_occ == 0 || !t.has_bvh || t.records_woop) return PT_OK;
-    if (!c->d_occ) HIP_TRY(c, hipMalloc((void**)&c->d_occ, 3 * PT_OCCLUDERS_MAX * sizeof(float4)));
+    HIP_TRY(c, c->d_occ.reserve(3 * PT_OCCLUDERS_MAX));   // (made once; nothing to wait for)
     OccList L;
     L.n = t.n_occ;
     std::memcpy(L.id, t.occ_ids, sizeof L.id);
     const uint32_t n_rec = (uint32_t)t.n_refs;
     // (a slot whose triangle the tree holds no record of stays all zero: a record no ray hits)
-    HIP_TRY(c, hipMemsetAsync(c->d_occ, 0, 3 * PT_OCCLUDERS_MAX * sizeof(float4), c->stream));
-    hipLaunchKernelGGL(k_collect_occluders, dim3((n_rec + 255) / 256), dim3(256), 0, c->stream, t.d_nodes + 4 * (size_t)t.n_inner, n_rec, L, c->d_occ);
+    HIP_TRY(c, hipMemsetAsync(c->d_occ.get(), 0, c->d_occ.bytes(), c->stream));
+    hipLaunchKernelGGL(k_collect_occluders, dim3((n_rec + 255) / 256), dim3(256), 0, c->stream, t.d_nodes + 4 * (size_t)t.n_inner, n_rec, L, c->d_occ.get());
     HIP_TRY(c, hipGetLastError());
     return PT_OK;
 }
@@ -125,15 +125,13 @@ int occluders_collect(pt_ctx* c) {
 static int tree_cost(pt_ctx* c, const TreeState& t, double* node_visits, double* tri_tests) {
     const unsigned n_blocks = (unsigned)((t.n_wide + 255) / 256);
     const size_t n_out = 1 + 2 * (size_t)n_blocks;
-    double* d_out = nullptr;
-    HIP_TRY(c, hipMalloc((void**)&d_out, n_out * sizeof(double)));
-    hipLaunchKernelGGL(k_tree_cost, dim3(n_blocks), dim3(256), 0, c->stream, t.d_nodes, t.wide_root, (uint32_t)t.n_wide, d_out);
-    hipError_t e = hipGetLastError();
+    DevBuf<double> d_out;
+    HIP_TRY(c, d_out.alloc(n_out));
+    hipLaunchKernelGGL(k_tree_cost, dim3(n_blocks), dim3(256), 0, c->stream, t.d_nodes, t.wide_root, (uint32_t)t.n_wide, d_out.get());
+    HIP_TRY(c, hipGetLastError());
     std::vector<double> h(n_out, 0.0);
-    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_out, n_out * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_out);
-    if (e != hipSuccess) return hip_fail(c, e, "tree cost (k_tree_cost)");
+    HIP_TRY(c, hipMemcpyAsync(h.data(), d_out.get(), d_out.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (!(h[0] > 0.0)) return fail(c, PT_ERR_INVALID, "tree cost: degenerate root box");
     double inner = 0.0, leaf = 0.0;
     for (unsigned b = 0; b < n_blocks; b++) { inner += h[1 + 2 * (size_t)b]; leaf += h[2 + 2 * (size_t)b]; }
@@ -145,7 +143,7 @@ static int tree_cost(pt_ctx* c, const TreeState& t, double* node_visits, double*
 // host hierarchy -> device tree: refine (leaves of at most PT_OPT_LEAF_MAX references), optimise (PT_OPT_OPTIMIZE), emit, upload
 static int tree_from_host(pt_ctx* c, ptscene::Tree& X, int32_t max_id, DevTree& out) {
     DevTree made;
-    TreeState& t = made.s;
+    DevTree& t = made;
     ptscene::refine(X, (uint32_t)c->opt_leaf_max);
     if (c->opt_optimize > 0 && c->opt_tri_test == 0) {   // every node re-inserted where the area cost grows least (pt_tree_opt.h)
         double before = 0.0, after = 0.0;
@@ -156,7 +154,7 @@ static int tree_from_host(pt_ctx* c, ptscene::Tree& X, int32_t max_id, DevTree& 
     const size_t nb = O.bin.size() * sizeof(float), tb = O.rec.size() * sizeof(float), wb = O.wide.size() * sizeof(float);
     if ((nb + tb + wb) / 16 >= (size_t)PT_SENTINEL) return fail(c, PT_ERR_INVALID, "tree from a host hierarchy: too large for 32-bit links");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMalloc((void**)&t.d_nodes, nb + tb + wb));
+    HIP_TRY(c, t.alloc_items((nb + tb + wb) / sizeof(float4)));   // (whole 64-byte items)
     HIP_TRY(c, hipMemcpy(t.d_nodes, O.bin.data(), nb, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy((char*)t.d_nodes + nb, O.rec.data(), tb, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy((char*)t.d_nodes + nb + tb, O.wide.data(), wb, hipMemcpyHostToDevice));
@@ -182,7 +180,7 @@ static int tree_from_host(pt_ctx* c, ptscene::Tree& X, int32_t max_id, DevTree& 
 // PT_OPT_OPTIMIZE and for Woop records.  soup: the nine vertex floats of the n triangles it was built from (the caller's own: records
 // are re-encoded from them bit for bit), triangle k reporting ids[k] (nullptr: k).
 static int optimise_device_tree(pt_ctx* c, DevTree& tree, const float* soup, const int32_t* ids, size_t n) {
-    const TreeState& in = tree.s;
+    const TreeState& in = tree;
     if (c->opt_optimize <= 0 || in.records_woop) return PT_OK;
     std::vector<const float*> by_id((size_t)in.max_tri_id + 1, nullptr);
     for (size_t k = 0; k < n; k++) by_id[ids ? (size_t)ids[k] : k] = soup + 9 * k;
@@ -197,20 +195,19 @@ static int optimise_device_tree(pt_ctx* c, DevTree& tree, const float* soup, con
         return fail(c, PT_ERR_DEVICE, "device-built tree: " + why);
     const float device_ms = in.build_ms;
     const int rc = tree_from_host(c, X, in.max_tri_id, tree);   // replaces `tree` when it succeeds
-    if (rc == PT_OK) tree.s.build_ms = device_ms;
+    if (rc == PT_OK) tree.build_ms = device_ms;
     return rc;
 }
 
-// ---- adoption: the only writer of pt_ctx::tree (pt_destroy frees it) ----------------------------------------------------------------
+// ---- adoption: the only writer of pt_ctx::tree ---------------------------------------------------------------------------------------
 // `occ`: the occluder list of the mesh the tree was made of (PT_OPT_LAST_OCCLUDERS; Woop records are not what the list's test reads).
 // The list and its table change with the tree and scene_gen: the old tree's table is overwritten behind the wait below, on the stream
 // every later launch of the context is ordered behind.  Should the copy fail the tree stands without a list.
 static int adopt_tree(pt_ctx* c, DevTree&& t, const OccList& occ) {
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // nothing in flight reads the old tree
-    refit_release(c);   // made for the old tree (pt_refit_bvh makes it again for this one)
-    (void)hipFree(c->tree.d_nodes);
-    c->tree = t.release();
+    HIP_TRY(c, quiesce(c));   // nothing in flight reads the old tree
+    c->refit = pt_ctx::Refit();   // made for the old tree (pt_refit_bvh makes it again for this one)
+    c->tree = std::move(t);
     c->scene_gen++;
     c->tree.n_occ = c->tree.records_woop ? 0u : occ.n;
     std::memcpy(c->tree.occ_ids, occ.id, sizeof occ.id);
@@ -246,7 +243,7 @@ int pt_upload_bvh(pt_ctx* c, const float* nodes, size_t n_node_vec4, const float
         return fail(c, PT_ERR_INVALID, "pt_upload_bvh: " + perr);
     int32_t max_id = -1;
     for (const ptscene::Ref& r : T.refs) max_id = std::max(max_id, r.id);
-    if (c->d_tri_matid && (size_t)max_id >= c->n_tri_matid)
+    if (c->mat.d_tri_matid && (size_t)max_id >= c->mat.n_tri_matid)
         return fail(c, PT_ERR_INVALID, "pt_upload_bvh: the triangle-material array on this context does not cover this BVH's triangle ids (clear or re-upload it first)");
     OccList occ;   // (from the parsed tree too, before a maker re-arranges its references)
     {
@@ -286,9 +283,9 @@ int pt_upload_bvh(pt_ctx* c, const float* nodes, size_t n_node_vec4, const float
     // PT_OPT_REBUILD 2: the re-clustered tree beside the caller's; the one that costs a random ray fewer wide-node visits stays.
     // Without a wide tree or a cost for the caller's, or with a failure on the re-clustered side (no error of the call), the caller's.
     double cost_a = 0.0, cost_b = 0.0, unused = 0.0;
-    if (rebuild == 2 && a.s.n_wide > 0 && tree_cost(c, a.s, &cost_a, &unused) == PT_OK) {
+    if (rebuild == 2 && a.n_wide > 0 && tree_cost(c, a, &cost_a, &unused) == PT_OK) {
         DevTree b;
-        if (reclustered(b) == PT_OK && tree_cost(c, b.s, &cost_b, &unused) == PT_OK && cost_b < cost_a) a = std::move(b);
+        if (reclustered(b) == PT_OK && tree_cost(c, b, &cost_b, &unused) == PT_OK && cost_b < cost_a) a = std::move(b);
         else c->err.clear();
     }
     return adopt_tree(c, std::move(a), occ);

@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -45,20 +46,16 @@ static bool auto_decide(pt_ctx* c, pt_ctx::AutoPick& a, bool wait) {
     bool wave_wanted = false;   // by any remembered configuration
     for (const AP& o : c->picks)
         if (o.key && (o.phase < AP::DECIDED || o.choice == PT_KERNEL_WAVEFRONT)) wave_wanted = true;
-    if (!wave_wanted && c->d_wave) {   // the pipeline's path records (3 GB at 1080p x 16 spp) are not needed; the trials that used them are done
-        (void)hipFree(c->d_wave);
-        c->d_wave = nullptr;
-        c->wave_bytes = 0;
-    }
+    if (!wave_wanted) c->d_wave.reset();   // the pipeline's path records (3 GB at 1080p x 16 spp) are not needed; the trials that used them are done
     return true;
 }
 
 int stage_mark(pt_ctx* c, int kind) {
     if (!c->opt_timing) return PT_OK;
     if (c->stage_used == c->stage_ev.size()) {
-        hipEvent_t e = nullptr;
-        HIP_TRY(c, hipEventCreate(&e));
-        c->stage_ev.push_back(e);
+        Event e;
+        HIP_TRY(c, e.ensure());
+        c->stage_ev.push_back(std::move(e));
         c->stage_kind.push_back(0);
     }
     HIP_TRY(c, hipEventRecord(c->stage_ev[c->stage_used], c->stream));
@@ -133,58 +130,27 @@ int pt_create(int device, pt_ctx** out) {
     hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess) return hip_fail(nullptr, e, "hipGetDeviceCount");
     if (device < 0 || device >= n) return fail(nullptr, PT_ERR_INVALID, "pt_create: no such device");
-    pt_ctx* c = new pt_ctx();
+    if ((e = hipSetDevice(device)) != hipSuccess) return hip_fail(nullptr, e, "hipSetDevice");
+    std::unique_ptr<pt_ctx> c(new pt_ctx());   // a failure below releases whatever the context holds by then
     c->device = device;
-    if ((e = hipSetDevice(device)) != hipSuccess) { delete c; return hip_fail(nullptr, e, "hipSetDevice"); }
-    if ((e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking)) != hipSuccess) { delete c; return hip_fail(nullptr, e, "hipStreamCreate"); }
+    if ((e = c->own_stream.create(hipStreamNonBlocking)) != hipSuccess) return hip_fail(nullptr, e, "pt_create: the context's own stream");
     c->stream = c->own_stream;
-    if ((e = hipMalloc(&c->d_counters, PT_CNT_N * sizeof(unsigned long long))) != hipSuccess) { pt_destroy(c); return hip_fail(nullptr, e, "hipMalloc"); }
-    if ((e = hipMemset(c->d_counters, 0, PT_CNT_N * sizeof(unsigned long long))) != hipSuccess) { pt_destroy(c); return hip_fail(nullptr, e, "hipMemset"); }
-    if ((e = queue_alloc(&c->d_queue)) != hipSuccess) { pt_destroy(c); return hip_fail(nullptr, e, "hipMalloc"); }
+    if ((e = c->d_counters.alloc(PT_CNT_N)) != hipSuccess) return hip_fail(nullptr, e, "pt_create: counters");
+    if ((e = hipMemset(c->d_counters.get(), 0, c->d_counters.bytes())) != hipSuccess) return hip_fail(nullptr, e, "hipMemset");
+    if ((e = c->d_queue.alloc(QUEUE_WORDS)) != hipSuccess) return hip_fail(nullptr, e, "pt_create: work counters");
     hipDeviceProp_t prop;
-    if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) { pt_destroy(c); return hip_fail(nullptr, e, "hipGetDeviceProperties"); }
+    if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return hip_fail(nullptr, e, "hipGetDeviceProperties");
     c->n_cu = prop.multiProcessorCount;
-    if ((e = hipEventCreate(&c->ev0)) != hipSuccess || (e = hipEventCreate(&c->ev1)) != hipSuccess) { pt_destroy(c); return hip_fail(nullptr, e, "hipEventCreate"); }
-    *out = c;
+    if ((e = c->ev0.ensure()) != hipSuccess || (e = c->ev1.ensure()) != hipSuccess) return hip_fail(nullptr, e, "pt_create: timing events");
+    *out = c.release();
     return PT_OK;
 }
 
 int pt_destroy(pt_ctx* c) {
     if (!c) return PT_OK;
     (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(c->tree.d_nodes);
-    (void)hipFree(c->d_spheres);
-    (void)hipFree(c->d_tri_matid);
-    (void)hipFree(c->d_mat_table);
-    (void)hipFree(c->d_light_slot);
-    (void)hipFree(c->d_tri_lights);
-    (void)hipFree(c->d_occ);
-    (void)hipFree(c->d_counters);
-    (void)hipFree(c->d_queue);
-    (void)hipFree(c->d_samples);
-    (void)hipFree(c->d_wave);
-    refit_release(c);
-    denoise_release(c);
-    for (pt_ctx::Side& s : c->side) {
-        if (s.stream) (void)hipStreamSynchronize(s.stream);
-        (void)hipFree(s.samples);
-        (void)hipFree(s.queue);
-        if (s.traced) (void)hipEventDestroy(s.traced);
-        if (s.folded) (void)hipEventDestroy(s.folded);
-        if (s.stream) (void)hipStreamDestroy(s.stream);
-    }
-    env_release(c);   // (behind the side streams' last kernels)
-    for (hipEvent_t e : c->stage_ev) (void)hipEventDestroy(e);
-    for (pt_ctx::AutoPick& a : c->picks)
-        for (hipEvent_t e : a.e) if (e) (void)hipEventDestroy(e);
-    if (c->lights_ev) (void)hipEventDestroy(c->lights_ev);
-    if (c->geom_ev) (void)hipEventDestroy(c->geom_ev);
-    if (c->switch_ev) (void)hipEventDestroy(c->switch_ev);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    (void)quiesce(c);   // every stream is idle before the first free
+    delete c;           // the members release what they own (pt_own.h)
     return PT_OK;
 }
 
@@ -196,7 +162,7 @@ int pt_set_stream(pt_ctx* c, void* s) {
         // calls on whichever stream is current, and a side stream's fold waits on the stream it was issued on: what the new stream is
         // given starts behind everything the old one has been given.  No host synchronisation.
         HIP_TRY(c, hipSetDevice(c->device));
-        if (!c->switch_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->switch_ev, hipEventDisableTiming));
+        HIP_TRY(c, c->switch_ev.ensure(hipEventDisableTiming));
         HIP_TRY(c, hipEventRecord(c->switch_ev, c->stream));
         HIP_TRY(c, hipStreamWaitEvent(next, c->switch_ev, 0));
     }
@@ -228,14 +194,14 @@ int pt_sync(pt_ctx* c) {
 int pt_malloc(pt_ctx* c, size_t bytes, void** out) {
     if (!c || !out || bytes == 0) return fail(c, PT_ERR_INVALID, "pt_malloc: bad argument");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMalloc(out, bytes));
+    HIP_TRY(c, device_alloc(out, bytes));
     return PT_OK;
 }
 int pt_free(pt_ctx* c, void* p) {
     if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipFree(p));
+    HIP_TRY(c, device_free(p));
     return PT_OK;
 }
 int pt_memset(pt_ctx* c, void* p, int v, size_t bytes) {
@@ -259,20 +225,8 @@ int pt_upload(pt_ctx* c, void* dst, const void* src, size_t bytes) {
     return PT_OK;
 }
 
-int pt_upload_tri_materials(pt_ctx* c, const pt_material* table, size_t n_materials, const int32_t* tri_material, size_t n_tris) {
-    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (n_materials == 0) {  // back to the one global material of pt_params
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(c->d_tri_matid); c->d_tri_matid = nullptr;
-        (void)hipFree(c->d_mat_table); c->d_mat_table = nullptr;
-        (void)hipFree(c->d_light_slot); c->d_light_slot = nullptr;
-        (void)hipFree(c->d_tri_lights); c->d_tri_lights = nullptr;
-        c->emissive_ids.clear();
-        c->n_tri_matid = 0;
-        c->mat_gen++;
-        return PT_OK;
-    }
+// the table and the light list of a pt_upload_tri_materials call (n_materials > 0) into `m`, the context untouched
+static int make_materials(pt_ctx* c, const pt_material* table, size_t n_materials, const int32_t* tri_material, size_t n_tris, Materials& m) {
     if (!table || !tri_material) return fail(c, PT_ERR_INVALID, "pt_upload_tri_materials: null array");
     if (n_materials > (1u << 24) || n_tris >= (size_t)0x7fffffff) return fail(c, PT_ERR_INVALID, "pt_upload_tri_materials: table too large");
     if (c->tree.has_bvh && (size_t)c->tree.max_tri_id >= n_tris && c->tree.max_tri_id >= 0)
@@ -282,33 +236,39 @@ int pt_upload_tri_materials(pt_ctx* c, const pt_material* table, size_t n_materi
     for (size_t i = 0; i < n_tris; i++)
         if (tri_material[i] < 0 || (size_t)tri_material[i] >= n_materials) return fail(c, PT_ERR_INVALID, "pt_upload_tri_materials: material index out of range");
     static_assert(sizeof(pt_material) == 32, "pt_material is two float4 rows");
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(c->d_tri_matid); c->d_tri_matid = nullptr;
-    (void)hipFree(c->d_mat_table); c->d_mat_table = nullptr;
-    c->n_tri_matid = 0;
-    HIP_TRY(c, hipMalloc((void**)&c->d_tri_matid, n_tris * sizeof(int32_t)));
-    HIP_TRY(c, hipMalloc((void**)&c->d_mat_table, n_materials * sizeof(pt_material)));
-    HIP_TRY(c, hipMemcpy(c->d_tri_matid, tri_material, n_tris * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_mat_table, table, n_materials * sizeof(pt_material), hipMemcpyHostToDevice));
-    c->n_tri_matid = n_tris;
+    HIP_TRY(c, m.d_tri_matid.alloc(n_tris));
+    HIP_TRY(c, m.d_mat_table.alloc(2 * n_materials));
+    HIP_TRY(c, hipMemcpy(m.d_tri_matid.get(), tri_material, n_tris * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(m.d_mat_table.get(), table, n_materials * sizeof(pt_material), hipMemcpyHostToDevice));
+    m.n_tri_matid = n_tris;
     // PT_FLAG_NEE: the triangles that emit, in id order, and where each one's light record goes
-    (void)hipFree(c->d_light_slot); c->d_light_slot = nullptr;
-    (void)hipFree(c->d_tri_lights); c->d_tri_lights = nullptr;
-    c->emissive_ids.clear();
-    c->mat_gen++;
     std::vector<int32_t> slot(n_tris, -1);
     for (size_t i = 0; i < n_tris; i++) {
-        const pt_material& m = table[tri_material[i]];
-        if (!(m.emi[0] == 0.0f && m.emi[1] == 0.0f && m.emi[2] == 0.0f)) {
-            slot[i] = (int32_t)c->emissive_ids.size();
-            c->emissive_ids.push_back((int32_t)i);
+        const pt_material& row = table[tri_material[i]];
+        if (!(row.emi[0] == 0.0f && row.emi[1] == 0.0f && row.emi[2] == 0.0f)) {
+            slot[i] = (int32_t)m.emissive_ids.size();
+            m.emissive_ids.push_back((int32_t)i);
         }
     }
-    if (!c->emissive_ids.empty()) {
-        HIP_TRY(c, hipMalloc((void**)&c->d_light_slot, n_tris * sizeof(int32_t)));
-        HIP_TRY(c, hipMalloc((void**)&c->d_tri_lights, c->emissive_ids.size() * 3 * sizeof(float4)));
-        HIP_TRY(c, hipMemcpy(c->d_light_slot, slot.data(), n_tris * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (!m.emissive_ids.empty()) {
+        HIP_TRY(c, m.d_light_slot.alloc(n_tris));
+        HIP_TRY(c, m.d_tri_lights.alloc(m.emissive_ids.size() * 3));
+        HIP_TRY(c, hipMemcpy(m.d_light_slot.get(), slot.data(), n_tris * sizeof(int32_t), hipMemcpyHostToDevice));
     }
+    return PT_OK;
+}
+
+int pt_upload_tri_materials(pt_ctx* c, const pt_material* table, size_t n_materials, const int32_t* tri_material, size_t n_tris) {
+    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Materials m;   // filled here, adopted at the end: a failure on the way leaves the context's table, light list and mat_gen as they were
+    if (n_materials > 0) {
+        const int rc = make_materials(c, table, n_materials, tri_material, n_tris, m);
+        if (rc != PT_OK) return rc;
+    }   // (else empty: back to the one global material of pt_params)
+    HIP_TRY(c, quiesce(c));   // nothing in flight reads the old table or light list
+    c->mat = std::move(m);
+    c->mat_gen++;
     return PT_OK;
 }
 
@@ -339,15 +299,13 @@ int pt_upload_spheres(pt_ctx* c, const pt_sphere* spheres, size_t n) {
     for (size_t i = 0; i < n; i++)
         if (spheres[i].mat < PT_MAT_DIFF || spheres[i].mat > PT_MAT_REFR) return fail(c, PT_ERR_INVALID, "pt_upload_spheres: bad material");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(c->d_spheres); c->d_spheres = nullptr;
-    c->n_spheres = 0;
-    if (n) {
-        HIP_TRY(c, hipMalloc((void**)&c->d_spheres, n * sizeof(pt_sphere)));
-        HIP_TRY(c, hipMemcpy(c->d_spheres, spheres, n * sizeof(pt_sphere), hipMemcpyHostToDevice));
-        c->n_spheres = (int)n;
-        std::memcpy(c->h_spheres, spheres, std::min<size_t>(n, PT_KSPHERES) * sizeof(pt_sphere));
-    }
+    pt_ctx::DevBuf<pt_sphere_d> fresh;   // complete before the old set is touched
+    HIP_TRY(c, fresh.alloc(n));
+    if (n) HIP_TRY(c, hipMemcpy(fresh.get(), spheres, n * sizeof(pt_sphere), hipMemcpyHostToDevice));
+    HIP_TRY(c, quiesce(c));   // nothing in flight reads the old spheres
+    c->d_spheres = std::move(fresh);
+    c->n_spheres = (int)n;
+    if (n) std::memcpy(c->h_spheres, spheres, std::min<size_t>(n, PT_KSPHERES) * sizeof(pt_sphere));
     return PT_OK;
 }
 
@@ -375,7 +333,7 @@ static int check_call(pt_ctx* c, const float* accum_dev, const uint32_t* rgba_de
 
 // PT_FLAG_NEE over emissive triangles: the call samples the light list
 static bool samples_tri_lights(const pt_ctx* c, const pt_params* p) {
-    return (p->flags & PT_FLAG_NEE) && c->tree.has_bvh && !c->emissive_ids.empty();
+    return (p->flags & PT_FLAG_NEE) && c->tree.has_bvh && !c->mat.emissive_ids.empty();
 }
 
 // the scene, its geometry (pt_refit_bvh) or the materials changed: copies the lights' vertices out of the records again
@@ -385,14 +343,14 @@ static int refresh_tri_lights(pt_ctx* c, const pt_params* p) {
     const uint64_t key = (c->scene_gen << 32) ^ c->mat_gen;
     if (c->lights_key == key && c->lights_geom == c->geom_gen) return PT_OK;
     const uint32_t n_rec = (uint32_t)c->tree.n_refs;
-    HIP_TRY(c, hipMemsetAsync(c->d_tri_lights, 0, c->emissive_ids.size() * 3 * sizeof(float4), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->mat.d_tri_lights.get(), 0, c->mat.d_tri_lights.bytes(), c->stream));
     hipLaunchKernelGGL(k_collect_tri_lights, dim3((n_rec + 255) / 256), dim3(256), 0, c->stream, c->tree.d_nodes + 4 * (size_t)c->tree.n_inner, n_rec,
-                       c->d_light_slot, (uint32_t)c->n_tri_matid, c->d_tri_matid, c->d_mat_table, c->d_tri_lights);
+                       c->mat.d_light_slot.get(), (uint32_t)c->mat.n_tri_matid, c->mat.d_tri_matid.get(), c->mat.d_mat_table.get(), c->mat.d_tri_lights.get());
     HIP_TRY(c, hipGetLastError());
     c->lights_key = key;
     c->lights_geom = c->geom_gen;
     // a path kernel on a side stream (PT_OPT_OVERLAP) must not read the list before it is written
-    if (!c->lights_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->lights_ev, hipEventDisableTiming));
+    HIP_TRY(c, c->lights_ev.ensure(hipEventDisableTiming));
     HIP_TRY(c, hipEventRecord(c->lights_ev, c->stream));
     c->lights_gen++;
     return PT_OK;
@@ -402,7 +360,7 @@ static int refresh_tri_lights(pt_ctx* c, const pt_params* p) {
 static void fill_path_params(const pt_ctx* c, const pt_params* p, uint32_t spp, KParams& P) {
     std::memset(&P, 0, sizeof P);
     scene_view(c, P.sc, P.ksph);
-    P.counters = c->d_counters;
+    P.counters = c->d_counters.get();
     P.W = p->width; P.H = p->height;
     P.depth = p->depth;
     P.cull = p->cull_backfaces;
@@ -410,14 +368,14 @@ static void fill_path_params(const pt_ctx* c, const pt_params* p, uint32_t spp, 
     P.tri_mat = p->tri_mat;
     for (int i = 0; i < 3; i++) { P.tri_col[i] = p->tri_col[i]; P.tri_emi[i] = p->tri_emi[i]; P.bk[i] = p->bk_color[i]; }
     P.air_ior = p->air_ior; P.glass_ior = p->glass_ior; P.phong = p->phong_expo;
-    P.tri_matid = c->d_tri_matid;
-    P.mat_table = c->d_mat_table;
+    P.tri_matid = c->mat.d_tri_matid.get();
+    P.mat_table = c->mat.d_mat_table.get();
     P.flags = p->flags;
     if (samples_tri_lights(c, p)) {
-        P.tri_lights = c->d_tri_lights;
-        P.n_tri_lights = (int)c->emissive_ids.size();
+        P.tri_lights = c->mat.d_tri_lights.get();
+        P.n_tri_lights = (int)c->mat.emissive_ids.size();
     }
-    pt_set_env(P, c->env);   // (all zero without a map; with one the stage-split pipeline, which writes wf over these bytes, is never chosen)
+    pt_set_env(P, c->env.k);   // (all zero without a map; with one the stage-split pipeline, which writes wf over these bytes, is never chosen)
 }
 
 // the kernel arguments that the context and the call's arguments give; what the plan decides (samples, LDS layout, queue) is added
@@ -468,7 +426,7 @@ static int auto_lookup(pt_ctx* c, const pt_params* p, uint32_t spp, bool moments
         slot = lru;
         AP& n = c->picks[slot];
         if (n.phase > 0 && n.phase < AP::DECIDED)   // trials of the configuration it held may still be in flight: its events must be idle
-            for (hipEvent_t e : n.e) if (e) (void)hipEventSynchronize(e);
+            for (const Event& e : n.e) if (e) (void)hipEventSynchronize(e);
         n.key = key; n.phase = 0; n.choice = PT_KERNEL_PERSISTENT; n.ms[0] = n.ms[1] = 0.f;
     }
     AP& a = c->picks[slot];
@@ -478,8 +436,7 @@ static int auto_lookup(pt_ctx* c, const pt_params* p, uint32_t spp, bool moments
     probe = -1;
     (void)auto_decide(c, a, false);   // all trials queued: decide once their events have completed, never wait for them
     if (a.phase < AP::TRIALS) {
-        for (hipEvent_t& e : a.e)
-            if (!e) HIP_TRY(c, hipEventCreate(&e));
+        for (Event& e : a.e) HIP_TRY(c, e.ensure());
         probe = a.phase++;   // (counted here, before the call's later steps, which can still fail: a trial that never ran stays counted)
     }
     return PT_OK;
@@ -506,7 +463,7 @@ static int plan_call(pt_ctx* c, const pt_params* p, const KParams& P, uint32_t s
     // the kernel family, every rule once and in this order: the option; PT_KERNEL_AUTO's table; PT_FLAG_NEE; what a family cannot run.
     // The stage-split pipeline needs a BVH, at least one bounce, the wide walk over exact records and a context without an
     // environment map (its last-segment any-hit launch shades misses without a ray in hand).
-    const bool wave_ok = t.has_bvh && P.depth > 0 && L.walk == 2 && !c->env.texels;
+    const bool wave_ok = t.has_bvh && P.depth > 0 && L.walk == 2 && !c->env.k.texels;
     int kernel = c->opt_kernel;
     plan.probe = -1;
     plan.pick = nullptr;
@@ -559,41 +516,35 @@ static int plan_call(pt_ctx* c, const pt_params* p, const KParams& P, uint32_t s
     L.work_blocks = (int)((slots + plan.chunk * waves_per_block - 1) / (plan.chunk * waves_per_block));
     L.n_cu = c->n_cu;
     L.moments = moments;
-    L.env = c->env.texels ? (c->env.cx ? 2 : 1) : 0;
+    L.env = c->env.k.texels ? (c->env.k.cx ? 2 : 1) : 0;
     return PT_OK;
 }
 
 // the next side slot; its stream, events and queue counters are made on first use
 static int side_acquire(pt_ctx* c, pt_ctx::Side*& sd) {
     sd = &c->side[c->side_next];
-    c->side_next ^= 1;   // (flipped before the creations below can fail: the slot is then made by its next turn)
-    if (sd->stream) return PT_OK;
+    c->side_next ^= 1;   // (flipped before the creations below can fail: the slot's next turn makes what is still missing)
     // a priority of its own: ROCm maps the streams of one priority onto a few hardware queues round-robin (four
     // by default, GPU_MAX_HW_QUEUES), and a side stream that shares a hardware queue with the caller's stream or
     // with the other side stream runs in order behind it — no overlap and a 5-9 % LOSS (measured with a second
     // context alive).  The high-priority class has queues of its own.
-    int prio_lo = 0, prio_hi = 0;
-    HIP_TRY(c, hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-    HIP_TRY(c, hipStreamCreateWithPriority(&sd->stream, hipStreamNonBlocking, prio_hi));
-    HIP_TRY(c, hipEventCreateWithFlags(&sd->traced, hipEventDisableTiming));
-    HIP_TRY(c, hipEventCreateWithFlags(&sd->folded, hipEventDisableTiming));
-    HIP_TRY(c, queue_alloc(&sd->queue));
+    if (!sd->stream) {
+        int prio_lo = 0, prio_hi = 0;
+        HIP_TRY(c, hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+        HIP_TRY(c, sd->stream.create(hipStreamNonBlocking, prio_hi));
+    }
+    HIP_TRY(c, sd->traced.ensure(hipEventDisableTiming));
+    HIP_TRY(c, sd->folded.ensure(hipEventDisableTiming));
+    HIP_TRY(c, sd->queue.reserve(QUEUE_WORDS));
     return PT_OK;
 }
 
-// the sample buffer of the call, the side slot's own or the context's, grown to `need` bytes
+// the sample buffer of the call, the side slot's own or the context's, grown to `need` floats
 static int samples_reserve(pt_ctx* c, pt_ctx::Side* sd, size_t need, KParams& P) {
-    float*& buf = sd ? sd->samples : c->d_samples;
-    size_t& have = sd ? sd->samples_bytes : c->samples_bytes;
-    if (need > have) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));   // every path kernel has a fold behind it on this stream
-        (void)hipFree(buf);
-        buf = nullptr;
-        have = 0;
-        HIP_TRY(c, hipMalloc((void**)&buf, need));
-        have = need;
-    }
-    P.samples = buf;
+    pt_ctx::DevBuf<float>& buf = sd ? sd->samples : c->d_samples;
+    if (need > buf.count()) HIP_TRY(c, hipStreamSynchronize(c->stream));   // every path kernel has a fold behind it on this stream
+    HIP_TRY(c, buf.reserve(need));
+    P.samples = buf.get();
     return PT_OK;
 }
 
@@ -624,7 +575,7 @@ static void apply_plan(const pt_ctx* c, const CallPlan& plan, const pt_ctx::Side
     P.sc.n_top = plan.n_top;
     P.sph_tab = plan.sph_tab;
     P.chunk = plan.chunk;
-    if (plan.kernel == PT_KERNEL_PERSISTENT) queue_params(c, sd ? sd->queue : c->d_queue, P);
+    if (plan.kernel == PT_KERNEL_PERSISTENT) queue_params(c, sd ? sd->queue.get() : c->d_queue.get(), P);
 }
 }  // namespace ptmi
 
@@ -648,12 +599,12 @@ int pt_render_moments(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, float* mo
     // the buffers the plan asks for
     pt_ctx::Side* sd = nullptr;
     if (plan.side && (rc = side_acquire(c, sd)) != PT_OK) return rc;
-    if (plan.samples && (rc = samples_reserve(c, sd, (size_t)spp * (size_t)p->width * (size_t)p->height * 3 * sizeof(float), P)) != PT_OK) return rc;
+    if (plan.samples && (rc = samples_reserve(c, sd, (size_t)spp * (size_t)p->width * (size_t)p->height * 3, P)) != PT_OK) return rc;
     if (sd && (rc = side_order(c, sd, P.tri_lights != nullptr)) != PT_OK) return rc;
-    hipStream_t trace_stream = sd ? sd->stream : c->stream;   // the stream the path kernel runs on
+    hipStream_t trace_stream = sd ? (hipStream_t)sd->stream : c->stream;   // the stream the path kernel runs on
     apply_plan(c, plan, sd, P);
 
-    if (c->opt_counters) HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, PT_CNT_N * sizeof(unsigned long long), c->stream));
+    if (c->opt_counters) HIP_TRY(c, hipMemsetAsync(c->d_counters.get(), 0, c->d_counters.bytes(), c->stream));
     if (probe >= 0 && (probe & 1)) {   // a trial of the pipeline: its path records are allocated BEFORE the timed span
         rc = wave_reserve(c, P, plan.work_tiles);
         if (rc != PT_OK) return rc;
@@ -773,10 +724,10 @@ int pt_render_rays(pt_ctx* c, const float* rays_dev, size_t n_rays, uint64_t fir
     P.sc.top_base = walk >= 2 ? P.sc.wide_root : 0;
     size_t lds = (size_t)16 * PT_BLOCK * 4;
     P.sph_tab = c->opt_sph_lds ? lds_sphere_table(lds) : -1;
-    queue_params(c, c->d_queue, P);   // the context's counters: every use is on the caller's stream, behind a reset of its own
+    queue_params(c, c->d_queue.get(), P);   // the context's counters: every use is on the caller's stream, behind a reset of its own
     const ptmi::RaysCall R{rays_dev, radiance_dev, first_index, n_rays, mode == PT_RAYS_HDR};
     const uint32_t per_launch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(spp, RAYS_MAX_SLOTS / n_rays));
-    if (per_launch > 1 && (rc = samples_reserve(c, nullptr, (size_t)per_launch * n_rays * 3 * sizeof(float), P)) != PT_OK) return rc;
+    if (per_launch > 1 && (rc = samples_reserve(c, nullptr, (size_t)per_launch * n_rays * 3, P)) != PT_OK) return rc;
     P.smp_ss = n_rays;
     P.smp_ps = 1u;
     HIP_TRY(c, span_begin(c));
@@ -799,7 +750,7 @@ int pt_get_counters(pt_ctx* c, pt_counters* out) {
     if (!c || !out) return fail(c, PT_ERR_INVALID, "pt_get_counters: null argument");
     unsigned long long h[PT_CNT_WAVE];
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h, c->d_counters.get(), sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     out->rays = h[PT_CNT_RAYS]; out->inner = h[PT_CNT_INNER]; out->tris = h[PT_CNT_TRIS]; out->leaves = h[PT_CNT_LEAVES];
     out->hits = h[PT_CNT_HITS]; out->paths = h[PT_CNT_PATHS];
@@ -810,7 +761,7 @@ int pt_get_wave_stats(pt_ctx* c, uint64_t* out, int n) {
     if (!c || !out || n < 0) return fail(c, PT_ERR_INVALID, "pt_get_wave_stats: bad argument");
     unsigned long long h[PT_CNT_N];
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h, c->d_counters.get(), sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < n && i < PT_WAVE_STATS; i++) out[i] = h[PT_CNT_WAVE + i];
     return PT_OK;

@@ -1,10 +1,11 @@
 """Call histories of one long-lived context, for tests/test_call_sequences.py (CPU) and tests/test_gpu_call_sequences.py (GPU).
 
 THE PROPERTY.  Whatever valid calls a context has seen, the next observation is bit for bit what a fresh context returns when it
-is given only the current state.  The library keeps state that outlives a call (csrc/pt_ctx.h: the grow-only buffers d_wave,
-d_samples, side[x].samples, d_denoise and d_frame_err; the generations scene_gen / geom_gen / mat_gen / env_gen and what is keyed
-by them; the emissive-triangle light list; PT_KERNEL_AUTO's table of picks; the two side-stream slots; the caller's stream), so a
-wrong key, a missed wait or a stale carve shows only after a particular history.
+is given only the current state.  The library keeps state that outlives a call (csrc/pt_ctx.h: the grow-only DevBuf members d_wave,
+d_samples, side[x].samples, d_denoise, d_frame_err and d_occ, each grown by one reserve() behind the wait its call site states; the
+scene's values tree / d_spheres / mat / env, each adopted behind quiesce(); the generations scene_gen / geom_gen / mat_gen / env_gen
+and what is keyed by them; the emissive-triangle light list in `mat`; PT_KERNEL_AUTO's table of picks; the two side-stream slots;
+the caller's stream), so a wrong key, a missed wait or a stale carve shows only after a particular history.
 
 WHAT IS HERE
   State        the shadow state: what the context should hold now, as a hashable value (`canon()` is its canonical form).
