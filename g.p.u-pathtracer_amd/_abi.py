@@ -94,6 +94,7 @@ FLAG_WRITE_RGBA = 1 << 1
 FLAG_FACE_FORWARD, FLAG_COSINE_DIFF, FLAG_GLASS_FIX, FLAG_RUSSIAN_ROULETTE, FLAG_MISS_KEEPS_PATH = 1 << 2, 1 << 3, 1 << 4, 1 << 5, 1 << 6
 FLAG_RR_CPU_TRACER = 1 << 7
 FLAG_NEE = 1 << 8
+FLAG_MIS = 1 << 9
 FLAGS_SMALLPT = FLAG_FACE_FORWARD | FLAG_COSINE_DIFF | FLAG_RUSSIAN_ROULETTE | FLAG_MISS_KEEPS_PATH
 FLAGS_CPU_TRACER = FLAG_FACE_FORWARD | FLAG_COSINE_DIFF | FLAG_RR_CPU_TRACER | FLAG_MISS_KEEPS_PATH
 RAYS_CLAMPED, RAYS_HDR = 0, 1

@@ -374,6 +374,7 @@ struct LaunchCfg {
     bool moments;      // the call keeps luminance moments (pt_render_moments): they are the separate fold launch's job
     int env;           // 1: the context has an environment map: the instantiations whose miss looks it up (pt_env.h); 2: the map is a
                        // light too (PT_OPT_ENV_LIGHT): the megakernel's instantiation whose NEE branch draws from it; 0: no map
+    bool mis;          // the call has PT_FLAG_MIS: the megakernel's instantiations that weigh shadow rays against bounce rays
 };
 hipError_t launch_mega(const LaunchCfg& L, const KParams& P, hipStream_t st);        // pt_k_mega.hip
 hipError_t launch_rays(const KScene& sc, size_t lds, const float4* rays, size_t n, int cull, float* t_out, int* tri_out,
@@ -413,7 +414,7 @@ struct RaysCall {
     size_t n;               // 0 < n < 2^32
     int hdr;                // mode == PT_RAYS_HDR
 };
-hipError_t launch_render_rays(const pt_ctx* c, int walk, bool nee, size_t lds, int work_blocks, const KParams& P, const RaysCall& r);
+hipError_t launch_render_rays(const pt_ctx* c, int walk, bool nee, bool mis, size_t lds, int work_blocks, const KParams& P, const RaysCall& r);
 hipError_t launch_fold_rays(const pt_ctx* c, const KParams& P, const RaysCall& r);
 // PT_OPT_TIMING: marks the end of a stage of the running call on the context's stream (no-op when timing is off)
 int stage_mark(pt_ctx* c, int kind_of_work_since_last_mark);

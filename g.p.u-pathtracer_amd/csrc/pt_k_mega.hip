@@ -7,7 +7,8 @@
 // OCC = waves per SIMD the register allocator must leave room for (4 / 6 / 8)
 // ALG = 0 while-while walk (Aila-Laine), 1 unified-step walk, 2 wide (4-way quantised) walk,
 //       3 wide walk over Woop records
-template <bool COUNT, int OCC, int LSTK, int ALG, int ENV>
+// MIS = the shadow rays and bounce rays of PT_FLAG_NEE weighed against each other (PT_FLAG_MIS, path_shade_hit)
+template <bool COUNT, int OCC, int LSTK, int ALG, int ENV, bool MIS>
 __global__ void __launch_bounds__(PT_BLOCK, OCC) k_trace_mega_bvh2(const KParams P) {
     float4* s_top = s_dyn;
     lds_load_top<PT_BLOCK>(P.sc, s_top);
@@ -33,7 +34,7 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_trace_mega_bvh2(const KParams
 
     uint32_t n_done = P.spp;
     if (P.samples) {
-        const v3 col = pt_get_sample<COUNT, ALG, ENV>(P, px, py, pix, P.frame + s_only, stk, s_top, tc, n_rays, n_hits);
+        const v3 col = pt_get_sample<COUNT, ALG, ENV, MIS>(P, px, py, pix, P.frame + s_only, stk, s_top, tc, n_rays, n_hits);
         float* dst = pt_sample_ptr(P, (uint32_t)s_only, (size_t)pix);
         dst[0] = col.x; dst[1] = col.y; dst[2] = col.z;
         n_done = 1;
@@ -42,7 +43,7 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_trace_mega_bvh2(const KParams
         float ax = 0.f, ay = 0.f, az = 0.f;
         if (P.sample_index != 1) { ax = acc[0]; ay = acc[1]; az = acc[2]; }
         for (uint32_t s = 0; s < P.spp; s++) {
-            const v3 col = pt_get_sample<COUNT, ALG, ENV>(P, px, py, pix, P.frame + s, stk, s_top, tc, n_rays, n_hits);
+            const v3 col = pt_get_sample<COUNT, ALG, ENV, MIS>(P, px, py, pix, P.frame + s, stk, s_top, tc, n_rays, n_hits);
             pt_accumulate(ax, ay, az, col, P.sample_index + s);
         }
         acc[0] = ax; acc[1] = ay; acc[2] = az;
@@ -88,11 +89,15 @@ hipError_t launch_mega(const LaunchCfg& L, const KParams& P, hipStream_t st) {
     auto go = [&](auto count, auto occ, auto lstk) {
         return with_int<2, 1, 0>(std::min(L.walk, 2), [&](auto alg) {
             return with_int<2, 1, 0>(L.env, [&](auto env) {   // a map on the context: the instantiation that looks it up (1), and samples it under PT_FLAG_NEE (2)
-                const auto kernel = k_trace_mega_bvh2<count(), occ(), lstk(), alg(), env()>;
-                const hipError_t e = allow_lds(kernel, L.lds);
-                if (e != hipSuccess) return e;
-                hipLaunchKernelGGL(kernel, dim3(L.blocks), dim3(PT_BLOCK), L.lds, st, P);
-                return hipGetLastError();
+                // PT_FLAG_MIS: instantiated without a map (0) and with one that is a light (2), which also serves one that is none
+                return with_bool(L.mis, [&](auto mis) {
+                    constexpr int ENV = mis() && env() == 1 ? 2 : env();
+                    const auto kernel = k_trace_mega_bvh2<count(), occ(), lstk(), alg(), ENV, mis()>;
+                    const hipError_t e = allow_lds(kernel, L.lds);
+                    if (e != hipSuccess) return e;
+                    hipLaunchKernelGGL(kernel, dim3(L.blocks), dim3(PT_BLOCK), L.lds, st, P);
+                    return hipGetLastError();
+                });
             });
         });
     };

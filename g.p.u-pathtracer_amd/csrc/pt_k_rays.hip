@@ -39,7 +39,8 @@ __device__ __forceinline__ bool rays_finite(v3 a) {
 }
 
 // NEE: the lane can walk the shadow ray path_shade asks for (PT_FLAG_NEE) before it goes on with the path
-template <bool NEE, int OCC, int LSTK, int ALG, int ENV>
+// MIS: ... and path_shade weighs that ray against the bounce ray (PT_FLAG_MIS); only with NEE
+template <bool NEE, int OCC, int LSTK, int ALG, int ENV, bool MIS>
 __global__ void __launch_bounds__(PT_BLOCK, OCC) k_render_rays(const KParams P, const KRays R) {
     // sphere attributes + centres for the shading code (see path_shade): the table of k_trace_persist_bvh2, filled from the device
     // array (the first PT_KSPHERES spheres there are the ones in the kernel arguments; rows past n_spheres are never read)
@@ -64,10 +65,11 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_render_rays(const KParams P, 
 
     int phase = RP_IDLE;
     uint32_t ray = 0, s_idx = 0;
-    PathState ps;
+    PathStateOf<MIS> ps;
     TravState ts;
     ps.o = ps.d = ps.mask = ps.accu = V3(0.f, 0.f, 0.f);
     ps.depth = 0; ps.rng.s0 = ps.rng.s1 = ps.rng.n = 0; ps.nee_mask = 0;
+    if constexpr (MIS) ps.pb = 0.f;
     ts.idx = ts.idy = ts.idz = ts.oodx = ts.oody = ts.oodz = 0.f;
     ts.node = PT_SENTINEL; ts.leaf = 0; ts.sp = 0;
     ts.h = pt_no_hit();
@@ -169,7 +171,7 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_render_rays(const KParams P, 
             } else {
                 NeeReq req;
                 req.want = false;
-                done = path_shade<ENV>(P, ps, ts.h, col, P.sph_tab, NEE && (P.flags & PT_FLAG_NEE) ? &req : nullptr);
+                done = path_shade<ENV, MIS>(P, ps, ts.h, col, P.sph_tab, NEE && (P.flags & PT_FLAG_NEE) ? &req : nullptr);
                 if (NEE && req.want) {
                     if (P.sc.has_bvh) {
                         walk_shadow = true;
@@ -226,8 +228,10 @@ static KRays rays_args(const RaysCall& r) { return KRays{(const float4*)r.rays, 
 
 // Instantiated: the wide walk (2; 3 = Woop records) and the unified binary walk (1: trees too deep for the wide one, PT_OPT_WALK 0 / 1),
 // each at 6 waves per SIMD without and at 4 with the shadow-ray state, 16 stack entries per lane in LDS; each of those without and
-// with the environment-map lookup (ENV 1), the NEE ones also with the draw from a map that is a light (ENV 2).
-hipError_t launch_render_rays(const pt_ctx* c, int walk, bool nee, size_t lds, int work_blocks, const KParams& P, const RaysCall& r) {
+// with the environment-map lookup (ENV 1), the NEE ones also with the draw from a map that is a light (ENV 2).  PT_FLAG_MIS (mis, only with
+// nee and never over Woop records: pt_render_rays has refused those): the NEE instantiations of walks 2 and 1 once more, without a map
+// and with ENV 2, which serves a map that is no light too.
+hipError_t launch_render_rays(const pt_ctx* c, int walk, bool nee, bool mis, size_t lds, int work_blocks, const KParams& P, const RaysCall& r) {
     const KRays R = rays_args(r);
     return with_bool(nee, [&](auto n) {
         return with_int<3, 2, 1>(walk, [&](auto alg) {
@@ -235,7 +239,11 @@ hipError_t launch_render_rays(const pt_ctx* c, int walk, bool nee, size_t lds, i
             // a map on the context: the instantiation that looks it up (1); a map that is a light, in a call that runs NEE: the one that samples it (2)
             return with_int<2, 1, 0>(c->env.k.texels ? (c->env.k.cx ? 2 : 1) : 0, [&](auto env) {
                 constexpr int ENV = (env() == 2 && !n()) ? 1 : env();
-                return launch_resident(k_render_rays<n(), OCC, 16, alg(), ENV>, lds, INT_MAX, c->n_cu, (size_t)std::max(1, work_blocks), c->stream, P, R);
+                if constexpr (n() && alg() != 3) {
+                    if (mis) return launch_resident(k_render_rays<true, OCC, 16, alg(), ENV == 1 ? 2 : ENV, true>, lds, INT_MAX, c->n_cu, (size_t)std::max(1, work_blocks), c->stream, P, R);
+                }
+                if (mis) return hipErrorInvalidValue;   // no such instantiation, and no quiet fall-back: pt_render_rays has refused the call
+                return launch_resident(k_render_rays<n(), OCC, 16, alg(), ENV, false>, lds, INT_MAX, c->n_cu, (size_t)std::max(1, work_blocks), c->stream, P, R);
             });
         });
     });

@@ -259,11 +259,11 @@ static_assert(PT_CNT_WAVE == sizeof(pt_counters) / sizeof(uint64_t) && PT_CNT_N 
 #include "pt_walks.h"
 #include "pt_shade.h"
 
-template <bool COUNT, int ALG, int ENV, class STK>
+template <bool COUNT, int ALG, int ENV, bool MIS, class STK>
 __device__ __forceinline__ v3 pt_get_sample(const KParams& P, int px, int py, uint64_t pix, uint64_t frame,
                                             STK& stk, const float4* __restrict__ s_top, TravCount& tc,
                                             uint32_t& n_rays, uint32_t& n_hits) {
-    PathState ps;
+    PathStateOf<MIS> ps;
     path_begin(P, px, py, pix, frame, ps);
     const bool cull = P.cull != 0;
     v3 col = V3(0.f, 0.f, 0.f);
@@ -288,7 +288,7 @@ __device__ __forceinline__ v3 pt_get_sample(const KParams& P, int px, int py, ui
         if (COUNT) { n_rays++; n_hits += (h.tri != -1); }
         NeeReq req;
         req.want = false;
-        const bool done = path_shade<ENV>(P, ps, h, col, -1, (P.flags & PT_FLAG_NEE) ? &req : nullptr);
+        const bool done = path_shade<ENV, MIS>(P, ps, h, col, -1, (P.flags & PT_FLAG_NEE) ? &req : nullptr);
         // the loop's exit condition crosses the shadow walk below in a VGPR: kept as a lane mask in SGPRs, hipcc (ROCm 7.2)
         // lost it across the walk's wave-uniform loop and a finished path ran one more bounce
         int done_v = done ? 1 : 0;

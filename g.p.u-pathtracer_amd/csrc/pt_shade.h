@@ -1,6 +1,7 @@
 // pt_shade.h — one sample of one pixel cut into pieces: camera ray, sphere tests, shading / BRDF, accumulate
 // (getSample, tracer.cu:27-339; rows a2-a4, a8-a10).  Included by pt_kernels.h.
 #pragma once
+#include <type_traits>
 #include "pt_env.h"
 
 // ---------------------------------------------------------------------------------------
@@ -12,6 +13,10 @@ struct PathState {
     pt_rng rng;
     uint32_t nee_mask;   // PT_FLAG_NEE: spheres whose light the previous bounce already sampled with a shadow ray
 };
+// PT_FLAG_MIS: the state gains the cosine lobe's density of the bounce direction the DIFF hit before took (p_b', ptmi.h) — in the MIS
+// instantiations alone: the others keep the PathState they had, so that their registers are allocated as they were
+struct PathStateMis : PathState { float pb; };
+template <bool MIS> using PathStateOf = std::conditional_t<MIS, PathStateMis, PathState>;
 
 // PT_FLAG_NEE: the shadow ray a DIFF hit asks for.  The caller traces it against the triangles (the spheres in its way
 // have been tested already) and, when nothing is hit closer than t_max, adds `contrib` to the path's gathered light.
@@ -125,6 +130,30 @@ __device__ __forceinline__ SceneHit pt_closest_sphere(const KParams& P, v3 o, v3
     return sh;
 }
 
+// PT_FLAG_MIS: the balance heuristic between a DIFF hit's shadow ray and its bounce ray (include/ptmi.h), per light.  Both weights go
+// through r = n_all / p_k = 1 / q, the reciprocal of the shadow technique's density of the direction: it stays finite where a
+// light's solid angle rounds to 0.  binary32, plain * and +.
+// lights that were pickable at the hit nee_mask was made at: the sphere bits, the emissive triangles with bit 8, the map with bit 9
+__device__ __forceinline__ float pt_mis_lights(uint32_t nee_mask, int n_tri_lights) {
+    return (float)(__popc(nee_mask & 0xffu) + ((nee_mask & 0x100u) ? n_tri_lights : 0) + (int)((nee_mask >> 9) & 1u));
+}
+// the shadow ray's weight w_l = q / (q + p_b) = 1 / (1 + p_b * r), p_b = cosl / pi
+__device__ __forceinline__ float pt_mis_light_weight(float cosl, float r) {
+    return 1.0f / (1.0f + (cosl / 3.14159274f) * r);
+}
+// the bounce ray's weight w_b = p_b' / (p_b' + q') = a / (a + 1) with a = p_b' * r', r' = n_all * inv_pk; a light whose density is
+// infinite (inv_pk = 0) leaves the bounce nothing, one the shadow technique cannot draw towards leaves it everything (below)
+__device__ __forceinline__ float pt_mis_bounce_weight_inv(float pb, float inv_pk, float n_all) {
+    const float a = fminf(pb * (n_all * inv_pk), PT_F32_MAX);
+    return a / (a + 1.0f);
+}
+// ... from the density itself (the map's): 1 where it is not greater than 0
+__device__ __forceinline__ float pt_mis_bounce_weight(float pb, float pk, float n_all) {
+    if (!(pk > 0.0f)) return 1.0f;
+    const float a = fminf(pb * (n_all / pk), PT_F32_MAX);
+    return a / (a + 1.0f);
+}
+
 // One bounce after the closest triangle hit `h` and the sphere tests `sh` are known
 // (tracer.cu:98-296).  Returns true when the sample is complete (col_out valid), false when ps
 // holds the next ray segment.  With sph_tab >= 0 the winner sphere's attributes are one short LDS
@@ -137,8 +166,13 @@ __device__ __forceinline__ SceneHit pt_closest_sphere(const KParams& P, v3 o, v3
 // map on the context (plan_call).  ENV = 0 compiles to the code there was before maps existed, 1 to the lookup in the miss branch
 // alone; 2, for a map with sampling tables (PT_OPT_ENV_LIGHT), also draws from them in the NEE branch: the kernels that run NEE
 // with a map have that instantiation beside the other two, so that a map that is no light costs what it did.
-template <int ENV = 0>
-__device__ __forceinline__ bool path_shade_hit(const KParams& P, PathState& ps, const Hit& h, const SceneHit& sh, v3 tri_n, v3& col_out, int sph_tab = -1,
+// MIS (PT_FLAG_MIS, include/ptmi.h "Multiple importance sampling"): the balance heuristic between the shadow ray and the bounce ray of a
+// DIFF hit that is not the path's last — the shadow ray's contribution times w_l, and what the bounce ray finds of the lights that
+// were pickable (nee_mask) added with w_b where MIS = false drops it.  Every line of it stands under `if constexpr (MIS)`: the other
+// instantiations are the code they were.  The MIS ones exist for ENV 0 and 2; a map that is no light runs ENV 2, whose draw from the
+// tables asks for them here (the map's cx) where ENV 2 alone is only launched with them.
+template <int ENV = 0, bool MIS = false>
+__device__ __forceinline__ bool path_shade_hit(const KParams& P, PathStateOf<MIS>& ps, const Hit& h, const SceneHit& sh, v3 tri_n, v3& col_out, int sph_tab = -1,
                                                NeeReq* nee = nullptr) {
     if (nee) nee->want = false;
     PT_KARGS(K);   // shading scalars: read where they are used (see the sphere loop)
@@ -152,6 +186,7 @@ __device__ __forceinline__ bool path_shade_hit(const KParams& P, PathState& ps, 
     v3 n, nl, objcol, emit;
     int mat;
     float phong = K.phong;
+    [[maybe_unused]] float4 sph_cr = make_float4(0.f, 0.f, 0.f, 0.f);   // MIS: centre and radius of the sphere that was hit
     if (geom == 1) {
         pt_sphere_d s;
         if (sph_tab >= 0 && sph_id < PT_KSPHERES) {
@@ -168,6 +203,7 @@ __device__ __forceinline__ bool path_shade_hit(const KParams& P, PathState& ps, 
         objcol = V3(s.col[0], s.col[1], s.col[2]);
         emit = V3(s.emi[0], s.emi[1], s.emi[2]);
         mat = s.mat;
+        if constexpr (MIS) sph_cr = make_float4(s.px, s.py, s.pz, s.rad);
     } else if (geom == 0) {
         n = vnormalize(tri_n);
         nl = n;  // tracer.cu:126-127
@@ -189,14 +225,37 @@ __device__ __forceinline__ bool path_shade_hit(const KParams& P, PathState& ps, 
         // extension: the map instead of the constant, by the same rules; nothing where the DIFF hit before sampled the map as a light
         // (nee_mask bit 9): its shadow ray has gathered it
         if (ENV == 1 && PT_KENV(K).texels) col_out = pt_env_lookup(PT_KENV(K), d);
+        if constexpr (MIS) {
+            // the map was pickable at the DIFF hit before: its radiance with the bounce ray's weight, p_b' against the density the
+            // tables have along d
+            if (ENV == 2 && PT_KENV(K).texels) {
+                col_out = pt_env_lookup(PT_KENV(K), d);
+                if (ps.nee_mask & 0x200u) col_out = vscale(col_out, pt_mis_bounce_weight(ps.pb, pt_env_pdf(PT_KENV(K), d), pt_mis_lights(ps.nee_mask, K.n_tri_lights)));
+            }
+        } else {
         if (ENV == 2 && PT_KENV(K).texels) col_out = (ps.nee_mask & 0x200u) ? V3(0.f, 0.f, 0.f) : pt_env_lookup(PT_KENV(K), d);
+        }
         if (K.flags & PT_FLAG_MISS_KEEPS_PATH) col_out = vadd(accu, vmul(mask, col_out));  // extension
         return true;
     }
     // not already gathered by a shadow ray (PT_FLAG_NEE): bits 0-7 the spheres that were eligible, bit 8 the emissive triangles
     // (bit 9, the environment map as a light, is the miss branch's above)
+    if constexpr (MIS) {
+        // ... under PT_FLAG_MIS gathered with the bounce ray's weight instead: p_b' against the density with which the shadow ray at
+        // ps.o would have drawn d towards this light (the sphere's cone from there; the triangle's area seen from there)
+        float wb = 1.0f;
+        if (geom == 1 && sph_id < 8 && ((ps.nee_mask >> sph_id) & 1u)) {
+            const v3 w = vsub(V3(sph_cr.x, sph_cr.y, sph_cr.z), o);
+            const float cos_max = sqrtf(fmaxf(0.0f, 1.0f - (sph_cr.w * sph_cr.w) / vdot(w, w)));
+            wb = pt_mis_bounce_weight_inv(ps.pb, 6.28318548f * (1.0f - cos_max), pt_mis_lights(ps.nee_mask, K.n_tri_lights));
+        } else if (geom == 0 && (ps.nee_mask & 0x100u)) {
+            wb = pt_mis_bounce_weight_inv(ps.pb, fabsf(vdot(tri_n, d)) / (2.0f * (scene_t * scene_t)), pt_mis_lights(ps.nee_mask, K.n_tri_lights));
+        }
+        accu = vadd(accu, vscale(vmul(mask, emit), wb));
+    } else {
     if (!(geom == 1 && sph_id < 8 && ((ps.nee_mask >> sph_id) & 1u)) && !(geom == 0 && (ps.nee_mask & 0x100u)))
         accu = vadd(accu, vmul(mask, emit));
+    }
     ps.nee_mask = 0;
 
     if ((K.flags & PT_FLAG_RUSSIAN_ROULETTE) && ps.depth >= 2) {  // extension
@@ -253,6 +312,13 @@ __device__ __forceinline__ bool path_shade_hit(const KParams& P, PathState& ps, 
             // light lies beyond the call's depth and the call's expectation is the same with and without the tables
             bool env_light = false;
             if constexpr (ENV == 2) env_light = (K.flags & PT_FLAG_MISS_KEEPS_PATH) != 0 && ps.depth + 1 < P.depth;
+            if constexpr (ENV == 2 && MIS) env_light = env_light && PT_KENV(K).cx != nullptr;   // (this instantiation also serves a map without tables)
+            // PT_FLAG_MIS: the weights apply where a bounce ray follows; at the path's last hit the shadow ray keeps weight 1
+            [[maybe_unused]] bool mis = false;
+            if constexpr (MIS) {
+                mis = ps.depth + 1 < P.depth;
+                ps.pb = fmaxf(0.0f, vdot(nl, nextdir)) / 3.14159274f;
+            }
             const int n_tl = K.n_tri_lights, n_all = n_el + n_tl + (env_light ? 1 : 0);
             ps.nee_mask = el | (n_tl > 0 ? 0x100u : 0u) | (env_light ? 0x200u : 0u);
             if (n_all > 0) {
@@ -273,7 +339,8 @@ __device__ __forceinline__ bool path_shade_hit(const KParams& P, PathState& ps, 
                             if (ts != 0.0f && ts > 0.01f) blocked = true;
                         }
                         if (!blocked) {
-                            const float k = (cosl * (float)n_all) / (3.14159274f * s.w);
+                            float k = (cosl * (float)n_all) / (3.14159274f * s.w);
+                            if constexpr (MIS) { if (mis) k *= pt_mis_light_weight(cosl, (float)n_all / s.w); }
                             nee->want = true;
                             nee->o = hitpos;
                             nee->d = l;
@@ -305,7 +372,8 @@ __device__ __forceinline__ bool path_shade_hit(const KParams& P, PathState& ps, 
                         if (ts != 0.0f && ts < t_light && ts > 0.01f) blocked = true;
                     }
                     if (!blocked) {
-                        const float k = ((cosl * (0.5f * proj)) * (float)n_all) / (3.14159274f * d2);
+                        float k = ((cosl * (0.5f * proj)) * (float)n_all) / (3.14159274f * d2);
+                        if constexpr (MIS) { if (mis) k *= pt_mis_light_weight(cosl, (float)n_all * (proj / (2.0f * d2))); }
                         nee->want = true;
                         nee->o = hitpos;
                         nee->d = l;
@@ -345,7 +413,8 @@ __device__ __forceinline__ bool path_shade_hit(const KParams& P, PathState& ps, 
                     if (j != li && ts != 0.0f && ts < t_light && ts > 0.01f) blocked = true;
                 }
                 if (!blocked) {
-                    const float k = (cosl * (2.0f * (1.0f - cos_max))) * (float)n_all;
+                    float k = (cosl * (2.0f * (1.0f - cos_max))) * (float)n_all;
+                    if constexpr (MIS) { if (mis) k *= pt_mis_light_weight(cosl, (float)n_all * (6.28318548f * (1.0f - cos_max))); }
                     nee->want = true;
                     nee->o = hitpos;
                     nee->d = l;
@@ -451,13 +520,13 @@ __device__ __forceinline__ v3 path_last_emission(const KParams& P, const PathSta
 // spheres + shading in one go (the kernels that shade in the lane that walked).  ENV: the instantiation for a context with an
 // environment map (1; 2 when it is a light too); without one the kernels run the ENV = 0 instantiations, whose code is what it
 // was before maps existed
-template <int ENV>
-__device__ __forceinline__ bool path_shade(const KParams& P, PathState& ps, const Hit& h, v3& col_out, int sph_tab = -1, NeeReq* nee = nullptr) {
+template <int ENV, bool MIS = false>
+__device__ __forceinline__ bool path_shade(const KParams& P, PathStateOf<MIS>& ps, const Hit& h, v3& col_out, int sph_tab = -1, NeeReq* nee = nullptr) {
     // the triangle's normal is asked for NOW so that its latency hides behind the sphere tests
     v3 tri_n = V3(0.f, 0.f, 0.f);
     if (h.tri != -1) tri_n = pt_hit_normal(P.sc, h);
     const SceneHit sh = pt_closest_sphere(P, ps.o, ps.d, h, sph_tab);
-    return path_shade_hit<ENV>(P, ps, h, sh, tri_n, col_out, sph_tab, nee);
+    return path_shade_hit<ENV, MIS>(P, ps, h, sh, tri_n, col_out, sph_tab, nee);
 }
 
 // running mean with per-frame clamp, tracer.cu:386-391

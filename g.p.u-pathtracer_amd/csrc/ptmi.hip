@@ -323,6 +323,7 @@ static int check_call(pt_ctx* c, const float* accum_dev, const uint32_t* rgba_de
     if (p->tri_mat < PT_MAT_DIFF || p->tri_mat > PT_MAT_REFR) return fail(c, PT_ERR_INVALID, "pt_render: bad triangle material");
     if ((p->flags & PT_FLAG_WRITE_RGBA) && !rgba_dev) return fail(c, PT_ERR_INVALID, "pt_render: PT_FLAG_WRITE_RGBA needs rgba_dev");
     if ((p->flags & PT_FLAG_NEE) && !(p->flags & PT_FLAG_COSINE_DIFF)) return fail(c, PT_ERR_INVALID, "pt_render: PT_FLAG_NEE needs PT_FLAG_COSINE_DIFF (the reference's DIFF lobe has no density to weigh a light sample against)");
+    if ((p->flags & PT_FLAG_MIS) && !(p->flags & PT_FLAG_NEE)) return fail(c, PT_ERR_INVALID, "pt_render: PT_FLAG_MIS needs PT_FLAG_NEE (it weighs NEE's shadow rays against the bounce rays)");
     if (!c->tree.has_bvh && c->n_spheres == 0) return fail(c, PT_ERR_NO_SCENE, "pt_render: no scene uploaded");
     if (p->part_count > 1) {
         if (p->part_index < 0 || p->part_index >= p->part_count) return fail(c, PT_ERR_INVALID, "pt_render: part_index out of range");
@@ -467,6 +468,11 @@ static int plan_call(pt_ctx* c, const pt_params* p, const KParams& P, uint32_t s
     int kernel = c->opt_kernel;
     plan.probe = -1;
     plan.pick = nullptr;
+    // PT_FLAG_MIS: the megakernel whatever the option says, and no trial — the pipeline's path record has no word for the bounce's
+    // density, and the megakernel does not read Woop records
+    const bool mis = (p->flags & PT_FLAG_MIS) != 0;
+    if (mis && L.walk == 3) return fail(c, PT_ERR_UNSUPPORTED, "pt_render: PT_FLAG_MIS needs the exact (Moller-Trumbore) records (upload with PT_OPT_TRI_TEST 0)");
+    if (mis) kernel = PT_KERNEL_MEGA_BVH2;
     if (kernel == PT_KERNEL_AUTO) {
         kernel = PT_KERNEL_PERSISTENT;
         if (wave_ok && !c->opt_counters && !nee) {   // (an instrumented call is no trial; a call with shadow rays has no choice)
@@ -517,6 +523,7 @@ static int plan_call(pt_ctx* c, const pt_params* p, const KParams& P, uint32_t s
     L.n_cu = c->n_cu;
     L.moments = moments;
     L.env = c->env.k.texels ? (c->env.k.cx ? 2 : 1) : 0;
+    L.mis = mis;
     return PT_OK;
 }
 
@@ -713,11 +720,14 @@ int pt_render_rays(pt_ctx* c, const float* rays_dev, size_t n_rays, uint64_t fir
     if (p->sample_index == 0) return fail(c, PT_ERR_INVALID, "pt_render_rays: sample_index starts at 1");
     if (p->tri_mat < PT_MAT_DIFF || p->tri_mat > PT_MAT_REFR) return fail(c, PT_ERR_INVALID, "pt_render_rays: bad triangle material");
     if ((p->flags & PT_FLAG_NEE) && !(p->flags & PT_FLAG_COSINE_DIFF)) return fail(c, PT_ERR_INVALID, "pt_render_rays: PT_FLAG_NEE needs PT_FLAG_COSINE_DIFF");
+    if ((p->flags & PT_FLAG_MIS) && !(p->flags & PT_FLAG_NEE)) return fail(c, PT_ERR_INVALID, "pt_render_rays: PT_FLAG_MIS needs PT_FLAG_NEE");
     HIP_TRY(c, hipSetDevice(c->device));
     int rc = refresh_tri_lights(c, p);
     if (rc != PT_OK) return rc;
     const int walk = choose_walk(c, "pt_render_rays", false);   // (0 runs as 1: launch_render_rays has no while-while walk)
     if (walk < 0) return walk;
+    const bool mis = (p->flags & PT_FLAG_MIS) != 0;
+    if (mis && walk == 3) return fail(c, PT_ERR_UNSUPPORTED, "pt_render_rays: PT_FLAG_MIS needs the exact (Moller-Trumbore) records (upload with PT_OPT_TRI_TEST 0)");
     KParams P;
     fill_path_params(c, p, spp, P);
     P.sc.stack_n = 16;
@@ -739,7 +749,7 @@ int pt_render_rays(pt_ctx* c, const float* rays_dev, size_t n_rays, uint64_t fir
         P.chunk = queue_chunk(c, slots);
         const int work_blocks = (int)std::min<uint64_t>((slots + (uint64_t)P.chunk * 4 - 1) / ((uint64_t)P.chunk * 4), (uint64_t)INT_MAX);
         HIP_TRY(c, queue_reset(P.queue, c->stream));
-        HIP_TRY(c, launch_render_rays(c, walk, (p->flags & PT_FLAG_NEE) != 0, lds, work_blocks, P, R));
+        HIP_TRY(c, launch_render_rays(c, walk, (p->flags & PT_FLAG_NEE) != 0, mis, lds, work_blocks, P, R));
         if (per_launch > 1) HIP_TRY(c, launch_fold_rays(c, P, R));
     }
     HIP_TRY(c, span_end(c));

@@ -7,7 +7,7 @@
 // Usage: pt_app --mesh assets/cornell.ptmesh [--width 1280 --height 720 --frames 16 --spp 1
 //               --depth 4 --mat 0..3 --no-spheres --no-materials --bk r g b --device 0
 //               --out image.ppm|.png|.pfm  --checkpoint state.ckpt [--checkpoint-every N]
-//               --resume state.ckpt --device-build --fix-estimators --nee --gpus N --tile ROWS
+//               --resume state.ckpt --device-build --fix-estimators --nee --mis --gpus N --tile ROWS
 //               --denoise-out image.ppm|.png|.pfm  --variance-out file.pfm  --until-error E --max-frames M
 //               --pan-deg D --dolly S --temporal-out image.ppm|.png|.pfm  --equirect
 //               --env file.pfm [--env-scale S] [--env-nearest] [--env-light]]
@@ -61,6 +61,8 @@
 // --env-light also samples the map as a light (PT_OPT_ENV_LIGHT): every diffuse hit may send its shadow ray towards the map, drawn
 // in proportion to the texels' brightness — what a map with a small, bright sun needs to converge.  It turns --nee on (next-event
 // estimation with the cosine-weighted DIFF lobe, a miss keeping the path's light); a black map is lit by nothing and stays no light.
+// --mis weighs next-event estimation's shadow rays against the bounce rays (PT_FLAG_MIS, the balance heuristic): it turns --nee on,
+// and the megakernel renders.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -83,7 +85,7 @@ int main(int argc, char** argv) {
     double env_scale = 1.0;
     bool env_scale_set = false, env_nearest = false, env_light = false;
     int W = 1280, H = 720, frames = 16, depth = 4, mat = PT_MAT_DIFF, device = 0, spp = 1, ckpt_every = 0, gpus = 1, tile = 8;
-    bool spheres = true, use_materials = true, device_build = false, fix_estimators = false, nee = false, equirect = false;
+    bool spheres = true, use_materials = true, device_build = false, fix_estimators = false, nee = false, mis = false, equirect = false;
     float bk[3] = {1.f, 1.f, 1.f};
     double until_error = -1.0;   // < 0: off
     long max_frames = -1;
@@ -114,6 +116,7 @@ int main(int argc, char** argv) {
         else if (a == "--device-build") device_build = true;
         else if (a == "--fix-estimators") fix_estimators = true;
         else if (a == "--nee") nee = true;   // next-event estimation (implies the cosine-weighted DIFF lobe and keeps a path's light on a miss)
+        else if (a == "--mis") mis = true;   // ... with its shadow rays weighed against the bounce rays (implies --nee)
         else if (a == "--equirect") equirect = true;
         else if (a == "--env") env_path = next("--env");
         else if (a == "--env-scale") { env_scale = std::atof(next("--env-scale")); env_scale_set = true; }
@@ -152,6 +155,7 @@ int main(int argc, char** argv) {
     if (env_path.empty() && env_nearest) return die("--env-nearest", "goes with --env");
     if (env_path.empty() && env_light) return die("--env-light", "goes with --env");
     if (env_light) nee = true;   // the map is one of next-event estimation's lights
+    if (mis) nee = true;
     if (!env_path.empty()) {
         if (!std::isfinite(env_scale) || env_scale < 0.0) return die("--env-scale", "must be finite and not negative");
         if (pth_read_pfm(env_path.c_str(), &env_w, &env_h, &env_px) != 0) return die("--env", pth_last_error());
@@ -254,6 +258,7 @@ int main(int argc, char** argv) {
     p.flags = PT_FLAG_WRITE_RGBA;
     if (fix_estimators) p.flags |= PT_FLAG_FACE_FORWARD | PT_FLAG_COSINE_DIFF | PT_FLAG_GLASS_FIX | PT_FLAG_RUSSIAN_ROULETTE;
     if (nee) p.flags |= PT_FLAG_COSINE_DIFF | PT_FLAG_NEE | PT_FLAG_MISS_KEEPS_PATH;
+    if (mis) p.flags |= PT_FLAG_MIS;
     p.part_count = gpus; p.part_rows = tile;
 
     // every context owns full-frame buffers (accum/rgba are always addressed by the global pixel); it touches only
@@ -291,7 +296,7 @@ int main(int argc, char** argv) {
 
     // what a checkpoint must agree on to be continued: geometry size, image size, the scalar parameters
     uint64_t tag = pth_frame_hash((uint64_t)pth_mesh_n_tris(mesh) * 1315423911ull + (uint64_t)W * 65537u + (uint64_t)H);
-    tag = pth_frame_hash(tag ^ ((uint64_t)depth << 32 | (uint64_t)mat << 8 | (fix_estimators ? 4u : 0u) | (nee ? 8u : 0u) | (spheres ? 2u : 0u) | (has_materials ? 1u : 0u)));
+    tag = pth_frame_hash(tag ^ ((uint64_t)depth << 32 | (uint64_t)mat << 8 | (fix_estimators ? 4u : 0u) | (nee ? 8u : 0u) | (mis ? 16u : 0u) | (spheres ? 2u : 0u) | (has_materials ? 1u : 0u)));
 
     uint64_t frameNumber = 0, constantPdf = 0;   // constantPdf = samples folded so far
     std::vector<float> host_acc;

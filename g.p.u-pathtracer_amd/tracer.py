@@ -175,7 +175,10 @@ class PathTracer:
 
     def launch_kernel(self, accum_ptr, rgba_ptr, cam, params, spp=1, moments_ptr=None):
         """render(accum, bvh, camera, spp): asynchronous until sync().  moments_ptr: float[H][W][2] device memory that also
-        receives the running (m1, m2) of the samples' luminance (pt_render_moments)."""
+        receives the running (m1, m2) of the samples' luminance (pt_render_moments).  params.flags with FLAG_NEE (needs
+        FLAG_COSINE_DIFF): a shadow ray per diffuse hit towards one of the lights; with FLAG_MIS as well (needs FLAG_NEE) the shadow
+        ray and the bounce ray are weighed against each other by the balance heuristic — the megakernel renders such a call whatever
+        OPT_KERNEL says, and it is refused over Woop records."""
         if moments_ptr is None:
             self._check(self._lib.pt_render(self._ctx, accum_ptr, rgba_ptr, C.byref(cam), C.byref(params), spp))
         else:
@@ -206,7 +209,7 @@ class PathTracer:
     def render_rays(self, rays_ptr, n, out_ptr, params, spp=1, first_index=0, hdr=False):
         """Path-trace a caller's rays (pt_render_rays): rays float[n][8] = (o, ignored, d, ignored) with unit d; out float[n][3], the
         running mean of the radiance per ray, N = params.sample_index ..; ray i draws the random numbers of pixel first_index + i.
-        hdr: the mean is not clamped to 0..1.  Asynchronous until sync()."""
+        hdr: the mean is not clamped to 0..1.  FLAG_NEE and FLAG_MIS in params.flags as in launch_kernel.  Asynchronous until sync()."""
         self._check(self._lib.pt_render_rays(self._ctx, rays_ptr, int(n), int(first_index), out_ptr, C.byref(params), int(spp),
                                              _abi.RAYS_HDR if hdr else _abi.RAYS_CLAMPED))
 
@@ -217,7 +220,8 @@ class PathTracer:
         ENV_NEAREST.  Waits for renders in flight; a render issued afterwards sees the new map.  With a map the stage-split
         pipeline is not chosen.  light: the map also gets a sampling distribution (PT_OPT_ENV_LIGHT for this upload; the option is
         0 again afterwards) and is one of FLAG_NEE's lights in calls that have FLAG_MISS_KEEPS_PATH too — what a map with a small,
-        bright sun needs; environment_is_light() tells whether it took (an orthonormal basis, a map that is not black)."""
+        bright sun needs (FLAG_MIS weighs those shadow rays against the bounce rays, which sample the dim sky around it better);
+        environment_is_light() tells whether it took (an orthonormal basis, a map that is not black)."""
         a = np.ascontiguousarray(texels, np.float32)
         if a.ndim != 3 or a.shape[2] != 3:
             raise ValueError("upload_environment: a float32 array of shape (H, W, 3) expected")

@@ -94,7 +94,15 @@ enum {
                                         (a shadow-ray stage per bounce) or the megakernel.  An environment map uploaded
                                         under PT_OPT_ENV_LIGHT is one more light of the pick where the call also has
                                         PT_FLAG_MISS_KEEPS_PATH (the environment section states the rule)                    */
-    PT_FLAG_MISS_KEEPS_PATH = 1u << 6  /* a segment that hits nothing ends the path with
+    PT_FLAG_MIS = 1u << 9,             /* multiple importance sampling under PT_FLAG_NEE (needs it: PT_ERR_INVALID without): at a
+                                        DIFF hit that is not the path's last the shadow ray and the bounce ray are weighed
+                                        against each other by the balance heuristic, per light, instead of the bounce ray
+                                        dropping what the shadow ray could have picked.  Same draws, same expectation; less
+                                        noise where one of the two samples badly (a large emitter close by, a small sun in a
+                                        map).  "Multiple importance sampling" below states it.  Runs PT_KERNEL_MEGA_BVH2
+                                        whatever PT_OPT_KERNEL says (no PT_KERNEL_AUTO trial; its table is neither read nor
+                                        changed); PT_ERR_UNSUPPORTED over Woop records (PT_OPT_TRI_TEST 1)                   */
+    PT_FLAG_MISS_KEEPS_PATH = 1u << 6 /* a segment that hits nothing ends the path with
                                         accu + mask * bk_color (smallpt, and the reference's own CPU
                                         tracer: CpuRayTracer/src/scene.cpp:27 returns black for the
                                         MISSING TERM only) instead of the reference GPU kernel's bare
@@ -544,8 +552,9 @@ int pt_any_hits(pt_ctx* ctx, const float* rays_dev, size_t n_rays, int cull_back
  * (pt_upload_environment): there is no direction to look up; at depth 0 black like every other ray.
  * Errors, in this order: NULL ctx PT_ERR_INVALID; neither a tree nor spheres PT_ERR_NO_SCENE; n_rays == 0 or spp == 0 PT_OK,
  * nothing written; a NULL rays_dev, radiance_dev or params PT_ERR_INVALID; a mode other than the two PT_ERR_INVALID;
- * n_rays >= 2^32 PT_ERR_INVALID; then pt_render's own: sample_index == 0, a bad tri_mat, PT_FLAG_NEE without PT_FLAG_COSINE_DIFF
- * PT_ERR_INVALID; PT_FLAG_NEE over emissive triangles with Woop records PT_ERR_UNSUPPORTED.  Woop records (PT_OPT_TRI_TEST 1)
+ * n_rays >= 2^32 PT_ERR_INVALID; then pt_render's own: sample_index == 0, a bad tri_mat, PT_FLAG_NEE without PT_FLAG_COSINE_DIFF,
+ * then PT_FLAG_MIS without PT_FLAG_NEE,
+ * PT_ERR_INVALID; PT_FLAG_NEE over emissive triangles, or PT_FLAG_MIS, with Woop records PT_ERR_UNSUPPORTED.  Woop records (PT_OPT_TRI_TEST 1)
  * otherwise run, as in pt_render's persistent kernel: the wide walk with tolerance-class parity, PT_ERR_UNSUPPORTED when the tree is
  * too deep for that walk.
  * The kernel is the persistent kernel's loop — (sample, ray) slots drawn from a work queue by resident waves, the 4-wide walk, or
@@ -632,9 +641,36 @@ int pt_render_rays(pt_ctx* ctx, const float* rays_dev, size_t n_rays, uint64_t f
  * bounce ray of such a hit gathers nothing from the map when it leaves the scene (accu + mask * 0): the exclusive scheme the
  * spheres and emissive triangles use.  Camera rays, mirror / glass / metal bounces and calls without the three flags gather the
  * map as before; a context whose map is no light renders exactly what it rendered.
- * Left out: multiple importance sampling between the shadow ray and the bounce ray (pt_sample_environment and
- * pt_environment_pdf let a host do its own), mip or hierarchical warps, building the tables on the device, the stage-split
- * pipeline with a map, the map as a light without PT_FLAG_MISS_KEEPS_PATH (a miss then discards the gathered light). */
+ * Left out: mip or hierarchical warps, building the tables on the device, the stage-split
+ * pipeline with a map, the map as a light without PT_FLAG_MISS_KEEPS_PATH (a miss then discards the gathered light).
+ *
+ * Multiple importance sampling (PT_FLAG_MIS; pt_render, pt_render_moments, pt_render_rays).  binary32, plain * and
+ * +.  The draws of PT_FLAG_NEE are unchanged (u0 picks the light, u1 and u2 draw on it): a path consumes the same random numbers
+ * with and without the flag.  With pi = 3.14159274f, 2 pi = 6.28318548f:
+ * At a DIFF hit x that is not the path's last (hit number < depth) and has n_all > 0 pickable lights, the shadow ray's contribution
+ * is multiplied by w_l = q / (q + p_b), where p_b = cosl / pi is the cosine lobe's density of the drawn direction l and
+ * q = p_k(l) / n_all the density with which the shadow ray draws it, p_k per steradian:
+ *     sphere              1 / (2 pi (1 - cos_max)), cos_max as the cone draw computes it
+ *     emissive triangle   2 d2 / proj, d2 the squared distance to the drawn point, proj = abs(dot(cross(e1, e2), l))
+ *     environment map     the draw's pdf
+ * Both weights are computed through r = n_all / p_k = 1 / q — n_all * (2 pi * (1 - cos_max)), n_all * (proj / (2 * d2)),
+ * n_all / pdf — which stays finite where a light's solid angle rounds to 0:  w_l = 1 / (1 + p_b * r).
+ * The path carries nee_mask (which lights were pickable at x) and p_b' = max(0, dot(nl, d)) / pi, the lobe's density of the bounce
+ * direction d it takes, to its next vertex.  Where plain NEE drops the emission of what d hits, or the map's radiance when d leaves
+ * the scene, because the light was pickable, it is added with w_b = p_b' / (p_b' + q') instead: a = min(p_b' * r', FLT_MAX),
+ * w_b = a / (a + 1), r' = n_all / p_k(d) for the light that was hit, seen from the bounce ray's origin (the point the draws used),
+ * n_all rebuilt from nee_mask (the sphere bits, + the emissive triangles, + 1 for the map):
+ *     sphere i            the same cos_max arithmetic from the ray's origin: r' = n_all * (2 pi * (1 - cos_max))
+ *     any triangle        r' = n_all * (abs(dot(N, d)) / (2 * (t * t))), N the hit's un-normalised normal (|N| = 2 area), t the
+ *                         hit distance (a row that does not emit adds nothing whatever its weight)
+ *     the map, on a miss  r' = n_all / pdf(d), "the density of a given direction" above; w_b = 1 where pdf(d) is not > 0
+ * so that w_l + w_b = 1 for one direction seen from both sides.  Everything plain NEE gathers in full stays so: spheres the path
+ * is inside of, spheres past the first 8, triangles under the one global material, whatever a mirror, glass or metal bounce
+ * reaches (it clears nee_mask), camera rays.  At the path's last hit no bounce ray follows: the shadow ray keeps weight 1 and the map
+ * is no light there, as under plain NEE — a depth-1 call renders the same bits with and without the flag, and the expectation at
+ * every depth is plain NEE's.
+ * Left out: the stage-split pipeline (its path record has no word for p_b'), the power heuristic, one-sample MIS, MIS for the
+ * Phong lobe of PT_MAT_METAL (its bounce gathers in full). */
 enum { PT_ENV_NEAREST = 0, PT_ENV_BILINEAR = 1 };
 typedef struct pt_environment {
     int32_t width, height;               /* texels: 1..16384 each, width * height <= 2^26 */

@@ -13,10 +13,11 @@ and the share of the call's segments that hit nothing, from one instrumented cal
 --mode light: what sampling the map as a light (PT_OPT_ENV_LIGHT, upload_environment(light=True)) buys on the same scene and
 camera under next-event estimation (PT_FLAGS_SMALLPT | PT_FLAG_NEE; the megakernel renders): a 4096 x 2048 bilinear map, dim sky
 with a sun of a few texels (radiance 20 000, 3 x 3 texels, 45 degrees up behind the camera's right shoulder),
-  (e) the step time with the light off and on
+  (e) the step time with the light off, on, and on with PT_FLAG_MIS (the shadow rays weighed against the bounce rays)
   (f) pt_frame_error's mean relative standard error of the frame after equal TIME: --budget-ms of device time each, whole calls,
       with the frame's mean luminance and the number of pixels the sun has reached beside it: the error is estimated from the
-      samples, so a pixel whose bounce rays never found the sun reports a small error around the wrong mean
+      samples, so a pixel whose bounce rays never found the sun reports a small error around the wrong mean; and the firefly
+      pixels: those whose own relative standard error is still above 0.5
   (g) pt_sample_environment: 2 M draws, with and without the radiance
 --skip-light runs (e) and (f) with the light off only and nothing that needs the option: the same file run in a checkout of an
 earlier commit gives that commit's time for the same frame.
@@ -86,9 +87,10 @@ def light_mode():
     tex = sun_map(4096, 2048)
     mom = t.malloc(W * H * 8)
     say(f"--mode light: PT_FLAGS_SMALLPT | PT_FLAG_NEE, 4096 x 2048 bilinear map with a 3 x 3 texel sun; equal time = {a.budget_ms:.0f} ms of device time")
-    for light in ((False,) if a.skip_light else (False, True)):
+    for light, mis in (((False, False),) if a.skip_light else ((False, False), (True, False), (True, True))):
         t.upload_environment(tex, **({"light": True} if light else {}))
-        tag = "on " if light else "off"
+        p.flags = g.FLAGS_SMALLPT | g.FLAG_NEE | (g.FLAG_MIS if mis else 0)
+        tag = "on + PT_FLAG_MIS" if mis else "on " if light else "off"
         ms = timed(f"(e) light {tag}: step", lambda: t.launch_kernel(acc.ptr, rgba.ptr, cam, p, a.spp), "paths", W * H * a.spp)
         calls = max(1, int(a.budget_ms / ms))
         q = g.Params.from_buffer_copy(p)
@@ -97,10 +99,11 @@ def light_mode():
             q.frame, q.sample_index = k * a.spp, 1 + k * a.spp
             t.launch_kernel(acc.ptr, rgba.ptr, cam, q, a.spp, mom.ptr)
             spent += t.last_kernel_ms()
-        rse, _ = t.frame_error(mom.ptr, W, H, calls * a.spp)
+        rse, fireflies = t.frame_error(mom.ptr, W, H, calls * a.spp, 0.5)
         m1 = mom.download(np.float32, (H, W, 2))[..., 0].astype(np.float64)
         say(f"  (f) light {tag}: {calls} calls = {calls * a.spp} samples per pixel in {spent:.1f} ms: mean relative standard error {rse:.5f}, "
-            f"mean luminance of the frame {m1.mean():.4f}, pixels brighter than 0.3 (three times the brightest sky texel: the sun reached them) {int((m1 > 0.3).sum())}")
+            f"mean luminance of the frame {m1.mean():.4f}, pixels brighter than 0.3 (three times the brightest sky texel: the sun reached them) {int((m1 > 0.3).sum())}, "
+            f"firefly pixels (relative standard error above 0.5) {fireflies}")
     if not a.skip_light:
         n = a.eval_rays
         u = np.random.default_rng(7).random((n, 2), dtype=np.float32)
