@@ -13,6 +13,7 @@
 #include <cstring>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/ptmi.h"
@@ -96,6 +97,7 @@ struct EnvMap {
     ptmi::DevBuf<float4> d_texels;
     ptmi::DevBuf<float> d_tables;   // cx, cy, zs
     KEnv k = {};
+    int code() const { return env_code(k.texels != nullptr, k.cx != nullptr); }   // LaunchCfg::env
 };
 
 struct pt_ctx {
@@ -288,10 +290,6 @@ inline bool path_history_holds(const KParams& P) {
         if (P.ksph[i].mat == PT_MAT_REFR) return false;
     return true;
 }
-// PT_OPT_LAST_OCCLUDERS: whether the shade launch that bounds the last segments (SHADE_BOUND, or the fused packet launch at depth 2) also
-// tests its walkers against the tree's occluder list: the any-hit launch runs behind it (that launch's own rule: WavePlan::anyhit), the
-// launch classifies its survivors at all (root cull: the decided lanes join the walk-free class), and the tree has a list.
-inline bool last_occluders_hold(const TreeState& t, bool anyhit_launch, bool root_cull) { return anyhit_launch && root_cull && t.n_occ > 0; }
 // The scene as a kernel sees it: one item buffer for nodes and records, the wide tree's root and, where ksph (KParams::ksph) is
 // given, the spheres: a ray-batch query sees none.  Zeroes the rest; the stack and LDS layout is the caller's.
 inline void scene_view(const pt_ctx* c, KScene& sc, pt_sphere_d* ksph = nullptr) {
@@ -342,11 +340,17 @@ inline hipError_t span_end(pt_ctx* c) {
 template <int V> constexpr std::integral_constant<int, V> int_c{};
 template <class F>   // f(true_type) or f(false_type), by v
 auto with_bool(bool v, F&& f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
-template <int V0, int... Vs, class F>   // f(int_c<V>) for the listed V that equals v, the LAST listed one when none does
-auto with_int(int v, F&& f) {
-    if constexpr (sizeof...(Vs) == 0) return f(int_c<V0>);
-    else return v == V0 ? f(int_c<V0>) : with_int<Vs...>(v, f);
+// One kernel family's dispatch (pt_variants.h): f(integral_constant<uint32_t, V>) for the word V of N_BITS bits that equals v — instantiated
+// for the words with EXISTS(V) and no other — or hipErrorInvalidValue when v is none of them: no request runs another request's kernel.
+// (a binary search over the words [LO, LO + N) at compile time: v lies among them)
+template <bool (*EXISTS)(uint32_t), uint32_t LO, uint32_t N, class F>
+hipError_t with_variant_in(uint32_t v, F& f) {
+    if constexpr (N > 1) return v < LO + N / 2 ? with_variant_in<EXISTS, LO, N / 2>(v, f) : with_variant_in<EXISTS, LO + N / 2, N / 2>(v, f);
+    else if constexpr (EXISTS(LO)) return f(std::integral_constant<uint32_t, LO>{});
+    else return hipErrorInvalidValue;
 }
+template <bool (*EXISTS)(uint32_t), int N_BITS, class F>
+hipError_t with_variant(uint32_t v, F&& f) { return v < (1u << N_BITS) ? with_variant_in<EXISTS, 0u, (1u << N_BITS)>(v, f) : hipErrorInvalidValue; }
 
 // A grid of resident blocks for a kernel whose waves draw work from a queue: what the device holds at once (at most `max_per_cu` per
 // CU), never more than `work_cap`.  No grid-wide wait anywhere: an over-estimate only means a few late blocks find the queue empty.
@@ -372,9 +376,8 @@ struct LaunchCfg {
     int work_blocks;   // persistent grid cap: blocks that have work at all
     int n_cu;
     bool moments;      // the call keeps luminance moments (pt_render_moments): they are the separate fold launch's job
-    int env;           // 1: the context has an environment map: the instantiations whose miss looks it up (pt_env.h); 2: the map is a
-                       // light too (PT_OPT_ENV_LIGHT): the megakernel's instantiation whose NEE branch draws from it; 0: no map
-    bool mis;          // the call has PT_FLAG_MIS: the megakernel's instantiations that weigh shadow rays against bounce rays
+    int env;           // the context's environment map (env_code, pt_variants.h): ENV_NONE, ENV_LOOKUP, or ENV_LIGHT with PT_OPT_ENV_LIGHT's tables
+    bool nee, mis;     // the call has PT_FLAG_NEE; PT_FLAG_MIS: the instantiations that weigh shadow rays against bounce rays
 };
 hipError_t launch_mega(const LaunchCfg& L, const KParams& P, hipStream_t st);        // pt_k_mega.hip
 hipError_t launch_rays(const KScene& sc, size_t lds, const float4* rays, size_t n, int cull, float* t_out, int* tri_out,
@@ -414,7 +417,7 @@ struct RaysCall {
     size_t n;               // 0 < n < 2^32
     int hdr;                // mode == PT_RAYS_HDR
 };
-hipError_t launch_render_rays(const pt_ctx* c, int walk, bool nee, bool mis, size_t lds, int work_blocks, const KParams& P, const RaysCall& r);
+hipError_t launch_render_rays(const LaunchCfg& L, const KParams& P, const RaysCall& r, hipStream_t st);
 hipError_t launch_fold_rays(const pt_ctx* c, const KParams& P, const RaysCall& r);
 // PT_OPT_TIMING: marks the end of a stage of the running call on the context's stream (no-op when timing is off)
 int stage_mark(pt_ctx* c, int kind_of_work_since_last_mark);

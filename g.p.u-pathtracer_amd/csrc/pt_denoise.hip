@@ -51,7 +51,7 @@ __global__ void __launch_bounds__(PT_BLOCK_RAYS) k_render_aux(const KParams P, c
     TravCount tc;
     TravOverflow<PT_STACK_CAP> stk_ovf;
     TravStack<PT_STACK_CAP, PT_BLOCK_RAYS> stk(__builtin_amdgcn_readfirstlane(16 * P.sc.n_top + (tid & ~63)), stk_ovf);
-    const Hit h = trav_bvh2<false, true>(P.sc, o, d, P.cull != 0, stk, tc, s_top);
+    const Hit h = trav_bvh2<TW_TOP>(P.sc, o, d, P.cull != 0, stk, tc, s_top);
     const SceneHit sh = pt_closest_sphere(P, o, d, h);
     float4 alb = make_float4(0.f, 0.f, 0.f, 0.f), nrm = alb, pos = alb;
     int32_t id = -1;

@@ -8,8 +8,12 @@
 // ALG = 0 while-while walk (Aila-Laine), 1 unified-step walk, 2 wide (4-way quantised) walk,
 //       3 wide walk over Woop records
 // MIS = the shadow rays and bounce rays of PT_FLAG_NEE weighed against each other (PT_FLAG_MIS, path_shade_hit)
-template <bool COUNT, int OCC, int LSTK, int ALG, int ENV, bool MIS>
-__global__ void __launch_bounds__(PT_BLOCK, OCC) k_trace_mega_bvh2(const KParams P) {
+// V: the word of pt_variants.h (PV_*; mega_exists: what is instantiated)
+template <bool COUNT, uint32_t V>
+__global__ void __launch_bounds__(PT_BLOCK, pv_occ(V)) k_trace_mega_bvh2(const KParams P) {
+    static_assert(COUNT == pv_count(V), "COUNT repeats the word's bit");
+    constexpr int LSTK = pv_lstk(V), ALG = pv_alg(V), ENV = pv_env(V);
+    constexpr bool MIS = pv_mis(V);
     float4* s_top = s_dyn;
     lds_load_top<PT_BLOCK>(P.sc, s_top);
     const int tid = threadIdx.x;
@@ -72,7 +76,7 @@ __global__ void __launch_bounds__(PT_BLOCK_RAYS) k_trace_rays_bvh2(const KScene 
     TravCount tc;
     TravOverflow<PT_STACK_CAP> stk_ovf;
     TravStack<PT_STACK_CAP, PT_BLOCK_RAYS> stk(__builtin_amdgcn_readfirstlane(16 * sc.n_top + ((int)threadIdx.x & ~63)), stk_ovf);
-    const Hit h = trav_bvh2<false, true>(sc, V3(ro.x, ro.y, ro.z), V3(rd.x, rd.y, rd.z), cull != 0, stk, tc, s_top);
+    const Hit h = trav_bvh2<TW_TOP>(sc, V3(ro.x, ro.y, ro.z), V3(rd.x, rd.y, rd.z), cull != 0, stk, tc, s_top);
     t_out[i] = h.t;
     tri_out[i] = h.tri;
     if (n_out) {
@@ -83,27 +87,14 @@ __global__ void __launch_bounds__(PT_BLOCK_RAYS) k_trace_rays_bvh2(const KScene 
 
 namespace ptmi {
 
-// Instantiated register / stack budgets: (8 waves/SIMD, 16-entry LDS window), (4, 16), (4, all 72 in LDS);
-// other requests run the nearest one (they are speed knobs, never results).
+// Instantiated: mega_exists; the request's word: mega_word (pt_variants.h).
 hipError_t launch_mega(const LaunchCfg& L, const KParams& P, hipStream_t st) {
-    auto go = [&](auto count, auto occ, auto lstk) {
-        return with_int<2, 1, 0>(std::min(L.walk, 2), [&](auto alg) {
-            return with_int<2, 1, 0>(L.env, [&](auto env) {   // a map on the context: the instantiation that looks it up (1), and samples it under PT_FLAG_NEE (2)
-                // PT_FLAG_MIS: instantiated without a map (0) and with one that is a light (2), which also serves one that is none
-                return with_bool(L.mis, [&](auto mis) {
-                    constexpr int ENV = mis() && env() == 1 ? 2 : env();
-                    const auto kernel = k_trace_mega_bvh2<count(), occ(), lstk(), alg(), ENV, mis()>;
-                    const hipError_t e = allow_lds(kernel, L.lds);
-                    if (e != hipSuccess) return e;
-                    hipLaunchKernelGGL(kernel, dim3(L.blocks), dim3(PT_BLOCK), L.lds, st, P);
-                    return hipGetLastError();
-                });
-            });
-        });
-    };
-    return with_bool(L.count, [&](auto count) {
-        if (L.lstk >= PT_STACK_CAP) return go(count, int_c<4>, int_c<PT_STACK_CAP>);
-        return L.occ >= 5 ? go(count, int_c<8>, int_c<16>) : go(count, int_c<4>, int_c<16>);
+    return with_variant<mega_exists, PV_BITS>(mega_word(L.count, L.occ, L.lstk, L.walk, L.env, L.mis), [&](auto v) {
+        const auto kernel = k_trace_mega_bvh2<pv_count(v()), v()>;
+        const hipError_t e = allow_lds(kernel, L.lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel, dim3(L.blocks), dim3(PT_BLOCK), L.lds, st, P);
+        return hipGetLastError();
     });
 }
 

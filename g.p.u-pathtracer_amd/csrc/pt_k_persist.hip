@@ -18,8 +18,11 @@
 #define PT_CHUNK 64
 enum { PH_IDLE = 0, PH_TRAV = 1, PH_SHADE = 2 };
 
-template <bool COUNT, int OCC, int LSTK, int ALG, bool ENV>
-__global__ void __launch_bounds__(PT_BLOCK, OCC) k_trace_persist_bvh2(const KParams P) {
+// V: the word of pt_variants.h (PV_*; persist_exists: what is instantiated)
+template <bool COUNT, uint32_t V>
+__global__ void __launch_bounds__(PT_BLOCK, pv_occ(V)) k_trace_persist_bvh2(const KParams P) {
+    static_assert(COUNT == pv_count(V), "COUNT repeats the word's bit");
+    constexpr int LSTK = pv_lstk(V), ALG = pv_alg(V), ENV = pv_env(V);
     float4* s_top = s_dyn;
     if (P.sph_tab >= 0 && threadIdx.x < 11 * PT_KSPHERES) {  // sphere attributes + centres for the shading code (see path_shade)
         PT_KARGS(K);
@@ -130,10 +133,10 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_trace_persist_bvh2(const KPar
         {
             const int n_dead = queue_empty ? __popcll(__ballot(phase == PH_IDLE)) : 0;
             if (phase == PH_TRAV) {
-                const bool fin = (ALG == 4)   ? trav_run_wide_pend<COUNT, true>(ts, P.sc, ps.o, ps.d, cull, stk, tc, n_dead, P.batch, P.vote_node, P.vote_rec)
-                                 : (ALG >= 2) ? trav_run_wide<COUNT, true, ALG == 3>(ts, P.sc, ps.o, ps.d, cull, stk, tc, n_dead, P.batch)
-                                 : (ALG == 1) ? trav_run_unified<COUNT, true>(ts, P.sc, ps.o, ps.d, cull, stk, tc, n_dead, P.batch)
-                                              : trav_run<COUNT, true, true>(ts, P.sc, ps.o, ps.d, cull, stk, tc, n_dead, P.batch, s_top);
+                const bool fin = (ALG == 4)   ? trav_run_wide_pend<tw_count(COUNT) | TW_DYN>(ts, P.sc, ps.o, ps.d, cull, stk, tc, n_dead, P.batch, P.vote_node, P.vote_rec)
+                                 : (ALG >= 2) ? trav_run_wide<tw_count(COUNT) | TW_DYN | (ALG == ALG_WIDE_WOOP ? TW_WOOP : 0u)>(ts, P.sc, ps.o, ps.d, cull, stk, tc, n_dead, P.batch)
+                                 : (ALG == 1) ? trav_run_unified<tw_count(COUNT) | TW_DYN>(ts, P.sc, ps.o, ps.d, cull, stk, tc, n_dead, P.batch)
+                                              : trav_run<tw_count(COUNT) | TW_DYN | TW_TOP>(ts, P.sc, ps.o, ps.d, cull, stk, tc, n_dead, P.batch, s_top);
                 if (fin) phase = PH_SHADE;
             }
         }
@@ -247,23 +250,10 @@ __global__ void __launch_bounds__(256) k_fold_samples_grouped(const KParams P, f
 
 namespace ptmi {
 
-// Instantiated budgets (waves/SIMD, LDS stack window): the wide walks (2, 3 = Woop records, 4 = postponed
-// leaf) get (4,16) (6,16) (6,24) (8,16) (4,72); the two exact binary walks (parity variants) (8,16) and
-// (4,72).  Other requests run the nearest one: they are speed knobs, never results.
+// Instantiated: persist_exists; the request's word: persist_word (pt_variants.h).
 hipError_t launch_persist(const LaunchCfg& L, const KParams& P, hipStream_t st) {
-    return with_bool(L.count, [&](auto count) {
-        auto go = [&](auto occ, auto lstk, auto alg) {
-            return with_bool(L.env != 0, [&](auto env) {   // a map on the context: the instantiation that looks it up (this kernel runs no NEE: a light or not)
-                return launch_resident(k_trace_persist_bvh2<count(), occ(), lstk(), alg(), env()>, L.lds, INT_MAX, L.n_cu,
-                                       (size_t)std::max(1, L.work_blocks), st, P);
-            });
-        };
-        auto binary = [&](auto occ, auto lstk) { return L.walk == 1 ? go(occ, lstk, int_c<1>) : go(occ, lstk, int_c<0>); };
-        auto wide = [&](auto occ, auto lstk) { return with_int<4, 3, 2>(L.walk, [&](auto alg) { return go(occ, lstk, alg); }); };
-        if (L.walk <= 1) return L.lstk >= PT_STACK_CAP ? binary(int_c<4>, int_c<PT_STACK_CAP>) : binary(int_c<8>, int_c<16>);
-        if (L.lstk >= PT_STACK_CAP) return wide(int_c<4>, int_c<PT_STACK_CAP>);
-        if (L.lstk == 24) return wide(int_c<6>, int_c<24>);
-        return L.occ >= 8 ? wide(int_c<8>, int_c<16>) : L.occ >= 5 ? wide(int_c<6>, int_c<16>) : wide(int_c<4>, int_c<16>);
+    return with_variant<persist_exists, PV_BITS>(persist_word(L.count, L.occ, L.lstk, L.walk, L.env), [&](auto v) {
+        return launch_resident(k_trace_persist_bvh2<pv_count(v()), v()>, L.lds, INT_MAX, L.n_cu, (size_t)std::max(1, L.work_blocks), st, P);
     });
 }
 
@@ -271,9 +261,12 @@ hipError_t launch_fold(const KParams& P, float2* moments, hipStream_t st) {
     with_bool(moments != nullptr, [&](auto mom) {   // pt_render_moments: the instantiations that keep the luminance moments too
         if (P.smp_ps > 1u) {   // sample groups: spp is a multiple of 4
             const uint32_t q = P.spp / 4u;
-            if ((q & 3u) == 0u) hipLaunchKernelGGL((k_fold_samples_grouped<4, mom()>), dim3(P.n_tiles), dim3(256), 0, st, P, moments);
-            else if ((q & 1u) == 0u) hipLaunchKernelGGL((k_fold_samples_grouped<2, mom()>), dim3((P.n_tiles + 1) / 2), dim3(256), 0, st, P, moments);
-            else hipLaunchKernelGGL((k_fold_samples_grouped<1, mom()>), dim3((P.n_tiles + 3) / 4), dim3(256), 0, st, P, moments);
+            auto go = [&](auto lp) {   // lp lanes per pixel: 4 / lp tiles per block
+                hipLaunchKernelGGL((k_fold_samples_grouped<lp(), mom()>), dim3((P.n_tiles + 4 / lp() - 1) / (4 / lp())), dim3(256), 0, st, P, moments);
+            };
+            if ((q & 3u) == 0u) go(int_c<4>);
+            else if ((q & 1u) == 0u) go(int_c<2>);
+            else go(int_c<1>);
         } else hipLaunchKernelGGL(k_fold_samples<mom()>, dim3((P.n_tiles + 3) / 4), dim3(256), 0, st, P, moments);
     });
     return hipGetLastError();

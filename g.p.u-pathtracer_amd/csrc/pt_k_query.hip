@@ -70,8 +70,11 @@ __device__ __forceinline__ void query_widen_boxes(TravState& ts) {
 }
 
 // ANY: trav_run_wide<.., ANY> — the lane leaves at the first record it accepts, with h.t = 0.
-template <bool ANY, int OCC, int LSTK>
-__global__ void __launch_bounds__(PT_BLOCK, OCC) k_query_rays(const KQuery Q) {
+// V: the word of pt_variants.h (QV_*; query_exists: what is instantiated)
+template <uint32_t V>
+__global__ void __launch_bounds__(PT_BLOCK, budget_occ(qv_budget(V))) k_query_rays(const KQuery Q) {
+    constexpr bool ANY = qv_any(V);
+    constexpr int LSTK = budget_lstk(qv_budget(V));
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     TravOverflow<LSTK> stk_ovf;
@@ -147,7 +150,7 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_query_rays(const KQuery Q) {
         // ---- walk until `batch` lanes have finished (lanes that can get no more work do not count)
         const int n_dead = empty ? 64 - __popcll(busy) : 0;
         if (live) {
-            const bool fin = trav_run_wide<false, true, false, true, ANY>(ts, Q.sc, o, d, cull, stk, tc, n_dead, batch);
+            const bool fin = trav_run_wide<TW_DYN | TW_AHEAD | (ANY ? TW_ANY : 0u)>(ts, Q.sc, o, d, cull, stk, tc, n_dead, batch);
             if (fin) {
                 if (ANY) Q.hit_out[idx] = ts.h.t == 0.0f ? 1 : 0;
                 else query_write_closest(Q, (size_t)idx, ts.h);
@@ -170,7 +173,7 @@ __global__ void __launch_bounds__(PT_BLOCK_RAYS) k_query_rays_bvh2(const KQuery 
         TravCount tc;
         TravOverflow<PT_STACK_CAP> stk_ovf;
         TravStack<PT_STACK_CAP, PT_BLOCK_RAYS> stk(__builtin_amdgcn_readfirstlane(16 * Q.sc.n_top + ((int)threadIdx.x & ~63)), stk_ovf);
-        h = trav_bvh2<false, true>(Q.sc, V3(ro.x, ro.y, ro.z), V3(rd.x, rd.y, rd.z), Q.cull != 0, stk, tc, s_top);
+        h = trav_bvh2<TW_TOP>(Q.sc, V3(ro.x, ro.y, ro.z), V3(rd.x, rd.y, rd.z), Q.cull != 0, stk, tc, s_top);
         if (!(h.t < fminf(rd.w, PT_F32_MAX))) h = pt_no_hit();   // (a miss holds F32_MAX, never below the bound)
     }
     if (Q.hit_out) Q.hit_out[i] = h.tri != -1 ? 1 : 0;
@@ -201,12 +204,10 @@ hipError_t launch_query(pt_ctx* c, const QueryCall& q) {
     const hipError_t e = queue_reset(Q.queue, st);
     if (e != hipSuccess) return e;
     // the extend stage's two budgets: (8 waves per SIMD, 16 stack entries in LDS), or (6, 24) under PT_OPT_LDS_STACK 24
-    return with_bool(q.hit != nullptr, [&](auto any) {
-        return with_bool(c->opt_lstk == 24, [&](auto deep) {
-            constexpr int OCC = deep() ? 6 : 8, LSTK = deep() ? 24 : 16;
-            Q.sc.stack_n = LSTK;
-            return launch_resident(k_query_rays<any(), OCC, LSTK>, (size_t)LSTK * PT_BLOCK * 4, c->opt_wave_blocks, c->n_cu, (size_t)Q.n_regions, st, Q);
-        });
+    return with_variant<query_exists, QV_BITS>(query_word(q.hit != nullptr, c->opt_lstk == 24), [&](auto v) {
+        constexpr int LSTK = budget_lstk(qv_budget(v()));
+        Q.sc.stack_n = LSTK;
+        return launch_resident(k_query_rays<v()>, (size_t)LSTK * PT_BLOCK * 4, c->opt_wave_blocks, c->n_cu, (size_t)Q.n_regions, st, Q);
     });
 }
 

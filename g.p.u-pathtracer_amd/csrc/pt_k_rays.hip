@@ -40,8 +40,11 @@ __device__ __forceinline__ bool rays_finite(v3 a) {
 
 // NEE: the lane can walk the shadow ray path_shade asks for (PT_FLAG_NEE) before it goes on with the path
 // MIS: ... and path_shade weighs that ray against the bounce ray (PT_FLAG_MIS); only with NEE
-template <bool NEE, int OCC, int LSTK, int ALG, int ENV, bool MIS>
-__global__ void __launch_bounds__(PT_BLOCK, OCC) k_render_rays(const KParams P, const KRays R) {
+// V: the word of pt_variants.h (PV_*; rays_exists: what is instantiated)
+template <uint32_t V>
+__global__ void __launch_bounds__(PT_BLOCK, pv_occ(V)) k_render_rays(const KParams P, const KRays R) {
+    constexpr bool NEE = pv_nee(V), MIS = pv_mis(V);
+    constexpr int LSTK = pv_lstk(V), ALG = pv_alg(V), ENV = pv_env(V);
     // sphere attributes + centres for the shading code (see path_shade): the table of k_trace_persist_bvh2, filled from the device
     // array (the first PT_KSPHERES spheres there are the ones in the kernel arguments; rows past n_spheres are never read)
     if (P.sph_tab >= 0 && (int)threadIdx.x < 11 * min(P.sc.n_spheres, PT_KSPHERES)) {
@@ -144,8 +147,8 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_render_rays(const KParams P, 
             const int n_dead = queue_empty ? __popcll(__ballot(phase == RP_IDLE)) : 0;
             if (phase == RP_TRAV) {
                 const v3 wo = NEE && (sh & 1) ? sh_o : ps.o, wd = NEE && (sh & 1) ? sh_d : ps.d;
-                const bool fin = (ALG >= 2) ? trav_run_wide<false, true, ALG == 3>(ts, P.sc, wo, wd, cull, stk, tc, n_dead, P.batch)
-                                            : trav_run_unified<false, true>(ts, P.sc, wo, wd, cull, stk, tc, n_dead, P.batch);
+                const bool fin = (ALG >= 2) ? trav_run_wide<TW_DYN | (ALG == ALG_WIDE_WOOP ? TW_WOOP : 0u)>(ts, P.sc, wo, wd, cull, stk, tc, n_dead, P.batch)
+                                            : trav_run_unified<TW_DYN>(ts, P.sc, wo, wd, cull, stk, tc, n_dead, P.batch);
                 if (fin) phase = RP_SHADE;
             }
         }
@@ -226,26 +229,12 @@ namespace ptmi {
 
 static KRays rays_args(const RaysCall& r) { return KRays{(const float4*)r.rays, r.out, r.first_index, (uint32_t)r.n, r.hdr}; }
 
-// Instantiated: the wide walk (2; 3 = Woop records) and the unified binary walk (1: trees too deep for the wide one, PT_OPT_WALK 0 / 1),
-// each at 6 waves per SIMD without and at 4 with the shadow-ray state, 16 stack entries per lane in LDS; each of those without and
-// with the environment-map lookup (ENV 1), the NEE ones also with the draw from a map that is a light (ENV 2).  PT_FLAG_MIS (mis, only with
-// nee and never over Woop records: pt_render_rays has refused those): the NEE instantiations of walks 2 and 1 once more, without a map
-// and with ENV 2, which serves a map that is no light too.
-hipError_t launch_render_rays(const pt_ctx* c, int walk, bool nee, bool mis, size_t lds, int work_blocks, const KParams& P, const RaysCall& r) {
+// Instantiated: rays_exists; the request's word: rays_word (pt_variants.h).  A request without an instantiation (PT_FLAG_MIS without
+// PT_FLAG_NEE or over Woop records) is none that pt_render_rays lets through.
+hipError_t launch_render_rays(const LaunchCfg& L, const KParams& P, const RaysCall& r, hipStream_t st) {
     const KRays R = rays_args(r);
-    return with_bool(nee, [&](auto n) {
-        return with_int<3, 2, 1>(walk, [&](auto alg) {
-            constexpr int OCC = n() ? 4 : 6;
-            // a map on the context: the instantiation that looks it up (1); a map that is a light, in a call that runs NEE: the one that samples it (2)
-            return with_int<2, 1, 0>(c->env.k.texels ? (c->env.k.cx ? 2 : 1) : 0, [&](auto env) {
-                constexpr int ENV = (env() == 2 && !n()) ? 1 : env();
-                if constexpr (n() && alg() != 3) {
-                    if (mis) return launch_resident(k_render_rays<true, OCC, 16, alg(), ENV == 1 ? 2 : ENV, true>, lds, INT_MAX, c->n_cu, (size_t)std::max(1, work_blocks), c->stream, P, R);
-                }
-                if (mis) return hipErrorInvalidValue;   // no such instantiation, and no quiet fall-back: pt_render_rays has refused the call
-                return launch_resident(k_render_rays<n(), OCC, 16, alg(), ENV, false>, lds, INT_MAX, c->n_cu, (size_t)std::max(1, work_blocks), c->stream, P, R);
-            });
-        });
+    return with_variant<rays_exists, PV_BITS>(rays_word(L.walk, L.env, L.nee, L.mis), [&](auto v) {
+        return launch_resident(k_render_rays<v()>, L.lds, INT_MAX, L.n_cu, (size_t)std::max(1, L.work_blocks), st, P, R);
     });
 }
 

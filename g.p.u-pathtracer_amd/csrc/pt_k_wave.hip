@@ -115,8 +115,12 @@ __device__ __forceinline__ float wf_anyhit_start(float ts) {
 // of pt_kernels.h, left by the shade lane that made the ray), so the lane starts BEHIND that step: the far children on the stack, in
 // the order the step pushes them, and the nearest one — a node or a leaf — as its item.  Stack, item and h.t are the walk's own after
 // its first step, and everything after it is the same bit for bit.
-template <bool COUNT, int OCC, int LSTK, bool FIRST, bool ANY = false, bool ENTRY = false>
-__global__ void __launch_bounds__(PT_BLOCK, OCC) k_wf_extend(const KParams P) {
+// V: the word of pt_variants.h (WX_*; extend_exists: what is instantiated)
+template <bool COUNT, uint32_t V>
+__global__ void __launch_bounds__(PT_BLOCK, budget_occ(wx_budget(V))) k_wf_extend(const KParams P) {
+    static_assert(COUNT == wx_count(V), "COUNT repeats the word's bit");
+    constexpr int LSTK = budget_lstk(wx_budget(V));
+    constexpr bool FIRST = wx_first(V), ANY = wx_any(V), ENTRY = wx_entry(V);
     static_assert(!(FIRST && ENTRY), "bounce 0's rays come from the camera: nobody ran their root step");
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -227,7 +231,7 @@ __global__ void __launch_bounds__(PT_BLOCK, OCC) k_wf_extend(const KParams P) {
         // ---- walk until `batch` lanes have finished (lanes that can get no more work do not count)
         const int n_dead = empty ? 64 - __popcll(busy) : 0;
         if (live) {
-            const bool fin = trav_run_wide<COUNT, true, false, true, ANY>(ts, P.sc, o, d, cull, stk, tc, n_dead, batch);
+            const bool fin = trav_run_wide<tw_count(COUNT) | TW_DYN | TW_AHEAD | (ANY ? TW_ANY : 0u)>(ts, P.sc, o, d, cull, stk, tc, n_dead, batch);
             if (fin) {
                 if (ANY) { if (ts.h.t == 0.0f) pt_sst1((float*)(P.wf.hit + idx), 0.0f); }
                 else pt_sst2(P.wf.hit + idx, make_float2(ts.h.t, __int_as_float(ts.h.rec)));
@@ -275,7 +279,7 @@ __global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet(const KParams 
             o = ps.o;
             d = ps.d;
         }
-        const Hit h = trav_packet_wide<COUNT>(P.sc, o, d, P.cull != 0, in, tc);
+        const Hit h = trav_packet_wide<tw_count(COUNT)>(P.sc, o, d, P.cull != 0, in, tc);
         if (in) pt_sst2(P.wf.hit + slot, make_float2(h.t, __int_as_float(h.rec)));
         if (COUNT) { n_rays += in ? 1u : 0u; n_walked++; }
     }
@@ -467,8 +471,12 @@ __device__ __forceinline__ void wf_region_counts(const KParams& P, uint32_t regi
 // planes are not touched; the lane rebuilds mask and accu from it, and the sample colour is written by the lane the path ends in
 // OCCL (PT_OPT_LAST_OCCLUDERS, BOUND only): the walkers among the survivors are tested against the tree's occluder table first
 // (wf_survivor_slot); an instrumented launch books the rays it decided
-template <bool COUNT, bool NEE, bool FIRST, bool LAST = false, int FOLD = 0, bool BOUND = false, bool HIST = false, bool OCCL = false>
+// V: the word of pt_variants.h (WS_*; shade_exists: what is instantiated)
+template <bool COUNT, uint32_t V>
 __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
+    static_assert(COUNT == ws_count(V), "COUNT repeats the word's bit");
+    constexpr bool NEE = ws_nee(V), FIRST = ws_first(V), LAST = ws_last(V), BOUND = ws_bound(V), HIST = ws_hist(V), OCCL = ws_occl(V);
+    constexpr int FOLD = ws_fold(V);
     __shared__ int s_cnt[PT_BLOCK / 64];
     __shared__ int s_cnt2[PT_BLOCK / 64];
     __shared__ int s_cnt_free[PT_BLOCK / 64];
@@ -595,8 +603,12 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade(const KParams P) {
 // sphere, t = 0 when a triangle lies at or before it: a triangle emits nothing (the launch is only chosen when none can), a sphere
 // adds path_last_emission's 0 + mask * emission, neither is the background rule of wf_shade_segment.  No ray, no sphere tests.
 // HIST: as k_wf_shade's — the lane holds the path's accu, and every verdict stores the sample once: accu when a triangle is in the way.
-template <bool COUNT, int FOLD, bool HIST = false>
+// V: the word of pt_variants.h (WS_*; shade_last_any_exists: what is instantiated)
+template <bool COUNT, uint32_t V>
 __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade_last_any(const KParams P) {
+    static_assert(COUNT == ws_count(V), "COUNT repeats the word's bit");
+    constexpr bool HIST = ws_hist(V);
+    constexpr int FOLD = ws_fold(V);
     const uint32_t region = blockIdx.x;
     const int n_in = P.wf.cnt_in[region];
     if (n_in == 0) {
@@ -651,8 +663,10 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_shade_last_any(const KParams P)
 // BOUND: as k_wf_shade's (depth 2: bounce 0's survivors are the last segments).
 // HIST: as k_wf_shade's (a path that goes on leaves its first code and no sample colour).
 // OCCL: as k_wf_shade's.
-template <bool BOUND, bool HIST = false, bool OCCL = false>
+// V: the word of pt_variants.h (WS_*; fused_exists: what is instantiated)
+template <uint32_t V>
 __global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet_shade(const KParams P) {
+    constexpr bool BOUND = ws_bound(V), HIST = ws_hist(V), OCCL = ws_occl(V);
     __shared__ int s_cnt[PT_BLOCK / 64];
     __shared__ int s_cnt_free[PT_BLOCK / 64];
     wf_sphere_table<HIST>();
@@ -666,7 +680,7 @@ __global__ void __launch_bounds__(PT_BLOCK, 8) k_wf_extend_packet_shade(const KP
     ps.o = ps.d = V3(0.f, 0.f, 0.f);
     if (have) path_begin_hashed(P, px, py, (uint64_t)pix, P.wf.hashes[s_idx], ps);
     TravCount tc;
-    Hit h = trav_packet_wide<false>(P.sc, ps.o, ps.d, P.cull != 0, have, tc);   // (every lane of the wave: EXEC = all 64)
+    Hit h = trav_packet_wide<TW_NONE>(P.sc, ps.o, ps.d, P.cull != 0, have, tc);   // (every lane of the wave: EXEC = all 64)
     bool alive = false;
     uint32_t code = 0;
     if (have) {
@@ -797,79 +811,35 @@ static WaveBuffers wave_carve(char* base, const WaveLayout& w) {
     return b;
 }
 
-// What one call launches, decided once: which extend and which shade kernel every bounce runs.
-enum WaveExtend { EXT_CLOSEST, EXT_ANY, EXT_FIRST, EXT_PACKET, EXT_FUSED };   // k_wf_extend<.., FIRST, ANY>, .._packet, .._packet_shade
-enum WaveShade { SHADE_PLAIN, SHADE_BOUND, SHADE_LAST, SHADE_LAST_ANY, SHADE_NONE };   // k_wf_shade<..>, k_wf_shade_last_any, in EXT_FUSED
-struct WavePlan {
-    bool count, nee, deep_stack;   // instrumented kernels; PT_FLAG_NEE; the (6 waves, 24 entries) budget instead of (8, 16)
-    bool packet;       // bounce 0 as wave-wide packets (PT_OPT_FIRST_WALK 1): the tree fits the packet stack budget (PT_OPT_PACKET_STACK)
-    // PT_OPT_FUSE_STAGES 1, the product launch without PT_FLAG_NEE: bounce 0's shade runs in the packet walk's launch, and the last shade
-    // launch folds the samples (fold_lp lanes per pixel) when every region holds all samples of its pixels (groups of spp = 16, 8 or 4)
-    bool fuse_first;
-    int fold_lp;
-    // PT_OPT_LAST_ANYHIT: when no triangle can emit, a path's last segment reaches the picture only through the sphere or the background it
-    // ends on.  The shade launch of bounce depth - 2 leaves the nearest sphere of every survivor's new ray in its hit slot, the walk of bounce
-    // depth - 1 is an any-hit query bounded by it, the last shade launch reads the verdict.  Instrumented launches: with the value 2 only.
-    bool anyhit;
-    // PT_OPT_ROOT_CULL: the shade launches keep the survivors whose new ray the tree's root turns away out of the next extend launch's
-    // queue (wf_survivor_slot).  Instrumented launches: with the value 2 only.
-    bool root_cull;
-    // PT_OPT_ROOT_ENTRY: ... and leave the rest of that node step in the walkers' records as an entry code, from which the extend launches
-    // of bounces >= 1 start below the root (k_wf_extend<.., ENTRY>).  Only with root_cull, without PT_FLAG_NEE (its shadow records carry
-    // no code, and ray1.w's top bit is taken) and when spp fits the narrowed sample field; every other call keeps the plain record.
-    // Instrumented launches: with the value 2 only.
-    bool root_entry;
-    // PT_OPT_PATH_HISTORY: the records carry the objects the path has hit (the history word of pt_kernels.h) in place of its mask, a
-    // shade lane rebuilds mask and accu from it, and a path's sample colour is written once, by the lane it ends in (path_history_holds).
-    // Instrumented launches: with the value 2 only.
-    bool history;
-    // PT_OPT_LAST_OCCLUDERS: the launch that bounds the last segments (SHADE_BOUND, or EXT_FUSED at depth 2) tests its walkers against the
-    // tree's occluder table and keeps the decided ones out of the any-hit launch's queue (last_occluders_hold).  Instrumented launches:
-    // with the value 2 only.
-    bool occluders;
-    WaveExtend extend(uint32_t b, uint32_t depth) const {
-        if (b == 0) return fuse_first ? EXT_FUSED : packet ? EXT_PACKET : EXT_FIRST;
-        return anyhit && b + 1 == depth ? EXT_ANY : EXT_CLOSEST;
-    }
-    WaveShade shade(uint32_t b, uint32_t depth) const {
-        if (b == 0 && fuse_first) return SHADE_NONE;
-        if (anyhit && b + 1 >= depth) return SHADE_LAST_ANY;   // behind the any-hit walk: the verdict's emission only
-        if (anyhit && b + 2 == depth) return SHADE_BOUND;      // its survivors' rays are the last segments: their sphere bound
-        if (b != 0 && !nee && !count && b + 1 >= depth) return SHADE_LAST;   // the final bounce: emission only
-        return SHADE_PLAIN;
-    }
-};
+// What one call launches, decided once: WavePlan (pt_variants.h), from what the context, the call and the tree say
 static WavePlan wave_plan(const pt_ctx* c, const KParams& P, const LaunchCfg& L, bool nee) {
-    WavePlan p;
-    p.count = L.count; p.nee = nee; p.deep_stack = L.lstk == 24;
-    p.packet = c->opt_first_walk == 1 && wide_walk_fits(c->tree, c->opt_packet_stack);
-    const bool fuse = c->opt_fuse_stages != 0 && !nee && !L.count, tri_dark = P.tri_emi[0] == 0.f && P.tri_emi[1] == 0.f && P.tri_emi[2] == 0.f;
-    p.fuse_first = fuse && p.packet;
-    // ... and the call keeps no luminance moments (pt_render_moments): those are the separate fold launch's job
-    p.fold_lp = fuse && !L.moments && P.depth >= 2 && P.sgroup_log2 >= 2 && P.sgroup_log2 <= 4 && P.spp == (1u << P.sgroup_log2) ? (int)P.spp / 4 : 0;
-    p.anyhit = (L.count ? c->opt_last_anyhit == 2 : c->opt_last_anyhit >= 1) && P.depth >= 2 && !nee && !P.tri_matid && tri_dark &&
-               P.sc.n_spheres <= PT_KSPHERES && !c->tree.records_woop;
-    p.root_cull = L.count ? c->opt_root_cull == 2 : c->opt_root_cull >= 1;
-    p.history = (L.count ? c->opt_path_history == 2 : c->opt_path_history >= 1) && path_history_holds(P);
-    p.occluders = (L.count ? c->opt_last_occluders == 2 : c->opt_last_occluders >= 1) && last_occluders_hold(c->tree, p.anyhit, p.root_cull);
-    p.root_entry = p.root_cull && !nee && P.spp < PT_REC_MAX_SAMPLES_ENTRY && (L.count ? c->opt_root_entry == 2 : c->opt_root_entry >= 1);
-    return p;
+    WaveRequest r = {};
+    r.count = L.count; r.nee = nee; r.deep_stack = L.lstk == 24; r.moments = L.moments;
+    r.packet = c->opt_first_walk == 1 && wide_walk_fits(c->tree, c->opt_packet_stack);
+    const bool tri_dark = P.tri_emi[0] == 0.f && P.tri_emi[1] == 0.f && P.tri_emi[2] == 0.f;
+    r.anyhit_scene = !P.tri_matid && tri_dark && P.sc.n_spheres <= PT_KSPHERES && !c->tree.records_woop;
+    r.history_holds = path_history_holds(P);
+    r.tree_has_occluders = c->tree.n_occ > 0;
+    r.spp_fits_entry = P.spp < PT_REC_MAX_SAMPLES_ENTRY;
+    r.fuse_stages = c->opt_fuse_stages; r.last_anyhit = c->opt_last_anyhit; r.root_cull = c->opt_root_cull; r.root_entry = c->opt_root_entry;
+    r.path_history = c->opt_path_history; r.last_occluders = c->opt_last_occluders;
+    r.depth = P.depth; r.spp = P.spp; r.sgroup_log2 = P.sgroup_log2;
+    return wave_plan_of(r);
 }
 
 constexpr size_t WF_LDS_SHADE = (15 * PT_KSPHERES + 6) * 4;   // wf_sphere_table, with the triangle material's row
-// the extend stage's persistent grid (resident blocks, at most `blocks_per_cu` per CU) over the records of Q
+// one block per region of Q
+template <class K>
+static hipError_t launch_regions(K kernel, size_t n_blocks, size_t lds, const KParams& Q, hipStream_t s) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n_blocks), dim3(PT_BLOCK), lds, s, Q);
+    return hipGetLastError();
+}
+// the extend stage's persistent grid (resident blocks, at most `blocks_per_cu` per CU) over the records of Q.
+// Instantiated: extend_exists, fused_exists; the words: extend_word, fused_word (pt_variants.h).
 static hipError_t launch_extend(const WavePlan& p, WaveExtend kind, const KParams& Q, const LaunchCfg& L, int blocks_per_cu, hipStream_t s) {
-    auto plain = [&](auto kernel, size_t n_blk, size_t lds) {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)n_blk), dim3(PT_BLOCK), lds, s, Q);
-        return hipGetLastError();
-    };
     const size_t n_reg = (size_t)Q.wf.n_regions;
-    if (kind == EXT_FUSED)   // (BOUND at depth 2: bounce 0's survivors are the last segments)
-        return with_bool(p.history, [&](auto hist) {
-            if (p.anyhit && Q.depth == 2)
-                return with_bool(p.occluders, [&](auto occl) { return plain(k_wf_extend_packet_shade<true, hist(), occl()>, n_reg, WF_LDS_SHADE); });
-            return plain(k_wf_extend_packet_shade<false, hist()>, n_reg, WF_LDS_SHADE);
-        });
+    if (kind == EXT_FUSED)
+        return with_variant<fused_exists, WS_BITS>(fused_word(p, Q.depth), [&](auto v) { return launch_regions(k_wf_extend_packet_shade<v()>, n_reg, WF_LDS_SHADE, Q, s); });
     if (kind == EXT_PACKET) {   // one block per region (4 groups); instrumented: the resident grid, 8 blocks per CU
 #ifdef PT_PACKET_RESIDENT_GRID   // experiment (tools/build_variant.sh): the product launch on the resident grid too
         const bool resident = true;
@@ -877,48 +847,21 @@ static hipError_t launch_extend(const WavePlan& p, WaveExtend kind, const KParam
         const bool resident = p.count;
 #endif
         const size_t n_blk = resident ? std::min<size_t>(n_reg, (size_t)8 * L.n_cu) : n_reg;
-        return p.count ? plain(k_wf_extend_packet<true>, n_blk, 0) : plain(k_wf_extend_packet<false>, n_blk, 0);
+        return p.count ? launch_regions(k_wf_extend_packet<true>, n_blk, 0, Q, s) : launch_regions(k_wf_extend_packet<false>, n_blk, 0, Q, s);
     }
-    return with_bool(p.count, [&](auto count) {
-        return with_bool(p.deep_stack, [&](auto deep) {
-            constexpr int OCC = deep() ? 6 : 8, LSTK = deep() ? 24 : 16;
-            auto go = [&](auto first, auto any, auto entry) {
-                return launch_resident(k_wf_extend<count(), OCC, LSTK, first(), any(), entry()>, (size_t)LSTK * PT_BLOCK * 4, blocks_per_cu, L.n_cu,
-                                       (size_t)Q.wf.n_regions, s, Q);
-            };
-            if (kind == EXT_FIRST) return go(std::true_type{}, std::false_type{}, std::false_type{});
-            return with_bool(p.root_entry, [&](auto entry) {
-                if (kind == EXT_ANY) return go(std::false_type{}, std::true_type{}, entry);
-                return go(std::false_type{}, std::false_type{}, entry);
-            });
-        });
+    return with_variant<extend_exists, WX_BITS>(extend_word(p, kind), [&](auto v) {
+        return launch_resident(k_wf_extend<wx_count(v()), v()>, (size_t)budget_lstk(wx_budget(v())) * PT_BLOCK * 4, blocks_per_cu, L.n_cu, n_reg, s, Q);
     });
 }
 
-// the shade stage: one block per region of Q
+// the shade stage.  Instantiated: shade_exists, shade_last_any_exists; the word: shade_word (pt_variants.h).
 static hipError_t launch_shade(const WavePlan& p, WaveShade kind, bool first, const KParams& Q, hipStream_t s) {
-    auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)Q.wf.n_regions), dim3(PT_BLOCK), WF_LDS_SHADE, s, Q);
-        return hipGetLastError();
-    };
-    if (p.nee) return with_bool(p.count, [&](auto count) {   // (never SHADE_BOUND, SHADE_LAST or a fold; never a history)
-        return with_bool(first, [&](auto f) { return go(k_wf_shade<count(), true, f()>); });
-    });
-    return with_bool(p.history, [&](auto hist) {
-        if (p.count) {   // (never SHADE_LAST, never a fold)
-            if (kind == SHADE_LAST_ANY) return go(k_wf_shade_last_any<true, 0, hist()>);
-            return with_bool(first, [&](auto f) {
-                if (kind == SHADE_BOUND) return with_bool(p.occluders, [&](auto occl) { return go(k_wf_shade<true, false, f(), false, 0, true, hist(), occl()>); });
-                return go(k_wf_shade<true, false, f(), false, 0, false, hist()>);
-            });
-        }
-        if (kind == SHADE_LAST_ANY) return with_int<4, 2, 1, 0>(p.fold_lp, [&](auto lp) { return go(k_wf_shade_last_any<false, lp(), hist()>); });
-        if (kind == SHADE_LAST) return with_int<4, 2, 1, 0>(p.fold_lp, [&](auto lp) { return go(k_wf_shade<false, false, false, true, lp(), false, hist()>); });
-        return with_bool(first, [&](auto f) {
-            if (kind == SHADE_BOUND) return with_bool(p.occluders, [&](auto occl) { return go(k_wf_shade<false, false, f(), false, 0, true, hist(), occl()>); });
-            return go(k_wf_shade<false, false, f(), false, 0, false, hist()>);
+    const size_t n_reg = (size_t)Q.wf.n_regions;
+    if (kind == SHADE_LAST_ANY)
+        return with_variant<shade_last_any_exists, WS_BITS>(shade_word(p, kind, first), [&](auto v) {
+            return launch_regions(k_wf_shade_last_any<ws_count(v()), v()>, n_reg, WF_LDS_SHADE, Q, s);
         });
-    });
+    return with_variant<shade_exists, WS_BITS>(shade_word(p, kind, first), [&](auto v) { return launch_regions(k_wf_shade<ws_count(v()), v()>, n_reg, WF_LDS_SHADE, Q, s); });
 }
 
 int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles, bool& folded) {

@@ -8,6 +8,7 @@
 #pragma once
 #include "pt_math.h"
 #include "pt_env.h"
+#include "pt_variants.h"
 #include "../../include/ptmi.h"
 
 #define PT_BLOCK 256          // frame kernels: 4 waves; one wave = one 8x8 pixel tile
@@ -15,6 +16,7 @@
 #define PT_TILE 8
 #define PT_MAX_TOP 1024       // most nodes the LDS copy of the top of the tree may hold
 #define PT_STACK_CAP 72       // deepest traversal stack (tree depth <= 64, SplitBVHBuilder MaxDepth)
+static_assert(budget_lstk(BUDGET_4x72) == PT_STACK_CAP, "the budget with the whole stack in LDS");
 #define PT_SHARDS 8           // work-queue counters (one per XCD worth of blocks)
 #define PT_SHARD_STRIDE 32    // uints between counters: one 128-byte line each
 #define PT_REGION 256         // stage-split pipeline: path-record slots per region (= one block)
@@ -274,15 +276,15 @@ __device__ __forceinline__ v3 pt_get_sample(const KParams& P, int px, int py, ui
             if (ALG >= 2) {
                 TravState ts;
                 trav_begin(ts, ps.o, ps.d, stk, P.sc.wide_root);
-                trav_run_wide<COUNT, false, ALG == 3>(ts, P.sc, ps.o, ps.d, cull, stk, tc, 0, 0);
+                trav_run_wide<tw_count(COUNT) | (ALG == ALG_WIDE_WOOP ? TW_WOOP : 0u)>(ts, P.sc, ps.o, ps.d, cull, stk, tc, 0, 0);
                 h = ts.h;
             } else if (ALG == 1) {
                 TravState ts;
                 trav_begin(ts, ps.o, ps.d, stk);
-                trav_run_unified<COUNT, false, STK>(ts, P.sc, ps.o, ps.d, cull, stk, tc, 0, 0);
+                trav_run_unified<tw_count(COUNT)>(ts, P.sc, ps.o, ps.d, cull, stk, tc, 0, 0);
                 h = ts.h;
             } else {
-                h = trav_bvh2<COUNT, true, STK>(P.sc, ps.o, ps.d, cull, stk, tc, s_top);
+                h = trav_bvh2<tw_count(COUNT) | TW_TOP>(P.sc, ps.o, ps.d, cull, stk, tc, s_top);
             }
         }
         if (COUNT) { n_rays++; n_hits += (h.tri != -1); }
@@ -299,13 +301,13 @@ __device__ __forceinline__ v3 pt_get_sample(const KParams& P, int px, int py, ui
                 TravState ts;
                 if (ALG >= 2) {
                     trav_begin(ts, req.o, req.d, stk, P.sc.wide_root);
-                    trav_run_wide<COUNT, false, ALG == 3>(ts, P.sc, req.o, req.d, cull, stk, tc, 0, 0);
+                    trav_run_wide<tw_count(COUNT) | (ALG == ALG_WIDE_WOOP ? TW_WOOP : 0u)>(ts, P.sc, req.o, req.d, cull, stk, tc, 0, 0);
                 } else if (ALG == 1) {
                     trav_begin(ts, req.o, req.d, stk);
-                    trav_run_unified<COUNT, false, STK>(ts, P.sc, req.o, req.d, cull, stk, tc, 0, 0);
+                    trav_run_unified<tw_count(COUNT)>(ts, P.sc, req.o, req.d, cull, stk, tc, 0, 0);
                 } else {
                     trav_begin(ts, req.o, req.d, stk);
-                    trav_run<COUNT, false, true, STK>(ts, P.sc, req.o, req.d, cull, stk, tc, 0, 0, s_top);
+                    trav_run<tw_count(COUNT) | TW_TOP>(ts, P.sc, req.o, req.d, cull, stk, tc, 0, 0, s_top);
                 }
                 h2 = ts.h;
             }

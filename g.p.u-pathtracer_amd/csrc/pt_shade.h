@@ -162,16 +162,16 @@ __device__ __forceinline__ float pt_mis_bounce_weight(float pb, float pk, float 
 // caller fetches it early so that the latency hides behind other work).
 // ENV: a segment that hits nothing looks the context's environment map up along its direction when one is set
 // (pt_upload_environment, pt_env.h) — the ENV instantiations of the kernels that shade in the lane that walked (path_shade), which
-// the launchers pick when the context has a map.  The stage-split pipeline's shade stage keeps ENV = false: it never runs with a
-// map on the context (plan_call).  ENV = 0 compiles to the code there was before maps existed, 1 to the lookup in the miss branch
-// alone; 2, for a map with sampling tables (PT_OPT_ENV_LIGHT), also draws from them in the NEE branch: the kernels that run NEE
+// the launchers pick when the context has a map (shade_env, pt_variants.h).  The stage-split pipeline's shade stage keeps ENV_NONE: it never
+// runs with a map on the context (plan_call).  ENV_NONE compiles to the code there was before maps existed, ENV_LOOKUP to the lookup in the
+// miss branch alone; ENV_LIGHT, for a map with sampling tables (PT_OPT_ENV_LIGHT), also draws from them in the NEE branch: the kernels that run NEE
 // with a map have that instantiation beside the other two, so that a map that is no light costs what it did.
 // MIS (PT_FLAG_MIS, include/ptmi.h "Multiple importance sampling"): the balance heuristic between the shadow ray and the bounce ray of a
 // DIFF hit that is not the path's last — the shadow ray's contribution times w_l, and what the bounce ray finds of the lights that
 // were pickable (nee_mask) added with w_b where MIS = false drops it.  Every line of it stands under `if constexpr (MIS)`: the other
 // instantiations are the code they were.  The MIS ones exist for ENV 0 and 2; a map that is no light runs ENV 2, whose draw from the
 // tables asks for them here (the map's cx) where ENV 2 alone is only launched with them.
-template <int ENV = 0, bool MIS = false>
+template <int ENV = ENV_NONE, bool MIS = false>
 __device__ __forceinline__ bool path_shade_hit(const KParams& P, PathStateOf<MIS>& ps, const Hit& h, const SceneHit& sh, v3 tri_n, v3& col_out, int sph_tab = -1,
                                                NeeReq* nee = nullptr) {
     if (nee) nee->want = false;
@@ -224,16 +224,16 @@ __device__ __forceinline__ bool path_shade_hit(const KParams& P, PathStateOf<MIS
         col_out = V3(K.bk[0], K.bk[1], K.bk[2]);  // tracer.cu:140-142: unmasked background
         // extension: the map instead of the constant, by the same rules; nothing where the DIFF hit before sampled the map as a light
         // (nee_mask bit 9): its shadow ray has gathered it
-        if (ENV == 1 && PT_KENV(K).texels) col_out = pt_env_lookup(PT_KENV(K), d);
+        if (ENV == ENV_LOOKUP && PT_KENV(K).texels) col_out = pt_env_lookup(PT_KENV(K), d);
         if constexpr (MIS) {
             // the map was pickable at the DIFF hit before: its radiance with the bounce ray's weight, p_b' against the density the
             // tables have along d
-            if (ENV == 2 && PT_KENV(K).texels) {
+            if (ENV == ENV_LIGHT && PT_KENV(K).texels) {
                 col_out = pt_env_lookup(PT_KENV(K), d);
                 if (ps.nee_mask & 0x200u) col_out = vscale(col_out, pt_mis_bounce_weight(ps.pb, pt_env_pdf(PT_KENV(K), d), pt_mis_lights(ps.nee_mask, K.n_tri_lights)));
             }
         } else {
-        if (ENV == 2 && PT_KENV(K).texels) col_out = (ps.nee_mask & 0x200u) ? V3(0.f, 0.f, 0.f) : pt_env_lookup(PT_KENV(K), d);
+        if (ENV == ENV_LIGHT && PT_KENV(K).texels) col_out = (ps.nee_mask & 0x200u) ? V3(0.f, 0.f, 0.f) : pt_env_lookup(PT_KENV(K), d);
         }
         if (K.flags & PT_FLAG_MISS_KEEPS_PATH) col_out = vadd(accu, vmul(mask, col_out));  // extension
         return true;
@@ -311,8 +311,8 @@ __device__ __forceinline__ bool path_shade_hit(const KParams& P, PathStateOf<MIS
             // and not at the path's last hit: the bounce ray that would have gathered the map from there is never traced, so that
             // light lies beyond the call's depth and the call's expectation is the same with and without the tables
             bool env_light = false;
-            if constexpr (ENV == 2) env_light = (K.flags & PT_FLAG_MISS_KEEPS_PATH) != 0 && ps.depth + 1 < P.depth;
-            if constexpr (ENV == 2 && MIS) env_light = env_light && PT_KENV(K).cx != nullptr;   // (this instantiation also serves a map without tables)
+            if constexpr (ENV == ENV_LIGHT) env_light = (K.flags & PT_FLAG_MISS_KEEPS_PATH) != 0 && ps.depth + 1 < P.depth;
+            if constexpr (ENV == ENV_LIGHT && MIS) env_light = env_light && PT_KENV(K).cx != nullptr;   // (this instantiation also serves a map without tables)
             // PT_FLAG_MIS: the weights apply where a bounce ray follows; at the path's last hit the shadow ray keeps weight 1
             [[maybe_unused]] bool mis = false;
             if constexpr (MIS) {
@@ -326,7 +326,7 @@ __device__ __forceinline__ bool path_shade_hit(const KParams& P, PathStateOf<MIS
                 int pick = (int)(u0 * (float)n_all);
                 if (pick > n_all - 1) pick = n_all - 1;
                 if (env_light && pick == n_all - 1) {
-                    if constexpr (ENV == 2) {
+                    if constexpr (ENV == ENV_LIGHT) {
                         // the map: a direction drawn from its tables (u1 the row, u2 the column), any sphere in the way blocks it
                         // as it would end the bounce ray; contribution = mask * L * cos(surface) * lights / (pi * pdf)
                         const float4 s = pt_env_draw(PT_KENV(K), u1, u2);

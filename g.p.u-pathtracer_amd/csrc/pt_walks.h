@@ -127,10 +127,11 @@ __device__ __forceinline__ void trav_begin(TravState& s, v3 o, v3 d, STK& stk, i
 }
 
 // returns true when the walk is complete
-template <bool COUNT, bool DYN, bool TOP, class STK>
+template <uint32_t W, class STK>   // W: TW_COUNT, TW_DYN, TW_TOP (pt_variants.h)
 __device__ __forceinline__ bool trav_run(TravState& s, const KScene& sc, v3 o, v3 d, bool cull,
                                          STK& stk, TravCount& tc, int n_dead, int batch,
                                          const float4* __restrict__ s_top) {
+    constexpr bool COUNT = (W & TW_COUNT) != 0, DYN = (W & TW_DYN) != 0, TOP = (W & TW_TOP) != 0;
     int node = s.node, leaf = s.leaf, sp = s.sp;
     Hit h = s.h;
     const float idx = s.idx, idy = s.idy, idz = s.idz, oodx = s.oodx, oody = s.oody, oodz = s.oodz;
@@ -231,9 +232,10 @@ __device__ __forceinline__ bool trav_run(TravState& s, const KScene& sc, v3 o, v
 // boxes/triangles a ray tests can differ slightly from the while-while order (a leaf is
 // tested as soon as it is popped, so later nodes see the shorter ray), the closest hit
 // (t, id, normal) cannot: ties go to the smaller id, so the result is order-independent.
-template <bool COUNT, bool DYN, class STK>
+template <uint32_t W, class STK>   // W: TW_COUNT, TW_DYN
 __device__ __forceinline__ bool trav_run_unified(TravState& s, const KScene& sc, v3 o, v3 d, bool cull, STK& stk,
                                                  TravCount& tc, int n_dead, int batch) {
+    constexpr bool COUNT = (W & TW_COUNT) != 0, DYN = (W & TW_DYN) != 0;
     int cur = s.node, sp = s.sp;
     Hit h = s.h;
     const float idx = s.idx, idy = s.idy, idz = s.idz, oodx = s.oodx, oody = s.oody, oodz = s.oodz;
@@ -399,9 +401,10 @@ __device__ __forceinline__ void wide_node_keys(const WideNode& w, float idx, flo
 // ANY (exact records only): an any-hit query — is there a record with 0 < t < s.h.t, the bound the caller starts the lane with?
 // The lane leaves at the first such record (no further record of the leaf, nothing popped) with s.h.t = 0; a lane that found
 // none keeps its bound.  h.tri / h.rec are not written.
-template <bool COUNT, bool DYN, bool WOOP, bool AHEAD = false, bool ANY = false, class STK>
+template <uint32_t W, class STK>   // W: TW_COUNT, TW_DYN, TW_WOOP, TW_AHEAD, TW_ANY
 __device__ __forceinline__ bool trav_run_wide(TravState& s, const KScene& sc, v3 o, v3 d, bool cull, STK& stk,
                                               TravCount& tc, int n_dead, int batch) {
+    constexpr bool COUNT = (W & TW_COUNT) != 0, DYN = (W & TW_DYN) != 0, WOOP = (W & TW_WOOP) != 0, AHEAD = (W & TW_AHEAD) != 0, ANY = (W & TW_ANY) != 0;
     int cur = s.node, sp = s.sp;
     Hit h = s.h;
     const float idx = s.idx, idy = s.idy, idz = s.idz, oodx = s.oodx, oody = s.oody, oodz = s.oodz;
@@ -566,9 +569,10 @@ __device__ __forceinline__ bool trav_run_wide(TravState& s, const KScene& sc, v3
 // reaches a second one.  The closest hit is order independent (every pruning test uses a valid
 // upper bound h.t, equal-t ties go to the smaller id), so the result is bit-identical to the
 // other walks; parking a leaf only delays the tightening of h.t by a few node steps.
-template <bool COUNT, bool DYN, class STK>
+template <uint32_t W, class STK>   // W: TW_COUNT, TW_DYN
 __device__ __forceinline__ bool trav_run_wide_pend(TravState& s, const KScene& sc, v3 o, v3 d, bool cull, STK& stk,
                                                    TravCount& tc, int n_dead, int batch, int vote_node, int vote_rec) {
+    constexpr bool COUNT = (W & TW_COUNT) != 0, DYN = (W & TW_DYN) != 0;
     int cur = s.node, sp = s.sp, pend = s.leaf;  // pend: ~address of the next record of the parked leaf, 0 = none
     Hit h = s.h;
     const float idx = s.idx, idy = s.idy, idz = s.idz, oodx = s.oodx, oody = s.oody, oodz = s.oodz;
@@ -677,8 +681,9 @@ __device__ __forceinline__ uint64_t pt_pick4(uint32_t k, uint64_t a, uint64_t b,
 }
 
 // the closest hit of every lane with `in` set; the whole wave must call it with every lane active (EXEC = all 64)
-template <bool COUNT>
+template <uint32_t W>   // W: TW_COUNT
 __device__ __forceinline__ Hit trav_packet_wide(const KScene& sc, v3 o, v3 d, bool cull, bool in, TravCount& tc) {
+    constexpr bool COUNT = (W & TW_COUNT) != 0;
     __shared__ int4 s_pkt[PT_BLOCK / 64][PT_PACKET_STACK_MAX];
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = (int)(threadIdx.x & 63);
@@ -757,12 +762,12 @@ __device__ __forceinline__ Hit trav_packet_wide(const KScene& sc, v3 o, v3 d, bo
     return h;
 }
 
-template <bool COUNT, bool TOP, class STK>
+template <uint32_t W, class STK>   // W: TW_COUNT, TW_TOP
 __device__ __forceinline__ Hit trav_bvh2(const KScene& sc, v3 o, v3 d, bool cull, STK& stk,
                                          TravCount& tc, const float4* __restrict__ s_top) {
     TravState s;
     trav_begin(s, o, d, stk);
-    trav_run<COUNT, false, TOP, STK>(s, sc, o, d, cull, stk, tc, 0, 0, s_top);
+    trav_run<W & (TW_COUNT | TW_TOP)>(s, sc, o, d, cull, stk, tc, 0, 0, s_top);
     return s.h;
 }
 

@@ -482,12 +482,8 @@ static int plan_call(pt_ctx* c, const pt_params* p, const KParams& P, uint32_t s
             else if (plan.pick->phase == pt_ctx::AutoPick::DECIDED) kernel = plan.pick->choice;
         }
     }
-    // shadow rays: the pipeline has a stage for them (the pixel rides below nee_mask in ray1.z, so it must fit), the megakernel a loop;
-    // the persistent kernel has neither (its lanes have no room for a second ray)
-    if (nee && kernel != PT_KERNEL_MEGA_BVH2)
-        kernel = wave_ok && (uint64_t)p->width * (uint64_t)p->height <= (1ull << PT_REC_PIXEL_BITS) ? PT_KERNEL_WAVEFRONT : PT_KERNEL_MEGA_BVH2;
-    if (kernel == PT_KERNEL_WAVEFRONT && !wave_ok) kernel = PT_KERNEL_PERSISTENT;   // same images
-    if (kernel == PT_KERNEL_MEGA_BVH2 && L.walk == 3) kernel = PT_KERNEL_PERSISTENT;   // Woop records: persistent kernel only
+    // shadow rays, what a family cannot run: path_kernel (pt_variants.h; the persistent kernel's lanes have no room for a second ray)
+    kernel = path_kernel(kernel, L.walk, wave_ok, nee, (uint64_t)p->width * (uint64_t)p->height <= (1ull << PT_REC_PIXEL_BITS));
     plan.kernel = kernel;
     const bool persistent = kernel == PT_KERNEL_PERSISTENT, wavefront = kernel == PT_KERNEL_WAVEFRONT;
 
@@ -522,7 +518,8 @@ static int plan_call(pt_ctx* c, const pt_params* p, const KParams& P, uint32_t s
     L.work_blocks = (int)((slots + plan.chunk * waves_per_block - 1) / (plan.chunk * waves_per_block));
     L.n_cu = c->n_cu;
     L.moments = moments;
-    L.env = c->env.k.texels ? (c->env.k.cx ? 2 : 1) : 0;
+    L.env = c->env.code();
+    L.nee = nee;
     L.mis = mis;
     return PT_OK;
 }
@@ -730,10 +727,16 @@ int pt_render_rays(pt_ctx* c, const float* rays_dev, size_t n_rays, uint64_t fir
     if (mis && walk == 3) return fail(c, PT_ERR_UNSUPPORTED, "pt_render_rays: PT_FLAG_MIS needs the exact (Moller-Trumbore) records (upload with PT_OPT_TRI_TEST 0)");
     KParams P;
     fill_path_params(c, p, spp, P);
-    P.sc.stack_n = 16;
+    ptmi::LaunchCfg L = {};   // (no instrumented kernel; the register budget is rays_word's: by PT_FLAG_NEE)
+    L.walk = walk;
+    L.lstk = P.sc.stack_n = 16;
     P.sc.top_base = walk >= 2 ? P.sc.wide_root : 0;
-    size_t lds = (size_t)16 * PT_BLOCK * 4;
-    P.sph_tab = c->opt_sph_lds ? lds_sphere_table(lds) : -1;
+    L.lds = (size_t)L.lstk * PT_BLOCK * 4;
+    P.sph_tab = c->opt_sph_lds ? lds_sphere_table(L.lds) : -1;
+    L.n_cu = c->n_cu;
+    L.env = c->env.code();
+    L.nee = (p->flags & PT_FLAG_NEE) != 0;
+    L.mis = mis;
     queue_params(c, c->d_queue.get(), P);   // the context's counters: every use is on the caller's stream, behind a reset of its own
     const ptmi::RaysCall R{rays_dev, radiance_dev, first_index, n_rays, mode == PT_RAYS_HDR};
     const uint32_t per_launch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(spp, RAYS_MAX_SLOTS / n_rays));
@@ -747,9 +750,9 @@ int pt_render_rays(pt_ctx* c, const float* rays_dev, size_t n_rays, uint64_t fir
         P.sample_index = p->sample_index + s0;
         const uint64_t slots = (uint64_t)n_rays * (per_launch > 1 ? P.spp : 1u);
         P.chunk = queue_chunk(c, slots);
-        const int work_blocks = (int)std::min<uint64_t>((slots + (uint64_t)P.chunk * 4 - 1) / ((uint64_t)P.chunk * 4), (uint64_t)INT_MAX);
+        L.work_blocks = (int)std::min<uint64_t>((slots + (uint64_t)P.chunk * 4 - 1) / ((uint64_t)P.chunk * 4), (uint64_t)INT_MAX);
         HIP_TRY(c, queue_reset(P.queue, c->stream));
-        HIP_TRY(c, launch_render_rays(c, walk, (p->flags & PT_FLAG_NEE) != 0, mis, lds, work_blocks, P, R));
+        HIP_TRY(c, launch_render_rays(L, P, R, c->stream));
         if (per_launch > 1) HIP_TRY(c, launch_fold_rays(c, P, R));
     }
     HIP_TRY(c, span_end(c));

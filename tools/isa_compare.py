@@ -11,7 +11,15 @@ name changed but whose code must not have, such as one that gained a template ar
 A stream is a kernel's lines without comments, directives and blank lines, every local label (.LBBn_m) renamed to one token.
 Prints one line per kernel: VGPRs, then occupancy / scratch / SGPR spill / VGPR spill / LDS on both sides, the instruction
 counts, and whether the streams are identical; where they are not, the first instruction at which they part.  Exit status 1
-when the sets of kernels or any resource figure differ."""
+when the sets of kernels or any resource figure differ.
+
+  tools/isa_compare.py parent/wave.remarks parent/wave.s head/wave.remarks head/wave.s --by-content
+
+--by-content: for a change that renames every kernel (other template arguments) and must change no code.  The two builds are compared as
+multisets of (family = the demangled name in front of `<`, instruction stream, all resource figures, VGPRs included).  A stream
+does not contain its kernel's own name; a call of another function would, and these kernels have none.  Prints per family the
+number of kernels on each side and how many have no partner on the other.  Exit status 1 on any difference."""
+import collections
 import re
 import subprocess
 import sys
@@ -58,8 +66,32 @@ def demangle(names):
     return dict(zip(names, (t.replace("void ", "").replace("(KParams)", "") for t in text.splitlines())))
 
 
+def by_content(ra, sa, rb, sb):
+    """The two builds as multisets of (instruction stream, resource figures), whatever the kernels are called."""
+    def family(pretty):
+        return re.match(r"(?:\(anonymous namespace\)::)?[^<(]*", pretty).group(0)
+
+    def bag(res, strm):
+        pretty, out = demangle(sorted(res)), collections.Counter()
+        for n in res:
+            out[(family(pretty[n]), tuple(strm[n]), tuple(res[n].get(f) for f in FIELDS))] += 1
+        return out
+    a, b = bag(ra, sa), bag(rb, sb)
+    bad = False
+    print("family | kernels parent -> head | without a partner: parent, head")
+    for fam in sorted({k[0] for k in a} | {k[0] for k in b}):
+        na, nb = sum(c for k, c in a.items() if k[0] == fam), sum(c for k, c in b.items() if k[0] == fam)
+        la, lb = sum(c for k, c in (a - b).items() if k[0] == fam), sum(c for k, c in (b - a).items() if k[0] == fam)
+        bad |= na != nb or la != 0 or lb != 0
+        print(f"{fam} | {na} -> {nb} | {la}, {lb}")
+    print(f"total | {sum(a.values())} -> {sum(b.values())} | {sum((a - b).values())}, {sum((b - a).values())} | {'DIFFERENT' if bad else 'identical'}")
+    return 1 if bad else 0
+
+
 def main():
     ra, sa, rb, sb = resources(sys.argv[1]), streams(sys.argv[2]), resources(sys.argv[3]), streams(sys.argv[4])
+    if sys.argv[5:] == ["--by-content"]:
+        return by_content(ra, sa, rb, sb)
     for k in range(5, len(sys.argv) - 1, 2):
         assert sys.argv[k] == "--rename", sys.argv[k]
         old, new = sys.argv[k + 1].split("=")
