@@ -1,6 +1,6 @@
 // pt_denoise.hip — pt_render_aux (first-hit guide buffers), pt_denoise (edge-avoiding a-trous wavelet filter, Dammertz et
-// al. 2010) and pt_temporal (the history of earlier frames reprojected into a new one, §10 f8).  One
-// translation unit of libptmi.so (pt_ctx.h).
+// al. 2010), pt_temporal (the history of earlier frames reprojected into a new one, §10 f8) and
+// pt_temporal_motion (the same for triangles moved by pt_refit_bvh, §10 f14).  One translation unit of libptmi.so (pt_ctx.h).
 //   k_render_aux     one lane per pixel, a 256-thread block per 16x16 tile (one wave per 8x8 quadrant): the pixel-centre camera
 //                    ray, the binary closest-hit walk of pt_trace_rays, the spheres by pt_closest_sphere; albedo, normal,
 //                    position (+ t) as float4 rows, the hit id
@@ -15,6 +15,10 @@
 //                    normal and position as one dwordx4 each, colour and length only for a tap that passed every test; no LDS
 //                    (neighbouring lanes share their taps through L1 / L2)
 //   k_tm_first       pt_temporal without a history: out = cur bit for bit, length 1 (+ display words)
+//   k_temporal_motion<MOTION>  pt_temporal_motion: k_temporal<true>'s pixel (tm_pixel, shared) behind one more
+//                    step — the pixel's triangle row in the previous and the current vertex buffer, a dwordx3 per vertex, and for
+//                    a row that changed the point the pixel's barycentric coordinates had on the previous triangle; that
+//                    point, not the pixel's own, is projected and tested (+ the motion, when asked for)
 //   k_frame_error    pt_frame_error: one lane per pixel, the relative standard error of the mean luminance from the moments
 //                    pt_render_moments keeps; a block adds its 256 values up in LDS, in double, and writes
 //                    ONE partial sum and ONE count to its own slot — the host adds the slots in block order
@@ -212,22 +216,80 @@ __global__ void __launch_bounds__(PTD_BLOCK) k_tm_first(const TmArgs A) {
     if (A.rgba) A.rgba[p] = pt_pack_rgba(r, g, b);
 }
 
-template <bool IDS>
-__global__ void __launch_bounds__(PTD_BLOCK) k_temporal(const TmArgs A) {
+// pt_temporal_motion (include/ptmi.h states the arithmetic, tests/motion_ref.py restates it): pt_temporal behind one more step,
+// where the pixel's surface point was when the history was rendered
+struct TmMotionArgs {
+    TmArgs t;                                  // t.prev_color null = no history: out = cur, motion 0
+    const float* __restrict__ prev_verts;      // [n_tris][9] by original id; may equal cur_verts
+    const float* __restrict__ cur_verts;
+    float2* __restrict__ motion;               // [H][W]; null unless the kernel writes it
+    uint32_t n_tris;
+};
+
+// Vertex k of a 36-byte row that is only 4-byte aligned: one dwordx3 load.  The empty asm keeps the compiler from seeing that the
+// three vertices are adjacent, or it joins their nine words into two dwordx4 loads and one dword.
+__device__ __forceinline__ v3 tm_vertex(const float* row, int k) {
+    const float* r = row + 3 * k;
+    asm("" : "+v"(r));
+    const __attribute__((address_space(1))) float* q = (const __attribute__((address_space(1))) float*)r;   // global, not flat
+    return V3(q[0], q[1], q[2]);
+}
+__device__ __forceinline__ bool tm_same_bits(const v3& a, const v3& b) {
+    return __float_as_uint(a.x) == __float_as_uint(b.x) && __float_as_uint(a.y) == __float_as_uint(b.y) && __float_as_uint(a.z) == __float_as_uint(b.z);
+}
+__device__ __forceinline__ bool tm_positive_finite(float a) { return a > 0.f && a < INFINITY; }
+
+// One pixel of k_temporal (MOVED 0: M unused, and nothing below differs from what the kernel held before the two shared it) and
+// of k_temporal_motion (MOVED 1; 2 = the motion is written as well).  The projection, the taps and the blend are the same
+// statements for both, so a surface point that did not move gets k_temporal<true>'s bits.
+template <bool IDS, int MOVED>
+__device__ __forceinline__ void tm_pixel(const TmArgs& A, const TmMotionArgs* M) {
     int x, y;
     if (!ptd_pixel(A, x, y)) return;
     const size_t p = (size_t)y * (size_t)A.W + (size_t)x;
     const float cr = A.cur_color[3 * p], cg = A.cur_color[3 * p + 1], cb = A.cur_color[3 * p + 2];
-    const float4 n4 = A.cur_normal[p];
+    const float4 n4 = (MOVED != 0 && !A.prev_color) ? make_float4(0.f, 0.f, 0.f, 0.f) : A.cur_normal[p];   // no history: every pixel as a miss
     float o0 = cr, o1 = cg, o2 = cb, on = 1.0f;   // no history accepted: the current frame, bit for bit
+    float mx = 0.f, my = 0.f;
     if (n4.x != 0.f || n4.y != 0.f || n4.z != 0.f) {
         const float4 x4 = A.cur_position[p];
-        const v3 np = V3(n4.x, n4.y, n4.z), xp = V3(x4.x, x4.y, x4.z);
+        v3 np = V3(n4.x, n4.y, n4.z), xp = V3(x4.x, x4.y, x4.z);
+        int idm = 0;
+        bool was = true;   // the point has a place in the previous frame's scene: (xp, np) become (x', n')
+        if constexpr (MOVED != 0) {
+            idm = A.cur_id[p];
+            if (idm >= 0) {
+                was = (uint32_t)idm < M->n_tris;   // past the rows: no history, and no row is read
+                if (was && M->prev_verts != M->cur_verts) {
+                    const float* cw = M->cur_verts + 9 * (size_t)idm;
+                    const float* pw = M->prev_verts + 9 * (size_t)idm;
+                    const v3 c0 = tm_vertex(cw, 0), c1 = tm_vertex(cw, 1), c2 = tm_vertex(cw, 2);
+                    const v3 p0 = tm_vertex(pw, 0), p1 = tm_vertex(pw, 1), p2 = tm_vertex(pw, 2);
+                    if (!(tm_same_bits(c0, p0) && tm_same_bits(c1, p1) && tm_same_bits(c2, p2))) {
+                        const v3 e1 = vsub(c1, c0), e2 = vsub(c2, c0), w = vsub(xp, c0);
+                        const v3 N = vcross(e1, e2);
+                        const float nn = vdot(N, N);
+                        const float inv = 1.0f / nn;
+                        const float u = vdot(vcross(w, e2), N) * inv, v = vdot(vcross(e1, w), N) * inv;   // barycentric, not clamped
+                        const v3 f1 = vsub(p1, p0), f2 = vsub(p2, p0);
+                        const v3 N1 = vcross(f1, f2);
+                        const float nn1 = vdot(N1, N1);
+                        was = tm_positive_finite(nn) && fabsf(u) < INFINITY && fabsf(v) < INFINITY && tm_positive_finite(nn1);
+                        xp = vmadd(f2, v, vmadd(f1, u, p0));
+                        // the previous triangle's unit normal on the face the current ray sees
+                        np = vscale(N1, (vdot(np, N) < 0.f ? -1.0f : 1.0f) * (1.0f / sqrtf(nn1)));
+                    }
+                }
+            }
+        }
         const v3 v = vsub(xp, V3(A.pos[0], A.pos[1], A.pos[2]));
         const float a = vdot(v, V3(A.front[0], A.front[1], A.front[2]));
-        if (a > 0.f) {
+        if (a > 0.f && (MOVED == 0 || was)) {
             const float fx = fmaf(vdot(v, V3(A.right[0], A.right[1], A.right[2])) / a, A.sx, A.cx);
             const float fy = fmaf(vdot(v, V3(A.up[0], A.up[1], A.up[2])) / a, A.sy, A.cy);
+            if constexpr (MOVED == 2) {
+                if (fabsf(fx) < INFINITY && fabsf(fy) < INFINITY) { mx = fx - (float)x; my = fy - (float)y; }
+            }
             // outside (-1, W) x (-1, H) no tap is inside the image; NaN and infinities fail here too, before the conversion to int
             if (fx > -1.0f && fx < (float)A.W && fy > -1.0f && fy < (float)A.H) {
                 const float x0f = floorf(fx), y0f = floorf(fy);
@@ -235,7 +297,8 @@ __global__ void __launch_bounds__(PTD_BLOCK) k_temporal(const TmArgs A) {
                 const int x0 = (int)x0f, y0 = (int)y0f;
                 const float tol = A.plane_tol * x4.w;
                 int idp = 0;
-                if (IDS) idp = A.cur_id[p];
+                if constexpr (MOVED != 0) idp = idm;
+                else if (IDS) idp = A.cur_id[p];
                 float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sl = 0.f;
 #pragma unroll
                 for (int j = 0; j < 2; j++) {
@@ -272,6 +335,19 @@ __global__ void __launch_bounds__(PTD_BLOCK) k_temporal(const TmArgs A) {
     A.out_color[3 * p] = o0; A.out_color[3 * p + 1] = o1; A.out_color[3 * p + 2] = o2;
     A.out_len[p] = on;
     if (A.rgba) A.rgba[p] = pt_pack_rgba(o0, o1, o2);
+    if constexpr (MOVED == 2) M->motion[p] = make_float2(mx, my);
+}
+
+template <bool IDS>
+__global__ void __launch_bounds__(PTD_BLOCK) k_temporal(const TmArgs A) {
+    tm_pixel<IDS, 0>(A, nullptr);
+}
+
+// A row of the vertex buffers is 36 bytes and only 4-byte aligned: three dwordx3 loads each.  The lanes of a tile mostly share a
+// few triangles, so the rows come from L1 / L2.
+template <bool MOTION>
+__global__ void __launch_bounds__(PTD_BLOCK) k_temporal_motion(const TmMotionArgs M) {
+    tm_pixel<true, MOTION ? 2 : 1>(M.t, &M);
 }
 
 // pt_frame_error: rse of pixel i in binary32 (include/ptmi.h states the formula); per block the sum of rse in double and the
@@ -392,29 +468,29 @@ extern "C" int pt_denoise(pt_ctx* c, const pt_denoise_params* dp, const float* c
     return PT_OK;
 }
 
-extern "C" int pt_temporal(pt_ctx* c, const pt_temporal_params* tp, const pt_camera* prev_cam, const float* prev_color_dev,
-                           const float* prev_length_dev, const float* prev_normal_dev, const float* prev_position_dev,
-                           const int32_t* prev_id_dev, const float* cur_color_dev, const float* cur_normal_dev,
-                           const float* cur_position_dev, const int32_t* cur_id_dev, float* out_color_dev, float* out_length_dev,
-                           uint32_t* rgba_dev) {
-    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
+namespace {
+
+// What pt_temporal and pt_temporal_motion share: the argument checks (messages under the caller's name `fn`) and the kernel
+// arguments of the reprojection.  PT_OK with A filled, or the error already recorded.
+int temporal_args(pt_ctx* c, const std::string& fn, const pt_temporal_params* tp, const pt_camera* prev_cam, const float* prev_color_dev,
+                  const float* prev_length_dev, const float* prev_normal_dev, const float* prev_position_dev, const int32_t* prev_id_dev,
+                  const float* cur_color_dev, const float* cur_normal_dev, const float* cur_position_dev, const int32_t* cur_id_dev,
+                  float* out_color_dev, float* out_length_dev, uint32_t* rgba_dev, TmArgs& A) {
     if (!tp || !cur_color_dev || !cur_normal_dev || !cur_position_dev || !out_color_dev || !out_length_dev)
-        return fail(c, PT_ERR_INVALID, "pt_temporal: null argument");
-    if (tp->width < 2 || tp->height < 2) return fail(c, PT_ERR_INVALID, "pt_temporal: width and height must be >= 2");
-    if (!std::isfinite(tp->max_history) || tp->max_history < 1.f) return fail(c, PT_ERR_INVALID, "pt_temporal: max_history must be finite and >= 1");
+        return fail(c, PT_ERR_INVALID, fn + ": null argument");
+    if (tp->width < 2 || tp->height < 2) return fail(c, PT_ERR_INVALID, fn + ": width and height must be >= 2");
+    if (!std::isfinite(tp->max_history) || tp->max_history < 1.f) return fail(c, PT_ERR_INVALID, fn + ": max_history must be finite and >= 1");
     if (!std::isfinite(tp->plane_tolerance) || tp->plane_tolerance < 0.f)
-        return fail(c, PT_ERR_INVALID, "pt_temporal: plane_tolerance must be finite and >= 0");
-    if (!(tp->normal_threshold >= -1.f && tp->normal_threshold <= 1.f)) return fail(c, PT_ERR_INVALID, "pt_temporal: normal_threshold must be in -1..1");
+        return fail(c, PT_ERR_INVALID, fn + ": plane_tolerance must be finite and >= 0");
+    if (!(tp->normal_threshold >= -1.f && tp->normal_threshold <= 1.f)) return fail(c, PT_ERR_INVALID, fn + ": normal_threshold must be in -1..1");
     const bool history = prev_color_dev != nullptr;
     if (history) {
         if (!prev_cam || !prev_length_dev || !prev_normal_dev || !prev_position_dev)
-            return fail(c, PT_ERR_INVALID, "pt_temporal: a history needs its camera, lengths, normals and positions");
-        if ((prev_id_dev == nullptr) != (cur_id_dev == nullptr)) return fail(c, PT_ERR_INVALID, "pt_temporal: ids of both frames or of neither");
+            return fail(c, PT_ERR_INVALID, fn + ": a history needs its camera, lengths, normals and positions");
+        if ((prev_id_dev == nullptr) != (cur_id_dev == nullptr)) return fail(c, PT_ERR_INVALID, fn + ": ids of both frames or of neither");
         if (out_color_dev == prev_color_dev || out_length_dev == prev_length_dev)
-            return fail(c, PT_ERR_INVALID, "pt_temporal: the new history may not overwrite the old one (ping-pong the buffers)");
+            return fail(c, PT_ERR_INVALID, fn + ": the new history may not overwrite the old one (ping-pong the buffers)");
     }
-    HIP_TRY(c, hipSetDevice(c->device));
-    TmArgs A;
     std::memset(&A, 0, sizeof A);
     A.cur_color = cur_color_dev;
     A.cur_normal = (const float4*)cur_normal_dev;
@@ -442,12 +518,69 @@ extern "C" int pt_temporal(pt_ctx* c, const pt_temporal_params* tp, const pt_cam
         A.plane_tol = tp->plane_tolerance;
         A.normal_thr = tp->normal_threshold;
     }
+    return PT_OK;
+}
+
+}  // namespace
+
+extern "C" int pt_temporal(pt_ctx* c, const pt_temporal_params* tp, const pt_camera* prev_cam, const float* prev_color_dev,
+                           const float* prev_length_dev, const float* prev_normal_dev, const float* prev_position_dev,
+                           const int32_t* prev_id_dev, const float* cur_color_dev, const float* cur_normal_dev,
+                           const float* cur_position_dev, const int32_t* cur_id_dev, float* out_color_dev, float* out_length_dev,
+                           uint32_t* rgba_dev) {
+    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
+    TmArgs A;
+    if (int rc = temporal_args(c, "pt_temporal", tp, prev_cam, prev_color_dev, prev_length_dev, prev_normal_dev, prev_position_dev, prev_id_dev,
+                               cur_color_dev, cur_normal_dev, cur_position_dev, cur_id_dev, out_color_dev, out_length_dev, rgba_dev, A))
+        return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
     const dim3 grid((unsigned)((tp->width + PTD_TILE - 1) / PTD_TILE), (unsigned)((tp->height + PTD_TILE - 1) / PTD_TILE));
     hipStream_t st = c->stream;
     HIP_TRY(c, span_begin(c));
-    if (!history) hipLaunchKernelGGL(k_tm_first, grid, dim3(PTD_BLOCK), 0, st, A);
+    if (!A.prev_color) hipLaunchKernelGGL(k_tm_first, grid, dim3(PTD_BLOCK), 0, st, A);
     else if (A.prev_id) hipLaunchKernelGGL(k_temporal<true>, grid, dim3(PTD_BLOCK), 0, st, A);
     else hipLaunchKernelGGL(k_temporal<false>, grid, dim3(PTD_BLOCK), 0, st, A);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, span_end(c));
+    return PT_OK;
+}
+
+extern "C" int pt_temporal_motion(pt_ctx* c, const pt_temporal_params* tp, const pt_camera* prev_cam, const float* prev_verts_dev,
+                                  const float* cur_verts_dev, size_t n_tris, const float* prev_color_dev, const float* prev_length_dev,
+                                  const float* prev_normal_dev, const float* prev_position_dev, const int32_t* prev_id_dev,
+                                  const float* cur_color_dev, const float* cur_normal_dev, const float* cur_position_dev,
+                                  const int32_t* cur_id_dev, float* out_color_dev, float* out_length_dev, uint32_t* rgba_dev,
+                                  float* motion_dev) {
+    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
+    TmMotionArgs M;
+    std::memset(&M, 0, sizeof M);
+    if (int rc = temporal_args(c, "pt_temporal_motion", tp, prev_cam, prev_color_dev, prev_length_dev, prev_normal_dev, prev_position_dev,
+                               prev_id_dev, cur_color_dev, cur_normal_dev, cur_position_dev, cur_id_dev, out_color_dev, out_length_dev,
+                               rgba_dev, M.t))
+        return rc;
+    const bool history = prev_color_dev != nullptr;
+    if (history) {
+        if (!prev_id_dev || !cur_id_dev) return fail(c, PT_ERR_INVALID, "pt_temporal_motion: the ids of both frames are required (they choose the vertex rows)");
+        if (n_tris > 0 && (!prev_verts_dev || !cur_verts_dev)) return fail(c, PT_ERR_INVALID, "pt_temporal_motion: a null vertex buffer with n_tris > 0");
+        if (n_tris >= ((size_t)1 << 31)) return fail(c, PT_ERR_INVALID, "pt_temporal_motion: n_tris must be < 2^31 (ids are int32)");
+        if (motion_dev) {
+            const void* others[] = {prev_verts_dev, cur_verts_dev, prev_color_dev, prev_length_dev, prev_normal_dev, prev_position_dev, prev_id_dev,
+                                    cur_color_dev, cur_normal_dev, cur_position_dev, cur_id_dev, out_color_dev, out_length_dev, rgba_dev};
+            for (const void* o : others)
+                if (o == (const void*)motion_dev) return fail(c, PT_ERR_INVALID, "pt_temporal_motion: motion_dev may not be one of the other buffers");
+        }
+        M.prev_verts = prev_verts_dev;
+        M.cur_verts = cur_verts_dev;
+        M.n_tris = (uint32_t)n_tris;
+    }
+    M.motion = (float2*)motion_dev;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const dim3 grid((unsigned)((tp->width + PTD_TILE - 1) / PTD_TILE), (unsigned)((tp->height + PTD_TILE - 1) / PTD_TILE));
+    hipStream_t st = c->stream;
+    HIP_TRY(c, span_begin(c));
+    if (motion_dev) hipLaunchKernelGGL(k_temporal_motion<true>, grid, dim3(PTD_BLOCK), 0, st, M);   // (without a history: out = cur, motion 0)
+    else if (history) hipLaunchKernelGGL(k_temporal_motion<false>, grid, dim3(PTD_BLOCK), 0, st, M);
+    else hipLaunchKernelGGL(k_tm_first, grid, dim3(PTD_BLOCK), 0, st, M.t);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, span_end(c));
     return PT_OK;

@@ -9,7 +9,7 @@
 //               --out image.ppm|.png|.pfm  --checkpoint state.ckpt [--checkpoint-every N]
 //               --resume state.ckpt --device-build --fix-estimators --nee --mis --gpus N --tile ROWS
 //               --denoise-out image.ppm|.png|.pfm  --variance-out file.pfm  --until-error E --max-frames M
-//               --pan-deg D --dolly S --temporal-out image.ppm|.png|.pfm  --equirect
+//               --pan-deg D --dolly S --spin-deg D --temporal-out image.ppm|.png|.pfm  --equirect
 //               --env file.pfm [--env-scale S] [--env-nearest] [--env-light]]
 // --gpus N splits the framebuffer over N contexts, one per GPU (devices device, device+1, ... modulo the number
 // present, so N > 1 also runs on a one-GPU box): stripes of --tile rows (default 8) are dealt round-robin
@@ -43,6 +43,12 @@
 // last call, and --out is what it is without the flag, byte for byte.  --temporal-out works on one context over the whole frame
 // and keeps no state a checkpoint could hold: it is refused with --gpus > 1, --resume, --checkpoint, --variance-out and
 // --until-error; so are the motion options with --resume, --checkpoint and --until-error (nothing accumulates across frames).
+// --spin-deg D moves the geometry instead: after every displayed frame the mesh (not the spheres) is turned to k x D degrees about
+// (0, 1, 0) through the centre of its rest-pose bounds — on the host, in double, from the rest pose, so nothing drifts — uploaded to
+// one of two device vertex buffers and applied with pt_refit_bvh (on every context of --gpus N).  Like a moving camera it restarts
+// the accumulation every frame and is refused in the same combinations; with --temporal-out the history goes through
+// pt_temporal_motion (ids from pt_render_aux, the previous and the current vertex buffer), which follows the turning triangles.
+// D = 0 issues no refit and changes nothing: the output is byte-identical to a run without the option.
 // --equirect renders a 360 x 180 degree latitude-longitude image seen from the camera position instead of the pinhole frame: column x
 // looks at longitude (x - W/2) 2 pi / W from `front` towards `right`, row y at latitude (y - H/2) pi / H towards `up` (the pole), so
 // the centre pixel looks along `front` and column 0 meets column W-1 behind it.  The rays are made on the host, one per pixel, and
@@ -89,7 +95,7 @@ int main(int argc, char** argv) {
     float bk[3] = {1.f, 1.f, 1.f};
     double until_error = -1.0;   // < 0: off
     long max_frames = -1;
-    double pan_deg = 0.0, dolly = 0.0;
+    double pan_deg = 0.0, dolly = 0.0, spin_deg = 0.0;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&](const char* name) -> const char* {
@@ -102,6 +108,7 @@ int main(int argc, char** argv) {
         else if (a == "--temporal-out") temporal_path = next("--temporal-out");
         else if (a == "--pan-deg") pan_deg = std::atof(next("--pan-deg"));
         else if (a == "--dolly") dolly = std::atof(next("--dolly"));
+        else if (a == "--spin-deg") spin_deg = std::atof(next("--spin-deg"));
         else if (a == "--variance-out") variance_path = next("--variance-out");
         else if (a == "--until-error") until_error = std::atof(next("--until-error"));
         else if (a == "--max-frames") max_frames = std::atol(next("--max-frames"));
@@ -139,14 +146,15 @@ int main(int argc, char** argv) {
     if (until && max_frames < (long)frames) return die("usage", "--until-error needs --max-frames >= --frames");
     if (!until && max_frames >= 0) return die("usage", "--max-frames goes with --until-error");
     if (with_moments && !resume_path.empty()) return die("usage", "--variance-out / --until-error do not combine with --resume (a checkpoint holds no moments)");
-    const bool moving = pan_deg != 0.0 || dolly != 0.0, temporal = !temporal_path.empty();
-    if (!std::isfinite(pan_deg) || !std::isfinite(dolly)) return die("usage", "--pan-deg and --dolly must be finite");
+    const bool spinning = spin_deg != 0.0;
+    const bool moving = pan_deg != 0.0 || dolly != 0.0 || spinning, temporal = !temporal_path.empty();
+    if (!std::isfinite(pan_deg) || !std::isfinite(dolly) || !std::isfinite(spin_deg)) return die("usage", "--pan-deg, --dolly and --spin-deg must be finite");
     if (temporal && (gpus > 1 || !resume_path.empty() || !ckpt_path.empty() || with_moments))
         return die("usage", "--temporal-out does not combine with --gpus > 1, --resume, --checkpoint, --variance-out or --until-error");
     if (moving && (!resume_path.empty() || !ckpt_path.empty() || until))
-        return die("usage", "--pan-deg / --dolly do not combine with --resume, --checkpoint or --until-error (a moving camera restarts the accumulation every frame)");
+        return die("usage", "--pan-deg / --dolly / --spin-deg do not combine with --resume, --checkpoint or --until-error (a moving camera or mesh restarts the accumulation every frame)");
     if (equirect && (!denoise_path.empty() || temporal || with_moments || gpus > 1 || !ckpt_path.empty() || !resume_path.empty() || moving))
-        return die("usage", "--equirect does not combine with --denoise-out, --temporal-out, --variance-out, --until-error, --gpus > 1, --checkpoint, --resume, --pan-deg or --dolly (they need the pinhole frame)");
+        return die("usage", "--equirect does not combine with --denoise-out, --temporal-out, --variance-out, --until-error, --gpus > 1, --checkpoint, --resume, --pan-deg, --dolly or --spin-deg (they need the pinhole frame)");
 
     // --env: the map is read and checked before anything is built or rendered
     int env_w = 0, env_h = 0;
@@ -323,7 +331,7 @@ int main(int argc, char** argv) {
     // --temporal-out: the ping-pong history (colour, length, guides) of TemporalHistory, on the one context
     const size_t n_pix_all = (size_t)W * H;
     void *t_color[2] = {nullptr, nullptr}, *t_len[2] = {nullptr, nullptr}, *t_alb[2] = {nullptr, nullptr}, *t_nrm[2] = {nullptr, nullptr},
-         *t_pos[2] = {nullptr, nullptr}, *t_rgba = nullptr;
+         *t_pos[2] = {nullptr, nullptr}, *t_id[2] = {nullptr, nullptr}, *t_rgba = nullptr;
     int t_cur = 0;          // the set the next push writes
     bool t_has = false;     // a history exists
     pt_camera t_cam{};      // its camera
@@ -332,14 +340,61 @@ int main(int argc, char** argv) {
         for (int k = 0; k < 2; k++)
             if (pt_malloc(ctx, n_pix_all * 12, &t_color[k]) != PT_OK || pt_malloc(ctx, n_pix_all * 4, &t_len[k]) != PT_OK ||
                 pt_malloc(ctx, n_pix_all * 16, &t_alb[k]) != PT_OK || pt_malloc(ctx, n_pix_all * 16, &t_nrm[k]) != PT_OK ||
-                pt_malloc(ctx, n_pix_all * 16, &t_pos[k]) != PT_OK)
+                pt_malloc(ctx, n_pix_all * 16, &t_pos[k]) != PT_OK || (spinning && pt_malloc(ctx, n_pix_all * 4, &t_id[k]) != PT_OK))
                 return die("pt_malloc", pt_last_error(ctx));
         if (pt_malloc(ctx, n_pix_all * 4, &t_rgba) != PT_OK) return die("pt_malloc", pt_last_error(ctx));
     }
+    // --spin-deg: the rest pose as rows v0, v1, v2 by triangle id, and per context two device vertex buffers (pt_refit_bvh's layout);
+    // displayed frame f is rendered from buffer f & 1, so the buffer of the frame before it is still whole when the history reads it
+    const size_t n_spin_tris = pth_mesh_n_tris(mesh);
+    std::vector<double> spin_rest;
+    std::vector<float> spin_rows;
+    double spin_c[3] = {0.0, 0.0, 0.0};
+    std::vector<void*> spin_buf((size_t)gpus * 2, nullptr);
+    if (spinning) {
+        const float* mv = pth_mesh_verts(mesh);
+        const int32_t* mt = pth_mesh_tris(mesh);
+        spin_rest.resize(n_spin_tris * 9);
+        spin_rows.resize(n_spin_tris * 9);
+        for (size_t i = 0; i < n_spin_tris * 3; i++)
+            for (int a = 0; a < 3; a++) spin_rest[3 * i + a] = (double)mv[3 * (size_t)mt[i] + a];
+        float lo[3], hi[3];
+        pth_mesh_bounds(mesh, lo, hi);
+        for (int a = 0; a < 3; a++) spin_c[a] = 0.5 * ((double)lo[a] + (double)hi[a]);
+        for (size_t i = 0; i < spin_rest.size(); i++) spin_rows[i] = (float)spin_rest[i];
+        for (int g = 0; g < gpus; g++)
+            for (int b = 0; b < 2; b++)
+                if (pt_malloc(ctxs[(size_t)g], spin_rows.size() * 4, &spin_buf[(size_t)g * 2 + b]) != PT_OK ||
+                    pt_upload(ctxs[(size_t)g], spin_buf[(size_t)g * 2 + b], spin_rows.data(), spin_rows.size() * 4) != PT_OK)
+                    return die("--spin-deg", pt_last_error(ctxs[(size_t)g]));
+    }
+    auto spin_mesh = [&](int f) -> int {   // the mesh of displayed frame f: the rest pose turned by f x spin_deg about (0, 1, 0) through spin_c
+        const double th = spin_deg * (double)f * 3.14159265358979323846 / 180.0, cs = std::cos(th), sn = std::sin(th);
+        for (size_t i = 0; i < n_spin_tris * 3; i++) {
+            const double x = spin_rest[3 * i] - spin_c[0], z = spin_rest[3 * i + 2] - spin_c[2];
+            spin_rows[3 * i] = (float)(spin_c[0] + cs * x + sn * z);
+            spin_rows[3 * i + 1] = (float)spin_rest[3 * i + 1];
+            spin_rows[3 * i + 2] = (float)(spin_c[2] - sn * x + cs * z);
+        }
+        for (int g = 0; g < gpus; g++) {
+            void* buf = spin_buf[(size_t)g * 2 + (f & 1)];
+            if (pt_upload(ctxs[(size_t)g], buf, spin_rows.data(), spin_rows.size() * 4) != PT_OK) return die("--spin-deg", pt_last_error(ctxs[(size_t)g]));
+            if (pt_refit_bvh(ctxs[(size_t)g], (const float*)buf, n_spin_tris, nullptr) != PT_OK) return die("pt_refit_bvh", pt_last_error(ctxs[(size_t)g]));
+        }
+        return 0;
+    };
+    int calls = 0;
     auto temporal_push = [&]() -> int {   // guides of `cam`, the frame in `accum` against the history, swap
         const int k = t_cur, o = 1 - t_cur;
-        if (pt_render_aux(ctx, &cam, &p, (float*)t_alb[k], (float*)t_nrm[k], (float*)t_pos[k], nullptr) != PT_OK) return die("pt_render_aux", pt_last_error(ctx));
-        if (pt_temporal(ctx, &tpar, t_has ? &t_cam : nullptr, t_has ? (const float*)t_color[o] : nullptr, (const float*)t_len[o],
+        if (pt_render_aux(ctx, &cam, &p, (float*)t_alb[k], (float*)t_nrm[k], (float*)t_pos[k], (int32_t*)t_id[k]) != PT_OK) return die("pt_render_aux", pt_last_error(ctx));
+        if (spinning) {   // the frame just rendered is number calls - 1: its vertices and those of the frame before it
+            const int f = calls - 1;
+            if (pt_temporal_motion(ctx, &tpar, t_has ? &t_cam : nullptr, (const float*)spin_buf[(size_t)(1 - (f & 1))], (const float*)spin_buf[(size_t)(f & 1)],
+                                   n_spin_tris, t_has ? (const float*)t_color[o] : nullptr, (const float*)t_len[o], (const float*)t_nrm[o],
+                                   (const float*)t_pos[o], (const int32_t*)t_id[o], (const float*)accum, (const float*)t_nrm[k], (const float*)t_pos[k],
+                                   (const int32_t*)t_id[k], (float*)t_color[k], (float*)t_len[k], (uint32_t*)t_rgba, nullptr) != PT_OK)
+                return die("pt_temporal_motion", pt_last_error(ctx));
+        } else if (pt_temporal(ctx, &tpar, t_has ? &t_cam : nullptr, t_has ? (const float*)t_color[o] : nullptr, (const float*)t_len[o],
                         (const float*)t_nrm[o], (const float*)t_pos[o], nullptr, (const float*)accum, (const float*)t_nrm[k],
                         (const float*)t_pos[k], nullptr, (float*)t_color[k], (float*)t_len[k], (uint32_t*)t_rgba) != PT_OK)
             return die("pt_temporal", pt_last_error(ctx));
@@ -392,7 +447,6 @@ int main(int argc, char** argv) {
     const uint64_t last_frame = until ? frameNumber + (uint64_t)max_frames : end_frame;   // --until-error: never past --max-frames
     std::vector<float> host_mom;
     double mean_rse = -1.0;   // pt_frame_error's figure after the last call, < 0: not computed (fewer than two samples)
-    int calls = 0;
     auto t0 = std::chrono::steady_clock::now();
     for (;;) {
         while (frameNumber < end_frame) {
@@ -400,6 +454,8 @@ int main(int argc, char** argv) {
                 if (pt_sync(cx) != PT_OK) return die("pt_sync", pt_last_error(cx));     // :395
             const uint32_t n = (uint32_t)std::min<uint64_t>((uint64_t)spp, end_frame - frameNumber);
             if (moving && calls > 0) move_camera(calls);                                // the camera is dirty: start over (:399)
+            if (spinning && calls > 0)
+                if (int rc = spin_mesh(calls)) return rc;
             p.frame = frameNumber;                                                      // :397
             p.sample_index = moving ? 1 : constantPdf + 1;                              // :399 (1 on the first frame: overwrite)
             if (equirect) {
@@ -530,9 +586,13 @@ int main(int argc, char** argv) {
     }
     if (temporal) {
         for (int k = 0; k < 2; k++)
-            for (void* b : {t_color[k], t_len[k], t_alb[k], t_nrm[k], t_pos[k]}) pt_free(ctx, b);
+            for (void* b : {t_color[k], t_len[k], t_alb[k], t_nrm[k], t_pos[k], t_id[k]})
+                if (b) pt_free(ctx, b);
         pt_free(ctx, t_rgba);
     }
+    for (int g = 0; g < gpus; g++)
+        for (int b = 0; b < 2; b++)
+            if (spin_buf[(size_t)g * 2 + b]) pt_free(ctxs[(size_t)g], spin_buf[(size_t)g * 2 + b]);
     if (eq_rays) pt_free(ctx, eq_rays);
     (void)accum; (void)rgba;
     if (moments_all != moments[0]) pt_free(ctx, moments_all);

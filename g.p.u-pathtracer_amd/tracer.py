@@ -287,6 +287,22 @@ class PathTracer:
                                           prev_color_ptr, prev_length_ptr, prev_normal_ptr, prev_position_ptr, prev_id_ptr,
                                           cur_color_ptr, cur_normal_ptr, cur_position_ptr, cur_id_ptr, out_color_ptr, out_length_ptr, rgba_ptr))
 
+    def temporal_motion(self, width, height, prev_cam, prev_verts, cur_verts, n_tris, prev_color_ptr, prev_length_ptr, prev_normal_ptr,
+                        prev_position_ptr, prev_id_ptr, cur_color_ptr, cur_normal_ptr, cur_position_ptr, cur_id_ptr, out_color_ptr,
+                        out_length_ptr, rgba_ptr=None, motion_ptr=None, max_history=TEMPORAL_DEFAULTS["max_history"],
+                        plane_tolerance=TEMPORAL_DEFAULTS["plane_tolerance"], normal_threshold=TEMPORAL_DEFAULTS["normal_threshold"]):
+        """temporal() for a scene whose triangles moved between the two frames (pt_temporal_motion): prev_verts / cur_verts are
+        the float32 rows v0, v1, v2 by original triangle id that refit_bvh took for the previous and for the current frame (a
+        DeviceBuffer or a raw device pointer each; they may be the same buffer), n_tris their number of rows.  Both id pointers are
+        required.  motion_ptr (optional): float[H][W][2], where in the previous frame each pixel's surface point was, relative
+        to the pixel.  Asynchronous until sync()."""
+        pv, cv = (v.ptr if isinstance(v, DeviceBuffer) else v for v in (prev_verts, cur_verts))
+        tp = TemporalParams(int(width), int(height), float(max_history), float(plane_tolerance), float(normal_threshold), 0)
+        self._check(self._lib.pt_temporal_motion(self._ctx, C.byref(tp), C.byref(prev_cam) if prev_cam is not None else None, pv, cv, int(n_tris),
+                                                 prev_color_ptr, prev_length_ptr, prev_normal_ptr, prev_position_ptr, prev_id_ptr,
+                                                 cur_color_ptr, cur_normal_ptr, cur_position_ptr, cur_id_ptr, out_color_ptr, out_length_ptr,
+                                                 rgba_ptr, motion_ptr))
+
     # ------------------------------------------------------------------ measurement
     def counters(self):
         c = Counters()
@@ -365,11 +381,14 @@ class TemporalHistory:
     def _ptrs(self, k):
         return [b.ptr if b is not None else None for b in self.guides[k]]
 
-    def push(self, cam, params, color_ptr, rgba_ptr=None, **temporal):
+    def push(self, cam, params, color_ptr, rgba_ptr=None, moved=None, motion_ptr=None, **temporal):
         """One frame: render_aux for `cam` (params: the frame's pt_params), then temporal() of the frame in color_ptr (rendered
         with sample_index = 1; never written) against the stored history — or with no history the first time — then the swap.
         Returns (color_ptr, length_ptr, (albedo, normal, position, id) ptrs) of the new history; the colour and the guides can be
-        passed to denoise() directly.  **temporal: max_history, plane_tolerance, normal_threshold.  Asynchronous."""
+        passed to denoise() directly.  **temporal: max_history, plane_tolerance, normal_threshold.  Asynchronous.
+        moved = (prev_verts_ptr, cur_verts_ptr, n_tris): the triangles moved since the last push (refit_bvh), so the frame goes
+        through temporal_motion() (the history needs ids), with motion_ptr as its motion buffer.  The caller owns and ping-pongs
+        the two vertex buffers: the previous one stays unchanged until the push that reads it has been issued."""
         k, o = self.cur, 1 - self.cur
         alb, nrm, pos, ids = self._ptrs(k)
         self.t.render_aux(cam, params, alb, nrm, pos, ids)
@@ -378,7 +397,13 @@ class TemporalHistory:
         else:
             _, pn, pp, pi = self._ptrs(o)
             prev = (self.cam, self.color[o].ptr, self.length[o].ptr, pn, pp, pi)
-        self.t.temporal(self.W, self.H, *prev, color_ptr, nrm, pos, ids, self.color[k].ptr, self.length[k].ptr, rgba_ptr, **temporal)
+        if moved is not None:
+            self.t.temporal_motion(self.W, self.H, prev[0], *moved, *prev[1:], color_ptr, nrm, pos, ids, self.color[k].ptr, self.length[k].ptr,
+                                   rgba_ptr, motion_ptr, **temporal)
+        else:
+            if motion_ptr is not None:
+                raise ValueError("TemporalHistory.push: motion_ptr goes with moved=")
+            self.t.temporal(self.W, self.H, *prev, color_ptr, nrm, pos, ids, self.color[k].ptr, self.length[k].ptr, rgba_ptr, **temporal)
         self.cam = Camera.from_buffer_copy(cam)
         self.cur = o
         return self.color[k].ptr, self.length[k].ptr, (alb, nrm, pos, ids)

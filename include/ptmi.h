@@ -778,8 +778,10 @@ int pt_denoise(pt_ctx* ctx, const pt_denoise_params* dp, const float* color_dev,
  * No scene needed; no scratch, no allocation, no synchronisation.  Asynchronous on the context's stream, hence ordered after
  * the fold of an earlier pt_render (which stays on that stream under PT_OPT_OVERLAP) and after pt_render_aux; the outputs can go
  * straight into pt_denoise.  With PT_OPT_TIMING=1, pt_last_kernel_ms reports its device time.
- * Triangles moved by pt_refit_bvh fail the plane test where they moved: their history is dropped, which is safe but not useful.
- * Out of scope: motion vectors for moving geometry, reprojecting pt_render_moments' moments, following specular first hits (a
+ * Triangles moved by pt_refit_bvh fail the plane test where they moved and lose their history — except one that slides within its
+ * own plane, which passes every test and takes the history of another surface point: pt_temporal_motion (below) is the call for
+ * a scene whose triangles move.
+ * Out of scope: reprojecting pt_render_moments' moments, following specular first hits (a
  * mirror's history is looked up where its surface was, not where its reflection was), per-stripe operation in the multi-GPU
  * tile split (the call is full-frame). */
 typedef struct pt_temporal_params {
@@ -795,6 +797,54 @@ int pt_temporal(pt_ctx* ctx, const pt_temporal_params* tp, const pt_camera* prev
                 const float* cur_color_dev,
                 const float* cur_normal_dev, const float* cur_position_dev, const int32_t* cur_id_dev,
                 float* out_color_dev, float* out_length_dev, uint32_t* rgba_dev);
+
+/* pt_temporal_motion: pt_temporal for a scene whose triangles moved between the two frames (pt_refit_bvh) — an EXTENSION
+ * (DESIGN.md §10 f14).  The id pt_render_aux wrote for a pixel names its triangle; the pixel's barycentric coordinates in that
+ * triangle NOW, applied to the vertices the triangle had THEN, give where the surface point was, and the history is looked up
+ * there.  prev_verts_dev / cur_verts_dev have pt_refit_bvh's layout: float[n_tris][9] = v0, v1, v2 of the triangle whose
+ * ORIGINAL id is the row; device memory; rows only 4-byte aligned; the two pointers may be equal.  prev_verts_dev is the scene
+ * the prev_* guides were rendered from, cur_verts_dev the scene the cur_* guides were rendered from (for a mesh that was never
+ * refit both are its rest pose).  Everything not named here — the buffers, pt_temporal_params, the bilinear footprint, the blend,
+ * rgba_dev, the aliasing rules, asynchrony on the context's stream, PT_OPT_TIMING — is pt_temporal's, word for word.
+ * For pixel p = (x, y) with normal n_p, position x_p, ray distance t_p and id i_p, in binary32 and in this order
+ * (vcross(u, v) = (fmaf(u.y, v.z, -(u.z * v.y)), fmaf(u.z, v.x, -(u.x * v.z)), fmaf(u.x, v.y, -(u.y * v.x))),
+ * vmadd(u, s, v) = fmaf(u, s, v) per component, vdot as above; no other fused operation):
+ *   1. n_p == (0, 0, 0), a current miss: out = cur, out_length = 1, motion = (0, 0).
+ *   2. Where the point was, (x', n'):
+ *      static, x' = x_p and n' = n_p, when i_p < 0 (a sphere, or an id that is no triangle), or when the nine words of row i_p
+ *        are equal as 32-bit patterns in both vertex buffers: an unmoved surface follows pt_temporal's arithmetic exactly;
+ *      i_p >= n_tris: the history is rejected, and neither vertex buffer is read at that row;
+ *      moved otherwise, with c0, c1, c2 the current row and p0, p1, p2 the previous one:
+ *        e1 = c1 - c0, e2 = c2 - c0, w = x_p - c0;  N = vcross(e1, e2);  nn = vdot(N, N); rejected unless nn > 0 and finite.
+ *        inv = 1.0f / nn;  u = vdot(vcross(w, e2), N) * inv;  v = vdot(vcross(e1, w), N) * inv (not clamped); rejected when
+ *        either is not finite.
+ *        f1 = p1 - p0, f2 = p2 - p0;  x' = vmadd(f2, v, vmadd(f1, u, p0)).
+ *        N' = vcross(f1, f2);  nn' = vdot(N', N'); rejected unless nn' > 0 and finite.
+ *        k = (vdot(n_p, N) < 0 ? -1.0f : 1.0f) * (1.0f / sqrtf(nn'));  n' = N' * k: the previous triangle's unit normal on the
+ *        face the current ray sees.
+ *   3. pt_temporal's step 2 on v = x' - prev_cam.pos: a, b, c, fx, fy with the same sx, sy and the same rejections.
+ *      motion = (fx - (float)x, fy - (float)y) whenever this step does not reject, whatever the taps then decide; else (0, 0).
+ *   4. The footprint and the weights are pt_temporal's.  A tap counts when it is inside the image, w_q > 0, n_q != 0,
+ *      prev_id[q] == i_p, vdot(n', n_q) >= normal_threshold and fabsf(vdot(n', x_q - x')) <= plane_tolerance * t_p: the surface
+ *      tests run in the previous frame's space, against the previous frame's guides.
+ *   5. pt_temporal's step 5.  Not accepted, or rejected above: out = cur bit for bit, out_length = 1.
+ * motion_dev (may be NULL): float[h][w][2], where in the previous frame the pixel's surface point was, relative to the pixel.
+ * prev_color_dev == NULL: no history yet; as pt_temporal, motion = (0, 0) everywhere, the vertex pointers and n_tris are ignored.
+ * PT_ERR_INVALID: everything pt_temporal refuses; with a history also either id pointer NULL (the ids choose the rows), a NULL
+ * vertex pointer while n_tris > 0, n_tris >= 2^31, motion_dev equal to any input or output buffer.  n_tris == 0 is valid: every
+ * triangle pixel then has no history.  No scene needed; no scratch, no allocation, no synchronisation.
+ * Left out: moving spheres (a sphere's pixels are static); history for points that were hidden or off screen in the previous
+ * frame (they restart, as under a camera move); the lag of lighting that changes because geometry moved — a shadow that wanders
+ * over a static wall keeps its history (max_history is the caller's handle); reprojecting pt_render_moments' moments; specular
+ * first hits; per-stripe operation in the multi-GPU tile split. */
+int pt_temporal_motion(pt_ctx* ctx, const pt_temporal_params* tp, const pt_camera* prev_cam,
+                       const float* prev_verts_dev, const float* cur_verts_dev, size_t n_tris,
+                       const float* prev_color_dev, const float* prev_length_dev,
+                       const float* prev_normal_dev, const float* prev_position_dev, const int32_t* prev_id_dev,
+                       const float* cur_color_dev,
+                       const float* cur_normal_dev, const float* cur_position_dev, const int32_t* cur_id_dev,
+                       float* out_color_dev, float* out_length_dev, uint32_t* rgba_dev,
+                       float* motion_dev /* float[h][w][2], may be NULL */);
 
 /* ---- measurement --------------------------------------------------------------- */
 int pt_get_counters(pt_ctx* ctx, pt_counters* out);

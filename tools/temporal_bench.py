@@ -2,7 +2,10 @@
 """pt_temporal measured: device time (PT_OPT_TIMING, pt_last_kernel_ms) at 1920x1080 on the bench scene (cornell_dragon + the
 sphere room, golden camera), the camera panning 1 degree between frames, the median of repeated timed calls — with and without
 ids, the first frame's copy path, and beside them the guide pass and pt_denoise at 4 iterations from the same run.
-Usage: python tools/temporal_bench.py [--out FILE] [--reps 20]"""
+--motion measures pt_temporal_motion instead: the dragon of the bench scene turned and moved between the two frames
+(tests/gpu_support.cornell_dragon_moved, applied with pt_refit_bvh), the camera still; pt_temporal_motion with and without its
+motion buffer and pt_temporal on the same guides, the three alternating call by call in one process.
+Usage: python tools/temporal_bench.py [--out FILE] [--reps 20] [--motion [--turn-deg 3]]"""
 import argparse
 import math
 import os
@@ -18,6 +21,8 @@ ap.add_argument("--out", default=None, help="also write the report here")
 ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--scene", default="cornell_dragon")
 ap.add_argument("--pan-deg", type=float, default=1.0)
+ap.add_argument("--motion", action="store_true", help="measure pt_temporal_motion on a moved dragon")
+ap.add_argument("--turn-deg", type=float, default=3.0, help="--motion: the dragon's turn between the two frames")
 a = ap.parse_args()
 W, H = 1920, 1080
 lines = []
@@ -37,6 +42,78 @@ def panned(cam, deg):
         getattr(c, name)[:] = (x * math.cos(th) + z * math.sin(th), y, -x * math.sin(th) + z * math.cos(th))
     return c
 
+
+def motion_bench():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from gpu_support import cornell_dragon_moved
+    mesh, rest, moved = cornell_dragon_moved(deg=a.turn_deg, shift=(0.3, 0.0, -0.2))
+    n = len(rest)
+    t = g.PathTracer(0)
+    t.upload_bvh(g.Bvh(mesh))
+    t.upload_spheres(g.reference_spheres())
+    cam = g.default_camera(W, H)
+    cam.dist = 18.0 * H / 1080.0
+    p = g.default_params(W, H)
+    p.flags = g.FLAG_WRITE_RGBA
+    acc, rgba = t.alloc_frame(W, H)
+    orgba, mo = t.malloc(W * H * 4), t.malloc(W * H * 8)
+    verts = [t.malloc(rest.nbytes) for _ in range(2)]
+    verts[0].upload(rest)
+    verts[1].upload(moved)
+    th = g.TemporalHistory(t, W, H)
+    p.frame, p.sample_index = 0, 1
+    t.launch_kernel(acc.ptr, rgba.ptr, cam, p, 4)
+    th.push(cam, p, acc.ptr)                      # the rest pose becomes the history
+    t.refit_bvh(verts[1], n)
+    p.frame = 4
+    t.launch_kernel(acc.ptr, rgba.ptr, cam, p, 4)
+    prev, cur = 1 - th.cur, th.cur
+    alb, nrm, pos, ids = th._ptrs(cur)
+    _, pn, pp, pi = th._ptrs(prev)
+    t.render_aux(cam, p, alb, nrm, pos, ids)      # the guides of the moved pose
+    t.sync()
+
+    def motion(with_motion):
+        t.temporal_motion(W, H, cam, verts[0], verts[1], n, th.color[prev].ptr, th.length[prev].ptr, pn, pp, pi, acc.ptr, nrm, pos, ids,
+                          th.color[cur].ptr, th.length[cur].ptr, orgba.ptr, mo.ptr if with_motion else None)
+
+    def static():
+        t.temporal(W, H, cam, th.color[prev].ptr, th.length[prev].ptr, pn, pp, pi, acc.ptr, nrm, pos, ids, th.color[cur].ptr, th.length[cur].ptr,
+                   orgba.ptr)
+
+    calls = (("pt_temporal_motion, motion buffer   ", lambda: motion(True)), ("pt_temporal_motion, no motion buffer", lambda: motion(False)),
+             ("pt_temporal, ids (same guides)      ", static))
+    t.set_option(g.OPT_TIMING, 1)
+    ms = {name: [] for name, _ in calls}
+    for _ in range(a.reps + 2):                   # alternating: every call sees the same clocks and caches as its neighbours
+        for name, fn in calls:
+            fn()
+            ms[name].append(t.last_kernel_ms())
+    say(f"{a.scene}-moved ({n} triangles, the dragon turned {a.turn_deg} deg and shifted) + 8 spheres, {W}x{H}, camera still; device ms "
+        f"(PT_OPT_TIMING), median / min of {a.reps} calls, alternating")
+    for name, _ in calls:
+        say(f"{name}  {float(np.median(ms[name][2:])):7.3f} / {float(np.min(ms[name][2:])):7.3f} ms")
+    t.set_option(g.OPT_TIMING, 0)
+    id_cur = th.guides[cur][3].download(np.int32, (H, W))
+    dragon = id_cur >= g.Mesh.asset("cornell").n_tris
+    for name, fn in calls[1:]:
+        fn()
+        t.sync()
+        length = th.length[cur].download(np.float32, (H, W))
+        say(f"  {name.strip()}: history accepted at {(length > 1).mean() * 100:.1f} % of the pixels, {(length > 1)[dragon].mean() * 100:.1f} % of the "
+            f"dragon's ({dragon.mean() * 100:.1f} % of the frame)")
+    for b in [acc, rgba, orgba, mo] + verts:
+        b.free()
+    th.free()
+    t.close()
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+if a.motion:
+    motion_bench()
+    sys.exit(0)
 
 t = g.PathTracer(0)
 mesh = g.scene_mesh(a.scene)
