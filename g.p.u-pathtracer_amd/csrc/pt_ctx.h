@@ -19,6 +19,7 @@
 #include "../../include/ptmi.h"
 #include "pt_kernels.h"
 #include "pt_own.h"
+#include "pt_plan.h"
 
 // the bounce-0 walk of a new context (PT_OPT_FIRST_WALK); -DPT_FIRST_WALK_DEFAULT=0 builds the per-lane one for A/B timing
 #ifndef PT_FIRST_WALK_DEFAULT
@@ -238,6 +239,7 @@ inline int fail(pt_ctx* c, int code, const std::string& msg) {
     g_err = msg;
     return code;
 }
+inline int fail(pt_ctx* c, const Refusal& r) { return r.code == PT_OK ? PT_OK : fail(c, r.code, r.msg); }   // (nothing to do: PT_OK, the last error stays)
 inline int hip_fail(pt_ctx* c, hipError_t e, const char* what) {
     return fail(c, PT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
 }
@@ -253,43 +255,14 @@ inline hipError_t quiesce(pt_ctx* c) {
     return e;
 }
 
-// LDS bytes of a frame-kernel block, top-of-tree planes + stack, with the largest n_top (halved from the one asked for) that fits
-// 160 KiB: a deep tree gives the LDS to the stack first
-inline size_t lds_fit(int& n_top, int stack_n, int block) {
-    const size_t stack = (size_t)stack_n * block * 4;
-    while (n_top > 0 && (size_t)n_top * 64 + stack > 160 * 1024) n_top /= 2;
-    return (size_t)n_top * 64 + stack;
-}
-
 template <typename K>
 hipError_t allow_lds(K kernel, size_t bytes) {
     return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
-// ---- the rules every entry point shares, each written here once ----------------
-// The wide walk pushes up to three entries per level: whether a stack of `cap` entries holds it for this tree.
-inline bool wide_walk_fits(const TreeState& t, int cap) { return t.has_bvh && 3 * t.wide_depth + 2 <= (uint32_t)cap; }
-// The walk a path call runs (LaunchCfg::walk) under PT_OPT_WALK, or PT_ERR_UNSUPPORTED (< 0) in `who`'s name: Woop records are only
-// understood by the wide walk, a tree too deep for it takes the unified binary walk.  postponed: the caller has walk 4, else it runs as 2.
-inline int choose_walk(pt_ctx* c, const char* who, bool postponed) {
-    const bool wide_ok = wide_walk_fits(c->tree, PT_STACK_CAP);
-    if (c->tree.has_bvh && c->tree.records_woop)
-        return wide_ok ? 3 : fail(c, PT_ERR_UNSUPPORTED, std::string(who) + ": Woop records need the wide walk and this tree is too deep for it");
-    const int walk = c->opt_walk == 4 && !postponed ? 2 : c->opt_walk;
-    return walk >= 2 && !wide_ok ? 1 : walk;
-}
-// PT_OPT_PATH_HISTORY: whether a call's masks and gathered light are functions of the objects its paths hit, in path_shade_hit's
-// DIFF / SPEC / METAL arithmetic (mask *= colour, accu += mask * emission) — nothing scales the colour (the roulettes), nothing adds in
-// place beside the shade lanes (PT_FLAG_NEE: k_wf_resolve), every object has a history code and a row in the shade stage's table (the
-// spheres of the kernel-argument block, ONE triangle material), no REFR branch scales the mask, and the word holds the codes.
-inline bool path_history_holds(const KParams& P) {
-    if ((P.flags & (PT_FLAG_NEE | PT_FLAG_RUSSIAN_ROULETTE | PT_FLAG_RR_CPU_TRACER)) || P.tri_matid || P.sc.n_spheres > PT_KSPHERES ||
-        P.tri_mat == PT_MAT_REFR || P.depth > PT_HIST_MAX_DEPTH)
-        return false;
-    for (int i = 0; i < P.sc.n_spheres; i++)
-        if (P.ksph[i].mat == PT_MAT_REFR) return false;
-    return true;
-}
+// ---- the rules every entry point shares are pt_plan.h's; here is what applies their answers to the context and the kernel arguments
+// What planning reads off the context (ptmi.hip): the one place that reads the tree's fields and the options for a plan
+CtxFacts ctx_facts(const pt_ctx* c);
 // The scene as a kernel sees it: one item buffer for nodes and records, the wide tree's root and, where ksph (KParams::ksph) is
 // given, the spheres: a ray-batch query sees none.  Zeroes the rest; the stack and LDS layout is the caller's.
 inline void scene_view(const pt_ctx* c, KScene& sc, pt_sphere_d* ksph = nullptr) {
@@ -301,31 +274,18 @@ inline void scene_view(const pt_ctx* c, KScene& sc, pt_sphere_d* ksph = nullptr)
     sc.spheres = c->d_spheres.get(); sc.n_spheres = c->n_spheres;
     std::memcpy(ksph, c->h_spheres, sizeof c->h_spheres);
 }
-// The binary walk with one thread per ray (pt_trace_rays, the deep-tree queries, pt_render_aux): all PT_STACK_CAP entries and the top
-// of the tree in LDS.  Returns the LDS bytes of a block of PT_BLOCK_RAYS.
-inline size_t binary_ray_layout(const pt_ctx* c, KScene& sc) {
+// The binary walk with one thread per ray (binary_ray_lds, pt_plan.h) in a kernel's scene view.  Returns the LDS bytes of a block.
+inline size_t binary_ray_layout(const CtxFacts& f, KScene& sc) {
     sc.stack_n = PT_STACK_CAP; sc.top_base = 0;
-    sc.n_top = (int)std::min<uint32_t>((uint32_t)c->opt_top, c->tree.n_top_layout);
-    return lds_fit(sc.n_top, sc.stack_n, PT_BLOCK_RAYS);
+    return binary_ray_lds(f, sc.n_top);
 }
 // The work counters of a persistent launch: PT_SHARDS of them, a cache line apart, zero when the launch starts.
 constexpr size_t QUEUE_WORDS = PT_SHARDS * PT_SHARD_STRIDE, QUEUE_BYTES = QUEUE_WORDS * sizeof(unsigned int);
 inline hipError_t queue_reset(unsigned int* q, hipStream_t st) { return hipMemsetAsync(q, 0, QUEUE_BYTES, st); }
-// queue granularity: 64-slot chunks when the launch has plenty of them per resident wave, smaller ones for small launches (an
-// eighth of a 1080p frame per GPU is ~4 000 tiles for ~5 000 waves)
-inline int queue_chunk(const pt_ctx* c, uint64_t slots) {
-    const uint64_t waves = (uint64_t)c->n_cu * 20;
-    return slots / 64 >= 4 * waves ? 64 : (slots / 32 >= 4 * waves ? 32 : 16);
+inline void queue_params(const QueueKnobs& q, unsigned int* queue, KParams& P) {
+    P.queue = queue; P.batch = q.batch; P.refill = q.refill;
+    P.vote_node = q.vote_node; P.vote_rec = q.vote_rec;
 }
-inline void queue_params(const pt_ctx* c, unsigned int* queue, KParams& P) {
-    P.queue = queue; P.batch = c->opt_batch;
-    // refill <= batch, or a wave can spin: the walk returns at once because `batch` lanes wait,
-    // none of them has anything to shade and the idle ones are too few to trigger a refill
-    P.refill = std::min(c->opt_refill, c->opt_batch);
-    P.vote_node = c->opt_vote_node; P.vote_rec = c->opt_vote_rec;
-}
-// the sphere table of a persistent kernel's block (PT_OPT_SPHERE_LDS) behind what `lds` holds: its first word; `lds` grows by it
-inline int lds_sphere_table(size_t& lds) { lds += 15 * PT_KSPHERES * 4; return (int)(lds / 4) - 15 * PT_KSPHERES; }
 // PT_OPT_TIMING: the span pt_last_kernel_ms reads, around a call's launches on the caller's stream (HIP_TRY(c, span_begin(c)) ...);
 // the context counts as timed only once the end event is recorded
 inline hipError_t span_begin(pt_ctx* c) { return c->opt_timing ? hipEventRecord(c->ev0, c->stream) : hipSuccess; }
@@ -366,35 +326,15 @@ hipError_t launch_resident(K kernel, size_t lds, int max_per_cu, int n_cu, size_
 }
 
 // ---- launchers of the kernel families (one translation unit each) -------------------------------
-struct LaunchCfg {
-    bool count;        // instrumented instantiation (PT_OPT_COUNTERS)
-    int occ;           // waves per SIMD the registers are budgeted for
-    int lstk;          // LDS stack entries per lane (16, 24 or PT_STACK_CAP)
-    int walk;          // 0 while-while, 1 unified, 2 wide, 3 wide over Woop records, 4 wide + postponed leaf
-    size_t lds;        // dynamic LDS bytes of a block
-    int blocks;        // megakernel grid (one wave per work tile)
-    int work_blocks;   // persistent grid cap: blocks that have work at all
-    int n_cu;
-    bool moments;      // the call keeps luminance moments (pt_render_moments): they are the separate fold launch's job
-    int env;           // the context's environment map (env_code, pt_variants.h): ENV_NONE, ENV_LOOKUP, or ENV_LIGHT with PT_OPT_ENV_LIGHT's tables
-    bool nee, mis;     // the call has PT_FLAG_NEE; PT_FLAG_MIS: the instantiations that weigh shadow rays against bounce rays
-};
 hipError_t launch_mega(const LaunchCfg& L, const KParams& P, hipStream_t st);        // pt_k_mega.hip
 hipError_t launch_rays(const KScene& sc, size_t lds, const float4* rays, size_t n, int cull, float* t_out, int* tri_out,
                        float* n_out, hipStream_t st);                                 // pt_k_mega.hip
 hipError_t launch_persist(const LaunchCfg& L, const KParams& P, hipStream_t st);     // pt_k_persist.hip
 hipError_t launch_fold(const KParams& P, float2* moments, hipStream_t st);           // pt_k_persist.hip; moments: nullptr = none
-// stage-split pipeline (pt_k_wave.hip): generate -> depth x (extend, shade) ; returns PT_* status; folded = the samples are
-// already folded into the accumulator (PT_OPT_FUSE_STAGES), no launch_fold after it
-int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles, bool& folded);
-// samples of one pixel that share a wave at bounce 0 of the stage-split pipeline, as a power of two (wf_slot_pixel): the largest
-// 2^k <= PT_OPT_WAVE_SAMPLES, k >= 2, that divides spp; else 0 (one sample of a whole tile per wave, the other kernels' order)
-inline uint32_t wave_sample_group_log2(uint32_t spp, int cap) {
-    for (int k = 6; k >= 2; k--)
-        if ((1 << k) <= cap && (spp & ((1u << k) - 1u)) == 0u) return (uint32_t)k;
-    return 0u;
-}
-int wave_reserve(pt_ctx* c, const KParams& P, int work_tiles);   // path records for this call, allocated now
+// stage-split pipeline (pt_k_wave.hip): generate -> depth x (extend, shade), as plan.wave and plan.wl say; returns PT_* status.  The
+// samples are already folded into the accumulator when plan.wave.fold_lp != 0 (PT_OPT_FUSE_STAGES): no launch_fold after it
+int render_wavefront(pt_ctx* c, KParams& P, const CallPlan& plan);
+int wave_reserve(pt_ctx* c, const WaveLayout& w);   // makes sure the context holds the path records of layout w (a PT_KERNEL_AUTO trial: ahead of its timed span)
 // ray-batch queries over the tree on the context (pt_k_query.hip): pt_closest_hits (hit = nullptr) and pt_any_hits (hit given; t, tri and
 // normal unused).  Resets the work counters on the stream, then one launch: the wide walk on a resident grid, or the binary walk with
 // the bound applied to its answer when the tree is too deep for the wide one
@@ -407,7 +347,7 @@ struct QueryCall {
     float* normal;       // may be nullptr
     uint8_t* hit;
 };
-hipError_t launch_query(pt_ctx* c, const QueryCall& q);
+hipError_t launch_query(pt_ctx* c, const QueryPlan& plan, const QueryCall& q);
 // the path loop over a caller's rays (pt_k_rays.hip), one launch of pt_render_rays: the persistent grid over the (sample, ray) slots
 // that P and the batch describe, on the context's stream, and the fold of a launch's sample buffer into the running means
 struct RaysCall {

@@ -391,7 +391,7 @@ extern "C" int pt_render_aux(pt_ctx* c, const pt_camera* cam, const pt_params* p
     KParams P;
     std::memset(&P, 0, sizeof P);
     scene_view(c, P.sc, P.ksph);
-    const size_t lds = binary_ray_layout(c, P.sc);
+    const size_t lds = binary_ray_layout(ctx_facts(c), P.sc);
     P.cam = *cam;
     P.W = p->width; P.H = p->height;
     P.cull = p->cull_backfaces;

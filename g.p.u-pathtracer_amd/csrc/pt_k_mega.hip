@@ -89,7 +89,7 @@ namespace ptmi {
 
 // Instantiated: mega_exists; the request's word: mega_word (pt_variants.h).
 hipError_t launch_mega(const LaunchCfg& L, const KParams& P, hipStream_t st) {
-    return with_variant<mega_exists, PV_BITS>(mega_word(L.count, L.occ, L.lstk, L.walk, L.env, L.mis), [&](auto v) {
+    return with_variant<mega_exists, PV_BITS>(mega_word(L), [&](auto v) {
         const auto kernel = k_trace_mega_bvh2<pv_count(v()), v()>;
         const hipError_t e = allow_lds(kernel, L.lds);
         if (e != hipSuccess) return e;

@@ -252,7 +252,7 @@ namespace ptmi {
 
 // Instantiated: persist_exists; the request's word: persist_word (pt_variants.h).
 hipError_t launch_persist(const LaunchCfg& L, const KParams& P, hipStream_t st) {
-    return with_variant<persist_exists, PV_BITS>(persist_word(L.count, L.occ, L.lstk, L.walk, L.env), [&](auto v) {
+    return with_variant<persist_exists, PV_BITS>(persist_word(L), [&](auto v) {
         return launch_resident(k_trace_persist_bvh2<pv_count(v()), v()>, L.lds, INT_MAX, L.n_cu, (size_t)std::max(1, L.work_blocks), st, P);
     });
 }

@@ -9,7 +9,7 @@
 // the boxes beyond it are never opened.  A ray whose t_max is not greater than 0 (0, negative, NaN) writes its miss where it is
 // drawn and never becomes live.
 //
-// A tree too deep for the wide walk's stack (wide_walk_fits, pt_ctx.h: the rule of every call) takes k_query_rays_bvh2: the binary walk
+// A tree too deep for the wide walk's stack (wide_walk_fits, pt_plan.h: the rule of every call) takes k_query_rays_bvh2: the binary walk
 // of pt_trace_rays, unbounded, and the bound applied to its answer — the nearest hit inside (0, t_max) is the nearest hit when it
 // lies inside and nothing otherwise, so both kernels give the same results.
 #include <cstring>
@@ -182,7 +182,7 @@ __global__ void __launch_bounds__(PT_BLOCK_RAYS) k_query_rays_bvh2(const KQuery 
 
 namespace ptmi {
 
-hipError_t launch_query(pt_ctx* c, const QueryCall& q) {
+hipError_t launch_query(pt_ctx* c, const QueryPlan& plan, const QueryCall& q) {
     KQuery Q;
     std::memset(&Q, 0, sizeof Q);
     scene_view(c, Q.sc);
@@ -190,12 +190,13 @@ hipError_t launch_query(pt_ctx* c, const QueryCall& q) {
     Q.t_out = q.t; Q.tri_out = q.tri; Q.n_out = q.normal; Q.hit_out = q.hit;
     Q.queue = c->d_queue.get();   // the context's counters: every use is on the caller's stream, behind a reset of its own
     Q.n = (uint32_t)q.n;
-    Q.n_regions = (uint32_t)((q.n + PT_REGION - 1) / PT_REGION);
+    Q.n_regions = plan.n_regions;
     Q.cull = q.cull;
-    Q.batch = c->opt_wave_batch;
+    Q.batch = plan.batch;
     hipStream_t st = c->stream;
-    if (!wide_walk_fits(c->tree, PT_STACK_CAP)) {   // pt_trace_rays' launch
-        const size_t lds = binary_ray_layout(c, Q.sc);
+    if (!plan.wide) {   // pt_trace_rays' launch
+        Q.sc.stack_n = PT_STACK_CAP; Q.sc.top_base = 0; Q.sc.n_top = plan.n_top;
+        const size_t lds = plan.lds;
         const hipError_t e = allow_lds(k_query_rays_bvh2, lds);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_query_rays_bvh2, dim3((unsigned)((q.n + PT_BLOCK_RAYS - 1) / PT_BLOCK_RAYS)), dim3(PT_BLOCK_RAYS), lds, st, Q);
@@ -203,11 +204,9 @@ hipError_t launch_query(pt_ctx* c, const QueryCall& q) {
     }
     const hipError_t e = queue_reset(Q.queue, st);
     if (e != hipSuccess) return e;
-    // the extend stage's two budgets: (8 waves per SIMD, 16 stack entries in LDS), or (6, 24) under PT_OPT_LDS_STACK 24
-    return with_variant<query_exists, QV_BITS>(query_word(q.hit != nullptr, c->opt_lstk == 24), [&](auto v) {
-        constexpr int LSTK = budget_lstk(qv_budget(v()));
-        Q.sc.stack_n = LSTK;
-        return launch_resident(k_query_rays<v()>, (size_t)LSTK * PT_BLOCK * 4, c->opt_wave_blocks, c->n_cu, (size_t)Q.n_regions, st, Q);
+    return with_variant<query_exists, QV_BITS>(plan.word, [&](auto v) {
+        Q.sc.stack_n = budget_lstk(qv_budget(v()));
+        return launch_resident(k_query_rays<v()>, plan.lds, plan.blocks_per_cu, plan.n_cu, (size_t)Q.n_regions, st, Q);
     });
 }
 

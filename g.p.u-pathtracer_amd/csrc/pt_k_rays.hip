@@ -233,7 +233,7 @@ static KRays rays_args(const RaysCall& r) { return KRays{(const float4*)r.rays, 
 // PT_FLAG_NEE or over Woop records) is none that pt_render_rays lets through.
 hipError_t launch_render_rays(const LaunchCfg& L, const KParams& P, const RaysCall& r, hipStream_t st) {
     const KRays R = rays_args(r);
-    return with_variant<rays_exists, PV_BITS>(rays_word(L.walk, L.env, L.nee, L.mis), [&](auto v) {
+    return with_variant<rays_exists, PV_BITS>(rays_word(L), [&](auto v) {
         return launch_resident(k_render_rays<v()>, L.lds, INT_MAX, L.n_cu, (size_t)std::max(1, L.work_blocks), st, P, R);
     });
 }

@@ -20,7 +20,7 @@
 //              (tracer.cu:140-142), survivors are packed to the front of their region's next generation with
 //              a ballot + prefix count (v_mbcnt) — dead paths cost nothing in the next stage; survivors whose new ray
 //              the tree's root turns away are packed behind the others and never queued (PT_OPT_ROOT_CULL)
-//   PT_OPT_PATH_HISTORY (the default where it holds: path_history_holds, pt_ctx.h): the record carries which objects the path has
+//   PT_OPT_PATH_HISTORY (the default where it holds: path_history_holds, pt_plan.h): the record carries which objects the path has
 //              hit instead of its mask, the shade lane rebuilds mask and accu from that word, and the sample colour is written once,
 //              by the lane the path ends in — no write at bounce 0 for a path that goes on, no add in place
 //   k_fold_samples folds the sample colours into the running mean (tracer.cu:386-391), as for every kernel.
@@ -729,102 +729,11 @@ __global__ void __launch_bounds__(PT_BLOCK) k_wf_resolve(const KParams P) {
 
 namespace ptmi {
 
-// sizes of one call's path records: [ray0 x2][ray1 x2][mask x2 (3 planes; PT_OPT_PATH_HISTORY uses the first: the history words)][hit][cnt x2][walk x2][hashes][queues][shadow records]
-struct WaveLayout {
-    size_t n_regions, cap, b_ray, b_mask, b_hit, b_cnt, b_hash, q_words, b_q, b_nee, need;
-    bool nee;
-};
-
-// most RNG draws one bounce can make with these flags (path_shade_hit): DIFF 4, or 2 cosine-weighted (+ 3 for the light
-// sample of PT_FLAG_NEE), METAL 2, REFR 1, + 1 per roulette switch
-static uint32_t draws_per_bounce(uint32_t flags) {
-    uint32_t k = (flags & PT_FLAG_COSINE_DIFF) ? 2u : 4u;
-    if (flags & PT_FLAG_NEE) k += 3u;
-    if (flags & PT_FLAG_RUSSIAN_ROULETTE) k += 1u;
-    if (flags & PT_FLAG_RR_CPU_TRACER) k += 1u;
-    return k;
-}
-
-static int wave_layout(pt_ctx* c, const KParams& P, int work_tiles, WaveLayout& w) {
-    // limits of the record's packed fields (pt_kernels.h): the RNG draw count (2 camera draws + draws_per_bounce per bounce), the sample
-    if ((uint64_t)P.depth * draws_per_bounce(P.flags) + 2u >= PT_REC_MAX_DRAWS || P.spp >= PT_REC_MAX_SAMPLES)
-        return fail(c, PT_ERR_UNSUPPORTED, "pt_render: PT_KERNEL_WAVEFRONT packs < " + std::to_string(PT_REC_MAX_DRAWS) + " RNG draws per path (2 + depth x 4..9, by flags) and < " +
-                                           std::to_string(PT_REC_MAX_SAMPLES) + " samples per call into a path record");
-    w.n_regions = ((size_t)work_tiles + PT_REGION / 64 - 1) / (PT_REGION / 64);
-    w.cap = w.n_regions * PT_REGION;
-    if (w.cap >= (1ull << 31)) return fail(c, PT_ERR_INVALID, "pt_render: too many path records for one call");
-    w.b_ray = w.cap * 16; w.b_mask = w.cap * 12; w.b_hit = w.cap * 8; w.b_cnt = ((w.n_regions * 4 + 255) / 256) * 256;
-    w.b_hash = (((size_t)P.spp * 8 + 255) / 256) * 256;
-    w.nee = (P.flags & PT_FLAG_NEE) != 0;
-    if (w.nee && P.spp >= PT_REC_MAX_SAMPLES_NEE) return fail(c, PT_ERR_UNSUPPORTED, "pt_render: PT_FLAG_NEE in the stage-split pipeline packs < " + std::to_string(PT_REC_MAX_SAMPLES_NEE) + " samples per call into a path record");
-    w.q_words = (size_t)P.depth * (w.nee ? 2 : 1) * PT_SHARDS * PT_SHARD_STRIDE;   // one set of queue counters per extend launch
-    w.b_q = w.q_words * 4;
-    w.b_nee = w.nee ? 3 * w.b_ray + w.b_hit + w.b_cnt : 0;   // shadow records: s_ray0, s_ray1, s_con, s_hit, s_cnt
-    w.need = 4 * w.b_ray + 2 * w.b_mask + w.b_hit + 4 * w.b_cnt + w.b_hash + w.b_q + w.b_nee;
-    return PT_OK;
-}
-
-// makes sure the context holds the path records of layout w
-static int wave_reserve(pt_ctx* c, const WaveLayout& w) {
+// makes sure the context holds the path records of layout w (plan_wave_layout, pt_plan.h)
+int wave_reserve(pt_ctx* c, const WaveLayout& w) {
     if (w.need > c->d_wave.count()) HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, c->d_wave.reserve(w.need));
     return PT_OK;
-}
-
-// the same for this call (PT_KERNEL_AUTO calls it ahead of the timed span of its trial)
-int wave_reserve(pt_ctx* c, const KParams& P, int work_tiles) {
-    WaveLayout w;
-    const int rc = wave_layout(c, P, work_tiles, w);
-    return rc != PT_OK ? rc : wave_reserve(c, w);
-}
-
-// c->d_wave carved by layout w: the two generations of every piece (bounce b reads [b & 1] and writes the other)
-struct WaveBuffers {
-    float4 *ray0[2], *ray1[2];
-    float* mask[2];
-    float2* hit;
-    int* cnt[2];
-    int* walk[2];   // the records at the front of every region that the extend launch walks (PT_OPT_ROOT_CULL; = cnt without it)
-    unsigned long long* hashes;   // then the queue counters of every extend launch
-    unsigned int* queues;
-    char* nee;   // the shadow records (PT_FLAG_NEE): s_ray0, s_ray1, s_con, s_hit, s_cnt
-};
-static WaveBuffers wave_carve(char* base, const WaveLayout& w) {
-    WaveBuffers b;
-    for (int g = 0; g < 2; g++) {
-        b.ray0[g] = (float4*)(base + g * w.b_ray);
-        b.ray1[g] = (float4*)(base + (2 + g) * w.b_ray);
-        b.mask[g] = (float*)(base + 4 * w.b_ray + g * w.b_mask);
-    }
-    base += 4 * w.b_ray + 2 * w.b_mask;
-    b.hit = (float2*)base;
-    base += w.b_hit;
-    b.cnt[0] = (int*)base;
-    b.cnt[1] = (int*)(base + w.b_cnt);
-    b.walk[0] = (int*)(base + 2 * w.b_cnt);
-    b.walk[1] = (int*)(base + 3 * w.b_cnt);
-    base += 4 * w.b_cnt;
-    b.hashes = (unsigned long long*)base;
-    base += w.b_hash;
-    b.queues = (unsigned int*)base;
-    b.nee = base + w.b_q;
-    return b;
-}
-
-// What one call launches, decided once: WavePlan (pt_variants.h), from what the context, the call and the tree say
-static WavePlan wave_plan(const pt_ctx* c, const KParams& P, const LaunchCfg& L, bool nee) {
-    WaveRequest r = {};
-    r.count = L.count; r.nee = nee; r.deep_stack = L.lstk == 24; r.moments = L.moments;
-    r.packet = c->opt_first_walk == 1 && wide_walk_fits(c->tree, c->opt_packet_stack);
-    const bool tri_dark = P.tri_emi[0] == 0.f && P.tri_emi[1] == 0.f && P.tri_emi[2] == 0.f;
-    r.anyhit_scene = !P.tri_matid && tri_dark && P.sc.n_spheres <= PT_KSPHERES && !c->tree.records_woop;
-    r.history_holds = path_history_holds(P);
-    r.tree_has_occluders = c->tree.n_occ > 0;
-    r.spp_fits_entry = P.spp < PT_REC_MAX_SAMPLES_ENTRY;
-    r.fuse_stages = c->opt_fuse_stages; r.last_anyhit = c->opt_last_anyhit; r.root_cull = c->opt_root_cull; r.root_entry = c->opt_root_entry;
-    r.path_history = c->opt_path_history; r.last_occluders = c->opt_last_occluders;
-    r.depth = P.depth; r.spp = P.spp; r.sgroup_log2 = P.sgroup_log2;
-    return wave_plan_of(r);
 }
 
 constexpr size_t WF_LDS_SHADE = (15 * PT_KSPHERES + 6) * 4;   // wf_sphere_table, with the triangle material's row
@@ -864,37 +773,36 @@ static hipError_t launch_shade(const WavePlan& p, WaveShade kind, bool first, co
     return with_variant<shade_exists, WS_BITS>(shade_word(p, kind, first), [&](auto v) { return launch_regions(k_wf_shade<ws_count(v()), v()>, n_reg, WF_LDS_SHADE, Q, s); });
 }
 
-int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles, bool& folded) {
-    folded = false;
-    WaveLayout w;
-    int rc = wave_layout(c, P, work_tiles, w);
-    if (rc == PT_OK) rc = wave_reserve(c, w);
+int render_wavefront(pt_ctx* c, KParams& P, const CallPlan& call) {
+    const WaveLayout& w = call.wl;
+    const WavePlan& plan = call.wave;
+    const LaunchCfg& L = call.L;
+    const int rc = wave_reserve(c, w);
     if (rc != PT_OK) return rc;
-    const WaveBuffers buf = wave_carve(c->d_wave.get(), w);
-    const WavePlan plan = wave_plan(c, P, L, w.nee);
-    folded = plan.fold_lp != 0;
+    char* const base = c->d_wave.get();   // the pieces of the layout: base + w.off[piece], the second generation of a piece at piece + 1
     P.wf.nee = w.nee ? 1 : 0;
     P.wf.root_cull = plan.root_cull ? 1 : 0;
     P.wf.root_entry = plan.root_entry ? 1 : 0;
     if (w.nee) {
-        P.wf.s_ray0 = (float4*)buf.nee;
-        P.wf.s_ray1 = (float4*)(buf.nee + w.b_ray);
-        P.wf.s_con = (float4*)(buf.nee + 2 * w.b_ray);
-        P.wf.s_hit = (float2*)(buf.nee + 3 * w.b_ray);
-        P.wf.s_cnt = (int*)(buf.nee + 3 * w.b_ray + w.b_hit);
+        P.wf.s_ray0 = (float4*)(base + w.off[W_S_RAY0]);
+        P.wf.s_ray1 = (float4*)(base + w.off[W_S_RAY1]);
+        P.wf.s_con = (float4*)(base + w.off[W_S_CON]);
+        P.wf.s_hit = (float2*)(base + w.off[W_S_HIT]);
+        P.wf.s_cnt = (int*)(base + w.off[W_S_CNT]);
     } else P.wf.s_con = plan.occluders ? c->d_occ.get() : nullptr;   // (the table of the tree on the context: occluders_collect)
+    unsigned int* const queues = (unsigned int*)(base + w.off[W_QUEUES]);
 
     hipStream_t st = c->stream;
     P.sc.n_top = 0;
     P.sph_tab = 0;
-    P.batch = c->opt_wave_batch;
-    P.wf.hit = buf.hit;
-    P.wf.hashes = buf.hashes;
-    P.wf.queues_all = buf.queues;
+    P.batch = call.wave_batch;
+    P.wf.hit = (float2*)(base + w.off[W_HIT]);
+    P.wf.hashes = (unsigned long long*)(base + w.off[W_HASHES]);
+    P.wf.queues_all = queues;
     P.wf.queues_words = (uint32_t)w.q_words;
     P.wf.cap = (uint32_t)w.cap;
     P.wf.n_regions = (int)w.n_regions;
-    P.wf.n_slots = (uint32_t)((size_t)work_tiles * 64);
+    P.wf.n_slots = (uint32_t)((size_t)call.work_tiles * 64);
     P.wf.bounce = 0;
     hipLaunchKernelGGL(k_wf_prepare, dim3(1), dim3(256), 0, st, P);
     HIP_TRY(c, hipGetLastError());
@@ -903,10 +811,13 @@ int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles, 
     for (uint32_t b = 0; b < P.depth; b++) {
         const int g = (int)(b & 1u);
         P.wf.bounce = b;
-        P.wf.ray0_in = buf.ray0[g]; P.wf.ray1_in = buf.ray1[g]; P.wf.mask_in = buf.mask[g]; P.wf.cnt_in = buf.cnt[g]; P.wf.walk_in = buf.walk[g];
-        P.wf.ray0_out = buf.ray0[g ^ 1]; P.wf.ray1_out = buf.ray1[g ^ 1]; P.wf.mask_out = buf.mask[g ^ 1]; P.wf.cnt_out = buf.cnt[g ^ 1]; P.wf.walk_out = buf.walk[g ^ 1];
-        P.wf.queue = buf.queues + (size_t)b * PT_SHARDS * PT_SHARD_STRIDE;
-        HIP_TRY(c, launch_extend(plan, plan.extend(b, P.depth), P, L, c->opt_wave_blocks, st));   // (EXT_FUSED: walk + shade, booked as extend)
+        const int o = g ^ 1;   // bounce b reads generation g and writes the other
+        P.wf.ray0_in = (float4*)(base + w.off[W_RAY0 + g]); P.wf.ray1_in = (float4*)(base + w.off[W_RAY1 + g]); P.wf.mask_in = (float*)(base + w.off[W_MASK + g]);
+        P.wf.cnt_in = (int*)(base + w.off[W_CNT + g]); P.wf.walk_in = (int*)(base + w.off[W_WALK + g]);   // (walk: the records at the front of every region that the extend launch walks)
+        P.wf.ray0_out = (float4*)(base + w.off[W_RAY0 + o]); P.wf.ray1_out = (float4*)(base + w.off[W_RAY1 + o]); P.wf.mask_out = (float*)(base + w.off[W_MASK + o]);
+        P.wf.cnt_out = (int*)(base + w.off[W_CNT + o]); P.wf.walk_out = (int*)(base + w.off[W_WALK + o]);
+        P.wf.queue = queues + (size_t)b * PT_SHARDS * PT_SHARD_STRIDE;
+        HIP_TRY(c, launch_extend(plan, plan.extend(b, P.depth), P, L, call.wave_blocks, st));   // (EXT_FUSED: walk + shade, booked as extend)
         if (stage_mark(c, PT_STAGE_EXTEND) != PT_OK) return PT_ERR_DEVICE;
         const WaveShade shade = plan.shade(b, P.depth);
         if (shade == SHADE_NONE) continue;
@@ -915,8 +826,8 @@ int render_wavefront(pt_ctx* c, KParams& P, const LaunchCfg& L, int work_tiles, 
         if (w.nee) {   // this bounce's shadow rays: the closest-hit extend kernel over the shadow records, then the resolve
             KParams S = P;
             S.wf.ray0_in = P.wf.s_ray0; S.wf.ray1_in = P.wf.s_ray1; S.wf.cnt_in = S.wf.walk_in = P.wf.s_cnt; S.wf.hit = P.wf.s_hit;   // (every shadow ray is walked)
-            S.wf.queue = buf.queues + ((size_t)P.depth + b) * PT_SHARDS * PT_SHARD_STRIDE;
-            HIP_TRY(c, launch_extend(plan, EXT_CLOSEST, S, L, c->opt_wave_blocks, st));
+            S.wf.queue = queues + ((size_t)P.depth + b) * PT_SHARDS * PT_SHARD_STRIDE;
+            HIP_TRY(c, launch_extend(plan, EXT_CLOSEST, S, L, call.wave_blocks, st));
             if (stage_mark(c, PT_STAGE_EXTEND) != PT_OK) return PT_ERR_DEVICE;
             hipLaunchKernelGGL(k_wf_resolve, dim3((unsigned)w.n_regions), dim3(PT_BLOCK), 0, st, P);
             HIP_TRY(c, hipGetLastError());

@@ -11,16 +11,6 @@
 #include "pt_variants.h"
 #include "../../include/ptmi.h"
 
-#define PT_BLOCK 256          // frame kernels: 4 waves; one wave = one 8x8 pixel tile
-#define PT_BLOCK_RAYS 256     // ray-batch kernel
-#define PT_TILE 8
-#define PT_MAX_TOP 1024       // most nodes the LDS copy of the top of the tree may hold
-#define PT_STACK_CAP 72       // deepest traversal stack (tree depth <= 64, SplitBVHBuilder MaxDepth)
-static_assert(budget_lstk(BUDGET_4x72) == PT_STACK_CAP, "the budget with the whole stack in LDS");
-#define PT_SHARDS 8           // work-queue counters (one per XCD worth of blocks)
-#define PT_SHARD_STRIDE 32    // uints between counters: one 128-byte line each
-#define PT_REGION 256         // stage-split pipeline: path-record slots per region (= one block)
-
 struct KScene {
     // One buffer of 64-byte items (4 float4 each): inner nodes first, then triangle records
     //   node: [c0.lo.x c0.hi.x c0.lo.y c0.hi.y][c1 ...][c0.lo.z c0.hi.z c1.lo.z c1.hi.z][link0 link1 0 0]
@@ -37,8 +27,6 @@ struct KScene {
     int wide_root; // float4 index of the 4-wide quantised tree's root (= its node 0), 0 if absent
 };
 
-#define PT_KSPHERES 8   // spheres carried in the kernel-argument block (scalar loads); more -> global array
-
 // Stage-split (wavefront) pipeline, pt_k_wave.hip: one generation of path records in HBM.  A record lives
 // in slot i of its REGION (256 consecutive slots = one block of the generate / shade stages); a region's live
 // records are packed at its front and counted in cnt[region], so compaction never leaves the block
@@ -50,18 +38,10 @@ struct KScene {
 //             (PT_OPT_PATH_HISTORY: plane 0 = the path's history word, below; the sample colour is then written once, where the path ends)
 //   hit[i]  = (t, bits(float4 index of the winning record)); t = F32_MAX: no triangle
 // PT_FLAG_NEE: the sphere bits of nee_mask ride above the pixel (ray1.z), its triangle-light bit above the sample (ray1.w).
-// The stages of pt_k_wave.hip pack and unpack the record with these; the limits wave_layout and pt_render check follow from them:
-constexpr uint32_t PT_REC_DRAW_BITS = 12;    // ray1.w: RNG draws of the path so far, below the sample number
-constexpr uint32_t PT_REC_LIGHT_BIT = 31;    // ray1.w, PT_FLAG_NEE: nee_mask bit 8 (the triangle lights)
-constexpr uint32_t PT_REC_PIXEL_BITS = 24;   // ray1.z, PT_FLAG_NEE: the pixel, below nee_mask bits 0-7 (the spheres)
-// exclusive limits: draws per path, samples per call without / with PT_FLAG_NEE
-constexpr uint32_t PT_REC_MAX_DRAWS = 1u << PT_REC_DRAW_BITS, PT_REC_MAX_SAMPLES = 1u << (32 - PT_REC_DRAW_BITS),
-                   PT_REC_MAX_SAMPLES_NEE = 1u << (PT_REC_LIGHT_BIT - PT_REC_DRAW_BITS);
+// The stages of pt_k_wave.hip pack and unpack the record with the PT_REC_* field widths of pt_variants.h.
 // PT_OPT_ROOT_ENTRY (KWave::root_entry; never with PT_FLAG_NEE): the top PT_REC_ENTRY_BITS of ray1.w hold the walker's ENTRY CODE, what the
 // walk's node step on the tree's root found for the record's ray — the shade lane that made the ray ran that step (PT_OPT_ROOT_CULL) —
 // and the sample number keeps the bits between.  A call whose spp does not fit them keeps the format above.
-constexpr uint32_t PT_REC_ENTRY_BITS = 8, PT_REC_ENTRY_SHIFT = 32 - PT_REC_ENTRY_BITS;
-constexpr uint32_t PT_REC_MAX_SAMPLES_ENTRY = 1u << (PT_REC_ENTRY_SHIFT - PT_REC_DRAW_BITS);   // exclusive, as the limits above
 // The entry code: the root's hit children nearest first, as wide_sort4 orders them — three 2-bit child numbers below (hit children - 1).
 // A walker has 1..4 hit children; with four the last one is the XOR of the other three (0 ^ 1 ^ 2 ^ 3 = 0).  The fields of children
 // that are not hit are not read.
@@ -98,7 +78,6 @@ static_assert(pt_entry_round_trips(), "the entry code of PT_OPT_ROOT_ENTRY");
 // neither read nor written.  The word has PT_HIST_BITS per finished bounce, bounce b's at bits 4b .. 4b + 3: the code of the object that
 // bounce ended on, 0-7 = sphere k (of the kernel-argument block), PT_HIST_TRI = a triangle (the call's one triangle material).  32 bits
 // hold the 8 bounces a path of depth 9 survives.  Mask and gathered light are functions of it (wf_history_replay, pt_k_wave.hip).
-constexpr uint32_t PT_HIST_BITS = 4, PT_HIST_TRI = 8, PT_HIST_MAX_DEPTH = 32 / PT_HIST_BITS + 1;
 constexpr uint32_t pt_hist_push(uint32_t word, uint32_t bounce, uint32_t code) { return word | (code << (PT_HIST_BITS * bounce)); }
 constexpr uint32_t pt_hist_code(uint32_t word, uint32_t bounce) { return (word >> (PT_HIST_BITS * bounce)) & ((1u << PT_HIST_BITS) - 1u); }
 // every code comes back from every bounce's field, whatever the other fields hold, and the lower fields stay what they were
@@ -195,7 +174,7 @@ struct KParams {
     KWave wf;
 };
 // The environment map of pt_upload_environment (KEnv, pt_env.h) rides in KParams WITHOUT making it larger: it is laid over the first
-// bytes of `wf`.  A call runs either the stage-split pipeline, which reads wf and never a map (plan_call: a context with a map does
+// bytes of `wf`.  A call runs either the stage-split pipeline, which reads wf and never a map (plan_walk, pt_plan.h: a context with a map does
 // not choose it), or a kernel that shades in the lane that walked, which reads the map (texels == nullptr: none, bk_color) and
 // never wf.  fill_path_params zeroes the block and copies the map in (pt_set_env); only render_wavefront writes wf.  So the size
 // of KParams, the offset of every kernel's second argument and the instruction streams of the pipeline's kernels are what they

@@ -163,7 +163,7 @@ __device__ __forceinline__ float pt_mis_bounce_weight(float pb, float pk, float 
 // ENV: a segment that hits nothing looks the context's environment map up along its direction when one is set
 // (pt_upload_environment, pt_env.h) — the ENV instantiations of the kernels that shade in the lane that walked (path_shade), which
 // the launchers pick when the context has a map (shade_env, pt_variants.h).  The stage-split pipeline's shade stage keeps ENV_NONE: it never
-// runs with a map on the context (plan_call).  ENV_NONE compiles to the code there was before maps existed, ENV_LOOKUP to the lookup in the
+// runs with a map on the context (plan_walk, pt_plan.h).  ENV_NONE compiles to the code there was before maps existed, ENV_LOOKUP to the lookup in the
 // miss branch alone; ENV_LIGHT, for a map with sampling tables (PT_OPT_ENV_LIGHT), also draws from them in the NEE branch: the kernels that run NEE
 // with a map have that instantiation beside the other two, so that a map that is no light costs what it did.
 // MIS (PT_FLAG_MIS, include/ptmi.h "Multiple importance sampling"): the balance heuristic between the shadow ray and the bounce ray of a

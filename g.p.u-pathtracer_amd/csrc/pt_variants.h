@@ -28,6 +28,30 @@ constexpr int BUDGET_BITS = 3;
 constexpr int budget_occ(uint32_t b) { return b == BUDGET_8x16 ? 8 : (b == BUDGET_6x16 || b == BUDGET_6x24) ? 6 : 4; }
 constexpr int budget_lstk(uint32_t b) { return b == BUDGET_4x72 ? 72 : b == BUDGET_6x24 ? 24 : 16; }
 
+// ---- the sizes the kernels and the host's planning (pt_plan.h) share
+#define PT_BLOCK 256          // frame kernels: 4 waves; one wave = one 8x8 pixel tile
+#define PT_BLOCK_RAYS 256     // ray-batch kernel
+#define PT_TILE 8
+#define PT_MAX_TOP 1024       // most nodes the LDS copy of the top of the tree may hold
+#define PT_STACK_CAP 72       // deepest traversal stack (tree depth <= 64, SplitBVHBuilder MaxDepth)
+static_assert(budget_lstk(BUDGET_4x72) == PT_STACK_CAP, "the budget with the whole stack in LDS");
+#define PT_SHARDS 8           // work-queue counters (one per XCD worth of blocks)
+#define PT_SHARD_STRIDE 32    // uints between counters: one 128-byte line each
+#define PT_REGION 256         // stage-split pipeline: path-record slots per region (= one block)
+#define PT_KSPHERES 8         // spheres carried in the kernel-argument block (scalar loads); more -> global array
+// the packed fields of the pipeline's path record (pt_kernels.h) and the limits plan_wave_layout (pt_plan.h) derives from them
+constexpr uint32_t PT_REC_DRAW_BITS = 12;    // ray1.w: RNG draws of the path so far, below the sample number
+constexpr uint32_t PT_REC_LIGHT_BIT = 31;    // ray1.w, PT_FLAG_NEE: nee_mask bit 8 (the triangle lights)
+constexpr uint32_t PT_REC_PIXEL_BITS = 24;   // ray1.z, PT_FLAG_NEE: the pixel, below nee_mask bits 0-7 (the spheres)
+// exclusive limits: draws per path, samples per call without / with PT_FLAG_NEE
+constexpr uint32_t PT_REC_MAX_DRAWS = 1u << PT_REC_DRAW_BITS, PT_REC_MAX_SAMPLES = 1u << (32 - PT_REC_DRAW_BITS),
+                   PT_REC_MAX_SAMPLES_NEE = 1u << (PT_REC_LIGHT_BIT - PT_REC_DRAW_BITS);
+// PT_OPT_ROOT_ENTRY: the top bits of ray1.w hold the walker's entry code (pt_kernels.h), the sample number keeps the bits between
+constexpr uint32_t PT_REC_ENTRY_BITS = 8, PT_REC_ENTRY_SHIFT = 32 - PT_REC_ENTRY_BITS;
+constexpr uint32_t PT_REC_MAX_SAMPLES_ENTRY = 1u << (PT_REC_ENTRY_SHIFT - PT_REC_DRAW_BITS);   // exclusive, as the limits above
+// PT_OPT_PATH_HISTORY: bits per finished bounce in the history word, a triangle's code, the deepest call the word serves (pt_kernels.h)
+constexpr uint32_t PT_HIST_BITS = 4, PT_HIST_TRI = 8, PT_HIST_MAX_DEPTH = 32 / PT_HIST_BITS + 1;
+
 // ---- the walk a path kernel runs (LaunchCfg::walk, the kernels' ALG) and what its miss and NEE branches do with the context's map (ENV)
 enum { ALG_WHILE = 0, ALG_UNIFIED = 1, ALG_WIDE = 2, ALG_WIDE_WOOP = 3, ALG_WIDE_PEND = 4 };
 enum { ENV_NONE = 0, ENV_LOOKUP = 1, ENV_LIGHT = 2 };   // no map; a miss looks the map up; ... and PT_FLAG_NEE draws from its tables
@@ -116,7 +140,7 @@ constexpr uint32_t rays_word(int walk, int map, bool nee, bool mis) {   // (it h
 }
 static_assert(variant_count(rays_exists, PV_BITS) == 19, "k_render_rays: 3 walks x (2 + 3 maps) + 2 walks x 2 under MIS");
 
-// The kernel family of a path call, from the one the option, PT_FLAG_MIS or PT_KERNEL_AUTO's table asks for (plan_call): shadow rays
+// The kernel family of a path call, from the one the option, PT_FLAG_MIS or PT_KERNEL_AUTO's table asks for (plan_family, pt_plan.h): shadow rays
 // have a stage in the pipeline (the pixel rides below nee_mask in the record, so it must fit) and a loop in the megakernel, nothing in
 // the persistent kernel; the pipeline runs where it can (wave_ok), the megakernel does not read Woop records.
 constexpr int path_kernel(int kernel, int walk, bool wave_ok, bool nee, bool pixels_fit) {
@@ -187,7 +211,7 @@ struct WaveRequest {
     bool count, nee, deep_stack, moments;   // PT_OPT_COUNTERS; PT_FLAG_NEE; PT_OPT_LDS_STACK 24; pt_render_moments
     bool packet;           // PT_OPT_FIRST_WALK 1 and the tree fits the packet stack budget
     bool anyhit_scene;     // no triangle can emit, one triangle material, the spheres fit the kernel arguments, exact records
-    bool history_holds;    // path_history_holds (pt_ctx.h); never with PT_FLAG_NEE
+    bool history_holds;    // path_history_holds (pt_plan.h); never with PT_FLAG_NEE
     bool tree_has_occluders;
     bool spp_fits_entry;   // spp < PT_REC_MAX_SAMPLES_ENTRY
     int fuse_stages, last_anyhit, root_cull, root_entry, path_history, last_occluders;   // the options' values

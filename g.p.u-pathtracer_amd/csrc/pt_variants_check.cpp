@@ -1,13 +1,18 @@
-// pt_variants_check.cpp — every request has a kernel and every kernel a request: a CPU program with its own main, no HIP library
-// (`make variants_check`, SAN=1 for the address and undefined-behaviour sanitizers; tests/test_variants.py runs both).
-// It loops over everything plan_call, wave_plan and pt_render_rays (ptmi.hip, pt_k_wave.hip) can hand the request functions of
-// pt_variants.h, asserts that each resulting word satisfies its family's _exists — with_variant (pt_ctx.h) would answer
-// hipErrorInvalidValue for any other — and, the other way round, that every word that exists came out of some request.
+// pt_variants_check.cpp — every request has a kernel and every kernel a request, and every plan is sound: a CPU program with its own
+// main, no HIP library (`make variants_check`, SAN=1 for the address and undefined-behaviour sanitizers; tests/test_variants.py runs both).
+// It RUNS the planner (pt_plan.h: the functions pt_render, pt_render_rays and the ray-batch queries call) over a domain of scenes x
+// options x calls x the runtime's answers, and holds no rule of its own: a call is skipped because the planner refused it, and the
+// refusal's code has to be the one REFUSALS lists for its text.  Of every plan it asserts what follows from the project's constants
+// (LDS, refill <= batch, grids, the record layout); of every variant word a plan asks a launcher for, that the word is instantiated —
+// with_variant (pt_ctx.h) would answer hipErrorInvalidValue for any other — and, the other way round, that every instantiated word
+// came out of some plan.
 #include <cstdio>
+#include <initializer_list>
 #include <set>
 #include <vector>
 
-#include "pt_variants.h"
+#include "pt_plan.h"
+using namespace ptmi;
 
 static int n_failed = 0;
 #define CHECK(cond)                                                             \
@@ -38,87 +43,335 @@ struct Family {
         std::printf("%-26s %9ld requests, %3d distinct words, %3d kernels\n", name, requests, words, variant_count(exists, n_bits));
     }
 };
+static Family mega{"k_trace_mega_bvh2", mega_exists, PV_BITS}, persist{"k_trace_persist_bvh2", persist_exists, PV_BITS},
+    rays{"k_render_rays", rays_exists, PV_BITS}, query{"k_query_rays", query_exists, QV_BITS}, extend{"k_wf_extend", extend_exists, WX_BITS},
+    shade{"k_wf_shade", shade_exists, WS_BITS}, last_any{"k_wf_shade_last_any", shade_last_any_exists, WS_BITS},
+    fused{"k_wf_extend_packet_shade", fused_exists, WS_BITS};
+
+// the refusals the planner knows, by a piece of their text, with the code each one answers; every one of them is met below
+static struct { const char* text; int code; long seen; } REFUSALS[] = {
+    {": no scene uploaded", PT_ERR_NO_SCENE, 0}, {": null argument", PT_ERR_INVALID, 0}, {"image must be at least 2x2", PT_ERR_INVALID, 0},
+    {"spp must be >= 1", PT_ERR_INVALID, 0}, {"mode must be PT_RAYS_CLAMPED or PT_RAYS_HDR", PT_ERR_INVALID, 0}, {"more than 2^32 - 1 rays", PT_ERR_INVALID, 0},
+    {" starts at 1", PT_ERR_INVALID, 0}, {": bad triangle material", PT_ERR_INVALID, 0}, {"PT_FLAG_WRITE_RGBA needs rgba_dev", PT_ERR_INVALID, 0},
+    {"PT_FLAG_NEE needs PT_FLAG_COSINE_DIFF", PT_ERR_INVALID, 0}, {"PT_FLAG_MIS needs PT_FLAG_NEE", PT_ERR_INVALID, 0},
+    {"part_index out of range", PT_ERR_INVALID, 0}, {"part_rows must be a positive multiple of 8", PT_ERR_INVALID, 0},
+    {"width*height*spp too large for one call", PT_ERR_INVALID, 0}, {"too many path records for one call", PT_ERR_INVALID, 0},
+    {"PT_FLAG_NEE over emissive triangles needs the exact", PT_ERR_UNSUPPORTED, 0}, {"Woop records need the wide walk", PT_ERR_UNSUPPORTED, 0},
+    {"PT_FLAG_MIS needs the exact", PT_ERR_UNSUPPORTED, 0}, {"RNG draws per path", PT_ERR_UNSUPPORTED, 0},
+    {"PT_FLAG_NEE in the stage-split pipeline packs", PT_ERR_UNSUPPORTED, 0},
+};
+static long n_refused = 0, n_planned = 0;
+// true: the planner refused the call or found nothing to do in it
+static bool turned_away(const Refusal& r) {
+    if (r.code == PT_OK) return r.nothing;
+    n_refused++;
+    int rows = 0;
+    for (auto& e : REFUSALS)
+        if (r.msg.find(e.text) != std::string::npos) { rows++; e.seen++; CHECK(r.code == e.code); }
+    if (rows != 1 && n_failed++ < 20) std::printf("FAILED: the refusal \"%s\" matches %d rows of REFUSALS\n", r.msg.c_str(), rows);
+    return true;
+}
+
+// ---- the domain: scenes
+struct Tree { bool has_bvh, woop; uint32_t wide_depth, n_occ; };
+static const Tree NO_TREE = {false, false, 0, 0}, TREE = {true, false, 10, 0}, TREE_OCC = {true, false, 10, 3}, TREE_WOOP = {true, true, 10, 0},
+                  TREE_23 = {true, false, 23, 0},   // 3 x 23 + 2 = 71 entries: the wide walk's stack holds it, a packet stack of 40 does not
+                  TREE_DEEP = {true, false, 24, 2}, TREE_WOOP_DEEP = {true, true, 24, 0};
+static const Tree TREES[] = {NO_TREE, TREE, TREE_OCC, TREE_WOOP, TREE_23, TREE_DEEP, TREE_WOOP_DEEP};
+struct Spheres { int n; bool refr; };   // refr: one of the first PT_KSPHERES is PT_MAT_REFR
+static const Spheres SPHERES[] = {{0, false}, {3, false}, {9, false}, {8, true}, {20, true}};
+struct Mats { bool table, emits; };
+static const Mats MATS[] = {{false, false}, {true, false}, {true, true}};
+
+// a new context's options (pt_ctx.h) over the scene
+static CtxFacts scene(const Tree& t, const Spheres& s, const Mats& m, int env) {
+    CtxFacts f = {};
+    f.has_bvh = t.has_bvh; f.records_woop = t.woop; f.wide_depth = t.wide_depth; f.n_occ = t.n_occ;
+    f.n_top_layout = t.has_bvh ? 100 : 0; f.wide_top_layout = t.has_bvh ? 40 : 0;
+    f.n_spheres = s.n;
+    for (int i = 0; i < PT_KSPHERES && i < s.n; i++) f.sphere_mat[i] = i == 1 && s.refr ? PT_MAT_REFR : PT_MAT_DIFF + i % 3;
+    f.mat_table = m.table; f.tri_emits = m.emits;
+    f.env = env; f.n_cu = 256;
+    f.kernel = PT_KERNEL_AUTO; f.overlap = 1; f.sph_lds = 1; f.top = 64; f.occ = 6; f.lstk = 16; f.walk = 2; f.batch = 36; f.refill = 8;
+    f.vote_node = f.vote_rec = 1; f.wave_batch = 16; f.wave_samples = 16; f.wave_blocks = 8; f.first_walk = 1; f.packet_stack = 72;
+    f.fuse_stages = f.last_anyhit = f.root_cull = f.root_entry = f.last_occluders = f.path_history = 1;
+    return f;
+}
+static pt_params params(int w, int h, uint32_t depth, uint32_t flags) {
+    pt_params p = {};
+    p.width = w; p.height = h; p.depth = depth; p.flags = flags;
+    p.sample_index = 1; p.tri_mat = PT_MAT_DIFF;
+    return p;
+}
+static CallFacts frame(const pt_params& p, uint32_t spp, bool moments = false) { return {true, &p, spp, true, true, moments, 0, 0}; }
+
+// ---- pt_render: the steps in pt_render_moments' order.  One frame call under given answers of the runtime; false: turned away
+static bool frame_call(const CtxFacts& f, const CallFacts& a, const AutoAnswer& au, bool caller_idle, CallPlan& plan) {
+    if (turned_away(check_path_call(f, a)) || turned_away(tri_lights_rule(f, a.p->flags))) return false;
+    TileGrid g;
+    if (turned_away(frame_tiles(*a.p, a.spp, g)) || turned_away(plan_walk(f, a, plan))) return false;
+    plan_family(f, a, au, plan);
+    return !turned_away(plan_launch(f, a, g.n_tiles, caller_idle, plan));
+}
+static std::set<int> wave_calls;   // (count, nee, deep stack, moments) of the calls that run the pipeline
+// what holds of every plan, and the words its launches ask for
+static void frame_plan(const CtxFacts& f, const CallFacts& a, const CallPlan& plan) {
+    const LaunchCfg& L = plan.L;
+    n_planned++;
+    CHECK(L.lds <= PT_LDS_BYTES && plan.q.refill <= plan.q.batch && L.work_blocks >= 1 && L.blocks >= 1 && plan.work_tiles >= 1);
+    CHECK(plan.chunk == 16 || plan.chunk == 32 || plan.chunk == 64);
+    CHECK(plan.sph_tab < 0 || (size_t)(plan.sph_tab + 15 * PT_KSPHERES) * 4 == L.lds);
+    CHECK(!plan.side || (plan.samples && plan.probe < 0));
+    if (plan.kernel == PT_KERNEL_MEGA_BVH2) mega.request(mega_word(L));
+    else if (plan.kernel == PT_KERNEL_PERSISTENT) persist.request(persist_word(L));
+    if (plan.kernel != PT_KERNEL_WAVEFRONT) {
+        CHECK(plan.kernel == PT_KERNEL_MEGA_BVH2 || plan.kernel == PT_KERNEL_PERSISTENT);
+        return;
+    }
+    CHECK(f.env == ENV_NONE && !L.mis && plan.samples && !plan.side);   // a pipeline plan never coexists with a map
+    wave_calls.insert((L.count ? 1 : 0) | (L.nee ? 2 : 0) | (L.lstk == 24 ? 4 : 0) | (a.moments ? 8 : 0));
+    const WaveLayout& w = plan.wl;
+    CHECK(w.cap < (1ull << 31) && w.cap >= (size_t)plan.work_tiles * 64 && w.off[0] == 0 && w.off[W_PIECES] == w.need && w.nee == L.nee);
+    for (int i = 0; i < W_PIECES; i++) CHECK(w.off[i] <= w.off[i + 1] && w.off[i] % 16 == 0);   // in order, none over the next; float4 pieces aligned
+    CHECK(w.off[W_RAY0 + 1] - w.off[W_RAY0] == w.cap * 16 && w.off[W_QUEUES + 1] - w.off[W_QUEUES] == w.q_words * 4);
+    CHECK((w.off[W_S_RAY0] == w.need) == !w.nee);   // the shadow records only under PT_FLAG_NEE
+    const WavePlan& p = plan.wave;
+    const uint32_t depth = a.p->depth;
+    for (uint32_t b = 0; b < depth; b++) {   // render_wavefront's launches, bounce by bounce
+        const WaveExtend e = p.extend(b, depth);
+        if (e == EXT_FUSED) fused.request(fused_word(p, depth));
+        else if (e != EXT_PACKET) extend.request(extend_word(p, e));   // (k_wf_extend_packet has COUNT alone)
+        const WaveShade s = p.shade(b, depth);
+        CHECK((s == SHADE_NONE) == (e == EXT_FUSED));
+        if (s == SHADE_LAST_ANY) last_any.request(shade_word(p, s, b == 0));
+        else if (s != SHADE_NONE) shade.request(shade_word(p, s, b == 0));
+        if (L.nee) extend.request(extend_word(p, EXT_CLOSEST));   // the bounce's shadow rays
+    }
+}
+// the call under every answer the runtime can give it: PT_KERNEL_AUTO's table where the plan looks it up (no trial and nothing decided, the
+// four trials, either choice), the caller's stream idle or busy where the plan asks
+static void frame_calls(const CtxFacts& f, const CallFacts& a) {
+    static const AutoAnswer AUTO[] = {{-1, false, PT_KERNEL_PERSISTENT}, {0, false, PT_KERNEL_PERSISTENT}, {1, false, PT_KERNEL_PERSISTENT}, {2, false, PT_KERNEL_PERSISTENT},
+                                      {3, false, PT_KERNEL_PERSISTENT}, {-1, true, PT_KERNEL_PERSISTENT}, {-1, true, PT_KERNEL_WAVEFRONT}};
+    CallPlan plan;
+    for (const AutoAnswer& au : AUTO) {
+        for (int idle = 0; idle < 2; idle++) {
+            if (!frame_call(f, a, au, idle != 0, plan)) return;   // (the refusals do not depend on the runtime's answers)
+            frame_plan(f, a, plan);
+            if (!plan.idle_query) break;
+        }
+        if (!plan.lookup) break;
+    }
+}
 
 int main() {
-    Family mega{"k_trace_mega_bvh2", mega_exists, PV_BITS}, persist{"k_trace_persist_bvh2", persist_exists, PV_BITS},
-        rays{"k_render_rays", rays_exists, PV_BITS}, query{"k_query_rays", query_exists, QV_BITS}, extend{"k_wf_extend", extend_exists, WX_BITS},
-        shade{"k_wf_shade", shade_exists, WS_BITS}, last_any{"k_wf_shade_last_any", shade_last_any_exists, WS_BITS},
-        fused{"k_wf_extend_packet_shade", fused_exists, WS_BITS};
-    const int occs[] = {4, 5, 6, 8}, lstks[] = {16, 24, 72};   // PT_OPT_OCCUPANCY; PT_OPT_LDS_STACK (0 = all 72 entries)
-    const int kernels[] = {PT_KERNEL_MEGA_BVH2, PT_KERNEL_PERSISTENT, PT_KERNEL_WAVEFRONT};   // the option, or PT_KERNEL_AUTO's pick
+    const uint32_t COS = PT_FLAG_COSINE_DIFF, NEE = PT_FLAG_NEE | COS, MIS = PT_FLAG_MIS | NEE;
+    const int KERNELS[] = {PT_KERNEL_AUTO, PT_KERNEL_MEGA_BVH2, PT_KERNEL_PERSISTENT, PT_KERNEL_WAVEFRONT};
 
-    // pt_render (plan_call): the walk is choose_walk's (0 .. 4; 3 = Woop records), the map env_code's.  The pipeline is possible
-    // (wave_ok) only with walk 2 and without a map; PT_FLAG_MIS comes with PT_FLAG_NEE, is refused over Woop records and runs the megakernel.
-    std::set<int> wave_calls;   // (count, nee, deep stack, moments) of the calls that run the pipeline
-    for (int kernel : kernels)
-        for (int walk = ALG_WHILE; walk <= ALG_WIDE_PEND; walk++)
-            for (int map = ENV_NONE; map <= ENV_LIGHT; map++)
-                for (int bits = 0; bits < 64; bits++)
-                    for (int occ : occs)
-                        for (int lstk : lstks) {
-                            const bool nee = bits & 1, mis = bits & 2, count = bits & 4, moments = bits & 8, wave_ok = bits & 16, pixels_fit = bits & 32;
-                            // skipped, each by a rule of ptmi.hip: PT_FLAG_MIS without PT_FLAG_NEE (pt_render's argument checks: PT_ERR_INVALID)
-                            // and over Woop records (plan_call: PT_ERR_UNSUPPORTED); wave_ok with another walk or with a map (plan_call's wave_ok)
-                            if ((mis && (!nee || walk == ALG_WIDE_WOOP)) || (wave_ok && (walk != ALG_WIDE || map != ENV_NONE))) continue;
-                            CHECK(env_code(map != ENV_NONE, map == ENV_LIGHT) == map);
-                            const int k = path_kernel(mis ? (int)PT_KERNEL_MEGA_BVH2 : kernel, walk, wave_ok, nee, pixels_fit);
-                            if (k == PT_KERNEL_MEGA_BVH2) mega.request(mega_word(count, occ, lstk, walk, map, mis));
-                            else if (k == PT_KERNEL_PERSISTENT) persist.request(persist_word(count, occ, lstk, walk, map));
-                            else {
-                                CHECK(k == PT_KERNEL_WAVEFRONT && wave_ok && !mis);
-                                wave_calls.insert((count ? 1 : 0) | (nee ? 2 : 0) | (lstk == 24 ? 4 : 0) | (moments ? 8 : 0));
+    // (a) which family, which budget: every tree x map x material table, the options that choose among the frame kernels, the flags that do
+    for (const Tree& t : TREES)
+        for (int env = ENV_NONE; env <= ENV_LIGHT; env++)
+            for (const Mats& m : {MATS[0], MATS[2]})
+                for (int kernel : KERNELS)
+                    for (int count = 0; count < 2; count++)
+                        for (int walk : {0, 1, 2, 4})
+                            for (int lstk : {0, 16, 24})
+                                for (int occ : {4, 5, 6, 8}) {
+                                    CtxFacts f = scene(t, SPHERES[t.has_bvh ? 1 : 0], m, env);
+                                    f.kernel = kernel; f.counters = count; f.walk = walk; f.lstk = lstk; f.occ = occ;
+                                    for (uint32_t flags : {0u, COS, NEE, MIS, (uint32_t)PT_FLAG_NEE, (uint32_t)(PT_FLAG_MIS | COS)})
+                                        for (uint32_t depth : {0u, 3u})
+                                            for (uint32_t spp : {1u, 4u})
+                                                for (int moments = 0; moments < 2; moments++) {
+                                                    const pt_params p = params(100, 60, depth, flags);
+                                                    frame_calls(f, frame(p, spp, moments != 0));
+                                                }
+                                }
+    CHECK(wave_calls.size() == 16);   // every (count, nee, deep stack, moments)
+
+    // (b) what the pipeline launches: the scenes that decide the last segment's any-hit query, the path history, the occluder test and
+    // the packet walk; every value of the stage options; depths 1 .. 4; (spp): one sample, the groups of 4, 8 and 16 that a fused fold
+    // needs, a group that is not the whole call
+    struct { Tree t; Spheres s; Mats m; } const WAVE_SCENES[] = {{TREE_OCC, SPHERES[1], MATS[0]}, {TREE, SPHERES[3], MATS[0]}, {TREE_OCC, SPHERES[4], MATS[0]},
+                                                               {TREE, SPHERES[0], MATS[2]}, {TREE_23, SPHERES[0], MATS[0]}, {TREE_OCC, SPHERES[2], MATS[1]}};
+    for (const auto& s : WAVE_SCENES)
+        for (int bits = 0; bits < 32; bits++)
+            for (int opts = 0; opts < 243; opts++) {
+                CtxFacts f = scene(s.t, s.s, s.m, ENV_NONE);
+                f.kernel = PT_KERNEL_WAVEFRONT;
+                f.counters = bits & 1; f.lstk = bits & 2 ? 24 : 16; f.first_walk = bits & 4 ? 1 : 0; f.packet_stack = bits & 8 ? 72 : 40; f.fuse_stages = bits & 16 ? 1 : 0;
+                f.last_anyhit = opts % 3; f.root_cull = opts / 3 % 3; f.root_entry = opts / 9 % 3; f.path_history = opts / 27 % 3; f.last_occluders = opts / 81 % 3;
+                for (uint32_t flags : {0u, NEE})
+                    for (uint32_t depth = 1; depth <= 4; depth++)
+                        for (uint32_t spp : {1u, 4u, 8u, 16u, 32u})
+                            for (int call = 0; call < 4; call++) {   // moments; a triangle material that emits
+                                pt_params p = params(100, 60, depth, flags);
+                                p.tri_emi[1] = call & 2 ? 1.f : 0.f;
+                                frame_calls(f, frame(p, spp, (call & 1) != 0));
                             }
-                        }
-    CHECK(wave_calls.size() == 16);   // every combination the loop below starts from
+            }
 
-    // render_wavefront: the plan of every such call (wave_plan), bounce by bounce at depths 1 .. 4.  (spp, sample group): one sample; the
-    // groups of 4, 8 and 16 that a fused fold needs; a group that is not the whole call.  The history never holds under PT_FLAG_NEE.
-    const uint32_t spps[][2] = {{1, 0}, {4, 2}, {8, 3}, {16, 4}, {32, 4}};
-    for (int call : wave_calls)
-        for (int bits = 0; bits < 64; bits++)
-            for (int opts = 0; opts < 243; opts++)
-                for (uint32_t depth = 1; depth <= 4; depth++)
-                    for (const uint32_t* ss : spps) {
-                        WaveRequest r = {};
-                        r.count = call & 1; r.nee = call & 2; r.deep_stack = call & 4; r.moments = call & 8;
-                        r.packet = bits & 1; r.anyhit_scene = bits & 2; r.history_holds = bits & 4; r.tree_has_occluders = bits & 8;
-                        r.spp_fits_entry = bits & 16; r.fuse_stages = bits & 32 ? 1 : 0;
-                        // skipped: path_history_holds (pt_ctx.h) is false for every call with PT_FLAG_NEE.  shade_word carries the plan's
-                        // history into WS_HIST whatever nee says, and no NEE kernel has it: a looser path_history_holds has to show up HERE
-                        if (r.history_holds && r.nee) continue;
-                        r.last_anyhit = opts % 3; r.root_cull = opts / 3 % 3; r.root_entry = opts / 9 % 3; r.path_history = opts / 27 % 3;
-                        r.last_occluders = opts / 81 % 3;
-                        r.depth = depth; r.spp = ss[0]; r.sgroup_log2 = ss[1];
-                        const WavePlan p = wave_plan_of(r);
-                        for (uint32_t b = 0; b < depth; b++) {
-                            const WaveExtend e = p.extend(b, depth);
-                            if (e == EXT_FUSED) fused.request(fused_word(p, depth));
-                            else if (e != EXT_PACKET) extend.request(extend_word(p, e));   // (k_wf_extend_packet has COUNT alone)
-                            const WaveShade s = p.shade(b, depth);
-                            CHECK((s == SHADE_NONE) == (e == EXT_FUSED));
-                            if (s == SHADE_LAST_ANY) last_any.request(shade_word(p, s, b == 0));
-                            else if (s != SHADE_NONE) shade.request(shade_word(p, s, b == 0));
-                            if (r.nee) extend.request(extend_word(p, EXT_CLOSEST));   // the bounce's shadow rays
-                        }
+    // (c) every other option planning reads, at the ends of its range and between, one at a time over a new context's values
+    struct { int CtxFacts::*opt; std::vector<int> values; } const KNOBS[] = {
+        {&CtxFacts::timing, {0, 1}}, {&CtxFacts::overlap, {0, 1}}, {&CtxFacts::sph_lds, {0, 1}}, {&CtxFacts::top, {0, 1, 64, 100, 1024}},
+        {&CtxFacts::batch, {1, 7, 36, 64}}, {&CtxFacts::refill, {1, 8, 37, 64}}, {&CtxFacts::vote_node, {1, 64}}, {&CtxFacts::vote_rec, {1, 64}},
+        {&CtxFacts::wave_batch, {1, 16, 64}}, {&CtxFacts::wave_samples, {1, 2, 4, 7, 8, 16, 32, 64}}, {&CtxFacts::wave_blocks, {1, 8}},
+        {&CtxFacts::packet_stack, {2, 31, 32, 72}}, {&CtxFacts::n_cu, {1, 256, 304}}};
+    for (const auto& knob : KNOBS)
+        for (int value : knob.values)
+            for (int kernel : KERNELS)
+                for (int walk : {0, 2})
+                    for (const Spheres& s : SPHERES)
+                        for (const Tree& t : {NO_TREE, TREE, TREE_OCC})
+                            for (uint32_t spp : {1u, 3u, 4u, 16u, 64u, 4096u}) {
+                                CtxFacts f = scene(t, s, MATS[0], ENV_NONE);
+                                f.*knob.opt = value; f.kernel = kernel; f.walk = walk;
+                                for (int side : {2, 100, 1920}) {   // one tile .. enough slots for 64-slot chunks
+                                    const pt_params p = params(side, side > 100 ? 1080 : side, 5, 0);
+                                    frame_calls(f, frame(p, spp));
+                                }
+                            }
+
+    // (d) the argument rules of pt_render, one broken at a time and several together (the first in the rules' order answers)
+    {
+        const CtxFacts f = scene(TREE, SPHERES[1], MATS[0], ENV_NONE), empty = scene(NO_TREE, SPHERES[0], MATS[0], ENV_NONE);
+        CallPlan plan;
+        const AutoAnswer none = {-1, false, PT_KERNEL_PERSISTENT};
+        for (int broken = 0; broken < (1 << 11); broken++) {
+            pt_params p = params(broken & 1 ? 1 : 64, 64, 3, broken & 2 ? (uint32_t)PT_FLAG_NEE : broken & 4 ? (uint32_t)(PT_FLAG_MIS | COS) : 0u);
+            if (broken & 8) p.sample_index = 0;
+            if (broken & 16) p.tri_mat = PT_MAT_REFR + 1;
+            if (broken & 32) p.flags |= PT_FLAG_WRITE_RGBA;
+            p.part_count = broken & 64 ? 4 : 0; p.part_rows = broken & 128 ? 12 : 8; p.part_index = broken & 256 ? 4 : 1;
+            CallFacts a = frame(p, broken & 512 ? 0 : 1);
+            a.rgba = false;
+            a.buffers = !(broken & 1024);
+            const bool ran = frame_call(f, a, none, false, plan);
+            const bool bad = (broken & ~(64 | 128 | 256)) || ((broken & 64) && (broken & (128 | 256)));   // (the part's fields count with part_count > 1)
+            CHECK(ran == !bad);
+            (void)frame_call(empty, a, none, false, plan);
+        }
+        const CallFacts null_params = {true, nullptr, 1, true, true, false, 0, 0};
+        CHECK(!frame_call(f, null_params, none, false, plan));
+        pt_params p = params(64, 8, 3, 0);   // one tile-row in stripes of 8 rows: part 1 of 2 owns no tile, nothing to render
+        p.part_count = 2; p.part_rows = 8; p.part_index = 1;
+        CHECK(check_path_call(f, frame(p, 1)).code == PT_OK && !frame_call(f, frame(p, 1), none, false, plan));
+    }
+
+    // (e) tests/test_gpu_call_plan.py::CASES, worked by hand: the family each call runs on a new context with a tree and nine spheres
+    {
+        struct { const char* id; int kernel; Tree tree; int walk, counters; uint32_t flags, depth; int family; bool lookup; } const CASES[] = {
+            {"wavefront", PT_KERNEL_WAVEFRONT, TREE, 2, 0, 0, 3, PT_KERNEL_WAVEFRONT, false},
+            {"wavefront-depth0", PT_KERNEL_WAVEFRONT, TREE, 2, 0, 0, 0, PT_KERNEL_PERSISTENT, false},
+            {"wavefront-walk0", PT_KERNEL_WAVEFRONT, TREE, 0, 0, 0, 3, PT_KERNEL_PERSISTENT, false},
+            {"wavefront-walk1", PT_KERNEL_WAVEFRONT, TREE, 1, 0, 0, 3, PT_KERNEL_PERSISTENT, false},
+            {"wavefront-walk4", PT_KERNEL_WAVEFRONT, TREE, 4, 0, 0, 3, PT_KERNEL_PERSISTENT, false},
+            {"wavefront-no-tree", PT_KERNEL_WAVEFRONT, NO_TREE, 2, 0, 0, 3, PT_KERNEL_PERSISTENT, false},
+            {"wavefront-woop", PT_KERNEL_WAVEFRONT, TREE_WOOP, 2, 0, 0, 3, PT_KERNEL_PERSISTENT, false},
+            {"persistent", PT_KERNEL_PERSISTENT, TREE, 2, 0, 0, 3, PT_KERNEL_PERSISTENT, false},
+            {"persistent-nee", PT_KERNEL_PERSISTENT, TREE, 2, 0, NEE, 3, PT_KERNEL_WAVEFRONT, false},
+            {"persistent-nee-walk0", PT_KERNEL_PERSISTENT, TREE, 0, 0, NEE, 3, PT_KERNEL_MEGA_BVH2, false},
+            {"auto", PT_KERNEL_AUTO, TREE, 2, 0, 0, 3, PT_KERNEL_WAVEFRONT, true},   // (under the answer below: trial 1, the pipeline's)
+            {"auto-counters", PT_KERNEL_AUTO, TREE, 2, 1, 0, 3, PT_KERNEL_PERSISTENT, false},
+            {"auto-nee", PT_KERNEL_AUTO, TREE, 2, 0, NEE, 3, PT_KERNEL_WAVEFRONT, false},
+            {"mis", PT_KERNEL_WAVEFRONT, TREE, 2, 0, MIS, 3, PT_KERNEL_MEGA_BVH2, false},
+            {"auto-mis", PT_KERNEL_AUTO, TREE, 2, 0, MIS, 3, PT_KERNEL_MEGA_BVH2, false},
+        };
+        for (const auto& k : CASES) {
+            CtxFacts f = scene(k.tree, SPHERES[2], MATS[0], ENV_NONE);
+            f.kernel = k.kernel; f.walk = k.walk; f.counters = k.counters;
+            const pt_params p = params(96, 64, k.depth, k.flags);
+            CallPlan plan;
+            const bool ran = frame_call(f, frame(p, 1), AutoAnswer{1, false, PT_KERNEL_PERSISTENT}, true, plan);
+            if ((!ran || plan.kernel != k.family || plan.lookup != k.lookup) && n_failed++ < 20) std::printf("FAILED: case %s plans family %d\n", k.id, ran ? plan.kernel : -1);
+        }
+    }
+
+    // (f) the pipeline's refusals at their edges: the last call that runs and the first that does not
+    {
+        CtxFacts f = scene(TREE, SPHERES[1], MATS[0], ENV_NONE);
+        f.kernel = PT_KERNEL_WAVEFRONT;
+        CallPlan plan;
+        const AutoAnswer none = {-1, false, PT_KERNEL_PERSISTENT};
+        auto runs = [&](int w, int h, uint32_t depth, uint32_t flags, uint32_t spp) {
+            const pt_params p = params(w, h, depth, flags);
+            const bool ran = frame_call(f, frame(p, spp), none, false, plan);
+            if (ran) frame_plan(f, frame(p, spp), plan);
+            return ran;
+        };
+        static_assert(2047 * 2 + 2 == PT_REC_MAX_DRAWS, "two draws per cosine-weighted bounce, two for the camera");
+        CHECK(runs(8, 8, 2046, COS, 1) && !runs(8, 8, 2047, COS, 1));                                       // depth * draws + 2 == PT_REC_MAX_DRAWS
+        CHECK(runs(8, 8, 3, 0, PT_REC_MAX_SAMPLES - 1) && !runs(8, 8, 3, 0, PT_REC_MAX_SAMPLES));         // spp == 2^20
+        CHECK(runs(8, 8, 3, NEE, PT_REC_MAX_SAMPLES_NEE - 1) && !runs(8, 8, 3, NEE, PT_REC_MAX_SAMPLES_NEE));
+        CHECK(runs(64, 64, 3, 0, (1u << 19) - 1) && !runs(64, 64, 3, 0, 1u << 19));                       // n_tiles * 64 * spp == 2^31: 64 tiles
+        // 2^25 - 1 = 31 * 601 * 1801 tiles are 2^23 regions, 2^31 records: one too many
+        CHECK(!runs(8 * 31 * 601, 8 * 1801, 3, 0, 1) && runs(8 * 31 * 601, 8 * 1800, 3, 0, 1));
+        f.kernel = PT_KERNEL_PERSISTENT;   // the frame kernels have no such limits
+        CHECK(runs(8, 8, 2047, COS, 1) && runs(8, 8, 3, 0, PT_REC_MAX_SAMPLES) && runs(8 * 31 * 601, 8 * 1801, 3, 0, 1));
+    }
+
+    // (g) pt_render_rays: every scene and map, the options its plan reads, the flags, batches around RAYS_MAX_SLOTS, every launch of a call
+    for (const Tree& t : TREES)
+        for (int env = ENV_NONE; env <= ENV_LIGHT; env++)
+            for (const Mats& m : {MATS[0], MATS[2]})
+                for (int walk : {0, 1, 2, 4})
+                    for (int knobs = 0; knobs < 4; knobs++)
+                        for (uint32_t flags : {0u, COS, NEE, MIS, (uint32_t)PT_FLAG_NEE, (uint32_t)(PT_FLAG_MIS | COS)})
+                            for (uint64_t n : {0ull, 1ull, 1000ull, (1ull << 26) / 3, 1ull << 26, (1ull << 32) - 1, 1ull << 32})
+                                for (uint32_t spp : {0u, 1u, 3u, 64u})
+                                    for (int mode : {(int)PT_RAYS_CLAMPED, (int)PT_RAYS_HDR, 7}) {
+                                        CtxFacts f = scene(t, SPHERES[t.has_bvh ? 2 : knobs & 1], m, env);
+                                        f.walk = walk; f.sph_lds = knobs & 1; f.n_cu = knobs & 2 ? 256 : 8;
+                                        pt_params p = params(0, 0, 4, flags);
+                                        const CallFacts a = {false, &p, spp, true, false, false, n, mode};
+                                        RaysPlan plan = {};
+                                        if (turned_away(check_path_call(f, a)) || turned_away(tri_lights_rule(f, flags)) || turned_away(plan_rays(f, a, plan))) continue;
+                                        n_planned++;
+                                        rays.request(rays_word(plan.L));
+                                        CHECK(plan.L.lds <= PT_LDS_BYTES && plan.q.refill <= plan.q.batch && plan.per_launch >= 1 && plan.per_launch <= spp);
+                                        CHECK(plan.per_launch == 1 || plan.per_launch * n <= RAYS_MAX_SLOTS);
+                                        for (uint32_t s0 = 0; s0 < spp; s0 += plan.per_launch) {
+                                            int work_blocks = 0;
+                                            const int chunk = plan_rays_launch(f, a, plan, std::min(plan.per_launch, spp - s0), work_blocks);
+                                            CHECK(work_blocks >= 1 && (chunk == 16 || chunk == 32 || chunk == 64));
+                                        }
+                                    }
+    {   // ... and its own argument rules
+        const CtxFacts f = scene(TREE, SPHERES[1], MATS[0], ENV_NONE);
+        pt_params p = params(0, 0, 4, 0);
+        CHECK(turned_away(check_path_call(f, CallFacts{false, &p, 1, false, false, false, 10, PT_RAYS_HDR})));
+        CHECK(turned_away(check_path_call(f, CallFacts{false, nullptr, 1, true, false, false, 10, PT_RAYS_HDR})));
+        CHECK(check_path_call(f, CallFacts{false, nullptr, 0, false, false, false, 10, 7}).nothing);   // nothing to do comes first
+        p.sample_index = 0;
+        CHECK(turned_away(check_path_call(f, CallFacts{false, &p, 1, true, false, false, 10, PT_RAYS_HDR})));
+        p.sample_index = 1; p.tri_mat = -1;
+        CHECK(turned_away(check_path_call(f, CallFacts{false, &p, 1, true, false, false, 10, PT_RAYS_HDR})));
+    }
+
+    // (h) pt_closest_hits / pt_any_hits: the wide walk's two budgets, the binary walk for a tree too deep
+    for (const Tree& t : {TREE, TREE_OCC, TREE_23, TREE_DEEP})
+        for (int lstk : {0, 16, 24})
+            for (int top : {0, 64, 1024})
+                for (int any = 0; any < 2; any++)
+                    for (uint64_t n : {1ull, 256ull, 257ull, (1ull << 32) - 1}) {
+                        CtxFacts f = scene(t, SPHERES[0], MATS[0], ENV_NONE);
+                        f.lstk = lstk; f.top = top;
+                        const QueryPlan q = plan_query(f, n, any != 0);
+                        n_planned++;
+                        CHECK(q.lds <= PT_LDS_BYTES && q.n_regions >= 1 && (uint64_t)q.n_regions * PT_REGION >= n && q.wide == (t.wide_depth < 24));
+                        if (q.wide) query.request(q.word);
+                        else CHECK(q.n_top <= top && q.lds == (size_t)q.n_top * 64 + (size_t)PT_STACK_CAP * PT_BLOCK_RAYS * 4);
                     }
 
-    // pt_render_rays: choose_walk without the postponed leaf (4 runs as 2); PT_FLAG_MIS as above
-    for (int walk = ALG_WHILE; walk <= ALG_WIDE_WOOP; walk++)
-        for (int map = ENV_NONE; map <= ENV_LIGHT; map++)
-            for (int bits = 0; bits < 4; bits++) {
-                const bool nee = bits & 1, mis = bits & 2;
-                if (mis && (!nee || walk == ALG_WIDE_WOOP)) continue;   // (pt_render_rays' own checks refuse both: PT_ERR_INVALID, PT_ERR_UNSUPPORTED)
-                rays.request(rays_word(walk, map, nee, mis));
-            }
-    // pt_closest_hits / pt_any_hits on a tree the wide walk fits: PT_OPT_LDS_STACK 0, 16, 24
-    for (int any = 0; any < 2; any++)
-        for (int lstk : {0, 16, 24}) query.request(query_word(any != 0, lstk == 24));
-
-    for (const Family* f : {&mega, &persist, &rays, &query, &extend, &shade, &last_any, &fused}) f->report();
+    for (const Family* fam : {&mega, &persist, &rays, &query, &extend, &shade, &last_any, &fused}) fam->report();
+    std::printf("%ld plans, %ld refusals\n", n_planned, n_refused);
+    for (const auto& e : REFUSALS)
+        if (!e.seen && n_failed++ < 20) std::printf("FAILED: no call of the domain is refused with \"%s\"\n", e.text);
     // the budgets the words carry are the ones the requests asked for, or the nearest
     CHECK(budget_occ(mega_budget(6, 16)) == 8 && budget_occ(mega_budget(4, 16)) == 4 && budget_lstk(mega_budget(8, 72)) == 72);
     CHECK(persist_budget(ALG_WIDE, 5, 16) == BUDGET_6x16 && persist_budget(ALG_WIDE, 8, 24) == BUDGET_6x24 && persist_budget(ALG_UNIFIED, 4, 24) == BUDGET_8x16);
     CHECK(shade_env(ENV_LIGHT, false, false) == ENV_LOOKUP && shade_env(ENV_LOOKUP, true, true) == ENV_LIGHT && shade_env(ENV_LIGHT, true, false) == ENV_LIGHT);
+    CHECK(env_code(false, false) == ENV_NONE && env_code(true, false) == ENV_LOOKUP && env_code(true, true) == ENV_LIGHT);
     for (int lp : {0, 1, 2, 4}) CHECK(ws_fold(ws_fold_field(lp)) == lp);
     if (n_failed) {
         std::printf("%d checks FAILED\n", n_failed);

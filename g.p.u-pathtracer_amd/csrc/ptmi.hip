@@ -64,6 +64,25 @@ int stage_mark(pt_ctx* c, int kind) {
     return PT_OK;
 }
 
+// What planning reads off the context: the one place that reads the tree's fields and the options for a plan (pt_plan.h)
+CtxFacts ctx_facts(const pt_ctx* c) {
+    const TreeState& t = c->tree;
+    CtxFacts f = {};
+    f.has_bvh = t.has_bvh; f.records_woop = t.records_woop;
+    f.wide_depth = t.wide_depth; f.n_top_layout = t.n_top_layout; f.wide_top_layout = t.wide_top_layout; f.n_occ = t.n_occ;
+    f.n_spheres = c->n_spheres;
+    for (int i = 0; i < PT_KSPHERES; i++) f.sphere_mat[i] = c->h_spheres[i].mat;
+    f.mat_table = c->mat.d_tri_matid.get() != nullptr; f.tri_emits = !c->mat.emissive_ids.empty();
+    f.env = c->env.code(); f.n_cu = c->n_cu;
+    f.kernel = c->opt_kernel; f.counters = c->opt_counters; f.timing = c->opt_timing; f.overlap = c->opt_overlap; f.sph_lds = c->opt_sph_lds;
+    f.top = c->opt_top; f.occ = c->opt_occ; f.lstk = c->opt_lstk; f.walk = c->opt_walk; f.batch = c->opt_batch; f.refill = c->opt_refill;
+    f.vote_node = c->opt_vote_node; f.vote_rec = c->opt_vote_rec; f.wave_batch = c->opt_wave_batch; f.wave_samples = c->opt_wave_samples;
+    f.wave_blocks = c->opt_wave_blocks; f.first_walk = c->opt_first_walk; f.packet_stack = c->opt_packet_stack; f.fuse_stages = c->opt_fuse_stages;
+    f.last_anyhit = c->opt_last_anyhit; f.root_cull = c->opt_root_cull; f.root_entry = c->opt_root_entry;
+    f.last_occluders = c->opt_last_occluders; f.path_history = c->opt_path_history;
+    return f;
+}
+
 // pt_set_option's table, one row per option: the member it sets, the values it takes and what a refused value is answered with.
 // TRI_TEST, LEAF_MAX and OPTIMIZE take effect at the next pt_upload_bvh, ENV_LIGHT at the next pt_upload_environment.
 struct OptionRow {
@@ -310,37 +329,15 @@ int pt_upload_spheres(pt_ctx* c, const pt_sphere* spheres, size_t n) {
 }
 
 // ---------------------------------------------------------------------------------------
-// pt_render in steps, in the order pt_render_moments runs them: check the arguments, bring the light list up to date, fill the
-// kernel arguments, PLAN the call (plan_call: every decision about what runs and with which buffers, made once), take the
-// buffers the plan asks for, launch.
+// pt_render in steps, in the order pt_render_moments runs them: gather the facts (ctx_facts, CallFacts), check the arguments, bring the
+// light list up to date, fill the kernel arguments, PLAN the call (pt_plan.h: every decision about what runs and with which buffers,
+// made once; plan_call asks the runtime what the plan's steps need to know), take the buffers the plan asks for, launch.
 namespace ptmi {
-static int check_call(pt_ctx* c, const float* accum_dev, const uint32_t* rgba_dev, const pt_camera* cam, const pt_params* p, uint32_t spp) {
-    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
-    if (!accum_dev || !cam || !p) return fail(c, PT_ERR_INVALID, "pt_render: null argument");
-    if (p->width < 2 || p->height < 2) return fail(c, PT_ERR_INVALID, "pt_render: image must be at least 2x2 (the camera divides by w-1, h-1)");
-    if (spp == 0) return fail(c, PT_ERR_INVALID, "pt_render: spp must be >= 1");
-    if (p->sample_index == 0) return fail(c, PT_ERR_INVALID, "pt_render: sample_index (constantPdf) starts at 1");
-    if (p->tri_mat < PT_MAT_DIFF || p->tri_mat > PT_MAT_REFR) return fail(c, PT_ERR_INVALID, "pt_render: bad triangle material");
-    if ((p->flags & PT_FLAG_WRITE_RGBA) && !rgba_dev) return fail(c, PT_ERR_INVALID, "pt_render: PT_FLAG_WRITE_RGBA needs rgba_dev");
-    if ((p->flags & PT_FLAG_NEE) && !(p->flags & PT_FLAG_COSINE_DIFF)) return fail(c, PT_ERR_INVALID, "pt_render: PT_FLAG_NEE needs PT_FLAG_COSINE_DIFF (the reference's DIFF lobe has no density to weigh a light sample against)");
-    if ((p->flags & PT_FLAG_MIS) && !(p->flags & PT_FLAG_NEE)) return fail(c, PT_ERR_INVALID, "pt_render: PT_FLAG_MIS needs PT_FLAG_NEE (it weighs NEE's shadow rays against the bounce rays)");
-    if (!c->tree.has_bvh && c->n_spheres == 0) return fail(c, PT_ERR_NO_SCENE, "pt_render: no scene uploaded");
-    if (p->part_count > 1) {
-        if (p->part_index < 0 || p->part_index >= p->part_count) return fail(c, PT_ERR_INVALID, "pt_render: part_index out of range");
-        if (p->part_rows <= 0 || (p->part_rows % PT_TILE) != 0) return fail(c, PT_ERR_INVALID, "pt_render: part_rows must be a positive multiple of 8");
-    }
-    return PT_OK;
-}
-
-// PT_FLAG_NEE over emissive triangles: the call samples the light list
-static bool samples_tri_lights(const pt_ctx* c, const pt_params* p) {
-    return (p->flags & PT_FLAG_NEE) && c->tree.has_bvh && !c->mat.emissive_ids.empty();
-}
-
 // the scene, its geometry (pt_refit_bvh) or the materials changed: copies the lights' vertices out of the records again
-static int refresh_tri_lights(pt_ctx* c, const pt_params* p) {
-    if (!samples_tri_lights(c, p)) return PT_OK;
-    if (c->tree.records_woop) return fail(c, PT_ERR_UNSUPPORTED, "pt_render: PT_FLAG_NEE over emissive triangles needs the exact (Moller-Trumbore) records");
+static int refresh_tri_lights(pt_ctx* c, const CtxFacts& f, const pt_params* p) {
+    if (!samples_tri_lights(f, p->flags)) return PT_OK;
+    const Refusal r = tri_lights_rule(f, p->flags);
+    if (r.code != PT_OK) return fail(c, r);
     const uint64_t key = (c->scene_gen << 32) ^ c->mat_gen;
     if (c->lights_key == key && c->lights_geom == c->geom_gen) return PT_OK;
     const uint32_t n_rec = (uint32_t)c->tree.n_refs;
@@ -358,7 +355,7 @@ static int refresh_tri_lights(pt_ctx* c, const pt_params* p) {
 }
 
 // the kernel arguments that the context and pt_params give to any path kernel, a frame's or a ray batch's; zeroes the rest
-static void fill_path_params(const pt_ctx* c, const pt_params* p, uint32_t spp, KParams& P) {
+static void fill_path_params(const pt_ctx* c, const CtxFacts& f, const pt_params* p, uint32_t spp, KParams& P) {
     std::memset(&P, 0, sizeof P);
     scene_view(c, P.sc, P.ksph);
     P.counters = c->d_counters.get();
@@ -372,7 +369,7 @@ static void fill_path_params(const pt_ctx* c, const pt_params* p, uint32_t spp, 
     P.tri_matid = c->mat.d_tri_matid.get();
     P.mat_table = c->mat.d_mat_table.get();
     P.flags = p->flags;
-    if (samples_tri_lights(c, p)) {
+    if (samples_tri_lights(f, p->flags)) {
         P.tri_lights = c->mat.d_tri_lights.get();
         P.n_tri_lights = (int)c->mat.emissive_ids.size();
     }
@@ -380,28 +377,16 @@ static void fill_path_params(const pt_ctx* c, const pt_params* p, uint32_t spp, 
 }
 
 // the kernel arguments that the context and the call's arguments give; what the plan decides (samples, LDS layout, queue) is added
-// by pt_render_moments.  A part that owns no tile leaves P.n_tiles <= 0 and PT_OK: nothing to render.
-static int fill_params(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, const pt_camera* cam, const pt_params* p, uint32_t spp, KParams& P) {
-    fill_path_params(c, p, spp, P);
+// by apply_plan
+static void fill_params(const pt_ctx* c, const CtxFacts& f, float* accum_dev, uint32_t* rgba_dev, const pt_camera* cam, const pt_params* p, uint32_t spp, const TileGrid& g, KParams& P) {
+    fill_path_params(c, f, p, spp, P);
     P.accum = accum_dev;
     P.rgba = rgba_dev;
     P.cam = *cam;
     P.smp_ss = (unsigned long long)p->width * (unsigned long long)p->height;   // one sample per pixel, or sample planes (plan.sgroup_log2 = 0)
     P.smp_ps = 1u;
-    P.tiles_x = (p->width + PT_TILE - 1) / PT_TILE;
-    P.tile_rows = (p->height + PT_TILE - 1) / PT_TILE;
-    if (p->part_count > 1) {
-        P.part_index = p->part_index; P.part_count = p->part_count; P.stripe_tr = p->part_rows / PT_TILE;
-        const int n_stripes = (P.tile_rows + P.stripe_tr - 1) / P.stripe_tr;
-        const int owned = (n_stripes - p->part_index + p->part_count - 1) / p->part_count;  // stripes index, index+count, ...
-        P.n_tiles = owned * P.stripe_tr * P.tiles_x;
-    } else {
-        P.part_index = 0; P.part_count = 1; P.stripe_tr = 1;
-        P.n_tiles = P.tile_rows * P.tiles_x;
-    }
-    if (P.n_tiles <= 0) return PT_OK;
-    if ((uint64_t)P.n_tiles * 64u * (uint64_t)spp >= (1ull << 31)) return fail(c, PT_ERR_INVALID, "pt_render: width*height*spp too large for one call (split the samples over several calls)");
-    return PT_OK;
+    P.tiles_x = g.tiles_x; P.tile_rows = g.tile_rows; P.n_tiles = g.n_tiles;
+    P.part_index = g.part_index; P.part_count = g.part_count; P.stripe_tr = g.stripe_tr;
 }
 
 // PT_KERNEL_AUTO: the entry of the call's configuration in the table of picks (a new configuration takes the least recently used one) and
@@ -443,85 +428,27 @@ static int auto_lookup(pt_ctx* c, const pt_params* p, uint32_t spp, bool moments
     return PT_OK;
 }
 
-// What one call runs and with which buffers.  plan_call decides it, once; nothing after it changes the kernel family.
-struct CallPlan {
-    int kernel;               // PT_KERNEL_MEGA_BVH2, PT_KERNEL_PERSISTENT or PT_KERNEL_WAVEFRONT
-    int probe;                // PT_KERNEL_AUTO: this call is timed trial `probe` of `pick`; -1: it is none
-    pt_ctx::AutoPick* pick;
-    bool side;                // the path kernel runs on a side stream (PT_OPT_OVERLAP)
-    bool samples;             // ... into a sample buffer that a fold reads afterwards
-    uint32_t sgroup_log2;     // the samples of a pixel side by side in the slot order and in the sample buffer (wave_sample_group_log2)
-    int n_top, sph_tab;       // LDS: nodes mirrored, first word of the sphere table (-1: none)
-    int chunk, work_tiles;    // queue granularity in slots, 64-slot work items of the call
-    LaunchCfg L;              // walk, stack window, LDS bytes, grids
-};
-
-static int plan_call(pt_ctx* c, const pt_params* p, const KParams& P, uint32_t spp, bool moments, CallPlan& plan) {
-    const TreeState& t = c->tree;
-    LaunchCfg& L = plan.L;
-    const bool nee = (p->flags & PT_FLAG_NEE) != 0;
-    if ((L.walk = choose_walk(c, "pt_render", true)) < 0) return L.walk;
-    // the kernel family, every rule once and in this order: the option; PT_KERNEL_AUTO's table; PT_FLAG_NEE; what a family cannot run.
-    // The stage-split pipeline needs a BVH, at least one bounce, the wide walk over exact records and a context without an
-    // environment map (its last-segment any-hit launch shades misses without a ray in hand).
-    const bool wave_ok = t.has_bvh && P.depth > 0 && L.walk == 2 && !c->env.k.texels;
-    int kernel = c->opt_kernel;
-    plan.probe = -1;
-    plan.pick = nullptr;
-    // PT_FLAG_MIS: the megakernel whatever the option says, and no trial — the pipeline's path record has no word for the bounce's
-    // density, and the megakernel does not read Woop records
-    const bool mis = (p->flags & PT_FLAG_MIS) != 0;
-    if (mis && L.walk == 3) return fail(c, PT_ERR_UNSUPPORTED, "pt_render: PT_FLAG_MIS needs the exact (Moller-Trumbore) records (upload with PT_OPT_TRI_TEST 0)");
-    if (mis) kernel = PT_KERNEL_MEGA_BVH2;
-    if (kernel == PT_KERNEL_AUTO) {
-        kernel = PT_KERNEL_PERSISTENT;
-        if (wave_ok && !c->opt_counters && !nee) {   // (an instrumented call is no trial; a call with shadow rays has no choice)
-            const int rc = auto_lookup(c, p, spp, moments, plan.pick, plan.probe);
-            if (rc != PT_OK) return rc;
-            if (plan.probe >= 0) kernel = (plan.probe & 1) ? PT_KERNEL_WAVEFRONT : PT_KERNEL_PERSISTENT;
-            else if (plan.pick->phase == pt_ctx::AutoPick::DECIDED) kernel = plan.pick->choice;
-        }
+// The plan of a frame call (CallPlan, pt_plan.h), its steps in order with the runtime's answers between them: PT_KERNEL_AUTO's table
+// where the plan looks the configuration up, whether the caller's stream is idle where the plan wants to know
+static int plan_call(pt_ctx* c, const CtxFacts& f, const CallFacts& a, int n_tiles, CallPlan& plan, pt_ctx::AutoPick*& pick) {
+    Refusal r = plan_walk(f, a, plan);
+    if (r.code != PT_OK) return fail(c, r);
+    AutoAnswer au = {-1, false, PT_KERNEL_PERSISTENT};
+    pick = nullptr;
+    if (plan.lookup) {
+        const int rc = auto_lookup(c, a.p, a.spp, a.moments, pick, au.probe);
+        if (rc != PT_OK) return rc;
+        au.decided = pick->phase == pt_ctx::AutoPick::DECIDED;
+        au.choice = pick->choice;
     }
-    // shadow rays, what a family cannot run: path_kernel (pt_variants.h; the persistent kernel's lanes have no room for a second ray)
-    kernel = path_kernel(kernel, L.walk, wave_ok, nee, (uint64_t)p->width * (uint64_t)p->height <= (1ull << PT_REC_PIXEL_BITS));
-    plan.kernel = kernel;
-    const bool persistent = kernel == PT_KERNEL_PERSISTENT, wavefront = kernel == PT_KERNEL_WAVEFRONT;
-
-    // overlap with the previous call: the path kernel goes to a side stream with its own sample buffer and queue
-    // counters, so it can start while the previous call's last paths drain (the tail of a call is as long as its
-    // longest path: ~15 % of a one-sample 1080p call); instrumented, timed and trial calls run in line
-    // ... and so does a call whose caller's stream is idle: a host that syncs before every launch (BasicScene.cpp:395) leaves nothing to
-    // overlap with, and in line the call is two launches shorter (no cross-stream events; one sample folds inside the path kernel)
+    plan_family(f, a, au, plan);
     bool caller_idle = false;
-    if (c->opt_overlap && !wavefront) {
+    if (plan.idle_query) {
         caller_idle = hipStreamQuery(c->stream) == hipSuccess;
         if (!caller_idle) (void)hipGetLastError();   // hipErrorNotReady is not an error of this call
     }
-    plan.side = c->opt_overlap && !wavefront && !c->opt_counters && !c->opt_timing && plan.probe < 0 && !caller_idle;
-    // spp > 1: trace the samples as independent work items, fold them afterwards (k_fold_samples); the stage-split pipeline always
-    // works that way, and the moments are the fold's job
-    plan.samples = spp > 1 || wavefront || plan.side || moments;
-    plan.sgroup_log2 = plan.samples && (wavefront || persistent) ? wave_sample_group_log2(spp, c->opt_wave_samples) : 0u;
-    plan.work_tiles = P.n_tiles * (plan.samples ? (int)spp : 1);
-
-    L.lstk = c->opt_lstk ? c->opt_lstk : PT_STACK_CAP;   // any depth <= 64 works with every LDS window: deeper entries overflow
-    plan.n_top = t.has_bvh ? (int)std::min<uint32_t>((uint32_t)c->opt_top, L.walk >= 2 ? t.wide_top_layout : t.n_top_layout) : 0;
-    if (L.walk >= 1) plan.n_top = 0;  // only the while-while walk reads the LDS mirror
-    L.lds = lds_fit(plan.n_top, L.lstk, PT_BLOCK);
-    plan.sph_tab = persistent && c->opt_sph_lds ? lds_sphere_table(L.lds) : -1;   // behind the stacks (and the LDS mirror)
-    const long slots = (long)plan.work_tiles * 64;
-    plan.chunk = queue_chunk(c, (uint64_t)slots);
-    const int waves_per_block = PT_BLOCK / 64;
-    L.count = c->opt_counters != 0;
-    L.occ = c->opt_occ;
-    L.blocks = (plan.work_tiles + waves_per_block - 1) / waves_per_block;
-    L.work_blocks = (int)((slots + plan.chunk * waves_per_block - 1) / (plan.chunk * waves_per_block));
-    L.n_cu = c->n_cu;
-    L.moments = moments;
-    L.env = c->env.code();
-    L.nee = nee;
-    L.mis = mis;
-    return PT_OK;
+    r = plan_launch(f, a, n_tiles, caller_idle, plan);
+    return r.code != PT_OK ? fail(c, r) : PT_OK;
 }
 
 // the next side slot; its stream, events and queue counters are made on first use
@@ -579,7 +506,7 @@ static void apply_plan(const pt_ctx* c, const CallPlan& plan, const pt_ctx::Side
     P.sc.n_top = plan.n_top;
     P.sph_tab = plan.sph_tab;
     P.chunk = plan.chunk;
-    if (plan.kernel == PT_KERNEL_PERSISTENT) queue_params(c, sd ? sd->queue.get() : c->d_queue.get(), P);
+    if (plan.kernel == PT_KERNEL_PERSISTENT) queue_params(plan.q, sd ? sd->queue.get() : c->d_queue.get(), P);
 }
 }  // namespace ptmi
 
@@ -590,14 +517,22 @@ int pt_render(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, const pt_camera* 
 // pt_render's body; moments_dev != NULL: the fold also keeps the luminance moments of the samples
 int pt_render_moments(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, float* moments_dev, const pt_camera* cam, const pt_params* p,
                       uint32_t spp) {
-    int rc = check_call(c, accum_dev, rgba_dev, cam, p, spp);
-    if (rc != PT_OK) return rc;
+    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
+    const CtxFacts f = ctx_facts(c);
+    const CallFacts a = {true, p, spp, accum_dev && cam, rgba_dev != nullptr, moments_dev != nullptr, 0, 0};
+    Refusal r = check_path_call(f, a);
+    if (r.code != PT_OK) return fail(c, r);
     HIP_TRY(c, hipSetDevice(c->device));
-    if ((rc = refresh_tri_lights(c, p)) != PT_OK) return rc;
+    int rc = refresh_tri_lights(c, f, p);
+    if (rc != PT_OK) return rc;
+    TileGrid g;
+    r = frame_tiles(*p, spp, g);
+    if (r.code != PT_OK || r.nothing) return fail(c, r);
     KParams P;
-    if ((rc = fill_params(c, accum_dev, rgba_dev, cam, p, spp, P)) != PT_OK || P.n_tiles <= 0) return rc;
+    fill_params(c, f, accum_dev, rgba_dev, cam, p, spp, g, P);
     CallPlan plan;
-    if ((rc = plan_call(c, p, P, spp, moments_dev != nullptr, plan)) != PT_OK) return rc;
+    pt_ctx::AutoPick* pick = nullptr;
+    if ((rc = plan_call(c, f, a, g.n_tiles, plan, pick)) != PT_OK) return rc;
     const int probe = plan.probe;
 
     // the buffers the plan asks for
@@ -608,21 +543,17 @@ int pt_render_moments(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, float* mo
     hipStream_t trace_stream = sd ? (hipStream_t)sd->stream : c->stream;   // the stream the path kernel runs on
     apply_plan(c, plan, sd, P);
 
-    if (c->opt_counters) HIP_TRY(c, hipMemsetAsync(c->d_counters.get(), 0, c->d_counters.bytes(), c->stream));
-    if (probe >= 0 && (probe & 1)) {   // a trial of the pipeline: its path records are allocated BEFORE the timed span
-        rc = wave_reserve(c, P, plan.work_tiles);
-        if (rc != PT_OK) return rc;
-    }
-    if (probe >= 0) HIP_TRY(c, hipEventRecord(plan.pick->e[2 * probe], c->stream));
+    if (plan.L.count) HIP_TRY(c, hipMemsetAsync(c->d_counters.get(), 0, c->d_counters.bytes(), c->stream));
+    if (probe >= 0 && (probe & 1) && (rc = wave_reserve(c, plan.wl)) != PT_OK) return rc;   // a trial of the pipeline: its path records are allocated BEFORE the timed span
+    if (probe >= 0) HIP_TRY(c, hipEventRecord(pick->e[2 * probe], c->stream));
     HIP_TRY(c, span_begin(c));
-    if (c->opt_timing) {
+    if (f.timing) {
         c->stage_used = 0;
         if (stage_mark(c, PT_STAGE_NONE) != PT_OK) return PT_ERR_DEVICE;
     }
-    bool folded = false;
+    const bool folded = plan.kernel == PT_KERNEL_WAVEFRONT && plan.wave.fold_lp != 0;   // (PT_OPT_FUSE_STAGES: in the last shade launch)
     if (plan.kernel == PT_KERNEL_WAVEFRONT) {
-        rc = render_wavefront(c, P, plan.L, plan.work_tiles, folded);
-        if (rc != PT_OK) return rc;
+        if ((rc = render_wavefront(c, P, plan)) != PT_OK) return rc;
     } else if (plan.kernel == PT_KERNEL_PERSISTENT) {
         HIP_TRY(c, queue_reset(P.queue, trace_stream));
         HIP_TRY(c, launch_persist(plan.L, P, trace_stream));
@@ -643,7 +574,7 @@ int pt_render_moments(pt_ctx* c, float* accum_dev, uint32_t* rgba_dev, float* mo
         HIP_TRY(c, hipEventRecord(sd->folded, c->stream));
         sd->fold_pending = true;
     }
-    if (probe >= 0) HIP_TRY(c, hipEventRecord(plan.pick->e[2 * probe + 1], c->stream));
+    if (probe >= 0) HIP_TRY(c, hipEventRecord(pick->e[2 * probe + 1], c->stream));
     HIP_TRY(c, span_end(c));
     return PT_OK;
 }
@@ -663,15 +594,16 @@ int pt_auto_choice(pt_ctx* c, int* kernel, float* ms_persistent, float* ms_wavef
 
 int pt_trace_rays(pt_ctx* c, const float* rays_dev, size_t n, int cull, float* t_dev, int32_t* tri_dev, float* normal_dev) {
     if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
-    if (!c->tree.has_bvh) return fail(c, PT_ERR_NO_SCENE, "pt_trace_rays: no BVH uploaded");
-    if (c->tree.records_woop) return fail(c, PT_ERR_UNSUPPORTED, "pt_trace_rays: the ray-batch kernel reads Moller-Trumbore records (upload with PT_OPT_TRI_TEST 0)");
+    const CtxFacts f = ctx_facts(c);
+    if (!f.has_bvh) return fail(c, PT_ERR_NO_SCENE, "pt_trace_rays: no BVH uploaded");
+    if (f.records_woop) return fail(c, PT_ERR_UNSUPPORTED, "pt_trace_rays: the ray-batch kernel reads Moller-Trumbore records (upload with PT_OPT_TRI_TEST 0)");
     if (n == 0) return PT_OK;
     if (!rays_dev || !t_dev || !tri_dev) return fail(c, PT_ERR_INVALID, "pt_trace_rays: null argument");
     HIP_TRY(c, hipSetDevice(c->device));
     KScene sc;
     scene_view(c, sc);
     HIP_TRY(c, span_begin(c));
-    const size_t lds = binary_ray_layout(c, sc);
+    const size_t lds = binary_ray_layout(f, sc);
     HIP_TRY(c, launch_rays(sc, lds, (const float4*)rays_dev, n, cull, t_dev, tri_dev, normal_dev, c->stream));
     HIP_TRY(c, span_end(c));
     return PT_OK;
@@ -681,14 +613,15 @@ int pt_trace_rays(pt_ctx* c, const float* rays_dev, size_t n, int cull, float* t
 static int query_call(pt_ctx* c, const char* who, bool outputs, const ptmi::QueryCall& q) {
     const std::string name(who);
     if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
-    if (!c->tree.has_bvh) return fail(c, PT_ERR_NO_SCENE, name + ": no BVH uploaded");
-    if (c->tree.records_woop) return fail(c, PT_ERR_UNSUPPORTED, name + ": ray-batch queries read Moller-Trumbore records (upload with PT_OPT_TRI_TEST 0)");
+    const CtxFacts f = ctx_facts(c);
+    if (!f.has_bvh) return fail(c, PT_ERR_NO_SCENE, name + ": no BVH uploaded");
+    if (f.records_woop) return fail(c, PT_ERR_UNSUPPORTED, name + ": ray-batch queries read Moller-Trumbore records (upload with PT_OPT_TRI_TEST 0)");
     if (q.n == 0) return PT_OK;
     if (!q.rays || !outputs) return fail(c, PT_ERR_INVALID, name + ": null argument");
     if (q.n >= (1ull << 32)) return fail(c, PT_ERR_INVALID, name + ": more than 2^32 - 1 rays in one call");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, span_begin(c));
-    HIP_TRY(c, launch_query(c, q));
+    HIP_TRY(c, launch_query(c, plan_query(f, q.n, q.hit != nullptr), q));
     HIP_TRY(c, span_end(c));
     return PT_OK;
 }
@@ -701,45 +634,27 @@ int pt_any_hits(pt_ctx* c, const float* rays_dev, size_t n, int cull, uint8_t* h
     return query_call(c, "pt_any_hits", hit_dev != nullptr, ptmi::QueryCall{rays_dev, n, cull, nullptr, nullptr, nullptr, hit_dev});
 }
 
-// slots of one pt_render_rays launch: what keeps its sample buffer below 768 MiB; more samples than that go out as several
-// launches, which the fold's order makes the same thing
-static constexpr uint64_t RAYS_MAX_SLOTS = 1ull << 26;
-
 int pt_render_rays(pt_ctx* c, const float* rays_dev, size_t n_rays, uint64_t first_index, float* radiance_dev, const pt_params* p,
                    uint32_t spp, int mode) {
     if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
-    if (!c->tree.has_bvh && c->n_spheres == 0) return fail(c, PT_ERR_NO_SCENE, "pt_render_rays: no scene uploaded");
-    if (n_rays == 0 || spp == 0) return PT_OK;
-    if (!rays_dev || !radiance_dev || !p) return fail(c, PT_ERR_INVALID, "pt_render_rays: null argument");
-    if (mode != PT_RAYS_CLAMPED && mode != PT_RAYS_HDR) return fail(c, PT_ERR_INVALID, "pt_render_rays: mode must be PT_RAYS_CLAMPED or PT_RAYS_HDR");
-    if (n_rays >= (1ull << 32)) return fail(c, PT_ERR_INVALID, "pt_render_rays: more than 2^32 - 1 rays in one call");
-    // ... then pt_render's own conditions on the fields both read
-    if (p->sample_index == 0) return fail(c, PT_ERR_INVALID, "pt_render_rays: sample_index starts at 1");
-    if (p->tri_mat < PT_MAT_DIFF || p->tri_mat > PT_MAT_REFR) return fail(c, PT_ERR_INVALID, "pt_render_rays: bad triangle material");
-    if ((p->flags & PT_FLAG_NEE) && !(p->flags & PT_FLAG_COSINE_DIFF)) return fail(c, PT_ERR_INVALID, "pt_render_rays: PT_FLAG_NEE needs PT_FLAG_COSINE_DIFF");
-    if ((p->flags & PT_FLAG_MIS) && !(p->flags & PT_FLAG_NEE)) return fail(c, PT_ERR_INVALID, "pt_render_rays: PT_FLAG_MIS needs PT_FLAG_NEE");
+    const CtxFacts f = ctx_facts(c);
+    const CallFacts a = {false, p, spp, rays_dev && radiance_dev, false, false, n_rays, mode};
+    Refusal r = check_path_call(f, a);
+    if (r.code != PT_OK || r.nothing) return fail(c, r);
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = refresh_tri_lights(c, p);
+    int rc = refresh_tri_lights(c, f, p);
     if (rc != PT_OK) return rc;
-    const int walk = choose_walk(c, "pt_render_rays", false);   // (0 runs as 1: launch_render_rays has no while-while walk)
-    if (walk < 0) return walk;
-    const bool mis = (p->flags & PT_FLAG_MIS) != 0;
-    if (mis && walk == 3) return fail(c, PT_ERR_UNSUPPORTED, "pt_render_rays: PT_FLAG_MIS needs the exact (Moller-Trumbore) records (upload with PT_OPT_TRI_TEST 0)");
+    RaysPlan plan;
+    r = plan_rays(f, a, plan);
+    if (r.code != PT_OK) return fail(c, r);
     KParams P;
-    fill_path_params(c, p, spp, P);
-    ptmi::LaunchCfg L = {};   // (no instrumented kernel; the register budget is rays_word's: by PT_FLAG_NEE)
-    L.walk = walk;
-    L.lstk = P.sc.stack_n = 16;
-    P.sc.top_base = walk >= 2 ? P.sc.wide_root : 0;
-    L.lds = (size_t)L.lstk * PT_BLOCK * 4;
-    P.sph_tab = c->opt_sph_lds ? lds_sphere_table(L.lds) : -1;
-    L.n_cu = c->n_cu;
-    L.env = c->env.code();
-    L.nee = (p->flags & PT_FLAG_NEE) != 0;
-    L.mis = mis;
-    queue_params(c, c->d_queue.get(), P);   // the context's counters: every use is on the caller's stream, behind a reset of its own
+    fill_path_params(c, f, p, spp, P);
+    P.sc.stack_n = plan.L.lstk;
+    P.sc.top_base = plan.L.walk >= 2 ? P.sc.wide_root : 0;
+    P.sph_tab = plan.sph_tab;
+    queue_params(plan.q, c->d_queue.get(), P);   // the context's counters: every use is on the caller's stream, behind a reset of its own
     const ptmi::RaysCall R{rays_dev, radiance_dev, first_index, n_rays, mode == PT_RAYS_HDR};
-    const uint32_t per_launch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(spp, RAYS_MAX_SLOTS / n_rays));
+    const uint32_t per_launch = plan.per_launch;
     if (per_launch > 1 && (rc = samples_reserve(c, nullptr, (size_t)per_launch * n_rays * 3, P)) != PT_OK) return rc;
     P.smp_ss = n_rays;
     P.smp_ps = 1u;
@@ -748,11 +663,9 @@ int pt_render_rays(pt_ctx* c, const float* rays_dev, size_t n_rays, uint64_t fir
         P.spp = std::min(per_launch, spp - s0);
         P.frame = p->frame + s0;
         P.sample_index = p->sample_index + s0;
-        const uint64_t slots = (uint64_t)n_rays * (per_launch > 1 ? P.spp : 1u);
-        P.chunk = queue_chunk(c, slots);
-        L.work_blocks = (int)std::min<uint64_t>((slots + (uint64_t)P.chunk * 4 - 1) / ((uint64_t)P.chunk * 4), (uint64_t)INT_MAX);
+        P.chunk = plan_rays_launch(f, a, plan, P.spp, plan.L.work_blocks);
         HIP_TRY(c, queue_reset(P.queue, c->stream));
-        HIP_TRY(c, launch_render_rays(L, P, R, c->stream));
+        HIP_TRY(c, launch_render_rays(plan.L, P, R, c->stream));
         if (per_launch > 1) HIP_TRY(c, launch_fold_rays(c, P, R));
     }
     HIP_TRY(c, span_end(c));

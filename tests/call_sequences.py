@@ -248,7 +248,7 @@ class Op:
                 return True
             return s.tree is not None and (a[0] == "dark" or s.tree.mesh == "cornell_box")
         if k == "refused":
-            if a[0] == "spp_2_20":   # the pipeline must be what the call would run (plan_call's wave_ok), or it is no refusal
+            if a[0] == "spp_2_20":   # the pipeline must be what the call would run (plan_walk's wave_ok), or it is no refusal
                 return s.tree is not None and s.env is None and s.opt("KERNEL") == g.KERNEL_WAVEFRONT and s.opt("WALK") == 2
             if a[0] == "refit_count":
                 return s.tree is not None

@@ -1,5 +1,5 @@
 """The traversal stack at full depth (TravStack in csrc/pt_walks.h: the LDS window of 16, 24 or all 72 entries, the private overflow
-array behind it; the packet walk's per-wave stack; plan_call's `3 * wide_depth + 2 <= PT_STACK_CAP` rule) on the hand-built trees of
+array behind it; the packet walk's per-wave stack; the planner's `3 * wide_depth + 2 <= PT_STACK_CAP` rule) on the hand-built trees of
 tests/deep_trees.py, whose CPU side tests/test_deep_trees.py checks.
 
 The scenes are tiny (at most a few hundred triangles, 64 x 64 pixels, 128 rays) and every stack entry decides some ray's answer:

@@ -24,7 +24,7 @@ the sample buffer held.  So every setting (`run`):
   (c) the frame is not empty and differs from the poison frame.
 
 WHY NO SETTING CAN SPIN (read off the loops before the first run; b = batch, r = refill as the kernel gets them)
-  - k_trace_persist_bvh2 / k_render_rays.  queue_params clamps r <= b.  A walk (every trav_run_*) only returns early when
+  - k_trace_persist_bvh2 / k_render_rays.  queue_knobs (pt_plan.h) clamps r <= b.  A walk (every trav_run_*) only returns early when
     64 - live - dead >= b lanes wait: they are finished walkers, lanes to shade, or idle lanes of a queue that is not empty (idle
     lanes of an empty queue are `dead` and never count).  Finished walkers and lanes to shade are shaded in the same round:
     progress.  If none of the b waiting lanes is one of those, all b are idle with work left, and b >= r triggers the refill at the
@@ -299,7 +299,7 @@ def test_two_calls_overlapped_or_in_line(case, walk):
 
 # ------------------------------------------------------------------------------------------------ the three chunk sizes
 def queue_chunk(n_cu, slots):
-    """pt_ctx.h::queue_chunk"""
+    """pt_plan.h::queue_chunk"""
     waves = n_cu * 20
     return 64 if slots // 64 >= 4 * waves else 32 if slots // 32 >= 4 * waves else 16
 

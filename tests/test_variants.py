@@ -32,11 +32,16 @@ def test_variants_check_program(san):
 
 
 def test_the_library_includes_no_check_program():
-    """The check program stays out of libptmi.so; the header it checks is one the kernels' objects depend on and is plain C++:
-    it includes nothing of the project but the C ABI's constants and names no runtime call."""
+    """The check program stays out of libptmi.so; the headers it checks are ones the kernels' objects depend on and are plain C++:
+    they include nothing of the project but the C ABI's constants (the planner: and the variant words), and name no runtime call
+    and no runtime type."""
     make = open(os.path.join(PKG, "Makefile"), encoding="utf-8").read()
     assert "pt_variants_check" not in re.search(r"^OBJS = (.*)$", make, re.M).group(1)
-    assert re.search(r"^KHDR = .*csrc/pt_variants\.h", make, re.M)
-    text = open(os.path.join(CSRC, "pt_variants.h"), encoding="utf-8").read()
-    assert re.findall(r'#include [<"](.*)[>"]', text) == ["cstdint", "../../include/ptmi.h"]
-    assert not re.search(r"\bhip[A-Z]\w*\(|__device__|__global__", text)
+    includes = {"pt_variants.h": ["cstdint", "../../include/ptmi.h"],
+                "pt_plan.h": ["algorithm", "climits", "cstdint", "string", "../../include/ptmi.h", "pt_variants.h"]}
+    for header, expected in includes.items():
+        assert re.search(r"^KHDR = .*csrc/%s\b" % re.escape(header), make, re.M), header
+        assert re.search(r"^csrc/pt_variants_check: .*csrc/%s\b" % re.escape(header), make, re.M), header
+        text = open(os.path.join(CSRC, header), encoding="utf-8").read()
+        assert re.findall(r'#include [<"](.*)[>"]', text) == expected, header
+        assert not re.search(r"\bhip[A-Z]\w*\(|\bhip\w+_t\b|__device__|__global__|\bfloat4\b|\bdim3\b", text), header
