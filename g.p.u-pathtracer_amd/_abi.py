@@ -41,6 +41,13 @@ class DenoiseParams(C.Structure):
                 ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float)]
 
 
+class DenoiseVarianceParams(C.Structure):
+    """pt_denoise_variance_params — the variance-guided filter of pt_denoise_variance (extension, include/ptmi.h; 32 bytes)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32),
+                ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float),
+                ("samples_per_frame", C.c_float), ("_pad", C.c_int32)]
+
+
 class TemporalParams(C.Structure):
     """pt_temporal_params — the reprojection of pt_temporal (extension, include/ptmi.h; 24 bytes)."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("max_history", C.c_float),
@@ -141,9 +148,11 @@ PTMI_SYMBOLS = [
     ("pt_environment_pdf", _i, [_vp, _vp, _sz, _vp]),
     ("pt_render_aux", _i, [_vp, C.POINTER(Camera), C.POINTER(Params), _vp, _vp, _vp, _vp]),
     ("pt_denoise", _i, [_vp, C.POINTER(DenoiseParams), _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("pt_denoise_variance", _i, [_vp, C.POINTER(DenoiseVarianceParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("pt_temporal", _i, [_vp, C.POINTER(TemporalParams), C.POINTER(Camera), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("pt_temporal_motion", _i, [_vp, C.POINTER(TemporalParams), C.POINTER(Camera), _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                 _vp]),
+    ("pt_temporal_moments", _i, [_vp, C.POINTER(TemporalParams), C.POINTER(Camera), _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("pt_build_bvh", _i, [_vp, _vp, C.c_size_t, _vp, C.c_size_t]),
     ("pt_last_build_ms", _i, [_vp, C.POINTER(C.c_float)]),
     ("pt_refit_bvh", _i, [_vp, _vp, _sz, _vp]),

@@ -1,6 +1,7 @@
 // pt_denoise.hip — pt_render_aux (first-hit guide buffers), pt_denoise (edge-avoiding a-trous wavelet filter, Dammertz et
-// al. 2010), pt_temporal (the history of earlier frames reprojected into a new one, §10 f8) and
-// pt_temporal_motion (the same for triangles moved by pt_refit_bvh, §10 f14).  One translation unit of libptmi.so (pt_ctx.h).
+// al. 2010), pt_temporal (the history of earlier frames reprojected into a new one, §10 f8),
+// pt_temporal_motion (the same for triangles moved by pt_refit_bvh, §10 f14), pt_denoise_variance (the filter steered by each pixel's
+// variance) and pt_temporal_moments (the moments reprojected as the colour is, §10 f15).  One translation unit of libptmi.so (pt_ctx.h).
 //   k_render_aux     one lane per pixel, a 256-thread block per 16x16 tile (one wave per 8x8 quadrant): the pixel-centre camera
 //                    ray, the binary closest-hit walk of pt_trace_rays, the spheres by pt_closest_sphere; albedo, normal,
 //                    position (+ t) as float4 rows, the hit id
@@ -19,6 +20,15 @@
 //                    step — the pixel's triangle row in the previous and the current vertex buffer, a dwordx3 per vertex, and for
 //                    a row that changed the point the pixel's barycentric coordinates had on the previous triangle; that
 //                    point, not the pixel's own, is projected and tested (+ the motion, when asked for)
+//   k_dv_seed<COPY>  pt_denoise_variance: colour / albedo and the variance of the mean luminance from the
+//                    moments into ping-pong buffer A as float4 (i, v) — the hit flag rides in the SIGN BIT of v (a miss with
+//                    variance 0 is -0.0f, so the flag is read as a bit, never with < 0); COPY is iterations = 0
+//   k_dv_iter<LAST>  k_dn_iter's launch shape and tap budget (one dwordx4 of (i, v); normal and position only where both ends
+//                    are hits; one v_exp_f32); per PIXEL, not per tap: the 3x3 pre-filter of v (eight dword loads from L1 —
+//                    no LDS apron, so no barrier and the lanes outside the image still leave at once) and one division for the
+//                    luminance stop 1 / (sigma_l sd + 1e-4); v travels as sum w^2 v / (sum w)^2
+//   k_temporal_moments<IDS, MOVED>  pt_temporal_moments: tm_pixel with the (m1, m2) payload — pt_temporal's rule (MOVED 0) or
+//                    pt_temporal_motion's (MOVED 1, also the launch without a history); no length, no display word
 //   k_frame_error    pt_frame_error: one lane per pixel, the relative standard error of the mean luminance from the moments
 //                    pt_render_moments keeps; a block adds its 256 values up in LDS, in double, and writes
 //                    ONE partial sum and ONE count to its own slot — the host adds the slots in block order
@@ -186,6 +196,140 @@ __global__ void __launch_bounds__(PTD_BLOCK) k_dn_iter(const DnArgs A) {
     }
 }
 
+// pt_denoise_variance (include/ptmi.h states the arithmetic, tests/denoise_var_ref.py restates it)
+struct DvArgs {
+    const float* color;                   // [H][W][3] (out may alias it)
+    const float2* __restrict__ moments;   // [H][W] (m1, m2)
+    const float* __restrict__ length;     // [H][W] frames behind the moments; null = 1
+    const float4* __restrict__ albedo;
+    const float4* __restrict__ normal;
+    const float4* __restrict__ position;
+    const float4* __restrict__ src;       // ping-pong (i, v): the sign bit of v set = the pixel is a miss
+    float4* __restrict__ dst;
+    float* out;                           // [H][W][3], may alias color
+    float* __restrict__ out_var;          // [H][W], may be null
+    uint32_t* rgba;                       // may be null
+    int W, H;
+    int step;                             // 2^l
+    float spf;                            // samples behind one frame of the moments
+    float sl;                             // sigma_luminance, 0 = off
+    float kn, kx;                         // log2(e) / sigma^2 of the normal and the position term, 0 = off
+};
+
+__device__ __forceinline__ float dv_lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+__device__ __forceinline__ bool dv_is_miss(float v) { return (__float_as_uint(v) >> 31) != 0u; }   // -0.0f is a miss too
+
+// The seed: (c / a', var_p / L(a')^2) into ping-pong buffer A.  COPY (iterations = 0): out = color bit for bit, out_var = var_p.
+template <bool COPY>
+__global__ void __launch_bounds__(PTD_BLOCK) k_dv_seed(const DvArgs A) {
+    int x, y;
+    if (!ptd_pixel(A, x, y)) return;
+    const size_t p = (size_t)y * (size_t)A.W + (size_t)x;
+    const float2 m = A.moments[p];
+    const float n = A.spf * (A.length ? A.length[p] : 1.0f);
+    const float var = fminf(fmaxf(n >= 2.0f ? fmaxf(0.f, m.y - m.x * m.x) / (n - 1.0f) : m.y, 0.f), 1e30f);   // NaN: 0
+    const float r = A.color[3 * p], g = A.color[3 * p + 1], b = A.color[3 * p + 2];
+    if (COPY) {
+        A.out[3 * p] = r; A.out[3 * p + 1] = g; A.out[3 * p + 2] = b;
+        if (A.rgba) A.rgba[p] = pt_pack_rgba(r, g, b);
+        if (A.out_var) A.out_var[p] = var;
+    } else {
+        const float4 a = A.albedo[p], nr = A.normal[p];
+        const float ax = ptd_demod_div(a.x), ay = ptd_demod_div(a.y), az = ptd_demod_div(a.z);
+        const float la = dv_lum(ax, ay, az);
+        const float v0 = var / (la * la);
+        const bool hit = nr.x != 0.f || nr.y != 0.f || nr.z != 0.f;
+        A.dst[p] = make_float4(r / ax, g / ay, b / az, hit ? v0 : __uint_as_float(__float_as_uint(v0) | 0x80000000u));
+    }
+}
+
+// One iteration.  Per pixel: the 3x3 pre-filter of v (eight dword loads of adjacent pixels, from L1: the step-1 taps of the same
+// tile touch the same lines) and one division for the luminance stop; per tap k_dn_iter's budget.
+template <bool LAST>
+__global__ void __launch_bounds__(PTD_BLOCK) k_dv_iter(const DvArgs A) {
+    int x, y;
+    if (!ptd_pixel(A, x, y)) return;
+    const size_t p = (size_t)y * (size_t)A.W + (size_t)x;
+    const float4 cp = A.src[p];
+    const bool mp = dv_is_miss(cp.w);
+    const bool hp = !mp;
+    const float vp = fabsf(cp.w);
+    float4 np = make_float4(0.f, 0.f, 0.f, 0.f), xp = np;
+    float kxp = 0.f;
+    if (hp) {
+        np = A.normal[p];
+        xp = A.position[p];
+        kxp = fminf(A.kx / (xp.w * xp.w), 1e30f);   // 1 / (sigma_x t_p)^2, finite
+    }
+    // g_p: the (1,2,1)x(1,2,1) mean of v over the adjacent pixels with p's hit flag
+    float gs = 4.0f * vp, gw = 4.0f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; dy++) {
+        const int yq = y + dy;
+        if (yq < 0 || yq >= A.H) continue;
+#pragma unroll
+        for (int dx = -1; dx <= 1; dx++) {
+            const int xq = x + dx;
+            if ((dx == 0 && dy == 0) || xq < 0 || xq >= A.W) continue;
+            const float vq = A.src[(size_t)yq * (size_t)A.W + (size_t)xq].w;
+            if (dv_is_miss(vq) != mp) continue;
+            const float gk = (float)((2 - (dx < 0 ? -dx : dx)) * (2 - (dy < 0 ? -dy : dy)));
+            gs = fmaf(gk, fabsf(vq), gs); gw += gk;
+        }
+    }
+    const float sd = sqrtf(fmaxf(gs / gw, 0.f));
+    const float kl = A.sl > 0.f ? 1.44269504f / fmaf(A.sl, sd, 1e-4f) : 0.f;   // log2(e) k_p
+    const float lp = dv_lum(cp.x, cp.y, cp.z);
+    const float hk[5] = {1.f / 16.f, 4.f / 16.f, 6.f / 16.f, 4.f / 16.f, 1.f / 16.f};
+    float sr = 0.f, sg = 0.f, sb = 0.f, sw = 0.f, sv = 0.f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+        const int yq = y + dy * A.step;
+        if (yq < 0 || yq >= A.H) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const int xq = x + dx * A.step;
+            if (xq < 0 || xq >= A.W) continue;
+            const float hh = hk[dy + 2] * hk[dx + 2];
+            if (dx == 0 && dy == 0) {   // the centre: e = 0
+                sr = fmaf(hh, cp.x, sr); sg = fmaf(hh, cp.y, sg); sb = fmaf(hh, cp.z, sb); sw += hh;
+                sv = fmaf(hh * hh, vp, sv);
+                continue;
+            }
+            const size_t q = (size_t)yq * (size_t)A.W + (size_t)xq;
+            const float4 cq = A.src[q];
+            if (dv_is_miss(cq.w) != mp) continue;   // exactly one of p, q is a miss
+            float e = kl * fabsf(lp - dv_lum(cq.x, cq.y, cq.z));
+            if (hp) {
+                const float4 nq = A.normal[q], xq4 = A.position[q];
+                const float ax = np.x - nq.x, ay = np.y - nq.y, az = np.z - nq.z;
+                const float bx = xp.x - xq4.x, by = xp.y - xq4.y, bz = xp.z - xq4.z;
+                e = fmaf(A.kn, fmaf(az, az, fmaf(ay, ay, ax * ax)), e);
+                e = fmaf(kxp, fmaf(bz, bz, fmaf(by, by, bx * bx)), e);
+            }
+            const float w = hh * __builtin_amdgcn_exp2f(-e);   // one v_exp_f32
+            sr = fmaf(w, cq.x, sr); sg = fmaf(w, cq.y, sg); sb = fmaf(w, cq.z, sb); sw += w;
+            sv = fmaf(w * w, fabsf(cq.w), sv);
+        }
+    }
+    const float inv = 1.0f / sw;
+    const float r = sr * inv, g = sg * inv, b = sb * inv;
+    const float v = sv * (inv * inv);
+    if (!LAST) {
+        A.dst[p] = make_float4(r, g, b, mp ? __uint_as_float(__float_as_uint(v) | 0x80000000u) : v);
+    } else {
+        const float4 a = A.albedo[p];
+        const float ax = ptd_demod_div(a.x), ay = ptd_demod_div(a.y), az = ptd_demod_div(a.z);
+        const float o0 = pt_clamp01(r * ax), o1 = pt_clamp01(g * ay), o2 = pt_clamp01(b * az);
+        A.out[3 * p] = o0; A.out[3 * p + 1] = o1; A.out[3 * p + 2] = o2;
+        if (A.rgba) A.rgba[p] = pt_pack_rgba(o0, o1, o2);
+        if (A.out_var) {
+            const float la = dv_lum(ax, ay, az);
+            A.out_var[p] = v * (la * la);
+        }
+    }
+}
+
 // pt_temporal (include/ptmi.h states the arithmetic, tests/temporal_ref.py restates it)
 struct TmArgs {
     const float* __restrict__ prev_color;      // [H][W][3]; never the out buffers (checked on the host)
@@ -242,12 +386,16 @@ __device__ __forceinline__ bool tm_positive_finite(float a) { return a > 0.f && 
 // One pixel of k_temporal (MOVED 0: M unused, and nothing below differs from what the kernel held before the two shared it) and
 // of k_temporal_motion (MOVED 1; 2 = the motion is written as well).  The projection, the taps and the blend are the same
 // statements for both, so a surface point that did not move gets k_temporal<true>'s bits.
-template <bool IDS, int MOVED>
+// PAY 3: the payload is the colour.  PAY 2 (pt_temporal_moments): the buffers named *_color hold (m1, m2) rows, the blend runs on
+// those two, and neither a length nor a display word is written; every other statement is shared.
+template <bool IDS, int MOVED, int PAY = 3>
 __device__ __forceinline__ void tm_pixel(const TmArgs& A, const TmMotionArgs* M) {
     int x, y;
     if (!ptd_pixel(A, x, y)) return;
     const size_t p = (size_t)y * (size_t)A.W + (size_t)x;
-    const float cr = A.cur_color[3 * p], cg = A.cur_color[3 * p + 1], cb = A.cur_color[3 * p + 2];
+    const float cr = A.cur_color[PAY * p], cg = A.cur_color[PAY * p + 1];
+    float cb = 0.f;
+    if constexpr (PAY == 3) cb = A.cur_color[3 * p + 2];
     const float4 n4 = (MOVED != 0 && !A.prev_color) ? make_float4(0.f, 0.f, 0.f, 0.f) : A.cur_normal[p];   // no history: every pixel as a miss
     float o0 = cr, o1 = cg, o2 = cb, on = 1.0f;   // no history accepted: the current frame, bit for bit
     float mx = 0.f, my = 0.f;
@@ -316,8 +464,9 @@ __device__ __forceinline__ void tm_pixel(const TmArgs& A, const TmMotionArgs* M)
                         if (!(vdot(np, V3(nq.x, nq.y, nq.z)) >= A.normal_thr)) continue;
                         const v3 dq = vsub(V3(xq4.x, xq4.y, xq4.z), xp);
                         if (!(fabsf(vdot(np, dq)) <= tol)) continue;
-                        const float* c = A.prev_color + 3 * q;
-                        sr = fmaf(w, c[0], sr); sg = fmaf(w, c[1], sg); sb = fmaf(w, c[2], sb);
+                        const float* c = A.prev_color + PAY * q;
+                        sr = fmaf(w, c[0], sr); sg = fmaf(w, c[1], sg);
+                        if constexpr (PAY == 3) sb = fmaf(w, c[2], sb);
                         sl = fmaf(w, A.prev_len[q], sl);
                         sw += w;
                     }
@@ -331,6 +480,10 @@ __device__ __forceinline__ void tm_pixel(const TmArgs& A, const TmMotionArgs* M)
                 }
             }
         }
+    }
+    if constexpr (PAY == 2) {
+        A.out_color[2 * p] = o0; A.out_color[2 * p + 1] = o1;
+        return;
     }
     A.out_color[3 * p] = o0; A.out_color[3 * p + 1] = o1; A.out_color[3 * p + 2] = o2;
     A.out_len[p] = on;
@@ -348,6 +501,13 @@ __global__ void __launch_bounds__(PTD_BLOCK) k_temporal(const TmArgs A) {
 template <bool MOTION>
 __global__ void __launch_bounds__(PTD_BLOCK) k_temporal_motion(const TmMotionArgs M) {
     tm_pixel<true, MOTION ? 2 : 1>(M.t, &M);
+}
+
+// pt_temporal_moments: tm_pixel with the (m1, m2) payload.  MOVED 0: pt_temporal's rule (IDS as there); MOVED 1: pt_temporal_motion's
+// rule, which is also the launch without a history (every pixel as a miss: out = cur).
+template <bool IDS, int MOVED>
+__global__ void __launch_bounds__(PTD_BLOCK) k_temporal_moments(const TmMotionArgs M) {
+    tm_pixel<IDS, MOVED, 2>(M.t, &M);
 }
 
 // pt_frame_error: rse of pixel i in binary32 (include/ptmi.h states the formula); per block the sum of rse in double and the
@@ -468,15 +628,83 @@ extern "C" int pt_denoise(pt_ctx* c, const pt_denoise_params* dp, const float* c
     return PT_OK;
 }
 
+extern "C" int pt_denoise_variance(pt_ctx* c, const pt_denoise_variance_params* dp, const float* color_dev, const float* moments_dev,
+                                   const float* length_dev, const float* albedo_dev, const float* normal_dev, const float* position_dev,
+                                   float* out_dev, float* out_variance_dev, uint32_t* rgba_dev) {
+    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
+    if (!dp || !color_dev || !albedo_dev || !normal_dev || !position_dev || !out_dev) return fail(c, PT_ERR_INVALID, "pt_denoise_variance: null argument");
+    if (dp->width < 1 || dp->height < 1) return fail(c, PT_ERR_INVALID, "pt_denoise_variance: width and height must be >= 1");
+    if (dp->iterations < 0 || dp->iterations > 10) return fail(c, PT_ERR_INVALID, "pt_denoise_variance: iterations must be 0..10");
+    if (!std::isfinite(dp->sigma_luminance) || !std::isfinite(dp->sigma_normal) || !std::isfinite(dp->sigma_position))
+        return fail(c, PT_ERR_INVALID, "pt_denoise_variance: a sigma is not finite");
+    if (!moments_dev) return fail(c, PT_ERR_INVALID, "pt_denoise_variance: null moments");
+    if (!std::isfinite(dp->samples_per_frame) || dp->samples_per_frame < 1.f)
+        return fail(c, PT_ERR_INVALID, "pt_denoise_variance: samples_per_frame must be finite and >= 1");
+    if (out_variance_dev) {
+        const void* inputs[] = {color_dev, moments_dev, length_dev, albedo_dev, normal_dev, position_dev};
+        for (const void* o : inputs)
+            if (o == (const void*)out_variance_dev) return fail(c, PT_ERR_INVALID, "pt_denoise_variance: out_variance_dev may not be one of the inputs");
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n_pix = (size_t)dp->width * (size_t)dp->height;
+    DvArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.color = color_dev;
+    A.moments = (const float2*)moments_dev;
+    A.length = length_dev;
+    A.albedo = (const float4*)albedo_dev;
+    A.normal = (const float4*)normal_dev;
+    A.position = (const float4*)position_dev;
+    A.out = out_dev;
+    A.out_var = out_variance_dev;
+    A.rgba = rgba_dev;
+    A.W = dp->width; A.H = dp->height;
+    A.spf = dp->samples_per_frame;
+    const dim3 grid((unsigned)((dp->width + PTD_TILE - 1) / PTD_TILE), (unsigned)((dp->height + PTD_TILE - 1) / PTD_TILE));
+    const int L = dp->iterations;
+    float4* ping[2] = {nullptr, nullptr};
+    if (L > 0) {   // pt_denoise's scratch, by its rule
+        if (2 * n_pix > c->d_denoise.count()) HIP_TRY(c, hipStreamSynchronize(c->stream));   // the old frames may still be read by an earlier call's launches
+        HIP_TRY(c, c->d_denoise.reserve(2 * n_pix));
+        ping[0] = c->d_denoise.get();
+        ping[1] = ping[0] + n_pix;
+    }
+    auto k_of = [](double sigma) -> float {   // log2(e) / sigma^2, as pt_denoise
+        if (!(sigma > 0.0)) return 0.f;
+        return (float)std::min(1.4426950408889634 / (sigma * sigma), 1e30);
+    };
+    hipStream_t st = c->stream;
+    HIP_TRY(c, span_begin(c));
+    if (L == 0) {
+        hipLaunchKernelGGL(k_dv_seed<true>, grid, dim3(PTD_BLOCK), 0, st, A);
+    } else {
+        A.dst = ping[0];
+        hipLaunchKernelGGL(k_dv_seed<false>, grid, dim3(PTD_BLOCK), 0, st, A);
+        A.sl = dp->sigma_luminance > 0.f ? fminf(dp->sigma_luminance, 1e30f) : 0.f;
+        A.kn = k_of(dp->sigma_normal);
+        A.kx = k_of(dp->sigma_position);
+        for (int l = 0; l < L; l++) {
+            A.step = 1 << l;
+            A.src = ping[l & 1];
+            A.dst = ping[(l + 1) & 1];
+            if (l + 1 < L) hipLaunchKernelGGL(k_dv_iter<false>, grid, dim3(PTD_BLOCK), 0, st, A);
+            else hipLaunchKernelGGL(k_dv_iter<true>, grid, dim3(PTD_BLOCK), 0, st, A);
+        }
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, span_end(c));
+    return PT_OK;
+}
+
 namespace {
 
-// What pt_temporal and pt_temporal_motion share: the argument checks (messages under the caller's name `fn`) and the kernel
+// What pt_temporal, pt_temporal_motion and pt_temporal_moments (with_length false: its payload writes no length) share: the argument checks (messages under the caller's name `fn`) and the kernel
 // arguments of the reprojection.  PT_OK with A filled, or the error already recorded.
 int temporal_args(pt_ctx* c, const std::string& fn, const pt_temporal_params* tp, const pt_camera* prev_cam, const float* prev_color_dev,
                   const float* prev_length_dev, const float* prev_normal_dev, const float* prev_position_dev, const int32_t* prev_id_dev,
                   const float* cur_color_dev, const float* cur_normal_dev, const float* cur_position_dev, const int32_t* cur_id_dev,
-                  float* out_color_dev, float* out_length_dev, uint32_t* rgba_dev, TmArgs& A) {
-    if (!tp || !cur_color_dev || !cur_normal_dev || !cur_position_dev || !out_color_dev || !out_length_dev)
+                  float* out_color_dev, float* out_length_dev, uint32_t* rgba_dev, TmArgs& A, bool with_length = true) {
+    if (!tp || !cur_color_dev || !cur_normal_dev || !cur_position_dev || !out_color_dev || (with_length && !out_length_dev))
         return fail(c, PT_ERR_INVALID, fn + ": null argument");
     if (tp->width < 2 || tp->height < 2) return fail(c, PT_ERR_INVALID, fn + ": width and height must be >= 2");
     if (!std::isfinite(tp->max_history) || tp->max_history < 1.f) return fail(c, PT_ERR_INVALID, fn + ": max_history must be finite and >= 1");
@@ -488,7 +716,7 @@ int temporal_args(pt_ctx* c, const std::string& fn, const pt_temporal_params* tp
         if (!prev_cam || !prev_length_dev || !prev_normal_dev || !prev_position_dev)
             return fail(c, PT_ERR_INVALID, fn + ": a history needs its camera, lengths, normals and positions");
         if ((prev_id_dev == nullptr) != (cur_id_dev == nullptr)) return fail(c, PT_ERR_INVALID, fn + ": ids of both frames or of neither");
-        if (out_color_dev == prev_color_dev || out_length_dev == prev_length_dev)
+        if (out_color_dev == prev_color_dev || (with_length && out_length_dev == prev_length_dev))
             return fail(c, PT_ERR_INVALID, fn + ": the new history may not overwrite the old one (ping-pong the buffers)");
     }
     std::memset(&A, 0, sizeof A);
@@ -581,6 +809,40 @@ extern "C" int pt_temporal_motion(pt_ctx* c, const pt_temporal_params* tp, const
     if (motion_dev) hipLaunchKernelGGL(k_temporal_motion<true>, grid, dim3(PTD_BLOCK), 0, st, M);   // (without a history: out = cur, motion 0)
     else if (history) hipLaunchKernelGGL(k_temporal_motion<false>, grid, dim3(PTD_BLOCK), 0, st, M);
     else hipLaunchKernelGGL(k_tm_first, grid, dim3(PTD_BLOCK), 0, st, M.t);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, span_end(c));
+    return PT_OK;
+}
+
+extern "C" int pt_temporal_moments(pt_ctx* c, const pt_temporal_params* tp, const pt_camera* prev_cam, const float* prev_verts_dev,
+                                   const float* cur_verts_dev, size_t n_tris, const float* prev_moments_dev, const float* prev_length_dev,
+                                   const float* prev_normal_dev, const float* prev_position_dev, const int32_t* prev_id_dev,
+                                   const float* cur_moments_dev, const float* cur_normal_dev, const float* cur_position_dev,
+                                   const int32_t* cur_id_dev, float* out_moments_dev) {
+    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
+    TmMotionArgs M;
+    std::memset(&M, 0, sizeof M);
+    if (int rc = temporal_args(c, "pt_temporal_moments", tp, prev_cam, prev_moments_dev, prev_length_dev, prev_normal_dev, prev_position_dev,
+                               prev_id_dev, cur_moments_dev, cur_normal_dev, cur_position_dev, cur_id_dev, out_moments_dev, nullptr, nullptr,
+                               M.t, false))
+        return rc;
+    const bool history = prev_moments_dev != nullptr;
+    const bool motion = prev_verts_dev != nullptr || cur_verts_dev != nullptr;   // pt_temporal_motion's rule
+    if (history && motion) {
+        if (!prev_id_dev || !cur_id_dev) return fail(c, PT_ERR_INVALID, "pt_temporal_moments: the ids of both frames are required (they choose the vertex rows)");
+        if (n_tris > 0 && (!prev_verts_dev || !cur_verts_dev)) return fail(c, PT_ERR_INVALID, "pt_temporal_moments: a null vertex buffer with n_tris > 0");
+        if (n_tris >= ((size_t)1 << 31)) return fail(c, PT_ERR_INVALID, "pt_temporal_moments: n_tris must be < 2^31 (ids are int32)");
+        M.prev_verts = prev_verts_dev;
+        M.cur_verts = cur_verts_dev;
+        M.n_tris = (uint32_t)n_tris;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const dim3 grid((unsigned)((tp->width + PTD_TILE - 1) / PTD_TILE), (unsigned)((tp->height + PTD_TILE - 1) / PTD_TILE));
+    hipStream_t st = c->stream;
+    HIP_TRY(c, span_begin(c));
+    if (!history || motion) hipLaunchKernelGGL((k_temporal_moments<true, 1>), grid, dim3(PTD_BLOCK), 0, st, M);   // (no history: out = cur)
+    else if (M.t.prev_id) hipLaunchKernelGGL((k_temporal_moments<true, 0>), grid, dim3(PTD_BLOCK), 0, st, M);
+    else hipLaunchKernelGGL((k_temporal_moments<false, 0>), grid, dim3(PTD_BLOCK), 0, st, M);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, span_end(c));
     return PT_OK;

@@ -8,7 +8,7 @@
 //               --depth 4 --mat 0..3 --no-spheres --no-materials --bk r g b --device 0
 //               --out image.ppm|.png|.pfm  --checkpoint state.ckpt [--checkpoint-every N]
 //               --resume state.ckpt --device-build --fix-estimators --nee --mis --gpus N --tile ROWS
-//               --denoise-out image.ppm|.png|.pfm  --variance-out file.pfm  --until-error E --max-frames M
+//               --denoise-out image.ppm|.png|.pfm  --denoise-variance  --variance-out file.pfm  --until-error E --max-frames M
 //               --pan-deg D --dolly S --spin-deg D --temporal-out image.ppm|.png|.pfm  --equirect
 //               --env file.pfm [--env-scale S] [--env-nearest] [--env-light]]
 // --gpus N splits the framebuffer over N contexts, one per GPU (devices device, device+1, ... modulo the number
@@ -25,6 +25,9 @@
 // progressive render: the result is bit-identical to one uninterrupted run.
 // --denoise-out also writes the final accumulator through pt_denoise (guides from pt_render_aux, the library's default
 // filter settings), format by extension as --out; with --gpus N the gathered frame is denoised on the first context.
+// --denoise-variance makes --denoise-out run pt_denoise_variance instead: the run renders through pt_render_moments (as
+// --variance-out does, --out unchanged) and the filter takes those moments with samples_per_frame = the samples per pixel behind
+// the accumulator and no lengths.  Refused without --denoise-out, with --temporal-out and with --resume.
 // --out is written first and is the same image with or without it.
 // --variance-out and --until-error render through pt_render_moments: every context keeps the luminance moments of its stripes
 // beside its accumulator (gathered with it).  --variance-out writes the variance of the pixel's mean luminance,
@@ -88,6 +91,7 @@ static int die(const char* what, const char* msg) {
 
 int main(int argc, char** argv) {
     std::string mesh_path, out_path, ckpt_path, resume_path, denoise_path, variance_path, temporal_path, env_path;
+    bool denoise_variance = false;
     double env_scale = 1.0;
     bool env_scale_set = false, env_nearest = false, env_light = false;
     int W = 1280, H = 720, frames = 16, depth = 4, mat = PT_MAT_DIFF, device = 0, spp = 1, ckpt_every = 0, gpus = 1, tile = 8;
@@ -105,6 +109,7 @@ int main(int argc, char** argv) {
         if (a == "--mesh") mesh_path = next("--mesh");
         else if (a == "--out") out_path = next("--out");
         else if (a == "--denoise-out") denoise_path = next("--denoise-out");
+        else if (a == "--denoise-variance") denoise_variance = true;
         else if (a == "--temporal-out") temporal_path = next("--temporal-out");
         else if (a == "--pan-deg") pan_deg = std::atof(next("--pan-deg"));
         else if (a == "--dolly") dolly = std::atof(next("--dolly"));
@@ -142,7 +147,10 @@ int main(int argc, char** argv) {
     if (spp < 1 || frames < 0 || W < 2 || H < 2) return die("usage", "--spp >= 1, --frames >= 0, --width/--height >= 2");
     if (gpus < 1 || gpus > 64 || tile < 8 || tile % 8) return die("usage", "--gpus 1..64, --tile a positive multiple of 8");
 
-    const bool until = until_error >= 0.0, with_moments = until || !variance_path.empty();
+    const bool until = until_error >= 0.0, with_moments = until || !variance_path.empty() || denoise_variance;
+    if (denoise_variance && denoise_path.empty()) return die("usage", "--denoise-variance goes with --denoise-out");
+    if (denoise_variance && (!temporal_path.empty() || !resume_path.empty()))
+        return die("usage", "--denoise-variance does not combine with --temporal-out or --resume (neither keeps the moments of the samples)");
     if (until && max_frames < (long)frames) return die("usage", "--until-error needs --max-frames >= --frames");
     if (!until && max_frames >= 0) return die("usage", "--max-frames goes with --until-error");
     if (with_moments && !resume_path.empty()) return die("usage", "--variance-out / --until-error do not combine with --resume (a checkpoint holds no moments)");
@@ -567,7 +575,22 @@ int main(int argc, char** argv) {
         }
         const pt_denoise_params dn = {W, H, 4, 0.0f, 1.0f, 0.03f};   // = gpu_pathtracer_amd.DENOISE_DEFAULTS
         if (pt_render_aux(ctx, &cam, &p, (float*)alb, (float*)nrm, (float*)pos, nullptr) != PT_OK) return die("pt_render_aux", pt_last_error(ctx));
-        if (pt_denoise(ctx, &dn, (const float*)color, (const float*)alb, (const float*)nrm, (const float*)pos, (float*)dout, (uint32_t*)drgba) != PT_OK)
+        if (denoise_variance) {   // the luminance stop from the moments of the run; every pixel has constantPdf samples, no lengths
+            void* mom = moments[0];
+            if (gpus > 1) {
+                host_mom.resize(n_pix * 2);
+                if (int grc = gather(moments, host_mom.data(), 8)) return grc;
+                if (pt_malloc(ctx, n_pix * 8, &mom) != PT_OK || pt_upload(ctx, mom, host_mom.data(), n_pix * 8) != PT_OK)
+                    return die("pt_upload", pt_last_error(ctx));
+            }
+            // = gpu_pathtracer_amd.DENOISE_VARIANCE_DEFAULTS
+            const pt_denoise_variance_params dv = {W, H, 4, 4.0f, 1.0f, 0.03f, (float)std::max<uint64_t>(constantPdf, 1), 0};
+            if (pt_denoise_variance(ctx, &dv, (const float*)color, (const float*)mom, nullptr, (const float*)alb, (const float*)nrm,
+                                    (const float*)pos, (float*)dout, nullptr, (uint32_t*)drgba) != PT_OK)
+                return die("pt_denoise_variance", pt_last_error(ctx));
+            if (pt_sync(ctx) != PT_OK) return die("pt_sync", pt_last_error(ctx));
+            if (gpus > 1) pt_free(ctx, mom);
+        } else if (pt_denoise(ctx, &dn, (const float*)color, (const float*)alb, (const float*)nrm, (const float*)pos, (float*)dout, (uint32_t*)drgba) != PT_OK)
             return die("pt_denoise", pt_last_error(ctx));
         const std::string ext = denoise_path.size() > 4 ? denoise_path.substr(denoise_path.size() - 4) : std::string();
         int rc;

@@ -13,11 +13,14 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import Camera, Counters, DenoiseParams, Environment, Material, Params, Sphere, TemporalParams
+from ._abi import Camera, Counters, DenoiseParams, DenoiseVarianceParams, Environment, Material, Params, Sphere, TemporalParams
 
 # pt_denoise defaults (iterations, sigma_color, sigma_normal, sigma_position): chosen by the CPU sweep of DESIGN.md §10 f6;
 # host/pt_app.cpp uses the same values
 DENOISE_DEFAULTS = dict(iterations=4, sigma_color=0.0, sigma_normal=1.0, sigma_position=0.03)
+# pt_denoise_variance defaults: the geometry stops of DENOISE_DEFAULTS and SVGF's luminance stop of 4 standard errors (DESIGN.md §10
+# f15); host/pt_app.cpp uses the same values
+DENOISE_VARIANCE_DEFAULTS = dict(iterations=4, sigma_luminance=4.0, sigma_normal=1.0, sigma_position=0.03)
 # pt_temporal defaults: starting values by definition, not tuned figures; host/pt_app.cpp uses the same values
 TEMPORAL_DEFAULTS = dict(max_history=32.0, plane_tolerance=0.02, normal_threshold=0.9)
 
@@ -274,6 +277,19 @@ class PathTracer:
         dp = DenoiseParams(int(width), int(height), int(iterations), float(sigma_color), float(sigma_normal), float(sigma_position))
         self._check(self._lib.pt_denoise(self._ctx, C.byref(dp), color_ptr, albedo_ptr, normal_ptr, position_ptr, out_ptr, rgba_ptr))
 
+    def denoise_variance(self, color_ptr, moments_ptr, length_ptr, albedo_ptr, normal_ptr, position_ptr, width, height, out_ptr,
+                         out_variance_ptr=None, rgba_ptr=None, samples_per_frame=1.0,
+                         iterations=DENOISE_VARIANCE_DEFAULTS["iterations"], sigma_luminance=DENOISE_VARIANCE_DEFAULTS["sigma_luminance"],
+                         sigma_normal=DENOISE_VARIANCE_DEFAULTS["sigma_normal"], sigma_position=DENOISE_VARIANCE_DEFAULTS["sigma_position"]):
+        """Variance-guided a-trous filter (pt_denoise_variance): denoise() with a luminance stop scaled by each pixel's standard
+        error.  moments float[H][W][2] as launch_kernel(moments_ptr=) keeps them, samples_per_frame the samples behind one frame
+        of them, length (optional) float[H][W] the frames behind each pixel as temporal() writes it; out_variance (optional)
+        float[H][W] receives the variance of the filtered mean luminance.  Asynchronous until sync()."""
+        dp = DenoiseVarianceParams(int(width), int(height), int(iterations), float(sigma_luminance), float(sigma_normal),
+                                   float(sigma_position), float(samples_per_frame), 0)
+        self._check(self._lib.pt_denoise_variance(self._ctx, C.byref(dp), color_ptr, moments_ptr, length_ptr, albedo_ptr, normal_ptr,
+                                                  position_ptr, out_ptr, out_variance_ptr, rgba_ptr))
+
     def temporal(self, width, height, prev_cam, prev_color_ptr, prev_length_ptr, prev_normal_ptr, prev_position_ptr, prev_id_ptr,
                  cur_color_ptr, cur_normal_ptr, cur_position_ptr, cur_id_ptr, out_color_ptr, out_length_ptr, rgba_ptr=None,
                  max_history=TEMPORAL_DEFAULTS["max_history"], plane_tolerance=TEMPORAL_DEFAULTS["plane_tolerance"],
@@ -302,6 +318,19 @@ class PathTracer:
                                                  prev_color_ptr, prev_length_ptr, prev_normal_ptr, prev_position_ptr, prev_id_ptr,
                                                  cur_color_ptr, cur_normal_ptr, cur_position_ptr, cur_id_ptr, out_color_ptr, out_length_ptr,
                                                  rgba_ptr, motion_ptr))
+
+    def temporal_moments(self, width, height, prev_cam, prev_verts, cur_verts, n_tris, prev_moments_ptr, prev_length_ptr, prev_normal_ptr,
+                         prev_position_ptr, prev_id_ptr, cur_moments_ptr, cur_normal_ptr, cur_position_ptr, cur_id_ptr, out_moments_ptr,
+                         max_history=TEMPORAL_DEFAULTS["max_history"], plane_tolerance=TEMPORAL_DEFAULTS["plane_tolerance"],
+                         normal_threshold=TEMPORAL_DEFAULTS["normal_threshold"]):
+        """The luminance moments float[H][W][2] reprojected as temporal() (prev_verts = cur_verts = None) or temporal_motion()
+        reprojects the colour (pt_temporal_moments).  prev_length_ptr is the one the colour call of the same frame reads; no
+        length is written.  prev_moments_ptr=None: no history, out = cur.  Asynchronous until sync()."""
+        pv, cv = (v.ptr if isinstance(v, DeviceBuffer) else v for v in (prev_verts, cur_verts))
+        tp = TemporalParams(int(width), int(height), float(max_history), float(plane_tolerance), float(normal_threshold), 0)
+        self._check(self._lib.pt_temporal_moments(self._ctx, C.byref(tp), C.byref(prev_cam) if prev_cam is not None else None, pv, cv, int(n_tris),
+                                                  prev_moments_ptr, prev_length_ptr, prev_normal_ptr, prev_position_ptr, prev_id_ptr,
+                                                  cur_moments_ptr, cur_normal_ptr, cur_position_ptr, cur_id_ptr, out_moments_ptr))
 
     # ------------------------------------------------------------------ measurement
     def counters(self):
@@ -365,9 +394,12 @@ class TemporalHistory:
     """The ping-pong buffers of a host's temporal accumulation: two history colours, two lengths, two sets of guide buffers and the
     camera of the frame pushed last.  push() is one displayed frame of the loop: guides, reprojection, swap."""
 
-    def __init__(self, tracer, width, height, with_ids=True):
+    def __init__(self, tracer, width, height, with_ids=True, with_moments=False):
         self.t, self.W, self.H = tracer, int(width), int(height)
         n = self.W * self.H
+        # with_moments: two moment histories beside the colours; self.moments = the one the last push wrote (None before it)
+        self.moment = [tracer.malloc(n * 8) for _ in range(2)] if with_moments else []
+        self.moments = None
         self.color = [tracer.malloc(n * 12) for _ in range(2)]
         self.length = [tracer.malloc(n * 4) for _ in range(2)]
         self.guides = [[tracer.malloc(n * 16) for _ in range(3)] + [tracer.malloc(n * 4) if with_ids else None] for _ in range(2)]
@@ -381,14 +413,19 @@ class TemporalHistory:
     def _ptrs(self, k):
         return [b.ptr if b is not None else None for b in self.guides[k]]
 
-    def push(self, cam, params, color_ptr, rgba_ptr=None, moved=None, motion_ptr=None, **temporal):
+    def push(self, cam, params, color_ptr, rgba_ptr=None, moved=None, motion_ptr=None, moments_ptr=None, **temporal):
         """One frame: render_aux for `cam` (params: the frame's pt_params), then temporal() of the frame in color_ptr (rendered
         with sample_index = 1; never written) against the stored history — or with no history the first time — then the swap.
         Returns (color_ptr, length_ptr, (albedo, normal, position, id) ptrs) of the new history; the colour and the guides can be
         passed to denoise() directly.  **temporal: max_history, plane_tolerance, normal_threshold.  Asynchronous.
         moved = (prev_verts_ptr, cur_verts_ptr, n_tris): the triangles moved since the last push (refit_bvh), so the frame goes
         through temporal_motion() (the history needs ids), with motion_ptr as its motion buffer.  The caller owns and ping-pongs
-        the two vertex buffers: the previous one stays unchanged until the push that reads it has been issued."""
+        the two vertex buffers: the previous one stays unchanged until the push that reads it has been issued.
+        moments_ptr (a history made with_moments=True needs it, no other takes it): the frame's moments, as launch_kernel(moments_ptr=)
+        kept them (never written); they are reprojected with the same history and the same lengths by temporal_moments(), and
+        self.moments is the new moment history, to go into denoise_variance() with the returned lengths."""
+        if (moments_ptr is not None) != bool(self.moment):
+            raise ValueError("TemporalHistory.push: moments_ptr goes with with_moments=True")
         k, o = self.cur, 1 - self.cur
         alb, nrm, pos, ids = self._ptrs(k)
         self.t.render_aux(cam, params, alb, nrm, pos, ids)
@@ -404,14 +441,20 @@ class TemporalHistory:
             if motion_ptr is not None:
                 raise ValueError("TemporalHistory.push: motion_ptr goes with moved=")
             self.t.temporal(self.W, self.H, *prev, color_ptr, nrm, pos, ids, self.color[k].ptr, self.length[k].ptr, rgba_ptr, **temporal)
+        if self.moment:
+            pm = None if self.cam is None else self.moment[o].ptr
+            self.t.temporal_moments(self.W, self.H, prev[0], *(moved if moved is not None else (None, None, 0)), pm, *prev[2:],
+                                    moments_ptr, nrm, pos, ids, self.moment[k].ptr, **temporal)
+            self.moments = self.moment[k].ptr
         self.cam = Camera.from_buffer_copy(cam)
         self.cur = o
         return self.color[k].ptr, self.length[k].ptr, (alb, nrm, pos, ids)
 
     def free(self):
-        for b in self.color + self.length + [x for gset in self.guides for x in gset if x is not None]:
+        for b in self.color + self.length + self.moment + [x for gset in self.guides for x in gset if x is not None]:
             b.free()
         self.color, self.length, self.guides, self.cam = [], [], [], None
+        self.moment, self.moments = [], None
 
 
 def algorithmic_bytes(counters, n_spheres):

@@ -741,6 +741,47 @@ int pt_denoise(pt_ctx* ctx, const pt_denoise_params* dp, const float* color_dev,
                const float* albedo_dev, const float* normal_dev, const float* position_dev,
                float* out_dev, uint32_t* rgba_dev);
 
+/* pt_denoise_variance: pt_denoise's filter with its colour stop replaced by a LUMINANCE stop that each pixel scales by the
+ * standard error of its own mean (the variance-guided a-trous filter of SVGF, Schied et al. 2017) — an EXTENSION (DESIGN.md §10
+ * f15).  The filter narrows as a pixel converges, so one setting serves 4 samples and 1000.  color, out (may alias color), the
+ * guides and rgba are pt_denoise's; moments_dev float[h][w][2] = (m1, m2) as pt_render_moments writes it; length_dev float[h][w]
+ * (may be NULL: 1 everywhere), the history length in frames as pt_temporal writes it; out_variance_dev float[h][w] (may be NULL).
+ * a' and the hit flag are pt_denoise's (albedo > 1e-3 ? albedo : 1 per channel; a hit when normal != 0);
+ * L(c) = (0.2126f c.r + 0.7152f c.g) + 0.0722f c.b.
+ *   Seed, in binary32, one rounding per operation: n = samples_per_frame * len_p;
+ *     var_p = n >= 2 ? fmaxf(0, m2 - m1 * m1) / (n - 1) : m2, then fminf(fmaxf(var_p, 0), 1e30f): a NaN counts as 0, the
+ *     result is finite (with fewer than two samples a pixel is taken to be as uncertain as it is bright);
+ *     i0 = c / a';  v0 = var_p / (L(a') * L(a')): the variance of the mean luminance, carried into demodulated space.
+ *   Iteration l = 0 .. iterations-1, step s = 2^l:
+ *     g_p = the (1, 2, 1) x (1, 2, 1) mean of v(l) over the 3x3 ADJACENT pixels (whatever s), of which only those inside the
+ *       image and with the hit flag of p take part; the mean divides by the weights actually used;
+ *     sd_p = sqrt(max(g_p, 0)),  k_p = 1 / (sigma_luminance sd_p + 1e-4);
+ *     w_pq = h(dx) h(dy) exp(-|L(i_p) - L(i_q)| k_p - |n_p - n_q|^2 / sigma_normal^2 - |x_p - x_q|^2 / (sigma_position t_p)^2),
+ *       the normal and position terms, h, the taps q = p + s (dx, dy) and w = 0 where exactly one of p, q is a miss as in
+ *       pt_denoise; the centre tap has weight h(0) h(0); a term with sigma <= 0 is left out;
+ *     i(l+1)_p = sum_q w_pq i(l)_q / sum_q w_pq,   v(l+1)_p = sum_q w_pq^2 v(l)_q / (sum_q w_pq)^2.
+ *   out = clamp01(i(L) a'), its display word into rgba_dev as pt_denoise packs it; out_variance = v(L) L(a')^2.
+ *   iterations = 0: out = color bit for bit, out_variance = var_p.
+ * PT_ERR_INVALID: everything pt_denoise refuses (NULL color / guide / out pointer, width or height < 1, iterations outside
+ * 0..10, a non-finite sigma); then NULL moments_dev; samples_per_frame not finite or < 1; out_variance_dev equal to an input
+ * (color, moments, length or a guide).  No scene needed.  Asynchronous on the context's stream, hence ordered after an earlier
+ * pt_render_moments; with PT_OPT_TIMING=1, pt_last_kernel_ms covers all of its launches.  Scratch: pt_denoise's two float[4]
+ * frames, the same buffer under the same rule (grown by whichever call needs more, that call synchronises once; a later call of
+ * either kind at the same or a smaller size neither allocates nor synchronises).
+ * Left out: a spatial variance estimate for short histories (SVGF's 7x7 fallback), per-channel variance, an unclamped output,
+ * per-stripe operation in the multi-GPU tile split. */
+typedef struct pt_denoise_variance_params {
+    int32_t width, height;
+    int32_t iterations;                                  /* 0..10                                              */
+    float sigma_luminance, sigma_normal, sigma_position; /* <= 0 switches that term off                        */
+    float samples_per_frame;                             /* >= 1, finite: samples behind ONE frame of the moments */
+    int32_t _pad;
+} pt_denoise_variance_params;                            /* 32 bytes                                           */
+int pt_denoise_variance(pt_ctx* ctx, const pt_denoise_variance_params* dp, const float* color_dev,
+                        const float* moments_dev, const float* length_dev /* may be NULL */,
+                        const float* albedo_dev, const float* normal_dev, const float* position_dev,
+                        float* out_dev, float* out_variance_dev /* may be NULL */, uint32_t* rgba_dev);
+
 /* ---- temporal reprojection — an EXTENSION ---------------------------------
  * pt_temporal: carries a history of earlier frames into a new frame rendered from a camera that has moved (the first stage of
  * SVGF-style chains), so that a displayed pixel keeps the samples of the frames before it instead of restarting at
@@ -781,7 +822,7 @@ int pt_denoise(pt_ctx* ctx, const pt_denoise_params* dp, const float* color_dev,
  * Triangles moved by pt_refit_bvh fail the plane test where they moved and lose their history — except one that slides within its
  * own plane, which passes every test and takes the history of another surface point: pt_temporal_motion (below) is the call for
  * a scene whose triangles move.
- * Out of scope: reprojecting pt_render_moments' moments, following specular first hits (a
+ * Out of scope: following specular first hits (a
  * mirror's history is looked up where its surface was, not where its reflection was), per-stripe operation in the multi-GPU
  * tile split (the call is full-frame). */
 typedef struct pt_temporal_params {
@@ -835,7 +876,7 @@ int pt_temporal(pt_ctx* ctx, const pt_temporal_params* tp, const pt_camera* prev
  * triangle pixel then has no history.  No scene needed; no scratch, no allocation, no synchronisation.
  * Left out: moving spheres (a sphere's pixels are static); history for points that were hidden or off screen in the previous
  * frame (they restart, as under a camera move); the lag of lighting that changes because geometry moved — a shadow that wanders
- * over a static wall keeps its history (max_history is the caller's handle); reprojecting pt_render_moments' moments; specular
+ * over a static wall keeps its history (max_history is the caller's handle); specular
  * first hits; per-stripe operation in the multi-GPU tile split. */
 int pt_temporal_motion(pt_ctx* ctx, const pt_temporal_params* tp, const pt_camera* prev_cam,
                        const float* prev_verts_dev, const float* cur_verts_dev, size_t n_tris,
@@ -845,6 +886,25 @@ int pt_temporal_motion(pt_ctx* ctx, const pt_temporal_params* tp, const pt_camer
                        const float* cur_normal_dev, const float* cur_position_dev, const int32_t* cur_id_dev,
                        float* out_color_dev, float* out_length_dev, uint32_t* rgba_dev,
                        float* motion_dev /* float[h][w][2], may be NULL */);
+
+/* pt_temporal_moments: the luminance moments of pt_render_moments reprojected the way the colour is — an EXTENSION (DESIGN.md
+ * §10 f15), what pt_denoise_variance needs beside a history made by pt_temporal / pt_temporal_motion.  The buffers named
+ * *_moments_dev are float[h][w][2] = (m1, m2); everything else is the colour call's.  The footprint, the tests of a tap, the
+ * acceptance and n = fminf(sl * inv + 1.0f, max_history) are those calls' statements; the payload is (m1, m2) instead of rgb:
+ * out = fmaf(cur - hist, 1.0f / n, hist) per component, and out = cur bit for bit where the history is not accepted.  Given the
+ * colour buffers (m1, m2, 0) the colour calls write these two values into their first two channels, bit for bit.
+ * Both vertex pointers NULL: pt_temporal's rule (ids of both frames or of neither).  Otherwise pt_temporal_motion's rule and
+ * requirements (both ids, no NULL vertex pointer while n_tris > 0, n_tris < 2^31).  prev_moments_dev == NULL: no history, out =
+ * cur.  No length and no display word is written: the host passes the prev_length_dev of the colour call of the same frame,
+ * before it swaps.  out_moments_dev may alias cur_moments_dev; out_moments_dev == prev_moments_dev is refused.  The other errors,
+ * asynchrony and PT_OPT_TIMING are pt_temporal's. */
+int pt_temporal_moments(pt_ctx* ctx, const pt_temporal_params* tp, const pt_camera* prev_cam,
+                        const float* prev_verts_dev, const float* cur_verts_dev, size_t n_tris,
+                        const float* prev_moments_dev, const float* prev_length_dev,
+                        const float* prev_normal_dev, const float* prev_position_dev, const int32_t* prev_id_dev,
+                        const float* cur_moments_dev,
+                        const float* cur_normal_dev, const float* cur_position_dev, const int32_t* cur_id_dev,
+                        float* out_moments_dev);
 
 /* ---- measurement --------------------------------------------------------------- */
 int pt_get_counters(pt_ctx* ctx, pt_counters* out);
