@@ -60,6 +60,12 @@ class Environment(C.Structure):
                 ("up", C.c_float * 3), ("scale", C.c_float * 3), ("filter", C.c_int32), ("_pad", C.c_int32)]
 
 
+class CameraModel(C.Structure):
+    """pt_camera_model — the camera model of pt_camera_rays (extension, include/ptmi.h; 32 bytes)."""
+    _fields_ = [("model", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("flags", C.c_int32),
+                ("lens_radius", C.c_float), ("focus_dist", C.c_float), ("ortho_height", C.c_float), ("fisheye_fov", C.c_float)]
+
+
 class CheckpointInfo(C.Structure):
     """pth_checkpoint_info (host/pthost.h)."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("next_frame", C.c_uint64),
@@ -106,6 +112,9 @@ FLAGS_SMALLPT = FLAG_FACE_FORWARD | FLAG_COSINE_DIFF | FLAG_RUSSIAN_ROULETTE | F
 FLAGS_CPU_TRACER = FLAG_FACE_FORWARD | FLAG_COSINE_DIFF | FLAG_RR_CPU_TRACER | FLAG_MISS_KEEPS_PATH
 RAYS_CLAMPED, RAYS_HDR = 0, 1
 ENV_NEAREST, ENV_BILINEAR = 0, 1
+CAM_PINHOLE, CAM_THIN_LENS, CAM_ORTHO, CAM_FISHEYE, CAM_EQUIRECT = 0, 1, 2, 3, 4
+CAMF_CENTRE = 1
+CAM_LENS_KEY = 0xC3A5C85C97CB3127   # PT_CAM_LENS_KEY: frame ^ this keys the thin lens' stream
 KERNEL_AUTO, KERNEL_MEGA_BVH2, KERNEL_PERSISTENT, KERNEL_WAVEFRONT = 0, 1, 3, 5
 OPT_KERNEL, OPT_COUNTERS, OPT_TIMING, OPT_BATCH, OPT_TOP_NODES, OPT_OCCUPANCY, OPT_LDS_STACK, OPT_WALK, OPT_LEAF_MAX, OPT_TRI_TEST, OPT_REFILL, OPT_VOTE_NODE, OPT_VOTE_REC, OPT_WAVE_BATCH, OPT_SPHERE_LDS, OPT_BUILD_ALGO, OPT_REBUILD, OPT_PRESPLIT, OPT_WAVE_BLOCKS, OPT_OVERLAP, OPT_OPTIMIZE, OPT_WAVE_SAMPLES = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 21, 24, 25
 OPT_FIRST_WALK, OPT_PACKET_STACK, OPT_FUSE_STAGES, OPT_LAST_ANYHIT = 26, 27, 28, 29
@@ -141,6 +150,7 @@ PTMI_SYMBOLS = [
     ("pt_closest_hits", _i, [_vp, _vp, _sz, _i, _vp, _vp, _vp]),
     ("pt_any_hits", _i, [_vp, _vp, _sz, _i, _vp]),
     ("pt_render_rays", _i, [_vp, _vp, _sz, C.c_uint64, _vp, C.POINTER(Params), _u32, _i]),
+    ("pt_camera_rays", _i, [_vp, C.POINTER(Camera), C.POINTER(CameraModel), C.c_uint64, _vp, _sz, C.c_uint64, _vp]),
     ("pt_upload_environment", _i, [_vp, C.POINTER(Environment), _vp]),
     ("pt_eval_environment", _i, [_vp, _vp, _sz, _vp]),
     ("pt_environment_is_light", _i, [_vp, C.POINTER(_i)]),

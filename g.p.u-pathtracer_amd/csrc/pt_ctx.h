@@ -1,7 +1,7 @@
 // pt_ctx.h — the context behind the C ABI (include/ptmi.h) and the host-side helpers shared by the
 // translation units of libptmi.so: ptmi.hip (API), pt_tree.hip (trees: makers, adoption, cost), pt_build.hip (device BVH
 // builder), pt_refit.hip (refit), pt_denoise.hip (guide buffers, denoiser, temporal filter, frame error), pt_k_*.hip (kernel families +
-// their launchers, no API function), pt_env.hip (environment map).  Host code only.
+// their launchers, no API function), pt_env.hip (environment map), pt_camera.hip (camera models).  Host code only.
 // Every device buffer, event and stream of the context is a member that owns it (pt_own.h): pt_destroy waits and deletes.  The scene's
 // resources — tree, spheres, materials, environment — are values: built in a local, adopted behind quiesce().
 #pragma once

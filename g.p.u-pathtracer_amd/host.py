@@ -241,6 +241,23 @@ def default_camera(width, height):
     return cam
 
 
+_CAMERA_KINDS = {"pinhole": _abi.CAM_PINHOLE, "thinlens": _abi.CAM_THIN_LENS, "thin_lens": _abi.CAM_THIN_LENS, "ortho": _abi.CAM_ORTHO,
+                 "fisheye": _abi.CAM_FISHEYE, "equirect": _abi.CAM_EQUIRECT}
+
+
+def camera_model(kind, width, height, centre=False, lens_radius=0.0, focus_dist=1.0, ortho_height=1.0, fisheye_fov=np.pi):
+    """A pt_camera_model for PathTracer.camera_rays / render_camera: kind is a CAM_* value or one of "pinhole", "thinlens",
+    "ortho", "fisheye", "equirect"; width x height is the image the pixel numbers refer to.  centre: no sub-pixel jitter
+    (CAMF_CENTRE).  The defaults of the model parameters are valid values, not tuned ones: a closed aperture focused at distance 1, a
+    view volume 1 high, a 180 degree fisheye."""
+    cm = _abi.CameraModel()
+    cm.model = _CAMERA_KINDS[kind] if isinstance(kind, str) else int(kind)
+    cm.width, cm.height = int(width), int(height)
+    cm.flags = _abi.CAMF_CENTRE if centre else 0
+    cm.lens_radius, cm.focus_dist, cm.ortho_height, cm.fisheye_fov = lens_radius, focus_dist, ortho_height, fisheye_fov
+    return cm
+
+
 def default_params(width, height, depth=4, tri_mat=MAT_DIFF):
     """kernelInfo defaults, BasicScene.cpp:220-236 and CpuStructs.hpp:45-72."""
     p = Params()

@@ -10,7 +10,8 @@
 //               --resume state.ckpt --device-build --fix-estimators --nee --mis --gpus N --tile ROWS
 //               --denoise-out image.ppm|.png|.pfm  --denoise-variance  --variance-out file.pfm  --until-error E --max-frames M
 //               --pan-deg D --dolly S --spin-deg D --temporal-out image.ppm|.png|.pfm  --equirect
-//               --env file.pfm [--env-scale S] [--env-nearest] [--env-light]]
+//               --env file.pfm [--env-scale S] [--env-nearest] [--env-light]
+//               --camera pinhole|thinlens|ortho|fisheye|equirect [--aperture R --focus D --ortho-height S --fisheye-deg A]]
 // --gpus N splits the framebuffer over N contexts, one per GPU (devices device, device+1, ... modulo the number
 // present, so N > 1 also runs on a one-GPU box): stripes of --tile rows (default 8) are dealt round-robin
 // (pt_params.part_*), every context holds the whole scene and renders only its stripes of every frame — the random
@@ -58,6 +59,17 @@
 // every call renders them through pt_render_rays (pixel y W + x draws the random numbers of that pixel of a pinhole frame):
 // clamped mode when --out is a .png / .ppm, HDR when it is a .pfm.  There is no pinhole frame, so --equirect is refused with
 // --denoise-out, --temporal-out, --variance-out, --until-error, --gpus > 1, --checkpoint, --resume and the motion options.
+// --camera MODEL renders through one of the camera models of pt_camera_rays instead of pt_render's pinhole: per sample one
+// pt_camera_rays call writes the jittered rays of every pixel for that sample's frame number on the device and one one-sample
+// pt_render_rays call traces them (the loop of gpu_pathtracer_amd.PathTracer.render_camera; --spp only groups the samples between two
+// pt_sync), so every sample has its own sub-pixel jitter and, for thinlens, its own point on the lens: anti-aliasing and depth of
+// field.  pinhole is pt_render's camera (the same samples, bit for bit); thinlens takes --aperture R (lens radius in world units,
+// default 0: everything sharp) and --focus D (distance of the plane in focus along front, default 35: the mirror sphere);
+// ortho takes --ortho-height S (world height of the view volume, default 30: the sphere room's); fisheye takes --fisheye-deg A
+// (full angle across the image circle, default 180; pixels outside the circle get --bk); equirect is the layout of --equirect,
+// jittered.  Clamped mode when --out is a .png / .ppm, HDR when it is a .pfm, as --equirect; refused with --equirect and in the
+// combinations --equirect is refused in (there are no guide buffers for these cameras).  --equirect itself keeps its host-made
+// centre rays and its output.
 // --env file.pfm lights the scene with a latitude-longitude radiance map (pt_upload_environment): a path that leaves the scene gathers
 // the map along its direction instead of --bk.  The map lies in the world frame front = (0, 0, -1), right = (1, 0, 0), up = (0, 1, 0)
 // — the frame of this app's camera, hence of the frames --equirect writes — and is looked up bilinearly (--env-nearest: the nearest
@@ -100,6 +112,8 @@ int main(int argc, char** argv) {
     double until_error = -1.0;   // < 0: off
     long max_frames = -1;
     double pan_deg = 0.0, dolly = 0.0, spin_deg = 0.0;
+    std::string camera_name;   // --camera: empty = pt_render's own pinhole
+    double aperture = 0.0, focus = 35.0, ortho_height = 30.0, fisheye_deg = 180.0;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&](const char* name) -> const char* {
@@ -130,6 +144,11 @@ int main(int argc, char** argv) {
         else if (a == "--nee") nee = true;   // next-event estimation (implies the cosine-weighted DIFF lobe and keeps a path's light on a miss)
         else if (a == "--mis") mis = true;   // ... with its shadow rays weighed against the bounce rays (implies --nee)
         else if (a == "--equirect") equirect = true;
+        else if (a == "--camera") camera_name = next("--camera");
+        else if (a == "--aperture") aperture = std::atof(next("--aperture"));
+        else if (a == "--focus") focus = std::atof(next("--focus"));
+        else if (a == "--ortho-height") ortho_height = std::atof(next("--ortho-height"));
+        else if (a == "--fisheye-deg") fisheye_deg = std::atof(next("--fisheye-deg"));
         else if (a == "--env") env_path = next("--env");
         else if (a == "--env-scale") { env_scale = std::atof(next("--env-scale")); env_scale_set = true; }
         else if (a == "--env-nearest") env_nearest = true;
@@ -163,6 +182,23 @@ int main(int argc, char** argv) {
         return die("usage", "--pan-deg / --dolly / --spin-deg do not combine with --resume, --checkpoint or --until-error (a moving camera or mesh restarts the accumulation every frame)");
     if (equirect && (!denoise_path.empty() || temporal || with_moments || gpus > 1 || !ckpt_path.empty() || !resume_path.empty() || moving))
         return die("usage", "--equirect does not combine with --denoise-out, --temporal-out, --variance-out, --until-error, --gpus > 1, --checkpoint, --resume, --pan-deg, --dolly or --spin-deg (they need the pinhole frame)");
+    // --camera: the model of pt_camera_rays; its own parameter is checked by the library at the first call
+    const bool ray_camera = !camera_name.empty();
+    pt_camera_model cmodel{};
+    if (ray_camera) {
+        const char* names[5] = {"pinhole", "thinlens", "ortho", "fisheye", "equirect"};   // PT_CAM_* in order
+        cmodel.model = -1;
+        for (int k = 0; k < 5; k++)
+            if (camera_name == names[k]) cmodel.model = k;
+        if (cmodel.model < 0) return die("--camera", "one of pinhole, thinlens, ortho, fisheye, equirect");
+        if (equirect) return die("usage", "--camera does not combine with --equirect (--camera equirect is its jittered form)");
+        if (!denoise_path.empty() || temporal || with_moments || gpus > 1 || !ckpt_path.empty() || !resume_path.empty() || moving)
+            return die("usage", "--camera does not combine with --denoise-out, --temporal-out, --variance-out, --until-error, --gpus > 1, --checkpoint, --resume, --pan-deg, --dolly or --spin-deg (they need pt_render's pinhole frame)");
+        cmodel.width = W; cmodel.height = H;
+        cmodel.lens_radius = (float)aperture; cmodel.focus_dist = (float)focus;
+        cmodel.ortho_height = (float)ortho_height;
+        cmodel.fisheye_fov = (float)(fisheye_deg * 3.14159265358979323846 / 180.0);
+    }
 
     // --env: the map is read and checked before anything is built or rendered
     int env_w = 0, env_h = 0;
@@ -449,6 +485,8 @@ int main(int argc, char** argv) {
         if (pt_malloc(ctx, rays.size() * 4, &eq_rays) != PT_OK || pt_upload(ctx, eq_rays, rays.data(), rays.size() * 4) != PT_OK)
             return die("equirect rays", pt_last_error(ctx));
     }
+    // --camera: the buffer pt_camera_rays fills for every sample, float[H W][8]
+    if (ray_camera && pt_malloc(ctx, (size_t)W * H * 32, &eq_rays) != PT_OK) return die("camera rays", pt_last_error(ctx));
 
     const uint64_t first_frame = frameNumber;
     uint64_t end_frame = frameNumber + (uint64_t)frames;
@@ -469,6 +507,15 @@ int main(int argc, char** argv) {
             if (equirect) {
                 if (pt_render_rays(ctx, (const float*)eq_rays, (size_t)W * H, 0, (float*)accum, &p, n, out_pfm ? PT_RAYS_HDR : PT_RAYS_CLAMPED) != PT_OK)
                     return die("pt_render_rays", pt_last_error(ctx));
+            } else if (ray_camera) {   // a fresh jittered ray per sample: generate, trace, on one stream
+                pt_params q = p;
+                for (uint32_t s = 0; s < n; s++) {
+                    q.frame = p.frame + s; q.sample_index = p.sample_index + s;
+                    if (pt_camera_rays(ctx, &cam, &cmodel, q.frame, nullptr, (size_t)W * H, 0, (float*)eq_rays) != PT_OK)
+                        return die("pt_camera_rays", pt_last_error(ctx));
+                    if (pt_render_rays(ctx, (const float*)eq_rays, (size_t)W * H, 0, (float*)accum, &q, 1, out_pfm ? PT_RAYS_HDR : PT_RAYS_CLAMPED) != PT_OK)
+                        return die("pt_render_rays", pt_last_error(ctx));
+                }
             } else
             for (int g = 0; g < gpus; g++) {                                            // :404, once per GPU: asynchronous, so the GPUs run side by side
                 p.part_index = g;
@@ -518,7 +565,7 @@ int main(int argc, char** argv) {
             rc = pth_write_pfm(out_path.c_str(), host_acc.data(), W, H);
         } else {
             std::vector<uint32_t> img((size_t)W * H);
-            if (frames == 0 || equirect) {  // nothing rendered in this run (e.g. --resume only to convert), or no display words (pt_render_rays): pack the accumulator here
+            if (frames == 0 || equirect || ray_camera) {  // nothing rendered in this run (e.g. --resume only to convert), or no display words (pt_render_rays): pack the accumulator here
                 host_acc.resize((size_t)W * H * 3);
                 if (int grc = gather(accums, host_acc.data(), 12)) return grc;
                 for (size_t i = 0; i < img.size(); i++) {   // rgbToUint, cudaUtils.h:99-105

@@ -216,6 +216,30 @@ class PathTracer:
         self._check(self._lib.pt_render_rays(self._ctx, rays_ptr, int(n), int(first_index), out_ptr, C.byref(params), int(spp),
                                              _abi.RAYS_HDR if hdr else _abi.RAYS_CLAMPED))
 
+    def camera_rays(self, cam, model, frame, rays_ptr, n=None, first_pixel=0, pixels_ptr=None):
+        """The jittered rays of frame `frame` under a camera model (pt_camera_rays; model: host.camera_model) into rays float[n][8],
+        the layout render_rays reads: row i is pixel first_pixel + i, or pixels_ptr[i] (uint32 on the device; n is then required,
+        and an index past the image gives a ray without direction, which renders as a miss).  n defaults to the pixels from
+        first_pixel to the end of the image.  Asynchronous on the context's stream: a render_rays issued next reads these rays."""
+        if n is None:
+            if pixels_ptr is not None:
+                raise ValueError("camera_rays: a pixel list needs n")
+            n = model.width * model.height - int(first_pixel)
+        self._check(self._lib.pt_camera_rays(self._ctx, C.byref(cam), C.byref(model), int(frame), pixels_ptr, int(n), int(first_pixel), rays_ptr))
+
+    def render_camera(self, cam, model, params, out_ptr, rays_ptr, spp=1, hdr=False):
+        """spp samples of the whole image of a camera model into out float[H][W][3] (the running mean of render_rays, N =
+        params.sample_index ..): per sample s one camera_rays of frame params.frame + s into rays float[H * W][8] and one one-sample
+        render_rays of that frame over them — a fresh jittered ray per sample (anti-aliasing; depth of field for a thin lens), all
+        on the context's stream, with no upload and no sync.  With a pinhole model this is launch_kernel's frame bit for bit
+        (hdr=False).  Asynchronous until sync()."""
+        n = model.width * model.height
+        q = Params.from_buffer_copy(params)
+        for s in range(int(spp)):
+            q.frame, q.sample_index = params.frame + s, params.sample_index + s
+            self.camera_rays(cam, model, q.frame, rays_ptr)
+            self.render_rays(rays_ptr, n, out_ptr, q, 1, 0, hdr)
+
     def upload_environment(self, texels, front=(0, 0, -1), right=(1, 0, 0), up=(0, 1, 0), scale=(1, 1, 1), filter=_abi.ENV_BILINEAR, light=False):
         """Light the paths that leave the scene with a latitude-longitude map (pt_upload_environment) instead of bk_color: texels
         float32 [H][W][3] on the host, in the layout `pt_app --equirect` writes for a camera with this front / right / up (the

@@ -571,6 +571,65 @@ enum { PT_RAYS_CLAMPED = 0, PT_RAYS_HDR = 1 };
 int pt_render_rays(pt_ctx* ctx, const float* rays_dev, size_t n_rays, uint64_t first_index,
                    float* radiance_dev, const pt_params* params, uint32_t spp, int mode);
 
+/* ---- camera models: the rays pt_render_rays reads, made on the device — an EXTENSION ------------
+ * pt_camera_rays writes, for frame `frame`, the jittered ray of every pixel of an image (or of a listed subset) under one of five
+ * camera models straight into a buffer of pt_render_rays' layout: no host loop, no upload, no pt_sync in between.  One call per
+ * sample gives anti-aliasing, and depth of field under PT_CAM_THIN_LENS, which needs a fresh ray per sample.
+ * Row i is the ray of pixel pix = pixels_dev ? pixels_dev[i] : first_pixel + i, px = pix % width, py = pix / width, written as
+ * (o.xyz, 0, d.xyz, 0): pt_trace_rays' stride, words 3 and 7 always 0.  rays_dev: float[n][8], 16-byte aligned.
+ * Jitter: the random stream of pt_render's pixel number pix in frame `frame` (csrc/pt_math.h: pt_rng_init of pt_wang64 [frame] and
+ * pix), jx = next - 0.5f, jy = next - 0.5f — the two draws and the arithmetic with which pt_render's camera path starts, the two
+ * draws pt_render_rays' stream stands behind.  So for PT_CAM_PINHOLE, this call for frame f over all pixels, then pt_render_rays
+ * with first_index 0, frame f, spp 1 and sample_index N, folds the sample pt_render folds for frame f, bit for bit.  With
+ * PT_CAMF_CENTRE jx = jy = 0 and nothing is drawn.
+ * Lens draws (PT_CAM_THIN_LENS only): (v0, v1) are the first two draws of a SECOND stream, that of pixel pix in "frame"
+ * frame ^ PT_CAM_LENS_KEY — draws 2 onward of the first stream belong to the path.
+ * The models.  front, right, up, pos, dist, aspect, fov are pt_camera's; W, H = width, height.  binary32 throughout, plain * and +
+ * but for the fused operations of vdot(u, v) = fmaf(u.z, v.z, fmaf(u.y, v.y, u.x * v.x)), normalize(v) = v * (1 / sqrtf(vdot(v, v)))
+ * and v * s + w = fmaf per component where a point or direction is built from the basis.  The basis is used as given; every model
+ * but the pinhole assumes it orthonormal.  ax = ((px - W/2) + 0.5) + jx, ay = ((py - H/2) + 0.5) + jy: the pixel's offsets from
+ * the image centre as pt_render's camera forms them.
+ *   PT_CAM_PINHOLE    pt_render's camera ray (getCamRayDir, cudaUtils.h:111-134): dir0 = front * dist + right * xs + up * ys with
+ *                     xs = ax * dist * aspect * fov / (W - 1), ys = ay * dist * fov / (H - 1); o = pos + dir0 — the reference's
+ *                     origin ON the image plane and its division by W - 1 — and d = normalize(dir0).  The one model pinned bit
+ *                     for bit (against pt_render and the oracle).
+ *   PT_CAM_THIN_LENS  dir0 as above; the point in focus pf = pos + dir0 * (focus_dist / dist); the lens point
+ *                     l = pos + right * (R r cos phi) + up * (R r sin phi), r = sqrtf(v0), phi = 2 pi v1 (the path kernels' sincos),
+ *                     R = lens_radius; o = l, d = normalize(pf - l).  R = 0: o = pos exactly, d the pinhole's direction.
+ *   PT_CAM_ORTHO      o = pos + right * (ax * ortho_height * aspect / W) + up * (ay * ortho_height / H), d = normalize(front).
+ *   PT_CAM_FISHEYE    equidistant: Rpx = min(W, H) / 2, rho = sqrtf(ax * ax + ay * ay), theta = rho / Rpx * (fisheye_fov / 2);
+ *                     o = pos, d = normalize(front * cos theta + (right * ax + up * ay) * (sin theta / rho)), d = normalize(front)
+ *                     where rho == 0.  A pixel with theta > fisheye_fov / 2 lies outside the image circle and has no ray: its
+ *                     row is o = pos, d = (0, 0, 0), which pt_render_rays renders as a miss (bk_color).
+ *   PT_CAM_EQUIRECT   the layout of `pt_app --equirect` and of pt_upload_environment (an integer coordinate is a texel centre):
+ *                     fx = px + jx, fy = py + jy, lon = (fx - W/2) * (2 pi / W), lat = clamp((fy - H/2) * (pi / H), -pi/2, pi/2);
+ *                     o = pos, d = normalize((front * cos lon + right * sin lon) * cos lat + up * sin lat).
+ * With a pixel list an index >= W * H gives the zero-direction row too (o = pos): the host cannot check a device list.
+ * Errors, in this order; nothing is written on any of them, nor for n == 0: NULL ctx PT_ERR_INVALID; n == 0 PT_OK; then each
+ * PT_ERR_INVALID: a NULL cam, cm or rays_dev; an unknown model or unknown flag bits; width or height < 2, or width * height >= 2^32;
+ * n >= 2^32; without a list, first_pixel + n > width * height; the parameter of the chosen model that is not finite or out of its
+ * range (lens_radius >= 0 and focus_dist > 0; ortho_height > 0; 0 < fisheye_fov <= 2 pi) — the parameters of other models are
+ * ignored.  No scene, no scratch, no allocation, no synchronisation: asynchronous on the context's stream, hence ordered before the
+ * pt_render_rays that follows.  With PT_OPT_TIMING=1, pt_last_kernel_ms covers it.
+ * Left out: guide buffers for these cameras (pt_render_aux stays pinhole, so pt_denoise and pt_temporal do not serve them yet);
+ * stereo pairs (a host calls twice); lens shapes other than a disk; RNG keys for pt_render_rays by pixel instead of
+ * first_index + i (a listed subset renders with the keys of its row numbers); the generator fused into the path kernel. */
+enum { PT_CAM_PINHOLE = 0, PT_CAM_THIN_LENS = 1, PT_CAM_ORTHO = 2, PT_CAM_FISHEYE = 3, PT_CAM_EQUIRECT = 4 };
+enum { PT_CAMF_CENTRE = 1 };           /* no sub-pixel jitter: jx = jy = 0 (guides, picking, tests) */
+#define PT_CAM_LENS_KEY 0xC3A5C85C97CB3127ull   /* frame ^ this keys the lens stream; the top bit is set, so no frame number a host counts up to meets its own lens stream */
+typedef struct pt_camera_model {
+    int32_t model;                     /* PT_CAM_*                                                    */
+    int32_t width, height;             /* the image the pixel numbers refer to; >= 2 each, w*h < 2^32 */
+    int32_t flags;                     /* PT_CAMF_*                                                   */
+    float lens_radius;                 /* THIN_LENS: aperture radius, >= 0                            */
+    float focus_dist;                  /* THIN_LENS: distance along front of the plane in focus, > 0  */
+    float ortho_height;                /* ORTHO: world height of the view volume, > 0                 */
+    float fisheye_fov;                 /* FISHEYE: full angle across the image circle, radians, (0, 2 pi] */
+} pt_camera_model;                     /* 32 bytes */
+int pt_camera_rays(pt_ctx* ctx, const pt_camera* cam, const pt_camera_model* cm, uint64_t frame,
+                   const uint32_t* pixels_dev /* may be NULL */, size_t n, uint64_t first_pixel,
+                   float* rays_dev /* float[n][8] */);
+
 /* ---- environment map — an EXTENSION -----------------------------------------
  * pt_upload_environment gives the context a latitude-longitude (equirectangular) radiance map: what a path segment that hits
  * nothing gathers instead of the one constant bk_color, so that open scenes — a mesh on its own, a probe rendered elsewhere — are
