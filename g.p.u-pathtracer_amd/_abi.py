@@ -151,6 +151,7 @@ PTMI_SYMBOLS = [
     ("pt_any_hits", _i, [_vp, _vp, _sz, _i, _vp]),
     ("pt_render_rays", _i, [_vp, _vp, _sz, C.c_uint64, _vp, C.POINTER(Params), _u32, _i]),
     ("pt_camera_rays", _i, [_vp, C.POINTER(Camera), C.POINTER(CameraModel), C.c_uint64, _vp, _sz, C.c_uint64, _vp]),
+    ("pt_render_camera", _i, [_vp, C.POINTER(Camera), C.POINTER(CameraModel), _vp, _sz, C.c_uint64, _vp, C.POINTER(Params), _u32, _i]),
     ("pt_upload_environment", _i, [_vp, C.POINTER(Environment), _vp]),
     ("pt_eval_environment", _i, [_vp, _vp, _sz, _vp]),
     ("pt_environment_is_light", _i, [_vp, C.POINTER(_i)]),

@@ -359,6 +359,17 @@ struct RaysCall {
 };
 hipError_t launch_render_rays(const LaunchCfg& L, const KParams& P, const RaysCall& r, hipStream_t st);
 hipError_t launch_fold_rays(const pt_ctx* c, const KParams& P, const RaysCall& r);
+// the same loop over the pixels of a camera model (pt_k_camera.hip), one launch of pt_render_camera; P.cam is the camera.  Its fold
+// is launch_fold_rays over RaysCall{nullptr, out, 0, n, hdr}
+struct CameraCall {
+    const pt_camera_model* cm;   // checked: check_camera_model (pt_plan.h)
+    const uint32_t* pixels;      // n pixel numbers on the device, or nullptr
+    uint64_t first_pixel;        // without a list: row i is pixel first_pixel + i
+    float* out;                  // float[n][3]
+    size_t n;                    // 0 < n < 2^32
+    int hdr;                     // mode == PT_RAYS_HDR
+};
+hipError_t launch_render_camera(const LaunchCfg& L, const KParams& P, const CameraCall& r, hipStream_t st);
 // PT_OPT_TIMING: marks the end of a stage of the running call on the context's stream (no-op when timing is off)
 int stage_mark(pt_ctx* c, int kind_of_work_since_last_mark);
 // device BVH builder (pt_build.hip), a maker: the tree over the mesh into `out` (its build_ms set), the context's own tree untouched.

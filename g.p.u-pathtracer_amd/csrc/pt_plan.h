@@ -31,9 +31,15 @@ struct CallFacts {
     const pt_params* p;
     uint32_t spp;
     bool buffers, rgba, moments;   // every required pointer but p is given; rgba_dev; moments_dev (frame)
-    uint64_t n_rays;       // pt_render_rays
+    uint64_t n_rays;       // pt_render_rays; pt_render_camera: its rows
     int mode;
+    // pt_render_camera (else pt_render_rays): buffers counts cam and cm in; whether a pixel list is given; first_pixel without one
+    bool camera = false;
+    const pt_camera_model* cm = nullptr;
+    bool list = false;
+    uint64_t first_pixel = 0;
 };
+inline const char* path_call_name(const CallFacts& a) { return a.frame ? "pt_render" : a.camera ? "pt_render_camera" : "pt_render_rays"; }
 // A call the rules turn away (code != PT_OK, with pt_last_error's text), or one with nothing to do (nothing: PT_OK at once)
 struct Refusal {
     int code = PT_OK;
@@ -41,9 +47,35 @@ struct Refusal {
     bool nothing = false;
 };
 
-// ---- the argument rules of pt_render and pt_render_rays, each call's in its own order and wording
+// ---- the rules of a camera model and the pixels asked of it, in pt_camera_rays' order and wording under the caller's name: an unknown
+// model or flag bits, the image, n, first_pixel + n without a list, the chosen model's own parameter (the others are ignored)
+inline bool plan_finite(float x) { return x - x == 0.0f; }   // neither an infinity nor a NaN
+inline Refusal check_camera_model(const std::string& who, const pt_camera_model& cm, uint64_t n, uint64_t first_pixel, bool list) {
+    if (cm.model < PT_CAM_PINHOLE || cm.model > PT_CAM_EQUIRECT) return {PT_ERR_INVALID, who + ": unknown camera model"};
+    if (cm.flags & ~PT_CAMF_CENTRE) return {PT_ERR_INVALID, who + ": unknown flag bits"};
+    const uint64_t n_pix = (uint64_t)(cm.width > 0 ? cm.width : 0) * (uint64_t)(cm.height > 0 ? cm.height : 0);
+    if (cm.width < 2 || cm.height < 2 || n_pix >= (1ull << 32)) return {PT_ERR_INVALID, who + ": width and height must be >= 2 with width * height < 2^32"};
+    if (n >= (1ull << 32)) return {PT_ERR_INVALID, who + ": more than 2^32 - 1 rays in one call"};
+    if (!list && (first_pixel > n_pix || n > n_pix - first_pixel)) return {PT_ERR_INVALID, who + ": first_pixel + n exceeds width * height"};
+    switch (cm.model) {
+    case PT_CAM_THIN_LENS:
+        if (!plan_finite(cm.lens_radius) || cm.lens_radius < 0.0f || !plan_finite(cm.focus_dist) || !(cm.focus_dist > 0.0f))
+            return {PT_ERR_INVALID, who + ": lens_radius must be finite and >= 0, focus_dist finite and > 0"};
+        break;
+    case PT_CAM_ORTHO:
+        if (!plan_finite(cm.ortho_height) || !(cm.ortho_height > 0.0f)) return {PT_ERR_INVALID, who + ": ortho_height must be finite and > 0"};
+        break;
+    case PT_CAM_FISHEYE:
+        if (!plan_finite(cm.fisheye_fov) || !(cm.fisheye_fov > 0.0f) || cm.fisheye_fov > 6.28318548f) return {PT_ERR_INVALID, who + ": fisheye_fov must be in (0, 2 pi]"};
+        break;
+    default: break;
+    }
+    return {};
+}
+
+// ---- the argument rules of pt_render, pt_render_rays and pt_render_camera, each call's in its own order and wording
 inline Refusal check_path_call(const CtxFacts& f, const CallFacts& a) {
-    const std::string who(a.frame ? "pt_render" : "pt_render_rays");
+    const std::string who(path_call_name(a));
     const bool no_scene = !f.has_bvh && f.n_spheres == 0;
     if (!a.frame) {
         if (no_scene) return {PT_ERR_NO_SCENE, who + ": no scene uploaded"};
@@ -55,8 +87,11 @@ inline Refusal check_path_call(const CtxFacts& f, const CallFacts& a) {
         if (p.width < 2 || p.height < 2) return {PT_ERR_INVALID, "pt_render: image must be at least 2x2 (the camera divides by w-1, h-1)"};
         if (a.spp == 0) return {PT_ERR_INVALID, "pt_render: spp must be >= 1"};
     } else {
-        if (a.mode != PT_RAYS_CLAMPED && a.mode != PT_RAYS_HDR) return {PT_ERR_INVALID, "pt_render_rays: mode must be PT_RAYS_CLAMPED or PT_RAYS_HDR"};
-        if (a.n_rays >= (1ull << 32)) return {PT_ERR_INVALID, "pt_render_rays: more than 2^32 - 1 rays in one call"};
+        if (a.mode != PT_RAYS_CLAMPED && a.mode != PT_RAYS_HDR) return {PT_ERR_INVALID, who + ": mode must be PT_RAYS_CLAMPED or PT_RAYS_HDR"};
+        if (a.camera) {
+            const Refusal r = check_camera_model(who, *a.cm, a.n_rays, a.first_pixel, a.list);
+            if (r.code != PT_OK) return r;
+        } else if (a.n_rays >= (1ull << 32)) return {PT_ERR_INVALID, who + ": more than 2^32 - 1 rays in one call"};
     }
     if (p.sample_index == 0) return {PT_ERR_INVALID, who + (a.frame ? ": sample_index (constantPdf) starts at 1" : ": sample_index starts at 1")};
     if (p.tri_mat < PT_MAT_DIFF || p.tri_mat > PT_MAT_REFR) return {PT_ERR_INVALID, who + ": bad triangle material"};
@@ -333,7 +368,7 @@ inline Refusal plan_launch(const CtxFacts& f, const CallFacts& a, int n_tiles, b
     return plan_wave_layout(a.p->flags, a.p->depth, a.spp, plan.work_tiles, plan.wl);
 }
 
-// ---- pt_render_rays -------------------------------------------------------------------------------
+// ---- pt_render_rays, pt_render_camera (the same plan under the call's own name: its rows are the batch) ---
 // slots of one launch: what keeps its sample buffer below 768 MiB; more samples than that go out as several launches, which the
 // fold's order makes the same thing
 constexpr uint64_t RAYS_MAX_SLOTS = 1ull << 26;
@@ -348,7 +383,7 @@ inline Refusal plan_rays(const CtxFacts& f, const CallFacts& a, RaysPlan& plan) 
     LaunchCfg& L = plan.L;
     L.nee = (a.p->flags & PT_FLAG_NEE) != 0;
     L.mis = (a.p->flags & PT_FLAG_MIS) != 0;
-    const Refusal r = choose_walk(f, "pt_render_rays", false, L.mis, L.walk);   // (0 runs as 1: launch_render_rays has no while-while walk)
+    const Refusal r = choose_walk(f, path_call_name(a), false, L.mis, L.walk);   // (0 runs as 1: the loop has no while-while walk)
     L.lstk = 16;
     L.lds = (size_t)L.lstk * PT_BLOCK * 4;
     plan.sph_tab = f.sph_lds ? lds_sphere_table(L.lds) : -1;

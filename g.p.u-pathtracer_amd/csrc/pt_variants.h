@@ -139,6 +139,10 @@ constexpr uint32_t rays_word(int walk, int map, bool nee, bool mis) {   // (it h
     return pv_word(false, nee, mis, nee ? BUDGET_4x16 : BUDGET_6x16, alg, shade_env(map, nee, mis));
 }
 static_assert(variant_count(rays_exists, PV_BITS) == 19, "k_render_rays: 3 walks x (2 + 3 maps) + 2 walks x 2 under MIS");
+// pt_render_camera's kernel, k_render_camera<V>, is the same loop with the camera model's ray as the path start: the same walks, budgets
+// and NEE / MIS / map rules, so its words ARE rays_exists / rays_word.  The camera model is a value of the launch, not a bit of the word.
+constexpr bool camera_exists(uint32_t v) { return rays_exists(v); }
+static_assert(variant_count(camera_exists, PV_BITS) == 19, "k_render_camera: one per k_render_rays, none per camera model");
 
 // The kernel family of a path call, from the one the option, PT_FLAG_MIS or PT_KERNEL_AUTO's table asks for (plan_family, pt_plan.h): shadow rays
 // have a stage in the pipeline (the pixel rides below nee_mask in the record, so it must fit) and a loop in the megakernel, nothing in

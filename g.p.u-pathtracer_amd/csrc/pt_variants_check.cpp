@@ -1,6 +1,6 @@
 // pt_variants_check.cpp — every request has a kernel and every kernel a request, and every plan is sound: a CPU program with its own
 // main, no HIP library (`make variants_check`, SAN=1 for the address and undefined-behaviour sanitizers; tests/test_variants.py runs both).
-// It RUNS the planner (pt_plan.h: the functions pt_render, pt_render_rays and the ray-batch queries call) over a domain of scenes x
+// It RUNS the planner (pt_plan.h: the functions pt_render, pt_render_rays, pt_render_camera and the ray-batch queries call) over a domain of scenes x
 // options x calls x the runtime's answers, and holds no rule of its own: a call is skipped because the planner refused it, and the
 // refusal's code has to be the one REFUSALS lists for its text.  Of every plan it asserts what follows from the project's constants
 // (LDS, refill <= batch, grids, the record layout); of every variant word a plan asks a launcher for, that the word is instantiated —
@@ -34,19 +34,21 @@ struct Family {
             if (n_failed++ < 20) std::printf("FAILED %s: a request asks for word 0x%x, which is not instantiated\n", name, v);
         } else seen[v] = 1;
     }
-    void report() const {
-        int words = 0;
+    int words() const {
+        int n = 0;
         for (uint32_t v = 0; v < seen.size(); v++) {
-            words += seen[v];
+            n += seen[v];
             if (exists(v) && !seen[v] && n_failed++ < 20) std::printf("FAILED %s: no request runs the instantiated word 0x%x\n", name, v);
         }
-        std::printf("%-26s %9ld requests, %3d distinct words, %3d kernels\n", name, requests, words, variant_count(exists, n_bits));
+        return n;
     }
+    void report() const { std::printf("%-26s %9ld requests, %3d distinct words, %3d kernels\n", name, requests, words(), variant_count(exists, n_bits)); }
 };
 static Family mega{"k_trace_mega_bvh2", mega_exists, PV_BITS}, persist{"k_trace_persist_bvh2", persist_exists, PV_BITS},
     rays{"k_render_rays", rays_exists, PV_BITS}, query{"k_query_rays", query_exists, QV_BITS}, extend{"k_wf_extend", extend_exists, WX_BITS},
     shade{"k_wf_shade", shade_exists, WS_BITS}, last_any{"k_wf_shade_last_any", shade_last_any_exists, WS_BITS},
-    fused{"k_wf_extend_packet_shade", fused_exists, WS_BITS};
+    fused{"k_wf_extend_packet_shade", fused_exists, WS_BITS},
+    camera{"k_render_camera", camera_exists, PV_BITS};   // the camera start of k_render_rays' loop: reported in a line of its own wording
 
 // the refusals the planner knows, by a piece of their text, with the code each one answers; every one of them is met below
 static struct { const char* text; int code; long seen; } REFUSALS[] = {
@@ -59,6 +61,10 @@ static struct { const char* text; int code; long seen; } REFUSALS[] = {
     {"PT_FLAG_NEE over emissive triangles needs the exact", PT_ERR_UNSUPPORTED, 0}, {"Woop records need the wide walk", PT_ERR_UNSUPPORTED, 0},
     {"PT_FLAG_MIS needs the exact", PT_ERR_UNSUPPORTED, 0}, {"RNG draws per path", PT_ERR_UNSUPPORTED, 0},
     {"PT_FLAG_NEE in the stage-split pipeline packs", PT_ERR_UNSUPPORTED, 0},
+    // check_camera_model's (pt_render_camera; pt_camera_rays asks the same function)
+    {": unknown camera model", PT_ERR_INVALID, 0}, {": unknown flag bits", PT_ERR_INVALID, 0}, {"width and height must be >= 2", PT_ERR_INVALID, 0},
+    {"first_pixel + n exceeds width * height", PT_ERR_INVALID, 0}, {"lens_radius must be finite", PT_ERR_INVALID, 0},
+    {"ortho_height must be finite", PT_ERR_INVALID, 0}, {"fisheye_fov must be in", PT_ERR_INVALID, 0},
 };
 static long n_refused = 0, n_planned = 0;
 // true: the planner refused the call or found nothing to do in it
@@ -348,6 +354,103 @@ int main() {
         CHECK(turned_away(check_path_call(f, CallFacts{false, &p, 1, true, false, false, 10, PT_RAYS_HDR})));
     }
 
+    // (g') pt_render_camera: (g)'s domain — its plan is plan_rays under its own name — over the five models, without and with a pixel
+    // list; the image holds every n of the domain but 2^32 - 1 and 2^32 (65536 x 65535 pixels), which a list alone can ask for
+    auto model = [](int kind, int w, int h) {
+        pt_camera_model cm = {};
+        cm.model = kind; cm.width = w; cm.height = h;
+        cm.lens_radius = 0.1f; cm.focus_dist = 3.0f; cm.ortho_height = 4.0f; cm.fisheye_fov = 3.0f;
+        return cm;
+    };
+    for (const Tree& t : TREES)
+        for (int env = ENV_NONE; env <= ENV_LIGHT; env++)
+            for (const Mats& m : {MATS[0], MATS[2]})
+                for (int walk : {0, 1, 2, 4})
+                    for (int knobs = 0; knobs < 4; knobs++)
+                        for (uint32_t flags : {0u, COS, NEE, MIS, (uint32_t)PT_FLAG_NEE, (uint32_t)(PT_FLAG_MIS | COS)})
+                            for (uint64_t n : {0ull, 1ull, 1000ull, (1ull << 26) / 3, 1ull << 26, (1ull << 32) - 1, 1ull << 32})
+                                for (uint32_t spp : {0u, 1u, 3u, 64u})
+                                    for (int call = 0; call < 10; call++) {   // model x list
+                                        CtxFacts f = scene(t, SPHERES[t.has_bvh ? 2 : knobs & 1], m, env);
+                                        f.walk = walk; f.sph_lds = knobs & 1; f.n_cu = knobs & 2 ? 256 : 8;
+                                        pt_params p = params(0, 0, 4, flags);
+                                        const pt_camera_model cm = model(call % 5, 65536, 65535);
+                                        const bool list = call >= 5;
+                                        const CallFacts a = {false, &p, spp, true, false, false, n, call == 3 ? (int)PT_RAYS_HDR : (int)PT_RAYS_CLAMPED, true, &cm, list, list ? 0u : 5u};
+                                        RaysPlan plan = {};
+                                        const Refusal r = check_path_call(f, a);
+                                        // the rows the image cannot hold, or 2^32 of them, are turned away in the call's own name
+                                        if (r.code != PT_OK) CHECK(r.msg.rfind("pt_render_camera: ", 0) == 0);
+                                        if (turned_away(r) || turned_away(tri_lights_rule(f, flags)) || turned_away(plan_rays(f, a, plan))) continue;
+                                        CHECK(n < (1ull << 32) && (list || n + 5 <= 65536ull * 65535ull));
+                                        n_planned++;
+                                        camera.request(rays_word(plan.L));
+                                        CHECK(plan.L.lds <= PT_LDS_BYTES && plan.q.refill <= plan.q.batch && plan.per_launch >= 1 && plan.per_launch <= spp);
+                                        CHECK(plan.per_launch == 1 || plan.per_launch * n <= RAYS_MAX_SLOTS);
+                                        for (uint32_t s0 = 0; s0 < spp; s0 += plan.per_launch) {
+                                            int work_blocks = 0;
+                                            const int chunk = plan_rays_launch(f, a, plan, std::min(plan.per_launch, spp - s0), work_blocks);
+                                            CHECK(work_blocks >= 1 && (chunk == 16 || chunk == 32 || chunk == 64));
+                                        }
+                                    }
+    {   // ... and its argument rules, each broken alone and the order in which they answer (include/ptmi.h)
+        const CtxFacts f = scene(TREE, SPHERES[1], MATS[0], ENV_NONE), empty = scene(NO_TREE, SPHERES[0], MATS[0], ENV_NONE), woop = scene(TREE_WOOP, SPHERES[1], MATS[0], ENV_NONE);
+        pt_params p = params(0, 0, 4, 0);
+        pt_camera_model cm = model(PT_CAM_PINHOLE, 37, 23);
+        auto call = [&](const CtxFacts& ctx, const pt_params* pp, uint32_t spp, bool buffers, uint64_t n, int mode, bool list, uint64_t first) {
+            const CallFacts a = {false, pp, spp, buffers, false, false, n, mode, true, &cm, list, first};
+            Refusal r = check_path_call(ctx, a);
+            RaysPlan plan = {};
+            if (r.code == PT_OK && !r.nothing) r = plan_rays(ctx, a, plan);
+            if (r.code != PT_OK) { CHECK(turned_away(r)); CHECK(r.msg.rfind("pt_render_camera: ", 0) == 0); }
+            return r;
+        };
+        auto says = [](const Refusal& r, const char* text) { return r.code != PT_OK && r.msg.find(text) != std::string::npos; };
+        CHECK(call(f, &p, 3, true, 37 * 23, PT_RAYS_CLAMPED, false, 0).code == PT_OK);
+        CHECK(says(call(empty, nullptr, 0, false, 0, 7, false, 0), "no scene uploaded"));        // no scene comes before nothing to do
+        CHECK(call(f, nullptr, 0, false, 10, 7, false, 0).nothing && call(f, nullptr, 3, false, 0, 7, false, 0).nothing);   // ... which comes before NULLs
+        CHECK(says(call(f, &p, 1, false, 10, 7, false, 0), "null argument") && says(call(f, nullptr, 1, true, 10, 7, false, 0), "null argument"));
+        cm.model = 9;
+        CHECK(says(call(f, &p, 1, true, 10, 7, false, 0), "mode must be"));                        // the mode before the model
+        CHECK(says(call(f, &p, 1, true, 10, PT_RAYS_HDR, false, 0), "unknown camera model"));
+        cm.model = -1;
+        CHECK(says(call(f, &p, 1, true, 10, PT_RAYS_HDR, false, 0), "unknown camera model"));
+        cm = model(PT_CAM_FISHEYE, 37, 23); cm.flags = 2; cm.width = 1;
+        CHECK(says(call(f, &p, 1, true, 10, PT_RAYS_HDR, false, 0), "unknown flag bits"));       // the flags before the image
+        cm.flags = PT_CAMF_CENTRE;
+        CHECK(says(call(f, &p, 1, true, 1ull << 32, PT_RAYS_HDR, false, 0), "width and height"));  // the image before n
+        cm.width = 65536; cm.height = 65536;
+        CHECK(says(call(f, &p, 1, true, 10, PT_RAYS_HDR, true, 0), "width and height"));
+        cm.width = 37; cm.height = 23;
+        CHECK(says(call(f, &p, 1, true, 1ull << 32, PT_RAYS_HDR, true, 0), "more than 2^32 - 1 rays"));
+        CHECK(says(call(f, &p, 1, true, 1ull << 32, PT_RAYS_HDR, false, 0), "more than 2^32 - 1 rays"));   // n before first_pixel + n
+        CHECK(says(call(f, &p, 1, true, 37 * 23, PT_RAYS_HDR, false, 1), "first_pixel + n exceeds") && says(call(f, &p, 1, true, 1, PT_RAYS_HDR, false, 37 * 23 + 1), "first_pixel + n exceeds"));
+        CHECK(call(f, &p, 1, true, 37 * 23 - 1, PT_RAYS_HDR, false, 1).code == PT_OK && call(f, &p, 1, true, 5000, PT_RAYS_HDR, true, 1ull << 40).code == PT_OK);   // a list: first_pixel is not read
+        cm.fisheye_fov = 7.0f; p.sample_index = 0;
+        CHECK(says(call(f, &p, 1, true, 37 * 23 + 1, PT_RAYS_HDR, false, 0), "first_pixel + n exceeds"));   // ... before the model's parameter
+        CHECK(says(call(f, &p, 1, true, 10, PT_RAYS_HDR, false, 0), "fisheye_fov must be"));       // the model's parameter before pt_render_rays' own rules
+        cm.fisheye_fov = 0.0f;
+        CHECK(says(call(f, &p, 1, true, 10, PT_RAYS_HDR, false, 0), "fisheye_fov must be"));
+        cm.model = PT_CAM_ORTHO;   // another model's parameter is ignored
+        CHECK(says(call(f, &p, 1, true, 10, PT_RAYS_HDR, false, 0), " starts at 1"));
+        const float inf = 1.0f / 0.0f * (float)(p.depth != 0), nan = inf - inf;
+        for (float bad : {0.0f, -1.0f, inf, nan}) { cm.ortho_height = bad; CHECK(says(call(f, &p, 1, true, 10, PT_RAYS_HDR, false, 0), "ortho_height must be")); }
+        cm = model(PT_CAM_THIN_LENS, 37, 23);
+        for (float bad : {-0.5f, inf, nan}) { cm.lens_radius = bad; CHECK(says(call(f, &p, 1, true, 10, PT_RAYS_HDR, false, 0), "lens_radius must be")); }
+        cm.lens_radius = 0.0f;
+        for (float bad : {0.0f, -1.0f, inf, nan}) { cm.focus_dist = bad; CHECK(says(call(f, &p, 1, true, 10, PT_RAYS_HDR, false, 0), "lens_radius must be")); }
+        cm.focus_dist = 1.0f;
+        CHECK(says(call(f, &p, 1, true, 10, PT_RAYS_HDR, false, 0), " starts at 1"));
+        p.sample_index = 1; p.tri_mat = -1; p.flags = PT_FLAG_NEE;
+        CHECK(says(call(f, &p, 1, true, 10, PT_RAYS_HDR, false, 0), "bad triangle material"));
+        p.tri_mat = PT_MAT_DIFF;
+        CHECK(says(call(f, &p, 1, true, 10, PT_RAYS_HDR, false, 0), "PT_FLAG_NEE needs PT_FLAG_COSINE_DIFF"));
+        p.flags = PT_FLAG_MIS | COS;
+        CHECK(says(call(f, &p, 1, true, 10, PT_RAYS_HDR, false, 0), "PT_FLAG_MIS needs PT_FLAG_NEE"));
+        p.flags = MIS;
+        CHECK(call(f, &p, 1, true, 10, PT_RAYS_HDR, false, 0).code == PT_OK && says(call(woop, &p, 1, true, 10, PT_RAYS_HDR, false, 0), "PT_FLAG_MIS needs the exact"));
+    }
+
     // (h) pt_closest_hits / pt_any_hits: the wide walk's two budgets, the binary walk for a tree too deep
     for (const Tree& t : {TREE, TREE_OCC, TREE_23, TREE_DEEP})
         for (int lstk : {0, 16, 24})
@@ -364,6 +467,7 @@ int main() {
                     }
 
     for (const Family* fam : {&mega, &persist, &rays, &query, &extend, &shade, &last_any, &fused}) fam->report();
+    std::printf("camera family %s: requests=%ld words=%d kernels=%d\n", camera.name, camera.requests, camera.words(), variant_count(camera.exists, camera.n_bits));
     std::printf("%ld plans, %ld refusals\n", n_planned, n_refused);
     for (const auto& e : REFUSALS)
         if (!e.seen && n_failed++ < 20) std::printf("FAILED: no call of the domain is refused with \"%s\"\n", e.text);

@@ -672,6 +672,47 @@ int pt_render_rays(pt_ctx* c, const float* rays_dev, size_t n_rays, uint64_t fir
     return PT_OK;
 }
 
+// pt_render_rays with the rays made in the kernel: the same plan, sample buffer, launches and fold over the call's rows
+int pt_render_camera(pt_ctx* c, const pt_camera* cam, const pt_camera_model* cm, const uint32_t* pixels_dev, size_t n, uint64_t first_pixel,
+                     float* radiance_dev, const pt_params* p, uint32_t spp, int mode) {
+    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
+    const CtxFacts f = ctx_facts(c);
+    const CallFacts a = {false, p, spp, cam && cm && radiance_dev, false, false, n, mode, true, cm, pixels_dev != nullptr, first_pixel};
+    Refusal r = check_path_call(f, a);
+    if (r.code != PT_OK || r.nothing) return fail(c, r);
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = refresh_tri_lights(c, f, p);
+    if (rc != PT_OK) return rc;
+    RaysPlan plan;
+    r = plan_rays(f, a, plan);
+    if (r.code != PT_OK) return fail(c, r);
+    KParams P;
+    fill_path_params(c, f, p, spp, P);
+    P.cam = *cam;
+    P.sc.stack_n = plan.L.lstk;
+    P.sc.top_base = plan.L.walk >= 2 ? P.sc.wide_root : 0;
+    P.sph_tab = plan.sph_tab;
+    queue_params(plan.q, c->d_queue.get(), P);
+    const ptmi::CameraCall R{cm, pixels_dev, first_pixel, radiance_dev, n, mode == PT_RAYS_HDR};
+    const ptmi::RaysCall fold{nullptr, radiance_dev, 0, n, mode == PT_RAYS_HDR};
+    const uint32_t per_launch = plan.per_launch;
+    if (per_launch > 1 && (rc = samples_reserve(c, nullptr, (size_t)per_launch * n * 3, P)) != PT_OK) return rc;
+    P.smp_ss = n;
+    P.smp_ps = 1u;
+    HIP_TRY(c, span_begin(c));
+    for (uint32_t s0 = 0; s0 < spp; s0 += per_launch) {
+        P.spp = std::min(per_launch, spp - s0);
+        P.frame = p->frame + s0;
+        P.sample_index = p->sample_index + s0;
+        P.chunk = plan_rays_launch(f, a, plan, P.spp, plan.L.work_blocks);
+        HIP_TRY(c, queue_reset(P.queue, c->stream));
+        HIP_TRY(c, launch_render_camera(plan.L, P, R, c->stream));
+        if (per_launch > 1) HIP_TRY(c, launch_fold_rays(c, P, fold));
+    }
+    HIP_TRY(c, span_end(c));
+    return PT_OK;
+}
+
 int pt_get_counters(pt_ctx* c, pt_counters* out) {
     if (!c || !out) return fail(c, PT_ERR_INVALID, "pt_get_counters: null argument");
     unsigned long long h[PT_CNT_WAVE];

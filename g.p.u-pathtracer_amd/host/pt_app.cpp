@@ -11,7 +11,7 @@
 //               --denoise-out image.ppm|.png|.pfm  --denoise-variance  --variance-out file.pfm  --until-error E --max-frames M
 //               --pan-deg D --dolly S --spin-deg D --temporal-out image.ppm|.png|.pfm  --equirect
 //               --env file.pfm [--env-scale S] [--env-nearest] [--env-light]
-//               --camera pinhole|thinlens|ortho|fisheye|equirect [--aperture R --focus D --ortho-height S --fisheye-deg A]]
+//               --camera pinhole|thinlens|ortho|fisheye|equirect [--aperture R --focus D --ortho-height S --fisheye-deg A] [--camera-loop]]
 // --gpus N splits the framebuffer over N contexts, one per GPU (devices device, device+1, ... modulo the number
 // present, so N > 1 also runs on a one-GPU box): stripes of --tile rows (default 8) are dealt round-robin
 // (pt_params.part_*), every context holds the whole scene and renders only its stripes of every frame — the random
@@ -59,11 +59,12 @@
 // every call renders them through pt_render_rays (pixel y W + x draws the random numbers of that pixel of a pinhole frame):
 // clamped mode when --out is a .png / .ppm, HDR when it is a .pfm.  There is no pinhole frame, so --equirect is refused with
 // --denoise-out, --temporal-out, --variance-out, --until-error, --gpus > 1, --checkpoint, --resume and the motion options.
-// --camera MODEL renders through one of the camera models of pt_camera_rays instead of pt_render's pinhole: per sample one
-// pt_camera_rays call writes the jittered rays of every pixel for that sample's frame number on the device and one one-sample
-// pt_render_rays call traces them (the loop of gpu_pathtracer_amd.PathTracer.render_camera; --spp only groups the samples between two
-// pt_sync), so every sample has its own sub-pixel jitter and, for thinlens, its own point on the lens: anti-aliasing and depth of
-// field.  pinhole is pt_render's camera (the same samples, bit for bit); thinlens takes --aperture R (lens radius in world units,
+// --camera MODEL renders through one of the camera models of pt_camera_rays instead of pt_render's pinhole: one pt_render_camera
+// call per --spp group makes every sample's jittered ray in the path kernel, so every sample has its own sub-pixel jitter and, for
+// thinlens, its own point on the lens: anti-aliasing and depth of field.  --camera-loop renders the same samples the way the call
+// is defined: per sample one pt_camera_rays call writes the jittered rays of every pixel for that sample's frame number on the
+// device and one one-sample pt_render_rays call traces them (the loop of gpu_pathtracer_amd.PathTracer.render_camera; --spp only
+// groups the samples between two pt_sync); only it allocates a ray buffer, and the two write byte-identical files.  pinhole is pt_render's camera (the same samples, bit for bit); thinlens takes --aperture R (lens radius in world units,
 // default 0: everything sharp) and --focus D (distance of the plane in focus along front, default 35: the mirror sphere);
 // ortho takes --ortho-height S (world height of the view volume, default 30: the sphere room's); fisheye takes --fisheye-deg A
 // (full angle across the image circle, default 180; pixels outside the circle get --bk); equirect is the layout of --equirect,
@@ -113,6 +114,7 @@ int main(int argc, char** argv) {
     long max_frames = -1;
     double pan_deg = 0.0, dolly = 0.0, spin_deg = 0.0;
     std::string camera_name;   // --camera: empty = pt_render's own pinhole
+    bool camera_loop = false;  // --camera-loop: pt_camera_rays + pt_render_rays per sample instead of pt_render_camera
     double aperture = 0.0, focus = 35.0, ortho_height = 30.0, fisheye_deg = 180.0;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -145,6 +147,7 @@ int main(int argc, char** argv) {
         else if (a == "--mis") mis = true;   // ... with its shadow rays weighed against the bounce rays (implies --nee)
         else if (a == "--equirect") equirect = true;
         else if (a == "--camera") camera_name = next("--camera");
+        else if (a == "--camera-loop") camera_loop = true;
         else if (a == "--aperture") aperture = std::atof(next("--aperture"));
         else if (a == "--focus") focus = std::atof(next("--focus"));
         else if (a == "--ortho-height") ortho_height = std::atof(next("--ortho-height"));
@@ -185,6 +188,7 @@ int main(int argc, char** argv) {
     // --camera: the model of pt_camera_rays; its own parameter is checked by the library at the first call
     const bool ray_camera = !camera_name.empty();
     pt_camera_model cmodel{};
+    if (camera_loop && !ray_camera) return die("usage", "--camera-loop needs --camera MODEL");
     if (ray_camera) {
         const char* names[5] = {"pinhole", "thinlens", "ortho", "fisheye", "equirect"};   // PT_CAM_* in order
         cmodel.model = -1;
@@ -485,8 +489,8 @@ int main(int argc, char** argv) {
         if (pt_malloc(ctx, rays.size() * 4, &eq_rays) != PT_OK || pt_upload(ctx, eq_rays, rays.data(), rays.size() * 4) != PT_OK)
             return die("equirect rays", pt_last_error(ctx));
     }
-    // --camera: the buffer pt_camera_rays fills for every sample, float[H W][8]
-    if (ray_camera && pt_malloc(ctx, (size_t)W * H * 32, &eq_rays) != PT_OK) return die("camera rays", pt_last_error(ctx));
+    // --camera --camera-loop: the buffer pt_camera_rays fills for every sample, float[H W][8]
+    if (ray_camera && camera_loop && pt_malloc(ctx, (size_t)W * H * 32, &eq_rays) != PT_OK) return die("camera rays", pt_last_error(ctx));
 
     const uint64_t first_frame = frameNumber;
     uint64_t end_frame = frameNumber + (uint64_t)frames;
@@ -507,7 +511,10 @@ int main(int argc, char** argv) {
             if (equirect) {
                 if (pt_render_rays(ctx, (const float*)eq_rays, (size_t)W * H, 0, (float*)accum, &p, n, out_pfm ? PT_RAYS_HDR : PT_RAYS_CLAMPED) != PT_OK)
                     return die("pt_render_rays", pt_last_error(ctx));
-            } else if (ray_camera) {   // a fresh jittered ray per sample: generate, trace, on one stream
+            } else if (ray_camera && !camera_loop) {   // a fresh jittered ray per sample, made where its path starts
+                if (pt_render_camera(ctx, &cam, &cmodel, nullptr, (size_t)W * H, 0, (float*)accum, &p, n, out_pfm ? PT_RAYS_HDR : PT_RAYS_CLAMPED) != PT_OK)
+                    return die("pt_render_camera", pt_last_error(ctx));
+            } else if (ray_camera) {   // the same samples by their definition: generate, trace, on one stream
                 pt_params q = p;
                 for (uint32_t s = 0; s < n; s++) {
                     q.frame = p.frame + s; q.sample_index = p.sample_index + s;

@@ -240,6 +240,20 @@ class PathTracer:
             self.camera_rays(cam, model, q.frame, rays_ptr)
             self.render_rays(rays_ptr, n, out_ptr, q, 1, 0, hdr)
 
+    def render_model(self, cam, model, params, out_ptr, spp=1, hdr=False, n=None, first_pixel=0, pixels_ptr=None):
+        """spp samples of pixels of a camera model's image in ONE call (pt_render_camera): what render_camera's loop computes, bit
+        for bit, without a ray buffer and without a launch per sample — each sample's jittered ray is made in the path kernel.
+        out float[n][3], the running mean of render_rays (N = params.sample_index ..); row i is pixel first_pixel + i, or
+        pixels_ptr[i] (uint32 on the device; n is then required): a listed pixel gets the bits it has in the full frame, an index
+        past the image the miss sample.  n defaults to the pixels from first_pixel to the end of the image.  Asynchronous until
+        sync()."""
+        if n is None:
+            if pixels_ptr is not None:
+                raise ValueError("render_model: a pixel list needs n")
+            n = model.width * model.height - int(first_pixel)
+        self._check(self._lib.pt_render_camera(self._ctx, C.byref(cam), C.byref(model), pixels_ptr, int(n), int(first_pixel), out_ptr,
+                                               C.byref(params), int(spp), _abi.RAYS_HDR if hdr else _abi.RAYS_CLAMPED))
+
     def upload_environment(self, texels, front=(0, 0, -1), right=(1, 0, 0), up=(0, 1, 0), scale=(1, 1, 1), filter=_abi.ENV_BILINEAR, light=False):
         """Light the paths that leave the scene with a latitude-longitude map (pt_upload_environment) instead of bk_color: texels
         float32 [H][W][3] on the host, in the layout `pt_app --equirect` writes for a camera with this front / right / up (the

@@ -630,6 +630,44 @@ int pt_camera_rays(pt_ctx* ctx, const pt_camera* cam, const pt_camera_model* cm,
                    const uint32_t* pixels_dev /* may be NULL */, size_t n, uint64_t first_pixel,
                    float* rays_dev /* float[n][8] */);
 
+/* ---- a camera model's frame in one call: each sample's ray made in the path kernel — an EXTENSION ----
+ * pt_render_camera path-traces pixels of a cm->width x cm->height image under any of the five camera models without a ray buffer
+ * and without a launch per sample: what the loop "per sample, pt_camera_rays then a one-sample pt_render_rays" computes, in one
+ * call.  binary32 throughout, as stated for those two calls.
+ * Pixel of a row: row i is pixel pix = pixels_dev ? pixels_dev[i] : first_pixel + i.  radiance_dev: float[n][3], the running mean
+ * per row; pixels_dev: n pixel numbers on the device, or NULL.
+ * Ray of a sample: sample s = 0 .. spp-1 of row i starts at exactly the row pt_camera_rays writes for pix in frame
+ * params->frame + s — the model's arithmetic, the jitter stream, PT_CAMF_CENTRE, the lens stream frame ^ PT_CAM_LENS_KEY, and the
+ * zero-direction row of a fisheye pixel outside the image circle or of a listed index >= W * H, which pt_render_rays' guard makes a
+ * first-segment miss (bk_color).
+ * The path's random stream is that of pixel pix — not of the row number — in frame params->frame + s, standing behind the two
+ * jitter draws: pt_render's stream for that pixel.  Under PT_CAMF_CENTRE it stands behind them too, as in the loop.
+ * Everything behind the first segment is pt_render_rays': depth, materials, spheres, every PT_FLAG_*, next-event estimation, MIS,
+ * the environment map (lookup and light), Woop records, and the fold with N = params->sample_index + s under PT_RAYS_CLAMPED /
+ * PT_RAYS_HDR.  spp samples in one call equal any split of them over calls (frame and sample_index advanced alike) bit for bit, and
+ * one call equals calls over its parts by first_pixel.  pt_params is read as by pt_render_rays: width only under
+ * PT_FLAG_METAL_LITERAL_W — the image is cm's.
+ * Guarantees (tests/test_gpu_render_camera.py):
+ *   (a) without a list the result equals, bit for bit, the loop over s of pt_camera_rays(frame + s, first_pixel) and
+ *       pt_render_rays(first_index = first_pixel, frame + s, sample_index + s, spp 1), for all five models;
+ *   (b) hence with PT_CAM_PINHOLE, first_pixel 0, n = W * H and PT_RAYS_CLAMPED it is pt_render's accumulator bit for bit;
+ *   (c) with a list, row i equals row pixels_dev[i] of the full-frame call bit for bit: repeated indices repeat the value, an index
+ *       past the image gives the miss sample (bk_color).  So any listed subset of pixels renders with the bits of the full frame.
+ * Errors, in this order; nothing is written on any of them: NULL ctx PT_ERR_INVALID; neither a tree nor spheres PT_ERR_NO_SCENE;
+ * n == 0 or spp == 0 PT_OK, nothing written; a NULL cam, cm, radiance_dev or params PT_ERR_INVALID; a mode other than the two
+ * PT_ERR_INVALID; pt_camera_rays' checks of cm, n and first_pixel in its order and with its wording, prefixed pt_render_camera:;
+ * then pt_render_rays' remaining ones: sample_index == 0, a bad tri_mat, the PT_FLAG_NEE / PT_FLAG_MIS combinations, its refusals
+ * over Woop records.
+ * Asynchronous on the context's stream.  Scratch is the shared sample buffer under pt_render_rays' rule: [spp][n][3] floats, at most
+ * 2^26 slots per launch, more samples go out as several launches.  With PT_OPT_TIMING=1, pt_last_kernel_ms covers the call.
+ * PT_OPT_BATCH, PT_OPT_REFILL and PT_OPT_SPHERE_LDS apply: speed, never results.  PT_OPT_KERNEL, the counters and PT_KERNEL_AUTO's
+ * table are neither read nor changed.  The kernel is pt_render_rays' loop with another path start (csrc/pt_rays_loop.h); the model
+ * is a value of the launch, not an instantiation.
+ * Left out: luminance moments; display words; guide buffers for these cameras; the stage-split pipeline. */
+int pt_render_camera(pt_ctx* ctx, const pt_camera* cam, const pt_camera_model* cm,
+                     const uint32_t* pixels_dev /* may be NULL */, size_t n, uint64_t first_pixel,
+                     float* radiance_dev /* float[n][3] */, const pt_params* params, uint32_t spp, int mode);
+
 /* ---- environment map — an EXTENSION -----------------------------------------
  * pt_upload_environment gives the context a latitude-longitude (equirectangular) radiance map: what a path segment that hits
  * nothing gathers instead of the one constant bk_color, so that open scenes — a mesh on its own, a probe rendered elsewhere — are

@@ -6,6 +6,11 @@ camera at 1920x1080, depth 4), device time by PT_OPT_TIMING (pt_last_kernel_ms; 
       jittered ray per sample — against ONE pt_render_rays(spp = 16) call over fixed rays (the pinhole's centre rays, made by the
       generator once): what anti-aliasing costs.  The loop's device time is the sum over its 32 calls, split into the generator's
       share and the one-sample traces'; the wall clock from sync to sync of both is printed beside it (the loop untimed there).
+  (c) the same frame three ways, per model, each as the span of ONE timed region on the stream (wall clock from sync to sync with
+      PT_OPT_TIMING off, so the loop's launches queue up as they do in a host's frame loop) and, for the single calls, the device
+      time of pt_last_kernel_ms beside it: (i) the loop, (ii) pt_render_camera(spp = 16) — PathTracer.render_model, the rays made
+      in the path kernel — and (iii) pt_render_rays(spp = 16) over fixed rays.  Median and min .. max of --reps after --warmup;
+      the three are interleaved rep by rep so that drift hits them alike.
 Usage: python tools/camera_bench.py [--out FILE] [--reps 7] [--warmup 2]"""
 import argparse
 import os
@@ -100,6 +105,40 @@ for name, kw in MODELS:
     loop = med(gen) + med(trace)
     say(f"  {name:<9} loop {loop:8.3f} ms = generator {med(gen):6.3f} + {a.spp} one-sample traces {med(trace):8.3f};  fixed rays, one call {med(one):8.3f} ms;"
         f"  loop / one call = {loop / med(one):.3f}   (wall clock {med(wall_loop):8.3f} / {med(wall_one):8.3f} = {med(wall_loop) / med(wall_one):.3f})")
+say(f"(c) a {a.spp}-sample frame, wall clock sync to sync in ms, median [min .. max]: (i) the loop, (ii) pt_render_camera(spp = {a.spp}), "
+    f"(iii) pt_render_rays(spp = {a.spp}) over fixed rays; device ms of (ii) and (iii) by PT_OPT_TIMING")
+
+
+def wall(fn):
+    t.sync()
+    t0 = time.perf_counter()
+    fn()
+    t.sync()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def spread(v):
+    v = v[a.warmup:]
+    return f"{np.median(v):8.3f} [{min(v):8.3f} .. {max(v):8.3f}]"
+
+
+for name, kw in MODELS:
+    cm = g.camera_model(name, W, H, **kw)
+    fixed = g.camera_model(name, W, H, centre=True, **kw)
+    w_loop, w_fused, w_fixed, d_fused, d_fixed = [], [], [], [], []
+    for k in range(a.warmup + a.reps):
+        t.set_option(g.OPT_TIMING, 0)
+        w_loop.append(wall(lambda: t.render_camera(cam, cm, p, out.ptr, rays.ptr, spp=a.spp)))
+        w_fused.append(wall(lambda: t.render_model(cam, cm, p, out.ptr, spp=a.spp)))
+        t.camera_rays(cam, fixed, 0, rays.ptr)
+        w_fixed.append(wall(lambda: t.render_rays(rays.ptr, W * H, out.ptr, p, a.spp)))
+        t.set_option(g.OPT_TIMING, 1)
+        t.render_model(cam, cm, p, out.ptr, spp=a.spp)
+        d_fused.append(t.last_kernel_ms())
+        t.render_rays(rays.ptr, W * H, out.ptr, p, a.spp)
+        d_fixed.append(t.last_kernel_ms())
+    say(f"  {name:<9} (i) {spread(w_loop)}  (ii) {spread(w_fused)}  (iii) {spread(w_fixed)}   (i) / (ii) = {med(w_loop) / med(w_fused):.3f}, "
+        f"(ii) - (iii) = {med(w_fused) - med(w_fixed):+.3f} ms;  device (ii) {spread(d_fused)}  (iii) {spread(d_fixed)}")
 rays.free()
 out.free()
 t.set_option(g.OPT_TIMING, 0)
