@@ -66,6 +66,12 @@ class CameraModel(C.Structure):
                 ("lens_radius", C.c_float), ("focus_dist", C.c_float), ("ortho_height", C.c_float), ("fisheye_fov", C.c_float)]
 
 
+class SelectParams(C.Structure):
+    """pt_select_params — the rule of pt_select_pixels (extension, include/ptmi.h; 24 bytes)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("threshold", C.c_float),
+                ("min_samples", C.c_uint32), ("max_samples", C.c_uint32), ("_pad", C.c_int32)]
+
+
 class CheckpointInfo(C.Structure):
     """pth_checkpoint_info (host/pthost.h)."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("next_frame", C.c_uint64),
@@ -152,6 +158,8 @@ PTMI_SYMBOLS = [
     ("pt_render_rays", _i, [_vp, _vp, _sz, C.c_uint64, _vp, C.POINTER(Params), _u32, _i]),
     ("pt_camera_rays", _i, [_vp, C.POINTER(Camera), C.POINTER(CameraModel), C.c_uint64, _vp, _sz, C.c_uint64, _vp]),
     ("pt_render_camera", _i, [_vp, C.POINTER(Camera), C.POINTER(CameraModel), _vp, _sz, C.c_uint64, _vp, C.POINTER(Params), _u32, _i]),
+    ("pt_render_pixels", _i, [_vp, C.POINTER(Camera), C.POINTER(CameraModel), _vp, _sz, _vp, _vp, _vp, C.POINTER(Params), _u32, _i]),
+    ("pt_select_pixels", _i, [_vp, C.POINTER(SelectParams), _vp, _vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     ("pt_upload_environment", _i, [_vp, C.POINTER(Environment), _vp]),
     ("pt_eval_environment", _i, [_vp, _vp, _sz, _vp]),
     ("pt_environment_is_light", _i, [_vp, C.POINTER(_i)]),

@@ -1,6 +1,6 @@
 // pt_ctx.h — the context behind the C ABI (include/ptmi.h) and the host-side helpers shared by the
 // translation units of libptmi.so: ptmi.hip (API), pt_tree.hip (trees: makers, adoption, cost), pt_build.hip (device BVH
-// builder), pt_refit.hip (refit), pt_denoise.hip (guide buffers, denoiser, temporal filter, frame error), pt_k_*.hip (kernel families +
+// builder), pt_refit.hip (refit), pt_denoise.hip (guide buffers, denoiser, temporal filter, frame error, pixel selection), pt_k_*.hip (kernel families +
 // their launchers, no API function), pt_env.hip (environment map), pt_camera.hip (camera models).  Host code only.
 // Every device buffer, event and stream of the context is a member that owns it (pt_own.h): pt_destroy waits and deletes.  The scene's
 // resources — tree, spheres, materials, environment — are values: built in a local, adopted behind quiesce().
@@ -221,6 +221,8 @@ struct pt_ctx {
     DevBuf<float4> d_denoise;
     // pt_frame_error's per-block partial results (pt_denoise.hip): [blocks] double sums, then [blocks] uint32 counts; grow-only
     DevBuf<char> d_frame_err;
+    // pt_select_pixels' per-block scratch (pt_denoise.hip): [blocks] double sums, [blocks] uint32 counts, [blocks] uint32 list offsets; grow-only
+    DevBuf<char> d_select;
     Event ev0, ev1;
     bool timed = false;
     // PT_OPT_TIMING: events between the stages of the last call (pt_get_stage_ms); stage_kind[i] is the
@@ -370,6 +372,18 @@ struct CameraCall {
     int hdr;                     // mode == PT_RAYS_HDR
 };
 hipError_t launch_render_camera(const LaunchCfg& L, const KParams& P, const CameraCall& r, hipStream_t st);
+// pt_render_pixels' fold (pt_k_rays.hip): the launch's sample buffer [P.spp][n][3] scattered into full-frame buffers, every listed
+// pixel from its own sample count on
+struct PixelsCall {
+    const uint32_t* pixels;   // n pixel numbers on the device, or nullptr: row i is pixel i
+    float* accum;             // float[n_pix][3]
+    float* moments;           // float[n_pix][2], or nullptr
+    uint32_t* counts;         // uint32[n_pix]
+    size_t n;                 // 0 < n < 2^32
+    uint32_t n_pix;           // width * height: a listed index from here on is skipped
+    int hdr;                  // mode == PT_RAYS_HDR
+};
+hipError_t launch_fold_pixels(const pt_ctx* c, const KParams& P, const PixelsCall& r);
 // PT_OPT_TIMING: marks the end of a stage of the running call on the context's stream (no-op when timing is off)
 int stage_mark(pt_ctx* c, int kind_of_work_since_last_mark);
 // device BVH builder (pt_build.hip), a maker: the tree over the mesh into `out` (its build_ms set), the context's own tree untouched.

@@ -1,6 +1,6 @@
 // pt_plan.h — what every call runs, decided in plain C++: the argument rules of the path calls, the walk, the kernel family, the side
 // stream, the sample and LDS layouts, the queue and the grids, the stage-split pipeline's records and launches, the plans of
-// pt_render_rays and of the ray-batch queries.  Every function here is a pure function of plain facts: what the context holds
+// pt_render_rays, of pt_select_pixels and of the ray-batch queries.  Every function here is a pure function of plain facts: what the context holds
 // (CtxFacts, filled by ctx_facts in ptmi.hip), what the caller passed (CallFacts) and the two answers only the runtime has (whether the
 // caller's stream is idle; PT_KERNEL_AUTO's table).  The entry points gather the facts, ask, and apply the answer; the check program
 // (pt_variants_check.cpp) asks the same functions over a domain of scenes x options x calls on the host.  No HIP call, no HIP type.
@@ -38,8 +38,10 @@ struct CallFacts {
     const pt_camera_model* cm = nullptr;
     bool list = false;
     uint64_t first_pixel = 0;
+    // pt_render_pixels (a camera call): buffers counts accum_dev and counts_dev in, moments is moments_dev; without a list its rows are the whole image
+    bool pixels = false;
 };
-inline const char* path_call_name(const CallFacts& a) { return a.frame ? "pt_render" : a.camera ? "pt_render_camera" : "pt_render_rays"; }
+inline const char* path_call_name(const CallFacts& a) { return a.frame ? "pt_render" : a.pixels ? "pt_render_pixels" : a.camera ? "pt_render_camera" : "pt_render_rays"; }
 // A call the rules turn away (code != PT_OK, with pt_last_error's text), or one with nothing to do (nothing: PT_OK at once)
 struct Refusal {
     int code = PT_OK;
@@ -48,14 +50,16 @@ struct Refusal {
 };
 
 // ---- the rules of a camera model and the pixels asked of it, in pt_camera_rays' order and wording under the caller's name: an unknown
-// model or flag bits, the image, n, first_pixel + n without a list, the chosen model's own parameter (the others are ignored)
+// model or flag bits, the image, n, first_pixel + n without a list (whole: n is the image, pt_render_pixels), the chosen model's own parameter
+// (the others are ignored)
 inline bool plan_finite(float x) { return x - x == 0.0f; }   // neither an infinity nor a NaN
-inline Refusal check_camera_model(const std::string& who, const pt_camera_model& cm, uint64_t n, uint64_t first_pixel, bool list) {
+inline Refusal check_camera_model(const std::string& who, const pt_camera_model& cm, uint64_t n, uint64_t first_pixel, bool list, bool whole = false) {
     if (cm.model < PT_CAM_PINHOLE || cm.model > PT_CAM_EQUIRECT) return {PT_ERR_INVALID, who + ": unknown camera model"};
     if (cm.flags & ~PT_CAMF_CENTRE) return {PT_ERR_INVALID, who + ": unknown flag bits"};
     const uint64_t n_pix = (uint64_t)(cm.width > 0 ? cm.width : 0) * (uint64_t)(cm.height > 0 ? cm.height : 0);
     if (cm.width < 2 || cm.height < 2 || n_pix >= (1ull << 32)) return {PT_ERR_INVALID, who + ": width and height must be >= 2 with width * height < 2^32"};
     if (n >= (1ull << 32)) return {PT_ERR_INVALID, who + ": more than 2^32 - 1 rays in one call"};
+    if (!list && whole && n != n_pix) return {PT_ERR_INVALID, who + ": without a pixel list n must equal width * height"};
     if (!list && (first_pixel > n_pix || n > n_pix - first_pixel)) return {PT_ERR_INVALID, who + ": first_pixel + n exceeds width * height"};
     switch (cm.model) {
     case PT_CAM_THIN_LENS:
@@ -73,7 +77,7 @@ inline Refusal check_camera_model(const std::string& who, const pt_camera_model&
     return {};
 }
 
-// ---- the argument rules of pt_render, pt_render_rays and pt_render_camera, each call's in its own order and wording
+// ---- the argument rules of pt_render, pt_render_rays, pt_render_camera and pt_render_pixels, each call's in its own order and wording
 inline Refusal check_path_call(const CtxFacts& f, const CallFacts& a) {
     const std::string who(path_call_name(a));
     const bool no_scene = !f.has_bvh && f.n_spheres == 0;
@@ -89,7 +93,7 @@ inline Refusal check_path_call(const CtxFacts& f, const CallFacts& a) {
     } else {
         if (a.mode != PT_RAYS_CLAMPED && a.mode != PT_RAYS_HDR) return {PT_ERR_INVALID, who + ": mode must be PT_RAYS_CLAMPED or PT_RAYS_HDR"};
         if (a.camera) {
-            const Refusal r = check_camera_model(who, *a.cm, a.n_rays, a.first_pixel, a.list);
+            const Refusal r = check_camera_model(who, *a.cm, a.n_rays, a.first_pixel, a.list, a.pixels);
             if (r.code != PT_OK) return r;
         } else if (a.n_rays >= (1ull << 32)) return {PT_ERR_INVALID, who + ": more than 2^32 - 1 rays in one call"};
     }
@@ -368,7 +372,7 @@ inline Refusal plan_launch(const CtxFacts& f, const CallFacts& a, int n_tiles, b
     return plan_wave_layout(a.p->flags, a.p->depth, a.spp, plan.work_tiles, plan.wl);
 }
 
-// ---- pt_render_rays, pt_render_camera (the same plan under the call's own name: its rows are the batch) ---
+// ---- pt_render_rays, pt_render_camera, pt_render_pixels (the same plan under the call's own name: its rows are the batch) ---
 // slots of one launch: what keeps its sample buffer below 768 MiB; more samples than that go out as several launches, which the
 // fold's order makes the same thing
 constexpr uint64_t RAYS_MAX_SLOTS = 1ull << 26;
@@ -376,7 +380,9 @@ struct RaysPlan {
     LaunchCfg L;           // (no instrumented kernel; the register budget is rays_word's: by PT_FLAG_NEE)
     int sph_tab;
     QueueKnobs q;
-    uint32_t per_launch;   // samples per launch; > 1: through the sample buffer and a fold
+    uint32_t per_launch;   // samples per launch
+    bool samples;          // the launches go through the sample buffer and a fold: more than one sample per launch, or a call whose fold
+                           // does more than the kernel's one-sample fold in line (pt_render_pixels: a count per pixel, the moments)
 };
 inline Refusal plan_rays(const CtxFacts& f, const CallFacts& a, RaysPlan& plan) {
     plan = RaysPlan();
@@ -391,14 +397,37 @@ inline Refusal plan_rays(const CtxFacts& f, const CallFacts& a, RaysPlan& plan) 
     L.env = f.env;
     plan.q = queue_knobs(f);
     plan.per_launch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(a.spp, RAYS_MAX_SLOTS / a.n_rays));
+    plan.samples = plan.per_launch > 1 || a.pixels;
     return r;
 }
 // one launch of `spp_now` samples: its slots' queue chunk (the return value) and the blocks that have work at all
 inline int plan_rays_launch(const CtxFacts& f, const CallFacts& a, const RaysPlan& plan, uint32_t spp_now, int& work_blocks) {
-    const uint64_t slots = a.n_rays * (plan.per_launch > 1 ? spp_now : 1u);
+    const uint64_t slots = a.n_rays * (plan.samples ? spp_now : 1u);
     const int chunk = queue_chunk(f.n_cu, slots);
     work_blocks = (int)std::min<uint64_t>((slots + (uint64_t)chunk * 4 - 1) / ((uint64_t)chunk * 4), (uint64_t)INT_MAX);
     return chunk;
+}
+
+// ---- pt_select_pixels: its argument rules in the header's order (buffers: moments, counts, pixels and n_selected are all given);
+// n_pix: width * height of a call that passes
+inline Refusal check_select_call(const pt_select_params* sp, bool buffers, uint64_t& n_pix) {
+    n_pix = 0;
+    if (!sp || !buffers) return {PT_ERR_INVALID, "pt_select_pixels: null argument"};
+    n_pix = (uint64_t)(sp->width > 0 ? sp->width : 0) * (uint64_t)(sp->height > 0 ? sp->height : 0);
+    if (sp->width < 1 || sp->height < 1 || n_pix >= (1ull << 32)) return {PT_ERR_INVALID, "pt_select_pixels: width and height must be >= 1 with width * height < 2^32"};
+    if (!plan_finite(sp->threshold) || sp->threshold < 0.0f) return {PT_ERR_INVALID, "pt_select_pixels: threshold must be finite and >= 0"};
+    if (sp->min_samples > sp->max_samples) return {PT_ERR_INVALID, "pt_select_pixels: min_samples must not exceed max_samples"};
+    return {};
+}
+// its launches: 256-pixel blocks, and the context's scratch — per block a double sum and a uint32 count, which the host reads back,
+// and a uint32 list offset
+struct SelectPlan { size_t n_blocks, read_back, scratch; };
+inline SelectPlan plan_select(uint64_t n_pix) {
+    SelectPlan s;
+    s.n_blocks = (size_t)((n_pix + 255) / 256);
+    s.read_back = s.n_blocks * 12;
+    s.scratch = s.n_blocks * 16;
+    return s;
 }
 
 // ---- pt_closest_hits / pt_any_hits: the wide walk on a resident grid over regions of PT_REGION rays at one of the extend stage's two

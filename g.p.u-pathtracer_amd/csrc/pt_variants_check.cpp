@@ -1,6 +1,6 @@
 // pt_variants_check.cpp — every request has a kernel and every kernel a request, and every plan is sound: a CPU program with its own
 // main, no HIP library (`make variants_check`, SAN=1 for the address and undefined-behaviour sanitizers; tests/test_variants.py runs both).
-// It RUNS the planner (pt_plan.h: the functions pt_render, pt_render_rays, pt_render_camera and the ray-batch queries call) over a domain of scenes x
+// It RUNS the planner (pt_plan.h: the functions pt_render, pt_render_rays, pt_render_camera, pt_render_pixels, pt_select_pixels and the ray-batch queries call) over a domain of scenes x
 // options x calls x the runtime's answers, and holds no rule of its own: a call is skipped because the planner refused it, and the
 // refusal's code has to be the one REFUSALS lists for its text.  Of every plan it asserts what follows from the project's constants
 // (LDS, refill <= batch, grids, the record layout); of every variant word a plan asks a launcher for, that the word is instantiated —
@@ -65,6 +65,9 @@ static struct { const char* text; int code; long seen; } REFUSALS[] = {
     {": unknown camera model", PT_ERR_INVALID, 0}, {": unknown flag bits", PT_ERR_INVALID, 0}, {"width and height must be >= 2", PT_ERR_INVALID, 0},
     {"first_pixel + n exceeds width * height", PT_ERR_INVALID, 0}, {"lens_radius must be finite", PT_ERR_INVALID, 0},
     {"ortho_height must be finite", PT_ERR_INVALID, 0}, {"fisheye_fov must be in", PT_ERR_INVALID, 0},
+    // pt_render_pixels' own, and pt_select_pixels' (its null argument is the row above)
+    {"without a pixel list n must equal", PT_ERR_INVALID, 0}, {"width and height must be >= 1", PT_ERR_INVALID, 0},
+    {"threshold must be finite", PT_ERR_INVALID, 0}, {"min_samples must not exceed", PT_ERR_INVALID, 0},
 };
 static long n_refused = 0, n_planned = 0;
 // true: the planner refused the call or found nothing to do in it
@@ -449,6 +452,117 @@ int main() {
         CHECK(says(call(f, &p, 1, true, 10, PT_RAYS_HDR, false, 0), "PT_FLAG_MIS needs PT_FLAG_NEE"));
         p.flags = MIS;
         CHECK(call(f, &p, 1, true, 10, PT_RAYS_HDR, false, 0).code == PT_OK && says(call(woop, &p, 1, true, 10, PT_RAYS_HDR, false, 0), "PT_FLAG_MIS needs the exact"));
+    }
+
+    // (g'') pt_render_pixels: pt_render_camera's kernels over a list or over the whole image (n = W * H then, so the image is the n of the
+    // domain where it can be one), with and without moments; every launch goes through the sample buffer, a one-sample launch too
+    for (const Tree& t : TREES)
+        for (int env = ENV_NONE; env <= ENV_LIGHT; env++)
+            for (const Mats& m : {MATS[0], MATS[2]})
+                for (int walk : {0, 1, 2, 4})
+                    for (int knobs = 0; knobs < 4; knobs++)
+                        for (uint32_t flags : {0u, COS, NEE, MIS, (uint32_t)PT_FLAG_NEE, (uint32_t)(PT_FLAG_MIS | COS)})
+                            for (uint64_t n : {0ull, 1ull, 1000ull, (1ull << 26) / 3, 1ull << 26, (1ull << 32) - 1, 1ull << 32})
+                                for (uint32_t spp : {0u, 1u, 3u, 64u})
+                                    for (int call = 0; call < 10; call++) {   // model x list
+                                        CtxFacts f = scene(t, SPHERES[t.has_bvh ? 2 : knobs & 1], m, env);
+                                        f.walk = walk; f.sph_lds = knobs & 1; f.n_cu = knobs & 2 ? 256 : 8;
+                                        pt_params p = params(0, 0, 4, flags);
+                                        const bool list = call >= 5;
+                                        // without a list the image has n pixels where two factors >= 2 give it: 1000, 2^26
+                                        const pt_camera_model cm = list ? model(call % 5, 65536, 65535) : n == 1000 ? model(call % 5, 40, 25) : model(call % 5, 8192, 8192);
+                                        CallFacts a = {false, &p, spp, true, false, (call & 1) != 0, n, call == 3 ? (int)PT_RAYS_HDR : (int)PT_RAYS_CLAMPED, true, &cm, list, 0};
+                                        a.pixels = true;
+                                        RaysPlan plan = {};
+                                        const Refusal r = check_path_call(f, a);
+                                        if (r.code != PT_OK) CHECK(r.msg.rfind("pt_render_pixels: ", 0) == 0);
+                                        if (turned_away(r) || turned_away(tri_lights_rule(f, flags)) || turned_away(plan_rays(f, a, plan))) continue;
+                                        CHECK(n < (1ull << 32) && (list || n == (uint64_t)cm.width * (uint64_t)cm.height));
+                                        n_planned++;
+                                        camera.request(rays_word(plan.L));
+                                        CHECK(plan.samples);   // never the kernel's fold in line
+                                        CHECK(plan.L.lds <= PT_LDS_BYTES && plan.q.refill <= plan.q.batch && plan.per_launch >= 1 && plan.per_launch <= spp);
+                                        CHECK(plan.per_launch == 1 || plan.per_launch * n <= RAYS_MAX_SLOTS);
+                                        for (uint32_t s0 = 0; s0 < spp; s0 += plan.per_launch) {
+                                            int work_blocks = 0;
+                                            const int chunk = plan_rays_launch(f, a, plan, std::min(plan.per_launch, spp - s0), work_blocks);
+                                            CHECK(work_blocks >= 1 && (chunk == 16 || chunk == 32 || chunk == 64));
+                                        }
+                                    }
+    {   // ... its argument rules are pt_render_camera's under its own name, with one of its own where first_pixel's stands
+        const CtxFacts f = scene(TREE, SPHERES[1], MATS[0], ENV_NONE), empty = scene(NO_TREE, SPHERES[0], MATS[0], ENV_NONE), woop = scene(TREE_WOOP, SPHERES[1], MATS[0], ENV_NONE);
+        pt_params p = params(0, 0, 4, 0);
+        pt_camera_model cm = model(PT_CAM_PINHOLE, 37, 23);
+        auto call = [&](const CtxFacts& ctx, const pt_params* pp, uint32_t spp, bool buffers, uint64_t n, int mode, bool list) {
+            CallFacts a = {false, pp, spp, buffers, false, true, n, mode, true, &cm, list, 0};
+            a.pixels = true;
+            Refusal r = check_path_call(ctx, a);
+            RaysPlan plan = {};
+            if (r.code == PT_OK && !r.nothing) { r = plan_rays(ctx, a, plan); CHECK(plan.samples); }
+            if (r.code != PT_OK) { CHECK(turned_away(r)); CHECK(r.msg.rfind("pt_render_pixels: ", 0) == 0); }
+            return r;
+        };
+        auto says = [](const Refusal& r, const char* text) { return r.code != PT_OK && r.msg.find(text) != std::string::npos; };
+        CHECK(call(f, &p, 1, true, 37 * 23, PT_RAYS_CLAMPED, false).code == PT_OK && call(f, &p, 3, true, 5, PT_RAYS_HDR, true).code == PT_OK);
+        CHECK(says(call(empty, nullptr, 0, false, 0, 7, false), "no scene uploaded"));           // no scene comes before nothing to do
+        CHECK(call(f, nullptr, 0, false, 10, 7, false).nothing && call(f, nullptr, 3, false, 0, 7, true).nothing);   // ... which comes before NULLs
+        CHECK(says(call(f, &p, 1, false, 10, 7, false), "null argument") && says(call(f, nullptr, 1, true, 10, 7, false), "null argument"));
+        cm.model = 9;
+        CHECK(says(call(f, &p, 1, true, 10, 7, false), "mode must be"));                           // the mode before the model
+        CHECK(says(call(f, &p, 1, true, 10, PT_RAYS_HDR, false), "unknown camera model"));       // the model before n against the image
+        cm = model(PT_CAM_FISHEYE, 37, 23); cm.flags = 2; cm.width = 1;
+        CHECK(says(call(f, &p, 1, true, 10, PT_RAYS_HDR, false), "unknown flag bits"));
+        cm.flags = 0;
+        CHECK(says(call(f, &p, 1, true, 1ull << 32, PT_RAYS_HDR, false), "width and height"));     // the image before n
+        cm.width = 37;
+        CHECK(says(call(f, &p, 1, true, 1ull << 32, PT_RAYS_HDR, false), "more than 2^32 - 1 rays"));   // n < 2^32 before n against the image
+        cm.fisheye_fov = 7.0f; p.sample_index = 0;
+        for (uint64_t n : {1ull, 37ull * 23 - 1, 37ull * 23 + 1}) CHECK(says(call(f, &p, 1, true, n, PT_RAYS_HDR, false), "without a pixel list n must equal"));
+        CHECK(says(call(f, &p, 1, true, 37 * 23, PT_RAYS_HDR, false), "fisheye_fov must be"));     // ... before the model's parameter
+        CHECK(says(call(f, &p, 1, true, 5000, PT_RAYS_HDR, true), "fisheye_fov must be"));         // a list may be longer than the image
+        cm.fisheye_fov = 3.0f;
+        CHECK(says(call(f, &p, 1, true, 37 * 23, PT_RAYS_HDR, false), " starts at 1"));            // then pt_render_rays' own rules
+        p.sample_index = 1; p.tri_mat = -1; p.flags = PT_FLAG_NEE;
+        CHECK(says(call(f, &p, 1, true, 37 * 23, PT_RAYS_HDR, false), "bad triangle material"));
+        p.tri_mat = PT_MAT_DIFF;
+        CHECK(says(call(f, &p, 1, true, 37 * 23, PT_RAYS_HDR, false), "PT_FLAG_NEE needs PT_FLAG_COSINE_DIFF"));
+        p.flags = PT_FLAG_MIS | COS;
+        CHECK(says(call(f, &p, 1, true, 37 * 23, PT_RAYS_HDR, false), "PT_FLAG_MIS needs PT_FLAG_NEE"));
+        p.flags = MIS;
+        CHECK(call(f, &p, 1, true, 37 * 23, PT_RAYS_HDR, false).code == PT_OK && says(call(woop, &p, 1, true, 37 * 23, PT_RAYS_HDR, false), "PT_FLAG_MIS needs the exact"));
+    }
+
+    // (g3) pt_select_pixels: every rule broken alone and together (the first in the header's order answers), and the scratch of a call that passes
+    {
+        const float inf = 1.0f / 0.0f * (float)(KERNELS[1] != 0), nan = inf - inf;
+        auto says = [](const Refusal& r, const char* text) { return r.code != PT_OK && r.msg.find(text) != std::string::npos; };
+        for (int broken = 0; broken < 32; broken++) {
+            pt_select_params sp = {};
+            sp.width = broken & 2 ? 0 : 1920; sp.height = 1080; sp.threshold = broken & 4 ? -0.5f : 0.05f;
+            sp.min_samples = broken & 8 ? 65u : 4u; sp.max_samples = 64u;
+            uint64_t n_pix = 0;
+            const Refusal r = check_select_call(broken & 16 ? nullptr : &sp, !(broken & 1), n_pix);
+            CHECK((r.code == PT_OK) == !broken);
+            if (broken) CHECK(turned_away(r));
+            CHECK(says(r, broken & 17 ? "null argument" : broken & 2 ? "width and height must be >= 1" : broken & 4 ? "threshold must be finite" : "min_samples must not exceed") == (broken != 0));
+            if (!broken) {
+                n_planned++;
+                const SelectPlan s = plan_select(n_pix);
+                CHECK(n_pix == 1920ull * 1080 && s.n_blocks == 8100 && s.read_back == 8100 * 12 && s.scratch == 8100 * 16);
+            }
+        }
+        pt_select_params sp = {};
+        sp.width = sp.height = 65536; sp.max_samples = 1;
+        uint64_t n_pix = 0;
+        CHECK(says(check_select_call(&sp, true, n_pix), "width and height must be >= 1"));   // 2^32 pixels
+        sp.height = 65535; sp.min_samples = 1;
+        CHECK(check_select_call(&sp, true, n_pix).code == PT_OK && plan_select(n_pix).n_blocks == (1u << 24) - 256);
+        sp.height = -3;
+        CHECK(says(check_select_call(&sp, true, n_pix), "width and height must be >= 1"));
+        sp.height = 1;
+        for (float bad : {-1.0f, inf, -inf, nan}) { sp.threshold = bad; CHECK(says(check_select_call(&sp, true, n_pix), "threshold must be finite")); }
+        sp.threshold = 0.0f;
+        CHECK(check_select_call(&sp, true, n_pix).code == PT_OK && n_pix == 65536 && plan_select(1).n_blocks == 1 && plan_select(257).n_blocks == 2);
     }
 
     // (h) pt_closest_hits / pt_any_hits: the wide walk's two budgets, the binary walk for a tree too deep

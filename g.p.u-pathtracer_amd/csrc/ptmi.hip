@@ -655,7 +655,7 @@ int pt_render_rays(pt_ctx* c, const float* rays_dev, size_t n_rays, uint64_t fir
     queue_params(plan.q, c->d_queue.get(), P);   // the context's counters: every use is on the caller's stream, behind a reset of its own
     const ptmi::RaysCall R{rays_dev, radiance_dev, first_index, n_rays, mode == PT_RAYS_HDR};
     const uint32_t per_launch = plan.per_launch;
-    if (per_launch > 1 && (rc = samples_reserve(c, nullptr, (size_t)per_launch * n_rays * 3, P)) != PT_OK) return rc;
+    if (plan.samples && (rc = samples_reserve(c, nullptr, (size_t)per_launch * n_rays * 3, P)) != PT_OK) return rc;
     P.smp_ss = n_rays;
     P.smp_ps = 1u;
     HIP_TRY(c, span_begin(c));
@@ -666,7 +666,7 @@ int pt_render_rays(pt_ctx* c, const float* rays_dev, size_t n_rays, uint64_t fir
         P.chunk = plan_rays_launch(f, a, plan, P.spp, plan.L.work_blocks);
         HIP_TRY(c, queue_reset(P.queue, c->stream));
         HIP_TRY(c, launch_render_rays(plan.L, P, R, c->stream));
-        if (per_launch > 1) HIP_TRY(c, launch_fold_rays(c, P, R));
+        if (plan.samples) HIP_TRY(c, launch_fold_rays(c, P, R));
     }
     HIP_TRY(c, span_end(c));
     return PT_OK;
@@ -696,7 +696,7 @@ int pt_render_camera(pt_ctx* c, const pt_camera* cam, const pt_camera_model* cm,
     const ptmi::CameraCall R{cm, pixels_dev, first_pixel, radiance_dev, n, mode == PT_RAYS_HDR};
     const ptmi::RaysCall fold{nullptr, radiance_dev, 0, n, mode == PT_RAYS_HDR};
     const uint32_t per_launch = plan.per_launch;
-    if (per_launch > 1 && (rc = samples_reserve(c, nullptr, (size_t)per_launch * n * 3, P)) != PT_OK) return rc;
+    if (plan.samples && (rc = samples_reserve(c, nullptr, (size_t)per_launch * n * 3, P)) != PT_OK) return rc;
     P.smp_ss = n;
     P.smp_ps = 1u;
     HIP_TRY(c, span_begin(c));
@@ -707,7 +707,55 @@ int pt_render_camera(pt_ctx* c, const pt_camera* cam, const pt_camera_model* cm,
         P.chunk = plan_rays_launch(f, a, plan, P.spp, plan.L.work_blocks);
         HIP_TRY(c, queue_reset(P.queue, c->stream));
         HIP_TRY(c, launch_render_camera(plan.L, P, R, c->stream));
-        if (per_launch > 1) HIP_TRY(c, launch_fold_rays(c, P, fold));
+        if (plan.samples) HIP_TRY(c, launch_fold_rays(c, P, fold));
+    }
+    HIP_TRY(c, span_end(c));
+    return PT_OK;
+}
+
+// pt_render_camera's launches over the listed pixels (or the whole image), always through the sample buffer (plan.samples), each
+// followed by the fold into the full-frame accumulator, moments and counts: every pixel from its own count on
+int pt_render_pixels(pt_ctx* c, const pt_camera* cam, const pt_camera_model* cm, const uint32_t* pixels_dev, size_t n, float* accum_dev,
+                     float* moments_dev, uint32_t* counts_dev, const pt_params* p, uint32_t spp, int mode) {
+    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
+    const CtxFacts f = ctx_facts(c);
+    CallFacts a = {false, p, spp, cam && cm && accum_dev && counts_dev, false, moments_dev != nullptr, n, mode, true, cm, pixels_dev != nullptr, 0};
+    a.pixels = true;
+    Refusal r = check_path_call(f, a);
+    if (r.code != PT_OK || r.nothing) return fail(c, r);
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = refresh_tri_lights(c, f, p);
+    if (rc != PT_OK) return rc;
+    RaysPlan plan;
+    r = plan_rays(f, a, plan);
+    if (r.code != PT_OK) return fail(c, r);
+    KParams P;
+    fill_path_params(c, f, p, spp, P);
+    P.cam = *cam;
+    P.sc.stack_n = plan.L.lstk;
+    P.sc.top_base = plan.L.walk >= 2 ? P.sc.wide_root : 0;
+    P.sph_tab = plan.sph_tab;
+    queue_params(plan.q, c->d_queue.get(), P);
+    const ptmi::CameraCall R{cm, pixels_dev, 0, nullptr, n, mode == PT_RAYS_HDR};   // no rows of running means: the kernel never folds in line
+    const ptmi::PixelsCall fold{pixels_dev, accum_dev, moments_dev, counts_dev, n, (uint32_t)((uint64_t)cm->width * (uint64_t)cm->height), mode == PT_RAYS_HDR};
+    const uint32_t per_launch = plan.per_launch;
+    if ((rc = samples_reserve(c, nullptr, (size_t)per_launch * n * 3, P)) != PT_OK) return rc;
+    P.smp_ss = n;
+    P.smp_ps = 1u;
+    HIP_TRY(c, span_begin(c));
+    if (f.timing) {   // pt_get_stage_ms: the path launches as PT_STAGE_FRAME, the folds as PT_STAGE_FOLD
+        c->stage_used = 0;
+        if (stage_mark(c, PT_STAGE_NONE) != PT_OK) return PT_ERR_DEVICE;
+    }
+    for (uint32_t s0 = 0; s0 < spp; s0 += per_launch) {
+        P.spp = std::min(per_launch, spp - s0);
+        P.frame = p->frame + s0;   // (sample_index is not read: the counts carry N)
+        P.chunk = plan_rays_launch(f, a, plan, P.spp, plan.L.work_blocks);
+        HIP_TRY(c, queue_reset(P.queue, c->stream));
+        HIP_TRY(c, launch_render_camera(plan.L, P, R, c->stream));
+        if (stage_mark(c, PT_STAGE_FRAME) != PT_OK) return PT_ERR_DEVICE;
+        HIP_TRY(c, launch_fold_pixels(c, P, fold));
+        if (stage_mark(c, PT_STAGE_FOLD) != PT_OK) return PT_ERR_DEVICE;
     }
     HIP_TRY(c, span_end(c));
     return PT_OK;

@@ -11,7 +11,8 @@
 //               --denoise-out image.ppm|.png|.pfm  --denoise-variance  --variance-out file.pfm  --until-error E --max-frames M
 //               --pan-deg D --dolly S --spin-deg D --temporal-out image.ppm|.png|.pfm  --equirect
 //               --env file.pfm [--env-scale S] [--env-nearest] [--env-light]
-//               --camera pinhole|thinlens|ortho|fisheye|equirect [--aperture R --focus D --ortho-height S --fisheye-deg A] [--camera-loop]]
+//               --camera pinhole|thinlens|ortho|fisheye|equirect [--aperture R --focus D --ortho-height S --fisheye-deg A] [--camera-loop]
+//               --adaptive E --min-spp A --max-spp B [--pass-spp K] [--samples-out counts.pfm]]
 // --gpus N splits the framebuffer over N contexts, one per GPU (devices device, device+1, ... modulo the number
 // present, so N > 1 also runs on a one-GPU box): stripes of --tile rows (default 8) are dealt round-robin
 // (pt_params.part_*), every context holds the whole scene and renders only its stripes of every frame — the random
@@ -71,6 +72,13 @@
 // jittered.  Clamped mode when --out is a .png / .ppm, HDR when it is a .pfm, as --equirect; refused with --equirect and in the
 // combinations --equirect is refused in (there are no guide buffers for these cameras).  --equirect itself keeps its host-made
 // centre rays and its output.
+// --adaptive E samples adaptively (the loop of gpu_pathtracer_amd.AdaptiveSampler): one pass of --pass-spp K samples (default 4) over
+// every pixel through pt_render_pixels, then pt_select_pixels lists the pixels below --min-spp A, or whose relative standard error
+// of the mean luminance is above E, and below --max-spp B, and pt_render_pixels gives those K more samples, until the list is
+// empty.  A and B are multiples of K, K <= A <= B; --frames and --spp are not read.  Pass k renders frames k K .. k K + K - 1, so a
+// pixel that ends with c samples holds exactly what a plain run of c samples gives it.  It works with --camera MODEL (not with
+// --camera-loop); without --camera the model is the pinhole, pt_render's camera.  --out as for --camera: clamped for .png / .ppm,
+// HDR for .pfm.  --samples-out writes the samples per pixel as a PFM (grey).  Refused in the combinations --camera is refused in.
 // --env file.pfm lights the scene with a latitude-longitude radiance map (pt_upload_environment): a path that leaves the scene gathers
 // the map along its direction instead of --bk.  The map lies in the world frame front = (0, 0, -1), right = (1, 0, 0), up = (0, 1, 0)
 // — the frame of this app's camera, hence of the frames --equirect writes — and is looked up bilinearly (--env-nearest: the nearest
@@ -116,6 +124,9 @@ int main(int argc, char** argv) {
     std::string camera_name;   // --camera: empty = pt_render's own pinhole
     bool camera_loop = false;  // --camera-loop: pt_camera_rays + pt_render_rays per sample instead of pt_render_camera
     double aperture = 0.0, focus = 35.0, ortho_height = 30.0, fisheye_deg = 180.0;
+    double adaptive_error = -1.0;   // --adaptive: < 0 = off
+    long min_spp = -1, max_spp = -1, pass_spp = 4;
+    std::string samples_path;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&](const char* name) -> const char* {
@@ -152,6 +163,11 @@ int main(int argc, char** argv) {
         else if (a == "--focus") focus = std::atof(next("--focus"));
         else if (a == "--ortho-height") ortho_height = std::atof(next("--ortho-height"));
         else if (a == "--fisheye-deg") fisheye_deg = std::atof(next("--fisheye-deg"));
+        else if (a == "--adaptive") adaptive_error = std::atof(next("--adaptive"));
+        else if (a == "--min-spp") min_spp = std::atol(next("--min-spp"));
+        else if (a == "--max-spp") max_spp = std::atol(next("--max-spp"));
+        else if (a == "--pass-spp") pass_spp = std::atol(next("--pass-spp"));
+        else if (a == "--samples-out") samples_path = next("--samples-out");
         else if (a == "--env") env_path = next("--env");
         else if (a == "--env-scale") { env_scale = std::atof(next("--env-scale")); env_scale_set = true; }
         else if (a == "--env-nearest") env_nearest = true;
@@ -188,6 +204,19 @@ int main(int argc, char** argv) {
     // --camera: the model of pt_camera_rays; its own parameter is checked by the library at the first call
     const bool ray_camera = !camera_name.empty();
     pt_camera_model cmodel{};
+    // --adaptive: pt_render_pixels / pt_select_pixels over the model's image, the pinhole without --camera
+    const bool adaptive = adaptive_error >= 0.0;
+    if (!adaptive && (min_spp >= 0 || max_spp >= 0 || pass_spp != 4 || !samples_path.empty()))
+        return die("usage", "--min-spp, --max-spp, --pass-spp and --samples-out go with --adaptive E");
+    if (adaptive) {
+        if (!std::isfinite(adaptive_error)) return die("--adaptive", "the threshold must be finite and >= 0");
+        if (pass_spp < 1 || min_spp < pass_spp || max_spp < min_spp || min_spp % pass_spp || max_spp % pass_spp || max_spp > 0x7fffffffL)
+            return die("usage", "--adaptive needs --min-spp and --max-spp, multiples of --pass-spp with pass <= min <= max");
+        if (camera_loop || equirect) return die("usage", "--adaptive does not combine with --camera-loop or --equirect");
+        if (!denoise_path.empty() || temporal || with_moments || gpus > 1 || !ckpt_path.empty() || !resume_path.empty() || moving)
+            return die("usage", "--adaptive does not combine with --denoise-out, --temporal-out, --variance-out, --until-error, --gpus > 1, --checkpoint, --resume, --pan-deg, --dolly or --spin-deg");
+        cmodel.model = PT_CAM_PINHOLE; cmodel.width = W; cmodel.height = H;
+    }
     if (camera_loop && !ray_camera) return die("usage", "--camera-loop needs --camera MODEL");
     if (ray_camera) {
         const char* names[5] = {"pinhole", "thinlens", "ortho", "fisheye", "equirect"};   // PT_CAM_* in order
@@ -498,7 +527,38 @@ int main(int argc, char** argv) {
     std::vector<float> host_mom;
     double mean_rse = -1.0;   // pt_frame_error's figure after the last call, < 0: not computed (fewer than two samples)
     auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
+    if (adaptive) {   // gpu_pathtracer_amd.AdaptiveSampler.run
+        void *a_mom = nullptr, *a_cnt = nullptr, *a_pix = nullptr;
+        if (pt_malloc(ctx, n_pix_all * 8, &a_mom) != PT_OK || pt_malloc(ctx, n_pix_all * 4, &a_cnt) != PT_OK || pt_malloc(ctx, n_pix_all * 4, &a_pix) != PT_OK ||
+            pt_memset(ctx, a_cnt, 0, n_pix_all * 4) != PT_OK)
+            return die("pt_malloc", pt_last_error(ctx));
+        const pt_select_params sel = {W, H, (float)adaptive_error, (uint32_t)min_spp, (uint32_t)max_spp, 0};
+        const int mode = out_pfm ? PT_RAYS_HDR : PT_RAYS_CLAMPED;
+        uint64_t n_sel = n_pix_all, total = 0;
+        p.sample_index = 1;   // (not read: the counts carry N)
+        for (const uint32_t* list = nullptr;; list = (const uint32_t*)a_pix) {
+            p.frame = first_frame + (uint64_t)calls * (uint64_t)pass_spp;
+            if (pt_render_pixels(ctx, &cam, &cmodel, list, (size_t)n_sel, (float*)accum, (float*)a_mom, (uint32_t*)a_cnt, &p, (uint32_t)pass_spp, mode) != PT_OK)
+                return die("pt_render_pixels", pt_last_error(ctx));
+            total += n_sel * (uint64_t)pass_spp;
+            calls++;
+            if (pt_select_pixels(ctx, &sel, (const float*)a_mom, (const uint32_t*)a_cnt, (uint32_t*)a_pix, &n_sel, &mean_rse) != PT_OK)
+                return die("pt_select_pixels", pt_last_error(ctx));
+            if (n_sel == 0) break;
+        }
+        std::printf("adaptive %g: %d passes, %llu samples, %.3f per pixel (min %ld, max %ld), mean_rse %.6g\n", adaptive_error, calls,
+                    (unsigned long long)total, (double)total / (double)n_pix_all, min_spp, max_spp, mean_rse);
+        frameNumber = first_frame + (uint64_t)((total + n_pix_all - 1) / n_pix_all);   // for the summary line: the mean, rounded up
+        if (!samples_path.empty()) {
+            std::vector<uint32_t> cnt(n_pix_all);
+            if (pt_download(ctx, cnt.data(), a_cnt, n_pix_all * 4) != PT_OK) return die("pt_download", pt_last_error(ctx));
+            std::vector<float> img(n_pix_all * 3);
+            for (size_t i = 0; i < n_pix_all; i++) img[3 * i] = img[3 * i + 1] = img[3 * i + 2] = (float)cnt[i];
+            if (pth_write_pfm(samples_path.c_str(), img.data(), W, H) != 0) return die("write", pth_last_error());
+        }
+        for (void* b : {a_mom, a_cnt, a_pix}) pt_free(ctx, b);
+    }
+    for (; !adaptive;) {
         while (frameNumber < end_frame) {
             for (pt_ctx* cx : ctxs)
                 if (pt_sync(cx) != PT_OK) return die("pt_sync", pt_last_error(cx));     // :395
@@ -572,7 +632,7 @@ int main(int argc, char** argv) {
             rc = pth_write_pfm(out_path.c_str(), host_acc.data(), W, H);
         } else {
             std::vector<uint32_t> img((size_t)W * H);
-            if (frames == 0 || equirect || ray_camera) {  // nothing rendered in this run (e.g. --resume only to convert), or no display words (pt_render_rays): pack the accumulator here
+            if (frames == 0 || equirect || ray_camera || adaptive) {  // nothing rendered in this run (e.g. --resume only to convert), or no display words (pt_render_rays): pack the accumulator here
                 host_acc.resize((size_t)W * H * 3);
                 if (int grc = gather(accums, host_acc.data(), 12)) return grc;
                 for (size_t i = 0; i < img.size(); i++) {   // rgbToUint, cudaUtils.h:99-105

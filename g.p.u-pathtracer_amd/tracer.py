@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import Camera, Counters, DenoiseParams, DenoiseVarianceParams, Environment, Material, Params, Sphere, TemporalParams
+from ._abi import Camera, Counters, DenoiseParams, DenoiseVarianceParams, Environment, Material, Params, SelectParams, Sphere, TemporalParams
 
 # pt_denoise defaults (iterations, sigma_color, sigma_normal, sigma_position): chosen by the CPU sweep of DESIGN.md §10 f6;
 # host/pt_app.cpp uses the same values
@@ -254,6 +254,29 @@ class PathTracer:
         self._check(self._lib.pt_render_camera(self._ctx, C.byref(cam), C.byref(model), pixels_ptr, int(n), int(first_pixel), out_ptr,
                                                C.byref(params), int(spp), _abi.RAYS_HDR if hdr else _abi.RAYS_CLAMPED))
 
+    def render_pixels(self, cam, model, params, accum_ptr, counts_ptr, moments_ptr=None, spp=1, hdr=False, n=None, pixels_ptr=None):
+        """spp more samples of listed pixels folded into FULL-FRAME buffers, every pixel from its own sample count on
+        (pt_render_pixels): accum float[H*W][3], counts uint32[H*W], moments float[H*W][2] (optional), the image being the model's.
+        pixels_ptr: n pixel numbers (uint32 on the device; n is then required, a pixel listed once at most), or None: every pixel.
+        Sample s of a pixel is render_model's for that pixel in frame params.frame + s; the pixel's count gives N, so only the counts
+        need zeroing before the first pass and params.sample_index is not read.  Unlisted pixels keep their bits.  Asynchronous
+        until sync()."""
+        if n is None:
+            if pixels_ptr is not None:
+                raise ValueError("render_pixels: a pixel list needs n")
+            n = model.width * model.height
+        self._check(self._lib.pt_render_pixels(self._ctx, C.byref(cam), C.byref(model), pixels_ptr, int(n), accum_ptr, moments_ptr, counts_ptr,
+                                               C.byref(params), int(spp), _abi.RAYS_HDR if hdr else _abi.RAYS_CLAMPED))
+
+    def select_pixels(self, moments_ptr, counts_ptr, pixels_ptr, width, height, threshold, min_samples=0, max_samples=0xFFFFFFFF):
+        """(n, mean relative standard error): the n pixels that need more samples, as an ascending list in pixels uint32[H*W]
+        (pt_select_pixels) — those below max_samples that are below max(min_samples, 2) or whose relative standard error, from the
+        moments and the pixel's own count, exceeds `threshold`.  Synchronises."""
+        sp = SelectParams(int(width), int(height), float(threshold), int(min_samples), int(max_samples), 0)
+        n, mean = C.c_uint64(), C.c_double()
+        self._check(self._lib.pt_select_pixels(self._ctx, C.byref(sp), moments_ptr, counts_ptr, pixels_ptr, C.byref(n), C.byref(mean)))
+        return n.value, mean.value
+
     def upload_environment(self, texels, front=(0, 0, -1), right=(1, 0, 0), up=(0, 1, 0), scale=(1, 1, 1), filter=_abi.ENV_BILINEAR, light=False):
         """Light the paths that leave the scene with a latitude-longitude map (pt_upload_environment) instead of bk_color: texels
         float32 [H][W][3] on the host, in the layout `pt_app --equirect` writes for a camera with this front / right / up (the
@@ -493,6 +516,49 @@ class TemporalHistory:
             b.free()
         self.color, self.length, self.guides, self.cam = [], [], [], None
         self.moment, self.moments = [], None
+
+
+class AdaptiveSampler:
+    """The buffers and the loop of adaptive sampling for one image of a camera model: accumulator, luminance moments, sample counts
+    and the pixel list.  run() renders one pass over every pixel, then select_pixels -> render_pixels over the list until nothing
+    is selected: every pixel gets samples until its relative standard error is at most `threshold` (never fewer than min_spp, never
+    more than max_spp, pass_spp per pass)."""
+
+    def __init__(self, tracer, model, threshold, min_spp, max_spp, pass_spp):
+        min_spp, max_spp, pass_spp = int(min_spp), int(max_spp), int(pass_spp)
+        if pass_spp < 1 or min_spp < pass_spp or max_spp < min_spp or min_spp % pass_spp or max_spp % pass_spp:
+            raise ValueError("AdaptiveSampler: min_spp and max_spp must be multiples of pass_spp with pass_spp <= min_spp <= max_spp")
+        self.t, self.model, self.W, self.H = tracer, model, model.width, model.height
+        self.threshold, self.min_spp, self.max_spp, self.pass_spp = float(threshold), min_spp, max_spp, pass_spp
+        n = self.W * self.H
+        self.accum, self.moments, self.counts, self.pixels = tracer.malloc(n * 12), tracer.malloc(n * 8), tracer.malloc(n * 4), tracer.malloc(n * 4)
+        self.passes = []    # of the last run: (pixels rendered, mean relative standard error before the pass; None for the first)
+
+    def run(self, cam, params, hdr=False):
+        """The whole loop for `cam` from frame params.frame on; pass k renders frames params.frame + k * pass_spp ..: a pixel that
+        ends with count c holds exactly the frames params.frame .. + c - 1, i.e. launch_kernel(spp=c)'s accumulator and moments for
+        a pinhole model.  Returns (samples rendered in all, mean relative standard error at the end); accum, moments and counts hold
+        the result.  Synchronises once per pass."""
+        t, n = self.t, self.W * self.H
+        self.counts.zero()
+        q = Params.from_buffer_copy(params)
+        q.sample_index = 1
+        t.render_pixels(cam, self.model, q, self.accum.ptr, self.counts.ptr, self.moments.ptr, spp=self.pass_spp, hdr=hdr)
+        self.passes = [(n, None)]
+        k = 1
+        while True:
+            m, mean = t.select_pixels(self.moments.ptr, self.counts.ptr, self.pixels.ptr, self.W, self.H, self.threshold, self.min_spp, self.max_spp)
+            if m == 0:
+                return sum(c for c, _ in self.passes) * self.pass_spp, mean
+            q.frame = params.frame + k * self.pass_spp
+            t.render_pixels(cam, self.model, q, self.accum.ptr, self.counts.ptr, self.moments.ptr, spp=self.pass_spp, hdr=hdr, n=m, pixels_ptr=self.pixels.ptr)
+            self.passes.append((m, mean))
+            k += 1
+
+    def free(self):
+        for b in (self.accum, self.moments, self.counts, self.pixels):
+            b.free()
+        self.accum = self.moments = self.counts = self.pixels = None
 
 
 def algorithmic_bytes(counters, n_spheres):

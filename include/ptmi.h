@@ -663,10 +663,86 @@ int pt_camera_rays(pt_ctx* ctx, const pt_camera* cam, const pt_camera_model* cm,
  * PT_OPT_BATCH, PT_OPT_REFILL and PT_OPT_SPHERE_LDS apply: speed, never results.  PT_OPT_KERNEL, the counters and PT_KERNEL_AUTO's
  * table are neither read nor changed.  The kernel is pt_render_rays' loop with another path start (csrc/pt_rays_loop.h); the model
  * is a value of the launch, not an instantiation.
- * Left out: luminance moments; display words; guide buffers for these cameras; the stage-split pipeline. */
+ * Left out: luminance moments in this call (pt_render_pixels below keeps them, for these cameras too); display words; guide buffers
+ * for these cameras; the stage-split pipeline. */
 int pt_render_camera(pt_ctx* ctx, const pt_camera* cam, const pt_camera_model* cm,
                      const uint32_t* pixels_dev /* may be NULL */, size_t n, uint64_t first_pixel,
                      float* radiance_dev /* float[n][3] */, const pt_params* params, uint32_t spp, int mode);
+
+/* ---- adaptive sampling: more samples only where the image is noisy — an EXTENSION --------------------------
+ * Two calls and a loop the host writes: pt_render_pixels renders listed pixels into full-frame buffers, each pixel from its own
+ * sample count on, and keeps the luminance moments; pt_select_pixels makes the list of the pixels whose error figure is still above
+ * a threshold, on the device.  zero the counts; pt_render_pixels over every pixel; then pt_select_pixels, pt_render_pixels over the
+ * list, until nothing is selected.  binary32, plain * and +, as stated for pt_render_moments and pt_frame_error.
+ *
+ * pt_render_pixels is pt_render_camera folded into full-frame buffers with a sample count per pixel.  The image is cm's,
+ * W x H = cm->width x cm->height.  accum_dev: float[H*W][3]; moments_dev: float[H*W][2] = (m1, m2), 8-byte aligned, may be NULL;
+ * counts_dev: uint32[H*W], the samples each pixel holds; pixels_dev: n pixel numbers on the device, or NULL: every pixel, row i is
+ * pixel i and n must be W * H.
+ * Samples: sample s = 0 .. spp-1 of listed pixel pix is exactly the sample pt_render_camera makes for pix in frame
+ * params->frame + s — the same ray and the same random stream, which is the pixel's and not the row's.  The path kernel is
+ * pt_render_camera's, with the caller's list; a call of more than 2^26 slots goes out as several launches, each followed by its fold.
+ * Fold: row i is pixel pix = pixels_dev ? pixels_dev[i] : i.  A pix >= W * H is skipped: nothing is written anywhere for it.
+ * Otherwise, with c = counts[pix] and, for every sample s of the call in order, N = c + 1 + s and col the sample colour:
+ *     accum[pix]   = pt_render_rays' running mean under the mode: (a * (float)(N - 1) + col) * (1.0f / (float)N), clamped to 0..1
+ *                    per step under PT_RAYS_CLAMPED, not under PT_RAYS_HDR; N == 1 overwrites
+ *     moments[pix] = pt_render_moments' formula with this N: L from col before the clamp, N == 1 overwrites, no fused multiply-add
+ * and then counts[pix] = c + spp.  N == 1 overwrites, so only counts_dev needs zeroing before the first pass.
+ * params->sample_index must be >= 1, as for every path call, and is otherwise not read: the counts carry N.
+ * A pixel listed twice in one call is the caller's error: it is not checked and the result for that pixel is unspecified.  A count
+ * that would pass 2^32 - 1 is the caller's error too.
+ * Guarantees (tests/test_gpu_adaptive.py):
+ *   (a) with pixels_dev == NULL, n == W * H and all counts equal to k, accum equals pt_render_camera's full-frame result with
+ *       sample_index = k + 1 bit for bit, for all five models and both modes; hence with PT_CAM_PINHOLE and PT_RAYS_CLAMPED it is
+ *       pt_render's accumulator, and in that case moments equals pt_render_moments';
+ *   (b) with a list, a listed pixel gets what (a) gives it for its own count, and every unlisted pixel keeps its bits in all three
+ *       buffers;
+ *   (c) any split of spp over calls, frame advanced alike, gives the same bits: the counts carry N;
+ *   (d) so a host loop whose pass k renders frames params->frame + k * pass_spp .. + pass_spp - 1 and whose selection only ever
+ *       drops pixels leaves every pixel with count c the accumulator and moments of pt_render_moments(spp = c) at params->frame.
+ * Errors: pt_render_camera's, in its order, prefixed pt_render_pixels: — NULL ctx; no scene; n == 0 or spp == 0 PT_OK, nothing
+ * written; a NULL cam, cm, accum_dev, counts_dev or params; the mode; the model, its flags, the image, n >= 2^32; without a list an
+ * n other than W * H PT_ERR_INVALID; the model's parameter; sample_index == 0, a bad tri_mat, the PT_FLAG_NEE / PT_FLAG_MIS
+ * combinations, the refusals over Woop records.
+ * Asynchronous on the context's stream.  Scratch is the shared sample buffer, [min(spp, 2^26 / n)][n][3] floats and always used,
+ * also at spp == 1: the moments and the counts are the fold's job, as for pt_render_moments.  With PT_OPT_TIMING=1,
+ * pt_last_kernel_ms covers the call and pt_get_stage_ms splits it into the path launches (PT_STAGE_FRAME) and the folds (PT_STAGE_FOLD).
+ * Options as for pt_render_camera.
+ * Left out: display words; a sample count read on the device for the path launch (the host passes n). */
+int pt_render_pixels(pt_ctx* ctx, const pt_camera* cam, const pt_camera_model* cm,
+                     const uint32_t* pixels_dev /* may be NULL: every pixel */, size_t n,
+                     float* accum_dev /* float[H*W][3] */, float* moments_dev /* float[H*W][2]; may be NULL */,
+                     uint32_t* counts_dev /* uint32[H*W] */, const pt_params* params, uint32_t spp, int mode);
+
+/* pt_select_pixels: the pixels that need more samples, as an ascending list made on the device.  Per pixel, in binary32, with
+ * n = counts[pix] and (m1, m2) = moments[pix]:
+ *     n >= 2:  var = fmaxf(0, m2 - m1 * m1),   rse = sqrtf(var / (float)(n - 1)) / (m1 + 0.01f)      pt_frame_error's, with the pixel's own n
+ *     n <  2:  rse = 0
+ *     an rse that is not finite counts as 0 and is never selected (a NaN pixel would be rendered again for ever)
+ *     selected  <=>  n < max_samples  and  (n < max(min_samples, 2)  or  rse > threshold)               (strictly above)
+ * pixels_dev[0 .. *n_selected) receives the selected pixel numbers in ASCENDING order — neighbouring pixels land in neighbouring
+ * lanes of the path kernel, and the list is the same run after run; nothing is written beyond entry *n_selected - 1.  pixels_dev:
+ * uint32[W*H].  *mean_rse (may be NULL) = the sum of rse over all pixels / (W * H), summed in double over pt_frame_error's 256-pixel
+ * blocks with its reduction tree, the blocks added on the host in order: for uniform counts n it equals pt_frame_error(.., n, ..)'s
+ * figure exactly, and with min_samples = 0 and max_samples = UINT32_MAX *n_selected equals its n_above.
+ * Three launches over 256-pixel blocks (count, one block's exclusive scan of the counts, write at the rank): no block waits for
+ * another and nothing is added atomically.  The call then copies the blocks' sums and counts back and SYNCHRONISES the context's
+ * stream, like pt_frame_error: one synchronisation per adaptive pass.  Scratch, 16 bytes per block, belongs to the context: grown
+ * on demand, freed by pt_destroy.  No scene needed.
+ * Errors, in this order, PT_ERR_INVALID each: NULL ctx; a NULL sp, moments_dev, counts_dev, pixels_dev or n_selected; width or
+ * height < 1, or W * H >= 2^32; a threshold that is not finite or is negative; min_samples > max_samples.
+ * Note: selecting by the variance of the same samples that form the mean is biased — a pixel that looks converged by chance stops
+ * early, and dark pixels are under-sampled.  min_samples is the guard.
+ * Left out: the unbiased scheme with two sample buffers (one to decide, one to show); a sample count for the path launch that
+ * stays on the device. */
+typedef struct pt_select_params {
+    int32_t width, height;
+    float threshold;                    /* finite, >= 0 */
+    uint32_t min_samples, max_samples;  /* min <= max */
+    int32_t _pad;
+} pt_select_params;                     /* 24 bytes */
+int pt_select_pixels(pt_ctx* ctx, const pt_select_params* sp, const float* moments_dev, const uint32_t* counts_dev,
+                     uint32_t* pixels_dev /* uint32[W*H] */, uint64_t* n_selected, double* mean_rse /* may be NULL */);
 
 /* ---- environment map — an EXTENSION -----------------------------------------
  * pt_upload_environment gives the context a latitude-longitude (equirectangular) radiance map: what a path segment that hits
