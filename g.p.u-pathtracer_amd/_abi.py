@@ -72,6 +72,18 @@ class SelectParams(C.Structure):
                 ("min_samples", C.c_uint32), ("max_samples", C.c_uint32), ("_pad", C.c_int32)]
 
 
+class TonemapParams(C.Structure):
+    """pt_tonemap_params — curve, transfer and exposure of pt_tonemap (extension, include/ptmi.h; 24 bytes)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("curve", C.c_int32), ("transfer", C.c_int32),
+                ("exposure", C.c_float), ("white", C.c_float)]
+
+
+class MeterParams(C.Structure):
+    """pt_meter_params — the rule of pt_meter (extension, include/ptmi.h; 32 bytes)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("key", C.c_float), ("low_pct", C.c_float), ("high_pct", C.c_float),
+                ("min_exposure", C.c_float), ("max_exposure", C.c_float), ("adapt", C.c_float)]
+
+
 class CheckpointInfo(C.Structure):
     """pth_checkpoint_info (host/pthost.h)."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("next_frame", C.c_uint64),
@@ -120,6 +132,8 @@ RAYS_CLAMPED, RAYS_HDR = 0, 1
 ENV_NEAREST, ENV_BILINEAR = 0, 1
 CAM_PINHOLE, CAM_THIN_LENS, CAM_ORTHO, CAM_FISHEYE, CAM_EQUIRECT = 0, 1, 2, 3, 4
 CAMF_CENTRE = 1
+TONE_CLAMP, TONE_REINHARD, TONE_ACES = 0, 1, 2
+XFER_LINEAR, XFER_SRGB, XFER_GAMMA22 = 0, 1, 2
 CAM_LENS_KEY = 0xC3A5C85C97CB3127   # PT_CAM_LENS_KEY: frame ^ this keys the thin lens' stream
 KERNEL_AUTO, KERNEL_MEGA_BVH2, KERNEL_PERSISTENT, KERNEL_WAVEFRONT = 0, 1, 3, 5
 OPT_KERNEL, OPT_COUNTERS, OPT_TIMING, OPT_BATCH, OPT_TOP_NODES, OPT_OCCUPANCY, OPT_LDS_STACK, OPT_WALK, OPT_LEAF_MAX, OPT_TRI_TEST, OPT_REFILL, OPT_VOTE_NODE, OPT_VOTE_REC, OPT_WAVE_BATCH, OPT_SPHERE_LDS, OPT_BUILD_ALGO, OPT_REBUILD, OPT_PRESPLIT, OPT_WAVE_BLOCKS, OPT_OVERLAP, OPT_OPTIMIZE, OPT_WAVE_SAMPLES = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 21, 24, 25
@@ -160,6 +174,9 @@ PTMI_SYMBOLS = [
     ("pt_render_camera", _i, [_vp, C.POINTER(Camera), C.POINTER(CameraModel), _vp, _sz, C.c_uint64, _vp, C.POINTER(Params), _u32, _i]),
     ("pt_render_pixels", _i, [_vp, C.POINTER(Camera), C.POINTER(CameraModel), _vp, _sz, _vp, _vp, _vp, C.POINTER(Params), _u32, _i]),
     ("pt_select_pixels", _i, [_vp, C.POINTER(SelectParams), _vp, _vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    ("pt_tonemap", _i, [_vp, C.POINTER(TonemapParams), _vp, _vp, _vp, _vp]),
+    ("pt_meter", _i, [_vp, C.POINTER(MeterParams), _vp, _vp, _i]),
+    ("pt_tonemap_thresholds", _i, [_i, _vp]),
     ("pt_upload_environment", _i, [_vp, C.POINTER(Environment), _vp]),
     ("pt_eval_environment", _i, [_vp, _vp, _sz, _vp]),
     ("pt_environment_is_light", _i, [_vp, C.POINTER(_i)]),

@@ -223,6 +223,10 @@ struct pt_ctx {
     DevBuf<char> d_frame_err;
     // pt_select_pixels' per-block scratch (pt_denoise.hip): [blocks] double sums, [blocks] uint32 counts, [blocks] uint32 list offsets; grow-only
     DevBuf<char> d_select;
+    // pt_meter's partial histograms (pt_denoise.hip): [METER_BLOCKS][METER_BINS + 1] uint32, reserved whole by the first call
+    DevBuf<uint32_t> d_meter;
+    // pt_tonemap's threshold tables (pt_denoise.hip): [2][256] floats, PT_XFER_SRGB then PT_XFER_GAMMA22, uploaded by the first call that needs one
+    DevBuf<float> d_tone;
     Event ev0, ev1;
     bool timed = false;
     // PT_OPT_TIMING: events between the stages of the last call (pt_get_stage_ms); stage_kind[i] is the

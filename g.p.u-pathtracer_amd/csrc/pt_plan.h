@@ -430,6 +430,53 @@ inline SelectPlan plan_select(uint64_t n_pix) {
     return s;
 }
 
+// ---- pt_tonemap / pt_meter: their argument rules in the header's order (buffers: every required pointer but the parameters is given —
+// tonemap: color_dev and one of out_dev, rgba_dev; meter: color_dev and state_dev); n_pix: width * height of a call that passes
+inline Refusal check_tonemap_call(const pt_tonemap_params* tp, bool buffers, uint64_t& n_pix) {
+    n_pix = 0;
+    if (!tp || !buffers) return {PT_ERR_INVALID, "pt_tonemap: null argument"};
+    n_pix = (uint64_t)(tp->width > 0 ? tp->width : 0) * (uint64_t)(tp->height > 0 ? tp->height : 0);
+    if (tp->width < 1 || tp->height < 1 || n_pix >= (1ull << 32)) return {PT_ERR_INVALID, "pt_tonemap: width and height must be >= 1 with width * height < 2^32"};
+    if (tp->curve < PT_TONE_CLAMP || tp->curve > PT_TONE_ACES || tp->transfer < PT_XFER_LINEAR || tp->transfer > PT_XFER_GAMMA22)
+        return {PT_ERR_INVALID, "pt_tonemap: unknown curve or transfer"};
+    if (!plan_finite(tp->exposure) || !(tp->exposure > 0.0f)) return {PT_ERR_INVALID, "pt_tonemap: exposure must be finite and > 0"};
+    if (tp->curve == PT_TONE_REINHARD && !(tp->white > 0.0f)) return {PT_ERR_INVALID, "pt_tonemap: white must be > 0 (+inf: plain Reinhard)"};
+    return {};
+}
+inline Refusal check_meter_call(const pt_meter_params* mp, bool buffers, uint64_t& n_pix) {
+    n_pix = 0;
+    if (!mp || !buffers) return {PT_ERR_INVALID, "pt_meter: null argument"};
+    n_pix = (uint64_t)(mp->width > 0 ? mp->width : 0) * (uint64_t)(mp->height > 0 ? mp->height : 0);
+    if (mp->width < 1 || mp->height < 1 || n_pix >= (1ull << 32)) return {PT_ERR_INVALID, "pt_meter: width and height must be >= 1 with width * height < 2^32"};
+    if (!plan_finite(mp->key) || !(mp->key > 0.0f)) return {PT_ERR_INVALID, "pt_meter: key must be finite and > 0"};
+    if (!(mp->low_pct >= 0.0f && mp->low_pct < mp->high_pct && mp->high_pct <= 1.0f)) return {PT_ERR_INVALID, "pt_meter: the percentages must hold 0 <= low_pct < high_pct <= 1"};
+    if (!plan_finite(mp->min_exposure) || !plan_finite(mp->max_exposure) || !(mp->min_exposure > 0.0f) || !(mp->min_exposure <= mp->max_exposure))
+        return {PT_ERR_INVALID, "pt_meter: the exposure limits must be finite with 0 < min_exposure <= max_exposure"};
+    if (!(mp->adapt >= 0.0f && mp->adapt <= 1.0f)) return {PT_ERR_INVALID, "pt_meter: adapt must be in 0..1"};
+    return {};
+}
+// their launches.  Tone map: four pixels per thread (three 16-byte loads, one 16-byte store of words) where the pixels come in fours
+// and every buffer given is 16-byte aligned (`aligned16`), else one pixel per thread; 256-thread blocks.  Meter: the histogram pass'
+// fixed grid of at most METER_BLOCKS blocks, whose threads stride, and the scratch [blocks][METER_BINS + 1] of uint32 counts (the last
+// one: the unmetered pixels), reserved at its largest once
+constexpr uint32_t METER_BINS = 256, METER_BLOCKS = 256;
+constexpr size_t METER_SCRATCH_WORDS = (size_t)METER_BLOCKS * (METER_BINS + 1);
+struct DisplayPlan { bool vec; uint64_t items; uint32_t n_blocks; };   // items: pixels, or groups of four (vec)
+inline DisplayPlan plan_tonemap(uint64_t n_pix, bool aligned16) {
+    DisplayPlan d;
+    d.vec = aligned16 && n_pix % 4 == 0;
+    d.items = d.vec ? n_pix / 4 : n_pix;
+    d.n_blocks = (uint32_t)((d.items + 255) / 256);
+    return d;
+}
+inline DisplayPlan plan_meter(uint64_t n_pix, bool aligned16) {
+    DisplayPlan d;
+    d.vec = aligned16 && n_pix % 4 == 0;
+    d.items = d.vec ? n_pix / 4 : n_pix;
+    d.n_blocks = (uint32_t)std::min<uint64_t>((n_pix + 255) / 256, METER_BLOCKS);
+    return d;
+}
+
 // ---- pt_closest_hits / pt_any_hits: the wide walk on a resident grid over regions of PT_REGION rays at one of the extend stage's two
 // budgets ((8 waves per SIMD, 16 stack entries in LDS), or (6, 24) under PT_OPT_LDS_STACK 24), or pt_trace_rays' binary launch with the
 // bound applied to its answer when the tree is too deep for the wide one

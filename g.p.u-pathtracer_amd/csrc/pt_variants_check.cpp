@@ -1,6 +1,6 @@
 // pt_variants_check.cpp — every request has a kernel and every kernel a request, and every plan is sound: a CPU program with its own
 // main, no HIP library (`make variants_check`, SAN=1 for the address and undefined-behaviour sanitizers; tests/test_variants.py runs both).
-// It RUNS the planner (pt_plan.h: the functions pt_render, pt_render_rays, pt_render_camera, pt_render_pixels, pt_select_pixels and the ray-batch queries call) over a domain of scenes x
+// It RUNS the planner (pt_plan.h: the functions pt_render, pt_render_rays, pt_render_camera, pt_render_pixels, pt_select_pixels, pt_tonemap, pt_meter and the ray-batch queries call) over a domain of scenes x
 // options x calls x the runtime's answers, and holds no rule of its own: a call is skipped because the planner refused it, and the
 // refusal's code has to be the one REFUSALS lists for its text.  Of every plan it asserts what follows from the project's constants
 // (LDS, refill <= batch, grids, the record layout); of every variant word a plan asks a launcher for, that the word is instantiated —
@@ -68,6 +68,10 @@ static struct { const char* text; int code; long seen; } REFUSALS[] = {
     // pt_render_pixels' own, and pt_select_pixels' (its null argument is the row above)
     {"without a pixel list n must equal", PT_ERR_INVALID, 0}, {"width and height must be >= 1", PT_ERR_INVALID, 0},
     {"threshold must be finite", PT_ERR_INVALID, 0}, {"min_samples must not exceed", PT_ERR_INVALID, 0},
+    // pt_tonemap's and pt_meter's (their null argument and image rows are above)
+    {"unknown curve or transfer", PT_ERR_INVALID, 0}, {"exposure must be finite and > 0", PT_ERR_INVALID, 0}, {"white must be > 0", PT_ERR_INVALID, 0},
+    {"key must be finite and > 0", PT_ERR_INVALID, 0}, {"0 <= low_pct < high_pct <= 1", PT_ERR_INVALID, 0},
+    {"0 < min_exposure <= max_exposure", PT_ERR_INVALID, 0}, {"adapt must be in 0..1", PT_ERR_INVALID, 0},
 };
 static long n_refused = 0, n_planned = 0;
 // true: the planner refused the call or found nothing to do in it
@@ -563,6 +567,80 @@ int main() {
         for (float bad : {-1.0f, inf, -inf, nan}) { sp.threshold = bad; CHECK(says(check_select_call(&sp, true, n_pix), "threshold must be finite")); }
         sp.threshold = 0.0f;
         CHECK(check_select_call(&sp, true, n_pix).code == PT_OK && n_pix == 65536 && plan_select(1).n_blocks == 1 && plan_select(257).n_blocks == 2);
+    }
+
+    // (g4) pt_tonemap and pt_meter: every rule broken alone and together (the first in the header's order answers), and the launches of calls that pass
+    {
+        const float inf = 1.0f / 0.0f * (float)(KERNELS[1] != 0), nan = inf - inf;
+        auto says = [](const Refusal& r, const char* text) { return r.code != PT_OK && r.msg.find(text) != std::string::npos; };
+        for (int broken = 0; broken < 64; broken++) {
+            pt_tonemap_params tp = {};
+            tp.width = 1920; tp.height = broken & 2 ? 0 : 1080; tp.curve = broken & 4 ? 3 : PT_TONE_REINHARD; tp.transfer = PT_XFER_SRGB;
+            tp.exposure = broken & 8 ? 0.0f : 1.5f; tp.white = broken & 16 ? -1.0f : 4.0f;
+            uint64_t n_pix = 0;
+            const Refusal r = check_tonemap_call(broken & 32 ? nullptr : &tp, !(broken & 1), n_pix);
+            CHECK((r.code == PT_OK) == !broken);
+            if (broken) CHECK(turned_away(r));
+            CHECK(says(r, broken & 33 ? "pt_tonemap: null argument" : broken & 2 ? "width and height must be >= 1" : broken & 4 ? "unknown curve or transfer"
+                          : broken & 8 ? "exposure must be finite and > 0" : "white must be > 0") == (broken != 0));
+            if (!broken) {
+                n_planned++;
+                const DisplayPlan v = plan_tonemap(n_pix, true), s = plan_tonemap(n_pix, false);
+                CHECK(n_pix == 1920ull * 1080 && v.vec && v.items == n_pix / 4 && v.n_blocks == 2025 && !s.vec && s.items == n_pix && s.n_blocks == 8100);
+            }
+        }
+        for (int broken = 0; broken < 128; broken++) {
+            pt_meter_params mp = {};
+            mp.width = broken & 2 ? -1 : 1920; mp.height = 1080; mp.key = broken & 4 ? 0.0f : 0.18f;
+            mp.low_pct = 0.1f; mp.high_pct = broken & 8 ? 0.1f : 0.9f;
+            mp.min_exposure = broken & 16 ? 4.0f : 0.25f; mp.max_exposure = 2.0f; mp.adapt = broken & 32 ? 1.5f : 0.25f;
+            uint64_t n_pix = 0;
+            const Refusal r = check_meter_call(broken & 64 ? nullptr : &mp, !(broken & 1), n_pix);
+            CHECK((r.code == PT_OK) == !broken);
+            if (broken) CHECK(turned_away(r));
+            CHECK(says(r, broken & 65 ? "pt_meter: null argument" : broken & 2 ? "width and height must be >= 1" : broken & 4 ? "key must be finite and > 0"
+                          : broken & 8 ? "0 <= low_pct < high_pct <= 1" : broken & 16 ? "0 < min_exposure <= max_exposure" : "adapt must be in 0..1") == (broken != 0));
+            if (!broken) {
+                n_planned++;
+                const DisplayPlan v = plan_meter(n_pix, true), s = plan_meter(n_pix, false);
+                CHECK(v.vec && v.items == n_pix / 4 && v.n_blocks == METER_BLOCKS && !s.vec && s.items == n_pix && s.n_blocks == METER_BLOCKS);
+            }
+        }
+        // the values each rule turns away, and the ones at its edge that pass
+        pt_tonemap_params tp = {};
+        tp.width = tp.height = 65536; tp.curve = PT_TONE_CLAMP; tp.transfer = PT_XFER_LINEAR; tp.exposure = 1.0f; tp.white = nan;   // (white: not read under CLAMP)
+        uint64_t n_pix = 0;
+        CHECK(says(check_tonemap_call(&tp, true, n_pix), "width and height must be >= 1"));   // 2^32 pixels
+        tp.height = 65535;
+        CHECK(check_tonemap_call(&tp, true, n_pix).code == PT_OK && plan_tonemap(n_pix, true).n_blocks == (1u << 22) - 64 && plan_tonemap(n_pix, false).n_blocks == (1u << 24) - 256);
+        tp.width = 37; tp.height = 23;
+        CHECK(check_tonemap_call(&tp, true, n_pix).code == PT_OK && !plan_tonemap(n_pix, true).vec && plan_tonemap(n_pix, true).n_blocks == 4);
+        for (int bad : {-1, 3}) {
+            tp.curve = bad; CHECK(says(check_tonemap_call(&tp, true, n_pix), "unknown curve or transfer"));
+            tp.curve = PT_TONE_ACES; tp.transfer = bad; CHECK(says(check_tonemap_call(&tp, true, n_pix), "unknown curve or transfer"));
+            tp.transfer = PT_XFER_GAMMA22;
+        }
+        for (float bad : {0.0f, -1.0f, inf, -inf, nan}) { tp.exposure = bad; CHECK(says(check_tonemap_call(&tp, true, n_pix), "exposure must be finite and > 0")); }
+        tp.exposure = 1e-30f; tp.curve = PT_TONE_REINHARD;
+        for (float bad : {0.0f, -2.0f, -inf, nan}) { tp.white = bad; CHECK(says(check_tonemap_call(&tp, true, n_pix), "white must be > 0")); }
+        tp.white = inf;
+        CHECK(check_tonemap_call(&tp, true, n_pix).code == PT_OK && n_pix == 37 * 23);
+        pt_meter_params mp = {};
+        mp.width = 1; mp.height = 1; mp.key = 0.18f; mp.low_pct = 0.0f; mp.high_pct = 1.0f; mp.min_exposure = mp.max_exposure = 1.0f; mp.adapt = 0.0f;
+        CHECK(check_meter_call(&mp, true, n_pix).code == PT_OK && n_pix == 1 && plan_meter(1, true).n_blocks == 1 && !plan_meter(1, true).vec);
+        CHECK(plan_meter(257, false).n_blocks == 2 && plan_meter(65536, true).n_blocks == 256 && plan_meter(66000, false).n_blocks == 256 && plan_meter((1ull << 32) - 1, true).n_blocks == 256);
+        CHECK(METER_SCRATCH_WORDS * 4 == 263168);
+        for (float bad : {0.0f, -1.0f, inf, nan}) { mp.key = bad; CHECK(says(check_meter_call(&mp, true, n_pix), "key must be finite and > 0")); }
+        mp.key = 0.18f;
+        for (float bad : {-0.1f, 1.0f, nan}) { mp.low_pct = bad; CHECK(says(check_meter_call(&mp, true, n_pix), "0 <= low_pct < high_pct <= 1")); }
+        mp.low_pct = 0.0f;
+        for (float bad : {0.0f, 1.5f, nan}) { mp.high_pct = bad; CHECK(says(check_meter_call(&mp, true, n_pix), "0 <= low_pct < high_pct <= 1")); }
+        mp.high_pct = 1.0f;
+        for (float bad : {0.0f, -1.0f, 2.0f, inf, nan}) { mp.min_exposure = bad; CHECK(says(check_meter_call(&mp, true, n_pix), "0 < min_exposure <= max_exposure")); }
+        mp.min_exposure = 1.0f;
+        for (float bad : {0.5f, inf, nan}) { mp.max_exposure = bad; CHECK(says(check_meter_call(&mp, true, n_pix), "0 < min_exposure <= max_exposure")); }
+        mp.max_exposure = 1.0f;
+        for (float bad : {-0.5f, 1.5f, nan}) { mp.adapt = bad; CHECK(says(check_meter_call(&mp, true, n_pix), "adapt must be in 0..1")); }
     }
 
     // (h) pt_closest_hits / pt_any_hits: the wide walk's two budgets, the binary walk for a tree too deep

@@ -12,7 +12,8 @@
 //               --pan-deg D --dolly S --spin-deg D --temporal-out image.ppm|.png|.pfm  --equirect
 //               --env file.pfm [--env-scale S] [--env-nearest] [--env-light]
 //               --camera pinhole|thinlens|ortho|fisheye|equirect [--aperture R --focus D --ortho-height S --fisheye-deg A] [--camera-loop]
-//               --adaptive E --min-spp A --max-spp B [--pass-spp K] [--samples-out counts.pfm]]
+//               --adaptive E --min-spp A --max-spp B [--pass-spp K] [--samples-out counts.pfm]
+//               --tonemap clamp|reinhard|aces --transfer linear|srgb|gamma22 --exposure E|auto --white W]
 // --gpus N splits the framebuffer over N contexts, one per GPU (devices device, device+1, ... modulo the number
 // present, so N > 1 also runs on a one-GPU box): stripes of --tile rows (default 8) are dealt round-robin
 // (pt_params.part_*), every context holds the whole scene and renders only its stripes of every frame — the random
@@ -25,6 +26,12 @@
 // A mesh that carries materials (OBJ usemtl + .mtl, PTMESH2) is shaded with them
 // (pt_upload_tri_materials) unless --no-materials.  --resume continues a checkpointed
 // progressive render: the result is bit-identical to one uninterrupted run.
+// --tonemap clamp|reinhard|aces, --transfer linear|srgb|gamma22, --exposure E|auto and --white W (reinhard: the scaled luminance shown
+// as white) switch the display stage on: with any of them the .png / .ppm of --out, --denoise-out and --temporal-out are pt_tonemap's
+// display words of the device buffer (the accumulator, the filtered frame, the history) — under --exposure auto after pt_meter, so the
+// exposure never reaches the host — on every route, --camera, --equirect and --adaptive included; those three then accumulate as they
+// do for a .pfm (PT_RAYS_HDR: the curve clamps, not the running mean).  Defaults: clamp, linear, 1.  A .pfm stays the linear floats.
+// Without these flags every output byte is what it was.
 // --denoise-out also writes the final accumulator through pt_denoise (guides from pt_render_aux, the library's default
 // filter settings), format by extension as --out; with --gpus N the gathered frame is denoised on the first context.
 // --denoise-variance makes --denoise-out run pt_denoise_variance instead: the run renders through pt_render_moments (as
@@ -127,6 +134,9 @@ int main(int argc, char** argv) {
     double adaptive_error = -1.0;   // --adaptive: < 0 = off
     long min_spp = -1, max_spp = -1, pass_spp = 4;
     std::string samples_path;
+    std::string tone_name, xfer_name, exposure_arg;   // --tonemap / --transfer / --exposure: any of them (or --white) sends the .png / .ppm outputs through pt_tonemap
+    double white = INFINITY;
+    bool white_set = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&](const char* name) -> const char* {
@@ -168,6 +178,10 @@ int main(int argc, char** argv) {
         else if (a == "--max-spp") max_spp = std::atol(next("--max-spp"));
         else if (a == "--pass-spp") pass_spp = std::atol(next("--pass-spp"));
         else if (a == "--samples-out") samples_path = next("--samples-out");
+        else if (a == "--tonemap") tone_name = next("--tonemap");
+        else if (a == "--transfer") xfer_name = next("--transfer");
+        else if (a == "--exposure") exposure_arg = next("--exposure");
+        else if (a == "--white") { white = std::atof(next("--white")); white_set = true; }
         else if (a == "--env") env_path = next("--env");
         else if (a == "--env-scale") { env_scale = std::atof(next("--env-scale")); env_scale_set = true; }
         else if (a == "--env-nearest") env_nearest = true;
@@ -184,6 +198,16 @@ int main(int argc, char** argv) {
     if (mesh_path.empty()) return die("usage", "--mesh <file.obj|file.ptmesh> is required");
     if (spp < 1 || frames < 0 || W < 2 || H < 2) return die("usage", "--spp >= 1, --frames >= 0, --width/--height >= 2");
     if (gpus < 1 || gpus > 64 || tile < 8 || tile % 8) return die("usage", "--gpus 1..64, --tile a positive multiple of 8");
+    // the display stage (pt_meter, pt_tonemap): off unless one of its flags is given
+    const bool display = !tone_name.empty() || !xfer_name.empty() || !exposure_arg.empty() || white_set;
+    const bool exposure_auto = exposure_arg == "auto";
+    const int tone_curve = tone_name.empty() || tone_name == "clamp" ? PT_TONE_CLAMP : tone_name == "reinhard" ? PT_TONE_REINHARD : tone_name == "aces" ? PT_TONE_ACES : -1;
+    const int tone_xfer = xfer_name.empty() || xfer_name == "linear" ? PT_XFER_LINEAR : xfer_name == "srgb" ? PT_XFER_SRGB : xfer_name == "gamma22" ? PT_XFER_GAMMA22 : -1;
+    const double exposure = exposure_arg.empty() || exposure_auto ? 1.0 : std::atof(exposure_arg.c_str());
+    if (tone_curve < 0) return die("--tonemap", "one of clamp, reinhard, aces");
+    if (tone_xfer < 0) return die("--transfer", "one of linear, srgb, gamma22");
+    if (!std::isfinite(exposure) || !(exposure > 0.0)) return die("--exposure", "a finite number > 0, or auto");
+    if (white_set && !(white > 0.0)) return die("--white", "must be > 0");
 
     const bool until = until_error >= 0.0, with_moments = until || !variance_path.empty() || denoise_variance;
     if (denoise_variance && denoise_path.empty()) return die("usage", "--denoise-variance goes with --denoise-out");
@@ -501,6 +525,7 @@ int main(int argc, char** argv) {
     // --equirect: the latitude-longitude rays of the pixels, float[H W][8], made once (the camera stands still)
     void* eq_rays = nullptr;
     const bool out_pfm = out_path.size() > 4 && out_path.substr(out_path.size() - 4) == ".pfm";
+    const bool out_hdr = out_pfm || display;   // the ray routes keep the unclamped mean for a .pfm and for the display stage, whose curve does the clamping
     if (equirect) {
         const double pi = 3.14159265358979323846;
         std::vector<float> rays((size_t)W * H * 8, 0.f);
@@ -533,7 +558,7 @@ int main(int argc, char** argv) {
             pt_memset(ctx, a_cnt, 0, n_pix_all * 4) != PT_OK)
             return die("pt_malloc", pt_last_error(ctx));
         const pt_select_params sel = {W, H, (float)adaptive_error, (uint32_t)min_spp, (uint32_t)max_spp, 0};
-        const int mode = out_pfm ? PT_RAYS_HDR : PT_RAYS_CLAMPED;
+        const int mode = out_hdr ? PT_RAYS_HDR : PT_RAYS_CLAMPED;
         uint64_t n_sel = n_pix_all, total = 0;
         p.sample_index = 1;   // (not read: the counts carry N)
         for (const uint32_t* list = nullptr;; list = (const uint32_t*)a_pix) {
@@ -569,10 +594,10 @@ int main(int argc, char** argv) {
             p.frame = frameNumber;                                                      // :397
             p.sample_index = moving ? 1 : constantPdf + 1;                              // :399 (1 on the first frame: overwrite)
             if (equirect) {
-                if (pt_render_rays(ctx, (const float*)eq_rays, (size_t)W * H, 0, (float*)accum, &p, n, out_pfm ? PT_RAYS_HDR : PT_RAYS_CLAMPED) != PT_OK)
+                if (pt_render_rays(ctx, (const float*)eq_rays, (size_t)W * H, 0, (float*)accum, &p, n, out_hdr ? PT_RAYS_HDR : PT_RAYS_CLAMPED) != PT_OK)
                     return die("pt_render_rays", pt_last_error(ctx));
             } else if (ray_camera && !camera_loop) {   // a fresh jittered ray per sample, made where its path starts
-                if (pt_render_camera(ctx, &cam, &cmodel, nullptr, (size_t)W * H, 0, (float*)accum, &p, n, out_pfm ? PT_RAYS_HDR : PT_RAYS_CLAMPED) != PT_OK)
+                if (pt_render_camera(ctx, &cam, &cmodel, nullptr, (size_t)W * H, 0, (float*)accum, &p, n, out_hdr ? PT_RAYS_HDR : PT_RAYS_CLAMPED) != PT_OK)
                     return die("pt_render_camera", pt_last_error(ctx));
             } else if (ray_camera) {   // the same samples by their definition: generate, trace, on one stream
                 pt_params q = p;
@@ -580,7 +605,7 @@ int main(int argc, char** argv) {
                     q.frame = p.frame + s; q.sample_index = p.sample_index + s;
                     if (pt_camera_rays(ctx, &cam, &cmodel, q.frame, nullptr, (size_t)W * H, 0, (float*)eq_rays) != PT_OK)
                         return die("pt_camera_rays", pt_last_error(ctx));
-                    if (pt_render_rays(ctx, (const float*)eq_rays, (size_t)W * H, 0, (float*)accum, &q, 1, out_pfm ? PT_RAYS_HDR : PT_RAYS_CLAMPED) != PT_OK)
+                    if (pt_render_rays(ctx, (const float*)eq_rays, (size_t)W * H, 0, (float*)accum, &q, 1, out_hdr ? PT_RAYS_HDR : PT_RAYS_CLAMPED) != PT_OK)
                         return die("pt_render_rays", pt_last_error(ctx));
                 }
             } else
@@ -623,6 +648,22 @@ int main(int argc, char** argv) {
     if (!ckpt_path.empty())
         if (int rc = save_checkpoint()) return rc;
 
+    // --tonemap / --transfer / --exposure / --white: a float[H][W][3] buffer of the first context into display words, on the device —
+    // pt_meter first under --exposure auto (key 0.18 over every metered pixel; the exposure never leaves the device), then pt_tonemap
+    void *tone_rgba = nullptr, *tone_state = nullptr;
+    auto display_words = [&](const void* color_dev, std::vector<uint32_t>& img) -> int {
+        if (!tone_rgba && pt_malloc(ctx, img.size() * 4, &tone_rgba) != PT_OK) return die("pt_malloc", pt_last_error(ctx));
+        if (exposure_auto) {
+            if (!tone_state && (pt_malloc(ctx, 16, &tone_state) != PT_OK || pt_memset(ctx, tone_state, 0, 16) != PT_OK)) return die("pt_malloc", pt_last_error(ctx));
+            const pt_meter_params mp = {W, H, 0.18f, 0.0f, 1.0f, 1.0f / 65536.0f, 65536.0f, 1.0f};
+            if (pt_meter(ctx, &mp, (const float*)color_dev, (float*)tone_state, 1) != PT_OK) return die("pt_meter", pt_last_error(ctx));
+        }
+        const pt_tonemap_params tp = {W, H, tone_curve, tone_xfer, (float)exposure, (float)white};
+        if (pt_tonemap(ctx, &tp, (const float*)color_dev, exposure_auto ? (const float*)tone_state : nullptr, nullptr, (uint32_t*)tone_rgba) != PT_OK)
+            return die("pt_tonemap", pt_last_error(ctx));
+        if (pt_download(ctx, img.data(), tone_rgba, img.size() * 4) != PT_OK) return die("pt_download", pt_last_error(ctx));
+        return 0;
+    };
     if (!out_path.empty()) {
         const std::string ext = out_path.size() > 4 ? out_path.substr(out_path.size() - 4) : std::string();
         int rc;
@@ -632,7 +673,17 @@ int main(int argc, char** argv) {
             rc = pth_write_pfm(out_path.c_str(), host_acc.data(), W, H);
         } else {
             std::vector<uint32_t> img((size_t)W * H);
-            if (frames == 0 || equirect || ray_camera || adaptive) {  // nothing rendered in this run (e.g. --resume only to convert), or no display words (pt_render_rays): pack the accumulator here
+            if (display) {   // the accumulator through pt_tonemap on the first context (the other contexts' stripes gathered into a buffer of it)
+                void* color = accum;
+                if (gpus > 1) {
+                    host_acc.resize((size_t)W * H * 3);
+                    if (int grc = gather(accums, host_acc.data(), 12)) return grc;
+                    if (pt_malloc(ctx, host_acc.size() * 4, &color) != PT_OK || pt_upload(ctx, color, host_acc.data(), host_acc.size() * 4) != PT_OK)
+                        return die("pt_upload", pt_last_error(ctx));
+                }
+                if (int drc = display_words(color, img)) return drc;
+                if (gpus > 1) pt_free(ctx, color);
+            } else if (frames == 0 || equirect || ray_camera || adaptive) {  // nothing rendered in this run (e.g. --resume only to convert), or no display words (pt_render_rays): pack the accumulator here
                 host_acc.resize((size_t)W * H * 3);
                 if (int grc = gather(accums, host_acc.data(), 12)) return grc;
                 for (size_t i = 0; i < img.size(); i++) {   // rgbToUint, cudaUtils.h:99-105
@@ -669,7 +720,9 @@ int main(int argc, char** argv) {
             rc = pth_write_pfm(temporal_path.c_str(), img.data(), W, H);
         } else {
             std::vector<uint32_t> img(n_pix_all);
-            if (pt_download(ctx, img.data(), t_rgba, img.size() * 4) != PT_OK) return die("pt_download", pt_last_error(ctx));
+            if (display) {
+                if (int drc = display_words(t_color[k], img)) return drc;
+            } else if (pt_download(ctx, img.data(), t_rgba, img.size() * 4) != PT_OK) return die("pt_download", pt_last_error(ctx));
             rc = ext == ".png" ? pth_write_png(temporal_path.c_str(), img.data(), W, H) : pth_write_ppm(temporal_path.c_str(), img.data(), W, H);
         }
         if (rc != 0) return die("write", pth_last_error());
@@ -714,7 +767,9 @@ int main(int argc, char** argv) {
             rc = pth_write_pfm(denoise_path.c_str(), img.data(), W, H);
         } else {
             std::vector<uint32_t> img(n_pix);
-            if (pt_download(ctx, img.data(), drgba, img.size() * 4) != PT_OK) return die("pt_download", pt_last_error(ctx));
+            if (display) {
+                if (int drc = display_words(dout, img)) return drc;
+            } else if (pt_download(ctx, img.data(), drgba, img.size() * 4) != PT_OK) return die("pt_download", pt_last_error(ctx));
             rc = ext == ".png" ? pth_write_png(denoise_path.c_str(), img.data(), W, H) : pth_write_ppm(denoise_path.c_str(), img.data(), W, H);
         }
         if (rc != 0) return die("write", pth_last_error());
@@ -731,6 +786,8 @@ int main(int argc, char** argv) {
         for (int b = 0; b < 2; b++)
             if (spin_buf[(size_t)g * 2 + b]) pt_free(ctxs[(size_t)g], spin_buf[(size_t)g * 2 + b]);
     if (eq_rays) pt_free(ctx, eq_rays);
+    for (void* b : {tone_rgba, tone_state})
+        if (b) pt_free(ctx, b);
     (void)accum; (void)rgba;
     if (moments_all != moments[0]) pt_free(ctx, moments_all);
     for (int g = 0; g < gpus; g++) {

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import Camera, Counters, DenoiseParams, DenoiseVarianceParams, Environment, Material, Params, SelectParams, Sphere, TemporalParams
+from ._abi import Camera, Counters, DenoiseParams, DenoiseVarianceParams, Environment, Material, MeterParams, Params, SelectParams, Sphere, TemporalParams, TonemapParams
 
 # pt_denoise defaults (iterations, sigma_color, sigma_normal, sigma_position): chosen by the CPU sweep of DESIGN.md §10 f6;
 # host/pt_app.cpp uses the same values
@@ -23,6 +23,17 @@ DENOISE_DEFAULTS = dict(iterations=4, sigma_color=0.0, sigma_normal=1.0, sigma_p
 DENOISE_VARIANCE_DEFAULTS = dict(iterations=4, sigma_luminance=4.0, sigma_normal=1.0, sigma_position=0.03)
 # pt_temporal defaults: starting values by definition, not tuned figures; host/pt_app.cpp uses the same values
 TEMPORAL_DEFAULTS = dict(max_history=32.0, plane_tolerance=0.02, normal_threshold=0.9)
+
+
+def tone_thresholds(transfer):
+    """The 256 thresholds T of tonemap()'s transfer XFER_SRGB or XFER_GAMMA22 (pt_tonemap_thresholds; host only): the display code of
+    a curve output y is the number of k in 1..255 with y >= T[k]."""
+    out = np.empty(256, np.float32)
+    lib = _abi.ptmi()
+    rc = lib.pt_tonemap_thresholds(int(transfer), out.ctypes.data)
+    if rc != 0:
+        raise PtError(rc, lib.pt_last_error(None).decode())
+    return out
 
 
 class PtError(RuntimeError):
@@ -276,6 +287,25 @@ class PathTracer:
         n, mean = C.c_uint64(), C.c_double()
         self._check(self._lib.pt_select_pixels(self._ctx, C.byref(sp), moments_ptr, counts_ptr, pixels_ptr, C.byref(n), C.byref(mean)))
         return n.value, mean.value
+
+    def tonemap(self, color_ptr, width, height, rgba_ptr=None, out_ptr=None, curve=_abi.TONE_CLAMP, transfer=_abi.XFER_LINEAR, exposure=1.0,
+                white=float("inf"), exposure_ptr=None):
+        """A float[H][W][3] buffer into display words (pt_tonemap): colour x exposure (x exposure_ptr[0] on the device, e.g. the
+        state meter() keeps), the curve TONE_CLAMP / TONE_REINHARD (white: the scaled luminance shown as white) / TONE_ACES, then the
+        transfer XFER_LINEAR / XFER_SRGB / XFER_GAMMA22 into rgba uint32[H][W]; out float[H][W][3] (optional, may be color) receives
+        the curve's output before the transfer.  At least one of rgba_ptr, out_ptr.  Asynchronous until sync()."""
+        tp = TonemapParams(int(width), int(height), int(curve), int(transfer), float(exposure), float(white))
+        self._check(self._lib.pt_tonemap(self._ctx, C.byref(tp), color_ptr, exposure_ptr, out_ptr, rgba_ptr))
+
+    def meter(self, color_ptr, width, height, state_ptr, key=0.18, low_pct=0.0, high_pct=1.0, min_exposure=2.0 ** -16, max_exposure=2.0 ** 16,
+              adapt=1.0, reset=False):
+        """The exposure that shows a float[H][W][3] buffer's average luminance at `key`, found and kept on the device (pt_meter):
+        state float[4] = (exposure in use, this frame's target, metered luminance, pixels that took part); the average is the
+        log-average of the pixels between the low_pct and high_pct shares of the luminance histogram; adapt < 1 moves the exposure
+        in use only part of the way to the target, reset jumps.  Pass state_ptr as tonemap(exposure_ptr=).  Asynchronous until
+        sync(); nothing comes back to the host."""
+        mp = MeterParams(int(width), int(height), float(key), float(low_pct), float(high_pct), float(min_exposure), float(max_exposure), float(adapt))
+        self._check(self._lib.pt_meter(self._ctx, C.byref(mp), color_ptr, state_ptr, 1 if reset else 0))
 
     def upload_environment(self, texels, front=(0, 0, -1), right=(1, 0, 0), up=(0, 1, 0), scale=(1, 1, 1), filter=_abi.ENV_BILINEAR, light=False):
         """Light the paths that leave the scene with a latitude-longitude map (pt_upload_environment) instead of bk_color: texels

@@ -1079,6 +1079,88 @@ int pt_temporal_moments(pt_ctx* ctx, const pt_temporal_params* tp, const pt_came
                         const float* cur_normal_dev, const float* cur_position_dev, const int32_t* cur_id_dev,
                         float* out_moments_dev);
 
+/* ---- display: exposure metering and tone mapping, an EXTENSION ---------------------------------
+ * The last stage of a frame: any float[H][W][3] buffer (an accumulator, PT_RAYS_HDR or clamped; a denoiser's or the temporal
+ * filter's output) becomes display words on the device, under an exposure a meter found on the device.  render, (temporal),
+ * (denoise), pt_meter, pt_tonemap then run on one stream with no host round trip.  Everything is binary32 / integer arithmetic
+ * with plain *, + and the correctly rounded / (no fused operation), so numpy restates it bit for bit (tests/tonemap_ref.py).
+ *
+ * pt_tonemap, per pixel and channel c of color_dev:
+ *   exposure  e = tp->exposure; with exposure_dev, e = tp->exposure * exposure_dev[0], read on the device; a product that is not
+ *             finite or is <= 0 falls back to e = tp->exposure
+ *   input     x = c * e, then x = x > 0 ? fminf(x, 65536.0f) : 0      (a NaN and a negative become 0, +inf becomes 65536)
+ *   curve     PT_TONE_CLAMP     y = fminf(x, 1)
+ *             PT_TONE_REINHARD  on the luminance, so the hue is kept:  L = (0.2126f x.r + 0.7152f x.g) + 0.0722f x.b,
+ *                               s = (1.0f + L * iw2) / (1.0f + L),  y = fminf(x * s, 1),  where iw2 = 0 for white == +inf (plain
+ *                               Reinhard) and 1.0f / (white * white) otherwise, computed on the host in binary32
+ *             PT_TONE_ACES      the Narkowicz fit, per channel:  a = x * (2.51f * x + 0.03f),  b = x * (2.43f * x + 0.59f) + 0.14f,
+ *                               y = fminf(a / b, 1)
+ *   out_dev   float[H][W][3] receives y, the curve's output BEFORE the transfer (for hosts with an encoding of their own)
+ *   rgba_dev  uint32[H][W] receives 0x00BBGGRR of three codes.  PT_XFER_LINEAR: the truncating pack of pt_render's display words,
+ *             (unsigned char)(255.0f * y) — so CLAMP + LINEAR + exposure 1 over an accumulator gives the words pt_render writes
+ *             under PT_FLAG_WRITE_RGBA.  PT_XFER_SRGB / PT_XFER_GAMMA22: code = the number of k in 1..255 with y >= T[k], T the
+ *             table of pt_tonemap_thresholds: round-to-nearest of the encoded value with no pow on the device.
+ * out_dev may alias color_dev (a thread reads its pixels before it writes them); at least one of out_dev, rgba_dev is given.
+ * One launch.  Where W * H is a multiple of 4 and every buffer given is 16-byte aligned a thread takes four pixels as three 16-byte
+ * loads and writes one 16-byte store of four words; otherwise one pixel per thread.  Both routes give the same bits.  The tables
+ * (2 KB) are uploaded to the context by the first call that needs them; no allocation afterwards.
+ * Errors, in this order, PT_ERR_INVALID each: NULL ctx; a NULL tp or color_dev, or out_dev and rgba_dev both NULL; width or height
+ * < 1, or W * H >= 2^32; a curve or a transfer that is not one of the three; an exposure that is not finite or is <= 0; under
+ * PT_TONE_REINHARD a white that is not > 0 (a NaN included; +inf is plain Reinhard).  Nothing is written by a refused call.
+ *
+ * pt_tonemap_thresholds: T[0] = 0 and T[k] = eotf((k - 0.5) / 255) for k = 1..255, evaluated in double and rounded once to binary32;
+ * PT_XFER_SRGB: eotf(v) = v <= 0.04045 ? v / 12.92 : pow((v + 0.055) / 1.055, 2.4);  PT_XFER_GAMMA22: pow(v, 2.2).  Strictly
+ * increasing.  Host only, no context.  PT_ERR_INVALID for a NULL out256 or another transfer (PT_XFER_LINEAR has no table).
+ *
+ * pt_meter leaves the exposure for a frame in state_dev, float[4] on the device, without the host seeing it:
+ *   state[0] the exposure in use   [1] this frame's target   [2] the metered luminance Lavg   [3] (float) the pixels that took part
+ *   histogram 256 bins of L = (0.2126f r + 0.7152f g) + 0.0722f b of the unscaled colour over 2^-16 .. 2^16, eight per octave, from
+ *             the float's own bits (a piecewise-linear logarithm: integer arithmetic).  A pixel whose L is not finite or is < 2^-16
+ *             is not metered; L >= 65536 goes to bin 255; otherwise bin = (float_as_uint of L >> 20) - ((127 - 16) << 3).
+ *   trim      n = the pixels metered; lo = (uint64)((double)low_pct * (double)n), hi likewise from high_pct; hi <= lo: lo = 0,
+ *             hi = n.  With inclusive prefix counts cum, bin b takes part with w_b = max(0, min(cum_b, hi) - max(cum_(b-1), lo)).
+ *   average   S = sum w_b (2b + 1), Wt = sum w_b in 64-bit integers; p = (double)S / (double)(16 Wt) - 16.0, i = floor of p,
+ *             Lavg = (float)ldexp(1.0 + (p - i), i): the inverse of the same logarithm, with no exp2 or log2
+ *   target    fminf(fmaxf(key / Lavg, min_exposure), max_exposure).  Wt == 0: Lavg = 0 and the target is the previous state[0] if
+ *             that is finite and > 0 (also under reset: zero the state before a first frame that may be black), else 1, clamped alike.
+ *   in use    state[0] = (reset or the previous state[0] is not finite or is <= 0) ? target : prev + (target - prev) * adapt
+ *   A uniform 0.18 grey meters as bin 107, Lavg = 0.1796875.
+ * Two launches: a histogram pass over min(ceil(W H / 256), 256) blocks of 256 threads, each thread striding over pixels (four at a
+ * time as three 16-byte loads where W * H is a multiple of 4 and color_dev is 16-byte aligned), counting into a 257-entry LDS
+ * histogram by integer LDS adds — the 257th entry counts the unmetered pixels — and storing the block's histogram into the context's
+ * scratch [blocks][257] with plain stores (no global atomics; integer adds give the same counts in any order); then one 256-thread
+ * block that adds the partial histograms per bin, scans them and writes the four floats from one thread.  No copy back, no
+ * synchronisation, no allocation after the first call: the scratch is 256 x 257 x 4 bytes (263 KB), freed by pt_destroy.
+ * Errors, in this order, PT_ERR_INVALID each: NULL ctx; a NULL mp, color_dev or state_dev; width or height < 1, or W * H >= 2^32; a
+ * key that is not finite or is <= 0; percentages outside 0 <= low_pct < high_pct <= 1; exposure limits that are not finite with
+ * 0 < min_exposure <= max_exposure; an adapt outside 0..1.  Nothing is written by a refused call, the state included.
+ *
+ * Both calls are asynchronous on the context's stream — pt_tonemap after pt_meter reads the state the meter wrote — need no scene,
+ * and with PT_OPT_TIMING=1 pt_last_kernel_ms covers each of them.
+ * Left out: dithering, bloom, per-channel or local operators, a log-domain adaptation rate, display words fused into the folds of
+ * the render calls, a display-space error criterion for pt_select_pixels. */
+enum { PT_TONE_CLAMP = 0, PT_TONE_REINHARD = 1, PT_TONE_ACES = 2 };
+enum { PT_XFER_LINEAR = 0, PT_XFER_SRGB = 1, PT_XFER_GAMMA22 = 2 };
+typedef struct pt_tonemap_params {
+    int32_t width, height;   /* >= 1, W * H < 2^32 */
+    int32_t curve;           /* PT_TONE_* */
+    int32_t transfer;        /* PT_XFER_* */
+    float exposure;          /* finite, > 0: scale on linear radiance */
+    float white;             /* PT_TONE_REINHARD: the scaled luminance shown as white; > 0, +inf = plain Reinhard; ignored otherwise */
+} pt_tonemap_params;         /* 24 bytes */
+int pt_tonemap(pt_ctx* ctx, const pt_tonemap_params* tp, const float* color_dev,
+               const float* exposure_dev /* may be NULL: float[1], e.g. pt_meter's state */,
+               float* out_dev /* may be NULL; may alias color_dev */, uint32_t* rgba_dev /* may be NULL; not both */);
+typedef struct pt_meter_params {
+    int32_t width, height;
+    float key;                        /* finite, > 0: the luminance the metered average is shown at (0.18) */
+    float low_pct, high_pct;          /* 0 <= low < high <= 1: share of the metered pixels ignored below / kept up to */
+    float min_exposure, max_exposure; /* finite, 0 < min <= max */
+    float adapt;                      /* 0..1: weight of this frame's target in the exposure in use; 1 = jump */
+} pt_meter_params;                    /* 32 bytes */
+int pt_meter(pt_ctx* ctx, const pt_meter_params* mp, const float* color_dev, float* state_dev /* float[4], device */, int reset);
+int pt_tonemap_thresholds(int transfer, float* out256);
+
 /* ---- measurement --------------------------------------------------------------- */
 int pt_get_counters(pt_ctx* ctx, pt_counters* out);
 /* Schedule statistics of the last instrumented launch of the persistent wide walk
