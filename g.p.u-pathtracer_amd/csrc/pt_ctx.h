@@ -1,6 +1,6 @@
 // pt_ctx.h — the context behind the C ABI (include/ptmi.h) and the host-side helpers shared by the
 // translation units of libptmi.so: ptmi.hip (API), pt_tree.hip (trees: makers, adoption, cost), pt_build.hip (device BVH
-// builder), pt_refit.hip (refit), pt_denoise.hip (guide buffers, denoiser, temporal filter, frame error, pixel selection), pt_k_*.hip (kernel families +
+// builder), pt_refit.hip (refit), pt_aux.hip, pt_filter.hip, pt_temporal.hip, pt_select.hip, pt_display.hip (the image stages: guide buffers, a-trous filters, reprojection, frame error and pixel selection, display; pt_image.h is what they share), pt_k_*.hip (kernel families +
 // their launchers, no API function), pt_env.hip (environment map), pt_camera.hip (camera models).  Host code only.
 // Every device buffer, event and stream of the context is a member that owns it (pt_own.h): pt_destroy waits and deletes.  The scene's
 // resources — tree, spheres, materials, environment — are values: built in a local, adopted behind quiesce().
@@ -217,15 +217,15 @@ struct pt_ctx {
         uint32_t* first_use = nullptr;           // bit per record: the first record of its triangle (counts a dropped triangle once)
         std::vector<uint32_t> bin_off, wide_off; // list offsets per height (size heights + 1)
     } refit;
-    // pt_denoise's two ping-pong colour frames (pt_denoise.hip): grow-only
+    // pt_denoise's two ping-pong colour frames (pt_filter.hip; pt_denoise_variance uses them too): grow-only
     DevBuf<float4> d_denoise;
-    // pt_frame_error's per-block partial results (pt_denoise.hip): [blocks] double sums, then [blocks] uint32 counts; grow-only
+    // pt_frame_error's per-block partial results (pt_select.hip): [blocks] double sums, then [blocks] uint32 counts; grow-only
     DevBuf<char> d_frame_err;
-    // pt_select_pixels' per-block scratch (pt_denoise.hip): [blocks] double sums, [blocks] uint32 counts, [blocks] uint32 list offsets; grow-only
+    // pt_select_pixels' per-block scratch (pt_select.hip): [blocks] double sums, [blocks] uint32 counts, [blocks] uint32 list offsets; grow-only
     DevBuf<char> d_select;
-    // pt_meter's partial histograms (pt_denoise.hip): [METER_BLOCKS][METER_BINS + 1] uint32, reserved whole by the first call
+    // pt_meter's partial histograms (pt_display.hip): [METER_BLOCKS][METER_BINS + 1] uint32, reserved whole by the first call
     DevBuf<uint32_t> d_meter;
-    // pt_tonemap's threshold tables (pt_denoise.hip): [2][256] floats, PT_XFER_SRGB then PT_XFER_GAMMA22, uploaded by the first call that needs one
+    // pt_tonemap's threshold tables (pt_display.hip): [2][256] floats, PT_XFER_SRGB then PT_XFER_GAMMA22, uploaded by the first call that needs one
     DevBuf<float> d_tone;
     Event ev0, ev1;
     bool timed = false;

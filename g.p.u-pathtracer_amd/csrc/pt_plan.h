@@ -1,6 +1,6 @@
 // pt_plan.h — what every call runs, decided in plain C++: the argument rules of the path calls, the walk, the kernel family, the side
 // stream, the sample and LDS layouts, the queue and the grids, the stage-split pipeline's records and launches, the plans of
-// pt_render_rays, of pt_select_pixels and of the ray-batch queries.  Every function here is a pure function of plain facts: what the context holds
+// pt_render_rays, of pt_select_pixels and of the ray-batch queries, the argument rules of every image-stage call.  Every function here is a pure function of plain facts: what the context holds
 // (CtxFacts, filled by ctx_facts in ptmi.hip), what the caller passed (CallFacts) and the two answers only the runtime has (whether the
 // caller's stream is idle; PT_KERNEL_AUTO's table).  The entry points gather the facts, ask, and apply the answer; the check program
 // (pt_variants_check.cpp) asks the same functions over a domain of scenes x options x calls on the host.  No HIP call, no HIP type.
@@ -475,6 +475,96 @@ inline DisplayPlan plan_meter(uint64_t n_pix, bool aligned16) {
     d.items = d.vec ? n_pix / 4 : n_pix;
     d.n_blocks = (uint32_t)std::min<uint64_t>((n_pix + 255) / 256, METER_BLOCKS);
     return d;
+}
+
+// ---- pt_render_aux, pt_denoise, pt_denoise_variance, the three reprojections and pt_frame_error: their argument rules in the
+// header's order.  Device pointers are compared, never read.
+// buffers: cam and the three guide buffers are given
+inline Refusal check_aux_call(const CtxFacts& f, const pt_params* p, bool buffers) {
+    if (!buffers || !p) return {PT_ERR_INVALID, "pt_render_aux: null argument"};
+    if (p->width < 1 || p->height < 1) return {PT_ERR_INVALID, "pt_render_aux: width and height must be >= 1"};
+    if (!f.has_bvh) return {PT_ERR_NO_SCENE, "pt_render_aux: no BVH uploaded"};
+    if (f.records_woop) return {PT_ERR_UNSUPPORTED, "pt_render_aux: the binary walk reads Moller-Trumbore records (upload with PT_OPT_TRI_TEST 0)"};
+    return {};
+}
+// buffers: the colour, the three guide buffers and out are given
+inline Refusal check_denoise_call(const pt_denoise_params* dp, bool buffers) {
+    if (!dp || !buffers) return {PT_ERR_INVALID, "pt_denoise: null argument"};
+    if (dp->width < 1 || dp->height < 1) return {PT_ERR_INVALID, "pt_denoise: width and height must be >= 1"};
+    if (dp->iterations < 0 || dp->iterations > 10) return {PT_ERR_INVALID, "pt_denoise: iterations must be 0..10"};
+    if (!plan_finite(dp->sigma_color) || !plan_finite(dp->sigma_normal) || !plan_finite(dp->sigma_position)) return {PT_ERR_INVALID, "pt_denoise: a sigma is not finite"};
+    return {};
+}
+// the caller's buffers as it passed them (length, out_variance and the display words may be null)
+struct VarianceBuffers { const void *color, *moments, *length, *albedo, *normal, *position, *out, *out_variance; };
+inline Refusal check_denoise_variance_call(const pt_denoise_variance_params* dp, const VarianceBuffers& b) {
+    if (!dp || !b.color || !b.albedo || !b.normal || !b.position || !b.out) return {PT_ERR_INVALID, "pt_denoise_variance: null argument"};
+    if (dp->width < 1 || dp->height < 1) return {PT_ERR_INVALID, "pt_denoise_variance: width and height must be >= 1"};
+    if (dp->iterations < 0 || dp->iterations > 10) return {PT_ERR_INVALID, "pt_denoise_variance: iterations must be 0..10"};
+    if (!plan_finite(dp->sigma_luminance) || !plan_finite(dp->sigma_normal) || !plan_finite(dp->sigma_position))
+        return {PT_ERR_INVALID, "pt_denoise_variance: a sigma is not finite"};
+    if (!b.moments) return {PT_ERR_INVALID, "pt_denoise_variance: null moments"};
+    if (!plan_finite(dp->samples_per_frame) || dp->samples_per_frame < 1.f) return {PT_ERR_INVALID, "pt_denoise_variance: samples_per_frame must be finite and >= 1"};
+    const void* const inputs[] = {b.color, b.moments, b.length, b.albedo, b.normal, b.position};
+    if (b.out_variance)
+        for (const void* in : inputs)
+            if (in == b.out_variance) return {PT_ERR_INVALID, "pt_denoise_variance: out_variance_dev may not be one of the inputs"};
+    return {};
+}
+// What the caller of pt_temporal, pt_temporal_motion (rows, motion) or pt_temporal_moments (rows; the buffers named *_color hold its
+// moments, and it has no out_length, no rgba) passed; a pointer the call does not have stays null
+enum TemporalKind { TEMPORAL_COLOUR, TEMPORAL_MOTION, TEMPORAL_MOMENTS };
+struct TemporalCall {
+    TemporalKind kind;
+    const pt_temporal_params* tp;
+    const pt_camera* prev_cam;
+    const float *prev_color, *prev_length, *prev_normal, *prev_position;
+    const int32_t* prev_id;
+    const float *cur_color, *cur_normal, *cur_position;
+    const int32_t* cur_id;
+    float *out_color, *out_length;
+    uint32_t* rgba;
+    const float *prev_verts, *cur_verts;   // the vertex rows by triangle id
+    size_t n_tris;
+    float* motion;
+};
+// a history: prev_color is given.  rows: the call finds moved triangles' points in the vertex rows (pt_temporal_motion always,
+// pt_temporal_moments where a row buffer is given)
+inline bool temporal_reads_rows(const TemporalCall& a) { return a.kind == TEMPORAL_MOTION || (a.kind == TEMPORAL_MOMENTS && (a.prev_verts || a.cur_verts)); }
+inline Refusal check_temporal_call(const std::string& who, const TemporalCall& a) {
+    const bool with_length = a.kind != TEMPORAL_MOMENTS;
+    const pt_temporal_params* tp = a.tp;
+    if (!tp || !a.cur_color || !a.cur_normal || !a.cur_position || !a.out_color || (with_length && !a.out_length)) return {PT_ERR_INVALID, who + ": null argument"};
+    if (tp->width < 2 || tp->height < 2) return {PT_ERR_INVALID, who + ": width and height must be >= 2"};
+    if (!plan_finite(tp->max_history) || tp->max_history < 1.f) return {PT_ERR_INVALID, who + ": max_history must be finite and >= 1"};
+    if (!plan_finite(tp->plane_tolerance) || tp->plane_tolerance < 0.f) return {PT_ERR_INVALID, who + ": plane_tolerance must be finite and >= 0"};
+    if (!(tp->normal_threshold >= -1.f && tp->normal_threshold <= 1.f)) return {PT_ERR_INVALID, who + ": normal_threshold must be in -1..1"};
+    if (!a.prev_color) return {};
+    if (!a.prev_cam || !a.prev_length || !a.prev_normal || !a.prev_position) return {PT_ERR_INVALID, who + ": a history needs its camera, lengths, normals and positions"};
+    if ((a.prev_id == nullptr) != (a.cur_id == nullptr)) return {PT_ERR_INVALID, who + ": ids of both frames or of neither"};
+    if (a.out_color == a.prev_color || (with_length && a.out_length == a.prev_length))
+        return {PT_ERR_INVALID, who + ": the new history may not overwrite the old one (ping-pong the buffers)"};
+    if (!temporal_reads_rows(a)) return {};
+    if (!a.prev_id || !a.cur_id) return {PT_ERR_INVALID, who + ": the ids of both frames are required (they choose the vertex rows)"};
+    if (a.n_tris > 0 && (!a.prev_verts || !a.cur_verts)) return {PT_ERR_INVALID, who + ": a null vertex buffer with n_tris > 0"};
+    if (a.n_tris >= ((size_t)1 << 31)) return {PT_ERR_INVALID, who + ": n_tris must be < 2^31 (ids are int32)"};
+    const void* const others[] = {a.prev_verts, a.cur_verts, a.prev_color, a.prev_length, a.prev_normal, a.prev_position, a.prev_id,
+                                  a.cur_color, a.cur_normal, a.cur_position, a.cur_id, a.out_color, a.out_length, a.rgba};
+    if (a.motion)
+        for (const void* o : others)
+            if (o == (const void*)a.motion) return {PT_ERR_INVALID, who + ": motion_dev may not be one of the other buffers"};
+    return {};
+}
+// buffers: the moments and one of mean_rse, n_above are given; n_pix: width * height of a call that passes
+inline Refusal check_frame_error_call(bool buffers, int32_t width, int32_t height, uint64_t n_samples, float threshold, uint64_t& n_pix) {
+    n_pix = 0;
+    if (!buffers) return {PT_ERR_INVALID, "pt_frame_error: null argument"};
+    if (width < 1 || height < 1) return {PT_ERR_INVALID, "pt_frame_error: width and height must be >= 1"};
+    if (n_samples < 2) return {PT_ERR_INVALID, "pt_frame_error: the standard error needs n_samples >= 2"};
+    if (!plan_finite(threshold) || threshold < 0.f) return {PT_ERR_INVALID, "pt_frame_error: threshold must be finite and >= 0"};
+    n_pix = (uint64_t)width * (uint64_t)height;
+    if (n_pix > 0xffffffffull) return {PT_ERR_INVALID, "pt_frame_error: more than 2^32 - 1 pixels"};
+    return {};
 }
 
 // ---- pt_closest_hits / pt_any_hits: the wide walk on a resident grid over regions of PT_REGION rays at one of the extend stage's two

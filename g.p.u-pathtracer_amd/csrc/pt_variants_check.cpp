@@ -1,6 +1,6 @@
 // pt_variants_check.cpp — every request has a kernel and every kernel a request, and every plan is sound: a CPU program with its own
 // main, no HIP library (`make variants_check`, SAN=1 for the address and undefined-behaviour sanitizers; tests/test_variants.py runs both).
-// It RUNS the planner (pt_plan.h: the functions pt_render, pt_render_rays, pt_render_camera, pt_render_pixels, pt_select_pixels, pt_tonemap, pt_meter and the ray-batch queries call) over a domain of scenes x
+// It RUNS the planner (pt_plan.h: the functions pt_render, pt_render_rays, pt_render_camera, pt_render_pixels, pt_select_pixels, pt_tonemap, pt_meter, the older image-stage calls and the ray-batch queries call) over a domain of scenes x
 // options x calls x the runtime's answers, and holds no rule of its own: a call is skipped because the planner refused it, and the
 // refusal's code has to be the one REFUSALS lists for its text.  Of every plan it asserts what follows from the project's constants
 // (LDS, refill <= batch, grids, the record layout); of every variant word a plan asks a launcher for, that the word is instantiated —
@@ -72,6 +72,16 @@ static struct { const char* text; int code; long seen; } REFUSALS[] = {
     {"unknown curve or transfer", PT_ERR_INVALID, 0}, {"exposure must be finite and > 0", PT_ERR_INVALID, 0}, {"white must be > 0", PT_ERR_INVALID, 0},
     {"key must be finite and > 0", PT_ERR_INVALID, 0}, {"0 <= low_pct < high_pct <= 1", PT_ERR_INVALID, 0},
     {"0 < min_exposure <= max_exposure", PT_ERR_INVALID, 0}, {"adapt must be in 0..1", PT_ERR_INVALID, 0},
+    // pt_render_aux's, the two filters', the three reprojections' and pt_frame_error's (null argument, image and threshold rows are above)
+    {": no BVH uploaded", PT_ERR_NO_SCENE, 0}, {"the binary walk reads Moller-Trumbore records", PT_ERR_UNSUPPORTED, 0},
+    {"iterations must be 0..10", PT_ERR_INVALID, 0}, {"a sigma is not finite", PT_ERR_INVALID, 0}, {": null moments", PT_ERR_INVALID, 0},
+    {"samples_per_frame must be finite and >= 1", PT_ERR_INVALID, 0}, {"out_variance_dev may not be one of the inputs", PT_ERR_INVALID, 0},
+    {"max_history must be finite and >= 1", PT_ERR_INVALID, 0}, {"plane_tolerance must be finite and >= 0", PT_ERR_INVALID, 0},
+    {"normal_threshold must be in -1..1", PT_ERR_INVALID, 0}, {"a history needs its camera, lengths, normals and positions", PT_ERR_INVALID, 0},
+    {": ids of both frames or of neither", PT_ERR_INVALID, 0}, {"the new history may not overwrite the old one", PT_ERR_INVALID, 0},
+    {"the ids of both frames are required", PT_ERR_INVALID, 0}, {"a null vertex buffer with n_tris > 0", PT_ERR_INVALID, 0},
+    {"n_tris must be < 2^31", PT_ERR_INVALID, 0}, {"motion_dev may not be one of the other buffers", PT_ERR_INVALID, 0},
+    {"the standard error needs n_samples >= 2", PT_ERR_INVALID, 0}, {"more than 2^32 - 1 pixels", PT_ERR_INVALID, 0},
 };
 static long n_refused = 0, n_planned = 0;
 // true: the planner refused the call or found nothing to do in it
@@ -641,6 +651,191 @@ int main() {
         for (float bad : {0.5f, inf, nan}) { mp.max_exposure = bad; CHECK(says(check_meter_call(&mp, true, n_pix), "0 < min_exposure <= max_exposure")); }
         mp.max_exposure = 1.0f;
         for (float bad : {-0.5f, 1.5f, nan}) { mp.adapt = bad; CHECK(says(check_meter_call(&mp, true, n_pix), "adapt must be in 0..1")); }
+    }
+
+    // (g5) pt_render_aux, pt_denoise, pt_denoise_variance, the three reprojections and pt_frame_error: every rule broken alone and together
+    // (the first in the header's order answers), a well-formed call passes, and the values each rule names.  The "device" pointers
+    // are addresses of host words that nothing reads.
+    {
+        const float inf = 1.0f / 0.0f * (float)(KERNELS[1] != 0), nan = inf - inf;
+        auto says = [](const Refusal& r, const char* text) { return r.code != PT_OK && r.msg.find(text) != std::string::npos; };
+        // `rules`: (broken, text) in the header's order; the call must answer with the first broken one, or pass
+        struct Rule { bool broken; const char* text; };
+        auto first_answers = [&](const Refusal& r, std::initializer_list<Rule> rules) {
+            for (const Rule& k : rules)
+                if (k.broken) {
+                    CHECK(turned_away(r));
+                    CHECK(says(r, k.text));
+                    return;
+                }
+            CHECK(r.code == PT_OK && !r.nothing && r.msg.empty());
+        };
+        static float mem[24];
+        static int32_t ids[2];
+        static uint32_t words[1];
+
+        for (int broken = 0; broken < 32; broken++) {
+            pt_params p = {};
+            p.width = broken & 2 ? 0 : 37; p.height = 23;
+            const CtxFacts f = scene(broken & 4 ? NO_TREE : broken & 8 ? TREE_WOOP : TREE, SPHERES[1], MATS[0], ENV_NONE);
+            first_answers(check_aux_call(f, broken & 16 ? nullptr : &p, !(broken & 1)),
+                          {{(broken & 17) != 0, "pt_render_aux: null argument"}, {(broken & 2) != 0, "pt_render_aux: width and height must be >= 1"},
+                           {(broken & 4) != 0, "pt_render_aux: no BVH uploaded"}, {(broken & 8) != 0, "the binary walk reads Moller-Trumbore records"}});
+        }
+        for (int broken = 0; broken < 32; broken++) {
+            pt_denoise_params dp = {};
+            dp.width = broken & 2 ? 0 : 37; dp.height = 23; dp.iterations = broken & 4 ? 11 : 4;
+            dp.sigma_color = 0.0f; dp.sigma_normal = broken & 8 ? nan : 1.0f; dp.sigma_position = 0.03f;
+            first_answers(check_denoise_call(broken & 16 ? nullptr : &dp, !(broken & 1)),
+                          {{(broken & 17) != 0, "pt_denoise: null argument"}, {(broken & 2) != 0, "pt_denoise: width and height must be >= 1"},
+                           {(broken & 4) != 0, "pt_denoise: iterations must be 0..10"}, {(broken & 8) != 0, "pt_denoise: a sigma is not finite"}});
+        }
+        for (int broken = 0; broken < 256; broken++) {
+            pt_denoise_variance_params dp = {};
+            dp.width = 37; dp.height = broken & 2 ? 0 : 23; dp.iterations = broken & 4 ? -1 : 4;
+            dp.sigma_luminance = broken & 8 ? inf : 4.0f; dp.sigma_normal = 1.0f; dp.sigma_position = 0.03f; dp.samples_per_frame = broken & 32 ? 0.5f : 4.0f;
+            const VarianceBuffers b = {broken & 1 ? nullptr : &mem[0], broken & 16 ? nullptr : &mem[1], &mem[2], &mem[3], &mem[4], &mem[5], &mem[6], broken & 64 ? &mem[2] : &mem[7]};
+            first_answers(check_denoise_variance_call(broken & 128 ? nullptr : &dp, b),
+                          {{(broken & 129) != 0, "pt_denoise_variance: null argument"}, {(broken & 2) != 0, "pt_denoise_variance: width and height must be >= 1"},
+                           {(broken & 4) != 0, "pt_denoise_variance: iterations must be 0..10"}, {(broken & 8) != 0, "pt_denoise_variance: a sigma is not finite"},
+                           {(broken & 16) != 0, "pt_denoise_variance: null moments"}, {(broken & 32) != 0, "samples_per_frame must be finite and >= 1"},
+                           {(broken & 64) != 0, "out_variance_dev may not be one of the inputs"}});
+        }
+        // the reprojections: bit 8192 takes the history away, and with it every rule behind the parameters'
+        const struct { TemporalKind kind; const char* who; } CALLS[] = {{TEMPORAL_COLOUR, "pt_temporal"}, {TEMPORAL_MOTION, "pt_temporal_motion"}, {TEMPORAL_MOMENTS, "pt_temporal_moments"}};
+        auto well_formed = [&](TemporalKind kind, pt_temporal_params* tp, pt_camera* cam) {
+            tp->width = 37; tp->height = 23; tp->max_history = 32.0f; tp->plane_tolerance = 0.02f; tp->normal_threshold = 0.9f;
+            TemporalCall a = {};
+            a.kind = kind; a.tp = tp; a.prev_cam = cam;
+            a.prev_color = &mem[0]; a.prev_length = &mem[1]; a.prev_normal = &mem[2]; a.prev_position = &mem[3]; a.prev_id = &ids[0];
+            a.cur_color = &mem[4]; a.cur_normal = &mem[5]; a.cur_position = &mem[6]; a.cur_id = &ids[1];
+            a.out_color = &mem[7];
+            if (kind != TEMPORAL_MOMENTS) { a.out_length = &mem[8]; a.rgba = &words[0]; }
+            if (kind != TEMPORAL_COLOUR) { a.prev_verts = &mem[9]; a.cur_verts = &mem[10]; a.n_tris = 5; }
+            if (kind == TEMPORAL_MOTION) a.motion = &mem[11];
+            return a;
+        };
+        for (const auto& call : CALLS)
+            for (int broken = 0; broken < 16384; broken++) {
+                pt_temporal_params tp = {};
+                pt_camera cam = {};
+                TemporalCall a = well_formed(call.kind, &tp, &cam);
+                const bool rows = call.kind != TEMPORAL_COLOUR, history = !(broken & 8192);
+                if (broken & 1) a.cur_normal = nullptr;
+                if (broken & 2) tp.width = 1;
+                if (broken & 4) tp.max_history = 0.5f;
+                if (broken & 8) tp.plane_tolerance = -1.0f;
+                if (broken & 16) tp.normal_threshold = 2.0f;
+                if (broken & 32) a.prev_normal = nullptr;
+                if (broken & (64 | 256)) a.prev_id = nullptr;   // 64 alone: the ids of one frame; 256: of neither
+                if (broken & 256) a.cur_id = nullptr;
+                if (broken & 128) a.out_color = (float*)a.prev_color;
+                if (broken & 512) a.prev_verts = nullptr;        // (the colour call has no rows: these three change nothing there)
+                if (broken & 1024) a.n_tris = (size_t)1 << 31;
+                if (broken & 2048 && call.kind == TEMPORAL_MOTION) a.motion = (float*)a.rgba;
+                if (broken & 4096) a.tp = nullptr;
+                if (!history) a.prev_color = nullptr;
+                const std::string who = std::string(call.who) + ": ";
+                const std::string t0 = who + "null argument", t1 = who + "width and height must be >= 2", t2 = who + "max_history must be finite and >= 1",
+                                  t3 = who + "plane_tolerance must be finite and >= 0", t4 = who + "normal_threshold must be in -1..1",
+                                  t5 = who + "a history needs its camera", t6 = who + "ids of both frames or of neither", t7 = who + "the new history may not overwrite",
+                                  t8 = who + "the ids of both frames are required", t9 = who + "a null vertex buffer with n_tris > 0", t10 = who + "n_tris must be < 2^31",
+                                  t11 = who + "motion_dev may not be one of the other buffers";
+                first_answers(check_temporal_call(call.who, a),
+                              {{(broken & (1 | 4096)) != 0, t0.c_str()}, {(broken & 2) != 0, t1.c_str()}, {(broken & 4) != 0, t2.c_str()}, {(broken & 8) != 0, t3.c_str()},
+                               {(broken & 16) != 0, t4.c_str()}, {history && (broken & 32), t5.c_str()}, {history && (broken & 64) && !(broken & 256), t6.c_str()},
+                               {history && (broken & 128), t7.c_str()}, {history && rows && (broken & 256), t8.c_str()}, {history && rows && (broken & 512), t9.c_str()},
+                               {history && rows && (broken & 1024), t10.c_str()}, {history && call.kind == TEMPORAL_MOTION && (broken & 2048), t11.c_str()}});
+            }
+        for (int broken = 0; broken < 32; broken++) {
+            uint64_t n_pix = 77;
+            const Refusal r = check_frame_error_call(!(broken & 1), broken & 16 ? 65536 : 37, broken & 2 ? 0 : broken & 16 ? 65536 : 23, broken & 4 ? 1 : 16, broken & 8 ? nan : 0.1f, n_pix);
+            first_answers(r, {{(broken & 1) != 0, "pt_frame_error: null argument"}, {(broken & 2) != 0, "pt_frame_error: width and height must be >= 1"},
+                              {(broken & 4) != 0, "the standard error needs n_samples >= 2"}, {(broken & 8) != 0, "pt_frame_error: threshold must be finite and >= 0"},
+                              {(broken & 16) != 0, "more than 2^32 - 1 pixels"}});
+            if (!broken) CHECK(n_pix == 37 * 23);
+        }
+        // the values each rule turns away, and the ones at its edge that pass
+        {
+            pt_denoise_params dp = {};
+            dp.width = dp.height = 1; dp.sigma_normal = -1.0f;   // (a sigma <= 0 switches its term off)
+            for (int ok : {0, 10}) { dp.iterations = ok; CHECK(check_denoise_call(&dp, true).code == PT_OK); }
+            for (int bad : {-1, 11}) { dp.iterations = bad; CHECK(says(check_denoise_call(&dp, true), "iterations must be 0..10")); }
+            dp.iterations = 4;
+            for (float bad : {inf, -inf, nan}) {
+                for (float* s : {&dp.sigma_color, &dp.sigma_normal, &dp.sigma_position}) {
+                    const float keep = *s;
+                    *s = bad; CHECK(says(check_denoise_call(&dp, true), "a sigma is not finite"));
+                    *s = keep;
+                }
+            }
+            pt_denoise_variance_params dv = {};
+            dv.width = dv.height = 1; dv.iterations = 10; dv.samples_per_frame = 1.0f;
+            const VarianceBuffers b = {&mem[0], &mem[1], nullptr, &mem[3], &mem[4], &mem[5], &mem[0], nullptr};   // no length, no out_variance, out = color
+            CHECK(check_denoise_variance_call(&dv, b).code == PT_OK);
+            for (float bad : {inf, -inf, nan}) {
+                for (float* s : {&dv.sigma_luminance, &dv.sigma_normal, &dv.sigma_position}) {
+                    const float keep = *s;
+                    *s = bad; CHECK(says(check_denoise_variance_call(&dv, b), "a sigma is not finite"));
+                    *s = keep;
+                }
+            }
+            for (float bad : {0.0f, 0.5f, -1.0f, inf, nan}) { dv.samples_per_frame = bad; CHECK(says(check_denoise_variance_call(&dv, b), "samples_per_frame must be finite and >= 1")); }
+            dv.samples_per_frame = 1.0f;
+            for (int k = 0; k < 6; k++) {   // out_variance on each input in turn; on out it is none of them
+                VarianceBuffers v = {&mem[0], &mem[1], &mem[2], &mem[3], &mem[4], &mem[5], &mem[6], &mem[k]};
+                CHECK(says(check_denoise_variance_call(&dv, v), "out_variance_dev may not be one of the inputs"));
+                v.out_variance = v.out;
+                CHECK(check_denoise_variance_call(&dv, v).code == PT_OK);
+            }
+            pt_temporal_params tp = {};
+            pt_camera cam = {};
+            for (const auto& call : CALLS) {
+                TemporalCall a = well_formed(call.kind, &tp, &cam);
+                tp.width = tp.height = 2; tp.max_history = 1.0f; tp.plane_tolerance = 0.0f;
+                for (float ok : {-1.0f, 1.0f}) { tp.normal_threshold = ok; CHECK(check_temporal_call(call.who, a).code == PT_OK); }
+                for (float bad : {0.5f, -1.0f, inf, -inf, nan}) { tp.max_history = bad; CHECK(says(check_temporal_call(call.who, a), "max_history must be finite and >= 1")); }
+                tp.max_history = 1.0f;
+                for (float bad : {-0.5f, inf, -inf, nan}) { tp.plane_tolerance = bad; CHECK(says(check_temporal_call(call.who, a), "plane_tolerance must be finite and >= 0")); }
+                tp.plane_tolerance = 0.0f;
+                for (float bad : {-1.5f, 1.5f, inf, -inf, nan}) { tp.normal_threshold = bad; CHECK(says(check_temporal_call(call.who, a), "normal_threshold must be in -1..1")); }
+                tp.normal_threshold = 0.9f;
+                a.prev_cam = nullptr;
+                CHECK(says(check_temporal_call(call.who, a), "a history needs its camera"));
+                a.prev_cam = &cam;
+                a.out_color = (float*)a.cur_color;   // in place over the current frame is allowed
+                CHECK(check_temporal_call(call.who, a).code == PT_OK);
+                if (call.kind != TEMPORAL_MOMENTS) {
+                    a.out_length = (float*)a.prev_length;
+                    CHECK(says(check_temporal_call(call.who, a), "the new history may not overwrite"));
+                    a.out_length = &mem[8];
+                }
+                if (call.kind == TEMPORAL_COLOUR) {
+                    a.prev_id = a.cur_id = nullptr;   // ids of neither frame
+                    CHECK(check_temporal_call(call.who, a).code == PT_OK);
+                    continue;
+                }
+                a.n_tris = ((size_t)1 << 31) - 1;
+                CHECK(check_temporal_call(call.who, a).code == PT_OK);
+                a.n_tris = 0; a.prev_verts = a.cur_verts;   // no rows at all, and one buffer for both
+                CHECK(check_temporal_call(call.who, a).code == PT_OK);
+                if (call.kind == TEMPORAL_MOMENTS) {
+                    a.prev_verts = a.cur_verts = nullptr; a.prev_id = a.cur_id = nullptr;   // pt_temporal's rule: no rows, ids of neither
+                    CHECK(!temporal_reads_rows(a) && check_temporal_call(call.who, a).code == PT_OK);
+                    continue;
+                }
+                const void* const others[] = {a.prev_verts, a.prev_color, a.prev_length, a.prev_normal, a.prev_position, a.prev_id,
+                                              a.cur_color, a.cur_normal, a.cur_position, a.cur_id, a.out_color, a.out_length, a.rgba};
+                for (const void* o : others) { a.motion = (float*)o; CHECK(says(check_temporal_call(call.who, a), "motion_dev may not be one of the other buffers")); }
+                a.prev_color = nullptr;   // without a history the motion buffer is not compared
+                CHECK(check_temporal_call(call.who, a).code == PT_OK);
+            }
+            uint64_t n_pix = 0;
+            for (float bad : {-1.0f, inf, -inf, nan}) CHECK(says(check_frame_error_call(true, 37, 23, 2, bad, n_pix), "threshold must be finite and >= 0"));
+            CHECK(check_frame_error_call(true, 65537, 65535, 2, 0.0f, n_pix).code == PT_OK && n_pix == 0xffffffffull);   // 2^32 - 1 pixels
+            CHECK(says(check_frame_error_call(true, 65536, 65536, 2, 0.0f, n_pix), "more than 2^32 - 1 pixels"));
+            CHECK(says(check_frame_error_call(true, 37, -23, 2, 0.0f, n_pix), "width and height must be >= 1"));
+        }
     }
 
     // (h) pt_closest_hits / pt_any_hits: the wide walk's two budgets, the binary walk for a tree too deep

@@ -87,17 +87,19 @@ def test_null_context_is_refused_first():
 
 
 def test_the_kernels_live_beside_their_neighbours_and_restate_nothing():
-    rays, den, api, plan = (open(os.path.join(CSRC, f)).read() for f in ("pt_k_rays.hip", "pt_denoise.hip", "ptmi.hip", "pt_plan.h"))
+    rays, den, api, plan = (open(os.path.join(CSRC, f)).read() for f in ("pt_k_rays.hip", "pt_select.hip", "ptmi.hip", "pt_plan.h"))
     fold = rays[rays.index("k_fold_pixels(const KParams"):rays.index("namespace ptmi")]
     assert "rays_accumulate<HDR>(" in fold and "pt_moments(" in fold and "0.2126f" not in fold, "the fold reuses the accumulator's and the moments' device functions"
-    sel = den[den.index("struct SelectArgs"):den.index("extern \"C\" int pt_render_aux")]
+    sel = den[den.index("namespace {"):den.index("}  // namespace")]   # the file's kernels, k_frame_error among them, and what its two calls share
     assert "atomic" not in sel and "__threadfence" not in sel and "while" not in sel, "no atomics, no fences, no waiting"
-    assert sel.count("__global__") == 3 and "__builtin_amdgcn_mbcnt_hi" in sel and "__ballot(" in sel
+    assert sel.count("__global__") == 4 and "__builtin_amdgcn_mbcnt_hi" in sel and "__ballot(" in sel
+    for k in ("k_select_count(const SelectArgs", "k_select_scan(const uint32_t*", "k_select_write(const SelectArgs"):
+        assert "__global__ void __launch_bounds__(256) " + k in sel, k
     body = api[api.index("int pt_render_pixels("):api.index("int pt_get_counters(")]
     assert "launch_render_camera(" in body and "launch_fold_pixels(" in body and "launch_fold_rays" not in body
     assert "plan.samples = plan.per_launch > 1 || a.pixels;" in plan
     mk = open(os.path.join(PKG, "Makefile")).read()
-    assert len(mk.split("OBJS =")[1].split("\n")[0].split()) == 13, "no new translation unit"
+    assert len(mk.split("OBJS =")[1].split("\n")[0].split()) == 17, "no new translation unit"
 
 
 # ---------------------------------------------------------------------------------------------------- the reference, by hand

@@ -107,7 +107,7 @@ def test_check_program_walks_both_calls_rules(san):
     """The error order of pt_tonemap and pt_meter — every rule broken alone and together — and the launches of calls that pass."""
     src = open(os.path.join(CSRC, "pt_variants_check.cpp")).read()
     assert "check_tonemap_call(" in src and "check_meter_call(" in src and "plan_tonemap(" in src and "plan_meter(" in src
-    den = open(os.path.join(CSRC, "pt_denoise.hip")).read()
+    den = open(os.path.join(CSRC, "pt_display.hip")).read()
     assert "check_tonemap_call(tp," in den and "check_meter_call(mp," in den, "the entry points ask the rules the check program runs"
     exe = os.path.join(CSRC, "pt_variants_check")
     build = subprocess.run(["make", "-B", "-C", PKG, "variants_check"] + ([san] if san else []), capture_output=True, text=True, timeout=300)
@@ -118,10 +118,10 @@ def test_check_program_walks_both_calls_rules(san):
     assert "all checks hold" in run.stdout and "FAILED" not in run.stdout
 
 
-def test_kernels_sit_above_the_selection_and_stage_the_table():
-    den = open(os.path.join(CSRC, "pt_denoise.hip")).read()
-    assert den.index("k_tonemap(const ToneArgs") < den.index("struct SelectArgs") and den.index("k_meter_finish(const MeterArgs") < den.index("struct SelectArgs")
-    body = den[den.index("struct ToneArgs"):den.index("struct SelectArgs")]
+def test_kernels_use_no_transcendental_and_stage_the_table():
+    den = open(os.path.join(CSRC, "pt_display.hip")).read()
+    body = den[den.index("struct ToneArgs"):den.index("}  // namespace")]   # the device part: every kernel of the file
+    assert "k_tonemap(const ToneArgs" in body and "k_meter_finish(const MeterArgs" in body
     assert "pt_pack_rgba(r, g, b)" in body, "LINEAR calls the pack of pt_render's words"
     assert "powf" not in body and "exp2" not in body and "log2" not in body and "fmaf" not in body
     assert "__shared__ float s_T[256]" in body and "pt_sld4(" in body and "make_uint4(" in body
