@@ -189,6 +189,9 @@ PTMI_SYMBOLS = [
     ("pt_temporal_motion", _i, [_vp, C.POINTER(TemporalParams), C.POINTER(Camera), _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                 _vp]),
     ("pt_temporal_moments", _i, [_vp, C.POINTER(TemporalParams), C.POINTER(Camera), _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("pt_render_aux_camera", _i, [_vp, C.POINTER(Camera), C.POINTER(CameraModel), C.POINTER(Params), _vp, _vp, _vp, _vp]),
+    ("pt_temporal_camera", _i, [_vp, C.POINTER(TemporalParams), C.POINTER(Camera), C.POINTER(CameraModel), _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                _vp, _vp, _vp, _vp, _vp, _vp]),
     ("pt_build_bvh", _i, [_vp, _vp, C.c_size_t, _vp, C.c_size_t]),
     ("pt_last_build_ms", _i, [_vp, C.POINTER(C.c_float)]),
     ("pt_refit_bvh", _i, [_vp, _vp, _sz, _vp]),

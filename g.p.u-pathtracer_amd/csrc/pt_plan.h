@@ -76,6 +76,10 @@ inline Refusal check_camera_model(const std::string& who, const pt_camera_model&
     }
     return {};
 }
+// ... asked for the model's whole image: n = width * height from pixel 0 (pt_render_aux_camera, pt_temporal_camera)
+inline Refusal check_camera_model_image(const std::string& who, const pt_camera_model& cm) {
+    return check_camera_model(who, cm, (uint64_t)(cm.width > 0 ? cm.width : 0) * (uint64_t)(cm.height > 0 ? cm.height : 0), 0, false, true);
+}
 
 // ---- the argument rules of pt_render, pt_render_rays, pt_render_camera and pt_render_pixels, each call's in its own order and wording
 inline Refusal check_path_call(const CtxFacts& f, const CallFacts& a) {
@@ -487,6 +491,15 @@ inline Refusal check_aux_call(const CtxFacts& f, const pt_params* p, bool buffer
     if (f.records_woop) return {PT_ERR_UNSUPPORTED, "pt_render_aux: the binary walk reads Moller-Trumbore records (upload with PT_OPT_TRI_TEST 0)"};
     return {};
 }
+// pt_render_aux_camera; buffers: cam and the three guide buffers are given.  The image is cm's, checked whole as pt_render_pixels' is
+inline Refusal check_aux_camera_call(const CtxFacts& f, const pt_camera_model* cm, const pt_params* p, bool buffers) {
+    if (!buffers || !cm || !p) return {PT_ERR_INVALID, "pt_render_aux_camera: null argument"};
+    const Refusal r = check_camera_model_image("pt_render_aux_camera", *cm);
+    if (r.code != PT_OK) return r;
+    if (!f.has_bvh) return {PT_ERR_NO_SCENE, "pt_render_aux_camera: no BVH uploaded"};
+    if (f.records_woop) return {PT_ERR_UNSUPPORTED, "pt_render_aux_camera: the binary walk reads Moller-Trumbore records (upload with PT_OPT_TRI_TEST 0)"};
+    return {};
+}
 // buffers: the colour, the three guide buffers and out are given
 inline Refusal check_denoise_call(const pt_denoise_params* dp, bool buffers) {
     if (!dp || !buffers) return {PT_ERR_INVALID, "pt_denoise: null argument"};
@@ -511,9 +524,10 @@ inline Refusal check_denoise_variance_call(const pt_denoise_variance_params* dp,
             if (in == b.out_variance) return {PT_ERR_INVALID, "pt_denoise_variance: out_variance_dev may not be one of the inputs"};
     return {};
 }
-// What the caller of pt_temporal, pt_temporal_motion (rows, motion) or pt_temporal_moments (rows; the buffers named *_color hold its
-// moments, and it has no out_length, no rgba) passed; a pointer the call does not have stays null
-enum TemporalKind { TEMPORAL_COLOUR, TEMPORAL_MOTION, TEMPORAL_MOMENTS };
+// What the caller of pt_temporal, pt_temporal_motion (rows, motion), pt_temporal_moments (rows; the buffers named *_color hold its
+// moments, and it has no out_length, no rgba) or pt_temporal_camera (rows where given, motion, the previous camera's model) passed; a
+// pointer the call does not have stays null
+enum TemporalKind { TEMPORAL_COLOUR, TEMPORAL_MOTION, TEMPORAL_MOMENTS, TEMPORAL_CAMERA };
 struct TemporalCall {
     TemporalKind kind;
     const pt_temporal_params* tp;
@@ -527,10 +541,13 @@ struct TemporalCall {
     const float *prev_verts, *cur_verts;   // the vertex rows by triangle id
     size_t n_tris;
     float* motion;
+    const pt_camera_model* prev_cm;        // pt_temporal_camera
 };
 // a history: prev_color is given.  rows: the call finds moved triangles' points in the vertex rows (pt_temporal_motion always,
-// pt_temporal_moments where a row buffer is given)
-inline bool temporal_reads_rows(const TemporalCall& a) { return a.kind == TEMPORAL_MOTION || (a.kind == TEMPORAL_MOMENTS && (a.prev_verts || a.cur_verts)); }
+// pt_temporal_moments and pt_temporal_camera where a row buffer is given)
+inline bool temporal_reads_rows(const TemporalCall& a) {
+    return a.kind == TEMPORAL_MOTION || ((a.kind == TEMPORAL_MOMENTS || a.kind == TEMPORAL_CAMERA) && (a.prev_verts || a.cur_verts));
+}
 inline Refusal check_temporal_call(const std::string& who, const TemporalCall& a) {
     const bool with_length = a.kind != TEMPORAL_MOMENTS;
     const pt_temporal_params* tp = a.tp;
@@ -541,13 +558,22 @@ inline Refusal check_temporal_call(const std::string& who, const TemporalCall& a
     if (!(tp->normal_threshold >= -1.f && tp->normal_threshold <= 1.f)) return {PT_ERR_INVALID, who + ": normal_threshold must be in -1..1"};
     if (!a.prev_color) return {};
     if (!a.prev_cam || !a.prev_length || !a.prev_normal || !a.prev_position) return {PT_ERR_INVALID, who + ": a history needs its camera, lengths, normals and positions"};
+    if (a.kind == TEMPORAL_CAMERA) {   // the model the history was rendered under: its own rules, and the image of the parameters
+        if (!a.prev_cm) return {PT_ERR_INVALID, who + ": a history needs the model of its camera"};
+        const pt_camera_model* prev_cm = a.prev_cm;   // (host memory, as tp)
+        const pt_camera_model& cm = *prev_cm;
+        const Refusal r = check_camera_model_image(who, cm);
+        if (r.code != PT_OK) return r;
+        if (cm.width != tp->width || cm.height != tp->height) return {PT_ERR_INVALID, who + ": the model's image must be the parameters' (prev_cm->width, height)"};
+    }
     if ((a.prev_id == nullptr) != (a.cur_id == nullptr)) return {PT_ERR_INVALID, who + ": ids of both frames or of neither"};
     if (a.out_color == a.prev_color || (with_length && a.out_length == a.prev_length))
         return {PT_ERR_INVALID, who + ": the new history may not overwrite the old one (ping-pong the buffers)"};
-    if (!temporal_reads_rows(a)) return {};
-    if (!a.prev_id || !a.cur_id) return {PT_ERR_INVALID, who + ": the ids of both frames are required (they choose the vertex rows)"};
-    if (a.n_tris > 0 && (!a.prev_verts || !a.cur_verts)) return {PT_ERR_INVALID, who + ": a null vertex buffer with n_tris > 0"};
-    if (a.n_tris >= ((size_t)1 << 31)) return {PT_ERR_INVALID, who + ": n_tris must be < 2^31 (ids are int32)"};
+    if (temporal_reads_rows(a)) {
+        if (!a.prev_id || !a.cur_id) return {PT_ERR_INVALID, who + ": the ids of both frames are required (they choose the vertex rows)"};
+        if (a.n_tris > 0 && (!a.prev_verts || !a.cur_verts)) return {PT_ERR_INVALID, who + ": a null vertex buffer with n_tris > 0"};
+        if (a.n_tris >= ((size_t)1 << 31)) return {PT_ERR_INVALID, who + ": n_tris must be < 2^31 (ids are int32)"};
+    }
     const void* const others[] = {a.prev_verts, a.cur_verts, a.prev_color, a.prev_length, a.prev_normal, a.prev_position, a.prev_id,
                                   a.cur_color, a.cur_normal, a.cur_position, a.cur_id, a.out_color, a.out_length, a.rgba};
     if (a.motion)

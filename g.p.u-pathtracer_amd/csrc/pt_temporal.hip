@@ -1,7 +1,7 @@
 // pt_temporal.hip — the history of earlier frames reprojected into a new one: pt_temporal (include/ptmi.h states the
 // arithmetic, tests/temporal_ref.py restates it), pt_temporal_motion (the same for triangles moved by pt_refit_bvh, §10 f14;
-// tests/motion_ref.py) and pt_temporal_moments (the luminance moments reprojected as the colour is, §10 f15).  One translation unit
-// of libptmi.so (pt_ctx.h).
+// tests/motion_ref.py), pt_temporal_moments (the luminance moments reprojected as the colour is, §10 f15) and pt_temporal_camera
+// (the history of any of the five camera models, §10 f20).  One translation unit of libptmi.so (pt_ctx.h).
 //   k_temporal<IDS>  one lane per pixel in 16x16 tiles; the current hit point projected into the previous camera, up to four
 //                    bilinear taps of the history — per tap the id (when given) first, then normal and position as one dwordx4
 //                    each, colour and length only for a tap that passed every test; no LDS (neighbouring lanes share their taps
@@ -13,6 +13,8 @@
 //                    projected and tested (+ the motion, when asked for)
 //   k_temporal_moments<IDS, MOVED>  tm_pixel with the (m1, m2) payload — pt_temporal's rule (MOVED 0) or pt_temporal_motion's
 //                    (MOVED 1, also the launch without a history); no length, no display word
+//   k_temporal_camera<IDS, MOVED>  tm_pixel with the projection of the previous camera's MODEL (pt_temporal_camera, §10 f20): the
+//                    inverses of pt_camera_model.h's five models, the model a value of the launch; rows where the caller gave them
 #include <cmath>
 #include <cstring>
 
@@ -71,13 +73,56 @@ __device__ __forceinline__ bool tm_same_bits(const v3& a, const v3& b) {
 }
 __device__ __forceinline__ bool tm_positive_finite(float a) { return a > 0.f && a < INFINITY; }
 
+// Where the previous camera saw a point, v = x' - pos, in the two steps tm_pixel takes: depth(v), which must be > 0 or the history is
+// rejected, and at(v, depth), the history coordinates (fx, fy) — not finite where the model rejects behind that.  TmPinhole is step 2
+// of pt_temporal, the statements tm_pixel held before its projection became a parameter.
+struct TmPinhole {
+    __device__ __forceinline__ float depth(const TmArgs& A, const v3& v) const { return vdot(v, V3(A.front[0], A.front[1], A.front[2])); }
+    __device__ __forceinline__ float2 at(const TmArgs& A, const v3& v, float a) const {
+        const float fx = fmaf(vdot(v, V3(A.right[0], A.right[1], A.right[2])) / a, A.sx, A.cx);
+        const float fy = fmaf(vdot(v, V3(A.up[0], A.up[1], A.up[2])) / a, A.sy, A.cy);
+        return make_float2(fx, fy);
+    }
+};
+// The inverses of the five camera models (pt_camera_model.h; include/ptmi.h states them under pt_temporal_camera), the model a value
+// of the launch: a scalar branch.  sx, sy, cx, cy hold the model's host constants (temporal_args).  The two models of all directions
+// have no depth test (1 passes it); what they reject comes back as NaN coordinates.
+struct TmModel {
+    int model;
+    __device__ __forceinline__ bool angular() const { return model == PT_CAM_FISHEYE || model == PT_CAM_EQUIRECT; }
+    __device__ __forceinline__ float depth(const TmArgs& A, const v3& v) const { return angular() ? 1.0f : TmPinhole().depth(A, v); }
+    __device__ __forceinline__ float2 at(const TmArgs& A, const v3& v, float a) const {
+        if (model == PT_CAM_PINHOLE || model == PT_CAM_THIN_LENS) return TmPinhole().at(A, v, a);
+        const float b = vdot(v, V3(A.right[0], A.right[1], A.right[2]));
+        const float c = vdot(v, V3(A.up[0], A.up[1], A.up[2]));
+        if (model == PT_CAM_ORTHO) return make_float2(fmaf(b, A.sx, A.cx), fmaf(c, A.sy, A.cy));   // sx = W / (ortho_height * aspect), sy = H / ortho_height
+        a = TmPinhole().depth(A, v);
+        const float nan = __uint_as_float(0x7fc00000u);
+        if (model == PT_CAM_FISHEYE) {   // sx = (min(W, H) / 2) / half, sy = half = fisheye_fov / 2
+            const float s = sqrtf(fmaf(c, c, b * b));
+            const float theta = atan2f(s, a);
+            if ((a == 0.f && s == 0.f) || theta > A.sy) return make_float2(nan, nan);
+            const float rho = theta * A.sx;
+            const float k = s > 0.f ? rho / s : 0.f;
+            return make_float2(fmaf(b, k, A.cx), fmaf(c, k, A.cy));
+        }
+        // PT_CAM_EQUIRECT: sx = W / 2 pi, sy = H / pi, cx = W / 2, cy = H / 2 (an integer coordinate is a texel centre)
+        const float h = sqrtf(fmaf(b, b, a * a));
+        if (h == 0.f && c == 0.f) return make_float2(nan, nan);
+        return make_float2(fmaf(atan2f(b, a), A.sx, A.cx), fmaf(atan2f(c, h), A.sy, A.cy));
+    }
+};
+
 // One pixel of k_temporal (MOVED 0: M unused, and nothing below differs from what the kernel held before the two shared it) and
 // of k_temporal_motion (MOVED 1; 2 = the motion is written as well).  The projection, the taps and the blend are the same
 // statements for both, so a surface point that did not move gets k_temporal<true>'s bits.
 // PAY 3: the payload is the colour.  PAY 2 (pt_temporal_moments): the buffers named *_color hold (m1, m2) rows, the blend runs on
 // those two, and neither a length nor a display word is written; every other statement is shared.
-template <bool IDS, int MOVED, int PAY = 3>
-__device__ __forceinline__ void tm_pixel(const TmArgs& A, const TmMotionArgs* M) {
+// PROJ: where the previous camera saw the point (above).  MOVED 3 (k_temporal_camera only): MOVED 0's static point with MOVED 2's
+// motion written — ROWS and MOTION below are what MOVED 0, 1, 2 always meant.
+template <bool IDS, int MOVED, int PAY = 3, class PROJ = TmPinhole>
+__device__ __forceinline__ void tm_pixel(const TmArgs& A, const TmMotionArgs* M, const PROJ proj = PROJ()) {
+    constexpr bool ROWS = MOVED == 1 || MOVED == 2, MOTION = MOVED >= 2;
     int x, y;
     if (!ptd_pixel(A, x, y)) return;
     const size_t p = (size_t)y * (size_t)A.W + (size_t)x;
@@ -92,7 +137,7 @@ __device__ __forceinline__ void tm_pixel(const TmArgs& A, const TmMotionArgs* M)
         v3 np = V3(n4.x, n4.y, n4.z), xp = V3(x4.x, x4.y, x4.z);
         int idm = 0;
         bool was = true;   // the point has a place in the previous frame's scene: (xp, np) become (x', n')
-        if constexpr (MOVED != 0) {
+        if constexpr (ROWS) {
             idm = A.cur_id[p];
             if (idm >= 0) {
                 was = (uint32_t)idm < M->n_tris;   // past the rows: no history, and no row is read
@@ -119,11 +164,11 @@ __device__ __forceinline__ void tm_pixel(const TmArgs& A, const TmMotionArgs* M)
             }
         }
         const v3 v = vsub(xp, V3(A.pos[0], A.pos[1], A.pos[2]));
-        const float a = vdot(v, V3(A.front[0], A.front[1], A.front[2]));
-        if (a > 0.f && (MOVED == 0 || was)) {
-            const float fx = fmaf(vdot(v, V3(A.right[0], A.right[1], A.right[2])) / a, A.sx, A.cx);
-            const float fy = fmaf(vdot(v, V3(A.up[0], A.up[1], A.up[2])) / a, A.sy, A.cy);
-            if constexpr (MOVED == 2) {
+        const float a = proj.depth(A, v);
+        if (a > 0.f && (!ROWS || was)) {
+            const float2 f = proj.at(A, v, a);
+            const float fx = f.x, fy = f.y;
+            if constexpr (MOTION) {
                 if (fabsf(fx) < INFINITY && fabsf(fy) < INFINITY) { mx = fx - (float)x; my = fy - (float)y; }
             }
             // outside (-1, W) x (-1, H) no tap is inside the image; NaN and infinities fail here too, before the conversion to int
@@ -133,7 +178,7 @@ __device__ __forceinline__ void tm_pixel(const TmArgs& A, const TmMotionArgs* M)
                 const int x0 = (int)x0f, y0 = (int)y0f;
                 const float tol = A.plane_tol * x4.w;
                 int idp = 0;
-                if constexpr (MOVED != 0) idp = idm;
+                if constexpr (ROWS) idp = idm;
                 else if (IDS) idp = A.cur_id[p];
                 float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sl = 0.f;
 #pragma unroll
@@ -176,7 +221,7 @@ __device__ __forceinline__ void tm_pixel(const TmArgs& A, const TmMotionArgs* M)
     A.out_color[3 * p] = o0; A.out_color[3 * p + 1] = o1; A.out_color[3 * p + 2] = o2;
     A.out_len[p] = on;
     if (A.rgba) A.rgba[p] = pt_pack_rgba(o0, o1, o2);
-    if constexpr (MOVED == 2) M->motion[p] = make_float2(mx, my);
+    if constexpr (MOTION) M->motion[p] = make_float2(mx, my);
 }
 
 template <bool IDS>
@@ -198,9 +243,20 @@ __global__ void __launch_bounds__(PTD_BLOCK) k_temporal_moments(const TmMotionAr
     tm_pixel<IDS, MOVED, 2>(M.t, &M);
 }
 
+// tm_pixel under the previous camera's model (pt_temporal_camera).  MOVED 0: no rows, IDS as k_temporal; 3: the same with the motion
+// written (also the launch without a history: every pixel as a miss, motion 0); 1, 2: k_temporal_motion's rows.
+struct TmCameraArgs {
+    TmMotionArgs m;
+    int model;
+};
+template <bool IDS, int MOVED>
+__global__ void __launch_bounds__(PTD_BLOCK) k_temporal_camera(const TmCameraArgs C) {
+    tm_pixel<IDS, MOVED, 3>(C.m.t, &C.m, TmModel{C.model});
+}
+
 using namespace ptmi;
 
-// What the three calls share: the argument rules (check_temporal_call, pt_plan.h, under the caller's name `fn`) and the kernel
+// What the four calls share: the argument rules (check_temporal_call, pt_plan.h, under the caller's name `fn`) and the kernel
 // arguments of the reprojection, with the vertex rows where the call reads them.  PT_OK with M filled, or the error already recorded.
 int temporal_args(pt_ctx* c, const char* fn, const TemporalCall& a, TmMotionArgs& M) {
     const Refusal r = check_temporal_call(fn, a);
@@ -232,6 +288,27 @@ int temporal_args(pt_ctx* c, const char* fn, const TemporalCall& a, TmMotionArgs
     A.sy = (float)(tp->height - 1) / prev_cam->fov;
     A.cx = (float)tp->width / 2.0f - 0.5f;
     A.cy = (float)tp->height / 2.0f - 0.5f;
+    if (a.kind == TEMPORAL_CAMERA) {   // ... or of pt_model_ray's (TmModel reads these four)
+        const pt_camera_model& cm = *a.prev_cm;
+        const float W = (float)tp->width, H = (float)tp->height;
+        switch (cm.model) {
+        case PT_CAM_ORTHO:
+            A.sx = W / (cm.ortho_height * prev_cam->aspect);
+            A.sy = H / cm.ortho_height;
+            break;
+        case PT_CAM_FISHEYE:
+            A.sy = cm.fisheye_fov / 2.0f;
+            A.sx = ((float)std::min(tp->width, tp->height) / 2.0f) / A.sy;
+            break;
+        case PT_CAM_EQUIRECT:
+            A.sx = W / 6.28318548f;
+            A.sy = H / 3.14159274f;
+            A.cx = W / 2.0f;
+            A.cy = H / 2.0f;
+            break;
+        default: break;   // the pinhole and the thin lens: every guide ray passes through pos along dir0
+        }
+    }
     A.max_history = tp->max_history;
     A.plane_tol = tp->plane_tolerance;
     A.normal_thr = tp->normal_threshold;
@@ -325,6 +402,41 @@ extern "C" int pt_temporal_moments(pt_ctx* c, const pt_temporal_params* tp, cons
     if (!history || motion) hipLaunchKernelGGL((k_temporal_moments<true, 1>), grid, dim3(PTD_BLOCK), 0, st, M);   // (no history: out = cur)
     else if (M.t.prev_id) hipLaunchKernelGGL((k_temporal_moments<true, 0>), grid, dim3(PTD_BLOCK), 0, st, M);
     else hipLaunchKernelGGL((k_temporal_moments<false, 0>), grid, dim3(PTD_BLOCK), 0, st, M);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, span_end(c));
+    return PT_OK;
+}
+
+extern "C" int pt_temporal_camera(pt_ctx* c, const pt_temporal_params* tp, const pt_camera* prev_cam, const pt_camera_model* prev_cm,
+                                  const float* prev_verts_dev, const float* cur_verts_dev, size_t n_tris, const float* prev_color_dev,
+                                  const float* prev_length_dev, const float* prev_normal_dev, const float* prev_position_dev,
+                                  const int32_t* prev_id_dev, const float* cur_color_dev, const float* cur_normal_dev,
+                                  const float* cur_position_dev, const int32_t* cur_id_dev, float* out_color_dev, float* out_length_dev,
+                                  uint32_t* rgba_dev, float* motion_dev) {
+    if (!c) return fail(nullptr, PT_ERR_INVALID, "null ctx");
+    TemporalCall a = {};
+    a.kind = TEMPORAL_CAMERA;
+    a.tp = tp; a.prev_cam = prev_cam; a.prev_cm = prev_cm;
+    a.prev_color = prev_color_dev; a.prev_length = prev_length_dev; a.prev_normal = prev_normal_dev; a.prev_position = prev_position_dev; a.prev_id = prev_id_dev;
+    a.cur_color = cur_color_dev; a.cur_normal = cur_normal_dev; a.cur_position = cur_position_dev; a.cur_id = cur_id_dev;
+    a.out_color = out_color_dev; a.out_length = out_length_dev; a.rgba = rgba_dev;
+    a.prev_verts = prev_verts_dev; a.cur_verts = cur_verts_dev; a.n_tris = n_tris; a.motion = motion_dev;
+    TmCameraArgs C;
+    if (int rc = temporal_args(c, "pt_temporal_camera", a, C.m)) return rc;
+    const bool history = prev_color_dev != nullptr, rows = temporal_reads_rows(a), ids = C.m.t.prev_id != nullptr;
+    C.model = history ? prev_cm->model : PT_CAM_PINHOLE;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const dim3 grid = ptd_grid(tp->width, tp->height), block(PTD_BLOCK);
+    hipStream_t st = c->stream;
+    HIP_TRY(c, span_begin(c));
+    if (!history && !motion_dev) hipLaunchKernelGGL(k_tm_first, grid, block, 0, st, C.m.t);
+    else if (!history) hipLaunchKernelGGL((k_temporal_camera<false, 3>), grid, block, 0, st, C);   // out = cur, motion 0
+    else if (rows && motion_dev) hipLaunchKernelGGL((k_temporal_camera<true, 2>), grid, block, 0, st, C);
+    else if (rows) hipLaunchKernelGGL((k_temporal_camera<true, 1>), grid, block, 0, st, C);
+    else if (motion_dev && ids) hipLaunchKernelGGL((k_temporal_camera<true, 3>), grid, block, 0, st, C);
+    else if (motion_dev) hipLaunchKernelGGL((k_temporal_camera<false, 3>), grid, block, 0, st, C);
+    else if (ids) hipLaunchKernelGGL((k_temporal_camera<true, 0>), grid, block, 0, st, C);
+    else hipLaunchKernelGGL((k_temporal_camera<false, 0>), grid, block, 0, st, C);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, span_end(c));
     return PT_OK;

@@ -82,6 +82,8 @@ static struct { const char* text; int code; long seen; } REFUSALS[] = {
     {"the ids of both frames are required", PT_ERR_INVALID, 0}, {"a null vertex buffer with n_tris > 0", PT_ERR_INVALID, 0},
     {"n_tris must be < 2^31", PT_ERR_INVALID, 0}, {"motion_dev may not be one of the other buffers", PT_ERR_INVALID, 0},
     {"the standard error needs n_samples >= 2", PT_ERR_INVALID, 0}, {"more than 2^32 - 1 pixels", PT_ERR_INVALID, 0},
+    // pt_temporal_camera's own (pt_render_aux_camera's are pt_render_aux's and check_camera_model's)
+    {"a history needs the model of its camera", PT_ERR_INVALID, 0}, {"the model's image must be the parameters'", PT_ERR_INVALID, 0},
 };
 static long n_refused = 0, n_planned = 0;
 // true: the planner refused the call or found nothing to do in it
@@ -653,7 +655,7 @@ int main() {
         for (float bad : {-0.5f, 1.5f, nan}) { mp.adapt = bad; CHECK(says(check_meter_call(&mp, true, n_pix), "adapt must be in 0..1")); }
     }
 
-    // (g5) pt_render_aux, pt_denoise, pt_denoise_variance, the three reprojections and pt_frame_error: every rule broken alone and together
+    // (g5) pt_render_aux, pt_render_aux_camera, pt_denoise, pt_denoise_variance, the four reprojections and pt_frame_error: every rule broken alone and together
     // (the first in the header's order answers), a well-formed call passes, and the values each rule names.  The "device" pointers
     // are addresses of host words that nothing reads.
     {
@@ -682,6 +684,21 @@ int main() {
                           {{(broken & 17) != 0, "pt_render_aux: null argument"}, {(broken & 2) != 0, "pt_render_aux: width and height must be >= 1"},
                            {(broken & 4) != 0, "pt_render_aux: no BVH uploaded"}, {(broken & 8) != 0, "the binary walk reads Moller-Trumbore records"}});
         }
+        // pt_render_aux_camera: the model's rules (the image is cm's; p's width and height are not read) between the pointers and the scene
+        for (int broken = 0; broken < 512; broken++) {
+            pt_params p = {};
+            pt_camera_model cm = {};
+            cm.model = broken & 2 ? 5 : PT_CAM_FISHEYE; cm.flags = broken & 4 ? 2 : PT_CAMF_CENTRE;
+            cm.width = broken & 8 ? 1 : 37; cm.height = 23;
+            cm.fisheye_fov = broken & 16 ? 7.0f : 3.0f;
+            cm.lens_radius = -1.0f;   // another model's parameter: ignored
+            const CtxFacts f = scene(broken & 32 ? NO_TREE : broken & 64 ? TREE_WOOP : TREE, SPHERES[1], MATS[0], ENV_NONE);
+            first_answers(check_aux_camera_call(f, broken & 128 ? nullptr : &cm, broken & 256 ? nullptr : &p, !(broken & 1)),
+                          {{(broken & (1 | 128 | 256)) != 0, "pt_render_aux_camera: null argument"}, {(broken & 2) != 0, "pt_render_aux_camera: unknown camera model"},
+                           {(broken & 4) != 0, "pt_render_aux_camera: unknown flag bits"}, {(broken & 8) != 0, "pt_render_aux_camera: width and height must be >= 2"},
+                           {(broken & 16) != 0, "pt_render_aux_camera: fisheye_fov must be in"}, {(broken & 32) != 0, "pt_render_aux_camera: no BVH uploaded"},
+                           {(broken & 64) != 0, "pt_render_aux_camera: the binary walk reads Moller-Trumbore records"}});
+        }
         for (int broken = 0; broken < 32; broken++) {
             pt_denoise_params dp = {};
             dp.width = broken & 2 ? 0 : 37; dp.height = 23; dp.iterations = broken & 4 ? 11 : 4;
@@ -702,8 +719,12 @@ int main() {
                            {(broken & 64) != 0, "out_variance_dev may not be one of the inputs"}});
         }
         // the reprojections: bit 8192 takes the history away, and with it every rule behind the parameters'
-        const struct { TemporalKind kind; const char* who; } CALLS[] = {{TEMPORAL_COLOUR, "pt_temporal"}, {TEMPORAL_MOTION, "pt_temporal_motion"}, {TEMPORAL_MOMENTS, "pt_temporal_moments"}};
+        const struct { TemporalKind kind; const char* who; } CALLS[] = {{TEMPORAL_COLOUR, "pt_temporal"}, {TEMPORAL_MOTION, "pt_temporal_motion"}, {TEMPORAL_MOMENTS, "pt_temporal_moments"},
+                                                                        {TEMPORAL_CAMERA, "pt_temporal_camera"}};
+        static pt_camera_model model;   // pt_temporal_camera's: an equirectangular 37 x 23 image, as the parameters'
         auto well_formed = [&](TemporalKind kind, pt_temporal_params* tp, pt_camera* cam) {
+            model = {};
+            model.model = PT_CAM_EQUIRECT; model.width = 37; model.height = 23;
             tp->width = 37; tp->height = 23; tp->max_history = 32.0f; tp->plane_tolerance = 0.02f; tp->normal_threshold = 0.9f;
             TemporalCall a = {};
             a.kind = kind; a.tp = tp; a.prev_cam = cam;
@@ -712,7 +733,8 @@ int main() {
             a.out_color = &mem[7];
             if (kind != TEMPORAL_MOMENTS) { a.out_length = &mem[8]; a.rgba = &words[0]; }
             if (kind != TEMPORAL_COLOUR) { a.prev_verts = &mem[9]; a.cur_verts = &mem[10]; a.n_tris = 5; }
-            if (kind == TEMPORAL_MOTION) a.motion = &mem[11];
+            if (kind == TEMPORAL_MOTION || kind == TEMPORAL_CAMERA) a.motion = &mem[11];
+            if (kind == TEMPORAL_CAMERA) a.prev_cm = &model;
             return a;
         };
         for (const auto& call : CALLS)
@@ -732,7 +754,8 @@ int main() {
                 if (broken & 128) a.out_color = (float*)a.prev_color;
                 if (broken & 512) a.prev_verts = nullptr;        // (the colour call has no rows: these three change nothing there)
                 if (broken & 1024) a.n_tris = (size_t)1 << 31;
-                if (broken & 2048 && call.kind == TEMPORAL_MOTION) a.motion = (float*)a.rgba;
+                const bool has_motion = call.kind == TEMPORAL_MOTION || call.kind == TEMPORAL_CAMERA;
+                if (broken & 2048 && has_motion) a.motion = (float*)a.rgba;
                 if (broken & 4096) a.tp = nullptr;
                 if (!history) a.prev_color = nullptr;
                 const std::string who = std::string(call.who) + ": ";
@@ -745,8 +768,49 @@ int main() {
                               {{(broken & (1 | 4096)) != 0, t0.c_str()}, {(broken & 2) != 0, t1.c_str()}, {(broken & 4) != 0, t2.c_str()}, {(broken & 8) != 0, t3.c_str()},
                                {(broken & 16) != 0, t4.c_str()}, {history && (broken & 32), t5.c_str()}, {history && (broken & 64) && !(broken & 256), t6.c_str()},
                                {history && (broken & 128), t7.c_str()}, {history && rows && (broken & 256), t8.c_str()}, {history && rows && (broken & 512), t9.c_str()},
-                               {history && rows && (broken & 1024), t10.c_str()}, {history && call.kind == TEMPORAL_MOTION && (broken & 2048), t11.c_str()}});
+                               {history && rows && (broken & 1024), t10.c_str()}, {history && has_motion && (broken & 2048), t11.c_str()}});
             }
+        // pt_temporal_camera's own rules, between the history's pointers and the ids: a model, the model's rules, the parameters' image; without
+        // rows the ids of neither frame pass and the motion buffer is still compared
+        for (int broken = 0; broken < 512; broken++) {
+            pt_temporal_params tp = {};
+            pt_camera cam = {};
+            TemporalCall a = well_formed(TEMPORAL_CAMERA, &tp, &cam);
+            const bool history = !(broken & 256);
+            if (broken & 1) a.prev_position = nullptr;
+            if (broken & 2) a.prev_cm = nullptr;
+            if (broken & 8) { model.model = PT_CAM_ORTHO; model.ortho_height = 0.0f; }
+            if (broken & 4) model.model = -1;
+            if (broken & 16) model.height = 24;
+            if (broken & 32) a.prev_id = nullptr;
+            if (broken & 64) { a.prev_verts = a.cur_verts = nullptr; a.n_tris = (size_t)1 << 40; }   // no rows: n_tris is ignored
+            if (broken & 128) a.motion = (float*)a.cur_normal;
+            if (!history) a.prev_color = nullptr;
+            first_answers(check_temporal_call("pt_temporal_camera", a),
+                          {{history && (broken & 1), "pt_temporal_camera: a history needs its camera, lengths"}, {history && (broken & 2), "pt_temporal_camera: a history needs the model of its camera"},
+                           {history && (broken & 4), "pt_temporal_camera: unknown camera model"}, {history && (broken & 8) && !(broken & 4), "pt_temporal_camera: ortho_height must be finite"},
+                           {history && (broken & 16), "pt_temporal_camera: the model's image must be the parameters'"}, {history && (broken & 32), "pt_temporal_camera: ids of both frames or of neither"},
+                           {history && (broken & 128), "pt_temporal_camera: motion_dev may not be one of the other buffers"}});
+        }
+        {   // without rows the ids of neither frame pass; with rows they are required
+            pt_temporal_params tp = {};
+            pt_camera cam = {};
+            TemporalCall a = well_formed(TEMPORAL_CAMERA, &tp, &cam);
+            a.prev_id = a.cur_id = nullptr;
+            CHECK(temporal_reads_rows(a) && says(check_temporal_call("pt_temporal_camera", a), "the ids of both frames are required"));
+            a.prev_verts = a.cur_verts = nullptr;
+            CHECK(!temporal_reads_rows(a) && check_temporal_call("pt_temporal_camera", a).code == PT_OK);
+            a.cur_verts = &mem[10];   // one row buffer: rows are read, and both are needed
+            a.prev_id = &ids[0]; a.cur_id = &ids[1];
+            CHECK(temporal_reads_rows(a) && says(check_temporal_call("pt_temporal_camera", a), "a null vertex buffer with n_tris > 0"));
+            for (int m = PT_CAM_PINHOLE; m <= PT_CAM_EQUIRECT; m++) {   // every model, with the parameters of the others out of range
+                a = well_formed(TEMPORAL_CAMERA, &tp, &cam);
+                model.model = m;
+                model.lens_radius = m == PT_CAM_THIN_LENS ? 0.5f : -1.0f; model.focus_dist = m == PT_CAM_THIN_LENS ? 35.0f : 0.0f;
+                model.ortho_height = m == PT_CAM_ORTHO ? 30.0f : -1.0f; model.fisheye_fov = m == PT_CAM_FISHEYE ? 6.28318548f : 9.0f;
+                CHECK(check_temporal_call("pt_temporal_camera", a).code == PT_OK);
+            }
+        }
         for (int broken = 0; broken < 32; broken++) {
             uint64_t n_pix = 77;
             const Refusal r = check_frame_error_call(!(broken & 1), broken & 16 ? 65536 : 37, broken & 2 ? 0 : broken & 16 ? 65536 : 23, broken & 4 ? 1 : 16, broken & 8 ? nan : 0.1f, n_pix);
@@ -793,6 +857,7 @@ int main() {
             for (const auto& call : CALLS) {
                 TemporalCall a = well_formed(call.kind, &tp, &cam);
                 tp.width = tp.height = 2; tp.max_history = 1.0f; tp.plane_tolerance = 0.0f;
+                model.width = model.height = 2;
                 for (float ok : {-1.0f, 1.0f}) { tp.normal_threshold = ok; CHECK(check_temporal_call(call.who, a).code == PT_OK); }
                 for (float bad : {0.5f, -1.0f, inf, -inf, nan}) { tp.max_history = bad; CHECK(says(check_temporal_call(call.who, a), "max_history must be finite and >= 1")); }
                 tp.max_history = 1.0f;

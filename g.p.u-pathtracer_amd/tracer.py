@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import Camera, Counters, DenoiseParams, DenoiseVarianceParams, Environment, Material, MeterParams, Params, SelectParams, Sphere, TemporalParams, TonemapParams
+from ._abi import Camera, CameraModel, Counters, DenoiseParams, DenoiseVarianceParams, Environment, Material, MeterParams, Params, SelectParams, Sphere, TemporalParams, TonemapParams
 
 # pt_denoise defaults (iterations, sigma_color, sigma_normal, sigma_position): chosen by the CPU sweep of DESIGN.md §10 f6;
 # host/pt_app.cpp uses the same values
@@ -360,6 +360,14 @@ class PathTracer:
         id as int32[H][W] (optional).  Asynchronous until sync()."""
         self._check(self._lib.pt_render_aux(self._ctx, C.byref(cam), C.byref(params), albedo_ptr, normal_ptr, position_ptr, id_ptr))
 
+    def render_aux_camera(self, cam, model, params, albedo_ptr, normal_ptr, position_ptr, id_ptr=None):
+        """render_aux() under a camera model (pt_render_aux_camera): the image is model.width x model.height, the ray of a pixel
+        the one camera_rays() writes for it with centre=True and no aperture; of params only cull_backfaces and tri_col are read.
+        The guides of a frame made by render_camera() / render_pixels(), for denoise(), denoise_variance() and
+        temporal_camera().  Asynchronous until sync()."""
+        self._check(self._lib.pt_render_aux_camera(self._ctx, C.byref(cam), C.byref(model), C.byref(params), albedo_ptr, normal_ptr,
+                                                   position_ptr, id_ptr))
+
     def denoise(self, color_ptr, albedo_ptr, normal_ptr, position_ptr, width, height, out_ptr, rgba_ptr=None,
                 iterations=DENOISE_DEFAULTS["iterations"], sigma_color=DENOISE_DEFAULTS["sigma_color"],
                 sigma_normal=DENOISE_DEFAULTS["sigma_normal"], sigma_position=DENOISE_DEFAULTS["sigma_position"]):
@@ -423,6 +431,23 @@ class PathTracer:
                                                   prev_moments_ptr, prev_length_ptr, prev_normal_ptr, prev_position_ptr, prev_id_ptr,
                                                   cur_moments_ptr, cur_normal_ptr, cur_position_ptr, cur_id_ptr, out_moments_ptr))
 
+    def temporal_camera(self, width, height, prev_cam, prev_model, prev_color_ptr, prev_length_ptr, prev_normal_ptr, prev_position_ptr,
+                        prev_id_ptr, cur_color_ptr, cur_normal_ptr, cur_position_ptr, cur_id_ptr, out_color_ptr, out_length_ptr,
+                        rgba_ptr=None, motion_ptr=None, prev_verts=None, cur_verts=None, n_tris=0,
+                        max_history=TEMPORAL_DEFAULTS["max_history"], plane_tolerance=TEMPORAL_DEFAULTS["plane_tolerance"],
+                        normal_threshold=TEMPORAL_DEFAULTS["normal_threshold"]):
+        """temporal() for a history rendered under a camera model (pt_temporal_camera): prev_cam and prev_model are the camera
+        and the CameraModel of the prev_* buffers (the guides of render_aux_camera()); the current camera is not needed.  With
+        prev_verts / cur_verts (and n_tris) it follows moved triangles as temporal_motion() does and needs both id pointers;
+        without them the ids are optional.  motion_ptr (optional, either way): float[H][W][2].  Asynchronous until sync()."""
+        pv, cv = (v.ptr if isinstance(v, DeviceBuffer) else v for v in (prev_verts, cur_verts))
+        tp = TemporalParams(int(width), int(height), float(max_history), float(plane_tolerance), float(normal_threshold), 0)
+        self._check(self._lib.pt_temporal_camera(self._ctx, C.byref(tp), C.byref(prev_cam) if prev_cam is not None else None,
+                                                 C.byref(prev_model) if prev_model is not None else None, pv, cv, int(n_tris),
+                                                 prev_color_ptr, prev_length_ptr, prev_normal_ptr, prev_position_ptr, prev_id_ptr,
+                                                 cur_color_ptr, cur_normal_ptr, cur_position_ptr, cur_id_ptr, out_color_ptr, out_length_ptr,
+                                                 rgba_ptr, motion_ptr))
+
     # ------------------------------------------------------------------ measurement
     def counters(self):
         c = Counters()
@@ -483,7 +508,8 @@ class PathTracer:
 
 class TemporalHistory:
     """The ping-pong buffers of a host's temporal accumulation: two history colours, two lengths, two sets of guide buffers and the
-    camera of the frame pushed last.  push() is one displayed frame of the loop: guides, reprojection, swap."""
+    camera (with its model, for a frame pushed with one) of the frame pushed last.  push() is one displayed frame of the loop: guides,
+    reprojection, swap."""
 
     def __init__(self, tracer, width, height, with_ids=True, with_moments=False):
         self.t, self.W, self.H = tracer, int(width), int(height)
@@ -495,16 +521,17 @@ class TemporalHistory:
         self.length = [tracer.malloc(n * 4) for _ in range(2)]
         self.guides = [[tracer.malloc(n * 16) for _ in range(3)] + [tracer.malloc(n * 4) if with_ids else None] for _ in range(2)]
         self.cam = None     # the camera of the history; None = nothing pushed yet
+        self.model = None   # ... and its CameraModel, when that frame was pushed with one
         self.cur = 0        # the set the NEXT push writes
 
     def reset(self):
         """Forget the history (a cut: the next push starts over)."""
-        self.cam = None
+        self.cam = self.model = None
 
     def _ptrs(self, k):
         return [b.ptr if b is not None else None for b in self.guides[k]]
 
-    def push(self, cam, params, color_ptr, rgba_ptr=None, moved=None, motion_ptr=None, moments_ptr=None, **temporal):
+    def push(self, cam, params, color_ptr, rgba_ptr=None, moved=None, motion_ptr=None, moments_ptr=None, model=None, **temporal):
         """One frame: render_aux for `cam` (params: the frame's pt_params), then temporal() of the frame in color_ptr (rendered
         with sample_index = 1; never written) against the stored history — or with no history the first time — then the swap.
         Returns (color_ptr, length_ptr, (albedo, normal, position, id) ptrs) of the new history; the colour and the guides can be
@@ -514,11 +541,33 @@ class TemporalHistory:
         the two vertex buffers: the previous one stays unchanged until the push that reads it has been issued.
         moments_ptr (a history made with_moments=True needs it, no other takes it): the frame's moments, as launch_kernel(moments_ptr=)
         kept them (never written); they are reprojected with the same history and the same lengths by temporal_moments(), and
-        self.moments is the new moment history, to go into denoise_variance() with the returned lengths."""
+        self.moments is the new moment history, to go into denoise_variance() with the returned lengths.
+        model (a CameraModel of this history's size; every push of one history with it, or none): the frame was rendered under
+        that camera model (render_camera, render_pixels), so its guides come from render_aux_camera() and the reprojection goes
+        through temporal_camera() with the model of the frame pushed before; motion_ptr then needs no moved=.  Not with
+        with_moments=True (there is no moments call for the camera models)."""
         if (moments_ptr is not None) != bool(self.moment):
             raise ValueError("TemporalHistory.push: moments_ptr goes with with_moments=True")
         k, o = self.cur, 1 - self.cur
         alb, nrm, pos, ids = self._ptrs(k)
+        if model is not None:
+            if self.moment:
+                raise ValueError("TemporalHistory.push: model= does not go with with_moments=True")
+            if (model.width, model.height) != (self.W, self.H):
+                raise ValueError("TemporalHistory.push: the model's image is not the history's")
+            if self.cam is not None and self.model is None:
+                raise ValueError("TemporalHistory.push: the history was pushed without a model (reset() first)")
+            self.t.render_aux_camera(cam, model, params, alb, nrm, pos, ids)
+            _, pn, pp, pi = self._ptrs(o)
+            prev = (None,) * 7 if self.cam is None else (self.cam, self.model, self.color[o].ptr, self.length[o].ptr, pn, pp, pi)
+            rows = dict(zip(("prev_verts", "cur_verts", "n_tris"), moved)) if moved is not None else {}
+            self.t.temporal_camera(self.W, self.H, *prev, color_ptr, nrm, pos, ids, self.color[k].ptr, self.length[k].ptr, rgba_ptr, motion_ptr,
+                                   **rows, **temporal)
+            self.cam, self.model = Camera.from_buffer_copy(cam), CameraModel.from_buffer_copy(model)
+            self.cur = o
+            return self.color[k].ptr, self.length[k].ptr, (alb, nrm, pos, ids)
+        if self.model is not None:
+            raise ValueError("TemporalHistory.push: the history was pushed with a model (reset() first)")
         self.t.render_aux(cam, params, alb, nrm, pos, ids)
         if self.cam is None:
             prev = (None,) * 6
@@ -544,7 +593,7 @@ class TemporalHistory:
     def free(self):
         for b in self.color + self.length + self.moment + [x for gset in self.guides for x in gset if x is not None]:
             b.free()
-        self.color, self.length, self.guides, self.cam = [], [], [], None
+        self.color, self.length, self.guides, self.cam, self.model = [], [], [], None, None
         self.moment, self.moments = [], None
 
 

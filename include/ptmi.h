@@ -611,9 +611,10 @@ int pt_render_rays(pt_ctx* ctx, const float* rays_dev, size_t n_rays, uint64_t f
  * range (lens_radius >= 0 and focus_dist > 0; ortho_height > 0; 0 < fisheye_fov <= 2 pi) — the parameters of other models are
  * ignored.  No scene, no scratch, no allocation, no synchronisation: asynchronous on the context's stream, hence ordered before the
  * pt_render_rays that follows.  With PT_OPT_TIMING=1, pt_last_kernel_ms covers it.
- * Left out: guide buffers for these cameras (pt_render_aux stays pinhole, so pt_denoise and pt_temporal do not serve them yet);
- * stereo pairs (a host calls twice); lens shapes other than a disk; RNG keys for pt_render_rays by pixel instead of
- * first_index + i (a listed subset renders with the keys of its row numbers); the generator fused into the path kernel. */
+ * Left out: guide buffers for these cameras in this call (pt_render_aux stays pinhole; pt_render_aux_camera below makes them and
+ * pt_temporal_camera carries them across frames); stereo pairs (a host calls twice); lens shapes other than
+ * a disk; RNG keys for pt_render_rays by pixel instead of first_index + i (a listed subset renders with the keys of its row
+ * numbers); the generator fused into the path kernel. */
 enum { PT_CAM_PINHOLE = 0, PT_CAM_THIN_LENS = 1, PT_CAM_ORTHO = 2, PT_CAM_FISHEYE = 3, PT_CAM_EQUIRECT = 4 };
 enum { PT_CAMF_CENTRE = 1 };           /* no sub-pixel jitter: jx = jy = 0 (guides, picking, tests) */
 #define PT_CAM_LENS_KEY 0xC3A5C85C97CB3127ull   /* frame ^ this keys the lens stream; the top bit is set, so no frame number a host counts up to meets its own lens stream */
@@ -664,7 +665,7 @@ int pt_camera_rays(pt_ctx* ctx, const pt_camera* cam, const pt_camera_model* cm,
  * table are neither read nor changed.  The kernel is pt_render_rays' loop with another path start (csrc/pt_rays_loop.h); the model
  * is a value of the launch, not an instantiation.
  * Left out: luminance moments in this call (pt_render_pixels below keeps them, for these cameras too); display words; guide buffers
- * for these cameras; the stage-split pipeline. */
+ * for these cameras in this call (pt_render_aux_camera below makes them); the stage-split pipeline. */
 int pt_render_camera(pt_ctx* ctx, const pt_camera* cam, const pt_camera_model* cm,
                      const uint32_t* pixels_dev /* may be NULL */, size_t n, uint64_t first_pixel,
                      float* radiance_dev /* float[n][3] */, const pt_params* params, uint32_t spp, int mode);
@@ -1078,6 +1079,71 @@ int pt_temporal_moments(pt_ctx* ctx, const pt_temporal_params* tp, const pt_came
                         const float* cur_moments_dev,
                         const float* cur_normal_dev, const float* cur_position_dev, const int32_t* cur_id_dev,
                         float* out_moments_dev);
+
+/* ---- guide buffers and reprojection for the camera models — an EXTENSION ----------------------------
+ * The two calls that carry pt_render_camera's and pt_render_pixels' frames through the image stages: guides under a camera model
+ * (for pt_denoise, pt_denoise_variance and the reprojection) and the reprojection into a previous frame of a camera model.  The
+ * filters read guides and never a camera, so they serve all five models as they are.
+ *
+ * pt_render_aux_camera: pt_render_aux under a camera model.  The image is cm's, W x H = cm->width x cm->height (as
+ * pt_render_camera reads pt_params); of params only cull_backfaces and tri_col are read.  The four outputs have pt_render_aux's
+ * layouts and meanings, a miss is all zero with id -1.
+ *   The ray of pixel pix = y * W + x is, bit for bit, the row pt_camera_rays writes for pix under PT_CAMF_CENTRE with lens_radius
+ *   taken as 0: no jitter, no lens draw, no random number read.  For PT_CAM_THIN_LENS that is the ray through the lens centre — the
+ *   surface that is sharp in the rendered frame.  cm->flags is checked for unknown bits and otherwise ignored, cm->lens_radius is
+ *   range-checked and otherwise ignored.  With PT_CAM_PINHOLE the four buffers are pt_render_aux's bit for bit.
+ *   The hit is pt_render_aux's: the binary closest-hit walk, then the spheres, the material row or tri_col.  A pixel without a ray
+ *   (d == (0, 0, 0): outside the fisheye's image circle) is not walked and writes a miss.
+ * Errors, in this order, nothing written on any of them: NULL ctx PT_ERR_INVALID; a NULL cam, cm, params or float buffer
+ * PT_ERR_INVALID; pt_camera_rays' checks of cm for the whole image (n = W * H, first_pixel 0) in its order and wording, prefixed
+ * pt_render_aux_camera:; no BVH PT_ERR_NO_SCENE; Woop records PT_ERR_UNSUPPORTED.  Asynchronous on the context's stream, ordered
+ * after pt_refit_bvh; no scratch, no allocation, no synchronisation; with PT_OPT_TIMING=1, pt_last_kernel_ms covers it. */
+int pt_render_aux_camera(pt_ctx* ctx, const pt_camera* cam, const pt_camera_model* cm, const pt_params* params,
+                         float* albedo_dev, float* normal_dev, float* position_dev, int32_t* id_dev /* may be NULL */);
+
+/* pt_temporal_camera: pt_temporal / pt_temporal_motion with the history seen through a camera MODEL: prev_cam and prev_cm are the
+ * camera and the model the prev_* guides and colours were rendered under (pt_render_aux_camera, pt_render_camera).  The current
+ * camera is not an argument: the current guides hold world positions.  Everything not named here — the buffers,
+ * pt_temporal_params, steps 1 and 3 to 5, the blend, rgba_dev, the aliasing rules, prev_color_dev == NULL, asynchrony,
+ * PT_OPT_TIMING — is pt_temporal's or pt_temporal_motion's, word for word.
+ * Where the point was, (x', n').  With a non-NULL vertex pointer: pt_temporal_motion's step 2 and its requirements (both id
+ * pointers, no NULL vertex pointer while n_tris > 0, n_tris < 2^31).  With both vertex pointers NULL: x' = x_p and n' = n_p for
+ * every pixel, no row is read, n_tris is ignored, and the ids are given for both frames or for neither (pt_temporal's rule).
+ * motion_dev (may be NULL, in either mode): (fx - x, fy - y), or (0, 0) where the projection rejects, as pt_temporal_motion
+ * defines it; it may not be one of the other buffers.
+ * The projection replaces step 2 of pt_temporal and is chosen by prev_cm->model.  v = x' - prev_cam.pos; a = vdot(v, front),
+ * b = vdot(v, right), c = vdot(v, up); cx = (float)W / 2.0f - 0.5f, cy = (float)H / 2.0f - 0.5f.  binary32 throughout, the only
+ * fused operations are the ones written; constants marked "host" are computed once on the host in binary32, one rounding per
+ * operation.
+ *   PT_CAM_PINHOLE, PT_CAM_THIN_LENS   pt_temporal's step 2, unchanged: both models' guide rays pass through pos along dir0.  With
+ *                     these two the call is pt_temporal (no rows, no motion_dev) or pt_temporal_motion (rows) bit for bit.
+ *   PT_CAM_ORTHO      rejected unless a > 0.  kx = (float)W / (ortho_height * aspect), ky = (float)H / ortho_height (host);
+ *                     fx = fmaf(b, kx, cx), fy = fmaf(c, ky, cy).
+ *   PT_CAM_FISHEYE    s = sqrtf(fmaf(c, c, b * b)); rejected when a == 0 and s == 0.  theta = atan2f(s, a), half = fisheye_fov /
+ *                     2.0f (host); rejected when theta > half.  kf = ((float)min(W, H) / 2.0f) / half (host); rho = theta * kf;
+ *                     k = s > 0 ? rho / s : 0; fx = fmaf(b, k, cx), fy = fmaf(c, k, cy).  There is no a > 0 test: a fisheye
+ *                     wider than 180 degrees sees behind itself.
+ *   PT_CAM_EQUIRECT   h = sqrtf(fmaf(b, b, a * a)); rejected when h == 0 and c == 0.  lon = atan2f(b, a), lat = atan2f(c, h);
+ *                     fx = fmaf(lon, (float)W / 6.28318548f, (float)W / 2.0f), fy = fmaf(lat, (float)H / 3.14159274f,
+ *                     (float)H / 2.0f), both factors host: the inverse of pt_camera_rays' model, an integer coordinate is a
+ *                     texel centre.
+ * In every model the history is rejected when fx or fy is not finite (atan2f is the device library's: the coordinates of the
+ * three models with an angle are not pinned bit for bit, tests/test_gpu_camera_guides.py holds them to 1e-3 pixel).
+ * PT_ERR_INVALID: everything pt_temporal refuses, in its order; then, with a history and right behind the NULL prev_* pointers:
+ * a NULL prev_cm; pt_camera_rays' checks of prev_cm for the whole image, prefixed pt_temporal_camera:; prev_cm->width or height
+ * other than the parameters'; then the ids, the aliasing, and with rows pt_temporal_motion's checks; motion_dev equal to another
+ * buffer.  Without a history prev_cam and prev_cm are ignored.
+ * Left out: horizontal wrap of the equirectangular taps at the +-180 degree seam (a footprint that straddles it uses its
+ * in-image taps); a moments variant (a host passes the moments as the first two channels of a three-channel buffer, see
+ * pt_temporal_moments); `pt_app --camera` with --denoise-out, --temporal-out or the motion options (still refused). */
+int pt_temporal_camera(pt_ctx* ctx, const pt_temporal_params* tp, const pt_camera* prev_cam, const pt_camera_model* prev_cm,
+                       const float* prev_verts_dev, const float* cur_verts_dev, size_t n_tris,
+                       const float* prev_color_dev, const float* prev_length_dev,
+                       const float* prev_normal_dev, const float* prev_position_dev, const int32_t* prev_id_dev,
+                       const float* cur_color_dev,
+                       const float* cur_normal_dev, const float* cur_position_dev, const int32_t* cur_id_dev,
+                       float* out_color_dev, float* out_length_dev, uint32_t* rgba_dev,
+                       float* motion_dev /* float[h][w][2], may be NULL */);
 
 /* ---- display: exposure metering and tone mapping, an EXTENSION ---------------------------------
  * The last stage of a frame: any float[H][W][3] buffer (an accumulator, PT_RAYS_HDR or clamped; a denoiser's or the temporal
